@@ -9,7 +9,7 @@ c4_dmel_twoset` (configs[3], rounds 1-3's line), `c2_bact_twoset` (configs[1]), 
 
 One "step" = the whole job on one batch of reads: 2-bit pack (K0) of both sets, minimizer index build over the targets,
 sketch + seed + chain of every query, distinct-target counts, per-read estimates, median (twoset.rs:587-606 from "reads in
-memory" on).  TWO clocks, both measured in every run:
+memory" on).  TWO clocks (a plain run times the one `value` is quoted on; --full measures the other one too):
   * `value` / `ms_per_step` -- SURVEY.md 8(d)'s clock: the ASCII reads are FASTA-parsed reads in (pinned) HOST memory when the
     clock starts; host-side 2-bit pack, the PCIe transfer (targets first, the queries travel while the target index is built)
     and everything behind them are inside.  This is the figure VERDICT r03 credits, and the smaller of the two.
@@ -45,10 +45,19 @@ def parse():
     ap.add_argument("--clock", default="host", choices=["host", "resident"],
                     help="which clock `value` is quoted on: host = SURVEY 8(d): ASCII reads in pinned host memory when the clock "
                          "starts (default); resident = ASCII reads already in HBM (rounds 1-3).  The other one is measured too "
-                         "(`resident` / `from_host` on the line) unless --no-from-host / --no-resident")
+                         "(`resident` / `from_host` on the line) with --full, unless --no-from-host / --no-resident")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the other clock (`resident` / `from_host`), one "
+                         "instrumented step behind the timed region (small jobs), the CPU baseline and the parity sample against the "
+                         "oracle.  Off by default: a plain run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32 / "
+                         "float64): counts (overlapping targets per query read), has_mapping (one GPU), estimates (per-read genome size "
+                         "estimates), median ([q15, median, q65], NaN where undefined)")
     ap.add_argument("--no-resident", action="store_true")
     ap.add_argument("--parity-sample", type=int, default=256, help="query reads whose FORWARD counts the CPU oracle recomputes at full "
-                                                                   "H. sapiens scale (restricted index: oracle/c5_sample.py); 0 = skip")
+                                                                   "H. sapiens scale (restricted index: oracle/c5_sample.py); 0 = skip "
+                                                                   "(--full only)")
     ap.add_argument("--preset", default=None, choices=["ont", "pb"], help="minimap2 preset (default: by the configuration's platform: pb for the HiFi sets, ont otherwise)")
     ap.add_argument("--inverse", action="store_true", help="--use-min-ref: index the queries, stream the targets")
     ap.add_argument("--scale", type=float, default=1.0, help="shrink the config (debug only; invalid as a result)")
@@ -56,9 +65,9 @@ def parse():
                     help="pcg: lrge_amd.synth (sequential numpy generator, host); cb: lrge_amd.synth_cb (counter-based, reads written "
                          "straight into HBM by the device twin -- what makes c5_human_twoset, 31.5 Gbases, a bench workload); "
                          "auto = cb for c5_human_twoset, pcg otherwise")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--no-from-host", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0)
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="(--full) time budget of the CPU baseline's sample")
     ap.add_argument("--emulate-world", type=int, default=0, metavar="N",
                     help="projection on ONE GPU of an N-rank strong-scaling run of the forward strategy with the target sketch sharded: "
                          "all N ranks run for real as threads of this process (one context each, the library's local communicator), "
@@ -74,8 +83,29 @@ def parse():
 
 from benchlib import (cpu_baseline, cpu_baseline_sampled, roofline_blocks, emulate_world)  # noqa: E402
 
+DUMP_MAX_READS = 1 << 21        # per-read arrays above this many reads are dumped as a fixed, seeded sample (<= 64 MB in all)
+
+
+def dump_outputs(out_dir, counts, has, estimates, med):
+    """What a caller of the timed path receives from its last step, as float32 / float64 .npy files: counts (exact in float64),
+    has_mapping (None: not written), the per-read estimates and [q15, median, q65] (NaN where the median is undefined).  A job with
+    more query reads than DUMP_MAX_READS writes the same seeded sample of every per-read array and its indices (read_index)."""
+    os.makedirs(out_dir, exist_ok=True)
+    per_read = {"counts": np.asarray(counts).astype(np.float64), "estimates": np.asarray(estimates).astype(np.float32)}
+    if has is not None:
+        per_read["has_mapping"] = np.asarray(has).astype(np.float32)
+    n = per_read["counts"].size
+    if n > DUMP_MAX_READS:
+        idx = np.sort(np.random.default_rng(20261016).choice(n, DUMP_MAX_READS, replace=False))
+        per_read = {k: v[idx] for k, v in per_read.items()}
+        per_read["read_index"] = idx.astype(np.float64)
+    per_read["median"] = np.array([np.nan if x is None else float(x) for x in med], dtype=np.float64)
+    for name, arr in per_read.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
 
 def main():
+    t_start = time.perf_counter()
     a = parse()
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -263,6 +293,7 @@ def main():
                     S.host = (lambda sub=sub: sub.bases)
             self.qs_lens = q_lens[q_rng[0]:q_rng[1]]
             self.shard_stats = None
+            self.last_has = None        # has_mapping of the last forward step (what --dump-outputs writes beside the counts)
 
         def load_resident(self):
             """(counter-based generator) the ASCII reads of this rank written into HBM by the device twin"""
@@ -341,6 +372,7 @@ def main():
                 _t1 = time.perf_counter()
                 _b1 = _busy() if _tr else 0.0
                 counts, has = ix.overlap_twoset(Qd)
+                self.last_has = has
                 _t2 = time.perf_counter()
                 _b2 = _busy() if _tr else 0.0
                 tm = ctx.timings(); cn = ctx.counters(); st = ix.stats()
@@ -382,7 +414,10 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    t_steps = [0.0]       # wall seconds in warm-up + timed steps (stderr: what a run spends outside them)
+
     def timed(src_q, src_t, warmup, steps):
+        t_w = time.perf_counter()
         for _ in range(warmup):
             step(src_q, src_t)
         sync_all()
@@ -396,11 +431,13 @@ def main():
             for k, v in cn.items(): acc_cn[k] = v if k in ("lpg_split", "index_parts") else acc_cn.get(k, 0) + v
         sync_all()
         elapsed = time.perf_counter() - t0
+        last_has = job.last_has
+        t_steps[0] += time.perf_counter() - t_w
         if use_dist:
             tt = torch.tensor([elapsed], dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             elapsed = float(tt.item())
-        return elapsed, acc_tb, acc_tm, acc_cn, last
+        return elapsed, acc_tb, acc_tm, acc_cn, last, last_has
 
     # big jobs (launches of milliseconds): an event pair around every k_rs_scatter launch costs nothing there, so the TIMED steps
     # carry them; small jobs time that kernel in one instrumented step behind the timed region (timer level 2 is host work
@@ -413,8 +450,8 @@ def main():
     # made from the resident reads first (untimed); with the counter-based generator the resident copies then make room for
     # the staging blocks of the uploads and are written again by the device twin before the resident clock runs.
     clock_host = a.clock == "host" and not emu
-    want_host = clock_host or (not a.no_from_host and not emu)
-    want_res = (not clock_host) or not a.no_resident
+    want_host = clock_host or (a.full and not a.no_from_host and not emu)
+    want_res = (not clock_host) or (a.full and not a.no_resident)
     res_host = res_res = None
     k_other = a.steps if a.config != "c5_human_twoset" else max(2, a.steps // 3)    # steps of the clock that is not `value`
     hq = ht = None
@@ -427,7 +464,10 @@ def main():
 
     if want_host:
         hq = ctx.host_alloc(max(qs.nbytes, 1)); ht = ctx.host_alloc(max(ts.nbytes, 1))
-        hq.array[:qs.nbytes] = qs.host(); ht.array[:ts.nbytes] = ts.host()
+        if gen == "cb":     # device -> pinned in one copy each (no pageable staging array of the 31.5 GB)
+            qs.dev.to_host(out=hq.array); ts.dev.to_host(out=ht.array)
+        else:
+            hq.array[:qs.nbytes] = qs.host(); ht.array[:ts.nbytes] = ts.host()
     if clock_host:
         if gen == "cb":
             qs.dev.free(); ts.dev.free()
@@ -446,12 +486,14 @@ def main():
             if gen == "cb":
                 job.load_resident()
     main_res = res_host if clock_host else res_res
-    elapsed, acc_tb, acc_tm, acc_cn, last = main_res
+    elapsed, acc_tb, acc_tm, acc_cn, last, last_has = main_res
     counts, est_all, med, _, _, _, st = last
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, counts, last_has if world == 1 else None, est_all, med)
     # one instrumented step AFTER the timed regions: an event pair around every k_rs_scatter launch (timer level 2 costs
     # host work between launches, so the timed steps run at the default level)
     tb2 = tm2 = cn2 = {}
-    if not lvl2_all:
+    if not lvl2_all and a.full:
         ctx.set_timer_level(2)
         if clock_host and not want_res:
             _, _, _, tb2, tm2, cn2, _ = step(hq, ht)
@@ -462,7 +504,7 @@ def main():
     def clock_block(res, steps, what):
         if res is None:
             return None
-        e_, _, tm_, _, last_ = res
+        e_, _, tm_, _, last_, _ = res
         return {"ms_per_step": e_ * 1e3 / steps, "value": Qn * steps / e_, "unit": "reads/s", "steps": steps, "what": what,
                 "counts_equal_other_clock": bool(np.array_equal(last_[0], counts))}
     what_host = ("ASCII reads in pinned host memory when the clock starts (SURVEY 8d): %.2f GB handed over per step; host-side 2-bit "
@@ -540,7 +582,7 @@ def main():
                                   **{k: v / K for k, v in acc_tm.items() if v}},
             "work_per_step": {k: (v if k in ("lpg_split", "index_parts") else v / K) for k, v in acc_cn.items()},
         }
-        if world == 1 and not a.no_cpu_baseline and not a.inverse:   # (the CPU leg times the forward strategy)
+        if a.full and world == 1 and not a.no_cpu_baseline and not a.inverse:   # (the CPU leg times the forward strategy)
             if gen == "cb" and Tn > 400000:
                 cb = cpu_baseline_sampled(spec, Qn, Tn, a.cpu_seconds, preset)
                 out["cpu_baseline"] = cb
@@ -602,6 +644,8 @@ def main():
                 n = len(ccounts)
                 out["parity_vs_oracle_sample"] = {"reads": n, "counts_equal": bool(np.array_equal(ccounts, counts[:n])),
                                                   "mid_occ_equal": bool(cmid == st["mid_occ"])}
+        sys.stderr.write("[bench] %.1f s from start to the result line, %.1f s of them in warm-up + timed steps\n"
+                         % (time.perf_counter() - t_start, t_steps[0]))
         print(json.dumps(out))
     if comm is not None:
         comm.close()

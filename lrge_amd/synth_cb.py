@@ -175,11 +175,13 @@ class DeviceReads:
         """Names are r%08d of the read index: lexicographic order = numeric order, so the index itself is the rank."""
         return np.arange(self.first, self.first + self.n, dtype=np.uint32)
 
-    def to_host(self, lo=0, hi=None):
-        """ASCII of reads [lo, hi) copied back (tests)."""
+    def to_host(self, lo=0, hi=None, out=None):
+        """ASCII of reads [lo, hi) copied back (tests); `out`: a contiguous uint8 array to copy into (e.g. pinned memory)."""
         hi = self.n if hi is None else hi
         b0, b1 = int(self.offsets[lo]), int(self.offsets[hi])
-        out = np.empty(b1 - b0, np.uint8)
+        if out is None:
+            out = np.empty(b1 - b0, np.uint8)
+        assert out.dtype == np.uint8 and out.flags.c_contiguous and out.size >= b1 - b0
         rc = _hip().cb_hip_to_host(self.device, _vp(out), C.c_void_p(self.ptr + b0), C.c_uint64(b1 - b0))
         if rc:
             raise RuntimeError("cb_hip_to_host: HIP error %d" % rc)

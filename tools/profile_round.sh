@@ -1,9 +1,9 @@
 #!/bin/bash
 # Collect the rocprofv3 evidence bench.py's roofline block refers to (run on the GPU box via gpurun):
 #   tools/profile_round.sh <tag> [bench args]   -> gpurun_out/<tag>_{stats,sq,fetch,write}/ + gpurun_out/<tag>_bench.json
-# Counter passes are separate runs with --kernel-trace only (TCC counters do not fit beside SQ ones; gpurun refuses
-# --pmc together with other trace domains).  The plain run is the full default bench (both clocks, CPU leg, parity sample);
-# the profiled runs time the `value` clock only (--no-resident) and skip the CPU legs.
+# Counter passes are separate runs with --kernel-trace only (TCC counters do not fit beside SQ ones, and --pmc is never
+# combined with other trace domains).  The first run is the bench with --full (both clocks, CPU leg, parity sample);
+# the profiled runs time the `value` clock only and skip the CPU legs.
 set -u
 tag=${1:-prof}
 shift || true
@@ -13,7 +13,7 @@ mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
 B="python $root/bench.py --no-cpu-baseline --no-resident --parity-sample 0 $*"
 if [ -z "${SKIP_PLAIN:-}" ]; then
-  timeout 1200 python $root/bench.py "$@" > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.err"
+  timeout 1200 python $root/bench.py --full "$@" > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.err"
 fi
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/${tag}_stats" -o s -- $B --steps 3 --warmup 1 > "$out/${tag}_stats.json" 2> "$out/${tag}_stats.err"
 timeout 900 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM SQ_INSTS_LDS SQ_ACTIVE_INST_VALU \
