@@ -353,6 +353,22 @@ int  lrge_hip_seqset_presketch_sharded(lrge_hip_ctx *ctx, lrge_hip_seqset *s, in
 int  lrge_hip_read_records(const char *path, void (*cb)(void *user, const char *name, uint64_t name_len, const char *bases, uint64_t n_bases),
                            void *user, char *errbuf, uint64_t errcap);
 
+/* BGZF input decompressed on the device (k_inflate: one wavefront per block, CRC32 and ISIZE checked there).
+   lrge_hip_bgzf_scan, host only: LRGE_OK when every gzip member of comp[0, comp_len) is a BGZF block (FEXTRA with a `BC`
+   subfield, ISIZE <= 65536) and the blocks tile the buffer exactly; *n_blocks and *out_len (either may be NULL) receive the
+   block count and the decompressed size.  Anything else (plain or multi-member gzip without BC, trailing bytes): LRGE_ERR_PARSE.
+   lrge_hip_bgzf_inflate: every block into out[0, *out_len of the scan) (caller-owned, out_len at least that); a bad block is
+   LRGE_ERR_PARSE and the message names its file offset; no host fallback.  Chunks of at most option INFLATE_CHUNK_BYTES
+   (compressed + decompressed, default 256 MiB) are staged through pinned buffers, so device memory stays bounded.
+   lrge_hip_read_records_gpu: the records, order and errors of lrge_hip_read_records; BGZF input is decompressed on the device,
+   every other input -- and a file with a block the device rejects -- by the unchanged host path (its messages, through
+   lrge_hip_last_error(ctx)).  *used_device (may be NULL): 1 if the device produced the bytes.  LRGE_ERR_DEVICE: a runtime failure. */
+int  lrge_hip_bgzf_scan(const void *comp, uint64_t comp_len, uint64_t *n_blocks, uint64_t *out_len);
+int  lrge_hip_bgzf_inflate(lrge_hip_ctx *ctx, const void *comp, uint64_t comp_len, void *out, uint64_t out_len);
+int  lrge_hip_read_records_gpu(lrge_hip_ctx *ctx, const char *path,
+                               void (*cb)(void *user, const char *name, uint64_t name_len, const char *bases, uint64_t n_bases),
+                               void *user, int *used_device);
+
 /* Host only: which side packs the reads of a set that starts in host memory when `ranks_on_host` ranks share this host's CPUs (option
    LRGE_HIP_RANKS_ON_HOST, set by the launcher; LRGE_HIP_PACK = host | device overrides): 1 = the host (2-bit pack with AVX2, packed words
    over PCIe), 0 = the device (ASCII over the rank's own PCIe link, k_pack).  *granted_cpus (may be NULL) receives the CPUs the host

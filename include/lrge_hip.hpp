@@ -10,6 +10,8 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <functional>
+#include <memory>
 #include <numeric>
 #include <optional>
 #include <stdexcept>
@@ -105,6 +107,22 @@ inline std::vector<std::vector<uint32_t>> name_ranks(const std::vector<std::vect
 // lib.rs:189-204: StdRng::seed_from_u64 + rand::seq::index::sample, restated in lrge_rand.hpp
 using ::lrge::unique_random_set;
 }  // namespace detail
+
+// BGZF input decompressed on the device (lrge_hip_bgzf_inflate), as the inflater hook of io::iter_records(path, cb, hook)
+// in lrge_io.hpp: false (the host path decompresses) for input that is not BGZF or holds a block the device rejects; a
+// device failure throws.  The hook owns a context on `device` for as long as it lives.
+inline std::function<bool(const std::string &, std::string &)> bgzf_inflater(int device) {
+    auto ctx = std::make_shared<detail::Ctx>(device);
+    return [ctx](const std::string &raw, std::string &out) -> bool {
+        uint64_t total = 0;
+        if (lrge_hip_bgzf_scan(raw.data(), raw.size(), nullptr, &total) != LRGE_OK) return false;
+        out.resize((size_t)total);
+        const int rc = lrge_hip_bgzf_inflate(ctx->h, raw.data(), raw.size(), &out[0], total);
+        if (rc == LRGE_ERR_PARSE) { out.clear(); return false; }
+        ctx->check(rc);
+        return true;
+    };
+}
 
 inline std::vector<std::string> paf_lines(lrge_hip_ctx *ctx, const lrge_hip_index *ix, const lrge_hip_seqset *qs, int dual,
                                           const std::vector<const std::string *> &qn, const std::vector<uint32_t> &qlen,

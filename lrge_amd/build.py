@@ -39,6 +39,19 @@ def build_lib(force=False, verbose=False):
     return LIB_PATH
 
 
+TWIN_PATH = os.path.join(LIB_DIR, "liblrge_inflate_twin.so")
+
+
+def build_twin(force=False):
+    """The host twin of k_inflate (csrc/inflate_twin.cpp, g++): the same bit-level core, for the CPU suite."""
+    os.makedirs(LIB_DIR, exist_ok=True)
+    srcs = [os.path.join(CSRC, f) for f in ("inflate_twin.cpp", "inflate_core.h", "bgzf_scan.h")]
+    if not force and os.path.exists(TWIN_PATH) and os.path.getmtime(TWIN_PATH) >= _newest(srcs):
+        return TWIN_PATH
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-fPIC", "-shared", "-o", TWIN_PATH, srcs[0]])
+    return TWIN_PATH
+
+
 CLI_PATH = os.path.join(LIB_DIR, "lrge-hip")
 
 

@@ -25,6 +25,8 @@
 #include "k_restrict.h"
 #include "k_route.h"
 #include "k_tshard.h"
+#include "k_inflate.h"
+#include "bgzf_scan.h"
 #include "../../include/lrge_rand.hpp"
 #include "../../include/lrge_io.hpp"
 
@@ -219,3 +221,4 @@ extern "C" int lrge_hip_last_counters(const lrge_hip_ctx *ctx, uint64_t c[LRGE_C
 #include "host_overlap_api.inl"
 #include "host_comm.inl"
 #include "host_estimate.inl"
+#include "host_inflate.inl"

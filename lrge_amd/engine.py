@@ -63,6 +63,18 @@ class Context:
         read once from the environment (LRGE_HIP_<NAME>) when the context is created, except DEBUG_*."""
         self._check(self._lib.lrge_hip_ctx_set_option(self.h, name.encode(), None if value is None else str(value).encode()))
 
+    def bgzf_inflate(self, data):
+        """A BGZF buffer decompressed on the device (lrge_hip_bgzf_inflate); bytes in, bytes out.  Input that is not BGZF,
+        or a damaged block, raises LrgeHipError with code ERR_PARSE."""
+        data = bytes(data)
+        n, total = C.c_uint64(), C.c_uint64()
+        rc = self._lib.lrge_hip_bgzf_scan(data, len(data), C.byref(n), C.byref(total))
+        if rc != 0:
+            raise LrgeHipError(rc, self._lib.lrge_hip_last_error(None).decode())
+        out = C.create_string_buffer(max(1, total.value))
+        self._check(self._lib.lrge_hip_bgzf_inflate(self.h, data, len(data), out, total.value))
+        return out.raw[:total.value]
+
     def set_timer_level(self, level):
         """0 = call total + chain stage only, 1 = every stage, 2 (default) = also every k_rs_scatter launch."""
         self._check(self._lib.lrge_hip_set_timer_level(self.h, int(level)))
