@@ -369,6 +369,34 @@ int  lrge_hip_read_records_gpu(lrge_hip_ctx *ctx, const char *path,
                                void (*cb)(void *user, const char *name, uint64_t name_len, const char *bases, uint64_t n_bases),
                                void *user, int *used_device);
 
+/* Plain and multi-member gzip decompressed on the device (speculative parallel inflate, DESIGN section 11: k_gz_find,
+   k_gz_decode, k_gz_window, k_gz_resolve).  lrge_hip_gzip_inflate accepts any gzip buffer, BGZF included, and delivers the
+   decompressed bytes in order through `sink` (a nonzero return stops the call with LRGE_ERR_IO).  On a non-OK return the bytes
+   delivered so far are void.  Every member's CRC32 and ISIZE are checked, and the buffer must end exactly after the last
+   member's trailer.  LRGE_ERR_PARSE: damaged or trailing data (the message names a file offset); LRGE_ERR_TOO_MANY: a chunk
+   decodes to more than its slot holds even after one retry with 4x (option GZIP_SLOT_RATIO), callers take the host path;
+   LRGE_ERR_DEVICE: a runtime failure.  Options GZIP_CHUNK_BYTES (default 512 KiB) and GZIP_ROUND_BYTES (default 256 MiB)
+   set the nominal chunk and the compressed bytes per round.  *stats (may be NULL) receives the counts of the call.
+   lrge_hip_read_records_gpu_ex: lrge_hip_read_records_gpu with a choice of device paths.  LRGE_GPU_INFLATE_BGZF reproduces
+   lrge_hip_read_records_gpu; | LRGE_GPU_INFLATE_GZIP also sends every other gzip input to lrge_hip_gzip_inflate (BGZF keeps
+   k_inflate).  Anything the device cannot prove falls back to the unchanged host path and its messages. */
+typedef struct lrge_hip_gzip_stats {
+    uint64_t members;            /* gzip members whose CRC32 and ISIZE were checked */
+    uint64_t chunks;             /* nominal chunks over all rounds */
+    uint64_t speculative_starts; /* chunks decoded from a finder candidate (not a round's first) */
+    uint64_t rejected_starts;    /* candidates the chain walk rejected */
+    uint64_t redecoded_chunks;   /* chunks decoded again from their predecessor's true end */
+    uint64_t overflow_retries;   /* chunks decoded again with a 4x slot */
+    uint64_t bytes_out;          /* decompressed bytes */
+} lrge_hip_gzip_stats;
+#define LRGE_GPU_INFLATE_BGZF 1
+#define LRGE_GPU_INFLATE_GZIP 2
+int  lrge_hip_gzip_inflate(lrge_hip_ctx *ctx, const void *comp, uint64_t comp_len, int (*sink)(void *user, const void *bytes, uint64_t n),
+                           void *user, lrge_hip_gzip_stats *stats);
+int  lrge_hip_read_records_gpu_ex(lrge_hip_ctx *ctx, const char *path, int flags,
+                                  void (*cb)(void *user, const char *name, uint64_t name_len, const char *bases, uint64_t n_bases),
+                                  void *user, int *used_device);
+
 /* Host only: which side packs the reads of a set that starts in host memory when `ranks_on_host` ranks share this host's CPUs (option
    LRGE_HIP_RANKS_ON_HOST, set by the launcher; LRGE_HIP_PACK = host | device overrides): 1 = the host (2-bit pack with AVX2, packed words
    over PCIe), 0 = the device (ASCII over the rank's own PCIe link, k_pack).  *granted_cpus (may be NULL) receives the CPUs the host

@@ -111,14 +111,36 @@ using ::lrge::unique_random_set;
 // BGZF input decompressed on the device (lrge_hip_bgzf_inflate), as the inflater hook of io::iter_records(path, cb, hook)
 // in lrge_io.hpp: false (the host path decompresses) for input that is not BGZF or holds a block the device rejects; a
 // device failure throws.  The hook owns a context on `device` for as long as it lives.
+namespace detail {
+inline bool bgzf_inflate_with(Ctx &ctx, const std::string &raw, std::string &out) {
+    uint64_t total = 0;
+    if (lrge_hip_bgzf_scan(raw.data(), raw.size(), nullptr, &total) != LRGE_OK) return false;
+    out.resize((size_t)total);
+    const int rc = lrge_hip_bgzf_inflate(ctx.h, raw.data(), raw.size(), &out[0], total);
+    if (rc == LRGE_ERR_PARSE) { out.clear(); return false; }
+    ctx.check(rc);
+    return true;
+}
+}  // namespace detail
+
 inline std::function<bool(const std::string &, std::string &)> bgzf_inflater(int device) {
     auto ctx = std::make_shared<detail::Ctx>(device);
+    return [ctx](const std::string &raw, std::string &out) -> bool { return detail::bgzf_inflate_with(*ctx, raw, out); };
+}
+
+// Every gzip input decompressed on the device: BGZF by k_inflate (as bgzf_inflater), any other gzip by the speculative
+// decode (lrge_hip_gzip_inflate).  False (the host path decompresses, with its messages) for input the device cannot prove:
+// damaged data, trailing bytes, a chunk beyond its slot; a device failure throws.
+inline std::function<bool(const std::string &, std::string &)> gzip_inflater(int device) {
+    auto ctx = std::make_shared<detail::Ctx>(device);            // one context for both device paths
     return [ctx](const std::string &raw, std::string &out) -> bool {
-        uint64_t total = 0;
-        if (lrge_hip_bgzf_scan(raw.data(), raw.size(), nullptr, &total) != LRGE_OK) return false;
-        out.resize((size_t)total);
-        const int rc = lrge_hip_bgzf_inflate(ctx->h, raw.data(), raw.size(), &out[0], total);
-        if (rc == LRGE_ERR_PARSE) { out.clear(); return false; }
+        if (lrge_hip_bgzf_scan(raw.data(), raw.size(), nullptr, nullptr) == LRGE_OK) return detail::bgzf_inflate_with(*ctx, raw, out);
+        out.clear();
+        const int rc = lrge_hip_gzip_inflate(ctx->h, raw.data(), raw.size(), [](void *u, const void *b, uint64_t n) {
+            static_cast<std::string *>(u)->append(static_cast<const char *>(b), (size_t)n);
+            return 0;
+        }, &out, nullptr);
+        if (rc == LRGE_ERR_PARSE || rc == LRGE_ERR_TOO_MANY) { out.clear(); return false; }
         ctx->check(rc);
         return true;
     };

@@ -18,11 +18,15 @@ C_NAMES = ["query_bases", "query_minimizers", "anchors", "groups", "groups_chain
            "chain_anchors", "chain_glb_launches", "chain_glb_anchors", "lpg_launches", "lpg_anchors",
            "rs_scatter_launches", "rs_scatter_items", "rs_scatter_bytes", "lpg_split", "lookup_launches", "table_disp_sum", "anchors_kept", "index_parts", "sketch_launches", "sketch_wave_launches"]
 
+# int (*sink)(void *user, const void *bytes, uint64_t n) of lrge_hip_gzip_inflate
+GZIP_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)
+
 EXPORTS = [
     "lrge_hip_device_count", "lrge_hip_ctx_create", "lrge_hip_ctx_destroy", "lrge_hip_last_error", "lrge_hip_ctx_set_option",
     "lrge_hip_seqset_upload", "lrge_hip_seqset_upload_async", "lrge_hip_seqset_wait", "lrge_hip_host_alloc",
     "lrge_hip_host_free", "lrge_hip_seqset_free", "lrge_hip_seqset_size", "lrge_hip_seqset_presketch", "lrge_hip_seqset_presketch_sharded", "lrge_hip_pack_choice", "lrge_hip_read_records",
     "lrge_hip_bgzf_scan", "lrge_hip_bgzf_inflate", "lrge_hip_read_records_gpu",
+    "lrge_hip_gzip_inflate", "lrge_hip_read_records_gpu_ex",
     "lrge_hip_index_build", "lrge_hip_index_build_for", "lrge_hip_index_build_sharded", "lrge_hip_index_build_tsharded", "lrge_hip_last_shard_stats", "lrge_hip_index_free",
     "lrge_hip_comm_alltoallv", "lrge_hip_comm_rccl_ranks", "lrge_hip_comm_rccl_ops", "lrge_hip_comm_local_group_serialize", "lrge_hip_comm_local_turn",
     "lrge_hip_comm_busy_ms", "lrge_hip_comm_standin_ms",
@@ -86,6 +90,7 @@ def lib():
     L.lrge_hip_seqset_presketch.argtypes = [vp, vp, C.c_int]
     L.lrge_hip_bgzf_scan.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.lrge_hip_bgzf_inflate.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64]
+    L.lrge_hip_gzip_inflate.argtypes = [vp, vp, C.c_uint64, GZIP_SINK, vp, vp]
     L.lrge_hip_pack_choice.argtypes = [C.c_int, C.POINTER(C.c_double)]
     L.lrge_hip_seqset_presketch_sharded.argtypes = [vp, vp, C.c_int, vp]
     L.lrge_hip_index_build.argtypes = [vp, vp, C.c_int, C.POINTER(vp)]

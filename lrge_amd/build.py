@@ -43,13 +43,28 @@ TWIN_PATH = os.path.join(LIB_DIR, "liblrge_inflate_twin.so")
 
 
 def build_twin(force=False):
-    """The host twin of k_inflate (csrc/inflate_twin.cpp, g++): the same bit-level core, for the CPU suite."""
+    """The host twins (g++), for the CPU suite: of k_inflate (csrc/inflate_twin.cpp, the same bit-level core), and of the
+    speculative gzip decode (build_gzip_twin)."""
     os.makedirs(LIB_DIR, exist_ok=True)
+    build_gzip_twin(force)
     srcs = [os.path.join(CSRC, f) for f in ("inflate_twin.cpp", "inflate_core.h", "bgzf_scan.h")]
     if not force and os.path.exists(TWIN_PATH) and os.path.getmtime(TWIN_PATH) >= _newest(srcs):
         return TWIN_PATH
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-fPIC", "-shared", "-o", TWIN_PATH, srcs[0]])
     return TWIN_PATH
+
+
+GZIP_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_gzip_twin.so")
+
+
+def build_gzip_twin(force=False):
+    """The host twin of the speculative gzip decode (csrc/gzip_twin.cpp, g++): the same core and round logic, for the CPU suite."""
+    os.makedirs(LIB_DIR, exist_ok=True)
+    srcs = [os.path.join(CSRC, f) for f in ("gzip_twin.cpp", "gzip_core.h", "gzip_round.h", "inflate_core.h")]
+    if not force and os.path.exists(GZIP_TWIN_PATH) and os.path.getmtime(GZIP_TWIN_PATH) >= _newest(srcs):
+        return GZIP_TWIN_PATH
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-fPIC", "-shared", "-o", GZIP_TWIN_PATH, srcs[0]])
+    return GZIP_TWIN_PATH
 
 
 CLI_PATH = os.path.join(LIB_DIR, "lrge-hip")

@@ -196,6 +196,7 @@ struct lrge_hip_ctx {
     float ms[LRGE_T_N];
     u64 counters[LRGE_C_N];
     int n_cu = 256;
+    u8 *gz_pin[2] = {nullptr, nullptr}; size_t gz_pin_cap[2] = {0, 0};   // pinned staging of lrge_hip_gzip_inflate (in, out)
     bool lsort_ok[3] = {false, false, false};   // which k_seg_sort_local variants this device can launch
     struct lrge_hip_seqset *presk_pending = nullptr; int presk_preset = -1;   // lrge_hip_seqset_presketch request
     struct PreSketch *presk_prepared = nullptr; struct lrge_hip_seqset *presk_prepared_set = nullptr;   // memory taken, kernels not yet queued

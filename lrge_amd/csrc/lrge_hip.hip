@@ -27,6 +27,7 @@
 #include "k_tshard.h"
 #include "k_inflate.h"
 #include "bgzf_scan.h"
+#include "k_gzip.h"
 #include "../../include/lrge_rand.hpp"
 #include "../../include/lrge_io.hpp"
 
@@ -182,6 +183,7 @@ extern "C" void lrge_hip_ctx_destroy(lrge_hip_ctx *ctx) {
     if (ctx->pin) (void)hipHostFree(ctx->pin);
     if (ctx->ev_meta) (void)hipEventDestroy(ctx->ev_meta);
     if (ctx->meta_pin) (void)hipHostFree(ctx->meta_pin);
+    for (int b = 0; b < 2; ++b) if (ctx->gz_pin[b]) (void)hipHostFree(ctx->gz_pin[b]);
     (void)hipStreamSynchronize(ctx->stream2);
     (void)hipEventDestroy(ctx->ev_fork); (void)hipEventDestroy(ctx->ev_join); (void)hipEventDestroy(ctx->ev_presk);
     (void)hipStreamDestroy(ctx->stream2);
@@ -222,3 +224,4 @@ extern "C" int lrge_hip_last_counters(const lrge_hip_ctx *ctx, uint64_t c[LRGE_C
 #include "host_comm.inl"
 #include "host_estimate.inl"
 #include "host_inflate.inl"
+#include "host_gzip.inl"

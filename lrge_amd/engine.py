@@ -75,6 +75,25 @@ class Context:
         self._check(self._lib.lrge_hip_bgzf_inflate(self.h, data, len(data), out, total.value))
         return out.raw[:total.value]
 
+    def gzip_inflate(self, data, stats=False):
+        """Any gzip buffer (plain, multi-member or BGZF) decompressed on the device (lrge_hip_gzip_inflate); bytes in, bytes
+        out.  Damaged or trailing data raises LrgeHipError with code ERR_PARSE, a chunk beyond its slot ERR_TOO_MANY.
+        stats=True returns (bytes, dict of lrge_hip_gzip_stats)."""
+        data = bytes(data)
+        parts = []
+
+        def sink(_user, p, n):
+            parts.append(C.string_at(p, n))
+            return 0
+        cb = _ffi.GZIP_SINK(sink)
+        st = (C.c_uint64 * 7)()
+        self._check(self._lib.lrge_hip_gzip_inflate(self.h, data, len(data), cb, None, C.cast(st, C.c_void_p)))
+        out = b"".join(parts)
+        if not stats:
+            return out
+        keys = ("members", "chunks", "speculative_starts", "rejected_starts", "redecoded_chunks", "overflow_retries", "bytes_out")
+        return out, dict(zip(keys, list(st)))
+
     def set_timer_level(self, level):
         """0 = call total + chain stage only, 1 = every stage, 2 (default) = also every k_rs_scatter launch."""
         self._check(self._lib.lrge_hip_set_timer_level(self.h, int(level)))

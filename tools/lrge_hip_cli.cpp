@@ -13,11 +13,12 @@
 #include "../include/lrge_hip.hpp"
 #include "../include/lrge_io.hpp"
 
-static lrge::Reads load_reads(const std::string &path, bool gpu_inflate, int device) {   // io.rs:154-184 via include/lrge_io.hpp
+static lrge::Reads load_reads(const std::string &path, bool gpu_inflate, bool gpu_gzip, int device) {   // io.rs:154-184 via include/lrge_io.hpp
     lrge::Reads r;
     try {
         auto add = [&](const std::string &name, const std::string &seq) { r.names.push_back(name); r.seqs.push_back(seq); };
-        if (gpu_inflate) lrge::io::iter_records(path, add, lrge::bgzf_inflater(device));   // BGZF decompressed on the device
+        if (gpu_gzip) lrge::io::iter_records(path, add, lrge::gzip_inflater(device));          // every gzip input on the device
+        else if (gpu_inflate) lrge::io::iter_records(path, add, lrge::bgzf_inflater(device));   // BGZF decompressed on the device
         else lrge::io::iter_records(path, add);
     } catch (const lrge::io::IoError &e) {
         throw lrge::LrgeError(LRGE_ERR_IO, e.what());
@@ -58,7 +59,7 @@ int main(int argc, char **argv) {
     bool T_set = false, Q_set = false, filter = false, with_inf = false, precise = false, use_min_ref = false, honour_platform = false;
     float q1 = lrge::LOWER_QUANTILE, q3 = lrge::UPPER_QUANTILE, ratio = 0.2f;
     size_t threads = 1; std::optional<uint64_t> seed; int quiet = 0, verbose = 0, device = 0;
-    bool keep_temp = false, dump_records = false, gpu_inflate = false; std::string temp_dir;
+    bool keep_temp = false, dump_records = false, gpu_inflate = false, gpu_gzip = false; std::string temp_dir;
     auto need = [&](int &i) -> const char * { if (i + 1 >= argc) { fprintf(stderr, "error: missing value for %s\n", argv[i]); exit(2); } return argv[++i]; };
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -81,6 +82,7 @@ int main(int argc, char **argv) {
         else if (a == "--honour-platform") honour_platform = true;
         else if (a == "--device") device = atoi(need(i));
         else if (a == "--gpu-inflate") gpu_inflate = true;       // BGZF input (BAM, bgzip FASTQ) decompressed on --device
+        else if (a == "--gpu-gzip") gpu_gzip = true;             // every gzip input (plain, multi-member, BGZF) decompressed on --device
         else if (a == "--dump-records") dump_records = true;   // host-only: print "id<TAB>sequence" per record and exit (tests)
         else if (a == "-q" || a == "--quiet") ++quiet; else if (a == "-qq") quiet += 2; else if (a == "-qqq") quiet += 3;
         else if (a == "-v" || a == "--verbose") ++verbose; else if (a == "-vv") verbose += 2;
@@ -99,7 +101,7 @@ int main(int argc, char **argv) {
             fprintf(stderr, "%zu records\n", n);
             return 0;
         }
-        lrge::Reads reads = load_reads(input, gpu_inflate, device);
+        lrge::Reads reads = load_reads(input, gpu_inflate, gpu_gzip, device);
         const lrge::Platform pf = (honour_platform && platform == "pb") ? lrge::Platform::PacBio : lrge::Platform::Nanopore;
         lrge::twoset::TwoSetStrategy ts(reads); lrge::ava::AvaStrategy as(reads);
         lrge::Estimate *st;
