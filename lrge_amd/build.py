@@ -47,7 +47,7 @@ def build_twin(force=False):
     speculative gzip decode (build_gzip_twin)."""
     os.makedirs(LIB_DIR, exist_ok=True)
     build_gzip_twin(force)
-    srcs = [os.path.join(CSRC, f) for f in ("inflate_twin.cpp", "inflate_core.h", "bgzf_scan.h")]
+    srcs = [os.path.join(CSRC, f) for f in ("inflate_twin.cpp", "inflate_core.h", "bgzf_scan.h", "twin_env.h")]
     if not force and os.path.exists(TWIN_PATH) and os.path.getmtime(TWIN_PATH) >= _newest(srcs):
         return TWIN_PATH
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-fPIC", "-shared", "-o", TWIN_PATH, srcs[0]])
@@ -60,7 +60,7 @@ GZIP_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_gzip_twin.so")
 def build_gzip_twin(force=False):
     """The host twin of the speculative gzip decode (csrc/gzip_twin.cpp, g++): the same core and round logic, for the CPU suite."""
     os.makedirs(LIB_DIR, exist_ok=True)
-    srcs = [os.path.join(CSRC, f) for f in ("gzip_twin.cpp", "gzip_core.h", "gzip_round.h", "inflate_core.h")]
+    srcs = [os.path.join(CSRC, f) for f in ("gzip_twin.cpp", "gzip_core.h", "gzip_round.h", "inflate_core.h", "twin_env.h")]
     if not force and os.path.exists(GZIP_TWIN_PATH) and os.path.getmtime(GZIP_TWIN_PATH) >= _newest(srcs):
         return GZIP_TWIN_PATH
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-fPIC", "-shared", "-o", GZIP_TWIN_PATH, srcs[0]])

@@ -1,6 +1,7 @@
 // gzip_core.h -- speculative decoding of plain and multi-member gzip (RFC 1952 members of RFC 1951 deflate): the marker
-// decode driver, the block-start predicates of the finder and the 64-bit CRC shift.  Compiled by hipcc (k_gzip.h) and g++
-// (gzip_twin.cpp) alike, on top of the bit-level core of inflate_core.h (whose inf_raw / k_inflate stay the BGZF path).
+// decode driver, the block-start predicates of the finder and the CRC shift by table.  Compiled by hipcc (k_gzip.h) and g++
+// (gzip_twin.cpp) alike, on top of inflate_core.h: the bit reader, the tables and the deflate block body (inf_block) are the
+// ones of the BGZF path (inf_raw / k_inflate).
 //
 // A chunk is decoded from a bit offset whose 32 KiB window is not known.  The driver emits 16-bit symbols: 0-255 a byte,
 // GZ_MARK | i byte i of the unknown window (a back-reference that reaches before the chunk's first symbol; markers are copied
@@ -133,12 +134,6 @@ INF_FN bool gz_maybe_candidate(const uint8_t *p, uint32_t n, uint32_t bit) {
 }
 
 // ---- the marker decode driver ----
-INF_FN uint32_t gz_bitpos(const InfBits &b) { return b.pos * 8u - (b.cnt - b.over); }
-INF_FN void gz_seek(InfBits &b, uint32_t bit) {
-    b.pos = bit >> 3; b.cnt = 0; b.over = 0; b.buf = 0;
-    inf_refill(b);
-    inf_drop(b, bit & 7);
-}
 // header length of the member at byte q, or -(status)
 INF_FN int gz_header_len(const uint8_t *p, uint32_t n, uint32_t q) {
     if (q + 10 > n) return -(int)INF_E_INPUT;
@@ -168,8 +163,9 @@ INF_FN int gz_header_len(const uint8_t *p, uint32_t n, uint32_t q) {
 
 // Decode p[0, n) from bit `start` until the first boundary at or past `stop` (or the end of the input when `eof`: p[n] is
 // the input's end).  E (see inflate_core.h) with output of u16 symbols: E::lit(b), E::copy(dist, len) (a source index
-// before 0 is marker GZ_MARK | (GZ_WIN + index)), E::stored(src, n), E::pos, E::cap (overflow: GZ_E_OVERFLOW);
-// E::seg(i, s) stores a segment record.
+// before 0 is marker GZ_MARK | (GZ_WIN + index)), E::stored(src, n), E::pos, E::cap (E::full: GZ_E_OVERFLOW);
+// E::seg(i, s) stores a segment record.  E::own / E::mstart (the member started in this chunk, at this symbol) are set here
+// and read by E::reach(): own ? pos - mstart : pos + GZ_WIN.
 template <class E> INF_FN void gz_decode(E &e, const uint8_t *p, uint32_t n, bool eof, uint32_t start, uint32_t stop,
                                          uint32_t max_seg, GzRes &r) {
     r.status = INF_OK; r.end_bit = start; r.n_sym = 0; r.n_seg = 0; r.eof = 0; r.pad = 0;
@@ -177,16 +173,16 @@ template <class E> INF_FN void gz_decode(E &e, const uint8_t *p, uint32_t n, boo
     uint32_t nseg = 0;
     GzSeg cur = {0, 0, 0, 0, 0};
     bool in_member = !((start & 7) == 0 && INF_UNI(gz_is_header(p, n, start >> 3)));
-    bool open = in_member, own = false;                          // own: the member started in this chunk
-    uint32_t mstart = 0;
+    bool open = in_member;
+    e.own = false; e.mstart = 0;
     InfBits b;
     inf_bits_init(b, p, 0, n);
-    if (start > 8 * n) rc = INF_E_INPUT; else gz_seek(b, start);
+    if (start > 8 * n) rc = INF_E_INPUT; else inf_seek(b, start);
     const uint32_t guard = 8 * n / 3 + 2;                        // every block takes >= 3 bits, every member >= 18 bytes
     bool ended = false;
     for (uint32_t it = 0; !rc && it < guard; ++it) {
         if (inf_overrun(b)) { rc = INF_E_INPUT; break; }
-        const uint32_t at = gz_bitpos(b);
+        const uint32_t at = inf_bitpos(b);
         const uint32_t cb = in_member ? INF_UNI(gz_canon(p, n, at)) : at;
         if (!in_member && (at >> 3) == n && eof) { r.eof = 1; r.end_bit = at; ended = true; break; }
         if (cb >= stop) { r.end_bit = cb; ended = true; break; }
@@ -194,69 +190,22 @@ template <class E> INF_FN void gz_decode(E &e, const uint8_t *p, uint32_t n, boo
             const int hl = gz_header_len(p, n, at >> 3);
             if (hl < 0) { rc = -hl; break; }
             cur = GzSeg{e.pos, 0, 0, 0, GZ_SEG_HEAD};
-            open = true; own = true; mstart = e.pos; in_member = true;
-            gz_seek(b, at + 8u * (uint32_t)hl);
+            open = true; e.own = true; e.mstart = e.pos; in_member = true;
+            inf_seek(b, at + 8u * (uint32_t)hl);
             continue;                                            // the first block's start is a boundary too
         }
-        inf_refill(b);
-        const bool last = inf_get(b, 1) != 0;
-        const uint32_t type = inf_get(b, 2);
-        if (type == 3) { rc = INF_E_BTYPE; break; }
-        if (type == 0) {
-            inf_drop(b, b.cnt & 7);
-            if (b.over > b.cnt) { rc = INF_E_INPUT; break; }
-            const uint32_t q = gz_bitpos(b) >> 3;
-            if (q + 4 > n) { rc = INF_E_INPUT; break; }
-            const uint32_t len = INF_UNI(gz_u16(p + q)), nlen = INF_UNI(gz_u16(p + q + 2));
-            if ((len ^ 0xFFFFu) != nlen) { rc = INF_E_STORED; break; }
-            if (len > n - q - 4) { rc = INF_E_INPUT; break; }
-            if (len > e.cap - e.pos) { rc = GZ_E_OVERFLOW; break; }
-            e.stored(p + q + 4, len);
-            gz_seek(b, 8 * (q + 4 + len));
-        } else {
-            rc = type == 1 ? inf_fixed(e) : inf_dynamic(e, b);
-            if (rc) break;
-            bool eob = false;
-            for (uint32_t g = 0; g <= e.cap; ++g) {
-                inf_refill(b);
-                if (inf_overrun(b)) { rc = INF_E_INPUT; break; }
-                const int s = inf_decode(b, e.lt);
-                if (s < 0) { rc = INF_E_SYMBOL; break; }
-                if (s < 256) {
-                    if (e.pos >= e.cap) { rc = GZ_E_OVERFLOW; break; }
-                    e.lit((uint8_t)s);
-                    continue;
-                }
-                if (s == 256) { eob = true; break; }
-                const uint32_t ls = (uint32_t)s - 257;
-                if (ls >= 29) { rc = INF_E_SYMBOL; break; }
-                uint32_t len;
-                if (ls < 8) len = ls + 3;
-                else if (ls == 28) len = 258;
-                else { const uint32_t x = (ls - 8) >> 2, eb = x + 1; len = 3 + (1u << (eb + 2)) + (((ls - 8) & 3) << eb) + inf_get(b, eb); }
-                inf_refill(b);
-                const int ds = inf_decode(b, e.dt);
-                if (ds < 0 || ds >= 30) { rc = INF_E_SYMBOL; break; }
-                uint32_t dist;
-                if (ds < 4) dist = (uint32_t)ds + 1;
-                else { const uint32_t eb = ((uint32_t)ds >> 1) - 1; dist = 1 + ((2u + ((uint32_t)ds & 1)) << eb) + inf_get(b, eb); }
-                if (inf_overrun(b)) { rc = INF_E_INPUT; break; }
-                if (own ? dist > e.pos - mstart : dist > e.pos + GZ_WIN) { rc = INF_E_DIST; break; }
-                if (len > e.cap - e.pos) { rc = GZ_E_OVERFLOW; break; }
-                e.copy(dist, len);
-            }
-            if (!rc && !eob) rc = GZ_E_OVERFLOW;                 // (the guard: more symbols than the slot holds)
-            if (rc) break;
-        }
+        bool last = false;
+        rc = inf_block(e, b, &last);
+        if (rc) break;
         if (last) {                                              // the trailer, then the next member's header
             if (inf_overrun(b)) { rc = INF_E_INPUT; break; }
-            const uint32_t q = (gz_bitpos(b) + 7) >> 3;
+            const uint32_t q = (inf_bitpos(b) + 7) >> 3;
             if (q + 8 > n) { rc = INF_E_INPUT; break; }
             cur.o1 = e.pos; cur.crc = INF_UNI(gz_u32(p + q)); cur.isize = INF_UNI(gz_u32(p + q + 4)); cur.flags |= GZ_SEG_TRAIL;
             if (nseg >= max_seg) { rc = GZ_E_SEGS; break; }
             e.seg(nseg++, cur);
-            open = false; own = false; in_member = false;
-            gz_seek(b, 8 * (q + 8));
+            open = false; e.own = false; in_member = false;
+            inf_seek(b, 8 * (q + 8));
         }
     }
     if (!rc && !ended) rc = INF_E_INPUT;
@@ -264,20 +213,11 @@ template <class E> INF_FN void gz_decode(E &e, const uint8_t *p, uint32_t n, boo
         cur.o1 = e.pos;
         if (nseg >= max_seg) rc = GZ_E_SEGS; else e.seg(nseg++, cur);
     }
-    if (rc) r.end_bit = inf_overrun(b) ? 8 * n : gz_bitpos(b);   // where it failed: the walk tells damage from a short buffer
+    if (rc) r.end_bit = inf_overrun(b) ? 8 * n : inf_bitpos(b);   // where it failed: the walk tells damage from a short buffer
     r.status = (uint32_t)rc; r.n_sym = e.pos; r.n_seg = nseg;
 }
 
-// ---- CRC-32 over any length ----
-// crc * x^(8 n) mod P for a 64-bit byte count (inf_crc_shift assumes n <= 65536 in its step count; this form does not)
-INF_FN uint32_t inf_crc_shift64(uint32_t crc, uint64_t n) {
-    uint32_t x = 1u << 23;                                       // x^8
-    for (; n; n >>= 1) {
-        if (n & 1) crc = inf_gf2_mul(x, crc);
-        x = inf_gf2_mul(x, x);
-    }
-    return crc;
-}
+// ---- CRC-32 shifts by table, and the running register ----
 // pw[i] = x^(8 * 2^i) mod P, for shifts by table (gz_crc_shift_tab)
 INF_FN void gz_crc_powers(uint32_t *pw, uint32_t k) { uint32_t x = 1u << 23; for (uint32_t i = 0; i < k; ++i) { pw[i] = x; x = inf_gf2_mul(x, x); } }
 INF_FN uint32_t gz_crc_shift_tab(const uint32_t *pw, uint32_t crc, uint32_t n) {

@@ -207,7 +207,7 @@ static int gz_run(D &dev, const uint8_t *d, uint64_t n, GzCfg cfg, Sink &&sink, 
             if (g.flags & GZ_SEG_HEAD) { if (in_member) return GZ_E_HEADER; in_member = true; mcrc = 0; msize = 0; }
             else if (!in_member) return GZ_E_HEADER;
             const uint64_t len = g.o1 - g.o0;
-            mcrc = inf_crc_shift64(mcrc, len) ^ seg_crc[s];
+            mcrc = inf_crc_shift(mcrc, len) ^ seg_crc[s];
             msize += len;
             if (g.flags & GZ_SEG_TRAIL) {
                 if (mcrc != g.crc || (uint32_t)msize != g.isize) {

@@ -9,19 +9,19 @@
 
 #include "gzip_core.h"
 #include "gzip_round.h"
+#include "twin_env.h"
 
 #define GZ_TWIN_STRIPE 1024u      // bytes per lane stripe of k_gz_resolve
 
 namespace {
-struct Env {
-    uint32_t lane = 0, nl = 1;
-    InfCode tabs[3];
-    InfCode *lt = &tabs[0], *dt = &tabs[1], *ct = &tabs[2];
-    uint8_t lens[320];
+struct Env : TwinTabs {
+    static constexpr int full = GZ_E_OVERFLOW;
     uint16_t *out = nullptr;
     GzSeg *sp = nullptr;
     uint32_t pos = 0, cap = 0;
-    void sync() {}
+    bool own = false;                                         // the current member started in this chunk, at symbol mstart
+    uint32_t mstart = 0;
+    uint32_t reach() const { return own ? pos - mstart : pos + GZ_WIN; }
     void lit(uint8_t b) { out[pos++] = b; }
     void copy(uint32_t dist, uint32_t len) {
         for (uint32_t j = 0; j < len; ++j, ++pos) {
@@ -33,12 +33,9 @@ struct Env {
     void seg(uint32_t i, const GzSeg &s) { sp[i] = s; }
 };
 
-struct CrcTab { uint32_t t[256]; CrcTab() { inf_crc_table(t, 0, 1); } };
-
 struct Twin {
     const uint8_t *p = nullptr;
     uint32_t n = 0;
-    GzCfg cfg{};
     std::vector<uint16_t> sym;
     std::vector<GzSeg> seg;
     std::vector<std::vector<uint16_t>> sym_big;      // retry buffers of the round
@@ -133,10 +130,8 @@ extern "C" {
 // stats[7]: members, chunks, speculative, rejected, redecoded, overflow retries, bytes out.
 int gzip_twin_inflate(const uint8_t *d, uint64_t n, uint64_t chunk, uint64_t round, uint64_t ratio, uint64_t *stats, uint64_t *bad_off) {
     Twin t;
-    t.cfg = GzCfg{chunk, round, ratio};
     g_out.clear();
     GzStats st;
-
     const int rc = gz_run(t, d, n, GzCfg{chunk, round, ratio}, [&](const uint8_t *b, uint64_t k) { g_out.insert(g_out.end(), b, b + k); return true; }, st, bad_off);
     if (stats) { stats[0] = st.members; stats[1] = st.chunks; stats[2] = st.speculative; stats[3] = st.rejected; stats[4] = st.redecoded; stats[5] = st.overflow_retries; stats[6] = st.bytes_out; }
     return rc == GZ_RUN_TOO_MANY ? -1 : rc;

@@ -102,8 +102,7 @@ struct GzDev {
         ctx->gz_pin_cap[i] = bytes;
         return ctx->gz_pin[i];
     }
-    std::vector<GzRes> *pend_res = nullptr; uint32_t pend_nt = 0;
-    bool launch(const GzTask *t, uint32_t nt, bool eof) { return launch_into(t, nt, eof); }
+    uint32_t pend_nt = 0;
     bool wait(GzRes *r) {
         if (!ok(hipMemcpyAsync(r, res.p, (size_t)pend_nt * sizeof(GzRes), hipMemcpyDeviceToHost, ctx->stream))) return false;
         return sync();
@@ -116,30 +115,25 @@ struct GzDev {
         if (!ok(hipMemcpyAsync(c + 1, cand.as<u32>() + 1, (size_t)(nc - 1) * 4, hipMemcpyDeviceToHost, ctx->stream))) return false;
         return sync();
     }
-    bool launch_into(const GzTask *t, uint32_t nt, bool eof) {
-        u16 *sy; GzSeg *sg;
+    bool launch(const GzTask *t, uint32_t nt, bool eof) {
+        u64 need_s = 0, need_g = 0;
+        for (uint32_t i = 0; i < nt; ++i) { need_s = std::max<u64>(need_s, t[i].sym_off + t[i].cap); need_g = std::max<u64>(need_g, (u64)t[i].seg_off + t[i].seg_cap); }
+        GzBuf *a = &sym, *b = &seg;
         if (t[0].big) {                                          // (every task of the call in one extra buffer of its own)
-            u64 need_s = 0, need_g = 0;
-            for (uint32_t i = 0; i < nt; ++i) { need_s = std::max<u64>(need_s, t[i].sym_off + t[i].cap); need_g = std::max<u64>(need_g, (u64)t[i].seg_off + t[i].seg_cap); }
-            GzBuf *a = new GzBuf, *b = new GzBuf;
+            a = new GzBuf; b = new GzBuf;
             a->ctx = ctx; b->ctx = ctx;
             big_sym.push_back(a); big_seg.push_back(b);
-            if (!a->need((size_t)need_s * 2, &e) || !b->need((size_t)need_g * sizeof(GzSeg), &e)) return false;
-            big_ptr.push_back(a->as<const u16>());
-            sy = a->as<u16>(); sg = b->as<GzSeg>();
-        } else {
-            u64 need_s = 0, need_g = 0;
-            for (uint32_t i = 0; i < nt; ++i) { need_s = std::max<u64>(need_s, t[i].sym_off + t[i].cap); need_g = std::max<u64>(need_g, (u64)t[i].seg_off + t[i].seg_cap); }
-            if (!sym.need(need_s * 2, &e) || !seg.need(need_g * sizeof(GzSeg), &e)) return false;
-            sy = sym.as<u16>(); sg = seg.as<GzSeg>();
         }
+        if (!a->need((size_t)need_s * 2, &e) || !b->need((size_t)need_g * sizeof(GzSeg), &e)) return false;
+        if (t[0].big) big_ptr.push_back(a->as<const u16>());
+        u16 *sy = a->as<u16>(); GzSeg *sg = b->as<GzSeg>();
         if (!tasks.need((size_t)nt * sizeof(GzTask), &e) || !res.need((size_t)nt * sizeof(GzRes), &e)) return false;
         if (!ok(hipMemcpyAsync(tasks.p, t, (size_t)nt * sizeof(GzTask), hipMemcpyHostToDevice, ctx->stream))) return false;
         hipLaunchKernelGGL(k_gz_decode, dim3(nt), dim3(64), 0, ctx->stream, in_ptr, n, (u32)eof, tasks.as<const GzTask>(), nt, sy, sg, res.as<GzRes>());
         pend_nt = nt;
         return ok(hipGetLastError());
     }
-    bool decode(const GzTask *t, uint32_t nt, bool eof, GzRes *r) { return launch_into(t, nt, eof) && wait(r); }
+    bool decode(const GzTask *t, uint32_t nt, bool eof, GzRes *r) { return launch(t, nt, eof) && wait(r); }
     bool segs(const GzTask &t, uint32_t k, GzSeg *o) {
         const GzSeg *src = (t.big ? big_seg[t.big - 1]->as<const GzSeg>() : seg.as<const GzSeg>()) + t.seg_off;
         return ok(hipMemcpy(o, src, (size_t)k * sizeof(GzSeg), hipMemcpyDeviceToHost));

@@ -1,5 +1,5 @@
-// host_inflate.inl -- BGZF decompression on the device (k_inflate.h): the block scan, the chunked pipeline and the record
-// reader that uses it.  Included into lrge_hip.hip.
+// host_inflate.inl -- BGZF decompression on the device (k_inflate.h): the block scan and the chunked pipeline; the record
+// reader is the one of host_gzip.inl with the BGZF path alone.  Included into lrge_hip.hip.
 //
 // The block table of a BGZF buffer (bgzf_scan.h) is cut into chunks that end on block boundaries and hold at most
 // INFLATE_CHUNK_BYTES (option; compressed + decompressed bytes, default 256 MiB, at least one block).  Two slots of pinned
@@ -130,30 +130,5 @@ extern "C" int lrge_hip_bgzf_inflate(lrge_hip_ctx *ctx, const void *comp, uint64
 
 extern "C" int lrge_hip_read_records_gpu(lrge_hip_ctx *ctx, const char *path, void (*cb)(void *, const char *, uint64_t, const char *, uint64_t),
                                          void *user, int *used_device) {
-    if (!ctx || !path || !cb) return LRGE_ERR_INVALID;
-    if (used_device) *used_device = 0;
-    struct DeviceFail { int rc; };
-    int used = 0;
-    try {
-        lrge::io::iter_records(path, [&](const std::string &n, const std::string &s) { cb(user, n.data(), (uint64_t)n.size(), s.data(), (uint64_t)s.size()); },
-                               [&](const std::string &raw, std::string &data) -> bool {
-            std::vector<BgzfBlock> t;
-            uint64_t total = 0;
-            if (!bgzf_scan_blocks((const uint8_t *)raw.data(), raw.size(), &t, &total)) return false;
-            data.resize((size_t)total);
-            const int rc = bgzf_inflate_table(ctx, (const uint8_t *)raw.data(), t, (uint8_t *)&data[0]);
-            if (rc == LRGE_ERR_DEVICE) throw DeviceFail{rc};
-            if (rc != LRGE_OK) { data.clear(); return false; }    // a block the device rejects: the host path, with its messages
-            used = 1;
-            return true;
-        });
-    } catch (const DeviceFail &) {
-        return LRGE_ERR_DEVICE;
-    } catch (const std::exception &e) {
-        ctx->err = e.what();
-        if (used_device) *used_device = used;
-        return strncmp(e.what(), "cannot open", 11) == 0 ? LRGE_ERR_IO : LRGE_ERR_PARSE;
-    }
-    if (used_device) *used_device = used;
-    return LRGE_OK;
+    return lrge_hip_read_records_gpu_ex(ctx, path, LRGE_GPU_INFLATE_BGZF, cb, user, used_device);      // (host_gzip.inl)
 }

@@ -1,13 +1,15 @@
-// inflate_core.h -- RFC 1951 (deflate) decoding of one BGZF block: the bit reader, block headers, code-length decode,
-// canonical-code tables and symbol decode, shared bit for bit by the device kernel (k_inflate.h, hipcc) and the host
-// twin (inflate_twin.cpp, g++) that the CPU suite checks against zlib.  Also the CRC-32 of a block computed over lane
-// stripes and combined (the twin emulates the 64 stripes, so the combine is checked on the host too).
+// inflate_core.h -- RFC 1951 (deflate) decoding: the bit reader, code-length decode, canonical-code tables and the body of
+// one deflate block (inf_block: header, stored path, symbol loop), shared bit for bit by the device kernels (k_inflate.h,
+// k_gzip.h; hipcc) and the host twins (inflate_twin.cpp, gzip_twin.cpp; g++) that the CPU suite checks against zlib.
+// inf_raw decodes one BGZF block with it; gzip_core.h's gz_decode drives it over plain gzip.  Also the CRC-32 of a block
+// computed over lane stripes and combined (the twin emulates the 64 stripes, so the combine is checked on the host too).
 //
 // The decoder is written once against an environment `E` that owns the output and the tables:
 //   E::lane, E::nl            this lane and the lane count (twin: 0, 1)
 //   E::sync()                 every lane's table writes visible to every lane (kernel: workgroup barrier of one wavefront)
 //   E::lt, E::dt, E::ct       InfCode tables (kernel: LDS);  E::lens  320 code lengths (kernel: LDS)
 //   E::pos, E::cap            bytes written so far / the block's ISIZE
+//   E::full, E::reach()       the status when the output has no room (INF_E_OUTPUT) / the largest legal distance at pos
 //   E::lit(b), E::copy(dist, len), E::stored(src, n)   output (kernel: spread over the lanes)
 // Every decision is taken on values that are the same in every lane (INF_UNI makes that explicit to the compiler), so
 // the bit reader and the symbol decode stay wave-uniform.
@@ -48,6 +50,7 @@ enum {
 #define INF_PRIM (1u << INF_PRIM_BITS)
 #define INF_MAX_ISIZE 65536u
 
+// Bit offsets of the input (inf_bitpos, inf_seek) are 32 bits wide: the caller keeps 8 * end < 2^32.
 struct InfBits {
     const uint8_t *p;
     uint32_t pos, end;      // next byte to read, one past the last readable byte
@@ -89,6 +92,14 @@ INF_FN bool inf_overrun(const InfBits &b) { return b.over > b.cnt; }      // a p
 INF_FN uint32_t inf_peek(const InfBits &b, uint32_t n) { return (uint32_t)(b.buf & ((1ull << n) - 1)); }
 INF_FN void inf_drop(InfBits &b, uint32_t n) { b.buf >>= n; b.cnt -= n; }
 INF_FN uint32_t inf_get(InfBits &b, uint32_t n) { const uint32_t v = inf_peek(b, n); inf_drop(b, n); return v; }
+
+// the bit offset of the next unread bit (not past an overrun), and the reader put on a bit offset
+INF_FN uint32_t inf_bitpos(const InfBits &b) { return b.pos * 8u - (b.cnt - b.over); }
+INF_FN void inf_seek(InfBits &b, uint32_t bit) {
+    b.pos = bit >> 3; b.cnt = 0; b.over = 0; b.buf = 0;
+    inf_refill(b);
+    inf_drop(b, bit & 7);
+}
 
 INF_FN uint32_t inf_rev(uint32_t c, uint32_t len) { uint32_t r = 0; for (uint32_t i = 0; i < len; ++i) { r = r << 1 | (c & 1); c >>= 1; } return r; }
 
@@ -202,6 +213,62 @@ template <class E> INF_FN int inf_dynamic(E &e, InfBits &b) {
     return rc;
 }
 
+// One deflate block at the reader's position (header bits included): *last = BFINAL.  INF_OK or a status; the order of the
+// checks decides which status a damaged stream gets.  What differs between the callers comes from E at compile time:
+// E::full (the status for "no room for this output") and E::reach() (the largest legal distance at e.pos).
+template <class E> INF_FN int inf_block(E &e, InfBits &b, bool *last) {
+    inf_refill(b);
+    if (inf_overrun(b)) return INF_E_INPUT;
+    *last = inf_get(b, 1) != 0;
+    const uint32_t type = inf_get(b, 2);
+    if (type == 3) return INF_E_BTYPE;
+    if (type == 0) {
+        inf_drop(b, b.cnt & 7);                                  // to a byte boundary
+        if (inf_overrun(b)) return INF_E_INPUT;
+        const uint32_t q = inf_bitpos(b) >> 3;                   // LEN's byte
+        if (q + 4 > b.end) return INF_E_INPUT;
+        const uint8_t *h = b.p + q;
+        const uint32_t len = INF_UNI((uint32_t)h[0] | (uint32_t)h[1] << 8), nlen = INF_UNI((uint32_t)h[2] | (uint32_t)h[3] << 8);
+        if ((len ^ 0xFFFFu) != nlen) return INF_E_STORED;
+        if (len > b.end - q - 4) return INF_E_INPUT;
+        if (len > e.cap - e.pos) return E::full;
+        e.stored(h + 4, len);
+        inf_seek(b, 8 * (q + 4 + len));
+        return INF_OK;
+    }
+    const int rc = type == 1 ? inf_fixed(e) : inf_dynamic(e, b);
+    if (rc) return rc;
+    for (uint32_t guard = 0; guard <= e.cap; ++guard) {         // every symbol but the last writes a byte
+        inf_refill(b);
+        if (inf_overrun(b)) return INF_E_INPUT;
+        const int s = inf_decode(b, e.lt);
+        if (s < 0) return INF_E_SYMBOL;
+        if (s < 256) {
+            if (e.pos >= e.cap) return E::full;
+            e.lit((uint8_t)s);
+            continue;
+        }
+        if (s == 256) return INF_OK;
+        const uint32_t ls = (uint32_t)s - 257;
+        if (ls >= 29) return INF_E_SYMBOL;
+        uint32_t len;
+        if (ls < 8) len = ls + 3;
+        else if (ls == 28) len = 258;
+        else { const uint32_t x = (ls - 8) >> 2, eb = x + 1; len = 3 + (1u << (eb + 2)) + (((ls - 8) & 3) << eb) + inf_get(b, eb); }
+        inf_refill(b);
+        const int ds = inf_decode(b, e.dt);
+        if (ds < 0 || ds >= 30) return INF_E_SYMBOL;
+        uint32_t dist;
+        if (ds < 4) dist = (uint32_t)ds + 1;
+        else { const uint32_t eb = ((uint32_t)ds >> 1) - 1; dist = 1 + ((2u + ((uint32_t)ds & 1)) << eb) + inf_get(b, eb); }
+        if (inf_overrun(b)) return INF_E_INPUT;
+        if (dist > e.reach()) return INF_E_DIST;
+        if (len > e.cap - e.pos) return E::full;
+        e.copy(dist, len);
+    }
+    return E::full;                                              // (the guard: more symbols than the output holds)
+}
+
 // The raw deflate stream of one block: input [start, end) of p, output through e.  The stream must end exactly at `end`
 // (up to the last byte's padding bits), like a gzip member whose trailer follows.
 template <class E> INF_FN int inf_raw(E &e, const uint8_t *p, uint32_t start, uint32_t end) {
@@ -210,64 +277,12 @@ template <class E> INF_FN int inf_raw(E &e, const uint8_t *p, uint32_t start, ui
     const uint32_t max_blocks = (end - start) * 8u / 3u + 1u;      // every deflate block takes at least 3 bits
     bool last = false;
     for (uint32_t blk = 0; blk < max_blocks && !last; ++blk) {
-        inf_refill(b);
-        if (inf_overrun(b)) return INF_E_INPUT;
-        last = inf_get(b, 1) != 0;
-        const uint32_t type = inf_get(b, 2);
-        if (type == 3) return INF_E_BTYPE;
-        if (type == 0) {
-            inf_drop(b, b.cnt & 7);                              // to a byte boundary
-            const uint32_t back = b.cnt >> 3;                    // whole bytes read ahead
-            if (b.over > b.cnt) return INF_E_INPUT;
-            const uint32_t held = back - (b.over >> 3);          // of which real input
-            b.pos -= held; b.buf = 0; b.cnt = 0; b.over = 0;
-            if (b.pos + 4 > b.end) return INF_E_INPUT;
-            const uint32_t len = INF_UNI((uint32_t)p[b.pos] | (uint32_t)p[b.pos + 1] << 8), nlen = INF_UNI((uint32_t)p[b.pos + 2] | (uint32_t)p[b.pos + 3] << 8);
-            b.pos += 4;
-            if ((len ^ 0xFFFFu) != nlen) return INF_E_STORED;
-            if (len > b.end - b.pos) return INF_E_INPUT;
-            if (len > e.cap - e.pos) return INF_E_OUTPUT;
-            e.stored(p + b.pos, len);
-            b.pos += len;
-            continue;
-        }
-        const int rc = type == 1 ? inf_fixed(e) : inf_dynamic(e, b);
+        const int rc = inf_block(e, b, &last);
         if (rc) return rc;
-        for (uint32_t guard = 0; guard <= e.cap; ++guard) {     // every symbol but the last writes a byte
-            inf_refill(b);
-            if (inf_overrun(b)) return INF_E_INPUT;
-            const int s = inf_decode(b, e.lt);
-            if (s < 0) return INF_E_SYMBOL;
-            if (s < 256) {
-                if (e.pos >= e.cap) return INF_E_OUTPUT;
-                e.lit((uint8_t)s);
-                continue;
-            }
-            if (s == 256) break;
-            const uint32_t ls = (uint32_t)s - 257;
-            if (ls >= 29) return INF_E_SYMBOL;
-            uint32_t len;
-            if (ls < 8) len = ls + 3;
-            else if (ls == 28) len = 258;
-            else { const uint32_t x = (ls - 8) >> 2, eb = x + 1; len = 3 + (1u << (eb + 2)) + (((ls - 8) & 3) << eb) + inf_get(b, eb); }
-            inf_refill(b);
-            const int ds = inf_decode(b, e.dt);
-            if (ds < 0) return INF_E_SYMBOL;
-            if (ds >= 30) return INF_E_SYMBOL;
-            uint32_t dist;
-            if (ds < 4) dist = (uint32_t)ds + 1;
-            else { const uint32_t eb = ((uint32_t)ds >> 1) - 1; dist = 1 + ((2u + ((uint32_t)ds & 1)) << eb) + inf_get(b, eb); }
-            if (inf_overrun(b)) return INF_E_INPUT;
-            if (dist > e.pos) return INF_E_DIST;
-            if (len > e.cap - e.pos) return INF_E_OUTPUT;
-            e.copy(dist, len);
-        }
     }
     if (!last) return INF_E_INPUT;
     if (inf_overrun(b)) return INF_E_INPUT;
-    // bytes consumed, padding bits of the last one included: exactly the deflate range
-    const uint32_t held_real = b.cnt - b.over;                   // real bits still held (over <= cnt here)
-    if (b.pos - (held_real >> 3) != end) return INF_E_INPUT;
+    if ((inf_bitpos(b) + 7) >> 3 != end) return INF_E_INPUT;       // bytes consumed, the last one's padding bits included
     if (e.pos != e.cap) return INF_E_SIZE;
     return INF_OK;
 }
@@ -293,9 +308,10 @@ INF_FN uint32_t inf_gf2_mul(uint32_t a, uint32_t b) {
 }
 // crc * x^(8 n) mod P: the CRC of A moved past n more bytes.  crc(A || B) = inf_crc_shift(crc(A), |B|) ^ crc(B), so the
 // CRC of the stripes S_0 .. S_k is the XOR over i of inf_crc_shift(crc(S_i), bytes after S_i).
-INF_FN uint32_t inf_crc_shift(uint32_t crc, uint32_t n) {
+// The byte count is 64 bits wide for gzip members above 4 GiB; a block's stripes stay below 17 steps (n <= 65536).
+INF_FN uint32_t inf_crc_shift(uint32_t crc, uint64_t n) {
     uint32_t x = 1u << 23;                                       // x^8
-    for (; n; n >>= 1) {                                         // at most 17 steps (n <= 65536)
+    for (; n; n >>= 1) {
         if (n & 1) crc = inf_gf2_mul(x, crc);
         x = inf_gf2_mul(x, x);
     }

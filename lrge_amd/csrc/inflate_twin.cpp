@@ -1,4 +1,4 @@
-// inflate_twin.cpp -- the host twin of k_inflate (g++): the same bit-level core (inflate_core.h) and block scan (bgzf_scan.h)
+// inflate_twin.cpp -- the host twin of k_inflate (g++): the same decoder (inflate_core.h) and block scan (bgzf_scan.h)
 // with a sequential environment, and the block CRC over 64 emulated lane stripes, so the CPU suite checks the decoding
 // logic against zlib with no GPU (tests/test_bgzf_twin.py).  TEST INFRASTRUCTURE, not part of the product library.
 #include <stdint.h>
@@ -7,23 +7,18 @@
 #include <vector>
 
 #include "bgzf_scan.h"
-#include "inflate_core.h"
+#include "twin_env.h"
 
 namespace {
-struct TwinEnv {
-    uint32_t lane = 0, nl = 1;
-    InfCode tabs[3];
-    InfCode *lt = &tabs[0], *dt = &tabs[1], *ct = &tabs[2];
-    uint8_t lens[320];
+struct TwinEnv : TwinTabs {
+    static constexpr int full = INF_E_OUTPUT;
     uint8_t *out;
     uint32_t pos = 0, cap;
-    void sync() {}
+    uint32_t reach() const { return pos; }
     void lit(uint8_t b) { out[pos++] = b; }
     void copy(uint32_t dist, uint32_t len) { for (uint32_t j = 0; j < len; ++j, ++pos) out[pos] = out[pos - dist]; }
     void stored(const uint8_t *src, uint32_t n) { memcpy(out + pos, src, n); pos += n; }
 };
-
-struct CrcTab { uint32_t t[256]; CrcTab() { inf_crc_table(t, 0, 1); } };
 
 // the block's CRC as the kernel forms it: 64 stripes, each shifted past the bytes after it, XOR-combined
 uint32_t crc_striped(const uint8_t *d, uint32_t n) {

@@ -3,7 +3,7 @@
 //   k_gz_find     one 256-thread workgroup per nominal chunk: the lanes test consecutive bit offsets (the 13-bit header test
 //                 of gz_maybe_candidate first, the full gz_is_candidate only for the survivors, with per-lane tables in LDS);
 //                 the smallest passing offset, or GZ_NONE.
-//   k_gz_decode   one wavefront per chunk, wave-uniform like k_inflate: gz_decode from the chunk's candidate to its stop.
+//   k_gz_decode   one wavefront per chunk, wave-uniform like k_inflate (whose LDS tables and wavefront-scope loads it shares): gz_decode from the chunk's candidate to its stop.
 //                 The last 32 Ki symbols live in an LDS ring of u16 (back-references never leave LDS); every symbol also
 //                 streams to the chunk's HBM slot.
 //   k_gz_window   one workgroup walks the round's accepted chunks in order: the window of chunk k+1 is the last 32 KiB of
@@ -13,6 +13,7 @@
 //                 segment, shifted to the segment's end and XOR-combined (vector atomics) into the segment's CRC.
 #pragma once
 #include "internal.h"
+#include "k_inflate.h"
 #include "gzip_core.h"
 #include "gzip_round.h"
 
@@ -45,23 +46,20 @@ __global__ __launch_bounds__(GZ_FIND_THREADS) void k_gz_find(const u8 *__restric
 
 struct alignas(16) GzLds {
     u16 ring[GZ_WIN];
-    InfCode lt, dt, ct;
-    u8 lens[320];
+    InfLdsTabs tabs;
 };
 
-__device__ __forceinline__ u16 ld_u16_wave(const u16 *p) { return __hip_atomic_load(const_cast<u16 *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
-__device__ __forceinline__ void st_u16_wave(u16 *p, u16 v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
-
-struct GzDevEnv {
-    u32 lane, nl;
-    InfCode *lt, *dt, *ct;
-    u8 *lens;
+struct GzDevEnv : InfDevTabs {
+    static constexpr int full = GZ_E_OVERFLOW;
     u16 *ring;
     u16 *out;              // the chunk's HBM slot
     GzSeg *sp;
     u32 pos, cap;
-    __device__ void sync() { __syncthreads(); }
-    __device__ void put(u32 i, u16 v) { st_u16_wave(ring + (i & (GZ_WIN - 1)), v); out[i] = v; }
+    bool own;              // the current member started in this chunk, at symbol mstart (set by gz_decode)
+    u32 mstart;
+    __device__ GzDevEnv(GzLds &S, u32 lane_, u16 *out_, GzSeg *sp_, u32 cap_) : InfDevTabs(S.tabs, lane_), ring(S.ring), out(out_), sp(sp_), pos(0), cap(cap_) {}
+    __device__ u32 reach() const { return own ? pos - mstart : pos + GZ_WIN; }
+    __device__ void put(u32 i, u16 v) { st_wave(ring + (i & (GZ_WIN - 1)), v); out[i] = v; }
     __device__ void lit(u8 b) { if (lane == 0) put(pos, b); ++pos; }
     __device__ void copy(u32 dist, u32 len) {
         for (u32 c = 0; c < len; c += 64) {                   // len <= 258: at most 5 steps
@@ -69,7 +67,7 @@ struct GzDevEnv {
             if (j < len) {
                 // j >= dist repeats the first dist symbols: the source is always before pos (see k_inflate.h)
                 const i64 src = (i64)pos - dist + (j < dist ? j : j % dist);
-                put(pos + j, src >= 0 ? ld_u16_wave(ring + ((u32)src & (GZ_WIN - 1))) : (u16)(GZ_MARK | (u32)(GZ_WIN + src)));
+                put(pos + j, src >= 0 ? ld_wave(ring + ((u32)src & (GZ_WIN - 1))) : (u16)(GZ_MARK | (u32)(GZ_WIN + src)));
             }
         }
         pos += len;
@@ -87,11 +85,7 @@ __global__ __launch_bounds__(64) void k_gz_decode(const u8 *__restrict__ in, u32
     const u32 k = blockIdx.x, lane = threadIdx.x;
     if (k >= nt) return;
     const GzTask T = tasks[k];
-    GzDevEnv e;
-    e.lane = lane; e.nl = 64;
-    e.lt = &S.lt; e.dt = &S.dt; e.ct = &S.ct; e.lens = S.lens; e.ring = S.ring;
-    e.out = sym + T.sym_off; e.sp = seg + T.seg_off;
-    e.pos = 0; e.cap = T.cap;
+    GzDevEnv e(S, lane, sym + T.sym_off, seg + T.seg_off, T.cap);
     GzRes r;
     gz_decode(e, in, n, eof != 0, T.start, T.stop, T.seg_cap, r);
     if (lane == 0) res[k] = r;

@@ -14,35 +14,48 @@
 // one block of a chunk: offsets relative to the chunk's input / output buffers (a chunk is < 2 GiB on either side)
 struct InfBlk { u32 c_off, d_len, o_off, isize, crc; };
 
-struct alignas(16) InfLds {
-    u8 out[INF_MAX_ISIZE];
+// the code tables and code lengths of one wavefront's decoder, in LDS
+struct InfLdsTabs {
     InfCode lt, dt, ct;
-    u32 crc_tab[256];
     u8 lens[320];
 };
 
-// Loads of bytes this wavefront stored moments before (the match source): relaxed atomics of wavefront scope, the house
-// idiom of k_chain_common.h -- no hardware fence, but the compiler may not reuse or reorder them across our stores.
-__device__ __forceinline__ u8 ld_u8_wave(const u8 *p) { return __hip_atomic_load(const_cast<u8 *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
-__device__ __forceinline__ void st_u8_wave(u8 *p, u8 v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
+struct alignas(16) InfLds {
+    u8 out[INF_MAX_ISIZE];
+    InfLdsTabs tabs;
+    u32 crc_tab[256];
+};
 
-struct InfDevEnv {
+// Loads of values this wavefront stored moments before (the match source): relaxed atomics of wavefront scope, the house
+// idiom of k_chain_common.h -- no hardware fence, but the compiler may not reuse or reorder them across our stores.
+template <class T> __device__ __forceinline__ T ld_wave(const T *p) { return __hip_atomic_load(const_cast<T *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
+template <class T> __device__ __forceinline__ void st_wave(T *p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
+
+// the part of the decoder's environment (inflate_core.h) that every one-wavefront kernel shares (k_gzip.h too)
+struct InfDevTabs {
     u32 lane, nl;
     InfCode *lt, *dt, *ct;
     u8 *lens;
+    __device__ InfDevTabs(InfLdsTabs &t, u32 lane_) : lane(lane_), nl(64), lt(&t.lt), dt(&t.dt), ct(&t.ct), lens(t.lens) {}
+    __device__ void sync() { __syncthreads(); }
+};
+
+struct InfDevEnv : InfDevTabs {
+    static constexpr int full = INF_E_OUTPUT;
     u8 *out;
     u32 pos, cap;
-    __device__ void sync() { __syncthreads(); }
-    __device__ void lit(u8 b) { if (lane == 0) st_u8_wave(out + pos, b); ++pos; }
+    __device__ InfDevEnv(InfLds &S, u32 lane_, u32 cap_) : InfDevTabs(S.tabs, lane_), out(S.out), pos(0), cap(cap_) {}
+    __device__ u32 reach() const { return pos; }             // a distance may not reach before the block's first byte
+    __device__ void lit(u8 b) { if (lane == 0) st_wave(out + pos, b); ++pos; }
     __device__ void copy(u32 dist, u32 len) {
         for (u32 c = 0; c < len; c += 64) {                   // len <= 258: at most 5 steps
             const u32 j = c + lane;
-            if (j < len) st_u8_wave(out + pos + j, ld_u8_wave(out + pos - dist + (j < dist ? j : j % dist)));
+            if (j < len) st_wave(out + pos + j, ld_wave(out + pos - dist + (j < dist ? j : j % dist)));
         }
         pos += len;
     }
     __device__ void stored(const u8 *src, u32 n) {
-        for (u32 j = lane; j < n; j += 64) st_u8_wave(out + pos + j, src[j]);
+        for (u32 j = lane; j < n; j += 64) st_wave(out + pos + j, src[j]);
         pos += n;
     }
 };
@@ -54,12 +67,9 @@ __global__ __launch_bounds__(64) void k_inflate(const u8 *__restrict__ in, const
     if (b >= n_blk) return;
     inf_crc_table(S.crc_tab, lane, 64);
     const InfBlk B = blk[b];
-    InfDevEnv e;
-    e.lane = lane; e.nl = 64;
-    e.lt = &S.lt; e.dt = &S.dt; e.ct = &S.ct; e.lens = S.lens; e.out = S.out;
-    e.pos = 0; e.cap = B.isize <= INF_MAX_ISIZE ? B.isize : INF_MAX_ISIZE;     // (the host scan guarantees <=)
+    InfDevEnv e(S, lane, B.isize <= INF_MAX_ISIZE ? B.isize : INF_MAX_ISIZE);     // (the host scan guarantees <=)
     __syncthreads();
-    int rc = inf_raw(e, in, B.c_off, B.c_off + B.d_len);
+    int rc = inf_raw(e, in + B.c_off, 0, B.d_len);              // block-relative: bit offsets stay far below 2^32
     if (B.isize > INF_MAX_ISIZE) rc = INF_E_OUTPUT;
     __syncthreads();
     if (!rc) {
