@@ -47,6 +47,7 @@ extern "C" {
 #define LRGE_ERR_DUPLICATE_ID  -7  /* DuplicateReadIdentifier (ava.rs:195-199, twoset.rs:439-449) */
 #define LRGE_ERR_PAF_WRITE     -8  /* PafWriteError */
 #define LRGE_ERR_INVALID       -9  /* bad argument (no reference equivalent: would not compile in Rust) */
+#define LRGE_ERR_UNPROVEN -10   /* the device cannot prove this input: take lrge_hip_read_records* (no reference equivalent) */
 
 #define LRGE_PRESET_AVA_ONT 0   /* Preset::AvaOnt, "-k15 -Xw5 -e0 -m100 -r2k" (preset.rs:26) */
 #define LRGE_PRESET_AVA_PB  1   /* Preset::AvaPb,  "-Hk19 -Xw5 -e0 -m100"     (preset.rs:24) */
@@ -396,6 +397,40 @@ int  lrge_hip_gzip_inflate(lrge_hip_ctx *ctx, const void *comp, uint64_t comp_le
 int  lrge_hip_read_records_gpu_ex(lrge_hip_ctx *ctx, const char *path, int flags,
                                   void (*cb)(void *user, const char *name, uint64_t name_len, const char *bases, uint64_t n_bases),
                                   void *user, int *used_device);
+
+/* Read sets built on the device from FASTA / FASTQ text (k_fx_census, k_fx_summary, k_fx_scatter, k_fx_records,
+   k_fx_names, k_fx_gather): the device-side form of the record reader (io.rs:154-184) and of the read selection that feeds the
+   strategies (twoset.rs:122-201).  The file's bytes are decompressed into HBM and stay there; the records are found there; only
+   the identifiers and the sequence lengths come back.
+   lrge_hip_reads_open (io.rs:154-184) reads `path` into memory and calls lrge_hip_reads_open_mem (io.rs:154-184), which takes the
+   bytes of a whole file.  `flags`: LRGE_GPU_INFLATE_BGZF | LRGE_GPU_INFLATE_GZIP choose the device decoders as in
+   lrge_hip_read_records_gpu_ex; with neither, only uncompressed input is taken.  The records equal those of lrge_hip_read_records
+   on the same file, one for one.  LRGE_ERR_UNPROVEN: the device does not prove this input and produces no parse error of its
+   own -- anything but FASTA or strict four-line FASTQ (an empty line between records, a truncated record, a missing '+', SAM,
+   BAM, CRAM), a compressed format without its flag or other than gzip, a damaged gzip file, text above option INGEST_MAX_BYTES
+   (default: half of the free device memory plus the context's idle arena bytes); the caller takes lrge_hip_read_records*, which
+   parses the file or gives the reference's message.  LRGE_ERR_TOO_MANY: 2^32 records or more, or a sequence of 2^32 bases or
+   more.  LRGE_ERR_IO: the file cannot be read.  An empty file is LRGE_OK with a count of 0.
+   lrge_hip_reads_count / _name_bytes / _text_bytes (io.rs:154-184): records, total identifier bytes, decompressed bytes.
+   lrge_hip_reads_table (io.rs:154-184): seq_len[n], name_off[n + 1] and the identifiers back to back in names[name_bytes]
+   (identifier i is names[name_off[i], name_off[i + 1]); any of the three may be NULL).
+   lrge_hip_reads_timings (io.rs:154-184): milliseconds of the open call -- text to HBM, record scan, identifiers and lengths to the
+   host, total.
+   lrge_hip_seqset_from_reads (twoset.rs:122-201): reads idx[0..n) of `reads`, in that order (any order, repeats allowed; an entry
+   out of range is LRGE_ERR_INVALID), as an ordinary read set: their bases are gathered on the device and packed by the
+   device-source path of lrge_hip_seqset_upload, so the set is bit-identical to an upload of the same sequences.  name_rank as
+   there.  The handle must outlive the call only; lrge_hip_reads_free (io.rs:154-184) releases the text. */
+typedef struct lrge_hip_reads lrge_hip_reads;
+int      lrge_hip_reads_open(lrge_hip_ctx *ctx, const char *path, int flags, lrge_hip_reads **out);
+int      lrge_hip_reads_open_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, int flags, lrge_hip_reads **out);
+uint64_t lrge_hip_reads_count(const lrge_hip_reads *reads);
+uint64_t lrge_hip_reads_name_bytes(const lrge_hip_reads *reads);
+uint64_t lrge_hip_reads_text_bytes(const lrge_hip_reads *reads);
+int      lrge_hip_reads_table(const lrge_hip_reads *reads, uint32_t *seq_len, uint64_t *name_off, char *names);
+int      lrge_hip_reads_timings(const lrge_hip_reads *reads, float ms[4]);
+int      lrge_hip_seqset_from_reads(lrge_hip_ctx *ctx, const lrge_hip_reads *reads, const uint32_t *idx, uint32_t n,
+                                    const uint32_t *name_rank, lrge_hip_seqset **out);
+void     lrge_hip_reads_free(lrge_hip_reads *reads);
 
 /* Host only: which side packs the reads of a set that starts in host memory when `ranks_on_host` ranks share this host's CPUs (option
    LRGE_HIP_RANKS_ON_HOST, set by the launcher; LRGE_HIP_PACK = host | device overrides): 1 = the host (2-bit pack with AVX2, packed words

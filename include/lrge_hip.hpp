@@ -73,10 +73,51 @@ struct Ctx {
     ~Ctx() { lrge_hip_ctx_destroy(h); }
     void check(int rc) const { if (rc) throw LrgeError(rc, lrge_hip_last_error(h)); }
 };
+}  // namespace detail
+
+// The records of one FASTA / FASTQ file parsed on the device (lrge_hip_reads_open, io.rs:154-184): identifiers and lengths on
+// the host, the bases resident in HBM as text.  Owns its context; the strategies built on it run in that context and take
+// their read sets with lrge_hip_seqset_from_reads.  open() gives nullptr for input the device does not prove (and for a file
+// it cannot read): the caller parses the file into a Reads with io::iter_records, which reports whatever is wrong with it.
+struct DeviceReads {
+    std::shared_ptr<detail::Ctx> ctx;
+    lrge_hip_reads *h = nullptr;
+    std::vector<std::string> names;
+    std::vector<uint32_t> lens;
+    DeviceReads() = default;
+    DeviceReads(const DeviceReads &) = delete;
+    DeviceReads &operator=(const DeviceReads &) = delete;
+    ~DeviceReads() { lrge_hip_reads_free(h); }
+    static std::unique_ptr<DeviceReads> open(const std::string &path, int flags = LRGE_GPU_INFLATE_BGZF | LRGE_GPU_INFLATE_GZIP, int device = 0) {
+        auto r = std::make_unique<DeviceReads>();
+        r->ctx = std::make_shared<detail::Ctx>(device);
+        const int rc = lrge_hip_reads_open(r->ctx->h, path.c_str(), flags, &r->h);
+        if (rc == LRGE_ERR_UNPROVEN || rc == LRGE_ERR_IO) return nullptr;
+        r->ctx->check(rc);
+        const uint64_t n = lrge_hip_reads_count(r->h);
+        std::vector<uint64_t> off(n + 1);
+        std::string blob(lrge_hip_reads_name_bytes(r->h), '\0');
+        r->lens.resize(n);
+        r->ctx->check(lrge_hip_reads_table(r->h, r->lens.data(), off.data(), blob.empty() ? nullptr : &blob[0]));
+        r->names.reserve(n);
+        for (uint64_t i = 0; i < n; ++i) r->names.emplace_back(blob, off[i], off[i + 1] - off[i]);
+        return r;
+    }
+};
+
+namespace detail {
 struct SeqSet {
     lrge_hip_seqset *h = nullptr;
     std::vector<uint32_t> lens;
-    SeqSet(const Ctx &c, const std::vector<const std::string *> &seqs, const std::vector<uint32_t> &ranks) {
+    // reads idx of a DeviceReads (dev != nullptr), or the given host sequences
+    SeqSet(const Ctx &c, const DeviceReads *dev, const std::vector<size_t> &idx, const std::vector<const std::string *> &seqs, const std::vector<uint32_t> &ranks) {
+        if (!dev) { upload(c, seqs, ranks); return; }
+        std::vector<uint32_t> ix(idx.begin(), idx.end());
+        for (uint32_t i : ix) lens.push_back(dev->lens[i]);
+        c.check(lrge_hip_seqset_from_reads(c.h, dev->h, ix.data(), (uint32_t)ix.size(), ranks.data(), &h));
+    }
+    SeqSet(const Ctx &c, const std::vector<const std::string *> &seqs, const std::vector<uint32_t> &ranks) { upload(c, seqs, ranks); }
+    void upload(const Ctx &c, const std::vector<const std::string *> &seqs, const std::vector<uint32_t> &ranks) {
         std::vector<uint64_t> off(seqs.size() + 1, 0);
         for (size_t i = 0; i < seqs.size(); ++i) { off[i + 1] = off[i] + seqs[i]->size(); lens.push_back((uint32_t)seqs[i]->size()); }
         std::string cat; cat.reserve(off.back());
@@ -158,7 +199,8 @@ constexpr size_t DEFAULT_TARGET_NUM_READS = 10000, DEFAULT_QUERY_NUM_READS = 500
 
 class TwoSetStrategy : public Estimate {
 public:
-    const Reads *input;
+    const Reads *input = nullptr;
+    const DeviceReads *dev_input = nullptr;   // set instead of `input`: the strategy runs in the reads' own context (`device` is not used)
     size_t target_num_reads = DEFAULT_TARGET_NUM_READS, query_num_reads = DEFAULT_QUERY_NUM_READS;
     size_t target_num_bases = 0, query_num_bases = 0;
     bool remove_internal = false, use_min_ref = false;
@@ -171,10 +213,13 @@ public:
     std::vector<std::string> *paf_sink = nullptr;   // when set, receives the lines of overlaps.paf (the reference always writes it)
 
     explicit TwoSetStrategy(const Reads &r) : input(&r) {}
+    explicit TwoSetStrategy(const DeviceReads &r) : dev_input(&r) {}
+    const std::vector<std::string> &names_in() const { return dev_input ? dev_input->names : input->names; }
+    size_t len_in(size_t i) const { return dev_input ? dev_input->lens[i] : input->seqs[i].size(); }
 
     // twoset.rs:122-201
     std::tuple<std::vector<size_t>, std::vector<size_t>, float> split_fastq() {
-        const size_t n = input->names.size();
+        const size_t n = names_in().size();
         if (n > 0xFFFFFFFFull) throw LrgeError(LRGE_ERR_TOO_MANY, "Number of reads in input file exceeds maximum allowed value");
         size_t n_req = target_num_reads + query_num_reads;
         if (n <= query_num_reads)
@@ -193,8 +238,8 @@ public:
             qset(idx.begin(), idx.end() - (std::ptrdiff_t)target_num_reads);
         std::vector<size_t> t, q;
         for (size_t i = 0; i < n; ++i) {   // file order, like iter_records
-            if (tset.count((uint32_t)i)) { t.push_back(i); target_num_bases += input->seqs[i].size(); }
-            else if (qset.count((uint32_t)i)) { q.push_back(i); query_num_bases += input->seqs[i].size(); }
+            if (tset.count((uint32_t)i)) { t.push_back(i); target_num_bases += len_in(i); }
+            else if (qset.count((uint32_t)i)) { q.push_back(i); query_num_bases += len_in(i); }
         }
         const float avg_target_len = (float)target_num_bases / (float)target_num_reads;
         return {t, q, avg_target_len};
@@ -204,11 +249,12 @@ public:
     std::pair<std::vector<float>, uint32_t> generate_estimates() override {
         auto [t, q, avg_target_len] = split_fastq();
         std::vector<const std::string *> tn, ts, qn, qs;
-        for (size_t i : t) { tn.push_back(&input->names[i]); ts.push_back(&input->seqs[i]); }
-        for (size_t i : q) { qn.push_back(&input->names[i]); qs.push_back(&input->seqs[i]); }
+        for (size_t i : t) { tn.push_back(&names_in()[i]); if (input) ts.push_back(&input->seqs[i]); }
+        for (size_t i : q) { qn.push_back(&names_in()[i]); if (input) qs.push_back(&input->seqs[i]); }
         auto ranks = detail::name_ranks({qn, tn});
-        detail::Ctx ctx(device);
-        detail::SeqSet Q(ctx, qs, ranks[0]), T(ctx, ts, ranks[1]);
+        std::shared_ptr<detail::Ctx> ctx_own = dev_input ? dev_input->ctx : std::make_shared<detail::Ctx>(device);
+        detail::Ctx &ctx = *ctx_own;
+        detail::SeqSet Q(ctx, dev_input, q, qs, ranks[0]), T(ctx, dev_input, t, ts, ranks[1]);
         const int preset = platform == Platform::PacBio ? LRGE_PRESET_AVA_PB : LRGE_PRESET_AVA_ONT;
         lrge_hip_params p{remove_internal ? 1 : 0, max_overhang_ratio};
         std::vector<uint32_t> counts(Q.lens.size()), has(Q.lens.size());
@@ -249,8 +295,9 @@ public:
     Builder &seed(std::optional<uint64_t> s) { seed_ = s; return *this; }
     Builder &platform(Platform p) { platform_ = p; return *this; }
     Builder &device(int d) { device_ = d; return *this; }
-    TwoSetStrategy build(const Reads &input) const {
-        TwoSetStrategy s(input);
+    TwoSetStrategy build(const Reads &input) const { return configure(TwoSetStrategy(input)); }
+    TwoSetStrategy build(const DeviceReads &input) const { return configure(TwoSetStrategy(input)); }
+    TwoSetStrategy configure(TwoSetStrategy s) const {
         s.target_num_reads = t_; s.query_num_reads = q_; s.remove_internal = remove_internal_; s.max_overhang_ratio = ratio_;
         s.use_min_ref = use_min_ref_; s.threads = threads_; s.seed = seed_; s.platform = platform_; s.device = device_;
         return s;
@@ -266,7 +313,8 @@ constexpr size_t DEFAULT_AVA_NUM_READS = 25000;   // ava.rs:62
 
 class AvaStrategy : public Estimate {
 public:
-    const Reads *input;
+    const Reads *input = nullptr;
+    const DeviceReads *dev_input = nullptr;   // as TwoSetStrategy::dev_input
     size_t num_reads = DEFAULT_AVA_NUM_READS, num_bases = 0, threads = 1;
     bool remove_internal = false;
     float max_overhang_ratio = 0.2f;
@@ -277,10 +325,12 @@ public:
     std::vector<std::string> *paf_sink = nullptr;
 
     explicit AvaStrategy(const Reads &r) : input(&r) {}
+    explicit AvaStrategy(const DeviceReads &r) : dev_input(&r) {}
 
     std::pair<std::vector<float>, uint32_t> generate_estimates() override {
         // ava.rs:108-161
-        const size_t n = input->names.size();
+        const std::vector<std::string> &names = dev_input ? dev_input->names : input->names;
+        const size_t n = names.size();
         if (n > 0xFFFFFFFFull) throw LrgeError(LRGE_ERR_TOO_MANY, "Number of reads in input file exceeds maximum allowed value");
         if (n < num_reads) {
             warnings.push_back("Number of reads in input file (" + std::to_string(n) + ") is less than the number requested (" +
@@ -290,11 +340,17 @@ public:
         auto idx = detail::unique_random_set(num_reads, (uint32_t)n, seed);
         std::unordered_set<uint32_t> keep(idx.begin(), idx.end());
         std::vector<const std::string *> rn, rs;
-        for (size_t i = 0; i < n; ++i) if (keep.count((uint32_t)i)) { rn.push_back(&input->names[i]); rs.push_back(&input->seqs[i]); num_bases += input->seqs[i].size(); }
+        std::vector<size_t> ri;
+        for (size_t i = 0; i < n; ++i) if (keep.count((uint32_t)i)) {
+            rn.push_back(&names[i]); ri.push_back(i);
+            if (input) rs.push_back(&input->seqs[i]);
+            num_bases += dev_input ? dev_input->lens[i] : input->seqs[i].size();
+        }
         // ava.rs:369-382 + :165-366
         auto ranks = detail::name_ranks({rn});
-        detail::Ctx ctx(device);
-        detail::SeqSet R(ctx, rs, ranks[0]);
+        std::shared_ptr<detail::Ctx> ctx_own = dev_input ? dev_input->ctx : std::make_shared<detail::Ctx>(device);
+        detail::Ctx &ctx = *ctx_own;
+        detail::SeqSet R(ctx, dev_input, ri, rs, ranks[0]);
         const int preset = platform == Platform::PacBio ? LRGE_PRESET_AVA_PB : LRGE_PRESET_AVA_ONT;
         ctx.check(lrge_hip_seqset_presketch(ctx.h, R.h, preset));
         detail::Index ix(ctx, R, preset);
@@ -326,8 +382,9 @@ public:
     Builder &seed(std::optional<uint64_t> s) { seed_ = s; return *this; }
     Builder &platform(Platform p) { platform_ = p; return *this; }
     Builder &device(int d) { device_ = d; return *this; }
-    AvaStrategy build(const Reads &input) const {
-        AvaStrategy s(input);
+    AvaStrategy build(const Reads &input) const { return configure(AvaStrategy(input)); }
+    AvaStrategy build(const DeviceReads &input) const { return configure(AvaStrategy(input)); }
+    AvaStrategy configure(AvaStrategy s) const {
         s.num_reads = n_; s.remove_internal = remove_internal_; s.max_overhang_ratio = ratio_; s.threads = threads_;
         s.seed = seed_; s.platform = platform_; s.device = device_;
         return s;

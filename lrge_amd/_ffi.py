@@ -10,6 +10,8 @@ from .build import LIB_PATH
 OK = 0
 ERR_IO, ERR_PARSE, ERR_TOO_MANY, ERR_TOO_FEW, ERR_DEVICE, ERR_MAP, ERR_DUPLICATE_ID, ERR_PAF_WRITE, ERR_INVALID = \
     -1, -2, -3, -4, -5, -6, -7, -8, -9
+ERR_UNPROVEN = -10
+GPU_INFLATE_BGZF, GPU_INFLATE_GZIP = 1, 2
 PRESET_AVA_ONT, PRESET_AVA_PB = 0, 1
 
 T_NAMES = ["pack", "sketch", "index_sort", "index_table", "qfilter", "lookup", "expand", "anchor_sort", "group",
@@ -27,6 +29,8 @@ EXPORTS = [
     "lrge_hip_host_free", "lrge_hip_seqset_free", "lrge_hip_seqset_size", "lrge_hip_seqset_presketch", "lrge_hip_seqset_presketch_sharded", "lrge_hip_pack_choice", "lrge_hip_read_records",
     "lrge_hip_bgzf_scan", "lrge_hip_bgzf_inflate", "lrge_hip_read_records_gpu",
     "lrge_hip_gzip_inflate", "lrge_hip_read_records_gpu_ex",
+    "lrge_hip_reads_open", "lrge_hip_reads_open_mem", "lrge_hip_reads_count", "lrge_hip_reads_name_bytes", "lrge_hip_reads_text_bytes",
+    "lrge_hip_reads_table", "lrge_hip_reads_timings", "lrge_hip_seqset_from_reads", "lrge_hip_reads_free",
     "lrge_hip_index_build", "lrge_hip_index_build_for", "lrge_hip_index_build_sharded", "lrge_hip_index_build_tsharded", "lrge_hip_last_shard_stats", "lrge_hip_index_free",
     "lrge_hip_comm_alltoallv", "lrge_hip_comm_rccl_ranks", "lrge_hip_comm_rccl_ops", "lrge_hip_comm_local_group_serialize", "lrge_hip_comm_local_turn",
     "lrge_hip_comm_busy_ms", "lrge_hip_comm_standin_ms",
@@ -56,6 +60,10 @@ class LrgeHipError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("lrge_hip error %d: %s" % (code, msg))
         self.code = code
+
+
+class UnprovenInput(LrgeHipError):
+    """LRGE_ERR_UNPROVEN: the device does not prove this input (Context.open_reads); the host readers take it."""
 
 
 def lib():
@@ -91,6 +99,15 @@ def lib():
     L.lrge_hip_bgzf_scan.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.lrge_hip_bgzf_inflate.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64]
     L.lrge_hip_gzip_inflate.argtypes = [vp, vp, C.c_uint64, GZIP_SINK, vp, vp]
+    L.lrge_hip_reads_open.argtypes = [vp, C.c_char_p, C.c_int, C.POINTER(vp)]
+    L.lrge_hip_reads_open_mem.argtypes = [vp, vp, C.c_uint64, C.c_int, C.POINTER(vp)]
+    for f in (L.lrge_hip_reads_count, L.lrge_hip_reads_name_bytes, L.lrge_hip_reads_text_bytes):
+        f.argtypes, f.restype = [vp], C.c_uint64
+    L.lrge_hip_reads_table.argtypes = [vp, vp, vp, vp]
+    L.lrge_hip_reads_timings.argtypes = [vp, C.POINTER(C.c_float * 4)]
+    L.lrge_hip_seqset_from_reads.argtypes = [vp, vp, vp, C.c_uint32, vp, C.POINTER(vp)]
+    L.lrge_hip_reads_free.argtypes = [vp]
+    L.lrge_hip_reads_free.restype = None
     L.lrge_hip_pack_choice.argtypes = [C.c_int, C.POINTER(C.c_double)]
     L.lrge_hip_seqset_presketch_sharded.argtypes = [vp, vp, C.c_int, vp]
     L.lrge_hip_index_build.argtypes = [vp, vp, C.c_int, C.POINTER(vp)]

@@ -44,9 +44,10 @@ TWIN_PATH = os.path.join(LIB_DIR, "liblrge_inflate_twin.so")
 
 def build_twin(force=False):
     """The host twins (g++), for the CPU suite: of k_inflate (csrc/inflate_twin.cpp, the same bit-level core), and of the
-    speculative gzip decode (build_gzip_twin)."""
+    speculative gzip decode (build_gzip_twin), and of the FASTA / FASTQ record scan (build_fastx_twin)."""
     os.makedirs(LIB_DIR, exist_ok=True)
     build_gzip_twin(force)
+    build_fastx_twin(force)
     srcs = [os.path.join(CSRC, f) for f in ("inflate_twin.cpp", "inflate_core.h", "bgzf_scan.h", "twin_env.h")]
     if not force and os.path.exists(TWIN_PATH) and os.path.getmtime(TWIN_PATH) >= _newest(srcs):
         return TWIN_PATH
@@ -65,6 +66,19 @@ def build_gzip_twin(force=False):
         return GZIP_TWIN_PATH
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-fPIC", "-shared", "-o", GZIP_TWIN_PATH, srcs[0]])
     return GZIP_TWIN_PATH
+
+
+FASTX_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_fastx_twin.so")
+
+
+def build_fastx_twin(force=False):
+    """The host twin of the device record scan (csrc/fastx_twin.cpp, g++): the same core and passes, for the CPU suite."""
+    os.makedirs(LIB_DIR, exist_ok=True)
+    srcs = [os.path.join(CSRC, f) for f in ("fastx_twin.cpp", "fastx_core.h")]
+    if not force and os.path.exists(FASTX_TWIN_PATH) and os.path.getmtime(FASTX_TWIN_PATH) >= _newest(srcs):
+        return FASTX_TWIN_PATH
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-fPIC", "-shared", "-o", FASTX_TWIN_PATH, srcs[0]])
+    return FASTX_TWIN_PATH
 
 
 CLI_PATH = os.path.join(LIB_DIR, "lrge-hip")

@@ -53,6 +53,7 @@ struct GzDev {
     ~GzDev() {
         (void)hipStreamSynchronize(ctx->copy_stream); (void)hipStreamSynchronize(ctx->stream2); (void)hipStreamSynchronize(ctx->stream);
         drop_big();
+        ctx->pool.release(keep);
         if (ev_in) (void)hipEventDestroy(ev_in);
         if (ev_out) (void)hipEventDestroy(ev_out);
     }
@@ -62,6 +63,24 @@ struct GzDev {
         big_sym.clear(); big_seg.clear(); big_ptr.clear();
     }
     bool ok(hipError_t x) { if (x != hipSuccess && e == hipSuccess) e = x; return e == hipSuccess; }
+    // keep_on (host_fastx.inl): every round's bytes are appended to one pool block on the device instead of travelling to the host.
+    // The block grows geometrically (a device-to-device copy on the main stream; the pool recycles in that stream's order); more than
+    // keep_max bytes stops the call with keep_over set.  The bytes count only when the call as a whole returns OK.
+    bool keep_on = false, keep_over = false;
+    u8 *keep = nullptr;
+    u64 keep_len = 0, keep_cap = 0, keep_max = 0, keep_hint = 0, keep_slack = 0;
+    bool keep_reserve(u64 more) {
+        const u64 need = keep_len + more;
+        if (need > keep_max) { keep_over = true; return false; }
+        if (keep && need <= keep_cap) return true;
+        const u64 cap = std::min<u64>(keep_max, std::max<u64>(std::max<u64>(need, keep_hint), std::max<u64>(2 * keep_cap, (u64)1 << 20)));
+        u8 *p = (u8 *)ctx->pool.alloc((size_t)(cap + keep_slack), &e);
+        if (!p) return false;
+        if (keep_len && !ok(hipMemcpyAsync(p, keep, (size_t)keep_len, hipMemcpyDeviceToDevice, ctx->stream))) { ctx->pool.release(p); return false; }
+        ctx->pool.release(keep);
+        keep = p; keep_cap = cap;
+        return true;
+    }
     bool sync() { return ok(hipStreamSynchronize(ctx->stream)); }
 
     // the round's input: two device slots, the next round staged through pinned memory on the copy stream while this one decodes
@@ -147,8 +166,8 @@ struct GzDev {
             !seg_crc.need(std::max<size_t>(1, ns) * 4, &e) || !err.need(4, &e) || !out.need(std::max<u64>(1, out_bytes), &e) ||
             !bigtab.need(std::max<size_t>(1, big_ptr.size()) * sizeof(void *), &e))
             return false;
-        u8 *h_out = ctx_pin(1, std::max<u64>(1, out_bytes));
-        if (!h_out) return false;
+        u8 *h_out = keep_on ? nullptr : ctx_pin(1, std::max<u64>(1, out_bytes));
+        if (!h_out && !keep_on) return false;
         hipStream_t st = ctx->stream;
         if (!ok(hipMemcpyAsync(links.p, l, (size_t)nl * sizeof(GzLink), hipMemcpyHostToDevice, st))) return false;
         if (!tl.empty() && !ok(hipMemcpyAsync(tiles.p, tl.data(), tl.size() * sizeof(GzTile), hipMemcpyHostToDevice, st))) return false;
@@ -166,14 +185,19 @@ struct GzDev {
         }
         if (ns && !ok(hipMemcpyAsync(seg_crc_h, seg_crc.p, (size_t)ns * 4, hipMemcpyDeviceToHost, st))) return false;
         if (!ok(hipMemcpyAsync(marker_err, err.p, 4, hipMemcpyDeviceToHost, st))) return false;
+        if (keep_on) {                                           // the round's bytes stay in HBM, behind what the earlier rounds left
+            if (!keep_reserve(out_bytes)) return false;
+            if (out_bytes && !ok(hipMemcpyAsync(keep + keep_len, out.p, out_bytes, hipMemcpyDeviceToDevice, st))) return false;
+            keep_len += out_bytes;
+        }
         // the bytes travel on the side stream while the next round is staged and decoded (bytes_ready waits for them)
         if (!ok(hipEventRecord(ev_out, st)) || !ok(hipStreamWaitEvent(ctx->stream2, ev_out, 0))) return false;
-        if (out_bytes && !ok(hipMemcpyAsync(h_out, out.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream2))) return false;
+        if (!keep_on && out_bytes && !ok(hipMemcpyAsync(h_out, out.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream2))) return false;
         if (!ok(hipEventRecord(ev_out, ctx->stream2))) return false;
         if (!sync()) return false;
         if (*marker_err == 0xFFFFFFFFu) *marker_err = 0;
         drop_big();
-        *bytes = h_out;
+        *bytes = keep_on ? keep : h_out;
         return true;
     }
 };

@@ -28,6 +28,7 @@
 #include "k_inflate.h"
 #include "bgzf_scan.h"
 #include "k_gzip.h"
+#include "k_fastx.h"
 #include "../../include/lrge_rand.hpp"
 #include "../../include/lrge_io.hpp"
 
@@ -225,3 +226,4 @@ extern "C" int lrge_hip_last_counters(const lrge_hip_ctx *ctx, uint64_t c[LRGE_C
 #include "host_estimate.inl"
 #include "host_inflate.inl"
 #include "host_gzip.inl"
+#include "host_fastx.inl"

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._ffi import LrgeHipError, Params
+from ._ffi import LrgeHipError, Params, UnprovenInput
 
 
 def name_ranks(*name_lists):
@@ -93,6 +93,12 @@ class Context:
             return out
         keys = ("members", "chunks", "speculative_starts", "rejected_starts", "redecoded_chunks", "overflow_retries", "bytes_out")
         return out, dict(zip(keys, list(st)))
+
+    def open_reads(self, path_or_bytes, flags=_ffi.GPU_INFLATE_BGZF | _ffi.GPU_INFLATE_GZIP):
+        """A FASTA / FASTQ file (a path, or the bytes of the whole file) parsed on the device: plain, BGZF or any other gzip,
+        by `flags` (lrge_hip_reads_open*).  Returns a DeviceReads with names, lens and seqset().  Input the device does not
+        prove raises UnprovenInput: read the file with the host readers (readio.load) instead."""
+        return DeviceReads(self, path_or_bytes, flags)
 
     def set_timer_level(self, level):
         """0 = call total + chain stage only, 1 = every stage, 2 (default) = also every k_rs_scatter launch."""
@@ -225,6 +231,71 @@ class SeqSet:
         self.ctx._check(self.ctx._lib.lrge_hip_sketch_dump(self.ctx.h, self.h, preset, x.ctypes.data, y.ctypes.data,
                                                            n.value, C.byref(n)))
         return x[:n.value], y[:n.value]
+
+
+class DeviceReads:
+    """The reads of one input file resident in HBM as text (lrge_hip_reads): `names` (list of bytes) and `lens` (uint32) are
+    on the host, the bases never are.  seqset(idx, ranks) is an ordinary SeqSet of the chosen reads."""
+
+    def __init__(self, ctx, src, flags):
+        self.ctx, self.h = ctx, None
+        h = C.c_void_p()
+        L = ctx._lib
+        if isinstance(src, (bytes, bytearray, memoryview, np.ndarray)):
+            buf = np.frombuffer(src, dtype=np.uint8) if not isinstance(src, np.ndarray) else np.ascontiguousarray(src, dtype=np.uint8)
+            rc = L.lrge_hip_reads_open_mem(ctx.h, buf.ctypes.data if buf.size else None, buf.size, int(flags), C.byref(h))
+        else:
+            import os
+            rc = L.lrge_hip_reads_open(ctx.h, os.fsencode(str(src)), int(flags), C.byref(h))
+        if rc == _ffi.ERR_UNPROVEN:
+            raise UnprovenInput(rc, L.lrge_hip_last_error(ctx.h).decode())
+        ctx._check(rc)
+        self.h = h
+        self.n = int(L.lrge_hip_reads_count(h))
+        self.text_bytes = int(L.lrge_hip_reads_text_bytes(h))
+        nb = int(L.lrge_hip_reads_name_bytes(h))
+        self.lens = np.zeros(self.n, dtype=np.uint32)
+        self.name_off = np.zeros(self.n + 1, dtype=np.uint64)
+        blob = C.create_string_buffer(max(1, nb))
+        ctx._check(L.lrge_hip_reads_table(h, self.lens.ctypes.data if self.n else None, self.name_off.ctypes.data, blob))
+        self._blob = blob.raw[:nb]
+        self._names = None
+
+    @property
+    def names(self):
+        if self._names is None:
+            o = self.name_off.tolist()
+            self._names = [self._blob[o[i]:o[i + 1]] for i in range(self.n)]
+        return self._names
+
+    def timings(self):
+        """milliseconds of the open call: text to HBM, record scan, identifiers and lengths to the host, total"""
+        a = (C.c_float * 4)()
+        self.ctx._check(self.ctx._lib.lrge_hip_reads_timings(self.h, C.byref(a)))
+        return dict(zip(("text", "scan", "names", "total"), [float(x) for x in a]))
+
+    def seqset(self, idx, ranks=None):
+        """reads idx (any order, repeats allowed) as a SeqSet; ranks as Context.upload"""
+        idx = np.ascontiguousarray(idx, dtype=np.uint32)
+        r = None if ranks is None else np.ascontiguousarray(ranks, dtype=np.uint32)
+        h = C.c_void_p()
+        self.ctx._check(self.ctx._lib.lrge_hip_seqset_from_reads(self.ctx.h, self.h, idx.ctypes.data if idx.size else None, idx.size,
+                                                                 None if r is None else r.ctypes.data, C.byref(h)))
+        s = SeqSet.__new__(SeqSet)
+        s.ctx, s.h, s.n, s._src = self.ctx, h, int(idx.size), None
+        s._offsets, s._lens = None, self.lens[idx] if idx.size else np.zeros(0, dtype=np.uint32)
+        return s
+
+    def free(self):
+        if getattr(self, "h", None):
+            self.ctx._lib.lrge_hip_reads_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 class Index:

@@ -59,7 +59,7 @@ int main(int argc, char **argv) {
     bool T_set = false, Q_set = false, filter = false, with_inf = false, precise = false, use_min_ref = false, honour_platform = false;
     float q1 = lrge::LOWER_QUANTILE, q3 = lrge::UPPER_QUANTILE, ratio = 0.2f;
     size_t threads = 1; std::optional<uint64_t> seed; int quiet = 0, verbose = 0, device = 0;
-    bool keep_temp = false, dump_records = false, gpu_inflate = false, gpu_gzip = false; std::string temp_dir;
+    bool keep_temp = false, dump_records = false, gpu_inflate = false, gpu_gzip = false, gpu_ingest = false; std::string temp_dir;
     auto need = [&](int &i) -> const char * { if (i + 1 >= argc) { fprintf(stderr, "error: missing value for %s\n", argv[i]); exit(2); } return argv[++i]; };
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -83,6 +83,7 @@ int main(int argc, char **argv) {
         else if (a == "--device") device = atoi(need(i));
         else if (a == "--gpu-inflate") gpu_inflate = true;       // BGZF input (BAM, bgzip FASTQ) decompressed on --device
         else if (a == "--gpu-gzip") gpu_gzip = true;             // every gzip input (plain, multi-member, BGZF) decompressed on --device
+        else if (a == "--gpu-ingest") { gpu_ingest = true; gpu_gzip = true; }   // FASTA / FASTQ parsed on --device too: the bases never reach host memory (implies --gpu-gzip)
         else if (a == "--dump-records") dump_records = true;   // host-only: print "id<TAB>sequence" per record and exit (tests)
         else if (a == "-q" || a == "--quiet") ++quiet; else if (a == "-qq") quiet += 2; else if (a == "-qqq") quiet += 3;
         else if (a == "-v" || a == "--verbose") ++verbose; else if (a == "-vv") verbose += 2;
@@ -101,18 +102,29 @@ int main(int argc, char **argv) {
             fprintf(stderr, "%zu records\n", n);
             return 0;
         }
-        lrge::Reads reads = load_reads(input, gpu_inflate, gpu_gzip, device);
+        // --gpu-ingest: input the device does not prove takes the usual route below, which parses it or reports it
+        std::unique_ptr<lrge::DeviceReads> dev;
+        if (gpu_ingest) {
+            dev = lrge::DeviceReads::open(input, LRGE_GPU_INFLATE_BGZF | LRGE_GPU_INFLATE_GZIP, device);
+            if (info) fprintf(stderr, "[INFO] gpu-ingest: %s\n", dev ? "device" : "host");
+            if (dev && dev->names.empty()) throw lrge::LrgeError(LRGE_ERR_IO, "IO error: Is the file empty?");
+        }
+        lrge::Reads reads;
+        if (!dev) reads = load_reads(input, gpu_inflate, gpu_gzip, device);
         const lrge::Platform pf = (honour_platform && platform == "pb") ? lrge::Platform::PacBio : lrge::Platform::Nanopore;
-        lrge::twoset::TwoSetStrategy ts(reads); lrge::ava::AvaStrategy as(reads);
+        lrge::twoset::TwoSetStrategy ts = dev ? lrge::twoset::TwoSetStrategy(*dev) : lrge::twoset::TwoSetStrategy(reads);
+        lrge::ava::AvaStrategy as = dev ? lrge::ava::AvaStrategy(*dev) : lrge::ava::AvaStrategy(reads);
         lrge::Estimate *st;
         if (N) {
             if (info) fprintf(stderr, "[INFO] Running all-vs-all strategy with %zu reads\n", *N);
-            as = lrge::ava::Builder().num_reads(*N).remove_internal(filter, ratio).threads(threads).seed(seed).platform(pf).device(device).build(reads);
+            const auto b = lrge::ava::Builder().num_reads(*N).remove_internal(filter, ratio).threads(threads).seed(seed).platform(pf).device(device);
+            as = dev ? b.build(*dev) : b.build(reads);
             st = &as;
         } else {
             if (info) fprintf(stderr, "[INFO] Running two-set strategy with %zu target reads and %zu query reads\n", *T, *Q);
-            ts = lrge::twoset::Builder().target_num_reads(*T).query_num_reads(*Q).remove_internal(filter, ratio).use_min_ref(use_min_ref)
-                     .threads(threads).seed(seed).platform(pf).device(device).build(reads);
+            const auto b = lrge::twoset::Builder().target_num_reads(*T).query_num_reads(*Q).remove_internal(filter, ratio).use_min_ref(use_min_ref)
+                               .threads(threads).seed(seed).platform(pf).device(device);
+            ts = dev ? b.build(*dev) : b.build(reads);
             st = &ts;
         }
         std::vector<std::string> paf;
