@@ -14,11 +14,12 @@ def deflate_raw(data, level=6, strategy=zlib.Z_DEFAULT_STRATEGY, memlevel=8):
 
 
 def bgzf_block(data, level=6, strategy=zlib.Z_DEFAULT_STRATEGY, memlevel=8, extra_before=b"", extra_after=b"",
-               fname=None, comment=None, fhcrc=False):
+               fname=None, comment=None, fhcrc=False, comp=None):
     """One BGZF member holding `data` (<= 65536 bytes).  extra_before / extra_after: whole subfields (SI1 SI2 SLEN data)
-    around the BC subfield."""
+    around the BC subfield.  comp: a ready-made raw deflate stream for `data` (tests/deflate_writer.py) instead of zlib's."""
     assert len(data) <= MAX_BLOCK
-    comp = deflate_raw(data, level, strategy, memlevel)
+    if comp is None:
+        comp = deflate_raw(data, level, strategy, memlevel)
     flg = 4 | (8 if fname is not None else 0) | (16 if comment is not None else 0) | (2 if fhcrc else 0)
     tail = (fname + b"\0" if fname is not None else b"") + (comment + b"\0" if comment is not None else b"")
     xlen = len(extra_before) + 6 + len(extra_after)

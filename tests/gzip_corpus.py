@@ -20,7 +20,9 @@ def gz_flushed(data, mode, step=3000, level=6):
     return b"".join(out) + c.flush()
 
 
-def gz_header(data, fname=None, comment=None, extra=None, fhcrc=False, level=6):
+def gz_header(data, fname=None, comment=None, extra=None, fhcrc=False, level=6, comp=None, crc=None, isize=None):
+    """one member with the optional header fields.  comp: a ready-made raw deflate stream instead of zlib's; crc / isize:
+    trailer fields other than those of `data` (for streams that are meant to be rejected)"""
     flg = (4 if extra is not None else 0) | (8 if fname is not None else 0) | (16 if comment is not None else 0) | (2 if fhcrc else 0)
     head = bytes([0x1f, 0x8b, 8, flg, 1, 2, 3, 4, 0, 3])
     if extra is not None:
@@ -31,7 +33,8 @@ def gz_header(data, fname=None, comment=None, extra=None, fhcrc=False, level=6):
         head += comment + b"\0"
     if fhcrc:
         head += struct.pack("<H", zlib.crc32(head) & 0xFFFF)
-    return head + W.deflate_raw(data, level) + struct.pack("<II", zlib.crc32(data), len(data) & 0xFFFFFFFF)
+    return head + (W.deflate_raw(data, level) if comp is None else comp) + \
+        struct.pack("<II", zlib.crc32(data) if crc is None else crc, (len(data) & 0xFFFFFFFF) if isize is None else isize)
 
 
 def fastq(n=2000, seed=3):
