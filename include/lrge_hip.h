@@ -399,15 +399,19 @@ int  lrge_hip_read_records_gpu_ex(lrge_hip_ctx *ctx, const char *path, int flags
                                   void *user, int *used_device);
 
 /* Read sets built on the device from FASTA / FASTQ text (k_fx_census, k_fx_summary, k_fx_scatter, k_fx_records,
-   k_fx_names, k_fx_gather): the device-side form of the record reader (io.rs:154-184) and of the read selection that feeds the
+   k_fx_names, k_fx_gather) and from unaligned BAM (k_bam_header, k_bam_find, k_bam_walk, k_bam_records,
+   k_bam_gather): the device-side form of the record reader (io.rs:154-184) and of the read selection that feeds the
    strategies (twoset.rs:122-201).  The file's bytes are decompressed into HBM and stay there; the records are found there; only
    the identifiers and the sequence lengths come back.
    lrge_hip_reads_open (io.rs:154-184) reads `path` into memory and calls lrge_hip_reads_open_mem (io.rs:154-184), which takes the
    bytes of a whole file.  `flags`: LRGE_GPU_INFLATE_BGZF | LRGE_GPU_INFLATE_GZIP choose the device decoders as in
-   lrge_hip_read_records_gpu_ex; with neither, only uncompressed input is taken.  The records equal those of lrge_hip_read_records
-   on the same file, one for one.  LRGE_ERR_UNPROVEN: the device does not prove this input and produces no parse error of its
-   own -- anything but FASTA or strict four-line FASTQ (an empty line between records, a truncated record, a missing '+', SAM,
-   BAM, CRAM), a compressed format without its flag or other than gzip, a damaged gzip file, text above option INGEST_MAX_BYTES
+   lrge_hip_read_records_gpu_ex; with neither, only uncompressed input is taken.  | LRGE_GPU_INGEST_BAM: text that starts with
+   the BAM magic is scanned as unaligned BAM (every record with flag 4, found by a speculative walk of the length chain that
+   is proven from the end of the header); without the flag BAM is unproven, as it was before the flag existed.  The records
+   equal those of lrge_hip_read_records on the same file, one for one.  LRGE_ERR_UNPROVEN: the device does not prove this input
+   and produces no parse error of its own -- anything but FASTA, strict four-line FASTQ or (with its flag) well-formed unaligned
+   BAM (an empty line between records, a truncated record, a missing '+', SAM, CRAM, BAM without LRGE_GPU_INGEST_BAM, a BAM
+   with a mapped record, a damaged header or record, or bytes behind the last record), a compressed format without its flag or other than gzip, a damaged gzip file, text above option INGEST_MAX_BYTES
    (default: half of the free device memory plus the context's idle arena bytes); the caller takes lrge_hip_read_records*, which
    parses the file or gives the reference's message.  LRGE_ERR_TOO_MANY: 2^32 records or more, or a sequence of 2^32 bases or
    more.  LRGE_ERR_IO: the file cannot be read.  An empty file is LRGE_OK with a count of 0.
@@ -415,12 +419,23 @@ int  lrge_hip_read_records_gpu_ex(lrge_hip_ctx *ctx, const char *path, int flags
    lrge_hip_reads_table (io.rs:154-184): seq_len[n], name_off[n + 1] and the identifiers back to back in names[name_bytes]
    (identifier i is names[name_off[i], name_off[i + 1]); any of the three may be NULL).
    lrge_hip_reads_timings (io.rs:154-184): milliseconds of the open call -- text to HBM, record scan, identifiers and lengths to the
-   host, total.
+   host, total (for BAM the record scan covers the candidate search, the walks, the repair rounds and the table).
+   lrge_hip_reads_bam_stats (io.rs:154-184): the counts of the BAM record scan of `reads` (option BAM_SEGMENT_BYTES, default 256 KiB,
+   at least 64, sets the segment); LRGE_ERR_INVALID when `reads` was not scanned as BAM.
    lrge_hip_seqset_from_reads (twoset.rs:122-201): reads idx[0..n) of `reads`, in that order (any order, repeats allowed; an entry
    out of range is LRGE_ERR_INVALID), as an ordinary read set: their bases are gathered on the device and packed by the
    device-source path of lrge_hip_seqset_upload, so the set is bit-identical to an upload of the same sequences.  name_rank as
    there.  The handle must outlive the call only; lrge_hip_reads_free (io.rs:154-184) releases the text. */
 typedef struct lrge_hip_reads lrge_hip_reads;
+typedef struct lrge_hip_bam_stats {
+    uint64_t segments;           /* segments of BAM_SEGMENT_BYTES the records area was cut into */
+    uint64_t empty_segments;     /* segments no record starts in: a record spans them */
+    uint64_t speculative_starts; /* segments behind the first that were walked from a candidate of the finder */
+    uint64_t rejected_starts;    /* candidates the chain from the header did not reach */
+    uint64_t repair_rounds;      /* rounds of walks from the landing of the segment in front */
+    uint64_t rewalked_segments;  /* segments walked in those rounds */
+} lrge_hip_bam_stats;
+#define LRGE_GPU_INGEST_BAM 4
 int      lrge_hip_reads_open(lrge_hip_ctx *ctx, const char *path, int flags, lrge_hip_reads **out);
 int      lrge_hip_reads_open_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, int flags, lrge_hip_reads **out);
 uint64_t lrge_hip_reads_count(const lrge_hip_reads *reads);
@@ -428,6 +443,7 @@ uint64_t lrge_hip_reads_name_bytes(const lrge_hip_reads *reads);
 uint64_t lrge_hip_reads_text_bytes(const lrge_hip_reads *reads);
 int      lrge_hip_reads_table(const lrge_hip_reads *reads, uint32_t *seq_len, uint64_t *name_off, char *names);
 int      lrge_hip_reads_timings(const lrge_hip_reads *reads, float ms[4]);
+int      lrge_hip_reads_bam_stats(const lrge_hip_reads *reads, lrge_hip_bam_stats *out);
 int      lrge_hip_seqset_from_reads(lrge_hip_ctx *ctx, const lrge_hip_reads *reads, const uint32_t *idx, uint32_t n,
                                     const uint32_t *name_rank, lrge_hip_seqset **out);
 void     lrge_hip_reads_free(lrge_hip_reads *reads);

@@ -12,6 +12,7 @@ ERR_IO, ERR_PARSE, ERR_TOO_MANY, ERR_TOO_FEW, ERR_DEVICE, ERR_MAP, ERR_DUPLICATE
     -1, -2, -3, -4, -5, -6, -7, -8, -9
 ERR_UNPROVEN = -10
 GPU_INFLATE_BGZF, GPU_INFLATE_GZIP = 1, 2
+GPU_INGEST_BAM = 4
 PRESET_AVA_ONT, PRESET_AVA_PB = 0, 1
 
 T_NAMES = ["pack", "sketch", "index_sort", "index_table", "qfilter", "lookup", "expand", "anchor_sort", "group",
@@ -19,6 +20,8 @@ T_NAMES = ["pack", "sketch", "index_sort", "index_table", "qfilter", "lookup", "
 C_NAMES = ["query_bases", "query_minimizers", "anchors", "groups", "groups_chained", "chain_launches", "batches",
            "chain_anchors", "chain_glb_launches", "chain_glb_anchors", "lpg_launches", "lpg_anchors",
            "rs_scatter_launches", "rs_scatter_items", "rs_scatter_bytes", "lpg_split", "lookup_launches", "table_disp_sum", "anchors_kept", "index_parts", "sketch_launches", "sketch_wave_launches"]
+
+BAM_STAT_NAMES = ["segments", "empty_segments", "speculative_starts", "rejected_starts", "repair_rounds", "rewalked_segments"]   # lrge_hip_bam_stats
 
 # int (*sink)(void *user, const void *bytes, uint64_t n) of lrge_hip_gzip_inflate
 GZIP_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)
@@ -30,7 +33,7 @@ EXPORTS = [
     "lrge_hip_bgzf_scan", "lrge_hip_bgzf_inflate", "lrge_hip_read_records_gpu",
     "lrge_hip_gzip_inflate", "lrge_hip_read_records_gpu_ex",
     "lrge_hip_reads_open", "lrge_hip_reads_open_mem", "lrge_hip_reads_count", "lrge_hip_reads_name_bytes", "lrge_hip_reads_text_bytes",
-    "lrge_hip_reads_table", "lrge_hip_reads_timings", "lrge_hip_seqset_from_reads", "lrge_hip_reads_free",
+    "lrge_hip_reads_table", "lrge_hip_reads_timings", "lrge_hip_reads_bam_stats", "lrge_hip_seqset_from_reads", "lrge_hip_reads_free",
     "lrge_hip_index_build", "lrge_hip_index_build_for", "lrge_hip_index_build_sharded", "lrge_hip_index_build_tsharded", "lrge_hip_last_shard_stats", "lrge_hip_index_free",
     "lrge_hip_comm_alltoallv", "lrge_hip_comm_rccl_ranks", "lrge_hip_comm_rccl_ops", "lrge_hip_comm_local_group_serialize", "lrge_hip_comm_local_turn",
     "lrge_hip_comm_busy_ms", "lrge_hip_comm_standin_ms",
@@ -105,6 +108,7 @@ def lib():
         f.argtypes, f.restype = [vp], C.c_uint64
     L.lrge_hip_reads_table.argtypes = [vp, vp, vp, vp]
     L.lrge_hip_reads_timings.argtypes = [vp, C.POINTER(C.c_float * 4)]
+    L.lrge_hip_reads_bam_stats.argtypes = [vp, C.POINTER(C.c_uint64 * len(BAM_STAT_NAMES))]
     L.lrge_hip_seqset_from_reads.argtypes = [vp, vp, vp, C.c_uint32, vp, C.POINTER(vp)]
     L.lrge_hip_reads_free.argtypes = [vp]
     L.lrge_hip_reads_free.restype = None

@@ -44,10 +44,12 @@ TWIN_PATH = os.path.join(LIB_DIR, "liblrge_inflate_twin.so")
 
 def build_twin(force=False):
     """The host twins (g++), for the CPU suite: of k_inflate (csrc/inflate_twin.cpp, the same bit-level core), and of the
-    speculative gzip decode (build_gzip_twin), and of the FASTA / FASTQ record scan (build_fastx_twin)."""
+    speculative gzip decode (build_gzip_twin), of the FASTA / FASTQ record scan (build_fastx_twin) and of the BAM record scan
+    (build_bam_twin)."""
     os.makedirs(LIB_DIR, exist_ok=True)
     build_gzip_twin(force)
     build_fastx_twin(force)
+    build_bam_twin(force)
     srcs = [os.path.join(CSRC, f) for f in ("inflate_twin.cpp", "inflate_core.h", "bgzf_scan.h", "twin_env.h")]
     if not force and os.path.exists(TWIN_PATH) and os.path.getmtime(TWIN_PATH) >= _newest(srcs):
         return TWIN_PATH
@@ -79,6 +81,19 @@ def build_fastx_twin(force=False):
         return FASTX_TWIN_PATH
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-fPIC", "-shared", "-o", FASTX_TWIN_PATH, srcs[0]])
     return FASTX_TWIN_PATH
+
+
+BAM_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_bam_twin.so")
+
+
+def build_bam_twin(force=False):
+    """The host twin of the device BAM record scan (csrc/bam_twin.cpp, g++): the same core and rounds, for the CPU suite."""
+    os.makedirs(LIB_DIR, exist_ok=True)
+    srcs = [os.path.join(CSRC, f) for f in ("bam_twin.cpp", "bam_core.h", "fastx_core.h")]
+    if not force and os.path.exists(BAM_TWIN_PATH) and os.path.getmtime(BAM_TWIN_PATH) >= _newest(srcs):
+        return BAM_TWIN_PATH
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-fPIC", "-shared", "-o", BAM_TWIN_PATH, srcs[0]])
+    return BAM_TWIN_PATH
 
 
 CLI_PATH = os.path.join(LIB_DIR, "lrge-hip")

@@ -1,4 +1,5 @@
-// host_fastx.inl -- read sets built on the device from FASTA / FASTQ text (k_fastx.h): the text reaches HBM
+// host_fastx.inl -- read sets built on the device from FASTA / FASTQ text (k_fastx.h) and from unaligned BAM
+// (k_bam.h, host_bam.inl): the text reaches HBM
 // decompressed (BGZF chunks decoded into one block, the gzip rounds appended device-to-device, plain input copied once), the
 // record scan runs there, only identifiers and lengths come back, and lrge_hip_seqset_from_reads gathers the selected reads
 // into dense ASCII for the device-source pack of host_seqset.inl.  Whatever the scan cannot prove is LRGE_ERR_UNPROVEN: the
@@ -14,6 +15,7 @@ struct lrge_hip_reads {
     std::vector<u64> name_off;                  // [n + 1]
     std::string names;
     float ms[4] = {0, 0, 0, 0};                 // text to HBM, record scan, identifiers and lengths to the host, the whole call
+    BamStats bam = {0, 0, 0, 0, 0, 0};          // fmt == FX_FMT_BAM: the counts of the record scan (lrge_hip_reads_bam_stats)
 };
 
 static double fx_now_ms() { return DevPool::now_ms(); }
@@ -28,6 +30,34 @@ static int fx_verdict_rc(lrge_hip_ctx *ctx, u32 verdict, const char *what) {
     if (verdict & FX_UNPROVEN) { LRGE_SET_ERR(ctx, "reads_open: not proven on the device (%s)", what); return LRGE_ERR_UNPROVEN; }
     LRGE_SET_ERR(ctx, "reads_open: 2^32 records or a sequence of 2^32 bases (%s)", what);
     return LRGE_ERR_TOO_MANY;
+}
+
+// identifiers and lengths to the host, behind a record scan that left the table in R->d_recs, the lengths in d_seq_len /
+// d_name_len and the identifiers' bytes in name_bytes: k_fx_names compacts the identifiers, three copies bring the tables down
+static int fx_tables_to_host(lrge_hip_ctx *ctx, lrge_hip_reads *R, Scratch &sc, u64 n_rec, const u32 *d_seq_len, const u32 *d_name_len, u64 name_bytes) {
+    const double t_scan = fx_now_ms();
+    hipStream_t st = ctx->stream;
+    int rc;
+    ALLOC_OR_FAIL(d_name_dst, sc, u32, n_rec);
+    if ((rc = scan_exclusive_u32(ctx, sc, d_name_len, d_name_dst, n_rec, nullptr))) return rc;
+    ALLOC_OR_FAIL(d_names, sc, u8, std::max<u64>(1, name_bytes));
+    hipLaunchKernelGGL(k_fx_names, dim3((u32)div_up(n_rec, FX_THREADS)), dim3(FX_THREADS), 0, st, (const u8 *)R->d_text, (const FxRec *)R->d_recs, (const u32 *)d_name_dst, n_rec,
+                       d_names);
+    KCHK(ctx);
+    R->n = n_rec;
+    R->seq_len.resize((size_t)n_rec);
+    std::vector<u32> name_len((size_t)n_rec);
+    R->names.resize((size_t)name_bytes);
+    HIPCHK(ctx, hipMemcpyAsync(R->seq_len.data(), d_seq_len, (size_t)n_rec * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(name_len.data(), d_name_len, (size_t)n_rec * 4, hipMemcpyDeviceToHost, st));
+    if (name_bytes) HIPCHK(ctx, hipMemcpyAsync(&R->names[0], d_names, (size_t)name_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    R->name_off.resize((size_t)n_rec + 1);
+    u64 o = 0;
+    for (u64 i = 0; i < n_rec; ++i) { R->name_off[i] = o; o += name_len[i]; }
+    R->name_off[n_rec] = o;
+    R->ms[2] = (float)(fx_now_ms() - t_scan);
+    return LRGE_OK;
 }
 
 // the record scan over R->d_text: fills the table, the lengths and the identifiers
@@ -90,7 +120,6 @@ static int fx_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R) {
     if (!(R->d_recs = (FxRec *)ctx->pool.alloc((size_t)n_rec * sizeof(FxRec), &e))) { LRGE_SET_ERR(ctx, "reads_open: record table: %s", hipGetErrorString(e)); return LRGE_ERR_DEVICE; }
     ALLOC_OR_FAIL(d_seq_len, sc, u32, n_rec);
     ALLOC_OR_FAIL(d_name_len, sc, u32, n_rec);
-    ALLOC_OR_FAIL(d_name_dst, sc, u32, n_rec);
     ALLOC_OR_FAIL(d_flags, sc, u64, 2);                   // [0]: verdict bits (low word), [1]: identifier bytes
     HIPCHK(ctx, hipMemsetAsync(d_flags, 0, 16, st));
     const u32 rec_blocks = (u32)div_up(n_rec, FX_THREADS);
@@ -102,27 +131,10 @@ static int fx_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R) {
     HIPCHK(ctx, ctx->d2h_sync(st));
     if ((u32)flags[0]) return fx_verdict_rc(ctx, (u32)flags[0], "a record outside the strict form");
     if (flags[1] >> 32) return fx_verdict_rc(ctx, FX_UNPROVEN, "4 GiB of identifiers or more");
-    const double t_scan = fx_now_ms();
-    // identifiers and lengths to the host
-    if ((rc = scan_exclusive_u32(ctx, sc, d_name_len, d_name_dst, n_rec, nullptr))) return rc;
-    ALLOC_OR_FAIL(d_names, sc, u8, std::max<u64>(1, flags[1]));
-    hipLaunchKernelGGL(k_fx_names, dim3(rec_blocks), dim3(FX_THREADS), 0, st, t, (const FxRec *)R->d_recs, (const u32 *)d_name_dst, n_rec, d_names);
-    KCHK(ctx);
-    R->n = n_rec;
-    R->seq_len.resize((size_t)n_rec);
-    std::vector<u32> name_len((size_t)n_rec);
-    R->names.resize((size_t)flags[1]);
-    HIPCHK(ctx, hipMemcpyAsync(R->seq_len.data(), d_seq_len, (size_t)n_rec * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(name_len.data(), d_name_len, (size_t)n_rec * 4, hipMemcpyDeviceToHost, st));
-    if (flags[1]) HIPCHK(ctx, hipMemcpyAsync(&R->names[0], d_names, (size_t)flags[1], hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    R->name_off.resize((size_t)n_rec + 1);
-    u64 o = 0;
-    for (u64 i = 0; i < n_rec; ++i) { R->name_off[i] = o; o += name_len[i]; }
-    R->name_off[n_rec] = o;
-    R->ms[2] = (float)(fx_now_ms() - t_scan);
-    return LRGE_OK;
+    return fx_tables_to_host(ctx, R, sc, n_rec, d_seq_len, d_name_len, flags[1]);
 }
+
+#include "host_bam.inl"      // bam_parse_device: the same for unaligned BAM (needs the struct and the tail above)
 
 // ---- text that stays in HBM ----
 // every block of `t` (a table of `comp`) decoded into d_text[0, sum of ISIZE): bgzf_inflate_table (host_inflate.inl) without the
@@ -255,6 +267,7 @@ extern "C" int lrge_hip_reads_open_mem(lrge_hip_ctx *ctx, const void *file_bytes
         return R->d_text != nullptr;
     };
     const auto b = [&](u64 i) -> u32 { return i < len ? d[i] : 0x100u; };
+    bool raw_text = false;                      // the file's bytes are the text
     if (b(0) == 0x1f && b(1) == 0x8b) {
         std::vector<BgzfBlock> t;
         uint64_t total = 0;
@@ -281,10 +294,18 @@ extern "C" int lrge_hip_reads_open_mem(lrge_hip_ctx *ctx, const void *file_bytes
         if (!text_block(len)) return LRGE_ERR_DEVICE;
         if (len) HIPCHK(ctx, hipMemcpyAsync(R->d_text, d, (size_t)len, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        R->n_text = len;
+        R->n_text = len; raw_text = true;
     }
     const double t1 = fx_now_ms();
-    const int rc = fx_parse_device(ctx, R);
+    // BAM by its magic, when the caller asked for it: the first four text bytes are here already for raw input
+    bool is_bam = false;
+    if ((flags & LRGE_GPU_INGEST_BAM) && R->n_text >= 4) {
+        u8 head[4];
+        if (raw_text) memcpy(head, d, 4);
+        else { HIPCHK(ctx, hipMemcpyAsync(head, R->d_text, 4, hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); }
+        is_bam = head[0] == 'B' && head[1] == 'A' && head[2] == 'M' && head[3] == 1;
+    }
+    const int rc = is_bam ? bam_parse_device(ctx, R) : fx_parse_device(ctx, R);
     if (rc) return rc;
     const double t2 = fx_now_ms();
     R->ms[0] = (float)(t1 - t0); R->ms[1] = (float)(t2 - t1) - R->ms[2]; R->ms[3] = (float)(t2 - t0);
@@ -340,8 +361,12 @@ extern "C" int lrge_hip_seqset_from_reads(lrge_hip_ctx *ctx, const lrge_hip_read
         HIPCHK(ctx, hipMemcpyAsync(d_idx, idx, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(ctx, hipMemcpyAsync(d_boff, boff.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
         const u32 grid = std::min<u32>(n, (u32)ctx->n_cu * 32);
-        hipLaunchKernelGGL(k_fx_gather, dim3(grid), dim3(64), 0, ctx->stream, (const u8 *)r->d_text, r->n_text, (const FxRec *)r->d_recs, (const u32 *)d_idx,
-                           (const u64 *)d_boff, n, d_dense);
+        if (r->fmt == FX_FMT_BAM)
+            hipLaunchKernelGGL(k_bam_gather, dim3(grid), dim3(64), 0, ctx->stream, (const u8 *)r->d_text, (const FxRec *)r->d_recs, (const u32 *)d_idx, (const u64 *)d_boff, n,
+                               d_dense);
+        else
+            hipLaunchKernelGGL(k_fx_gather, dim3(grid), dim3(64), 0, ctx->stream, (const u8 *)r->d_text, r->n_text, (const FxRec *)r->d_recs, (const u32 *)d_idx,
+                               (const u64 *)d_boff, n, d_dense);
         KCHK(ctx);
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));        // (idx and boff are pageable: their copies are done; the pack below is ordered behind the gather anyway)
     }

@@ -29,6 +29,7 @@
 #include "bgzf_scan.h"
 #include "k_gzip.h"
 #include "k_fastx.h"
+#include "k_bam.h"
 #include "../../include/lrge_rand.hpp"
 #include "../../include/lrge_io.hpp"
 

@@ -96,7 +96,7 @@ class Context:
 
     def open_reads(self, path_or_bytes, flags=_ffi.GPU_INFLATE_BGZF | _ffi.GPU_INFLATE_GZIP):
         """A FASTA / FASTQ file (a path, or the bytes of the whole file) parsed on the device: plain, BGZF or any other gzip,
-        by `flags` (lrge_hip_reads_open*).  Returns a DeviceReads with names, lens and seqset().  Input the device does not
+        by `flags` (lrge_hip_reads_open*); | _ffi.GPU_INGEST_BAM takes unaligned BAM as well.  Returns a DeviceReads with names, lens and seqset().  Input the device does not
         prove raises UnprovenInput: read the file with the host readers (readio.load) instead."""
         return DeviceReads(self, path_or_bytes, flags)
 
@@ -273,6 +273,13 @@ class DeviceReads:
         a = (C.c_float * 4)()
         self.ctx._check(self.ctx._lib.lrge_hip_reads_timings(self.h, C.byref(a)))
         return dict(zip(("text", "scan", "names", "total"), [float(x) for x in a]))
+
+    @property
+    def bam_stats(self):
+        """the counts of the BAM record scan (lrge_hip_bam_stats) as a dict; raises when the input was not scanned as BAM"""
+        a = (C.c_uint64 * len(_ffi.BAM_STAT_NAMES))()
+        self.ctx._check(self.ctx._lib.lrge_hip_reads_bam_stats(self.h, C.byref(a)))
+        return dict(zip(_ffi.BAM_STAT_NAMES, [int(x) for x in a]))
 
     def seqset(self, idx, ranks=None):
         """reads idx (any order, repeats allowed) as a SeqSet; ranks as Context.upload"""

@@ -1,7 +1,9 @@
 """FASTQ file -> read set consumable on the device: the device ingest (lrge_hip_reads_open + lrge_hip_seqset_from_reads) against
 the route without it (lrge_hip_read_records_gpu_ex into per-record strings, concatenation into the upload arrays,
-lrge_hip_seqset_upload), on one synthetic FASTQ (the seeded parts of tools/gzip_bench.py) raw, in BGZF and as plain gzip.  Usage:
-  python tools/ingest_bench.py [--gbases 1.08] [--dir /tmp] [--reps 5] [--out profiles/ingest_bench.json]
+lrge_hip_seqset_upload), on one synthetic FASTQ (the seeded parts of tools/gzip_bench.py) raw, in BGZF and as plain gzip, and on
+the same reads as a BGZF unaligned BAM (written here from the SAM/BAM specification) at several BAM_SEGMENT_BYTES.  Usage:
+  python tools/ingest_bench.py [--gbases 1.08] [--dir /tmp] [--reps 5] [--kinds fq,bgzf.fq.gz,fq.gz,bam]
+                               [--bam-segments 262144,1048576,4194304] [--out profiles/ingest_bench.json]
 
 Both routes are driven by a small C++ helper (compiled here with g++ against liblrge_hip.so), so that no Python callback sits
 in either clock.  Both start from the file's path with the file in the page cache and end when lrge_hip_seqset_wait has
@@ -12,6 +14,7 @@ import json
 import multiprocessing as mp
 import os
 import statistics
+import struct
 import subprocess
 import sys
 import tempfile
@@ -55,7 +58,8 @@ extern "C" int route_host(lrge_hip_ctx *ctx, const char *path, int flags, double
     return rc;
 }
 // ms: open (stages[0..2]: text to HBM, record scan, identifiers and lengths), seqset of all reads + wait
-extern "C" int route_device(lrge_hip_ctx *ctx, const char *path, int flags, double ms[2], float stages[4], uint64_t *n_reads, uint64_t *n_bases, uint64_t *text_bytes) {
+extern "C" int route_device(lrge_hip_ctx *ctx, const char *path, int flags, double ms[2], float stages[4], uint64_t *n_reads, uint64_t *n_bases, uint64_t *text_bytes,
+                            lrge_hip_bam_stats *bam) {
     const double t0 = now();
     lrge_hip_reads *r = nullptr;
     int rc = lrge_hip_reads_open(ctx, path, flags, &r);
@@ -71,6 +75,7 @@ extern "C" int route_device(lrge_hip_ctx *ctx, const char *path, int flags, doub
     lrge_hip_reads_table(r, len.data(), nullptr, nullptr);
     uint64_t b = 0; for (uint32_t l : len) b += l;
     lrge_hip_reads_timings(r, stages);
+    if (lrge_hip_reads_bam_stats(r, bam)) *bam = lrge_hip_bam_stats{0, 0, 0, 0, 0, 0};
     *n_reads = n; *n_bases = b; *text_bytes = lrge_hip_reads_text_bytes(r);
     lrge_hip_seqset_free(s); lrge_hip_reads_free(r);
     ms[0] = t1 - t0; ms[1] = t2 - t1;
@@ -79,23 +84,59 @@ extern "C" int route_device(lrge_hip_ctx *ctx, const char *path, int flags, doub
 """
 
 
+BAM_HEADER = b"BAM\x01" + struct.pack("<i", 22) + b"@HD\tVN:1.6\tSO:unknown\n" + struct.pack("<i", 0)
+BAM_STATS = ["segments", "empty_segments", "speculative_starts", "rejected_starts", "repair_rounds", "rewalked_segments"]
+
+
+def _ubam(fq):
+    """the reads of a FASTQ part as unaligned BAM records (SAM/BAM specification 4.2): flag 4, no reference, qualities kept"""
+    import numpy as np
+    code = np.full(256, 15, np.uint8)
+    code[np.frombuffer(b"=ACMGRSVTWYHKDBN", np.uint8)] = np.arange(16, dtype=np.uint8)
+    lines = fq.split(b"\n")
+    out = []
+    for i in range(0, len(lines) - 1, 4):
+        name, seq = lines[i][1:].split()[0] + b"\0", lines[i + 1]
+        c = code[np.frombuffer(seq, np.uint8)]
+        if c.size & 1:
+            c = np.append(c, np.uint8(0))
+        body = struct.pack("<iiBBHHHiiii", -1, -1, len(name), 0, 4680, 0, 4, len(seq), -1, -1, 0) + name + ((c[0::2] << 4) | c[1::2]).tobytes() + \
+            (np.frombuffer(lines[i + 3], np.uint8) - 33).tobytes()
+        out.append(struct.pack("<i", len(body)) + body)
+    return b"".join(out)
+
+
+def _bgzf(data, block=65280, level=1):
+    """`data` as BGZF members (SAM/BAM specification 4.1), without the end-of-file block"""
+    out = []
+    for i in range(0, len(data), block):
+        c = zlib.compressobj(level, zlib.DEFLATED, -15)
+        comp = c.compress(data[i:i + block]) + c.flush()
+        out.append(bytes([0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0]) + b"BC" + struct.pack("<HH", 2, len(comp) + 25) + comp +
+                   struct.pack("<II", zlib.crc32(data[i:i + block]), len(data[i:i + block])))
+    return b"".join(out)
+
+
 def _bgzf_part(idx):
     import bgzf_writer as W
     import gzip_bench as GB
     d = GB._fastq(idx)
     c = zlib.compressobj(1, zlib.DEFLATED, 31)
-    return len(d), d, W.bgzf_compress(d, eof=False, level=1), c.compress(d) + c.flush()
+    bam = (BAM_HEADER if idx == 0 else b"") + _ubam(d)
+    return len(d), d, W.bgzf_compress(d, eof=False, level=1), c.compress(d) + c.flush(), len(bam), _bgzf(bam)
 
 
 def write_files(d, parts):
     import bgzf_writer as W
-    paths = {k: os.path.join(d, "ingest." + k) for k in ("fq", "bgzf.fq.gz", "fq.gz")}
-    size = 0
-    with mp.get_context("spawn").Pool(16) as pool, open(paths["fq"], "wb") as fr, open(paths["bgzf.fq.gz"], "wb") as fb, open(paths["fq.gz"], "wb") as fg:
-        for n, raw, bg, gz in pool.imap(_bgzf_part, range(parts)):
-            fr.write(raw); fb.write(bg); fg.write(gz)        # (the plain gzip file: one member per part)
-            size += n
-        fb.write(W.EOF_BLOCK)
+    paths = {k: os.path.join(d, "ingest." + k) for k in ("fq", "bgzf.fq.gz", "fq.gz", "bam")}
+    size = {k: 0 for k in paths}
+    with mp.get_context("spawn").Pool(16) as pool, open(paths["fq"], "wb") as fr, open(paths["bgzf.fq.gz"], "wb") as fb, open(paths["fq.gz"], "wb") as fg, \
+            open(paths["bam"], "wb") as fm:
+        for n, raw, bg, gz, n_bam, bam in pool.imap(_bgzf_part, range(parts)):
+            fr.write(raw); fb.write(bg); fg.write(gz); fm.write(bam)        # (the plain gzip file: one member per part)
+            for k in paths:
+                size[k] += n_bam if k == "bam" else n
+        fb.write(W.EOF_BLOCK); fm.write(W.EOF_BLOCK)
     return paths, size
 
 
@@ -104,6 +145,8 @@ def main():
     ap.add_argument("--gbases", type=float, default=1.08)
     ap.add_argument("--dir", default=tempfile.gettempdir())
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--kinds", default="fq,bgzf.fq.gz,fq.gz,bam")
+    ap.add_argument("--bam-segments", default="262144,1048576,4194304")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ingest_bench.json"))
     a = ap.parse_args()
     from lrge_amd import build as B, engine
@@ -116,14 +159,18 @@ def main():
     parts = max(1, round(a.gbases * 1e9 * 2.02 / (256 << 20)))       # a record is 2 bytes per base and a header
     t0 = time.perf_counter()
     paths, text_bytes = write_files(work, parts)
-    print("files written in %.0f s: %d text bytes" % (time.perf_counter() - t0, text_bytes), flush=True)
+    print("files written in %.0f s: %s text bytes" % (time.perf_counter() - t0, text_bytes), flush=True)
     ctx = engine.Context(0)
     H = C.CDLL(so)
     H.route_host.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_double * 3), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     H.route_device.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_double * 2), C.POINTER(C.c_float * 4), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
-                               C.POINTER(C.c_uint64)]
-    result = {"text_bytes": text_bytes, "reps": a.reps, "files": {}}
-    for kind, p in paths.items():
+                               C.POINTER(C.c_uint64), C.POINTER(C.c_uint64 * 6)]
+    result = {"text_bytes": text_bytes["fq"], "bam_text_bytes": text_bytes["bam"], "reps": a.reps, "files": {}}
+    # (a BAM run per segment size: the host route it is compared with does not depend on the option, and is timed beside each)
+    work_list = [(k, k, None) for k in a.kinds.split(",") if k != "bam"] + [("bam", "bam@%d" % int(S), int(S)) for S in a.bam_segments.split(",") if "bam" in a.kinds.split(",")]
+    for kind, label, seg in work_list:
+        p = paths[kind]
+        ctx.set_option("BAM_SEGMENT_BYTES", None if seg is None else str(seg))
         with open(p, "rb") as fh:
             while fh.read(64 << 20):
                 pass                                                  # page cache
@@ -132,10 +179,10 @@ def main():
             ms3, nr, nb = (C.c_double * 3)(), C.c_uint64(), C.c_uint64()
             rc = H.route_host(ctx.h, p.encode(), 3, C.byref(ms3), C.byref(nr), C.byref(nb))
             assert rc == 0, (kind, rc)
-            ms2, st, nr2, nb2, tb = (C.c_double * 2)(), (C.c_float * 4)(), C.c_uint64(), C.c_uint64(), C.c_uint64()
-            rc = H.route_device(ctx.h, p.encode(), 3, C.byref(ms2), C.byref(st), C.byref(nr2), C.byref(nb2), C.byref(tb))
+            ms2, st, nr2, nb2, tb, bs = (C.c_double * 2)(), (C.c_float * 4)(), C.c_uint64(), C.c_uint64(), C.c_uint64(), (C.c_uint64 * 6)()
+            rc = H.route_device(ctx.h, p.encode(), 7, C.byref(ms2), C.byref(st), C.byref(nr2), C.byref(nb2), C.byref(tb), C.byref(bs))
             assert rc == 0, (kind, rc, ctx._lib.lrge_hip_last_error(ctx.h))
-            assert (nr.value, nb.value) == (nr2.value, nb2.value) and tb.value == text_bytes
+            assert (nr.value, nb.value) == (nr2.value, nb2.value) and tb.value == text_bytes[kind]
             if rep:                                                    # (run 0 is the warm-up)
                 runs_h.append(dict(records_ms=ms3[0], arrays_ms=ms3[1], upload_ms=ms3[2], total_ms=sum(ms3)))
                 runs_d.append(dict(open_ms=ms2[0], seqset_ms=ms2[1], total_ms=sum(ms2), text_ms=st[0], scan_ms=st[1], names_ms=st[2]))
@@ -144,9 +191,11 @@ def main():
         f = dict(file_bytes=os.path.getsize(p), reads=nr.value, bases=nb.value, host_route=runs_h, device_route=runs_d,
                  host_total_ms_median=med(runs_h, "total_ms"), host_total_ms_range=rng(runs_h, "total_ms"),
                  device_total_ms_median=med(runs_d, "total_ms"), device_total_ms_range=rng(runs_d, "total_ms"),
-                 scan_ms_median=med(runs_d, "scan_ms"), scan_text_gb_per_s=text_bytes / med(runs_d, "scan_ms") / 1e6)
-        result["files"][kind] = f
-        print(kind, json.dumps({k: v for k, v in f.items() if not k.endswith("_route")}), flush=True)
+                 scan_ms_median=med(runs_d, "scan_ms"), scan_ms_range=rng(runs_d, "scan_ms"), scan_text_gb_per_s=text_bytes[kind] / med(runs_d, "scan_ms") / 1e6)
+        if seg is not None:
+            f.update(bam_segment_bytes=seg, bam_stats=dict(zip(BAM_STATS, [int(x) for x in bs])))
+        result["files"][label] = f
+        print(label, json.dumps({k: v for k, v in f.items() if not k.endswith("_route")}), flush=True)
     ctx.close()
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     json.dump(result, open(a.out, "w"), indent=1)
