@@ -40,60 +40,43 @@ def build_lib(force=False, verbose=False):
 
 
 TWIN_PATH = os.path.join(LIB_DIR, "liblrge_inflate_twin.so")
-
-
-def build_twin(force=False):
-    """The host twins (g++), for the CPU suite: of k_inflate (csrc/inflate_twin.cpp, the same bit-level core), and of the
-    speculative gzip decode (build_gzip_twin), of the FASTA / FASTQ record scan (build_fastx_twin) and of the BAM record scan
-    (build_bam_twin)."""
-    os.makedirs(LIB_DIR, exist_ok=True)
-    build_gzip_twin(force)
-    build_fastx_twin(force)
-    build_bam_twin(force)
-    srcs = [os.path.join(CSRC, f) for f in ("inflate_twin.cpp", "inflate_core.h", "bgzf_scan.h", "twin_env.h")]
-    if not force and os.path.exists(TWIN_PATH) and os.path.getmtime(TWIN_PATH) >= _newest(srcs):
-        return TWIN_PATH
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-fPIC", "-shared", "-o", TWIN_PATH, srcs[0]])
-    return TWIN_PATH
-
-
 GZIP_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_gzip_twin.so")
-
-
-def build_gzip_twin(force=False):
-    """The host twin of the speculative gzip decode (csrc/gzip_twin.cpp, g++): the same core and round logic, for the CPU suite."""
-    os.makedirs(LIB_DIR, exist_ok=True)
-    srcs = [os.path.join(CSRC, f) for f in ("gzip_twin.cpp", "gzip_core.h", "gzip_round.h", "inflate_core.h", "twin_env.h")]
-    if not force and os.path.exists(GZIP_TWIN_PATH) and os.path.getmtime(GZIP_TWIN_PATH) >= _newest(srcs):
-        return GZIP_TWIN_PATH
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-fPIC", "-shared", "-o", GZIP_TWIN_PATH, srcs[0]])
-    return GZIP_TWIN_PATH
-
-
 FASTX_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_fastx_twin.so")
-
-
-def build_fastx_twin(force=False):
-    """The host twin of the device record scan (csrc/fastx_twin.cpp, g++): the same core and passes, for the CPU suite."""
-    os.makedirs(LIB_DIR, exist_ok=True)
-    srcs = [os.path.join(CSRC, f) for f in ("fastx_twin.cpp", "fastx_core.h")]
-    if not force and os.path.exists(FASTX_TWIN_PATH) and os.path.getmtime(FASTX_TWIN_PATH) >= _newest(srcs):
-        return FASTX_TWIN_PATH
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-fPIC", "-shared", "-o", FASTX_TWIN_PATH, srcs[0]])
-    return FASTX_TWIN_PATH
-
-
 BAM_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_bam_twin.so")
 
 
-def build_bam_twin(force=False):
-    """The host twin of the device BAM record scan (csrc/bam_twin.cpp, g++): the same core and rounds, for the CPU suite."""
+def _build_twin(out, main, force):
+    """One host twin (g++) of csrc/<main>, for the CPU suite.  It is stale when any source of the main library is newer,
+    whichever headers it includes today: a rebuild takes seconds, a stale twin gives a wrong test result."""
     os.makedirs(LIB_DIR, exist_ok=True)
-    srcs = [os.path.join(CSRC, f) for f in ("bam_twin.cpp", "bam_core.h", "fastx_core.h")]
-    if not force and os.path.exists(BAM_TWIN_PATH) and os.path.getmtime(BAM_TWIN_PATH) >= _newest(srcs):
-        return BAM_TWIN_PATH
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-fPIC", "-shared", "-o", BAM_TWIN_PATH, srcs[0]])
-    return BAM_TWIN_PATH
+    if not force and os.path.exists(out) and os.path.getmtime(out) >= _newest(_sources()):
+        return out
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-fPIC", "-shared", "-o", out, os.path.join(CSRC, main)])
+    return out
+
+
+def build_twin(force=False):
+    """The host twins, all four: of k_inflate (csrc/inflate_twin.cpp, the same bit-level core), and of the speculative gzip
+    decode (build_gzip_twin), of the FASTA / FASTQ record scan (build_fastx_twin) and of the BAM record scan (build_bam_twin)."""
+    build_gzip_twin(force)
+    build_fastx_twin(force)
+    build_bam_twin(force)
+    return _build_twin(TWIN_PATH, "inflate_twin.cpp", force)
+
+
+def build_gzip_twin(force=False):
+    """The host twin of the speculative gzip decode (csrc/gzip_twin.cpp): the same core and round logic."""
+    return _build_twin(GZIP_TWIN_PATH, "gzip_twin.cpp", force)
+
+
+def build_fastx_twin(force=False):
+    """The host twin of the device record scan (csrc/fastx_twin.cpp): the same core and passes."""
+    return _build_twin(FASTX_TWIN_PATH, "fastx_twin.cpp", force)
+
+
+def build_bam_twin(force=False):
+    """The host twin of the device BAM record scan (csrc/bam_twin.cpp): the same core and the same driver of the rounds."""
+    return _build_twin(BAM_TWIN_PATH, "bam_twin.cpp", force)
 
 
 CLI_PATH = os.path.join(LIB_DIR, "lrge-hip")

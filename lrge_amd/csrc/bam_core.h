@@ -1,13 +1,13 @@
 // bam_core.h -- the record scan of uncompressed unaligned BAM, shared by the device (k_bam.h, host_bam.inl; hipcc) and the host
 // twin (bam_twin.cpp; g++): the per-record rule, the header walk, the candidate predicate of the speculative starts, the
-// nibble decode of the gather, and the host-side chain logic between the rounds.  The result must equal
+// nibble decode of the gather.  The host-side logic between the rounds is bam_round.h.  The result must equal
 // lrge::io::detail::parse_bam (include/lrge_io.hpp) record for record; whatever these rules cannot prove is the verdict
 // BAM_UNPROVEN, and the caller takes the host parser.
 //
 // BAM records form a length-prefixed chain: where record i + 1 starts is known only from the block size of record i.  The
 // records area [hdr_end, n) is cut into segments of S bytes; a record belongs to the segment its first byte lies in.  Every
 // segment is walked from a start of its own -- segment 0 from hdr_end, the others from a candidate (bam_plausible) -- and
-// bam_chain_plan ties the walks together: a start counts only once it is the landing of the segment in front of it.
+// bam_chain_plan (bam_round.h) ties the walks together: a start counts only once it is the landing of the segment in front of it.
 #pragma once
 #include <stdint.h>
 
@@ -156,42 +156,3 @@ FX_HD uint64_t bam_window(const uint8_t *a) {
 }
 // bases [i0, i0 + 8) of the packed sequence at s as two words of ASCII
 FX_HD void bam_group8(const uint8_t *s, uint64_t i0, uint32_t out[2]) { bam_decode8(bam_window(s + (i0 >> 1)), (uint32_t)(i0 & 1), out); }
-
-// ---- host side, between the rounds ----
-// One pass over the summaries, in segment order.  Segment s > 0 is consistent when a record of segment s - 1 reaches to its end
-// or beyond (it is empty then, and inherits that landing: set here), or when its walk started at landing[s - 1].  Every other
-// segment goes on the list to be walked again from landing[s - 1], unless the segment in front of it is on the list itself (its
-// landing is about to change) or has no landing yet (a speculative walk that stopped at a record it refuses).  The first segment
-// on the list always follows a proven prefix, so every round proves at least one more segment; an isolated false start is
-// settled by the one round that walks its segment again, because the segment behind it started at the true landing.
-// Returns the length of the list (list[i], from[i]); 0 means every start is proven by induction from segment 0.
-// *verdict: BAM_UNPROVEN when a proven walk met a record bam_record refuses, or when the last walk does not end exactly at n.
-static inline uint64_t bam_chain_plan(BamSeg *seg, uint64_t n_seg, uint64_t hdr_end, uint64_t S, uint64_t n, uint32_t *list, uint64_t *from, uint32_t *verdict) {
-    *verdict = 0;
-    uint64_t k = 0;
-    bool proven = true, prev_listed = false;            // proven: every segment in front of s is consistent and not listed
-    for (uint64_t s = 1; s < n_seg; ++s) {
-        const uint64_t land = seg[s - 1].landing;
-        if (prev_listed) { prev_listed = false; proven = false; continue; }
-        if (land == BAM_NONE) {
-            if (proven) { *verdict = BAM_UNPROVEN; return 0; }
-            continue;
-        }
-        if (land >= bam_seg_end(hdr_end, S, n, s)) { seg[s].start = BAM_NONE; seg[s].count = 0; seg[s].landing = land; continue; }
-        if (seg[s].start == land) continue;
-        list[k] = (uint32_t)s; from[k] = land; ++k;
-        prev_listed = true; proven = false;
-    }
-    if (k == 0 && n_seg && seg[n_seg - 1].landing != n) *verdict = BAM_UNPROVEN;
-    return k;
-}
-
-// the counts behind a proven chain (cand: what the finder gave each segment, BAM_NONE for none and for segment 0)
-static inline void bam_chain_stats(const BamSeg *seg, const uint64_t *cand, uint64_t n_seg, BamStats *st) {
-    st->segments = n_seg;
-    for (uint64_t s = 1; s < n_seg; ++s) {
-        st->empty_segments += seg[s].start == BAM_NONE;
-        st->speculative_starts += cand[s] != BAM_NONE;
-        st->rejected_starts += cand[s] != BAM_NONE && seg[s].start != cand[s];
-    }
-}

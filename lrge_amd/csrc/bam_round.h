@@ -1,0 +1,106 @@
+// bam_round.h -- host side of the BAM record scan: the header's result, the segments, round 0, the repair rounds, the counts and
+// the table step.  One template drives both the device (host_bam.inl: kernels of k_bam.h) and the host twin (bam_twin.cpp: the
+// same steps run segment by segment on the CPU), so the CPU suite tests this logic as the library runs it.  The rules of a
+// single record, walk and candidate are bam_core.h.
+#pragma once
+#include <stdint.h>
+
+#include <vector>
+
+#include "bam_core.h"
+
+// One pass over the summaries, in segment order.  Segment s > 0 is consistent when a record of segment s - 1 reaches to its end
+// or beyond (it is empty then, and inherits that landing: set here), or when its walk started at landing[s - 1].  Every other
+// segment goes on the list to be walked again from landing[s - 1], unless the segment in front of it is on the list itself (its
+// landing is about to change) or has no landing yet (a speculative walk that stopped at a record it refuses).  The first segment
+// on the list always follows a proven prefix, so every round proves at least one more segment; an isolated false start is
+// settled by the one round that walks its segment again, because the segment behind it started at the true landing.
+// Returns the length of the list (list[i], from[i]); 0 means every start is proven by induction from segment 0.
+// *verdict: BAM_UNPROVEN when a proven walk met a record bam_record refuses, or when the last walk does not end exactly at n.
+static inline uint64_t bam_chain_plan(BamSeg *seg, uint64_t n_seg, uint64_t hdr_end, uint64_t S, uint64_t n, uint32_t *list, uint64_t *from, uint32_t *verdict) {
+    *verdict = 0;
+    uint64_t k = 0;
+    bool proven = true, prev_listed = false;            // proven: every segment in front of s is consistent and not listed
+    for (uint64_t s = 1; s < n_seg; ++s) {
+        const uint64_t land = seg[s - 1].landing;
+        if (prev_listed) { prev_listed = false; proven = false; continue; }
+        if (land == BAM_NONE) {
+            if (proven) { *verdict = BAM_UNPROVEN; return 0; }
+            continue;
+        }
+        if (land >= bam_seg_end(hdr_end, S, n, s)) { seg[s].start = BAM_NONE; seg[s].count = 0; seg[s].landing = land; continue; }
+        if (seg[s].start == land) continue;
+        list[k] = (uint32_t)s; from[k] = land; ++k;
+        prev_listed = true; proven = false;
+    }
+    if (k == 0 && n_seg && seg[n_seg - 1].landing != n) *verdict = BAM_UNPROVEN;
+    return k;
+}
+
+// the counts behind a proven chain (cand: what the finder gave each segment, BAM_NONE for none and for segment 0)
+static inline void bam_chain_stats(const BamSeg *seg, const uint64_t *cand, uint64_t n_seg, BamStats *st) {
+    st->segments = n_seg;
+    for (uint64_t s = 1; s < n_seg; ++s) {
+        st->empty_segments += seg[s].start == BAM_NONE;
+        st->speculative_starts += cand[s] != BAM_NONE;
+        st->rejected_starts += cand[s] != BAM_NONE && seg[s].start != cand[s];
+    }
+}
+
+enum { BAM_RUN_DEVICE = -2 };
+
+// B (the backend) holds the text of n bytes and does the passes over it.  Every step returns 0, or nonzero for a runtime failure
+// (an int, so that the device's steps keep the library's checking macros): bam_run stops with BAM_RUN_DEVICE, the backend knows why.
+//   int header(uint64_t *hdr_end, uint32_t *verdict)              bam_header
+//   int round0(uint64_t hdr_end, uint64_t S, uint64_t n_seg, uint64_t *cand, BamSeg *seg)
+//                                                                  cand[s], 0 < s < n_seg: the first bam_plausible offset of
+//                                                                  segment s, or BAM_NONE (cand[0]: anything); seg[s]: bam_walk
+//                                                                  from there, seg[0] from hdr_end (both hold for the later steps)
+//   int rewalk(const uint32_t *list, const uint64_t *from, uint64_t k, BamSeg *got)
+//                                                                  got[i]: bam_walk of segment list[i] from from[i]
+//   int records(const uint64_t *start, const uint64_t *base, uint64_t n_seg, uint64_t n_rec, uint32_t *flags, uint64_t *name_bytes)
+//                                                                  the table of n_rec records: bam_walk_records of every segment
+//                                                                  with a start (not BAM_NONE), base[s + 1] - base[s] records at
+//                                                                  base[s]; *flags: the verdict bits of all of them together
+// S: bytes per segment, at least 64 (the callers' business: the device clamps, the twin refuses).
+// Returns 0 (*n_rec records in the backend's table, *name_bytes of identifiers; no record at all behind a header that ends the
+// text), BAM_RUN_DEVICE, or the verdict bits BAM_UNPROVEN / FX_TOO_MANY with *refused naming the step that gave them.
+template <class B>
+static int bam_run(B &be, uint64_t n, uint64_t S, BamStats *st, uint64_t *n_rec, uint64_t *name_bytes, const char **refused) {
+    *st = BamStats{0, 0, 0, 0, 0, 0};
+    *n_rec = *name_bytes = 0;
+    *refused = nullptr;
+    uint64_t hdr_end = 0;
+    uint32_t verdict = 0;
+    if (be.header(&hdr_end, &verdict)) return BAM_RUN_DEVICE;
+    if (verdict) { *refused = "BAM header"; return (int)verdict; }
+    if (hdr_end == n) return 0;                                         // no record: an empty read set, as on the host
+    const uint64_t n_seg = (n - hdr_end + S - 1) / S;
+    if (n_seg >> 31) { *refused = "2^31 BAM segments or more"; return (int)BAM_UNPROVEN; }
+    std::vector<uint64_t> cand(n_seg), from(n_seg + 1), start(n_seg);
+    std::vector<BamSeg> seg(n_seg), got(n_seg);
+    std::vector<uint32_t> list(n_seg);
+    // round 0: every segment from its candidate
+    if (be.round0(hdr_end, S, n_seg, cand.data(), seg.data())) return BAM_RUN_DEVICE;
+    cand[0] = BAM_NONE;
+    // repair rounds
+    for (;;) {
+        const uint64_t k = bam_chain_plan(seg.data(), n_seg, hdr_end, S, n, list.data(), from.data(), &verdict);
+        if (verdict) { *refused = "the BAM record chain"; return (int)verdict; }
+        if (!k) break;
+        ++st->repair_rounds; st->rewalked_segments += k;
+        if (be.rewalk(list.data(), from.data(), k, got.data())) return BAM_RUN_DEVICE;
+        for (uint64_t i = 0; i < k; ++i) seg[list[i]] = got[i];
+    }
+    bam_chain_stats(seg.data(), cand.data(), n_seg, st);
+    // the table: every segment again from its proven start, at the exclusive scan of the counts
+    uint64_t total = 0;
+    for (uint64_t s = 0; s < n_seg; ++s) { from[s] = total; total += seg[s].count; start[s] = seg[s].start; }
+    from[n_seg] = total;
+    if (total >> 32) { *refused = "records"; return (int)FX_TOO_MANY; }
+    uint32_t flags = 0;
+    if (be.records(start.data(), from.data(), n_seg, total, &flags, name_bytes)) return BAM_RUN_DEVICE;
+    if (flags) { *refused = "a BAM record changed between the walks"; return (int)flags; }
+    *n_rec = total;
+    return 0;
+}

@@ -1,15 +1,15 @@
-// bam_twin.cpp -- the host twin of the device BAM record scan (k_bam.h, host_bam.inl; g++): the same passes over the same core
-// (bam_core.h) run segment by segment on the CPU -- header, candidate search, walks, the repair rounds of bam_chain_plan, the
-// table, the nibble gather -- with the segment size a parameter, so the CPU suite checks the algorithm and its counts against
-// the host parser with records straddling segment edges (tests/test_bam_twin.py).  TEST INFRASTRUCTURE, not part of the
-// product library.
+// bam_twin.cpp -- the host twin of the device BAM record scan (k_bam.h, host_bam.inl; g++): the library's own driver (bam_run,
+// bam_round.h) over a backend that runs the same passes over the same core (bam_core.h) segment by segment on the CPU --
+// header, candidate search, walks, the table -- and the nibble gather, with the segment size a parameter, so the CPU suite
+// checks the algorithm, the repair rounds and their counts against the host parser with records straddling segment edges
+// (tests/test_bam_twin.py).  TEST INFRASTRUCTURE, not part of the product library.
 #include <stdint.h>
 #include <string.h>
 
 #include <algorithm>
 #include <vector>
 
-#include "bam_core.h"
+#include "bam_round.h"
 
 namespace {
 struct Parsed {
@@ -19,6 +19,39 @@ struct Parsed {
 };
 Parsed g;
 const uint64_t PAD = 64;
+
+// the backend of bam_run: every pass a loop over the segments
+struct Twin {
+    const uint8_t *t; uint64_t n, hdr_end, S;
+    uint64_t end(uint64_t s) const { return bam_seg_end(hdr_end, S, n, s); }
+    int header(uint64_t *he, uint32_t *verdict) { *verdict = bam_header(t, n, he); return 0; }
+    int round0(uint64_t he, uint64_t seg_bytes, uint64_t n_seg, uint64_t *cand, BamSeg *seg) {
+        hdr_end = he; S = seg_bytes;
+        cand[0] = hdr_end;
+        for (uint64_t s = 1; s < n_seg; ++s) {
+            cand[s] = BAM_NONE;
+            for (uint64_t off = bam_seg_begin(hdr_end, S, s); off < end(s); ++off)
+                if (bam_plausible(t, n, off)) { cand[s] = off; break; }
+        }
+        for (uint64_t s = 0; s < n_seg; ++s) seg[s] = bam_walk(t, n, cand[s], end(s));
+        return 0;
+    }
+    int rewalk(const uint32_t *list, const uint64_t *from, uint64_t k, BamSeg *got) {
+        for (uint64_t i = 0; i < k; ++i) got[i] = bam_walk(t, n, from[i], end(list[i]));
+        return 0;
+    }
+    int records(const uint64_t *start, const uint64_t *base, uint64_t n_seg, uint64_t n_rec, uint32_t *flags, uint64_t *name_bytes) {
+        g.recs.resize(n_rec);
+        std::vector<uint32_t> seq_len(n_rec), name_len(n_rec);
+        for (uint64_t s = 0; s < n_seg; ++s) {
+            if (start[s] == BAM_NONE) continue;
+            uint64_t nb = 0;
+            *flags |= bam_walk_records(t, n, start[s], end(s), base[s + 1] - base[s], g.recs.data() + base[s], seq_len.data() + base[s], name_len.data() + base[s], &nb);
+            *name_bytes += nb;
+        }
+        return 0;
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -29,48 +62,12 @@ int bam_twin_parse(const uint8_t *text, uint64_t n, uint64_t S) {
     if (S < 64) return -1;
     g.text.assign(n + PAD, 0);
     if (n) memcpy(g.text.data(), text, n);
-    const uint8_t *t = g.text.data();
-    uint64_t hdr_end = 0;
-    if (bam_header(t, n, &hdr_end)) return (int)BAM_UNPROVEN;
-    if (hdr_end == n) return 0;
-    const uint64_t n_seg = (n - hdr_end + S - 1) / S;
-    if (n_seg >> 31) return (int)BAM_UNPROVEN;
-    // the finder: the first plausible offset of every segment behind the first
-    std::vector<uint64_t> cand(n_seg, BAM_NONE), from(n_seg + 1);
-    for (uint64_t s = 1; s < n_seg; ++s) {
-        const uint64_t end = bam_seg_end(hdr_end, S, n, s);
-        for (uint64_t off = bam_seg_begin(hdr_end, S, s); off < end; ++off)
-            if (bam_plausible(t, n, off)) { cand[s] = off; break; }
-    }
-    // round 0, then the repair rounds
-    std::vector<BamSeg> seg(n_seg);
-    std::vector<uint32_t> list(n_seg);
-    for (uint64_t s = 0; s < n_seg; ++s) seg[s] = bam_walk(t, n, s ? cand[s] : hdr_end, bam_seg_end(hdr_end, S, n, s));
-    for (;;) {
-        uint32_t verdict = 0;
-        const uint64_t k = bam_chain_plan(seg.data(), n_seg, hdr_end, S, n, list.data(), from.data(), &verdict);
-        if (verdict) return (int)verdict;
-        if (!k) break;
-        ++g.st.repair_rounds; g.st.rewalked_segments += k;
-        for (uint64_t i = 0; i < k; ++i) seg[list[i]] = bam_walk(t, n, from[i], bam_seg_end(hdr_end, S, n, list[i]));
-    }
-    bam_chain_stats(seg.data(), cand.data(), n_seg, &g.st);
-    // the table
-    uint64_t n_rec = 0;
-    for (uint64_t s = 0; s < n_seg; ++s) { from[s] = n_rec; n_rec += seg[s].count; }
-    from[n_seg] = n_rec;
-    if (n_rec >> 32) return (int)FX_TOO_MANY;
-    g.recs.resize(n_rec);
-    std::vector<uint32_t> seq_len(n_rec), name_len(n_rec);
-    uint32_t flags = 0;
-    for (uint64_t s = 0; s < n_seg; ++s) {
-        if (seg[s].start == BAM_NONE) continue;
-        uint64_t nb = 0;
-        flags |= bam_walk_records(t, n, seg[s].start, bam_seg_end(hdr_end, S, n, s), from[s + 1] - from[s], g.recs.data() + from[s], seq_len.data() + from[s],
-                                  name_len.data() + from[s], &nb);
-    }
-    if (flags) { g.recs.clear(); return (int)BAM_UNPROVEN; }
-    return 0;
+    Twin be = {g.text.data(), n, 0, 0};
+    uint64_t n_rec = 0, name_bytes = 0;
+    const char *refused = nullptr;
+    const int rc = bam_run(be, n, S, &g.st, &n_rec, &name_bytes, &refused);
+    if (rc) g.recs.clear();
+    return rc > 0 && rc != (int)FX_TOO_MANY ? (int)BAM_UNPROVEN : rc;       // (any bits of the table step are unproven, as before)
 }
 
 uint64_t bam_twin_count(void) { return g.recs.size(); }

@@ -1,6 +1,6 @@
 // host_fastx.inl -- read sets built on the device from FASTA / FASTQ text (k_fastx.h) and from unaligned BAM
 // (k_bam.h, host_bam.inl): the text reaches HBM
-// decompressed (BGZF chunks decoded into one block, the gzip rounds appended device-to-device, plain input copied once), the
+// decompressed (BGZF chunks decoded into one block by the pipeline of host_inflate.inl, the gzip rounds appended device-to-device, plain input copied once), the
 // record scan runs there, only identifiers and lengths come back, and lrge_hip_seqset_from_reads gathers the selected reads
 // into dense ASCII for the device-source pack of host_seqset.inl.  Whatever the scan cannot prove is LRGE_ERR_UNPROVEN: the
 // caller takes lrge_hip_read_records*, which parses the file or reports it with the reference's messages.  Included into
@@ -24,6 +24,11 @@ static u64 ingest_cap(lrge_hip_ctx *ctx) {
     size_t mfree = 0, mtot = 0;
     if (hipMemGetInfo(&mfree, &mtot) != hipSuccess) { (void)hipGetLastError(); mfree = 0; }
     return ctx->opt_u64("INGEST_MAX_BYTES", ((u64)mfree + ctx->pool.idle()) / 2);       // (the batch planner's accounting: idle arena bytes are reusable)
+}
+
+static int fx_over_cap_rc(lrge_hip_ctx *ctx, u64 cap) {
+    LRGE_SET_ERR(ctx, "reads_open: text above INGEST_MAX_BYTES (%llu)", (unsigned long long)cap);
+    return LRGE_ERR_UNPROVEN;
 }
 
 static int fx_verdict_rc(lrge_hip_ctx *ctx, u32 verdict, const char *what) {
@@ -137,88 +142,10 @@ static int fx_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R) {
 #include "host_bam.inl"      // bam_parse_device: the same for unaligned BAM (needs the struct and the tail above)
 
 // ---- text that stays in HBM ----
-// every block of `t` (a table of `comp`) decoded into d_text[0, sum of ISIZE): bgzf_inflate_table (host_inflate.inl) without the
-// trip down -- the chunks decode into one block and only their status words come back.  *bad: a block failed its checks.
-static int bgzf_inflate_to_device(lrge_hip_ctx *ctx, const uint8_t *comp, const std::vector<BgzfBlock> &t, u8 *d_text, bool *bad) {
-    struct Chunk { size_t b0, b1; u64 c0, cn, o0, on; };
-    const u64 limit = std::max<u64>(1, ctx->opt_u64("INFLATE_CHUNK_BYTES", (u64)256 << 20));
-    std::vector<Chunk> ch;
-    u64 max_c = 0; size_t max_n = 0;
-    for (size_t i = 0; i < t.size();) {
-        Chunk c{i, i, t[i].c_off, 0, t[i].o_off, 0};
-        while (c.b1 < t.size() && (c.b1 == i || c.cn + c.on + t[c.b1].c_len + t[c.b1].isize <= limit) &&
-               c.cn + t[c.b1].c_len < ((u64)1 << 31) && c.on + t[c.b1].isize < ((u64)1 << 31)) {
-            c.cn += t[c.b1].c_len; c.on += t[c.b1].isize; ++c.b1;
-        }
-        max_c = std::max(max_c, c.cn); max_n = std::max(max_n, c.b1 - c.b0);
-        ch.push_back(c);
-        i = c.b1;
-    }
-    *bad = false;
-    if (ch.empty()) return LRGE_OK;
-    const size_t tab_off = (size_t)((max_c + 15) & ~(u64)15), up_bytes = tab_off + max_n * sizeof(InfBlk), st_bytes = max_n * 4;
-    u8 *d_up[2] = {nullptr, nullptr}, *h_up[2] = {nullptr, nullptr};
-    u32 *d_st[2] = {nullptr, nullptr}, *h_st[2] = {nullptr, nullptr};
-    hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_k[2] = {nullptr, nullptr}, ev_dn[2] = {nullptr, nullptr};
-    hipError_t e = hipSuccess;
-    for (int s = 0; s < 2 && e == hipSuccess; ++s) {
-        if (!(d_up[s] = (u8 *)ctx->pool.alloc(up_bytes, &e)) || !(d_st[s] = (u32 *)ctx->pool.alloc(st_bytes, &e))) break;
-        if ((e = hipHostMalloc((void **)&h_up[s], up_bytes, hipHostMallocDefault)) != hipSuccess) break;
-        if ((e = hipHostMalloc((void **)&h_st[s], st_bytes, hipHostMallocDefault)) != hipSuccess) break;
-        if ((e = hipEventCreateWithFlags(&ev_up[s], hipEventDisableTiming)) != hipSuccess) break;
-        if ((e = hipEventCreateWithFlags(&ev_k[s], hipEventDisableTiming)) != hipSuccess) break;
-        e = hipEventCreateWithFlags(&ev_dn[s], hipEventDisableTiming);
-    }
-    auto finish = [&](size_t k) -> hipError_t {
-        const int s = (int)(k & 1);
-        const hipError_t he = hipEventSynchronize(ev_dn[s]);
-        if (he != hipSuccess) return he;
-        for (size_t i = 0; i < ch[k].b1 - ch[k].b0; ++i) if (h_st[s][i] != INF_OK) *bad = true;
-        return hipSuccess;
-    };
-    for (size_t k = 0; k <= ch.size() && e == hipSuccess && !*bad; ++k) {
-        if (k < ch.size()) {
-            const int s = (int)(k & 1);
-            const Chunk &c = ch[k];
-            const u32 n = (u32)(c.b1 - c.b0);
-            // k_inflate stores 4-byte words aligned relative to its output pointer: the pointer is the chunk's start rounded down
-            const u32 lead = (u32)(c.o0 & 3);
-            memcpy(h_up[s], comp + c.c0, (size_t)c.cn);
-            InfBlk *tb = (InfBlk *)(h_up[s] + tab_off);
-            for (u32 i = 0; i < n; ++i) {
-                const BgzfBlock &b = t[c.b0 + i];
-                tb[i] = InfBlk{(u32)(b.c_off - c.c0) + b.d_off, b.d_len, (u32)(b.o_off - c.o0) + lead, b.isize, b.crc};
-            }
-            if ((e = hipMemcpyAsync(d_up[s], h_up[s], tab_off + (size_t)n * sizeof(InfBlk), hipMemcpyHostToDevice, ctx->copy_stream)) != hipSuccess) break;
-            if ((e = hipEventRecord(ev_up[s], ctx->copy_stream)) != hipSuccess) break;
-            if ((e = hipStreamWaitEvent(ctx->stream, ev_up[s], 0)) != hipSuccess) break;
-            hipLaunchKernelGGL(k_inflate, dim3(n), dim3(64), 0, ctx->stream, d_up[s], (const InfBlk *)(d_up[s] + tab_off), n, d_text + (c.o0 - lead), d_st[s]);
-            if ((e = hipGetLastError()) != hipSuccess) break;
-            if ((e = hipEventRecord(ev_k[s], ctx->stream)) != hipSuccess) break;
-            if ((e = hipStreamWaitEvent(ctx->stream2, ev_k[s], 0)) != hipSuccess) break;
-            if ((e = hipMemcpyAsync(h_st[s], d_st[s], (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream2)) != hipSuccess) break;
-            if ((e = hipEventRecord(ev_dn[s], ctx->stream2)) != hipSuccess) break;
-        }
-        if (k >= 1) e = finish(k - 1);
-    }
-    (void)hipStreamSynchronize(ctx->copy_stream); (void)hipStreamSynchronize(ctx->stream); (void)hipStreamSynchronize(ctx->stream2);
-    int rc = LRGE_OK;
-    if (e != hipSuccess) { LRGE_SET_ERR(ctx, "reads_open: bgzf inflate: %s", hipGetErrorString(e)); (void)hipGetLastError(); rc = LRGE_ERR_DEVICE; }
-    for (int s = 0; s < 2; ++s) {
-        ctx->pool.release(d_up[s]); ctx->pool.release(d_st[s]);
-        if (h_up[s]) (void)hipHostFree(h_up[s]);
-        if (h_st[s]) (void)hipHostFree(h_st[s]);
-        if (ev_up[s]) (void)hipEventDestroy(ev_up[s]);
-        if (ev_k[s]) (void)hipEventDestroy(ev_k[s]);
-        if (ev_dn[s]) (void)hipEventDestroy(ev_dn[s]);
-    }
-    return rc;
-}
-
 // any other gzip input: the rounds of gz_run with GzDev keeping every round's bytes on the device (host_gzip.inl: keep_*).
 // LRGE_OK with the block in *d_text (the caller's now), LRGE_ERR_UNPROVEN, LRGE_ERR_DEVICE
 static int gzip_inflate_to_device(lrge_hip_ctx *ctx, const uint8_t *comp, uint64_t comp_len, u64 max_bytes, u8 **d_text, u64 *n_text) {
-    const GzCfg cfg{ctx->opt_u64("GZIP_CHUNK_BYTES", (u64)512 << 10), ctx->opt_u64("GZIP_ROUND_BYTES", (u64)256 << 20), ctx->opt_u64("GZIP_SLOT_RATIO", 8)};
+    const GzCfg cfg = gz_cfg(ctx);
     GzStats st;
     u64 bad = 0;
     GzDev dev(ctx, cfg);
@@ -232,7 +159,7 @@ static int gzip_inflate_to_device(lrge_hip_ctx *ctx, const uint8_t *comp, uint64
         *d_text = dev.keep; *n_text = dev.keep_len; dev.keep = nullptr;
         return LRGE_OK;
     }
-    if (dev.keep_over) { LRGE_SET_ERR(ctx, "reads_open: text above INGEST_MAX_BYTES (%llu)", (unsigned long long)max_bytes); return LRGE_ERR_UNPROVEN; }
+    if (dev.keep_over) return fx_over_cap_rc(ctx, max_bytes);
     if (rc == GZ_RUN_DEVICE) {
         LRGE_SET_ERR(ctx, "reads_open: gzip inflate: %s", hipGetErrorString(dev.e != hipSuccess ? dev.e : hipErrorUnknown));
         (void)hipGetLastError();
@@ -273,12 +200,12 @@ extern "C" int lrge_hip_reads_open_mem(lrge_hip_ctx *ctx, const void *file_bytes
         uint64_t total = 0;
         if (bgzf_scan_blocks(d, len, &t, &total)) {
             if (!(flags & LRGE_GPU_INFLATE_BGZF)) { ctx->err = "reads_open: BGZF input without LRGE_GPU_INFLATE_BGZF"; return LRGE_ERR_UNPROVEN; }
-            if (total > cap) { LRGE_SET_ERR(ctx, "reads_open: text above INGEST_MAX_BYTES (%llu)", (unsigned long long)cap); return LRGE_ERR_UNPROVEN; }
+            if (total > cap) return fx_over_cap_rc(ctx, cap);
             if (!text_block(total)) return LRGE_ERR_DEVICE;
-            bool bad = false;
-            const int rc = bgzf_inflate_to_device(ctx, d, t, R->d_text, &bad);
+            BgzfBad bad;                        // the chunk pipeline of host_inflate.inl, decoding into the block
+            const int rc = bgzf_inflate_chunks(ctx, d, t, nullptr, R->d_text, "reads_open: bgzf inflate", &bad);
             if (rc) return rc;
-            if (bad) { ctx->err = "reads_open: a BGZF block failed its checks"; return LRGE_ERR_UNPROVEN; }
+            if (bad.status != INF_OK) { ctx->err = "reads_open: a BGZF block failed its checks"; return LRGE_ERR_UNPROVEN; }
             R->n_text = total;
         } else {
             if (!(flags & LRGE_GPU_INFLATE_GZIP)) { ctx->err = "reads_open: gzip input without LRGE_GPU_INFLATE_GZIP"; return LRGE_ERR_UNPROVEN; }
@@ -290,7 +217,7 @@ extern "C" int lrge_hip_reads_open_mem(lrge_hip_ctx *ctx, const void *file_bytes
         ctx->err = "reads_open: bzip2, zstd and xz input is decompressed on the host";
         return LRGE_ERR_UNPROVEN;
     } else {
-        if (len > cap) { LRGE_SET_ERR(ctx, "reads_open: text above INGEST_MAX_BYTES (%llu)", (unsigned long long)cap); return LRGE_ERR_UNPROVEN; }
+        if (len > cap) return fx_over_cap_rc(ctx, cap);
         if (!text_block(len)) return LRGE_ERR_DEVICE;
         if (len) HIPCHK(ctx, hipMemcpyAsync(R->d_text, d, (size_t)len, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));

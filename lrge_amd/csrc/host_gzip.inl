@@ -203,11 +203,15 @@ struct GzDev {
 };
 }  // namespace
 
+static GzCfg gz_cfg(lrge_hip_ctx *ctx) {
+    return GzCfg{ctx->opt_u64("GZIP_CHUNK_BYTES", (u64)512 << 10), ctx->opt_u64("GZIP_ROUND_BYTES", (u64)256 << 20), ctx->opt_u64("GZIP_SLOT_RATIO", 8)};
+}
+
 // the whole gzip buffer through `sink`; LRGE_ERR_PARSE / TOO_MANY / DEVICE as lrge_hip_gzip_inflate
 static int gzip_inflate_impl(lrge_hip_ctx *ctx, const uint8_t *comp, uint64_t comp_len, int (*sink)(void *, const void *, uint64_t), void *user,
                              lrge_hip_gzip_stats *stats) {
     (void)hipSetDevice(ctx->device);
-    const GzCfg cfg{ctx->opt_u64("GZIP_CHUNK_BYTES", (u64)512 << 10), ctx->opt_u64("GZIP_ROUND_BYTES", (u64)256 << 20), ctx->opt_u64("GZIP_SLOT_RATIO", 8)};
+    const GzCfg cfg = gz_cfg(ctx);
     GzStats st;
     u64 bad = 0;
     bool sink_stop = false;

@@ -122,6 +122,18 @@ def test_records_cross_chunks_and_rounds(ctx, tmp_path, knobs):
             check_against_host(ctx, tmp_path, name + "/" + wrap, text, wrappings(text)[wrap], rng)
 
 
+def test_chunks_start_unaligned_in_the_text(ctx, tmp_path, knobs):
+    """one block of 2999 bytes per chunk: the chunks start at every residue mod 4 of the text, which the resident block takes
+    with the output pointer rounded down to a word (3000-byte and 65280-byte blocks never leave a word boundary)"""
+    knobs.set("INFLATE_CHUNK_BYTES", 1)
+    text = dict(F.well_formed())["fq_big"][:30000]
+    text = text[:text.rindex(b"\n@big") + 1]
+    assert len(text) > 8 * 2999
+    data = W.bgzf_compress(text, block=2999)
+    assert check_against_host(ctx, tmp_path, "fq_big/bgzf2999", text, data, np.random.default_rng(11)) > 0
+    assert ctx.bgzf_inflate(data) == text
+
+
 def upload_still_works(ctx):
     S = ctx.upload(*to_arrays([b"ACGTACGTACGTTTGACCA" * 20, b"GGGTTTACACACGT" * 11]))
     x, _ = S.sketch(0)
