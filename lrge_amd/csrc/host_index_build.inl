@@ -129,7 +129,10 @@ static int index_build_one(lrge_hip_ctx *ctx, const lrge_hip_seqset *targets, in
             segw = !pk && !ro && extra != ~0u && 2 * P.k >= 24 && !ctx->opt("NO_SEG_PACK") && !ctx->opt("NO_SEGW") && 2 * (u32)P.k - 16 + yb_p <= 64 &&
                    (double)targets->total_bases * dens >= (double)ctx->opt_u64("SEG_PACK_MIN", 1ULL << 22);
         }
-        rc = sketch_device(ctx, sc, targets, preset, true, &so, (pk || segw) ? pk_pos1 : 0, segw ? pk_rid + pk_pos1 : pk_ybits, nullptr, keep_slots, segw, /*wave_ok=*/true);
+        SketchReq rq;
+        rq.entry = sk_index_entry(pk_ybits, segw); rq.pk_pos1 = (pk || segw) ? pk_pos1 : 0; rq.pk_ybits = segw ? pk_rid + pk_pos1 : pk_ybits;
+        rq.keep_slots = keep_slots; rq.wave_ok = true;
+        rc = sketch_device(ctx, sc, targets, preset, rq, &so);
         if (rc) return rc;
         if (so.mz_off) sc.drop(so.mz_off);
     }

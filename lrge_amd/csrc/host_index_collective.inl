@@ -15,11 +15,8 @@ static int sketch_restrict_launch(lrge_hip_ctx *ctx, Scratch &sc, const lrge_hip
     *done = false;
     if (s->n_chunks >= (1ULL << 32) || s->n_chunks == 0 || ctx->opt("SKETCH_TWO_PASS")) return LRGE_OK;
     const u32 n_chunks = (u32)s->n_chunks;
-    const u64 slot_bytes = (u64)n_chunks * SK_CAP * 8 * (pk ? 2 : 3);
-    size_t mfree = (size_t)64 << 30, mtot = 0;
-    if (slot_bytes > ((u64)4 << 30)) (void)hipMemGetInfo(&mfree, &mtot);
-    if (slot_bytes >= ((u64)mfree + ctx->pool.idle()) / 4) return LRGE_OK;
-    const u32 sk_cap = ctx->opt("DEBUG_SK_CAP") ? (u32)std::min<u64>(ctx->opt_u64("DEBUG_SK_CAP", SK_CAP), SK_CAP) : (u32)SK_CAP;
+    if (!sketch_slots_fit(ctx, (u64)n_chunks * SK_CAP * 8 * (pk ? 2 : 3))) return LRGE_OK;
+    const u32 sk_cap = sketch_slot_cap(ctx);
     u64 *tx = sc.get<u64>((size_t)n_chunks * SK_CAP), *ty = pk ? nullptr : sc.get<u64>((size_t)n_chunks * SK_CAP);
     u64 *th = sc.get<u64>((size_t)n_chunks * SK_CAP);
     auto drop_slots = [&]() { if (tx) sc.drop(tx); if (ty) sc.drop(ty); if (th) sc.drop(th); };
@@ -43,11 +40,9 @@ static int sketch_restrict_launch(lrge_hip_ctx *ctx, Scratch &sc, const lrge_hip
     u64 *dy = nullptr;
     if (!pk) { dy = sc.get<u64>((size_t)tot[0] + 1); if (!dy) return LRGE_ERR_DEVICE; }
     ALLOC_OR_FAIL(dh, sc, u64, (size_t)tot[1] + 1);
-    const dim3 cgrid((u32)div_up(div_up(n_chunks, 64), 4));
-    if (pk) hipLaunchKernelGGL(k_sketch_compact<false>, cgrid, dim3(256), 0, ctx->stream, tx, ty, ck, d_tot, n_chunks, dx, dy);
-    else hipLaunchKernelGGL(k_sketch_compact<true>, cgrid, dim3(256), 0, ctx->stream, tx, ty, ck, d_tot, n_chunks, dx, dy);
+    sketch_compact_launch(ctx, pk ? SKC_X_ONLY : SKC_XY, tx, ty, ck, d_tot, 0u, n_chunks, dx, dy);
     KCHK(ctx);
-    hipLaunchKernelGGL(k_sketch_compact<false>, cgrid, dim3(256), 0, ctx->stream, th, (const u64 *)nullptr, co, d_tot + 1, n_chunks, dh, (u64 *)nullptr);
+    sketch_compact_launch(ctx, SKC_X_ONLY, th, nullptr, co, d_tot + 1, 0u, n_chunks, dh, nullptr);
     KCHK(ctx);
     drop_slots(); sc.drop(ck); sc.drop(co); sc.drop(d_tot);
     o->x = dx; o->y = dy; o->mz_off = nullptr; o->n = tot[0];
@@ -161,7 +156,8 @@ static int sharded_collect(lrge_hip_ctx *ctx, Scratch &sc, const Preset &P, int 
         KCHK(ctx);
         HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
         // the shard's own sketch runs on the main stream meanwhile
-        int r = sketch_device(ctx, sc, Tsh, preset, true, &raw, pk ? pk_pos1 : 0, pk_ybits, nullptr); if (r) return r;
+        SketchReq rq; rq.entry = sk_index_entry(pk_ybits, false); rq.pk_pos1 = pk ? pk_pos1 : 0; rq.pk_ybits = pk_ybits;
+        int r = sketch_device(ctx, sc, Tsh, preset, rq, &raw); if (r) return r;
         sc.drop(raw.mz_off);
         if (raw.n && ro->shard_first) {     // read index inside the shard -> index in the whole target set
             if (pk) hipLaunchKernelGGL(k_add_u64, dim3((u32)div_up(raw.n, 256)), dim3(256), 0, st, raw.x, raw.n, (u64)ro->shard_first << pk_pos1);

@@ -174,7 +174,8 @@ int OverlapRun::seeds() {
         so = job.qcache->so; h_mzoff = job.qcache->h_mzoff;
     } else {
         if (job.qcache && !job.qcache->sc) job.qcache->sc.reset(new Scratch(ctx));
-        rc = sketch_device(ctx, job.qcache ? *job.qcache->sc : sc, Q, ix->preset_id, false, &so, 0, 0, &h_mzoff);
+        SketchReq rq; rq.h_mzoff = &h_mzoff;
+        rc = sketch_device(ctx, job.qcache ? *job.qcache->sc : sc, Q, ix->preset_id, rq, &so);
         if (rc) return rc;
         if (job.qcache) { job.qcache->so = so; job.qcache->h_mzoff = h_mzoff; job.qcache->valid = true; }
     }

@@ -91,7 +91,7 @@ extern "C" int lrge_hip_seqset_presketch_sharded(lrge_hip_ctx *ctx, lrge_hip_seq
         HIPCHK(ctx, hipEventRecord(ev_start, st));
         if (r1 > r0) {
             rc = seqset_view(ctx, s, r0, r1, &view); if (rc) return rc;
-            rc = sketch_device(ctx, lsc, view, preset, false, &so); if (rc) return rc;
+            rc = sketch_device(ctx, lsc, view, preset, SketchReq(), &so); if (rc) return rc;
             if (so.n) {
                 if (words) hipLaunchKernelGGL(k_qs_pack, dim3((u32)div_up(so.n, 256)), dim3(256), 0, st, so.x, so.y, so.n, pbits);
                 else hipLaunchKernelGGL(k_qs_rid_base, dim3((u32)div_up(so.n, 256)), dim3(256), 0, st, so.y, so.n, r0);

@@ -70,17 +70,14 @@ __global__ __launch_bounds__(SK_THREADS) void k_sketch_restrict(const u64 *__res
                                                                u32 rank, u32 world) {
     const u32 c = blockIdx.x * SK_THREADS + threadIdx.x;
     if (c >= n_chunks) return;
-    const u32 r = cm.find(c);
-    const i32 len = (i32)lens[r];
-    const i32 s = (i32)(c - cm.chunk_start[r]) * SK_CHUNK;
-    const i32 e = s + SK_CHUNK < len ? s + SK_CHUNK : len;
+    const ChunkSpan sp = cm.span(c, lens);
     const u64 base = (u64)c * SK_CAP;
     u32 nk = 0, no = 0;
-    sketch_chunk<K, W, HPC>(pack, nmask, woff[r], len, r, s, e, [&](u64 x, u64 y) {
+    sketch_chunk<K, W, HPC>(pack, nmask, woff[sp.r], sp.len, sp.r, sp.s, sp.e, [&](u64 x, u64 y) {
         const u64 h = x >> 8;
         if (ks_test(ks, h)) {
             if (nk < cap) {
-                if (PK) tmp_x[base + nk] = h << pk_ybits | (y >> 32) << pk_pos1 | (u64)(u32)y;
+                if (PK) tmp_x[base + nk] = sk_packed_word(h, y >> 32, (u32)y, pk_pos1, pk_ybits);
                 else { tmp_x[base + nk] = h; tmp_y[base + nk] = y; }
             }
             ++nk;

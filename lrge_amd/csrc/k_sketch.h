@@ -16,7 +16,7 @@
 #define SK_CHUNK 128            // bases per lane
 #endif
 #define SK_THREADS 256
-#define ST_REDO 0xFFFFFFFFu     // counts[c] of a chunk the tile form (k_sketch_tile.h) left to k_sketch_direct(only_marked)
+#define ST_REDO 0xFFFFFFFFu     // counts[c] of a chunk the tile form (k_sketch_tile.h) left to k_sketch_direct<..., REDO = true>
 
 // ------------------------------------------------------------------------------------------
 // K0: one thread per 32-base word of the packed image
@@ -263,7 +263,7 @@ struct RunWords {            // "word" = 16 bases = one half of a packed word
 };
 
 // POS_OWN = false: the chunk owns the loop steps that START in [s, e) and writes what mm_sketch writes DURING those steps (the
-// minimizer written at a step lies up to w steps back -- possibly in the chunk before).  POS_OWN = true (k_sketch_redo, behind
+// minimizer written at a step lies up to w steps back -- possibly in the chunk before).  POS_OWN = true (k_sketch_direct<REDO>, behind
 // k_sketch_tile.h): the chunk owns the minimizers whose own step ENDS in [s, e), whenever they are written -- the attribution of the
 // tile form, so that the two can share a read: the replay starts one step earlier, goes on for w steps past e, and filters by position.
 template <int K, int W, bool POS_OWN = false, typename Emit>
@@ -407,7 +407,7 @@ __device__ __forceinline__ void sketch_chunk_hpc(const u64 *pack, const u32 *nma
 template <int K, int W, bool HPC, bool POS_OWN = false, typename Emit>
 __device__ __forceinline__ void sketch_chunk(const u64 *pack, const u32 *nmask, u64 word_base, i32 len, u32 rid,
                                              i32 s, i32 e, Emit &&emit) {
-    static_assert(HPC || !POS_OWN, "position ownership exists for the HPC form only (k_sketch_redo)");
+    static_assert(HPC || !POS_OWN, "position ownership exists for the HPC form only (k_sketch_direct<REDO>)");
     if constexpr (HPC) { sketch_chunk_hpc<K, W, POS_OWN>(pack, nmask, word_base, len, rid, s, e, emit); return; }
     constexpr u64 mask = (1ULL << (2 * K)) - 1;
     constexpr int shift1 = 2 * (K - 1);
@@ -454,6 +454,7 @@ __device__ __forceinline__ void sketch_chunk(const u64 *pack, const u32 *nmask, 
 // the true span is >= 256 too, except the single case span == 255 exactly built from one 255-run and
 // K-1 ... (impossible: K-1 >= 14 further runs add >= 14).  So `kmer_span < 256` is decided identically.
 
+struct ChunkSpan { u32 r; i32 len, s, e; };  // a chunk: bases [s, e) of read r, which has len bases
 struct ChunkMap {  // chunk id -> (read, first base)
     const u32 *chunk_start;  // [n_reads+1] prefix of ceil(len/SK_CHUNK)
     u32 n_reads;
@@ -462,7 +463,17 @@ struct ChunkMap {  // chunk id -> (read, first base)
         while (hi - lo > 1) { u32 mid = (lo + hi) >> 1; if (chunk_start[mid] <= c) lo = mid; else hi = mid; }
         return lo;
     }
+    __device__ __forceinline__ ChunkSpan span(u32 c, const u32 *__restrict__ lens) const {
+        const u32 r = find(c);
+        const i32 len = (i32)lens[r];
+        const i32 s = (i32)(c - chunk_start[r]) * SK_CHUNK;
+        return {r, len, s, s + SK_CHUNK < len ? s + SK_CHUNK : len};
+    }
 };
+
+// The one-word index entry: hash | read | pos << 1 | strand.  (The SEGW entry is this word with the low 2k - 16 bits of the hash's
+// significance string S in place of the hash, beside S >> (2k - 16); its two writers spell the S part out: sketch_write_chunk, k_sketch_wave.)
+__device__ __forceinline__ u64 sk_packed_word(u64 hash, u64 rid, u32 y32, u32 pk_pos1, u32 pk_ybits) { return hash << pk_ybits | rid << pk_pos1 | (u64)y32; }
 
 template <int K, int W, bool HPC>
 __global__ __launch_bounds__(SK_THREADS) void k_sketch_count(const u64 *__restrict__ pack, const u32 *__restrict__ nmask,
@@ -470,12 +481,9 @@ __global__ __launch_bounds__(SK_THREADS) void k_sketch_count(const u64 *__restri
                                                             ChunkMap cm, u32 n_chunks, u32 *__restrict__ counts) {
     u32 c = blockIdx.x * SK_THREADS + threadIdx.x;
     if (c >= n_chunks) return;
-    u32 r = cm.find(c);
-    i32 len = (i32)lens[r];
-    i32 s = (i32)(c - cm.chunk_start[r]) * SK_CHUNK;
-    i32 e = s + SK_CHUNK < len ? s + SK_CHUNK : len;
+    const ChunkSpan sp = cm.span(c, lens);
     u32 n = 0;
-    sketch_chunk<K, W, HPC>(pack, nmask, woff[r], len, r, s, e, [&](u64, u64) { ++n; });
+    sketch_chunk<K, W, HPC>(pack, nmask, woff[sp.r], sp.len, sp.r, sp.s, sp.e, [&](u64, u64) { ++n; });
     counts[c] = n;
 }
 
@@ -510,7 +518,7 @@ __device__ __forceinline__ u32 sketch_write_chunk(const u64 *__restrict__ pack, 
         if (found++ >= cap) return;                     // counted, not stored (the caller notices found > cap)
         bx0 = bx1; bx1 = bx2; bx2 = bx3;
         by0 = by1; by1 = by2; by2 = by3;
-        if (PK == 1) bx3 = (x >> 8) << pk_ybits | (y >> 32) << pk_pos1 | (u64)(u32)y;
+        if (PK == 1) bx3 = sk_packed_word(x >> 8, y >> 32, (u32)y, pk_pos1, pk_ybits);
         else if (PK == 2) {
             const u64 S = hash_to_sig(x >> 8, 2 * K);
             bx3 = (S & ((1ULL << (2 * K - 16)) - 1)) << pk_ybits | (y >> 32) << pk_pos1 | (u64)(u32)y;
@@ -546,11 +554,8 @@ __global__ __launch_bounds__(SK_THREADS) void k_sketch_write(const u64 *__restri
                                                             u64 *__restrict__ out_x, u64 *__restrict__ out_y, u32 pk_pos1, u32 pk_ybits) {
     u32 c = blockIdx.x * SK_THREADS + threadIdx.x;
     if (c >= n_chunks) return;
-    u32 r = cm.find(c);
-    i32 len = (i32)lens[r];
-    i32 s = (i32)(c - cm.chunk_start[r]) * SK_CHUNK;
-    i32 e = s + SK_CHUNK < len ? s + SK_CHUNK : len;
-    (void)sketch_write_chunk<K, W, HPC, INDEX_KEYS, PK>(pack, nmask, woff[r], len, r, s, e, offs[c], 0xFFFFFFFFu, out_x, out_y, pk_pos1, pk_ybits);
+    const ChunkSpan sp = cm.span(c, lens);
+    (void)sketch_write_chunk<K, W, HPC, INDEX_KEYS, PK>(pack, nmask, woff[sp.r], sp.len, sp.r, sp.s, sp.e, offs[c], 0xFFFFFFFFu, out_x, out_y, pk_pos1, pk_ybits);
 }
 
 // One-pass form: every chunk writes into its own slot of SK_CAP entries (tmp[c * SK_CAP ...)) and reports its count;
@@ -559,23 +564,23 @@ __global__ __launch_bounds__(SK_THREADS) void k_sketch_write(const u64 *__restri
 // SK_CAP minimizers (possible in principle: a step can emit up to w of them) raises *overflow and the caller falls
 // back to the two-pass form.
 #define SK_CAP (SK_CHUNK + 8)
-template <int K, int W, bool HPC, bool INDEX_KEYS, int PK>
+// REDO (HPC only; behind k_sketch_tile, which gives the chunks of some tiles back by marking their counts ST_REDO): those chunks alone, the
+// same sequential way, with the tile form's attribution of a minimizer to a chunk (POS_OWN above).
+template <int K, int W, bool HPC, bool INDEX_KEYS, int PK, bool REDO = false>
 __global__ __launch_bounds__(SK_THREADS) void k_sketch_direct(const u64 *__restrict__ pack, const u32 *__restrict__ nmask,
                                                              const u64 *__restrict__ woff, const u32 *__restrict__ lens,
                                                              ChunkMap cm, u32 n_chunks, u32 *__restrict__ counts, u32 *__restrict__ overflow,
                                                              u64 *__restrict__ tmp_x, u64 *__restrict__ tmp_y, u32 pk_pos1, u32 pk_ybits,
                                                              u32 cap /* <= SK_CAP; smaller only in tests */, u32 c_base = 0) {
     // chunks [c_base, n_chunks): a set whose upload is still in flight is sketched range by range, each behind the chunk of the
-    // packed image it needs (host_sketch.inl, sketch_launch)
+    // packed image it needs (host_sketch.inl, GateWalk)
     u32 c = c_base + blockIdx.x * SK_THREADS + threadIdx.x;
     if (c >= n_chunks) return;
-    u32 r = cm.find(c);
-    i32 len = (i32)lens[r];
-    i32 s = (i32)(c - cm.chunk_start[r]) * SK_CHUNK;
-    i32 e = s + SK_CHUNK < len ? s + SK_CHUNK : len;
+    if (REDO && counts[c] != ST_REDO) return;
+    const ChunkSpan sp = cm.span(c, lens);
     const u64 base = (u64)c * SK_CAP;
-    const u32 found = sketch_write_chunk<K, W, HPC, INDEX_KEYS, PK>(pack, nmask, woff[r], len, r, s, e, 0u, cap, tmp_x + base,
-                                                                    PK == 1 ? tmp_y : PK == 2 ? (u64 *)((u32 *)tmp_y + base) : tmp_y + base, pk_pos1, pk_ybits);
+    const u32 found = sketch_write_chunk<K, W, HPC, INDEX_KEYS, PK, REDO>(pack, nmask, woff[sp.r], sp.len, sp.r, sp.s, sp.e, 0u, cap, tmp_x + base,
+                                                                          PK == 1 ? tmp_y : PK == 2 ? (u64 *)((u32 *)tmp_y + base) : tmp_y + base, pk_pos1, pk_ybits);
     counts[c] = found;
     if (found > cap) *overflow = 1u;
 }
@@ -611,17 +616,14 @@ __global__ __launch_bounds__(SK_THREADS) void k_sketch_wave(const u64 *__restric
     const u64 sbase = (u64)(c0 >> 6) * cap;
     const u32 c = c0 + lane;
     if (c < n_chunks) {
-        const u32 r = cm.find(c);
-        const i32 len = (i32)lens[r];
-        const i32 s = (i32)(c - cm.chunk_start[r]) * SK_CHUNK;
-        const i32 e = s + SK_CHUNK < len ? s + SK_CHUNK : len;
-        sketch_chunk<K, W, HPC>(pack, nmask, woff[r], len, r, s, e, [&](u64 x, u64 y) {
+        const ChunkSpan sp = cm.span(c, lens);
+        sketch_chunk<K, W, HPC>(pack, nmask, woff[sp.r], sp.len, sp.r, sp.s, sp.e, [&](u64 x, u64 y) {
             const u64 m = __ballot(1);                                   // the lanes at this emission site right now
             const u32 b = cnt_get();                                     // (one broadcast LDS read)
             if (lane == (u32)__builtin_ctzll(m)) cnt_set(b + (u32)__popcll(m));
             const u32 idx = b + (u32)__popcll(m & lanemask_lt());
             if (idx < cap) {
-                if (PK == 1) out_x[sbase + idx] = (x >> 8) << pk_ybits | (y >> 32) << pk_pos1 | (u64)(u32)y;
+                if (PK == 1) out_x[sbase + idx] = sk_packed_word(x >> 8, y >> 32, (u32)y, pk_pos1, pk_ybits);
                 else {
                     const u64 S = hash_to_sig(x >> 8, 2 * K);
                     out_x[sbase + idx] = (S & ((1ULL << (2 * K - 16)) - 1)) << pk_ybits | (y >> 32) << pk_pos1 | (u64)(u32)y;
@@ -633,34 +635,14 @@ __global__ __launch_bounds__(SK_THREADS) void k_sketch_wave(const u64 *__restric
     if (lane == 0) { const u32 t = cnt_get(); wave_cnt[c0 >> 6] = t; if (t > cap) *overflow = 1u; }
 }
 
-// Behind k_sketch_tile (HPC): the chunks it marked ST_REDO, the sequential way, with the tile form's attribution (POS_OWN above).
-template <int K, int W, bool INDEX_KEYS, int PK>
-__global__ __launch_bounds__(SK_THREADS) void k_sketch_redo(const u64 *__restrict__ pack, const u32 *__restrict__ nmask,
-                                                           const u64 *__restrict__ woff, const u32 *__restrict__ lens,
-                                                           ChunkMap cm, u32 n_chunks, u32 *__restrict__ counts, u32 *__restrict__ overflow,
-                                                           u64 *__restrict__ tmp_x, u64 *__restrict__ tmp_y, u32 pk_pos1, u32 pk_ybits,
-                                                           u32 cap, u32 c_base) {
-    const u32 c = c_base + blockIdx.x * SK_THREADS + threadIdx.x;
-    if (c >= n_chunks) return;
-    if (counts[c] != ST_REDO) return;
-    const u32 r = cm.find(c);
-    const i32 len = (i32)lens[r];
-    const i32 s = (i32)(c - cm.chunk_start[r]) * SK_CHUNK;
-    const i32 e = s + SK_CHUNK < len ? s + SK_CHUNK : len;
-    const u64 base = (u64)c * SK_CAP;
-    const u32 found = sketch_write_chunk<K, W, true, INDEX_KEYS, PK, true>(pack, nmask, woff[r], len, r, s, e, 0u, cap, tmp_x + base,
-                                                                          PK == 1 ? tmp_y : PK == 2 ? (u64 *)((u32 *)tmp_y + base) : tmp_y + base, pk_pos1, pk_ybits);
-    counts[c] = found;
-    if (found > cap) *overflow = 1u;
-}
-
 // One wavefront per 64 consecutive chunks: their minimizers form one contiguous output range, which the lanes walk 64
 // entries at a time (the chunk of an entry by a 6-step search through the 64 scanned counts), so the writes are
 // consecutive across the wave and the reads touch the fronts of two or three slots.
 // c_base / out_cap / ovf: the ranged form (host_sketch.inl: a set whose slots do not fit at once is sketched range by range into the
 // same slots): the launch covers chunks [c_base, n_chunks), `*d_total` is the output offset behind the range, and an entry that
 // would land at or beyond out_cap raises *ovf instead (the caller's estimate of the output size was too small: it starts over).
-// PAIRS: 0 = x only, 1 = (x, y) of 8 bytes each, 2 = x + a u32 per entry (tmp_y / out_y read as u32 arrays: the SEGW entries)
+// PAIRS: what an entry is made of
+enum : int { SKC_X_ONLY = 0, SKC_XY = 1 /* (x, y) of 8 bytes each */, SKC_X_U32 = 2 /* x + a u32 (tmp_y / out_y read as u32 arrays: the SEGW entries) */ };
 template <int PAIRS>
 __global__ __launch_bounds__(256) void k_sketch_compact(const u64 *__restrict__ tmp_x, const u64 *__restrict__ tmp_y,
                                                         const u32 *__restrict__ offs, const u32 *__restrict__ d_total, u32 n_chunks,
@@ -686,8 +668,8 @@ __global__ __launch_bounds__(256) void k_sketch_compact(const u64 *__restrict__ 
         if (o >= out_cap) { if (ovf) *ovf = 1u; continue; }
         const u64 src = (u64)(c0 + j) * SK_CAP + within;
         out_x[o] = tmp_x[src];
-        if (PAIRS == 1) out_y[o] = tmp_y[src];
-        else if (PAIRS == 2) ((u32 *)out_y)[o] = ((const u32 *)tmp_y)[src];
+        if (PAIRS == SKC_XY) out_y[o] = tmp_y[src];
+        else if (PAIRS == SKC_X_U32) ((u32 *)out_y)[o] = ((const u32 *)tmp_y)[src];
     }
 }
 

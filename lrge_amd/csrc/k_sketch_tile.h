@@ -20,7 +20,7 @@
 // Output contract = k_sketch_direct's (per-chunk counts, chunk c's entries at tmp[c * SK_CAP ...), *overflow), so the scan, the
 // compaction, the sort's slot-reading first pass and the ranged / gated launches of host_sketch.inl go on unchanged.
 // HPC only: a tile whose halo does not hold the w + k steps in front of it / the w + 1 step starts behind it (homopolymer runs of
-// dozens of bases around a tile edge) marks its chunks with ST_REDO and k_sketch_redo does them the sequential way.
+// dozens of bases around a tile edge) marks its chunks with ST_REDO and k_sketch_direct<..., REDO = true> does them the sequential way.
 #pragma once
 #include "k_sketch.h"
 
@@ -308,7 +308,7 @@ __global__ __launch_bounds__(ST_THREADS) void k_sketch_tile(const u64 *__restric
                         const u32 y32 = i_last << 1 | z;
                         u64 xfull;
                         if constexpr (C::NARROW) xfull = (u64)xp << 8 | (u64)K; else xfull = (u64)xp;
-                        if (PK) tmp_x[slot + rank] = (xfull >> 8) << pk_ybits | (u64)r << pk_pos1 | (u64)y32;
+                        if (PK) tmp_x[slot + rank] = sk_packed_word(xfull >> 8, (u64)r, y32, pk_pos1, pk_ybits);
                         else {
                             tmp_x[slot + rank] = INDEX_KEYS ? xfull >> 8 : xfull;
                             tmp_y[slot + rank] = (u64)r << 32 | (u64)y32;

@@ -1141,3 +1141,79 @@ def test_wave_dense_index_sketch_and_its_fallbacks(ctx, oracle, edge_set, tiny_o
     rc, ec, eh = ixo2.twoset_counts(oracle.ReadSet(ds.q.seqs(), ds.q.names), threads=8)
     assert rc == 0 and np.array_equal(counts, ec) and np.array_equal(has, eh) and ix.stats()["mid_occ"] == ixo2.mid_occ
     ix.free()
+
+
+GATED_PACK_CHUNK_WORDS = 900       # 28 800 bases per upload chunk, ~70 gates over the reads below (the option is taken as given: no lower bound).
+# Not larger: one read has to be longer than a chunk, and the pb preset packs its entries only while reads stay under 2^15 bases.
+
+
+@pytest.fixture(scope="module")
+def gated_reads():
+    """~2 Mbases in a few hundred reads of 200 .. 6 000 bases (about 16 000 sketch chunks); among them reads shorter than k, an empty
+    read, and one read longer than a whole upload chunk of GATED_PACK_CHUNK_WORDS words (a gate falls inside it)."""
+    rng = np.random.Generator(np.random.PCG64(1806))
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    genome = acgt[rng.integers(4, size=700_000)]
+
+    def cut(ln):
+        st = int(rng.integers(0, len(genome) - ln))
+        return genome[st:st + ln].tobytes()
+
+    seqs = [cut(int(n)) for n in rng.integers(200, 6001, size=640)]
+    seqs[3] = cut(7); seqs[100] = b""; seqs[101] = cut(14); seqs[250] = cut(18); seqs[639] = cut(11)
+    s = bytearray(cut(32_000)); s[15_000:15_040] = b"N" * 40; s[20_000:20_300] = b"A" * 300
+    seqs[320] = bytes(s)
+    names = [b"t%06d" % i for i in range(len(seqs))]
+    return seqs, names, {}
+
+
+@pytest.mark.parametrize("layout", ["packed", "segw"])
+@pytest.mark.parametrize("form", ["wave", "chunk_slots", "ranged", "two_pass"])
+@pytest.mark.parametrize("preset", ["ont", "pb"])
+def test_index_sketch_behind_the_gates_of_an_upload_in_flight(ctx, oracle, gated_reads, preset, form, layout, knobs):
+    """An index built from a target set whose host-side pack is still running (pinned source, wait=False): the sketch does not wait for
+    the upload but walks its chunk gates (host_sketch.inl) -- what every run from host memory takes.  Every form behind the gates: the
+    wave-dense kernel (wavefronts of 64 chunks, launched gate by gate), the per-chunk slots (NO_WAVE_SKETCH: gate by gate), the ranged
+    form (each range waits for the gate that covers it) and the two-pass form (waits for the whole set first); packed and SEGW entries;
+    both presets (HPC: only the chunks of reads that have arrived whole run behind a gate).  A gate inside one long read gives a walk
+    step with nothing new to launch.  The index must be the oracle's, and that of the same reads uploaded with wait=True."""
+    from lrge_amd import engine
+    seqs, names, cache = gated_reads
+    if layout == "segw":
+        knobs.set("NO_PACKED_INDEX", "1"); knobs.set("SEG_PACK_MIN", "1")
+    if form != "wave":
+        knobs.set({"chunk_slots": "NO_WAVE_SKETCH", "ranged": "DEBUG_SK_RANGE_CHUNKS", "two_pass": "SKETCH_TWO_PASS"}[form],
+                  {"chunk_slots": "1", "ranged": "256", "two_pass": "1"}[form])
+    knobs.set("HOST_PACK_CHUNK_WORDS", GATED_PACK_CHUNK_WORDS)
+    if preset not in cache:                        # the oracle's index: once per preset
+        opt = oracle.make_opt(oracle.PRESET_AVA_PB if preset == "pb" else oracle.PRESET_AVA_ONT, dual=True)
+        ixo = oracle.Index(oracle.ReadSet(seqs, names), opt)
+        mz = ixo.minimizers()
+        order = np.lexsort((mz["y"], mz["x"] >> np.uint64(8)))       # (hash, y) ascending == mm_idx_get lists
+        cache[preset] = ((mz["x"] >> np.uint64(8))[order], mz["y"][order], ixo.n_minimizers, ixo.n_keys, ixo.mid_occ)
+    ekeys, epos, e_mz, e_keys, e_mid = cache[preset]
+    bases, offs = to_arrays(seqs)
+    ranks = np.arange(len(seqs), dtype=np.uint32)
+    pinned = ctx.host_alloc(bases.size); pinned.array[:] = bases
+    Tw = ctx.upload(pinned, offs, ranks, wait=True)
+    ixw = engine.Index(ctx, Tw, PRESETS[preset])
+    Tg = ctx.upload(pinned, offs, ranks, wait=False)
+    ixg = engine.Index(ctx, Tg, PRESETS[preset])       # straight away: the upload job has ~70 chunks to pack and send
+    cb = ixg.build_counters
+    print("gated build: sketch_wave_launches %d, sketch_launches %d" % (cb.get("sketch_wave_launches", 0), cb.get("sketch_launches", 0)))
+    st, stw = ixg.stats(), ixw.stats()
+    assert st["n_minimizers"] == e_mz and e_mz > 400_000
+    assert st["n_keys"] == e_keys
+    assert st["mid_occ"] == e_mid
+    keys, pos = ixg.dump()
+    assert np.array_equal(keys, ekeys)
+    assert np.array_equal(pos, epos)
+    kw, pw = ixw.dump()
+    assert stw == st and np.array_equal(kw, keys) and np.array_equal(pw, pos)
+    # the gated walk really ran: a set stays pending until a consumer asks for it, and the walk launches behind every gate that brings
+    # new chunks whether or not the transfer is already over
+    if form == "wave":
+        assert cb.get("sketch_wave_launches", 0) > 1 and cb.get("sketch_launches", 0) == 0, cb
+    elif form == "chunk_slots":
+        assert cb.get("sketch_launches", 0) > 1 and cb.get("sketch_wave_launches", 0) == 0, cb
+    ixg.free(); ixw.free(); Tg.free(); Tw.free(); pinned.free()
