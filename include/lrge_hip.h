@@ -108,6 +108,9 @@ enum {
                           LRGE_C_LOOKUP_LAUNCHES count every streamed minimizer once PER PART */,
     LRGE_C_SKETCH_LAUNCHES /* k_sketch_direct launches of the last index build / overlap call (LRGE_T_K_SKETCH) */,
     LRGE_C_SKETCH_WAVE_LAUNCHES /* k_sketch_wave launches (the wave-dense form of the index sketch; LRGE_T_K_SKETCH times whichever ran) */,
+    LRGE_C_SHARED_NAME_PAIRS /* forward two-set against a partitioned index whose parts share target names: (query, name) pairs the parts
+                                emitted for such names instead of counting them part by part; 0 when no name is shared across parts */,
+    LRGE_C_SHARED_NAME_DISTINCT /* of those, the distinct ones: what the call added to the counts for names shared across parts */,
     LRGE_C_N
 };
 
@@ -200,7 +203,8 @@ int  lrge_hip_index_build_sharded(lrge_hip_ctx *ctx, const uint32_t *all_target_
    PRECONDITION the caller checks (it holds every target's name rank; lrge_amd/parallel.py: cross_shard_duplicates, the Rust shim):
    no target identifier occurs in two DIFFERENT shards.  The reference counts distinct target NAMES (twoset.rs:286-317) and never
    rejects a duplicate id in this mode; a duplicate inside one shard is counted once, one across shards would be counted once per
-   shard.  (A partitioned single-GPU index has the same limit and checks it itself: LRGE_ERR_DUPLICATE_ID.) */
+   shard.  (The parts of a partitioned single-GPU index -- of one rank's share here as well -- have no such limit:
+   lrge_hip_overlap_twoset counts a name its parts share once per query.) */
 int  lrge_hip_index_build_tsharded(lrge_hip_ctx *ctx, const lrge_hip_seqset *target_shard, int preset, lrge_hip_comm *comm,
                                    lrge_hip_index **out);
 /* Exchange volumes of the last lrge_hip_index_build_sharded on this context: {key-set bytes contributed, entries sketched here,

@@ -44,8 +44,9 @@ static int run_overlap(lrge_hip_ctx *ctx, const lrge_hip_index *ix, const lrge_h
         rc = R.batch(q0, q1, A);
         if (rc == LRGE_ERR_DEVICE && q1 - q0 > 1 && shrinks < 6 && ctx->err.compare(0, 17, "device allocation") == 0 && !ctx->opt("NO_BATCH_RETRY")) {
             // The batch's scratch did not fit after all (the plan budgets 48 B per anchor out of 4/5 of the free HBM; other users of
-            // the device, a fragmented arena): nothing of the batch has reached the counts yet (k_count is its last launch and
-            // needs no memory), so drain both streams, give idle segments back and take the same queries in smaller batches.
+            // the device, a fragmented arena): nothing of the batch has reached the counts yet (k_count is its last launch, and the
+            // room k_count_shared's pairs need is made in front of it), so drain both streams, give idle segments back and take the
+            // same queries in smaller batches.
             (void)hipStreamSynchronize(ctx->stream); (void)hipStreamSynchronize(ctx->stream2); (void)hipGetLastError();
             ctx->pool.trim();
             memcpy(ctx->counters, cn_before, sizeof cn_before);
@@ -118,6 +119,7 @@ static int twoset_one_index(lrge_hip_ctx *ctx, const lrge_hip_index *ix, const l
         OverlapJob j = job;
         if (j.counts) j.counts += cuts[v];
         if (j.has_map) j.has_map += cuts[v];
+        j.q_base = cuts[v];
         rc = run_overlap(ctx, ix, view, j);
         acc.add(ctx);
         lrge_hip_seqset_free(view);
@@ -142,35 +144,76 @@ extern "C" int lrge_hip_overlap_twoset(lrge_hip_ctx *ctx, const lrge_hip_index *
     // partitioned index: the parts hold disjoint target reads, so a query's distinct-target count is the sum over the
     // parts and it has a mapping if it has one in any part; every part sees the same queries and the global mid_occ.
     // The reference counts distinct target NAMES (twoset.rs:286-317) and never rejects a duplicate identifier in this mode: a name
-    // that two reads of ONE part share is counted once (k_count's t_dup walk), a name shared across PARTS would be counted once per
-    // part -- refused instead of counted wrongly (the target-sharded multi-GPU form has the same limit: lrge_hip_index_build_tsharded)
+    // that two reads of ONE part share is counted once in that part (k_count's t_dup walk).  A name shared across PARTS would be
+    // counted once per part: the groups onto its bearers are kept out of the per-part counts (k_count_shared) and leave
+    // (query, name) pairs instead, whose distinct ones are counted after the last part (NamePairs).  Without such a name -- an
+    // all-distinct set, duplicates confined to one part -- nothing of this exists and the call launches what it always did.
+    const u32 nq = queries->n;
+    std::unique_ptr<NamePairs> np;
     if (ix->seqs && ix->seqs->dup_rank) {
         std::vector<std::pair<u32, u32>> rp;      // (name rank, part)
         for (size_t pi = 0; pi < ix->parts.size(); ++pi)
             for (u32 r : ix->parts[pi]->seqs->h_rank) rp.emplace_back(r, (u32)pi);
         std::sort(rp.begin(), rp.end());
+        std::vector<u32> shared;                  // ranks that occur in two or more different parts, ascending
         for (size_t i = 1; i < rp.size(); ++i)
-            if (rp[i].first == rp[i - 1].first && rp[i].second != rp[i - 1].second) {
-                LRGE_SET_ERR(ctx, "Duplicate read identifier across the parts of a partitioned index (target set above PART_BASES bases): distinct target names cannot be counted part by part");
-                return LRGE_ERR_DUPLICATE_ID;
+            if (rp[i].first == rp[i - 1].first && rp[i].second != rp[i - 1].second && (shared.empty() || shared.back() != rp[i].first)) shared.push_back(rp[i].first);
+        if (!shared.empty()) {
+            HIPCHK(ctx, hipSetDevice(ctx->device));
+            np.reset(new NamePairs(ctx));
+            np->bits_q = std::max<u32>(1, ceil_log2_u64((u64)nq));
+            np->bits_rank = std::max<u32>(1, ceil_log2_u64((u64)rp.back().first + 1));
+            np->d_bits.assign(ix->parts.size(), nullptr);
+            std::vector<std::vector<u32>> h_bits(ix->parts.size());     // (read by the copies until the sync below)
+            for (size_t pi = 0; pi < ix->parts.size(); ++pi) {
+                const std::vector<u32> &hr = ix->parts[pi]->seqs->h_rank;
+                std::vector<u32> &w = h_bits[pi];
+                w.assign(hr.size() / 32 + 1, 0u);
+                bool any = false;
+                for (size_t r = 0; r < hr.size(); ++r)
+                    if (std::binary_search(shared.begin(), shared.end(), hr[r])) { w[r >> 5] |= 1u << (r & 31); any = true; }
+                if (!any) continue;               // (a part without a shared name: plain k_count)
+                hipError_t e = hipErrorOutOfMemory;
+                np->d_bits[pi] = (u32 *)ctx->pool.alloc(w.size() * 4, &e);
+                if (!np->d_bits[pi]) { LRGE_SET_ERR(ctx, "device allocation of %zu bytes for a part's shared-name bitmap failed: %s", w.size() * 4, hipGetErrorString(e)); return LRGE_ERR_DEVICE; }
+                HIPCHK(ctx, hipMemcpyAsync(np->d_bits[pi], w.data(), w.size() * 4, hipMemcpyHostToDevice, ctx->stream));
             }
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        }
     }
-    const u32 nq = queries->n;
     acc.parts = ix->parts.size();
     std::vector<u32> c((size_t)nq + 1), h((size_t)nq + 1);
     if (counts) std::fill(counts, counts + nq, 0u);
     if (has_mapping) std::fill(has_mapping, has_mapping + nq, 0u);
     SketchCache qcache;
     const bool cache_ok = queries->total_bases <= stream_limit(ctx) || queries->n < 2;     // (in views every view is sketched per part)
-    for (const lrge_hip_index *part : ix->parts) {
+    for (size_t pi = 0; pi < ix->parts.size(); ++pi) {
+        const lrge_hip_index *part = ix->parts[pi];
         OverlapJob pj = job;
         if (cache_ok) pj.qcache = &qcache;
         pj.counts = c.data(); pj.has_map = h.data();
+        if (np && np->d_bits[pi]) { pj.name_pairs = np.get(); pj.d_shared_bits = np->d_bits[pi]; }
         rc = twoset_one_index(ctx, part, queries, pj, acc);
         if (rc) return rc;
         for (u32 q = 0; q < nq; ++q) { if (counts) counts[q] += c[q]; if (has_mapping) has_mapping[q] |= h[q]; }
     }
+    if (np) {
+        // the names shared across parts, once per query: a short pass of its own behind the last part (its sort's launches and
+        // its time join the call's counters and timings)
+        const u64 split = ctx->counters[LRGE_C_LPG_SPLIT];
+        memset(ctx->ms, 0, sizeof(ctx->ms)); memset(ctx->counters, 0, sizeof(ctx->counters));
+        {
+            StageTimer t_total(ctx, LRGE_T_TOTAL), t_count(ctx, LRGE_T_COUNT);
+            rc = np->resolve(nq, counts);
+        }
+        (void)hipStreamSynchronize(ctx->stream);
+        ctx->resolve_timers();
+        ctx->counters[LRGE_C_LPG_SPLIT] = split;
+        acc.add(ctx);
+        if (rc) return rc;
+    }
     acc.store(ctx);
+    if (np) { ctx->counters[LRGE_C_SHARED_NAME_PAIRS] = np->emitted; ctx->counters[LRGE_C_SHARED_NAME_DISTINCT] = np->distinct; }
     return LRGE_OK;
 }
 

@@ -53,6 +53,96 @@ int OverlapRun::dump_sorted_anchors(const u64 *skey, const u64 *sval, u64 A) {
     return RUN_DONE;
 }
 
+// ---- NamePairs (host_overlap_seeds.inl): the (query, shared target name) pairs of a forward call over a partitioned index ----
+int NamePairs::read_cursor(u64 *n) {
+    u32 c = 0;
+    if (d_cur) {
+        HIPCHK(ctx, ctx->d2h(&c, d_cur, 4, ctx->stream));
+        HIPCHK(ctx, ctx->d2h_sync(ctx->stream));
+    }
+    if (c > cap || c > upper) {     // (cannot happen: room() precedes every launch; k_count_shared does not write past cap either)
+        LRGE_SET_ERR(ctx, "shared target names: %u pairs emitted into a buffer of %llu (bound %llu)", c, (unsigned long long)cap, (unsigned long long)upper);
+        return LRGE_ERR_DEVICE;
+    }
+    emitted += c - at_flush; at_flush = c; upper = c;
+    *n = c;
+    return LRGE_OK;
+}
+
+int NamePairs::sort(u64 n, u64 **res, Scratch &sc, u64 **other) {
+    u64 *tmp = sc.get<u64>(n + 1);
+    if (!tmp) return LRGE_ERR_DEVICE;
+    u64 *r1 = nullptr, *r2 = nullptr;
+    int rc = radix_sort_keys(ctx, sc, buf, tmp, n, 0, (int)bits_rank, &r1, false);          // by name rank,
+    if (rc) return rc;
+    rc = radix_sort_keys(ctx, sc, r1, r1 == buf ? tmp : buf, n, 32, (int)bits_q, &r2, false);   // then (stable) by query
+    if (rc) return rc;
+    *res = r2; *other = r2 == buf ? tmp : buf;
+    return LRGE_OK;
+}
+
+int NamePairs::flush() {
+    u64 n = 0;
+    int rc = read_cursor(&n);
+    if (rc || n < 2) return rc;
+    Scratch sc(ctx);
+    u64 *sorted = nullptr, *other = nullptr;
+    rc = sort(n, &sorted, sc, &other);
+    if (rc) return rc;
+    u32 *starts = nullptr, n_runs = 0;
+    rc = compact_heads(ctx, sc, sorted, n, 0, &starts, &n_runs);      // (its host read of the run count is this path's one round trip)
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_gather_index_u64, dim3((u32)div_up(n_runs, 256)), dim3(256), 0, ctx->stream, sorted, starts, n_runs, other);
+    KCHK(ctx);
+    if (other != buf) HIPCHK(ctx, hipMemcpyAsync(buf, other, (size_t)n_runs * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_cur, &n_runs, 4, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));      // (n_runs is a local)
+    at_flush = upper = n_runs;
+    return LRGE_OK;
+}
+
+int NamePairs::room(u64 need) {
+    if (!d_cur) {
+        hipError_t e = hipErrorOutOfMemory;
+        d_cur = (u32 *)ctx->pool.alloc(4, &e);
+        if (!d_cur) { LRGE_SET_ERR(ctx, "device allocation of the shared-name pair cursor failed: %s", hipGetErrorString(e)); return LRGE_ERR_DEVICE; }
+        HIPCHK(ctx, hipMemsetAsync(d_cur, 0, 4, ctx->stream));
+    }
+    if (buf && upper + need <= cap) return LRGE_OK;
+    // what is there may hold the same pair many times (a name's bearers in several parts, every part a hit): unique it first
+    if (buf) { int rc = flush(); if (rc) return rc; }
+    if (buf && upper + need <= cap && upper <= cap / 2) return LRGE_OK;     // (a buffer that stays more than half full after a flush would be flushed batch after batch)
+    const u64 want = std::max<u64>(std::max<u64>(2 * cap, upper + need), ctx->opt_u64("DEBUG_NAME_PAIRS_CAP", 1ull << 20));
+    if (want >= (1ULL << 32)) { LRGE_SET_ERR(ctx, "shared target names: %llu (query, name) pairs pending (limit 2^32)", (unsigned long long)want); return LRGE_ERR_TOO_MANY; }
+    hipError_t e = hipErrorOutOfMemory;
+    u64 *nb = (u64 *)ctx->pool.alloc((size_t)want * 8, &e);
+    if (!nb) { LRGE_SET_ERR(ctx, "device allocation of %llu bytes for the pairs of shared target names failed: %s", (unsigned long long)want * 8, hipGetErrorString(e)); return LRGE_ERR_DEVICE; }
+    if (buf && upper) HIPCHK(ctx, hipMemcpyAsync(nb, buf, (size_t)upper * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    ctx->pool.release(buf);        // (reusable at once: every user is ordered on ctx->stream)
+    buf = nb; cap = want;
+    return LRGE_OK;
+}
+
+int NamePairs::resolve(u32 nq, u32 *counts) {
+    u64 n = 0;
+    int rc = read_cursor(&n);
+    if (rc) return rc;
+    if (n == 0) return LRGE_OK;
+    Scratch sc(ctx);
+    u64 *sorted = buf, *other = nullptr;
+    if (n > 1) { rc = sort(n, &sorted, sc, &other); if (rc) return rc; }
+    ALLOC_OR_FAIL(d_add, sc, u32, (size_t)nq + 2);       // [nq]: the number of distinct pairs
+    HIPCHK(ctx, hipMemsetAsync(d_add, 0, ((size_t)nq + 2) * 4, ctx->stream));
+    hipLaunchKernelGGL(k_name_pairs_count, dim3((u32)div_up(n, 256)), dim3(256), 0, ctx->stream, sorted, (u32)n, d_add, d_add + nq);
+    KCHK(ctx);
+    std::vector<u32> add((size_t)nq + 1);
+    HIPCHK(ctx, hipMemcpyAsync(add.data(), d_add, ((size_t)nq + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (counts) for (u32 q = 0; q < nq; ++q) counts[q] += add[q];
+    distinct = add[nq];
+    return LRGE_OK;
+}
+
 int OverlapRun::batch(u32 q0, u32 q1, u64 A) {
     const lrge_hip_seqset *T = ix->seqs; const Preset &P = ix->P; const u32 nq = Q->n, nt = T->n;
     (void)T; (void)P; (void)nq; (void)nt;
@@ -343,7 +433,17 @@ int OverlapRun::batch(u32 q0, u32 q1, u64 A) {
         cnp.q_rank = Q->has_rank ? Q->d_rank : nullptr; cnp.t_rank = T->has_rank ? T->d_rank : nullptr;
         cnp.t_dup = T->dup_rank ? 1 : 0;
         cnp.q_map = d_qmap; cnp.rid_base = job.rid_base;
-        if (n_chained) {
+        cnp.shared_bits = nullptr; cnp.pairs = nullptr; cnp.pair_cur = nullptr; cnp.pair_cap = 0; cnp.q_base = job.q_base;
+        if (n_chained && job.mode == MODE_TWOSET && job.name_pairs && job.d_shared_bits && cnp.t_rank) {
+            // this part shares target names with other parts: every chained group may leave one pair
+            NamePairs &np = *job.name_pairs;
+            rc = np.room(n_chained);
+            if (rc) return rc;
+            cnp.shared_bits = job.d_shared_bits; cnp.pairs = np.buf; cnp.pair_cur = np.d_cur; cnp.pair_cap = (u32)np.cap;
+            hipLaunchKernelGGL(k_count_shared, dim3((u32)div_up(n_chained, 256)), dim3(256), 0, ctx->stream, skey, gstart, gflags, hw_list, n_chained, cnp, d_counts, d_hasmap);
+            KCHK(ctx);
+            np.upper += n_chained;
+        } else if (n_chained) {
             hipLaunchKernelGGL(k_count, dim3((u32)div_up(n_chained, 256)), dim3(256), 0, ctx->stream, skey, gstart, gflags, hw_list, n_chained, cnp, d_counts, d_hasmap);
             KCHK(ctx);
         }

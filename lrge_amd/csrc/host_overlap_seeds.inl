@@ -8,6 +8,31 @@ enum { MODE_TWOSET = 0, MODE_INVERSE = 1, MODE_AVA = 2 };
 // once per part -- 8 x 12.7 ms at full-size C5)
 struct SketchCache { std::unique_ptr<Scratch> sc; SketchOut so; std::vector<u32> h_mzoff; bool valid = false; };
 
+// Forward two-set against a partitioned index whose parts share target names (lrge_hip_overlap_twoset): what a call keeps over
+// all its parts and query views.  A counted group onto a read whose name also occurs in ANOTHER part is not counted in that
+// part (k_count_shared): it leaves the pair (global query, name rank) here, and the distinct pairs are counted once the last
+// part is through (resolve) -- the HashSet<target_name> of twoset.rs:286-317, which a per-part count cannot be.
+// The buffer never drops a pair: before a batch's k_count_shared the host makes room for as many pairs as the batch has
+// chained groups (room) -- first by sorting and uniquing what is there (flush), then by growing the buffer from the arena.
+struct NamePairs {
+    lrge_hip_ctx *ctx;
+    std::vector<u32 *> d_bits;          // per part: one bit per read of the part, set when its name occurs in another part too
+    u64 *buf = nullptr; u32 *d_cur = nullptr;
+    u64 cap = 0;                        // entries of buf
+    u64 upper = 0;                      // what *d_cur cannot exceed (the host adds every batch's chained groups; the cursor is read only when this runs out)
+    u64 at_flush = 0;                   // the cursor's value after the last flush
+    u64 emitted = 0, distinct = 0;      // LRGE_C_SHARED_NAME_PAIRS / _DISTINCT
+    u32 bits_q = 1, bits_rank = 1;      // sort key: bits [0, bits_rank) and [32, 32 + bits_q) of a pair
+    explicit NamePairs(lrge_hip_ctx *c) : ctx(c) {}
+    ~NamePairs() { for (u32 *b : d_bits) ctx->pool.release(b); ctx->pool.release(buf); ctx->pool.release(d_cur); }
+    NamePairs(const NamePairs &) = delete; NamePairs &operator=(const NamePairs &) = delete;
+    int read_cursor(u64 *n);            // *d_cur to the host (one round trip); folds what was emitted since the last flush into `emitted`
+    int sort(u64 n, u64 **res, Scratch &sc, u64 **other);   // buf[0, n) by (query, name): the result is in *res (buf or a block of sc)
+    int flush();                        // sort, unique, compact: buf holds the distinct pairs, the cursor their number
+    int room(u64 need);                 // before a launch that may append `need` pairs
+    int resolve(u32 nq, u32 *counts);   // after the last part: counts[q] += distinct names of q among the pairs
+};
+
 struct OverlapJob {
     int mode;
     int dual;                       // 1: NO_DUAL cleared, 0: set
@@ -27,6 +52,8 @@ struct OverlapJob {
     const u32 *d_hc_global = nullptr;                   // chain records: those counts, complete (a seed's rank among the KEPT seeds
                                                         // of its query -- n_seeds / dv -- counts seeds kept in ANY part)
     SketchCache *qcache = nullptr;                      // the streamed set's sketch, shared by the parts' runs
+    NamePairs *name_pairs = nullptr; const u32 *d_shared_bits = nullptr;   // forward mode, names shared across parts: the call's pair sink, this part's bitmap
+    u32 q_base = 0;                                     // first query of the streamed view in the whole query set
 };
 
 

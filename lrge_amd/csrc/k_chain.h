@@ -83,12 +83,22 @@ struct CountParams {
                                   // indexed set (null: the query set is the indexed set itself)
     u32 rid_base;                 // all-vs-all against one PART of a partitioned index: first read of the part in the whole
                                   // indexed set (counts are keyed by the whole set)
+    // forward mode against one PART whose reads share identifiers with reads of OTHER parts (host_overlap_api.inl: NamePairs).
+    // shared_bits: one bit per read of the part, set when its name occurs in another part too (null: no such name -- k_count;
+    // non-null: k_count_shared).  A counted group onto such a read leaves counts[] alone and appends (global query << 32 | name
+    // rank) to pairs[] at *pair_cur; the pairs of all parts are sorted and counted once per distinct pair (k_name_pairs_count).
+    const u32 *shared_bits;
+    u64 *pairs; u32 *pair_cur; u32 pair_cap;   // (the host keeps *pair_cur + the batch's chained groups <= pair_cap)
+    u32 q_base;                   // first query of the streamed view in the whole query set (pairs carry global query indices)
 };
 
 // list / n_list: the groups that were chained (all others carry no flags: one lane per CHAINED group instead of one per
 // group -- 0.5 M of 109 M at C4)
-__global__ void k_count(const u64 *__restrict__ skey, const u32 *__restrict__ gstart, const u32 *__restrict__ gflags,
-                        const u32 *__restrict__ list, u32 n_list, CountParams cp, u32 *__restrict__ counts, u32 *__restrict__ has_map) {
+// SHARED: the instantiation of calls whose index parts share target names (k_count_shared); k_count itself is the body with
+// SHARED = false, i.e. the code it always was.
+template <bool SHARED>
+__device__ __forceinline__ void count_group(const u64 *__restrict__ skey, const u32 *__restrict__ gstart, const u32 *__restrict__ gflags,
+                                            const u32 *__restrict__ list, u32 n_list, const CountParams &cp, u32 *__restrict__ counts, u32 *__restrict__ has_map) {
     const u32 li = blockIdx.x * blockDim.x + threadIdx.x;
     if (li >= n_list) return;
     const u32 g = list[li];
@@ -118,6 +128,22 @@ __global__ void k_count(const u64 *__restrict__ skey, const u32 *__restrict__ gs
             if (r2 != rid && (gflags[gg] & 2u) && cp.t_rank[r2] == tr) return;
         }
     }
+    if (SHARED) {      // (forward mode only: the host launches k_count_shared for nothing else)
+        if ((cp.shared_bits[rid >> 5] >> (rid & 31)) & 1u) {
+            // the name lives in other parts too: the distinct-name count of this query is settled over all parts.  One atomic per
+            // wavefront claims the slots of every lane that got here: the lowest of them adds their number, all read its answer.
+            const u64 m = __ballot(1);
+            const u32 before = (u32)__popcll(m & ((1ULL << lane_id()) - 1));
+            u32 base = 0;
+            if (before == 0) base = atomicAdd(cp.pair_cur, (u32)__popcll(m));
+            base = RFL(base);
+            const u32 slot = base + before;
+            if (slot < cp.pair_cap) cp.pairs[slot] = (u64)(cp.q_base + q) << 32 | cp.t_rank[rid];   // (never false: the host checks the cursor, a pair is not dropped silently)
+            return;
+        }
+        atomicAdd(&counts[q], 1u);
+        return;
+    }
     if (cp.mode == 0) atomicAdd(&counts[q], 1u);
     else if (cp.mode == 1) atomicAdd(&counts[rid], 1u);
     else {
@@ -125,6 +151,25 @@ __global__ void k_count(const u64 *__restrict__ skey, const u32 *__restrict__ gs
         atomicAdd(&counts[cp.q_map ? cp.q_map[q] : q], 1u);
         atomicAdd(&counts[rid + cp.rid_base], 1u);
     }
+}
+
+__global__ void k_count(const u64 *__restrict__ skey, const u32 *__restrict__ gstart, const u32 *__restrict__ gflags,
+                        const u32 *__restrict__ list, u32 n_list, CountParams cp, u32 *__restrict__ counts, u32 *__restrict__ has_map) {
+    count_group<false>(skey, gstart, gflags, list, n_list, cp, counts, has_map);
+}
+__global__ void k_count_shared(const u64 *__restrict__ skey, const u32 *__restrict__ gstart, const u32 *__restrict__ gflags,
+                               const u32 *__restrict__ list, u32 n_list, CountParams cp, u32 *__restrict__ counts, u32 *__restrict__ has_map) {
+    count_group<true>(skey, gstart, gflags, list, n_list, cp, counts, has_map);
+}
+
+// The (query, name) pairs of a call, sorted: a pair that differs from its predecessor is a target name the query has not counted yet.
+// n_distinct: their number (one atomic per wavefront).
+__global__ void k_name_pairs_count(const u64 *__restrict__ pairs, u32 n, u32 *__restrict__ counts, u32 *__restrict__ n_distinct) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool first = i < n && (i == 0 || pairs[i] != pairs[i - 1]);
+    if (first) atomicAdd(&counts[(u32)(pairs[i] >> 32)], 1u);
+    const u64 m = __ballot(first);
+    if (lane_id() == 0 && m) atomicAdd(n_distinct, (u32)__popcll(m));
 }
 
 // K8: per_read_estimate (estimate.rs:142-157), f32, explicit rounding per operation

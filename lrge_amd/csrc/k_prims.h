@@ -1093,6 +1093,10 @@ __global__ void k_gather_index_u32(const u32 *__restrict__ src, const u32 *__res
 }
 
 // out[i] = src[i * stride] (the starts of the 256 first-digit segments out of a scanned histogram)
+__global__ void k_gather_index_u64(const u64 *__restrict__ src, const u32 *__restrict__ idx, u32 n, u64 *__restrict__ out) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = src[idx[i]];
+}
 __global__ void k_gather_strided_u32(const u32 *__restrict__ src, u64 stride, u32 n, u32 *__restrict__ out) {
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = src[(u64)i * stride];
