@@ -404,18 +404,21 @@ int  lrge_hip_read_records_gpu_ex(lrge_hip_ctx *ctx, const char *path, int flags
 
 /* Read sets built on the device from FASTA / FASTQ text (k_fx_census, k_fx_summary, k_fx_scatter, k_fx_records,
    k_fx_names, k_fx_gather) and from unaligned BAM (k_bam_header, k_bam_find, k_bam_walk, k_bam_records,
-   k_bam_gather): the device-side form of the record reader (io.rs:154-184) and of the read selection that feeds the
+   k_bam_gather; SAM, DESIGN section 14: k_sam_mark, k_sam_records): the device-side form of the record reader (io.rs:154-184) and of the read selection that feeds the
    strategies (twoset.rs:122-201).  The file's bytes are decompressed into HBM and stay there; the records are found there; only
    the identifiers and the sequence lengths come back.
    lrge_hip_reads_open (io.rs:154-184) reads `path` into memory and calls lrge_hip_reads_open_mem (io.rs:154-184), which takes the
    bytes of a whole file.  `flags`: LRGE_GPU_INFLATE_BGZF | LRGE_GPU_INFLATE_GZIP choose the device decoders as in
    lrge_hip_read_records_gpu_ex; with neither, only uncompressed input is taken.  | LRGE_GPU_INGEST_BAM: text that starts with
    the BAM magic is scanned as unaligned BAM (every record with flag 4, found by a speculative walk of the length chain that
-   is proven from the end of the header); without the flag BAM is unproven, as it was before the flag existed.  The records
+   is proven from the end of the header); without the flag BAM is unproven, as it was before the flag existed.
+   | LRGE_GPU_INGEST_SAM: text that starts with "@HD", "@SQ" or "@RG" is scanned as unaligned SAM (every line that is neither
+   empty nor starts with '@' has ten tabs and a flag of 1 to 9 digits with bit 2 set); without the flag SAM is unproven.  The records
    equal those of lrge_hip_read_records on the same file, one for one.  LRGE_ERR_UNPROVEN: the device does not prove this input
    and produces no parse error of its own -- anything but FASTA, strict four-line FASTQ or (with its flag) well-formed unaligned
-   BAM (an empty line between records, a truncated record, a missing '+', SAM, CRAM, BAM without LRGE_GPU_INGEST_BAM, a BAM
-   with a mapped record, a damaged header or record, or bytes behind the last record), a compressed format without its flag or other than gzip, a damaged gzip file, text above option INGEST_MAX_BYTES
+   BAM (an empty line between records, a truncated record, a missing '+', CRAM, BAM without LRGE_GPU_INGEST_BAM, a BAM
+   with a mapped record, a damaged header or record, or bytes behind the last record, SAM without LRGE_GPU_INGEST_SAM, a SAM
+   record line with fewer than ten tabs, with a flag that is not plain digits or with a mapped flag), a compressed format without its flag or other than gzip, a damaged gzip file, text above option INGEST_MAX_BYTES
    (default: half of the free device memory plus the context's idle arena bytes); the caller takes lrge_hip_read_records*, which
    parses the file or gives the reference's message.  LRGE_ERR_TOO_MANY: 2^32 records or more, or a sequence of 2^32 bases or
    more.  LRGE_ERR_IO: the file cannot be read.  An empty file is LRGE_OK with a count of 0.
@@ -440,6 +443,7 @@ typedef struct lrge_hip_bam_stats {
     uint64_t rewalked_segments;  /* segments walked in those rounds */
 } lrge_hip_bam_stats;
 #define LRGE_GPU_INGEST_BAM 4
+#define LRGE_GPU_INGEST_SAM 8
 int      lrge_hip_reads_open(lrge_hip_ctx *ctx, const char *path, int flags, lrge_hip_reads **out);
 int      lrge_hip_reads_open_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, int flags, lrge_hip_reads **out);
 uint64_t lrge_hip_reads_count(const lrge_hip_reads *reads);

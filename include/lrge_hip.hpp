@@ -75,7 +75,7 @@ struct Ctx {
 };
 }  // namespace detail
 
-// The records of one FASTA / FASTQ file (or, with | LRGE_GPU_INGEST_BAM, one unaligned BAM) parsed on the device
+// The records of one FASTA / FASTQ file (or, with | LRGE_GPU_INGEST_BAM / LRGE_GPU_INGEST_SAM, one unaligned BAM / SAM) parsed on the device
 // (lrge_hip_reads_open, io.rs:154-184): identifiers and lengths on
 // the host, the bases resident in HBM as text.  Owns its context; the strategies built on it run in that context and take
 // their read sets with lrge_hip_seqset_from_reads.  open() gives nullptr for input the device does not prove (and for a file

@@ -13,6 +13,7 @@ ERR_IO, ERR_PARSE, ERR_TOO_MANY, ERR_TOO_FEW, ERR_DEVICE, ERR_MAP, ERR_DUPLICATE
 ERR_UNPROVEN = -10
 GPU_INFLATE_BGZF, GPU_INFLATE_GZIP = 1, 2
 GPU_INGEST_BAM = 4
+GPU_INGEST_SAM = 8
 PRESET_AVA_ONT, PRESET_AVA_PB = 0, 1
 
 T_NAMES = ["pack", "sketch", "index_sort", "index_table", "qfilter", "lookup", "expand", "anchor_sort", "group",

@@ -1,5 +1,5 @@
-// host_fastx.inl -- read sets built on the device from FASTA / FASTQ text (k_fastx.h) and from unaligned BAM
-// (k_bam.h, host_bam.inl): the text reaches HBM
+// host_fastx.inl -- read sets built on the device from FASTA / FASTQ text (k_fastx.h), from unaligned BAM
+// (k_bam.h, host_bam.inl) and from unaligned SAM (k_sam.h, host_sam.inl): the text reaches HBM
 // decompressed (BGZF chunks decoded into one block by the pipeline of host_inflate.inl, the gzip rounds appended device-to-device, plain input copied once), the
 // record scan runs there, only identifiers and lengths come back, and lrge_hip_seqset_from_reads gathers the selected reads
 // into dense ASCII for the device-source pack of host_seqset.inl.  Whatever the scan cannot prove is LRGE_ERR_UNPROVEN: the
@@ -140,6 +140,7 @@ static int fx_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R) {
 }
 
 #include "host_bam.inl"      // bam_parse_device: the same for unaligned BAM (needs the struct and the tail above)
+#include "host_sam.inl"      // sam_parse_device: the same for unaligned SAM
 
 // ---- text that stays in HBM ----
 // any other gzip input: the rounds of gz_run with GzDev keeping every round's bytes on the device (host_gzip.inl: keep_*).
@@ -224,15 +225,17 @@ extern "C" int lrge_hip_reads_open_mem(lrge_hip_ctx *ctx, const void *file_bytes
         R->n_text = len; raw_text = true;
     }
     const double t1 = fx_now_ms();
-    // BAM by its magic, when the caller asked for it: the first four text bytes are here already for raw input
-    bool is_bam = false;
-    if ((flags & LRGE_GPU_INGEST_BAM) && R->n_text >= 4) {
-        u8 head[4];
-        if (raw_text) memcpy(head, d, 4);
-        else { HIPCHK(ctx, hipMemcpyAsync(head, R->d_text, 4, hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); }
-        is_bam = head[0] == 'B' && head[1] == 'A' && head[2] == 'M' && head[3] == 1;
+    // BAM and SAM by their magic, when the caller asked for them: the first text bytes are here already for raw input
+    bool is_bam = false, is_sam = false;
+    if ((flags & (LRGE_GPU_INGEST_BAM | LRGE_GPU_INGEST_SAM)) && R->n_text >= 3) {
+        u8 head[4] = {0, 0, 0, 0};
+        const size_t k = (size_t)std::min<u64>(4, R->n_text);
+        if (raw_text) memcpy(head, d, k);
+        else { HIPCHK(ctx, hipMemcpyAsync(head, R->d_text, k, hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); }
+        is_bam = (flags & LRGE_GPU_INGEST_BAM) && R->n_text >= 4 && head[0] == 'B' && head[1] == 'A' && head[2] == 'M' && head[3] == 1;
+        is_sam = (flags & LRGE_GPU_INGEST_SAM) && sam_sniff(head, R->n_text);
     }
-    const int rc = is_bam ? bam_parse_device(ctx, R) : fx_parse_device(ctx, R);
+    const int rc = is_bam ? bam_parse_device(ctx, R) : is_sam ? sam_parse_device(ctx, R) : fx_parse_device(ctx, R);
     if (rc) return rc;
     const double t2 = fx_now_ms();
     R->ms[0] = (float)(t1 - t0); R->ms[1] = (float)(t2 - t1) - R->ms[2]; R->ms[3] = (float)(t2 - t0);

@@ -1,0 +1,68 @@
+// host_sam.inl -- the record scan of unaligned SAM text in HBM (k_sam.h): the line table by the census and
+// scatter passes of the FASTQ scan, a mark and a rank per line, then a wavefront per record line.  Included into host_fastx.inl,
+// whose tail (fx_tables_to_host) brings the identifiers and the lengths down.
+
+// the caller has seen the SAM magic at the start of R->d_text
+static int sam_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R) {
+    const u64 n = R->n_text;
+    const u8 *t = R->d_text;
+    R->name_off.assign(1, 0);
+    hipStream_t st = ctx->stream;
+    Scratch sc(ctx);
+    ctx->pin_items.clear(); ctx->pin_used = 0;
+    const u64 n_tiles = div_up(n, FX_TILE);
+    if (n_tiles >> 31) return fx_verdict_rc(ctx, FX_UNPROVEN, "text of 8 TiB or more");
+    // the line starts, as for FASTQ
+    ALLOC_OR_FAIL(c_lf, sc, u32, n_tiles);
+    ALLOC_OR_FAIL(c_rem, sc, u32, n_tiles);
+    ALLOC_OR_FAIL(c_hdr, sc, u32, n_tiles);
+    ALLOC_OR_FAIL(d_sum, sc, FxSummary, 1);
+    hipLaunchKernelGGL(k_fx_census, dim3((u32)n_tiles), dim3(FX_THREADS), 0, st, t, n, c_lf, c_rem, c_hdr);
+    KCHK(ctx);
+    hipLaunchKernelGGL(k_fx_summary, dim3(1), dim3(FX_THREADS), 0, st, t, n, (const u32 *)c_lf, (const u32 *)c_rem, (const u32 *)c_hdr, n_tiles, d_sum);
+    KCHK(ctx);
+    FxSummary hs;
+    HIPCHK(ctx, ctx->d2h(&hs, d_sum, sizeof hs, st));
+    HIPCHK(ctx, ctx->d2h_sync(st));
+    FxCensus c;
+    memset(&c, 0, sizeof c);
+    c.n_lf = hs.n_lf; c.first = hs.first; c.last = hs.last;
+    u32 verdict = fx_limits(FX_FMT_FASTQ, c);
+    if (!verdict && (c.n_lf + 1) >> 32) verdict = FX_UNPROVEN;
+    if (verdict) return fx_verdict_rc(ctx, verdict, "line count");
+    const u64 n_lines = c.n_lf + 1;                         // (the last one is empty when the text ends with a line feed)
+    int rc;
+    if ((rc = scan_exclusive_u32(ctx, sc, c_lf, c_lf, n_tiles, nullptr))) return rc;
+    ALLOC_OR_FAIL(ls, sc, u64, n_lines);
+    ALLOC_OR_FAIL(d_lines, sc, u64, 2);
+    hipLaunchKernelGGL(k_fx_scatter, dim3((u32)n_tiles), dim3(FX_THREADS), 0, st, t, n, (int)FX_FMT_FASTQ, (const u32 *)c_lf, (const u32 *)c_rem, (const u32 *)c_hdr, c.first,
+                       c.last, ls, d_lines, (u64 *)nullptr, (u32 *)nullptr);
+    KCHK(ctx);
+    // which lines carry a record, and the rank of each
+    ALLOC_OR_FAIL(d_mark, sc, u32, n_lines);
+    ALLOC_OR_FAIL(d_rank, sc, u32, n_lines);
+    ALLOC_OR_FAIL(d_flags, sc, u64, 3);                   // [0]: verdict bits (low word), [1]: identifier bytes, [2]: records (low word)
+    HIPCHK(ctx, hipMemsetAsync(d_flags, 0, 24, st));
+    hipLaunchKernelGGL(k_sam_mark, dim3((u32)div_up(n_lines, SAM_THREADS)), dim3(SAM_THREADS), 0, st, t, n, (const u64 *)ls, c.n_lf, n_lines, d_mark);
+    KCHK(ctx);
+    if ((rc = scan_exclusive_u32(ctx, sc, d_mark, d_rank, n_lines, (u32 *)(d_flags + 2)))) return rc;
+    u64 flags[3] = {0, 0, 0};
+    HIPCHK(ctx, ctx->d2h(flags + 2, d_flags + 2, 8, st));
+    HIPCHK(ctx, ctx->d2h_sync(st));
+    const u64 n_rec = flags[2];
+    if (!n_rec) { R->fmt = FX_FMT_SAM; return LRGE_OK; }    // header lines only: the host returns no record
+    hipError_t e = hipSuccess;
+    if (!(R->d_recs = (FxRec *)ctx->pool.alloc((size_t)n_rec * sizeof(FxRec), &e))) { LRGE_SET_ERR(ctx, "reads_open: record table: %s", hipGetErrorString(e)); return LRGE_ERR_DEVICE; }
+    ALLOC_OR_FAIL(d_seq_len, sc, u32, n_rec);
+    ALLOC_OR_FAIL(d_name_len, sc, u32, n_rec);
+    const u32 grid = (u32)std::min<u64>(div_up(n_lines, SAM_WAVES), (u64)ctx->n_cu * 8);
+    hipLaunchKernelGGL(k_sam_records, dim3(grid), dim3(SAM_THREADS), 0, st, t, n, (const u64 *)ls, c.n_lf, n_lines, (const u32 *)d_mark, (const u32 *)d_rank, R->d_recs,
+                       d_seq_len, d_name_len, (u32 *)d_flags, (unsigned long long *)(d_flags + 1));
+    KCHK(ctx);
+    HIPCHK(ctx, ctx->d2h(flags, d_flags, 16, st));
+    HIPCHK(ctx, ctx->d2h_sync(st));
+    if ((u32)flags[0]) return fx_verdict_rc(ctx, (u32)flags[0], "a SAM record line outside the strict form");
+    if (flags[1] >> 32) return fx_verdict_rc(ctx, FX_UNPROVEN, "4 GiB of identifiers or more");
+    R->fmt = FX_FMT_SAM;                                    // (a refused file leaves no read set, so no format either)
+    return fx_tables_to_host(ctx, R, sc, n_rec, d_seq_len, d_name_len, flags[1]);
+}

@@ -30,6 +30,7 @@
 #include "k_gzip.h"
 #include "k_fastx.h"
 #include "k_bam.h"
+#include "k_sam.h"
 #include "../../include/lrge_rand.hpp"
 #include "../../include/lrge_io.hpp"
 

@@ -1,8 +1,10 @@
 """FASTQ file -> read set consumable on the device: the device ingest (lrge_hip_reads_open + lrge_hip_seqset_from_reads) against
 the route without it (lrge_hip_read_records_gpu_ex into per-record strings, concatenation into the upload arrays,
 lrge_hip_seqset_upload), on one synthetic FASTQ (the seeded parts of tools/gzip_bench.py) raw, in BGZF and as plain gzip, and on
-the same reads as a BGZF unaligned BAM (written here from the SAM/BAM specification) at several BAM_SEGMENT_BYTES.  Usage:
-  python tools/ingest_bench.py [--gbases 1.08] [--dir /tmp] [--reps 5] [--kinds fq,bgzf.fq.gz,fq.gz,bam]
+the same reads as a BGZF unaligned BAM (written here from the SAM/BAM specification) at several BAM_SEGMENT_BYTES and as plain
+unaligned SAM text (the "sam" kind: its record scan beside the FASTQ kind's, and the host reader's time on the same file).  Only
+the files of the kinds asked for are written.  Usage:
+  python tools/ingest_bench.py [--gbases 1.08] [--dir /tmp] [--reps 5] [--kinds fq,bgzf.fq.gz,fq.gz,bam,sam]
                                [--bam-segments 262144,1048576,4194304] [--out profiles/ingest_bench.json]
 
 Both routes are driven by a small C++ helper (compiled here with g++ against liblrge_hip.so), so that no Python callback sits
@@ -106,6 +108,15 @@ def _ubam(fq):
     return b"".join(out)
 
 
+SAM_HEADER = b"@HD\tVN:1.6\tSO:unknown\n"
+
+
+def _usam(fq):
+    """the reads of a FASTQ part as unaligned SAM lines (SAM specification 1.4): flag 4, no reference, qualities kept"""
+    lines = fq.split(b"\n")
+    return b"".join(b"%s\t4\t*\t0\t0\t*\t*\t0\t0\t%s\t%s\n" % (lines[i][1:].split()[0], lines[i + 1], lines[i + 3]) for i in range(0, len(lines) - 1, 4))
+
+
 def _bgzf(data, block=65280, level=1):
     """`data` as BGZF members (SAM/BAM specification 4.1), without the end-of-file block"""
     out = []
@@ -117,26 +128,46 @@ def _bgzf(data, block=65280, level=1):
     return b"".join(out)
 
 
-def _bgzf_part(idx):
+KINDS = ("fq", "bgzf.fq.gz", "fq.gz", "bam", "sam")
+
+
+def _part(args):
+    """(kind -> (text bytes, file bytes)) of part idx, for the kinds asked for"""
     import bgzf_writer as W
     import gzip_bench as GB
+    idx, kinds = args
     d = GB._fastq(idx)
-    c = zlib.compressobj(1, zlib.DEFLATED, 31)
-    bam = (BAM_HEADER if idx == 0 else b"") + _ubam(d)
-    return len(d), d, W.bgzf_compress(d, eof=False, level=1), c.compress(d) + c.flush(), len(bam), _bgzf(bam)
+    out = {}
+    if "fq" in kinds:
+        out["fq"] = (len(d), d)
+    if "bgzf.fq.gz" in kinds:
+        out["bgzf.fq.gz"] = (len(d), W.bgzf_compress(d, eof=False, level=1))
+    if "fq.gz" in kinds:
+        c = zlib.compressobj(1, zlib.DEFLATED, 31)
+        out["fq.gz"] = (len(d), c.compress(d) + c.flush())                  # (the plain gzip file: one member per part)
+    if "bam" in kinds:
+        bam = (BAM_HEADER if idx == 0 else b"") + _ubam(d)
+        out["bam"] = (len(bam), _bgzf(bam))
+    if "sam" in kinds:
+        sam = (SAM_HEADER if idx == 0 else b"") + _usam(d)
+        out["sam"] = (len(sam), sam)
+    return out
 
 
-def write_files(d, parts):
+def write_files(d, parts, kinds):
     import bgzf_writer as W
-    paths = {k: os.path.join(d, "ingest." + k) for k in ("fq", "bgzf.fq.gz", "fq.gz", "bam")}
+    paths = {k: os.path.join(d, "ingest." + k) for k in kinds}
     size = {k: 0 for k in paths}
-    with mp.get_context("spawn").Pool(16) as pool, open(paths["fq"], "wb") as fr, open(paths["bgzf.fq.gz"], "wb") as fb, open(paths["fq.gz"], "wb") as fg, \
-            open(paths["bam"], "wb") as fm:
-        for n, raw, bg, gz, n_bam, bam in pool.imap(_bgzf_part, range(parts)):
-            fr.write(raw); fb.write(bg); fg.write(gz); fm.write(bam)        # (the plain gzip file: one member per part)
-            for k in paths:
-                size[k] += n_bam if k == "bam" else n
-        fb.write(W.EOF_BLOCK); fm.write(W.EOF_BLOCK)
+    files = {k: open(p, "wb") for k, p in paths.items()}
+    with mp.get_context("spawn").Pool(16) as pool:
+        for part in pool.imap(_part, [(i, tuple(kinds)) for i in range(parts)]):
+            for k, (n, data) in part.items():
+                files[k].write(data)
+                size[k] += n
+    for k, fh in files.items():
+        if k in ("bgzf.fq.gz", "bam"):
+            fh.write(W.EOF_BLOCK)
+        fh.close()
     return paths, size
 
 
@@ -145,7 +176,7 @@ def main():
     ap.add_argument("--gbases", type=float, default=1.08)
     ap.add_argument("--dir", default=tempfile.gettempdir())
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--kinds", default="fq,bgzf.fq.gz,fq.gz,bam")
+    ap.add_argument("--kinds", default=",".join(KINDS))
     ap.add_argument("--bam-segments", default="262144,1048576,4194304")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ingest_bench.json"))
     a = ap.parse_args()
@@ -158,16 +189,17 @@ def main():
                            "-L" + B.LIB_DIR, "-llrge_hip", "-Wl,-rpath," + B.LIB_DIR])
     parts = max(1, round(a.gbases * 1e9 * 2.02 / (256 << 20)))       # a record is 2 bytes per base and a header
     t0 = time.perf_counter()
-    paths, text_bytes = write_files(work, parts)
+    kinds = [k for k in KINDS if k in a.kinds.split(",")]
+    paths, text_bytes = write_files(work, parts, kinds)
     print("files written in %.0f s: %s text bytes" % (time.perf_counter() - t0, text_bytes), flush=True)
     ctx = engine.Context(0)
     H = C.CDLL(so)
     H.route_host.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_double * 3), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     H.route_device.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_double * 2), C.POINTER(C.c_float * 4), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                C.POINTER(C.c_uint64), C.POINTER(C.c_uint64 * 6)]
-    result = {"text_bytes": text_bytes["fq"], "bam_text_bytes": text_bytes["bam"], "reps": a.reps, "files": {}}
+    result = {"text_bytes": text_bytes, "reps": a.reps, "files": {}}
     # (a BAM run per segment size: the host route it is compared with does not depend on the option, and is timed beside each)
-    work_list = [(k, k, None) for k in a.kinds.split(",") if k != "bam"] + [("bam", "bam@%d" % int(S), int(S)) for S in a.bam_segments.split(",") if "bam" in a.kinds.split(",")]
+    work_list = [(k, k, None) for k in kinds if k != "bam"] + [("bam", "bam@%d" % int(S), int(S)) for S in a.bam_segments.split(",") if "bam" in kinds]
     for kind, label, seg in work_list:
         p = paths[kind]
         ctx.set_option("BAM_SEGMENT_BYTES", None if seg is None else str(seg))
@@ -180,7 +212,7 @@ def main():
             rc = H.route_host(ctx.h, p.encode(), 3, C.byref(ms3), C.byref(nr), C.byref(nb))
             assert rc == 0, (kind, rc)
             ms2, st, nr2, nb2, tb, bs = (C.c_double * 2)(), (C.c_float * 4)(), C.c_uint64(), C.c_uint64(), C.c_uint64(), (C.c_uint64 * 6)()
-            rc = H.route_device(ctx.h, p.encode(), 7, C.byref(ms2), C.byref(st), C.byref(nr2), C.byref(nb2), C.byref(tb), C.byref(bs))
+            rc = H.route_device(ctx.h, p.encode(), 15, C.byref(ms2), C.byref(st), C.byref(nr2), C.byref(nb2), C.byref(tb), C.byref(bs))
             assert rc == 0, (kind, rc, ctx._lib.lrge_hip_last_error(ctx.h))
             assert (nr.value, nb.value) == (nr2.value, nb2.value) and tb.value == text_bytes[kind]
             if rep:                                                    # (run 0 is the warm-up)
@@ -190,6 +222,7 @@ def main():
         rng = lambda runs, k: (min(r[k] for r in runs), max(r[k] for r in runs))   # noqa: E731
         f = dict(file_bytes=os.path.getsize(p), reads=nr.value, bases=nb.value, host_route=runs_h, device_route=runs_d,
                  host_total_ms_median=med(runs_h, "total_ms"), host_total_ms_range=rng(runs_h, "total_ms"),
+                 host_records_ms_median=med(runs_h, "records_ms"), host_records_ms_range=rng(runs_h, "records_ms"),
                  device_total_ms_median=med(runs_d, "total_ms"), device_total_ms_range=rng(runs_d, "total_ms"),
                  scan_ms_median=med(runs_d, "scan_ms"), scan_ms_range=rng(runs_d, "scan_ms"), scan_text_gb_per_s=text_bytes[kind] / med(runs_d, "scan_ms") / 1e6)
         if seg is not None:

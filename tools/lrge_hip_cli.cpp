@@ -83,7 +83,7 @@ int main(int argc, char **argv) {
         else if (a == "--device") device = atoi(need(i));
         else if (a == "--gpu-inflate") gpu_inflate = true;       // BGZF input (BAM, bgzip FASTQ) decompressed on --device
         else if (a == "--gpu-gzip") gpu_gzip = true;             // every gzip input (plain, multi-member, BGZF) decompressed on --device
-        else if (a == "--gpu-ingest") { gpu_ingest = true; gpu_gzip = true; }   // FASTA / FASTQ / unaligned BAM parsed on --device too: the bases never reach host memory (implies --gpu-gzip)
+        else if (a == "--gpu-ingest") { gpu_ingest = true; gpu_gzip = true; }   // FASTA / FASTQ / unaligned BAM / unaligned SAM parsed on --device too: the bases never reach host memory (implies --gpu-gzip)
         else if (a == "--dump-records") dump_records = true;   // host-only: print "id<TAB>sequence" per record and exit (tests)
         else if (a == "-q" || a == "--quiet") ++quiet; else if (a == "-qq") quiet += 2; else if (a == "-qqq") quiet += 3;
         else if (a == "-v" || a == "--verbose") ++verbose; else if (a == "-vv") verbose += 2;
@@ -105,7 +105,7 @@ int main(int argc, char **argv) {
         // --gpu-ingest: input the device does not prove takes the usual route below, which parses it or reports it
         std::unique_ptr<lrge::DeviceReads> dev;
         if (gpu_ingest) {
-            dev = lrge::DeviceReads::open(input, LRGE_GPU_INFLATE_BGZF | LRGE_GPU_INFLATE_GZIP | LRGE_GPU_INGEST_BAM, device);
+            dev = lrge::DeviceReads::open(input, LRGE_GPU_INFLATE_BGZF | LRGE_GPU_INFLATE_GZIP | LRGE_GPU_INGEST_BAM | LRGE_GPU_INGEST_SAM, device);
             if (info) fprintf(stderr, "[INFO] gpu-ingest: %s\n", dev ? "device" : "host");
             if (dev && dev->names.empty()) throw lrge::LrgeError(LRGE_ERR_IO, "IO error: Is the file empty?");
         }
