@@ -201,12 +201,33 @@ int  lrge_hip_index_build_sharded(lrge_hip_ctx *ctx, const uint32_t *all_target_
    crosses a link.  Collective: every rank of `comm` calls it; a failure on one rank fails it on all (the build ends with an
    agreement: no rank leaves with LRGE_OK alone).
    PRECONDITION the caller checks (it holds every target's name rank; lrge_amd/parallel.py: cross_shard_duplicates, the Rust shim):
-   no target identifier occurs in two DIFFERENT shards.  The reference counts distinct target NAMES (twoset.rs:286-317) and never
-   rejects a duplicate id in this mode; a duplicate inside one shard is counted once, one across shards would be counted once per
-   shard.  (The parts of a partitioned single-GPU index -- of one rank's share here as well -- have no such limit:
+   no target identifier occurs in two DIFFERENT shards -- or call lrge_hip_overlap_twoset_tsharded, which counts such a name once.
+   The reference counts distinct target NAMES (twoset.rs:286-317) and never rejects a duplicate id in this mode; a duplicate inside
+   one shard is counted once, one across shards would be counted once per shard by lrge_hip_overlap_twoset and the caller's sum.
+   (The parts of a partitioned single-GPU index -- of one rank's share here as well -- have no such limit:
    lrge_hip_overlap_twoset counts a name its parts share once per query.) */
 int  lrge_hip_index_build_tsharded(lrge_hip_ctx *ctx, const lrge_hip_seqset *target_shard, int preset, lrge_hip_comm *comm,
                                    lrge_hip_index **out);
+/* Two-set forward over the ranks of a target-sharded world, whatever names the shards share: collective.  Every rank of `comm`
+   calls it with the index lrge_hip_index_build_tsharded gave it on that communicator and with the SAME query set in the same order;
+   on return every rank holds counts[] and has_mapping[] (0 / 1) of the WHOLE job -- the all-reduce that closes the step is inside.
+   The result is what one index over all targets gives, bit for bit: the reference inserts target_name into a HashSet per query
+   (twoset.rs:286-317), so a name borne by reads of two shards counts once.  The ranks find the names that occur in two or more
+   shards (an all-gather of every shard's distinct name ranks); a kept mapping onto a bearer of such a name leaves a
+   (query, name) pair instead of a count, the distinct pairs travel to the rank that owns the query (contiguous query ranges in
+   rank order, one variable-size all-to-all) and are counted there once.  When no name is shared across shards nothing of this
+   runs: the call is lrge_hip_overlap_twoset between two small all-gathers and the closing all-reduce.
+   LRGE_C_SHARED_NAME_PAIRS: pairs this rank emitted; LRGE_C_SHARED_NAME_DISTINCT: distinct pairs this rank counted as owner.
+   A failure on one rank fails the call on every rank (the call ends with an all-reduce that carries a status word; no rank is
+   left waiting).  LRGE_ERR_INVALID, on every rank: `ix` belongs to another context or is not this communicator's target-sharded
+   index on some rank, some shards were uploaded with name ranks and others without (NULL ranks = all distinct: shares nothing),
+   the query sets differ in size.  ONE refusal cannot travel: a NULL `comm` or a `comm` of another context is LRGE_ERR_INVALID
+   on that rank alone, before any collective (there is no communicator of this context to say it through) -- the caller MUST then
+   call lrge_hip_comm_abort on the communicator its peers are using, or they wait in the first all-gather.  LRGE_ERR_TOO_MANY: 2^32
+   pairs at one owner.  Inverse and all-vs-all keep LRGE_ERR_DUPLICATE_ID: the reference rejects duplicates there. */
+int  lrge_hip_overlap_twoset_tsharded(lrge_hip_ctx *ctx, const lrge_hip_index *ix, const lrge_hip_seqset *queries,
+                                      const lrge_hip_params *p, lrge_hip_comm *comm,
+                                      uint32_t *counts, uint32_t *has_mapping);
 /* Exchange volumes of the last lrge_hip_index_build_sharded on this context: {key-set bytes contributed, entries sketched here,
    entries sent to other ranks, entries received from other ranks, hashes sent, hashes received, bytes per entry | bytes per hash << 8
    (4 when the hash has at most 32 bits: k = 15), entries kept}. */

@@ -82,6 +82,8 @@ extern "C" {
     fn lrge_hip_index_free(ix: *mut lrge_hip_index);
     fn lrge_hip_overlap_twoset(ctx: *mut lrge_hip_ctx, ix: *const lrge_hip_index, queries: *const lrge_hip_seqset,
                                p: *const lrge_hip_params, counts: *mut u32, has_mapping: *mut u32) -> c_int;
+    fn lrge_hip_overlap_twoset_tsharded(ctx: *mut lrge_hip_ctx, ix: *const lrge_hip_index, queries: *const lrge_hip_seqset,
+                                        p: *const lrge_hip_params, comm: *mut lrge_hip_comm, counts: *mut u32, has_mapping: *mut u32) -> c_int;
     fn lrge_hip_overlap_inverse(ctx: *mut lrge_hip_ctx, ix: *const lrge_hip_index, streamed: *const lrge_hip_seqset,
                                 p: *const lrge_hip_params, counts: *mut u32) -> c_int;
     fn lrge_hip_overlap_ava(ctx: *mut lrge_hip_ctx, ix: *const lrge_hip_index, reads: *const lrge_hip_seqset,
@@ -182,6 +184,16 @@ impl Ctx {
         let n = queries.n as usize;
         let (mut counts, mut has) = (vec![0u32; n.max(1)], vec![0u32; n.max(1)]);
         check!(self.h, lrge_hip_overlap_twoset(self.h, ix.h, queries.h, p, counts.as_mut_ptr(), has.as_mut_ptr()));
+        counts.truncate(n); has.truncate(n);
+        Ok((counts, has))
+    }
+
+    /// The same over the ranks of a target-sharded world, collective (`lrge_hip_overlap_twoset_tsharded`): the counts and has_mapping
+    /// of the WHOLE job on every rank, a target name counted once per query whichever shards bear it (twoset.rs:286-317).
+    fn overlap_twoset_tsharded(&self, ix: &Index, queries: &SeqSet, p: &lrge_hip_params, comm: &Comm) -> crate::Result<(Vec<u32>, Vec<u32>)> {
+        let n = queries.n as usize;
+        let (mut counts, mut has) = (vec![0u32; n.max(1)], vec![0u32; n.max(1)]);
+        check!(self.h, lrge_hip_overlap_twoset_tsharded(self.h, ix.h, queries.h, p, comm.h, counts.as_mut_ptr(), has.as_mut_ptr()));
         counts.truncate(n); has.truncate(n);
         Ok((counts, has))
     }
@@ -430,7 +442,9 @@ pub fn shard_by_bases(lens: &[u32], world: usize) -> Vec<usize> {
 /// human-scale jobs): every rank uploads and indexes ITS contiguous share of the target reads and maps ALL queries against it;
 /// `lrge_hip_index_build_tsharded` makes the occurrence statistics (mid_occ) those of the one index, the count vectors of the
 /// ranks add up (disjoint targets: twoset.rs:286-317 counts distinct target names) in one all-reduce, and the estimates are
-/// computed once from the summed counts.  No index entry crosses a link.
+/// computed once from the summed counts.  No index entry crosses a link.  A target name borne by reads of two shards (a
+/// concatenated or re-basecalled file) would be counted once per shard that way: such a set takes the collective
+/// `lrge_hip_overlap_twoset_tsharded` for the overlap step, which counts the name once and closes the step itself.
 pub fn twoset_estimates_target_sharded(job: &TwoSetJob, devices: &[i32]) -> crate::Result<(Vec<f32>, u32)> {
     let world = devices.len();
     if world <= 1 { return twoset_estimates(job); }
@@ -440,7 +454,7 @@ pub fn twoset_estimates_target_sharded(job: &TwoSetJob, devices: &[i32]) -> crat
     let ranks = name_ranks(&[&t.names, &q.names]);
     let (q_lens, t_lens) = (q.lens(), t.lens());
     let t_bounds = shard_by_bases(&t_lens, world);
-    if cross_shard_duplicates(&ranks[0], &t_bounds) { return twoset_estimates_multi(job, devices); }   // (names shared across shards: sharded by query instead)
+    let shared_names = cross_shard_duplicates(&ranks[0], &t_bounds);   // (names shared across shards: the collective overlap call counts them once)
     let mut group = ptr::null_mut();
     check!(ptr::null(), lrge_hip_comm_local_group_create(world as c_int, &mut group));
     let group = SendPtr(group);
@@ -467,6 +481,13 @@ pub fn twoset_estimates_target_sharded(job: &TwoSetJob, devices: &[i32]) -> crat
                 let mut h = ptr::null_mut();
                 check!(ctx.h, lrge_hip_index_build_tsharded(ctx.h, ts.h, preset, comm.h, &mut h));   // collective, and failure-collective
                 let ix = Index { h, _ctx: &ctx };
+                if shared_names {
+                    // collective, and failure-collective: every rank leaves with the counts of the whole job, or every rank with an error
+                    let (counts, has) = ctx.overlap_twoset_tsharded(&ix, &qs, &p, &comm)?;
+                    comm.done();
+                    let est = ctx.estimates(&counts, q_lens, job.avg_target_len, job.target_num_reads as u64, 100)?;
+                    return Ok((est, has.iter().filter(|&&h| h == 0).count() as u32));
+                }
                 // The overlap call is this rank's own: if it fails the rank STILL enters the all-reduce that closes the step -- zeros
                 // and a status word -- and returns its error afterwards; its peers see the word and fail too.  One vector
                 // [counts | has_mapping | status]: disjoint targets, so the counts add up and has_mapping ORs.
@@ -512,7 +533,7 @@ impl Drop for Comm {
 
 /// True if a target identifier occurs in two DIFFERENT shards (`bounds` from `shard_by_bases`; equal names <=> equal rank).  The
 /// shards' distinct-target counts add up only over disjoint names (twoset.rs:286-317 counts `target_name`s and never rejects a
-/// duplicate id): such a set goes to `twoset_estimates_multi` (queries sharded) or to one GPU.
+/// duplicate id): such a set takes `lrge_hip_overlap_twoset_tsharded` for its overlap step.
 pub fn cross_shard_duplicates(target_ranks: &[u32], bounds: &[usize]) -> bool {
     let mut rp: Vec<(u32, u32)> = Vec::with_capacity(target_ranks.len());
     for s in 0..bounds.len() - 1 { for i in bounds[s]..bounds[s + 1] { rp.push((target_ranks[i], s as u32)); } }

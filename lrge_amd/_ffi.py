@@ -42,7 +42,7 @@ EXPORTS = [
     "lrge_hip_comm_unique_id", "lrge_hip_comm_create", "lrge_hip_comm_local_group_create", "lrge_hip_comm_local_group_destroy",
     "lrge_hip_comm_create_local", "lrge_hip_comm_create_host", "lrge_hip_comm_destroy", "lrge_hip_comm_abort", "lrge_hip_comm_rank", "lrge_hip_comm_world",
     "lrge_hip_comm_allreduce_u32", "lrge_hip_comm_allgather", "lrge_hip_index_stats",
-    "lrge_hip_overlap_twoset", "lrge_hip_overlap_inverse", "lrge_hip_overlap_ava", "lrge_hip_chains",
+    "lrge_hip_overlap_twoset", "lrge_hip_overlap_twoset_tsharded", "lrge_hip_overlap_inverse", "lrge_hip_overlap_ava", "lrge_hip_chains",
     "lrge_hip_estimates", "lrge_hip_median", "lrge_hip_paf_stats",
     "lrge_hip_unique_random_set", "lrge_hip_chacha_block",
     "lrge_hip_sketch_dump", "lrge_hip_index_dump", "lrge_hip_anchors_dump",
@@ -147,6 +147,7 @@ def lib():
     L.lrge_hip_index_free.restype = None
     L.lrge_hip_index_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]
     L.lrge_hip_overlap_twoset.argtypes = [vp, vp, vp, C.POINTER(Params), vp, vp]
+    L.lrge_hip_overlap_twoset_tsharded.argtypes = [vp, vp, vp, C.POINTER(Params), vp, vp, vp]
     L.lrge_hip_overlap_inverse.argtypes = [vp, vp, vp, C.POINTER(Params), vp]
     L.lrge_hip_overlap_ava.argtypes = [vp, vp, vp, C.POINTER(Params), vp]
     L.lrge_hip_chains.argtypes = [vp, vp, vp, C.c_int, vp, C.c_uint64, C.POINTER(C.c_uint64)]

@@ -128,59 +128,84 @@ static int twoset_one_index(lrge_hip_ctx *ctx, const lrge_hip_index *ix, const l
     return LRGE_OK;
 }
 
-extern "C" int lrge_hip_overlap_twoset(lrge_hip_ctx *ctx, const lrge_hip_index *ix, const lrge_hip_seqset *queries,
-                                       const lrge_hip_params *p, uint32_t *counts, uint32_t *has_mapping) {
-    int rc = check_common(ctx, ix, queries, /*parts_ok=*/true);
-    if (rc) return rc;
-    OverlapJob job; job.mode = MODE_TWOSET; job.dual = 1;
-    job.prm = p ? *p : lrge_hip_params{0, 0.2f};
-    job.counts = counts; job.has_map = has_mapping;
-    StageAcc acc;
+// ---- names shared across the parts of one index / the shards of a world (NamePairs, host_overlap_seeds.inl) ----
+// the units a forward call maps against one after the other: the parts of a partitioned index, or the index itself
+static std::vector<const lrge_hip_index *> index_units(const lrge_hip_index *ix) {
+    if (ix->parts.empty()) return {ix};
+    return std::vector<const lrge_hip_index *>(ix->parts.begin(), ix->parts.end());
+}
+// name ranks borne by reads of two or more different PARTS of `ix`, ascending (none without parts or without repeated identifiers)
+static std::vector<u32> names_shared_across_parts(const lrge_hip_index *ix, u32 *max_rank) {
+    std::vector<u32> shared;
+    if (ix->parts.empty() || !ix->seqs || !ix->seqs->dup_rank) return shared;
+    std::vector<std::pair<u32, u32>> rp;      // (name rank, part)
+    for (size_t pi = 0; pi < ix->parts.size(); ++pi)
+        for (u32 r : ix->parts[pi]->seqs->h_rank) rp.emplace_back(r, (u32)pi);
+    std::sort(rp.begin(), rp.end());
+    for (size_t i = 1; i < rp.size(); ++i)
+        if (rp[i].first == rp[i - 1].first && rp[i].second != rp[i - 1].second && (shared.empty() || shared.back() != rp[i].first)) shared.push_back(rp[i].first);
+    if (!rp.empty()) *max_rank = std::max(*max_rank, rp.back().first);
+    return shared;
+}
+// The pair sink of a call and the bitmap of every unit: one bit per read of the unit, set when its name is in `shared` (ascending
+// name ranks: the names that also occur in another part -- or, for lrge_hip_overlap_twoset_tsharded, in another shard).  A unit
+// without a flagged read gets no bitmap and runs plain k_count.
+static int name_pairs_setup(lrge_hip_ctx *ctx, const lrge_hip_index *ix, u32 nq, const std::vector<u32> &shared, u32 max_rank, std::unique_ptr<NamePairs> &np) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const std::vector<const lrge_hip_index *> units = index_units(ix);
+    np.reset(new NamePairs(ctx));
+    np->bits_q = std::max<u32>(1, ceil_log2_u64((u64)nq));
+    np->bits_rank = std::max<u32>(1, ceil_log2_u64((u64)max_rank + 1));
+    np->d_bits.assign(units.size(), nullptr);
+    if (shared.empty()) return LRGE_OK;
+    std::vector<std::vector<u32>> h_bits(units.size());     // (read by the copies until the sync below)
+    for (size_t pi = 0; pi < units.size(); ++pi) {
+        const std::vector<u32> &hr = units[pi]->seqs->h_rank;
+        std::vector<u32> &w = h_bits[pi];
+        w.assign(hr.size() / 32 + 1, 0u);
+        bool any = false;
+        for (size_t r = 0; r < hr.size(); ++r)
+            if (std::binary_search(shared.begin(), shared.end(), hr[r])) { w[r >> 5] |= 1u << (r & 31); any = true; }
+        if (!any) continue;               // (a unit without a shared name: plain k_count)
+        hipError_t e = hipErrorOutOfMemory;
+        np->d_bits[pi] = (u32 *)ctx->pool.alloc(w.size() * 4, &e);
+        if (!np->d_bits[pi]) { LRGE_SET_ERR(ctx, "device allocation of %zu bytes for a part's shared-name bitmap failed: %s", w.size() * 4, hipGetErrorString(e)); return LRGE_ERR_DEVICE; }
+        HIPCHK(ctx, hipMemcpyAsync(np->d_bits[pi], w.data(), w.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return LRGE_OK;
+}
+// The pass behind the last part that settles the shared names (NamePairs::resolve, or the exchange of the target-sharded world): a
+// short pass of its own -- its sort's launches and its time join the call's counters and timings
+template <typename F>
+static int name_pairs_pass(lrge_hip_ctx *ctx, StageAcc &acc, F pass) {
+    const u64 split = ctx->counters[LRGE_C_LPG_SPLIT];
+    memset(ctx->ms, 0, sizeof(ctx->ms)); memset(ctx->counters, 0, sizeof(ctx->counters));
+    int rc;
+    {
+        StageTimer t_total(ctx, LRGE_T_TOTAL), t_count(ctx, LRGE_T_COUNT);
+        rc = pass();
+    }
+    (void)hipStreamSynchronize(ctx->stream);
+    ctx->resolve_timers();
+    ctx->counters[LRGE_C_LPG_SPLIT] = split;
+    acc.add(ctx);
+    return rc;
+}
+
+// Forward two-set of all queries against this context's index -- one index or its parts -- with the pairs of shared names left in
+// `np` (may be null: no shared name).  counts / has_mapping: nq entries each, or null.
+static int twoset_local(lrge_hip_ctx *ctx, const lrge_hip_index *ix, const lrge_hip_seqset *queries, const OverlapJob &job, NamePairs *np,
+                        uint32_t *counts, uint32_t *has_mapping, StageAcc &acc) {
     if (ix->parts.empty()) {
-        rc = twoset_one_index(ctx, ix, queries, job, acc);
-        acc.store(ctx);
-        return rc;
+        OverlapJob j = job;
+        j.counts = counts; j.has_map = has_mapping;
+        if (np && np->d_bits[0]) { j.name_pairs = np; j.d_shared_bits = np->d_bits[0]; }
+        return twoset_one_index(ctx, ix, queries, j, acc);
     }
     // partitioned index: the parts hold disjoint target reads, so a query's distinct-target count is the sum over the
     // parts and it has a mapping if it has one in any part; every part sees the same queries and the global mid_occ.
-    // The reference counts distinct target NAMES (twoset.rs:286-317) and never rejects a duplicate identifier in this mode: a name
-    // that two reads of ONE part share is counted once in that part (k_count's t_dup walk).  A name shared across PARTS would be
-    // counted once per part: the groups onto its bearers are kept out of the per-part counts (k_count_shared) and leave
-    // (query, name) pairs instead, whose distinct ones are counted after the last part (NamePairs).  Without such a name -- an
-    // all-distinct set, duplicates confined to one part -- nothing of this exists and the call launches what it always did.
     const u32 nq = queries->n;
-    std::unique_ptr<NamePairs> np;
-    if (ix->seqs && ix->seqs->dup_rank) {
-        std::vector<std::pair<u32, u32>> rp;      // (name rank, part)
-        for (size_t pi = 0; pi < ix->parts.size(); ++pi)
-            for (u32 r : ix->parts[pi]->seqs->h_rank) rp.emplace_back(r, (u32)pi);
-        std::sort(rp.begin(), rp.end());
-        std::vector<u32> shared;                  // ranks that occur in two or more different parts, ascending
-        for (size_t i = 1; i < rp.size(); ++i)
-            if (rp[i].first == rp[i - 1].first && rp[i].second != rp[i - 1].second && (shared.empty() || shared.back() != rp[i].first)) shared.push_back(rp[i].first);
-        if (!shared.empty()) {
-            HIPCHK(ctx, hipSetDevice(ctx->device));
-            np.reset(new NamePairs(ctx));
-            np->bits_q = std::max<u32>(1, ceil_log2_u64((u64)nq));
-            np->bits_rank = std::max<u32>(1, ceil_log2_u64((u64)rp.back().first + 1));
-            np->d_bits.assign(ix->parts.size(), nullptr);
-            std::vector<std::vector<u32>> h_bits(ix->parts.size());     // (read by the copies until the sync below)
-            for (size_t pi = 0; pi < ix->parts.size(); ++pi) {
-                const std::vector<u32> &hr = ix->parts[pi]->seqs->h_rank;
-                std::vector<u32> &w = h_bits[pi];
-                w.assign(hr.size() / 32 + 1, 0u);
-                bool any = false;
-                for (size_t r = 0; r < hr.size(); ++r)
-                    if (std::binary_search(shared.begin(), shared.end(), hr[r])) { w[r >> 5] |= 1u << (r & 31); any = true; }
-                if (!any) continue;               // (a part without a shared name: plain k_count)
-                hipError_t e = hipErrorOutOfMemory;
-                np->d_bits[pi] = (u32 *)ctx->pool.alloc(w.size() * 4, &e);
-                if (!np->d_bits[pi]) { LRGE_SET_ERR(ctx, "device allocation of %zu bytes for a part's shared-name bitmap failed: %s", w.size() * 4, hipGetErrorString(e)); return LRGE_ERR_DEVICE; }
-                HIPCHK(ctx, hipMemcpyAsync(np->d_bits[pi], w.data(), w.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-            }
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        }
-    }
     acc.parts = ix->parts.size();
     std::vector<u32> c((size_t)nq + 1), h((size_t)nq + 1);
     if (counts) std::fill(counts, counts + nq, 0u);
@@ -192,26 +217,102 @@ extern "C" int lrge_hip_overlap_twoset(lrge_hip_ctx *ctx, const lrge_hip_index *
         OverlapJob pj = job;
         if (cache_ok) pj.qcache = &qcache;
         pj.counts = c.data(); pj.has_map = h.data();
-        if (np && np->d_bits[pi]) { pj.name_pairs = np.get(); pj.d_shared_bits = np->d_bits[pi]; }
-        rc = twoset_one_index(ctx, part, queries, pj, acc);
+        if (np && np->d_bits[pi]) { pj.name_pairs = np; pj.d_shared_bits = np->d_bits[pi]; }
+        int rc = twoset_one_index(ctx, part, queries, pj, acc);
         if (rc) return rc;
         for (u32 q = 0; q < nq; ++q) { if (counts) counts[q] += c[q]; if (has_mapping) has_mapping[q] |= h[q]; }
     }
+    return LRGE_OK;
+}
+
+extern "C" int lrge_hip_overlap_twoset(lrge_hip_ctx *ctx, const lrge_hip_index *ix, const lrge_hip_seqset *queries,
+                                       const lrge_hip_params *p, uint32_t *counts, uint32_t *has_mapping) {
+    int rc = check_common(ctx, ix, queries, /*parts_ok=*/true);
+    if (rc) return rc;
+    OverlapJob job; job.mode = MODE_TWOSET; job.dual = 1;
+    job.prm = p ? *p : lrge_hip_params{0, 0.2f};
+    StageAcc acc;
+    // The reference counts distinct target NAMES (twoset.rs:286-317) and never rejects a duplicate identifier in this mode: a name
+    // that two reads of ONE part share is counted once in that part (k_count's t_dup walk).  A name shared across PARTS would be
+    // counted once per part: the groups onto its bearers are kept out of the per-part counts (k_count_shared) and leave
+    // (query, name) pairs instead, whose distinct ones are counted after the last part (NamePairs).  Without such a name -- an
+    // all-distinct set, duplicates confined to one part, an index without parts -- nothing of this exists and the call launches
+    // what it always did.
+    const u32 nq = queries->n;
+    std::unique_ptr<NamePairs> np;
+    u32 max_rank = 0;
+    const std::vector<u32> shared = names_shared_across_parts(ix, &max_rank);
+    if (!shared.empty()) { rc = name_pairs_setup(ctx, ix, nq, shared, max_rank, np); if (rc) return rc; }
+    rc = twoset_local(ctx, ix, queries, job, np.get(), counts, has_mapping, acc);
+    if (rc) { if (ix->parts.empty()) acc.store(ctx); return rc; }      // (one index: what ran is reported, as it always was)
     if (np) {
-        // the names shared across parts, once per query: a short pass of its own behind the last part (its sort's launches and
-        // its time join the call's counters and timings)
-        const u64 split = ctx->counters[LRGE_C_LPG_SPLIT];
-        memset(ctx->ms, 0, sizeof(ctx->ms)); memset(ctx->counters, 0, sizeof(ctx->counters));
-        {
-            StageTimer t_total(ctx, LRGE_T_TOTAL), t_count(ctx, LRGE_T_COUNT);
-            rc = np->resolve(nq, counts);
-        }
-        (void)hipStreamSynchronize(ctx->stream);
-        ctx->resolve_timers();
-        ctx->counters[LRGE_C_LPG_SPLIT] = split;
-        acc.add(ctx);
+        // the names shared across parts, once per query
+        rc = name_pairs_pass(ctx, acc, [&]() { return np->resolve(nq, counts); });
         if (rc) return rc;
     }
+    acc.store(ctx);
+    if (np) { ctx->counters[LRGE_C_SHARED_NAME_PAIRS] = np->emitted; ctx->counters[LRGE_C_SHARED_NAME_DISTINCT] = np->distinct; }
+    return LRGE_OK;
+}
+
+// The forward strategy with the targets sharded, whatever names the shards share (include/lrge_hip.h; twoset.rs:286-317): the steps
+//   a  discovery            ts_shared_names (host_tshard.inl): the names that occur in two or more shards
+//   b  bitmaps              name_pairs_setup: a read is flagged when its name lives in another shard, or in another part of this one
+//   c  local overlap        twoset_local with the pair sink
+//   d-g  flush, owners by query range, exchange, count at the owner      NamePairs::exchange
+//   h  closing all-reduce   u32[2 nq + 1]: counts, has_mapping, status
+// Without a name shared across shards d-g do not exist: the call is lrge_hip_overlap_twoset (its own parts' shared names resolved
+// locally) between the discovery's all-gathers and the closing all-reduce.
+extern "C" int lrge_hip_overlap_twoset_tsharded(lrge_hip_ctx *ctx, const lrge_hip_index *ix, const lrge_hip_seqset *queries,
+                                                const lrge_hip_params *p, lrge_hip_comm *comm, uint32_t *counts, uint32_t *has_mapping) {
+    if (!ctx || !comm) return LRGE_ERR_INVALID;
+    // (a communicator of another context cannot carry this rank's refusal: the one argument error that stays rank-local)
+    if (comm->ctx != ctx) { LRGE_SET_ERR(ctx, "overlap_twoset_tsharded: the communicator belongs to another context"); return LRGE_ERR_INVALID; }
+    // every other refusal travels in the discovery's status word: the call is refused on every rank
+    int rc = check_common(ctx, ix, queries, /*parts_ok=*/true);
+    if (!rc && (ix->ts_world == 0 || ix->ts_world != comm->world || ix->ts_rank != comm->rank)) {
+        LRGE_SET_ERR(ctx, "overlap_twoset_tsharded: the index was not built by lrge_hip_index_build_tsharded on this communicator");
+        rc = LRGE_ERR_INVALID;
+    }
+    if (!rc && hipSetDevice(ctx->device) != hipSuccess) { (void)hipGetLastError(); LRGE_SET_ERR(ctx, "overlap_twoset_tsharded: hipSetDevice failed"); rc = LRGE_ERR_DEVICE; }
+    const u32 nq = queries ? queries->n : 0;
+    TsNames tn;
+    rc = ts_shared_names(ctx, rc ? nullptr : ix->seqs, nq, comm, rc, &tn);
+    if (rc) return rc;
+    const bool cross = !tn.cross.empty();
+    OverlapJob job; job.mode = MODE_TWOSET; job.dual = 1;
+    job.prm = p ? *p : lrge_hip_params{0, 0.2f};
+    StageAcc acc;
+    std::vector<u32> v((size_t)2 * nq + 1, 0);      // [counts | has_mapping | status]
+    std::unique_ptr<NamePairs> np;
+    auto local = [&]() -> int {
+        u32 max_rank = tn.max_rank;
+        std::vector<u32> shared = names_shared_across_parts(ix, &max_rank), both;
+        std::set_union(shared.begin(), shared.end(), tn.cross.begin(), tn.cross.end(), std::back_inserter(both));
+        // (`both` holds tn.cross: a world that shares names has a sink on every rank, also on one whose own reads bear none of them)
+        if (!both.empty()) { int r = name_pairs_setup(ctx, ix, nq, both, max_rank, np); if (r) return r; }
+        int r = twoset_local(ctx, ix, queries, job, np.get(), v.data(), v.data() + nq, acc);
+        if (r) return r;
+        if (np && !cross) return name_pairs_pass(ctx, acc, [&]() { return np->resolve(nq, v.data()); });      // this shard's parts only: settled here
+        return LRGE_OK;
+    };
+    rc = local();
+    if (cross) {
+        std::vector<u32> add((size_t)nq + 1, 0);
+        const int rc_local = rc;
+        rc = name_pairs_pass(ctx, acc, [&]() { return NamePairs::exchange(rc_local ? nullptr : np.get(), comm, nq, rc_local, add.data()); });
+        if (rc_local) return rc_local;
+        if (rc && !np->exchanged) return rc;      // (in front of the owner's own work every rank leaves the exchange with an error together)
+        if (!rc) for (u32 q = 0; q < nq; ++q) v[q] += add[q];
+    }
+    if (rc) std::fill(v.begin(), v.end(), 0u);
+    v[(size_t)2 * nq] = rc ? 1u : 0u;
+    const std::string mine = ctx->err;
+    const int r2 = comm_allreduce_sum_host(comm, v.data(), v.size(), 4, ctx->stream);
+    if (rc) { ctx->err = mine; return rc; }
+    if (r2) return r2;
+    if (v[(size_t)2 * nq]) { LRGE_SET_ERR(ctx, "overlap_twoset_tsharded: %u other rank(s) failed", v[(size_t)2 * nq]); return LRGE_ERR_DEVICE; }
+    for (u32 q = 0; q < nq; ++q) { if (counts) counts[q] = v[q]; if (has_mapping) has_mapping[q] = v[(size_t)nq + q] ? 1u : 0u; }
     acc.store(ctx);
     if (np) { ctx->counters[LRGE_C_SHARED_NAME_PAIRS] = np->emitted; ctx->counters[LRGE_C_SHARED_NAME_DISTINCT] = np->distinct; }
     return LRGE_OK;

@@ -127,6 +127,11 @@ int NamePairs::resolve(u32 nq, u32 *counts) {
     u64 n = 0;
     int rc = read_cursor(&n);
     if (rc) return rc;
+    return count(n, nq, counts);
+}
+
+int NamePairs::count(u64 n, u32 nq, u32 *counts) {
+    int rc = LRGE_OK;
     if (n == 0) return LRGE_OK;
     Scratch sc(ctx);
     u64 *sorted = buf, *other = nullptr;
@@ -141,6 +146,57 @@ int NamePairs::resolve(u32 nq, u32 *counts) {
     if (counts) for (u32 q = 0; q < nq; ++q) counts[q] += add[q];
     distinct = add[nq];
     return LRGE_OK;
+}
+
+// The sequence of collectives is fixed (host_tshard.inl's convention); a rank that fails joins the next one with the status set:
+//   X1 all-gather  u64[W + 1]   pairs this rank sends to every owner, status
+//   A1 agreement                (the receive buffer taken)
+//   X2 all-to-all  u64          the pairs
+// What fails behind X2 -- the owner's sort and count -- is this function's return value: the caller's closing all-reduce carries it.
+int NamePairs::exchange(NamePairs *np, lrge_hip_comm *c, u32 nq, int rc_in, u32 *counts) {
+    lrge_hip_ctx *ctx = c->ctx;
+    const int W = c->world, me = c->rank;
+    hipStream_t st = ctx->stream;
+    Scratch sc(ctx);
+    std::vector<u64> s_off((size_t)W + 1, 0), r_off((size_t)W + 1, 0), mine((size_t)W + 1, 0), matrix(((size_t)W + 1) * (size_t)W, 0);
+    // ---- flush: the distinct pairs of this rank, sorted by (query, name) -- every owner's share is one contiguous range ----
+    auto local1 = [&]() -> int {
+        if (rc_in) return rc_in;
+        int rc = np->flush(); if (rc) return rc;
+        const u64 n = np->at_flush;
+        ALLOC_OR_FAIL(d_cuts, sc, u64, (size_t)W + 1);
+        hipLaunchKernelGGL(k_pair_cuts, dim3((u32)div_up((u64)W + 1, 64)), dim3(64), 0, st, np->buf, (u32)n, nq, (u32)W, d_cuts);
+        KCHK(ctx);
+        HIPCHK(ctx, hipMemcpyAsync(s_off.data(), d_cuts, ((size_t)W + 1) * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipStreamSynchronize(st));
+        if (s_off[0] != 0 || s_off[(size_t)W] != n) { LRGE_SET_ERR(ctx, "shared target names: the owners' ranges do not tile the %llu pairs", (unsigned long long)n); return LRGE_ERR_DEVICE; }
+        for (int d = 0; d < W; ++d) mine[(size_t)d] = s_off[(size_t)d + 1] - s_off[(size_t)d];
+        return LRGE_OK;
+    };
+    int rc = local1();
+    const bool failed1 = rc != LRGE_OK;
+    if (failed1) { std::fill(s_off.begin(), s_off.end(), 0); std::fill(mine.begin(), mine.end(), 0); }
+    mine[(size_t)W] = failed1 ? 1 : 0;
+    const int r1 = comm_allgather_host(c, mine.data(), mine.size() * 8, matrix.data(), st);
+    if (failed1) return rc;
+    if (r1) return r1;
+    const size_t row = (size_t)W + 1;
+    for (int r = 0; r < W; ++r) if (matrix[(size_t)r * row + W]) { LRGE_SET_ERR(ctx, "overlap_twoset_tsharded: rank %d failed", r); return LRGE_ERR_DEVICE; }
+    for (int o = 0; o < W; ++o) {      // (every rank sees every owner's total: the refusal needs no agreement)
+        u64 tot = 0;
+        for (int r = 0; r < W; ++r) tot += matrix[(size_t)r * row + (size_t)o];
+        if (tot >= (1ULL << 32)) { LRGE_SET_ERR(ctx, "shared target names: rank %d owns %llu (query, name) pairs (limit 2^32)", o, (unsigned long long)tot); return LRGE_ERR_TOO_MANY; }
+    }
+    for (int s = 0; s < W; ++s) r_off[(size_t)s + 1] = r_off[(size_t)s] + matrix[(size_t)s * row + (size_t)me];
+    const u64 n_r = r_off[(size_t)W];
+    u64 *recv = sc.get<u64>(n_r + 1);
+    rc = comm_agree(c, recv ? LRGE_OK : LRGE_ERR_DEVICE, st); if (rc) return rc;
+    rc = comm_alltoallv(c, np->buf, s_off.data(), recv, r_off.data(), 8, st); if (rc) return rc;
+    // ---- at the owner: the received runs become the buffer; sorted as one, a pair that differs from its predecessor counts ----
+    sc.keep(recv); np->exchanged = true;
+    ctx->pool.release(np->buf);        // (reusable at once: every user is ordered on ctx->stream; the peers have read it -- X2 ends behind their copies)
+    np->buf = recv; np->cap = n_r + 1; np->at_flush = np->upper = n_r;      // (the cursor on the device is not used any more)
+    return np->count(n_r, nq, counts);
 }
 
 int OverlapRun::batch(u32 q0, u32 q1, u64 A) {

@@ -8,7 +8,9 @@ enum { MODE_TWOSET = 0, MODE_INVERSE = 1, MODE_AVA = 2 };
 // once per part -- 8 x 12.7 ms at full-size C5)
 struct SketchCache { std::unique_ptr<Scratch> sc; SketchOut so; std::vector<u32> h_mzoff; bool valid = false; };
 
-// Forward two-set against a partitioned index whose parts share target names (lrge_hip_overlap_twoset): what a call keeps over
+struct lrge_hip_comm;
+// Forward two-set against a partitioned index whose parts share target names (lrge_hip_overlap_twoset), or against the shards of a
+// target-sharded world that do (lrge_hip_overlap_twoset_tsharded: read "shard" for "part" below): what a call keeps over
 // all its parts and query views.  A counted group onto a read whose name also occurs in ANOTHER part is not counted in that
 // part (k_count_shared): it leaves the pair (global query, name rank) here, and the distinct pairs are counted once the last
 // part is through (resolve) -- the HashSet<target_name> of twoset.rs:286-317, which a per-part count cannot be.
@@ -31,6 +33,12 @@ struct NamePairs {
     int flush();                        // sort, unique, compact: buf holds the distinct pairs, the cursor their number
     int room(u64 need);                 // before a launch that may append `need` pairs
     int resolve(u32 nq, u32 *counts);   // after the last part: counts[q] += distinct names of q among the pairs
+    int count(u64 n, u32 nq, u32 *counts);   // resolve's second half: sort buf[0, n), count the distinct pairs into counts
+    // lrge_hip_overlap_twoset_tsharded: the names are shared across the SHARDS of a world.  Every rank flushes its own pairs, sends
+    // each to the rank that owns its query (pair_owner.h), and counts what it receives.  Collective; `np` may be null on a rank that
+    // has failed already (rc_in != 0): it still joins the first exchange to say so.
+    static int exchange(NamePairs *np, lrge_hip_comm *c, u32 nq, int rc_in, u32 *counts);
+    bool exchanged = false;             // the pairs have travelled: what fails from here on fails on this rank alone
 };
 
 struct OverlapJob {

@@ -1,5 +1,6 @@
 // host_tshard.inl -- part of lrge_hip.hip (one translation unit; included there, in this order): lrge_hip_index_build_tsharded, the
-// collective index build of the forward strategy with the TARGETS sharded over the ranks (k_tshard.h says why and what travels).
+// collective index build of the forward strategy with the TARGETS sharded over the ranks (k_tshard.h says why and what travels).  Behind it:
+// ts_shared_names, the discovery step of lrge_hip_overlap_twoset_tsharded (which target names occur in two or more shards).
 // ------------------------------------------------------------------------------------------
 // A collective call: the sequence of collectives is fixed, a rank that fails joins the next one in its own shape with the status
 // word set (CollectiveGuard, host_index_collective.inl).
@@ -267,6 +268,73 @@ extern "C" int lrge_hip_index_build_tsharded(lrge_hip_ctx *ctx, const lrge_hip_s
     ctx->event_pool.push_back(e0); ctx->event_pool.push_back(e1);
     memcpy(ctx->ms, ms_keep, sizeof ms_keep); memcpy(ctx->counters, cn_keep, sizeof cn_keep);
     ctx->ms[LRGE_T_INDEX_RESTRICT] += ms; ctx->ms[LRGE_T_TOTAL] += ms;
+    ix->ts_world = comm->world; ix->ts_rank = comm->rank;
     *out = g.release();
+    return LRGE_OK;
+}
+
+// ---- lrge_hip_overlap_twoset_tsharded (host_overlap_api.inl), step a: which target names occur in two or more SHARDS ----
+// twoset.rs:286-317 counts a target NAME once per query; the shards' counts add up only over disjoint names.  Every rank sorts and
+// uniques the name ranks of its shard, the ranks exchange the sizes and then the lists (host all-gathers), and every rank finds the
+// same answer: the ranks that occur in two lists (a merge of the sorted lists).  A shard uploaded without name ranks (NULL: all distinct) shares nothing; a world
+// in which some shards have name ranks and others do not is refused on every rank (an empty shard sides with the others).
+//   D1 all-gather  u64[4]     distinct names of this shard, has name ranks (0 / 1 / 2: empty shard), queries, status
+//   D2 all-gather  u32[max]   the lists, padded to the longest (not entered when nobody has a name)
+// The status word of D1 carries the CODE a rank has failed with so far (rc_in: the entry point's argument checks among them), so
+// that a refusal on one rank is the same refusal on every rank.
+struct TsNames { std::vector<u32> cross; u32 max_rank = 0; };     // ascending; the largest name rank of any shard
+static int ts_shared_names(lrge_hip_ctx *ctx, const lrge_hip_seqset *shard, u32 nq, lrge_hip_comm *c, int rc_in, TsNames *out) {
+    const int W = c->world;
+    hipStream_t st = ctx->stream;
+    std::vector<u32> mine;
+    u64 flag = 2;
+    if (!rc_in && shard && shard->n) {
+        flag = shard->has_rank ? 1 : 0;
+        if (shard->has_rank) {
+            mine = shard->h_rank;
+            std::sort(mine.begin(), mine.end());
+            mine.erase(std::unique(mine.begin(), mine.end()), mine.end());
+        }
+    }
+    const u64 d1[4] = {(u64)mine.size(), flag, (u64)nq, (u64)(u32)(rc_in ? -rc_in : 0)};
+    std::vector<u64> all((size_t)4 * W, 0);
+    int rc = comm_allgather_host(c, d1, sizeof d1, all.data(), st); if (rc) return rc_in ? rc_in : rc;
+    u64 max_n = 0; bool with = false, without = false, nq_differs = false;
+    for (int r = 0; r < W; ++r) {
+        const u64 *a = &all[(size_t)4 * r];
+        if (a[3]) {
+            if (rc_in) return rc_in;
+            LRGE_SET_ERR(ctx, "overlap_twoset_tsharded: rank %d refused the call (code %d)", r, -(int)a[3]);
+            return -(int)a[3];
+        }
+        max_n = std::max(max_n, a[0]);
+        with |= a[1] == 1; without |= a[1] == 0; nq_differs |= a[2] != (u64)nq;
+    }
+    if (with && without) { LRGE_SET_ERR(ctx, "overlap_twoset_tsharded: some target shards were uploaded with name ranks, others without"); return LRGE_ERR_INVALID; }
+    if (nq_differs) { LRGE_SET_ERR(ctx, "overlap_twoset_tsharded: the ranks passed query sets of different sizes"); return LRGE_ERR_INVALID; }
+    if (max_n == 0) return LRGE_OK;
+    std::vector<u32> send((size_t)max_n, 0), lists((size_t)max_n * W, 0);
+    std::copy(mine.begin(), mine.end(), send.begin());
+    rc = comm_allgather_host(c, send.data(), (size_t)max_n * 4, lists.data(), st); if (rc) return rc;
+    // every list is sorted and unique in itself: adjacent runs are merged pairwise (log2 W linear passes, no sort), and a value seen
+    // twice in the merged sequence lives in two shards
+    std::vector<u32> u;
+    std::vector<size_t> cut{0};
+    for (int r = 0; r < W; ++r) {
+        u.insert(u.end(), lists.begin() + (size_t)max_n * r, lists.begin() + (size_t)max_n * r + (size_t)all[(size_t)4 * r]);
+        cut.push_back(u.size());
+    }
+    while (cut.size() > 2) {
+        std::vector<size_t> next{0};
+        for (size_t i = 0; i + 1 < cut.size(); i += 2) {
+            const size_t end = i + 2 < cut.size() ? cut[i + 2] : cut[i + 1];
+            if (i + 2 < cut.size()) std::inplace_merge(u.begin() + cut[i], u.begin() + cut[i + 1], u.begin() + end);
+            next.push_back(end);
+        }
+        cut.swap(next);
+    }
+    for (size_t i = 1; i < u.size(); ++i)
+        if (u[i] == u[i - 1] && (out->cross.empty() || out->cross.back() != u[i])) out->cross.push_back(u[i]);
+    out->max_rank = u.empty() ? 0 : u.back();
     return LRGE_OK;
 }

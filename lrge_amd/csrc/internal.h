@@ -316,6 +316,7 @@ struct lrge_hip_index {
     std::vector<lrge_hip_index *> parts;
     std::vector<lrge_hip_seqset *> part_sets;
     std::vector<u32> part_r0;
+    int ts_world = 0, ts_rank = 0;   // lrge_hip_index_build_tsharded: the communicator's shape (ts_world == 0: not a target-sharded index)
 };
 
 #define LRGE_SET_ERR(ctx, ...)                                  \

@@ -16,6 +16,7 @@
 #include "internal.h"
 #include "k_prims.h"
 #include "k_seed.h"
+#include "pair_owner.h"
 
 struct ChainParams {
     i32 max_dist_x, max_dist_y, bw, max_skip, max_iter, min_cnt, min_sc, max_drop;
@@ -170,6 +171,21 @@ __global__ void k_name_pairs_count(const u64 *__restrict__ pairs, u32 n, u32 *__
     if (first) atomicAdd(&counts[(u32)(pairs[i] >> 32)], 1u);
     const u64 m = __ballot(first);
     if (lane_id() == 0 && m) atomicAdd(n_distinct, (u32)__popcll(m));
+}
+
+// The distinct (query, name) pairs of one rank, sorted by query (NamePairs::flush): where the share of every owner rank begins
+// (pair_owner.h).  One lane per boundary b in [0, world]: cuts[b] = the first pair whose query is not below the first query of
+// rank b -- a lower-bound search over the high words; cuts[0] = 0 and cuts[world] = n.  (n == 0: pairs is never read.)
+__global__ void k_pair_cuts(const u64 *__restrict__ pairs, u32 n, u32 nq, u32 world, u64 *__restrict__ cuts) {
+    const u32 b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b > world) return;
+    const u64 first = pair_owner_first(b, nq, world);
+    u32 lo = 0, hi = n;
+    while (lo < hi) {
+        const u32 mid = lo + (hi - lo) / 2;
+        if ((pairs[mid] >> 32) < first) lo = mid + 1; else hi = mid;
+    }
+    cuts[b] = lo;
 }
 
 // K8: per_read_estimate (estimate.rs:142-157), f32, explicit rounding per operation

@@ -395,6 +395,17 @@ class Index:
                                                               counts.ctypes.data, has.ctypes.data))
         return counts[:queries.n], has[:queries.n]
 
+    def overlap_twoset_tsharded(self, queries, comm, remove_internal=False, max_overhang_ratio=0.2):
+        """Collective (every rank of `comm`, each with its own tshard=True index and the SAME queries): counts and has_mapping
+        (0 / 1) of the whole job on every rank, a target name counted once per query whichever shards bear it
+        (lrge_hip_overlap_twoset_tsharded; twoset.rs:286-317).  The all-reduce that closes the step is inside."""
+        counts = np.zeros(max(queries.n, 1), dtype=np.uint32)
+        has = np.zeros(max(queries.n, 1), dtype=np.uint32)
+        p = self._params(remove_internal, max_overhang_ratio)
+        self.ctx._check(self.ctx._lib.lrge_hip_overlap_twoset_tsharded(self.ctx.h, self.h, queries.h, C.byref(p), comm.h,
+                                                                       counts.ctypes.data, has.ctypes.data))
+        return counts[:queries.n], has[:queries.n]
+
     def overlap_inverse(self, streamed, remove_internal=False, max_overhang_ratio=0.2):
         counts = np.zeros(max(self.targets.n, 1), dtype=np.uint32)
         p = self._params(remove_internal, max_overhang_ratio)

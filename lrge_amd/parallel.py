@@ -152,6 +152,30 @@ def _close_step(comm, sizes, work):
     return out
 
 
+def _close_status(comm, work):
+    """_close_step without the payload: `work()` is rank-local and its result stays here; one status word travels, so that a rank
+    whose `work()` failed raises after the agreement and its peers raise RankFailed."""
+    err, out = None, None
+    try:
+        out = work()
+        if len(out) != 2 or len(out[0]) != len(out[1]):
+            raise ValueError("a collective overlap step returned %r vectors" % (len(out),))
+    except BaseException as e:      # noqa: BLE001 -- re-raised below, after the agreement
+        err = e
+    try:
+        st = comm.all_reduce_u32(np.array([1 if err is not None else 0], np.uint32))
+    except BaseException:
+        _abort(comm)
+        if err is not None:
+            raise err
+        raise
+    if err is not None:
+        raise err
+    if int(st[0]):
+        raise RankFailed("%d other rank(s) failed inside the step; this rank's results are discarded" % int(st[0]))
+    return out
+
+
 class RcclComm(_Comm):
     """RCCL over xGMI, one process per GPU.  The 128-byte unique id travels through whatever the host has."""
 
@@ -418,7 +442,17 @@ def cross_shard_duplicates(t_ranks, bounds):
     return bool(((r[1:] == r[:-1]) & (sh[1:] != sh[:-1])).any())
 
 
-def twoset_forward_target_sharded(overlap_fn, t_lens, comm, n_queries=None, build_fn=None, t_ranks=None):
+def pair_owner_bounds(nq, world):
+    """lrge_hip_overlap_twoset_tsharded: rank r counts the (query, shared name) pairs of the queries [b[r], b[r + 1]) --
+    b[r] = floor(r * nq / world), the rule of lrge_amd/csrc/pair_owner.h restated (Python integers: no 64-bit wrap to mind).
+    Returns the world + 1 boundaries."""
+    nq, world = int(nq), int(world)
+    if world < 1 or nq < 0:
+        raise ValueError("pair_owner_bounds: world >= 1 and nq >= 0")
+    return [r * nq // world for r in range(world + 1)]
+
+
+def twoset_forward_target_sharded(overlap_fn, t_lens, comm, n_queries=None, build_fn=None, t_ranks=None, count_shared=False):
     """Two-set forward over comm.world GPUs with the TARGETS sharded (lrge_hip_index_build_tsharded): the target reads are cut into
     contiguous ranges with equal base counts, every rank maps ALL queries against the index of its range (built with the occurrence
     statistics of the whole target set: engine.Index(ctx, target_shard, preset, comm=comm, tshard=True)); the shards hold disjoint
@@ -432,11 +466,28 @@ def twoset_forward_target_sharded(overlap_fn, t_lens, comm, n_queries=None, buil
       n_queries                         Q (needed for the status-word form: a failed rank still sends vectors of the right shape)
       t_ranks                           name ranks of ALL targets: a target identifier that occurs in two shards would be counted
                                         twice -- refused with ValueError before anything is built (use the query-sharded form, or
-                                        one GPU, for such a set)
+                                        one GPU, for such a set -- or count_shared=True)
+      count_shared                      True: overlap_fn is the COLLECTIVE call (engine.Index.overlap_twoset_tsharded), which counts a
+                                        name once whichever shards bear it and returns the counts of the whole job on every rank
+                                        (the all-reduce of the counts is inside it): no refusal.  overlap_fn and build_fn are
+                                        collective: a failure in either aborts the communicator and is raised; a one-word status
+                                        agreement follows the call
 
     Returns (counts, has_mapping 0/1, (t_lo, t_hi))."""
     b = shard_by_bases(t_lens, comm.world)
     lo, hi = b[comm.rank], b[comm.rank + 1]
+    if count_shared:
+        # build_fn and overlap_fn are COLLECTIVE here: a rank that fails in or around them has left a collective its peers are still in
+        # (or heading for), so it must not enter another one -- it aborts the communicator, which wakes the peers with an error, and
+        # raises (as a failing build_fn does below).  Only a rank that has LEFT the collective call goes on to the status agreement,
+        # which carries what can still fail on this rank alone: the shape of what overlap_fn returned.
+        try:
+            res = overlap_fn(lo, hi) if build_fn is None else overlap_fn(build_fn(lo, hi))
+        except BaseException:
+            _abort(comm)
+            raise
+        (counts, has) = _close_status(comm, lambda: tuple(np.ascontiguousarray(x, dtype=np.uint32) for x in res))
+        return counts, (has > 0).astype(np.uint32), (lo, hi)
     if t_ranks is not None and cross_shard_duplicates(t_ranks, b):       # (every rank holds the same ranks: every rank refuses)
         raise ValueError("Duplicate read identifier across target shards: the target-sharded forward form cannot count distinct names over shards")
     if build_fn is None or n_queries is None:
