@@ -423,13 +423,38 @@ int  lrge_hip_read_records_gpu_ex(lrge_hip_ctx *ctx, const char *path, int flags
                                   void (*cb)(void *user, const char *name, uint64_t name_len, const char *bases, uint64_t n_bases),
                                   void *user, int *used_device);
 
+/* bzip2 decompressed on the device (k_bz_find, k_bz_decode, k_bz_scatter, k_bz_walk, k_bz_rle_count,
+   k_bz_rle_write): the blocks of one stream are found by their 48-bit magic at every bit offset and decoded in parallel; a chain
+   from bit 32 accepts a block only where the block in front of it ended.  lrge_hip_bzip2_inflate has the contract of
+   lrge_hip_gzip_inflate: the bytes arrive in order through `sink` (a nonzero return stops the call with LRGE_ERR_IO); on a non-OK
+   return the bytes delivered so far are void; there is no host fall-back inside the call.  The device accepts exactly what the
+   host reader takes, the first stream: one header "BZh1".."BZh9", blocks, the end-of-stream magic, a correct combined CRC, at most
+   7 padding bits and nothing behind them.  LRGE_ERR_PARSE (the message names a byte offset): a second stream or any trailing
+   byte, a randomised block, nGroups outside 2..6, a selector or a code length out of range, more bytes than the level's block
+   size, origPtr outside the block, a missing end-of-block symbol, a block that stops behind four equal bytes where their count belongs, a wrong block or stream
+   CRC, a truncated file.
+   LRGE_ERR_DEVICE: a runtime failure.  Option BZIP2_ROUND_BLOCKS: candidates decoded per round (default: what half of the free
+   device memory plus the context's idle arena bytes holds, at most 4096).  *stats (may be NULL) receives the counts of the call.
+   lrge_hip_read_records_gpu_ex | LRGE_GPU_INFLATE_BZIP2 sends bzip2 input to this decoder and falls back to the unchanged host
+   path for anything it does not accept; lrge_hip_reads_open* | LRGE_GPU_INFLATE_BZIP2 keeps the text in HBM. */
+typedef struct lrge_hip_bzip2_stats {
+    uint64_t blocks;              /* accepted blocks, each with its CRC checked */
+    uint64_t candidates;          /* bit offsets that carry the block magic */
+    uint64_t rejected_candidates; /* candidates the chain did not arrive at */
+    uint64_t rounds;              /* rounds of at most BZIP2_ROUND_BLOCKS candidates */
+    uint64_t bytes_out;           /* decompressed bytes */
+} lrge_hip_bzip2_stats;
+#define LRGE_GPU_INFLATE_BZIP2 16
+int  lrge_hip_bzip2_inflate(lrge_hip_ctx *ctx, const void *comp, uint64_t comp_len, int (*sink)(void *user, const void *bytes, uint64_t n),
+                            void *user, lrge_hip_bzip2_stats *stats);
+
 /* Read sets built on the device from FASTA / FASTQ text (k_fx_census, k_fx_summary, k_fx_scatter, k_fx_records,
    k_fx_names, k_fx_gather) and from unaligned BAM (k_bam_header, k_bam_find, k_bam_walk, k_bam_records,
    k_bam_gather; SAM, DESIGN section 14: k_sam_mark, k_sam_records): the device-side form of the record reader (io.rs:154-184) and of the read selection that feeds the
    strategies (twoset.rs:122-201).  The file's bytes are decompressed into HBM and stay there; the records are found there; only
    the identifiers and the sequence lengths come back.
    lrge_hip_reads_open (io.rs:154-184) reads `path` into memory and calls lrge_hip_reads_open_mem (io.rs:154-184), which takes the
-   bytes of a whole file.  `flags`: LRGE_GPU_INFLATE_BGZF | LRGE_GPU_INFLATE_GZIP choose the device decoders as in
+   bytes of a whole file.  `flags`: LRGE_GPU_INFLATE_BGZF | LRGE_GPU_INFLATE_GZIP | LRGE_GPU_INFLATE_BZIP2 choose the device decoders as in
    lrge_hip_read_records_gpu_ex; with neither, only uncompressed input is taken.  | LRGE_GPU_INGEST_BAM: text that starts with
    the BAM magic is scanned as unaligned BAM (every record with flag 4, found by a speculative walk of the length chain that
    is proven from the end of the header); without the flag BAM is unproven, as it was before the flag existed.
@@ -439,7 +464,7 @@ int  lrge_hip_read_records_gpu_ex(lrge_hip_ctx *ctx, const char *path, int flags
    and produces no parse error of its own -- anything but FASTA, strict four-line FASTQ or (with its flag) well-formed unaligned
    BAM (an empty line between records, a truncated record, a missing '+', CRAM, BAM without LRGE_GPU_INGEST_BAM, a BAM
    with a mapped record, a damaged header or record, or bytes behind the last record, SAM without LRGE_GPU_INGEST_SAM, a SAM
-   record line with fewer than ten tabs, with a flag that is not plain digits or with a mapped flag), a compressed format without its flag or other than gzip, a damaged gzip file, text above option INGEST_MAX_BYTES
+   record line with fewer than ten tabs, with a flag that is not plain digits or with a mapped flag), a compressed format without its flag or other than gzip and (with LRGE_GPU_INFLATE_BZIP2) bzip2, a damaged gzip file, a bzip2 file the device decoder does not accept, text above option INGEST_MAX_BYTES
    (default: half of the free device memory plus the context's idle arena bytes); the caller takes lrge_hip_read_records*, which
    parses the file or gives the reference's message.  LRGE_ERR_TOO_MANY: 2^32 records or more, or a sequence of 2^32 bases or
    more.  LRGE_ERR_IO: the file cannot be read.  An empty file is LRGE_OK with a count of 0.

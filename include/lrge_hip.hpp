@@ -154,6 +154,7 @@ using ::lrge::unique_random_set;
 // in lrge_io.hpp: false (the host path decompresses) for input that is not BGZF or holds a block the device rejects; a
 // device failure throws.  The hook owns a context on `device` for as long as it lives.
 namespace detail {
+inline bool is_bzip2(const std::string &raw) { return raw.size() >= 2 && raw[0] == 0x42 && raw[1] == 0x5a; }   // (lrge_io.hpp: detect_compression_format)
 inline bool bgzf_inflate_with(Ctx &ctx, const std::string &raw, std::string &out) {
     uint64_t total = 0;
     if (lrge_hip_bgzf_scan(raw.data(), raw.size(), nullptr, &total) != LRGE_OK) return false;
@@ -176,6 +177,7 @@ inline std::function<bool(const std::string &, std::string &)> bgzf_inflater(int
 inline std::function<bool(const std::string &, std::string &)> gzip_inflater(int device) {
     auto ctx = std::make_shared<detail::Ctx>(device);            // one context for both device paths
     return [ctx](const std::string &raw, std::string &out) -> bool {
+        if (detail::is_bzip2(raw)) return false;
         if (lrge_hip_bgzf_scan(raw.data(), raw.size(), nullptr, nullptr) == LRGE_OK) return detail::bgzf_inflate_with(*ctx, raw, out);
         out.clear();
         const int rc = lrge_hip_gzip_inflate(ctx->h, raw.data(), raw.size(), [](void *u, const void *b, uint64_t n) {
@@ -183,6 +185,24 @@ inline std::function<bool(const std::string &, std::string &)> gzip_inflater(int
             return 0;
         }, &out, nullptr);
         if (rc == LRGE_ERR_PARSE || rc == LRGE_ERR_TOO_MANY) { out.clear(); return false; }
+        ctx->check(rc);
+        return true;
+    };
+}
+
+// bzip2 input decompressed on the device (lrge_hip_bzip2_inflate); gzip input goes to `gzip` when one is given (gzip_inflater,
+// bgzf_inflater).  False (the host path decompresses, with its messages) for input the device does not accept; a device
+// failure throws.
+inline std::function<bool(const std::string &, std::string &)> bzip2_inflater(int device, std::function<bool(const std::string &, std::string &)> gzip = nullptr) {
+    auto ctx = std::make_shared<detail::Ctx>(device);
+    return [ctx, gzip](const std::string &raw, std::string &out) -> bool {
+        if (!detail::is_bzip2(raw)) return gzip ? gzip(raw, out) : false;
+        out.clear();
+        const int rc = lrge_hip_bzip2_inflate(ctx->h, raw.data(), raw.size(), [](void *u, const void *b, uint64_t n) {
+            static_cast<std::string *>(u)->append(static_cast<const char *>(b), (size_t)n);
+            return 0;
+        }, &out, nullptr);
+        if (rc == LRGE_ERR_PARSE) { out.clear(); return false; }
         ctx->check(rc);
         return true;
     };

@@ -14,6 +14,7 @@ ERR_UNPROVEN = -10
 GPU_INFLATE_BGZF, GPU_INFLATE_GZIP = 1, 2
 GPU_INGEST_BAM = 4
 GPU_INGEST_SAM = 8
+GPU_INFLATE_BZIP2 = 16
 PRESET_AVA_ONT, PRESET_AVA_PB = 0, 1
 
 T_NAMES = ["pack", "sketch", "index_sort", "index_table", "qfilter", "lookup", "expand", "anchor_sort", "group",
@@ -23,9 +24,10 @@ C_NAMES = ["query_bases", "query_minimizers", "anchors", "groups", "groups_chain
            "rs_scatter_launches", "rs_scatter_items", "rs_scatter_bytes", "lpg_split", "lookup_launches", "table_disp_sum", "anchors_kept", "index_parts", "sketch_launches", "sketch_wave_launches",
            "shared_name_pairs", "shared_name_distinct"]
 
+BZIP2_STAT_NAMES = ["blocks", "candidates", "rejected_candidates", "rounds", "bytes_out"]   # lrge_hip_bzip2_stats
 BAM_STAT_NAMES = ["segments", "empty_segments", "speculative_starts", "rejected_starts", "repair_rounds", "rewalked_segments"]   # lrge_hip_bam_stats
 
-# int (*sink)(void *user, const void *bytes, uint64_t n) of lrge_hip_gzip_inflate
+# int (*sink)(void *user, const void *bytes, uint64_t n) of lrge_hip_gzip_inflate and lrge_hip_bzip2_inflate
 GZIP_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)
 
 EXPORTS = [
@@ -33,7 +35,7 @@ EXPORTS = [
     "lrge_hip_seqset_upload", "lrge_hip_seqset_upload_async", "lrge_hip_seqset_wait", "lrge_hip_host_alloc",
     "lrge_hip_host_free", "lrge_hip_seqset_free", "lrge_hip_seqset_size", "lrge_hip_seqset_presketch", "lrge_hip_seqset_presketch_sharded", "lrge_hip_pack_choice", "lrge_hip_read_records",
     "lrge_hip_bgzf_scan", "lrge_hip_bgzf_inflate", "lrge_hip_read_records_gpu",
-    "lrge_hip_gzip_inflate", "lrge_hip_read_records_gpu_ex",
+    "lrge_hip_gzip_inflate", "lrge_hip_read_records_gpu_ex", "lrge_hip_bzip2_inflate",
     "lrge_hip_reads_open", "lrge_hip_reads_open_mem", "lrge_hip_reads_count", "lrge_hip_reads_name_bytes", "lrge_hip_reads_text_bytes",
     "lrge_hip_reads_table", "lrge_hip_reads_timings", "lrge_hip_reads_bam_stats", "lrge_hip_seqset_from_reads", "lrge_hip_reads_free",
     "lrge_hip_index_build", "lrge_hip_index_build_for", "lrge_hip_index_build_sharded", "lrge_hip_index_build_tsharded", "lrge_hip_last_shard_stats", "lrge_hip_index_free",
@@ -104,6 +106,7 @@ def lib():
     L.lrge_hip_bgzf_scan.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.lrge_hip_bgzf_inflate.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64]
     L.lrge_hip_gzip_inflate.argtypes = [vp, vp, C.c_uint64, GZIP_SINK, vp, vp]
+    L.lrge_hip_bzip2_inflate.argtypes = [vp, vp, C.c_uint64, GZIP_SINK, vp, vp]
     L.lrge_hip_reads_open.argtypes = [vp, C.c_char_p, C.c_int, C.POINTER(vp)]
     L.lrge_hip_reads_open_mem.argtypes = [vp, vp, C.c_uint64, C.c_int, C.POINTER(vp)]
     for f in (L.lrge_hip_reads_count, L.lrge_hip_reads_name_bytes, L.lrge_hip_reads_text_bytes):

@@ -45,6 +45,7 @@ FASTX_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_fastx_twin.so")
 BAM_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_bam_twin.so")
 SAM_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_sam_twin.so")
 NAMES_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_names_twin.so")
+BZIP2_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_bzip2_twin.so")
 
 
 def _build_twin(out, main, force):
@@ -58,14 +59,15 @@ def _build_twin(out, main, force):
 
 
 def build_twin(force=False):
-    """The host twins, all six: of k_inflate (csrc/inflate_twin.cpp, the same bit-level core), and of the speculative gzip
+    """The host twins, all seven: of k_inflate (csrc/inflate_twin.cpp, the same bit-level core), and of the speculative gzip
     decode (build_gzip_twin), of the FASTA / FASTQ record scan (build_fastx_twin), of the BAM record scan (build_bam_twin), of
-    the SAM record scan (build_sam_twin) and of the identifier ranking (build_names_twin)."""
+    the SAM record scan (build_sam_twin), of the identifier ranking (build_names_twin) and of the bzip2 decode (build_bzip2_twin)."""
     build_gzip_twin(force)
     build_fastx_twin(force)
     build_bam_twin(force)
     build_sam_twin(force)
     build_names_twin(force)
+    build_bzip2_twin(force)
     return _build_twin(TWIN_PATH, "inflate_twin.cpp", force)
 
 
@@ -92,6 +94,11 @@ def build_sam_twin(force=False):
 def build_names_twin(force=False):
     """The identifier ranking by radix refinement as host code (csrc/names_twin.cpp over csrc/name_core.h)."""
     return _build_twin(NAMES_TWIN_PATH, "names_twin.cpp", force)
+
+
+def build_bzip2_twin(force=False):
+    """The host twin of the block-parallel bzip2 decode (csrc/bz_twin.cpp): the same core and the same driver of the rounds."""
+    return _build_twin(BZIP2_TWIN_PATH, "bz_twin.cpp", force)
 
 
 CLI_PATH = os.path.join(LIB_DIR, "lrge-hip")

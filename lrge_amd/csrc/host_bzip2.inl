@@ -1,0 +1,206 @@
+// host_bzip2.inl -- bzip2 decompressed on the device (k_bzip2.h): the backend that bz_round.h's bz_run drives and
+// the C entry point.  Included into lrge_hip.hip behind host_gzip.inl (DevKeep, GzBuf).
+//
+// The compressed bytes go up once and stay for the call (they are a fraction of the text).  Option BZIP2_ROUND_BLOCKS: the
+// candidates decoded per round; its default is what half of the arena's idle bytes plus the device's free bytes hold at
+// bz_candidate_bytes per candidate, at most BZ_ROUND_MAX.  Option BZIP2_TIMING: the stages are separated by synchronisations and
+// their times are printed to stderr when the call ends (tools/bzip2_bench.py).
+
+static const char *bz_status_name(int s) {
+    switch (s) {
+    case BZ_E_MAGIC: return "no bzip2 stream header or block magic";
+    case BZ_E_INPUT: return "unexpected end of compressed data";
+    case BZ_E_RANDOMISED: return "a randomised block";
+    case BZ_E_GROUPS: return "invalid number of coding tables, selectors or symbols";
+    case BZ_E_SELECTOR: return "a selector out of range";
+    case BZ_E_LENGTH: return "a code length out of range";
+    case BZ_E_CODE: return "invalid code";
+    case BZ_E_SIZE: return "a block above the level's block size";
+    case BZ_E_NO_EOB: return "no end-of-block symbol";
+    case BZ_E_ORIGPTR: return "origPtr outside the block";
+    case BZ_E_BLOCK_CRC: return "block CRC mismatch";
+    case BZ_E_STREAM_CRC: return "stream CRC mismatch";
+    case BZ_E_TRAILING: return "bytes behind the end of the stream";
+    case BZ_E_CHAIN: return "a block ends where no block starts";
+    case BZ_E_RUN: return "a block stops behind four equal bytes";
+    default: return "unknown status";
+    }
+}
+
+namespace {
+struct BzDev : DevKeep {
+    GzBuf in, list, count, pos, res, L, cnt, links, tt, lens, crc, out, bad;
+    u64 n = 0;
+    u32 bs = 0;
+    bool timing = false;
+    double ms[5] = {0, 0, 0, 0, 0};                               // find, entropy, scatter, walk, run-length layer and CRC
+    explicit BzDev(lrge_hip_ctx *c) : DevKeep(c) {
+        for (GzBuf *b : {&in, &list, &count, &pos, &res, &L, &cnt, &links, &tt, &lens, &crc, &out, &bad}) b->ctx = c;
+        timing = c->opt("BZIP2_TIMING") != nullptr;
+    }
+    ~BzDev() { (void)hipStreamSynchronize(ctx->stream); }
+    // a stage's time, when asked for: the stream is drained at its end
+    struct Lap {
+        BzDev &d; int slot; double t0;
+        Lap(BzDev &dev, int s) : d(dev), slot(s), t0(dev.timing ? DevPool::now_ms() : 0) {}
+        bool end() { if (!d.timing) return true; const bool r = d.sync(); d.ms[slot] += DevPool::now_ms() - t0; return r; }
+    };
+    bool load(const uint8_t *d, uint64_t len) {
+        n = len;
+        const u64 body = len & ~(u64)15, size = ((len + 15) & ~(u64)15) + BZ_PAD;
+        if (!in.need((size_t)size, &e)) return false;
+        if (!ok(hipMemsetAsync(in.as<u8>() + body, 0, (size_t)(size - body), ctx->stream))) return false;
+        if (!ok(hipMemcpyAsync(in.p, d, (size_t)len, hipMemcpyHostToDevice, ctx->stream))) return false;
+        return sync();
+    }
+    bool find(std::vector<uint64_t> &c) {
+        Lap lap(*this, 0);
+        // about one candidate per block is expected: a list that proves too short is sized by the count, and the scan runs once more
+        u64 cap = n / 64 + 16;
+        for (int pass = 0;; ++pass) {
+            u32 found = 0;
+            if (cap > 0xFFFFFFFFull) { e = hipErrorInvalidValue; return false; }
+            if (!list.need((size_t)cap * 8, &e) || !count.need(4, &e)) return false;
+            if (!ok(hipMemsetAsync(count.p, 0, 4, ctx->stream))) return false;
+            hipLaunchKernelGGL(k_bz_find, dim3((u32)div_up(div_up(n, 16), BZ_FIND_THREADS)), dim3(BZ_FIND_THREADS), 0, ctx->stream, in.as<const u8>(), n, list.as<u64>(),
+                               (u32)cap, count.as<u32>());
+            if (!ok(hipGetLastError())) return false;
+            if (!ok(hipMemcpyAsync(&found, count.p, 4, hipMemcpyDeviceToHost, ctx->stream)) || !sync()) return false;
+            if (found > cap) {
+                if (pass) { e = hipErrorUnknown; return false; }   // (the same bytes gave another count)
+                cap = found;
+                continue;
+            }
+            c.resize(found);
+            if (found && (!ok(hipMemcpyAsync(c.data(), list.p, (size_t)found * 8, hipMemcpyDeviceToHost, ctx->stream)) || !sync())) return false;
+            std::sort(c.begin(), c.end(), [](uint64_t a, uint64_t b) { return (a & ~BZ_END_FLAG) < (b & ~BZ_END_FLAG); });
+            return lap.end();
+        }
+    }
+    uint32_t default_round(uint32_t block) {
+        size_t mfree = 0, mtot = 0;
+        if (hipMemGetInfo(&mfree, &mtot) != hipSuccess) { (void)hipGetLastError(); mfree = 0; }
+        // (the text of a block is about its size again)
+        return (uint32_t)std::min<u64>(BZ_ROUND_MAX, std::max<u64>(1, ((u64)mfree + ctx->pool.idle()) / 2 / (bz_candidate_bytes(block) + block)));
+    }
+    bool decode(const uint64_t *p, uint32_t k, uint32_t block, BzRes *r) {
+        Lap lap(*this, 1);
+        bs = block;
+        if (!pos.need((size_t)k * 8, &e) || !res.need((size_t)k * sizeof(BzRes), &e) || !L.need((size_t)k * bs, &e) || !cnt.need((size_t)k * 1024, &e)) return false;
+        if (!ok(hipMemcpyAsync(pos.p, p, (size_t)k * 8, hipMemcpyHostToDevice, ctx->stream))) return false;
+        hipLaunchKernelGGL(k_bz_decode, dim3(k), dim3(64), 0, ctx->stream, in.as<const u8>(), n, pos.as<const u64>(), k, bs, L.as<u8>(), cnt.as<u32>(), res.as<BzRes>());
+        if (!ok(hipGetLastError())) return false;
+        if (!ok(hipMemcpyAsync(r, res.p, (size_t)k * sizeof(BzRes), hipMemcpyDeviceToHost, ctx->stream)) || !sync()) return false;
+        return lap.end();
+    }
+    bool finish(BzLink *l, uint32_t m, uint32_t *crc_h, uint64_t *out_bytes, const uint8_t **bytes) {
+        hipStream_t st = ctx->stream;
+        u64 links_n = 0;
+        for (uint32_t a = 0; a < m; ++a) { l[a].tt_off = links_n; links_n += l[a].n; }
+        if (!links.need((size_t)m * sizeof(BzLink), &e) || !tt.need((size_t)links_n * 4, &e) || !lens.need((size_t)m * 8, &e) || !crc.need((size_t)m * 4, &e) ||
+            !bad.need(4, &e))
+            return false;
+        if (!ok(hipMemcpyAsync(links.p, l, (size_t)m * sizeof(BzLink), hipMemcpyHostToDevice, st)) || !ok(hipMemsetAsync(bad.p, 0, 4, st))) return false;
+        const u32 lane_blocks = (u32)div_up(m, 64);
+        {
+            Lap lap(*this, 2);
+            hipLaunchKernelGGL(k_bz_scatter, dim3(m), dim3(64), 0, st, links.as<const BzLink>(), m, bs, L.as<const u8>(), cnt.as<const u32>(), tt.as<u32>());
+            if (!ok(hipGetLastError()) || !lap.end()) return false;
+        }
+        {
+            Lap lap(*this, 3);
+            hipLaunchKernelGGL(k_bz_walk, dim3(lane_blocks), dim3(64), 0, st, links.as<const BzLink>(), m, bs, tt.as<const u32>(), L.as<u8>(), bad.as<u32>());
+            if (!ok(hipGetLastError()) || !lap.end()) return false;
+        }
+        Lap lap(*this, 4);
+        hipLaunchKernelGGL(k_bz_rle_count, dim3(lane_blocks), dim3(64), 0, st, links.as<const BzLink>(), m, bs, L.as<const u8>(), lens.as<u64>());
+        if (!ok(hipGetLastError())) return false;
+        std::vector<u64> len_h(m);
+        u32 bad_h = 0;
+        if (!ok(hipMemcpyAsync(len_h.data(), lens.p, (size_t)m * 8, hipMemcpyDeviceToHost, st)) || !ok(hipMemcpyAsync(&bad_h, bad.p, 4, hipMemcpyDeviceToHost, st)) || !sync())
+            return false;
+        if (bad_h) { e = hipErrorUnknown; return false; }          // (a link left its block: the counts were not L's)
+        u64 total = 0;
+        for (uint32_t a = 0; a < m; ++a) { l[a].out_off = total; l[a].run_open = (len_h[a] & BZ_RUN_OPEN) != 0; total += len_h[a] & ~BZ_RUN_OPEN; }
+        // the text: behind the earlier rounds' in the block that stays (keep_on), or in a buffer of the round
+        u8 *dst;
+        if (keep_on) { if (!keep_reserve(total)) return false; dst = keep + keep_len; }
+        else { if (!out.need((size_t)total + 4, &e)) return false; dst = out.as<u8>(); }
+        if (!ok(hipMemcpyAsync(links.p, l, (size_t)m * sizeof(BzLink), hipMemcpyHostToDevice, st))) return false;
+        hipLaunchKernelGGL(k_bz_rle_write, dim3(lane_blocks), dim3(64), 0, st, links.as<const BzLink>(), m, bs, L.as<const u8>(), dst, crc.as<u32>());
+        if (!ok(hipGetLastError())) return false;
+        if (!ok(hipMemcpyAsync(crc_h, crc.p, (size_t)m * 4, hipMemcpyDeviceToHost, st))) return false;
+        if (!lap.end()) return false;
+        u8 *h_out = nullptr;
+        if (keep_on) keep_len += total;
+        else {
+            if (!(h_out = ctx_pin(1, std::max<u64>(1, total)))) return false;
+            if (!ok(hipMemcpyAsync(h_out, dst, (size_t)total, hipMemcpyDeviceToHost, st))) return false;
+        }
+        if (!sync()) return false;
+        *out_bytes = total;
+        *bytes = keep_on ? keep : h_out;
+        return true;
+    }
+};
+}  // namespace
+
+// the whole bzip2 buffer through `sink`; LRGE_ERR_PARSE / DEVICE as lrge_hip_bzip2_inflate
+static int bzip2_inflate_impl(lrge_hip_ctx *ctx, const uint8_t *comp, uint64_t comp_len, int (*sink)(void *, const void *, uint64_t), void *user,
+                              lrge_hip_bzip2_stats *stats) {
+    (void)hipSetDevice(ctx->device);
+    BzStats st;
+    u64 bad = 0;
+    bool sink_stop = false;
+    int rc;
+    {
+        BzDev dev(ctx);
+        rc = bz_run(dev, comp, comp_len, ctx->opt_u64("BZIP2_ROUND_BLOCKS", 0), [&](const uint8_t *b, uint64_t k) {
+            if (sink(user, b, k) != 0) { sink_stop = true; return false; }
+            return true;
+        }, st, &bad);
+        if (rc == BZ_RUN_DEVICE && !sink_stop) {
+            LRGE_SET_ERR(ctx, "bzip2 inflate: %s", hipGetErrorString(dev.e != hipSuccess ? dev.e : hipErrorUnknown));
+            (void)hipGetLastError();
+        }
+        (void)hipStreamSynchronize(ctx->stream);
+        if (dev.timing) fprintf(stderr, "[lrge_hip] bzip2 stages ms: find %.3f entropy %.3f scatter %.3f walk %.3f rle_crc %.3f\n", dev.ms[0], dev.ms[1], dev.ms[2], dev.ms[3], dev.ms[4]);
+    }
+    if (stats) { stats->blocks = st.blocks; stats->candidates = st.candidates; stats->rejected_candidates = st.rejected; stats->rounds = st.rounds; stats->bytes_out = st.bytes_out; }
+    if (rc == BZ_RUN_OK) return LRGE_OK;
+    if (sink_stop) { ctx->err = "bzip2 inflate: the sink stopped the call"; return LRGE_ERR_IO; }
+    if (rc == BZ_RUN_DEVICE) return LRGE_ERR_DEVICE;
+    LRGE_SET_ERR(ctx, "bzip2 data at file offset %llu: %s", (unsigned long long)bad, bz_status_name(rc));
+    return LRGE_ERR_PARSE;
+}
+
+extern "C" int lrge_hip_bzip2_inflate(lrge_hip_ctx *ctx, const void *comp, uint64_t comp_len, int (*sink)(void *user, const void *bytes, uint64_t n),
+                                      void *user, lrge_hip_bzip2_stats *stats) {
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (!ctx || !sink || (!comp && comp_len)) return LRGE_ERR_INVALID;
+    return bzip2_inflate_impl(ctx, (const uint8_t *)comp, comp_len, sink, user, stats);
+}
+
+// bzip2 input whose text stays in HBM: the rounds of bz_run with BzDev writing every round's text behind the earlier rounds'
+// (DevKeep: keep_*).  LRGE_OK with the block in *d_text (the caller's now), LRGE_ERR_UNPROVEN, LRGE_ERR_DEVICE
+static int bzip2_inflate_to_device(lrge_hip_ctx *ctx, const uint8_t *comp, uint64_t comp_len, u64 max_bytes, u64 slack, u8 **d_text, u64 *n_text) {
+    BzStats st;
+    u64 bad = 0;
+    BzDev dev(ctx);
+    dev.keep_on = true; dev.keep_max = max_bytes; dev.keep_slack = slack;
+    const int rc = bz_run(dev, comp, comp_len, ctx->opt_u64("BZIP2_ROUND_BLOCKS", 0), [&](const uint8_t *, uint64_t) { return true; }, st, &bad);
+    (void)hipStreamSynchronize(ctx->stream);
+    if (rc == BZ_RUN_OK) {
+        if (!dev.keep && !dev.keep_reserve(0)) { LRGE_SET_ERR(ctx, "reads_open: device allocation failed"); return LRGE_ERR_DEVICE; }
+        *d_text = dev.keep; *n_text = dev.keep_len; dev.keep = nullptr;
+        return LRGE_OK;
+    }
+    if (dev.keep_over) { LRGE_SET_ERR(ctx, "reads_open: text above INGEST_MAX_BYTES (%llu)", (unsigned long long)max_bytes); return LRGE_ERR_UNPROVEN; }
+    if (rc == BZ_RUN_DEVICE) {
+        LRGE_SET_ERR(ctx, "reads_open: bzip2 inflate: %s", hipGetErrorString(dev.e != hipSuccess ? dev.e : hipErrorUnknown));
+        (void)hipGetLastError();
+        return LRGE_ERR_DEVICE;
+    }
+    LRGE_SET_ERR(ctx, "reads_open: bzip2 data not accepted by the device (%s near file offset %llu)", bz_status_name(rc), (unsigned long long)bad);
+    return LRGE_ERR_UNPROVEN;
+}

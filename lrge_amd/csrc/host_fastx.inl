@@ -1,6 +1,6 @@
 // host_fastx.inl -- read sets built on the device from FASTA / FASTQ text (k_fastx.h), from unaligned BAM
 // (k_bam.h, host_bam.inl) and from unaligned SAM (k_sam.h, host_sam.inl): the text reaches HBM
-// decompressed (BGZF chunks decoded into one block by the pipeline of host_inflate.inl, the gzip rounds appended device-to-device, plain input copied once), the
+// decompressed (BGZF chunks decoded into one block by the pipeline of host_inflate.inl, the gzip and bzip2 rounds appended device-to-device, plain input copied once), the
 // record scan runs there, only identifiers and lengths come back, and lrge_hip_seqset_from_reads gathers the selected reads
 // into dense ASCII for the device-source pack of host_seqset.inl.  Whatever the scan cannot prove is LRGE_ERR_UNPROVEN: the
 // caller takes lrge_hip_read_records*, which parses the file or reports it with the reference's messages.  Included into
@@ -213,6 +213,9 @@ extern "C" int lrge_hip_reads_open_mem(lrge_hip_ctx *ctx, const void *file_bytes
             const int rc = gzip_inflate_to_device(ctx, d, len, cap, &R->d_text, &R->n_text);
             if (rc) return rc;
         }
+    } else if (b(0) == 0x42 && b(1) == 0x5a && (flags & LRGE_GPU_INFLATE_BZIP2)) {
+        const int rc = bzip2_inflate_to_device(ctx, d, len, cap, FX_PAD, &R->d_text, &R->n_text);
+        if (rc) return rc;
     } else if ((b(0) == 0x42 && b(1) == 0x5a) || (b(0) == 0x28 && b(1) == 0xb5 && b(2) == 0x2f && b(3) == 0xfd) ||
                (b(0) == 0xfd && b(1) == 0x37 && b(2) == 0x7a && b(3) == 0x58 && b(4) == 0x5a)) {
         ctx->err = "reads_open: bzip2, zstd and xz input is decompressed on the host";

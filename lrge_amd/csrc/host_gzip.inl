@@ -34,34 +34,13 @@ struct GzBuf {
     ~GzBuf() { if (ctx) ctx->pool.release(p); }
 };
 
-struct GzDev {
+// what the device decoders share (GzDev here, BzDev of host_bzip2.inl): the first runtime error, the text that stays in HBM
+// and the context's pinned buffers
+struct DevKeep {
     lrge_hip_ctx *ctx;
     hipError_t e = hipSuccess;
-    GzBuf cand, tasks, res, sym, seg, links, tiles, windows, fsegs, seg_crc, err, out, carry, bigtab;
-    std::vector<GzBuf *> big_sym, big_seg;
-    std::vector<const u16 *> big_ptr;
-    uint32_t n = 0;
-    u64 S = 0; u32 SG = 0;
-    explicit GzDev(lrge_hip_ctx *c, const GzCfg &cfg) : ctx(c) {
-        for (GzBuf *b : {&cand, &tasks, &res, &sym, &seg, &links, &tiles, &windows, &fsegs, &seg_crc, &err, &out, &carry, &bigtab}) b->ctx = c;
-        in2[0].ctx = c; in2[1].ctx = c;
-        S = gz_slot_symbols(cfg); SG = gz_slot_segs(cfg);
-        if (carry.need(GZ_WIN, &e)) ok(hipMemsetAsync(carry.p, 0, GZ_WIN, ctx->stream));
-        ok(hipEventCreateWithFlags(&ev_in, hipEventDisableTiming));
-        ok(hipEventCreateWithFlags(&ev_out, hipEventDisableTiming));
-    }
-    ~GzDev() {
-        (void)hipStreamSynchronize(ctx->copy_stream); (void)hipStreamSynchronize(ctx->stream2); (void)hipStreamSynchronize(ctx->stream);
-        drop_big();
-        ctx->pool.release(keep);
-        if (ev_in) (void)hipEventDestroy(ev_in);
-        if (ev_out) (void)hipEventDestroy(ev_out);
-    }
-    void drop_big() {
-        for (GzBuf *b : big_sym) delete b;
-        for (GzBuf *b : big_seg) delete b;
-        big_sym.clear(); big_seg.clear(); big_ptr.clear();
-    }
+    explicit DevKeep(lrge_hip_ctx *c) : ctx(c) {}
+    ~DevKeep() { ctx->pool.release(keep); }
     bool ok(hipError_t x) { if (x != hipSuccess && e == hipSuccess) e = x; return e == hipSuccess; }
     // keep_on (host_fastx.inl): every round's bytes are appended to one pool block on the device instead of travelling to the host.
     // The block grows geometrically (a device-to-device copy on the main stream; the pool recycles in that stream's order); more than
@@ -82,6 +61,42 @@ struct GzDev {
         return true;
     }
     bool sync() { return ok(hipStreamSynchronize(ctx->stream)); }
+    // pinned host buffers of the context, kept across calls (0: input staging, 1: output)
+    u8 *ctx_pin(int i, size_t bytes) {
+        if (ctx->gz_pin_cap[i] >= bytes && ctx->gz_pin[i]) return ctx->gz_pin[i];
+        if (ctx->gz_pin[i]) (void)hipHostFree(ctx->gz_pin[i]);
+        ctx->gz_pin[i] = nullptr; ctx->gz_pin_cap[i] = 0;
+        if (!ok(hipHostMalloc((void **)&ctx->gz_pin[i], bytes, hipHostMallocDefault))) { ctx->gz_pin[i] = nullptr; return nullptr; }
+        ctx->gz_pin_cap[i] = bytes;
+        return ctx->gz_pin[i];
+    }
+};
+
+struct GzDev : DevKeep {
+    GzBuf cand, tasks, res, sym, seg, links, tiles, windows, fsegs, seg_crc, err, out, carry, bigtab;
+    std::vector<GzBuf *> big_sym, big_seg;
+    std::vector<const u16 *> big_ptr;
+    uint32_t n = 0;
+    u64 S = 0; u32 SG = 0;
+    explicit GzDev(lrge_hip_ctx *c, const GzCfg &cfg) : DevKeep(c) {
+        for (GzBuf *b : {&cand, &tasks, &res, &sym, &seg, &links, &tiles, &windows, &fsegs, &seg_crc, &err, &out, &carry, &bigtab}) b->ctx = c;
+        in2[0].ctx = c; in2[1].ctx = c;
+        S = gz_slot_symbols(cfg); SG = gz_slot_segs(cfg);
+        if (carry.need(GZ_WIN, &e)) ok(hipMemsetAsync(carry.p, 0, GZ_WIN, ctx->stream));
+        ok(hipEventCreateWithFlags(&ev_in, hipEventDisableTiming));
+        ok(hipEventCreateWithFlags(&ev_out, hipEventDisableTiming));
+    }
+    ~GzDev() {
+        (void)hipStreamSynchronize(ctx->copy_stream); (void)hipStreamSynchronize(ctx->stream2); (void)hipStreamSynchronize(ctx->stream);
+        drop_big();
+        if (ev_in) (void)hipEventDestroy(ev_in);
+        if (ev_out) (void)hipEventDestroy(ev_out);
+    }
+    void drop_big() {
+        for (GzBuf *b : big_sym) delete b;
+        for (GzBuf *b : big_seg) delete b;
+        big_sym.clear(); big_seg.clear(); big_ptr.clear();
+    }
 
     // the round's input: two device slots, the next round staged through pinned memory on the copy stream while this one decodes
     GzBuf in2[2];
@@ -112,15 +127,6 @@ struct GzDev {
         return true;
     }
     const u8 *in_ptr = nullptr;
-    // pinned host buffers of the context, kept across calls (0: input staging, 1: output)
-    u8 *ctx_pin(int i, size_t bytes) {
-        if (ctx->gz_pin_cap[i] >= bytes && ctx->gz_pin[i]) return ctx->gz_pin[i];
-        if (ctx->gz_pin[i]) (void)hipHostFree(ctx->gz_pin[i]);
-        ctx->gz_pin[i] = nullptr; ctx->gz_pin_cap[i] = 0;
-        if (!ok(hipHostMalloc((void **)&ctx->gz_pin[i], bytes, hipHostMallocDefault))) { ctx->gz_pin[i] = nullptr; return nullptr; }
-        ctx->gz_pin_cap[i] = bytes;
-        return ctx->gz_pin[i];
-    }
     uint32_t pend_nt = 0;
     bool wait(GzRes *r) {
         if (!ok(hipMemcpyAsync(r, res.p, (size_t)pend_nt * sizeof(GzRes), hipMemcpyDeviceToHost, ctx->stream))) return false;
@@ -247,6 +253,10 @@ extern "C" int lrge_hip_gzip_inflate(lrge_hip_ctx *ctx, const void *comp, uint64
     return gzip_inflate_impl(ctx, (const uint8_t *)comp, comp_len, sink, user, stats);
 }
 
+// (host_bzip2.inl)
+static int bzip2_inflate_impl(lrge_hip_ctx *ctx, const uint8_t *comp, uint64_t comp_len, int (*sink)(void *, const void *, uint64_t), void *user,
+                              lrge_hip_bzip2_stats *stats);
+
 extern "C" int lrge_hip_read_records_gpu_ex(lrge_hip_ctx *ctx, const char *path, int flags,
                                             void (*cb)(void *, const char *, uint64_t, const char *, uint64_t), void *user, int *used_device) {
     if (!ctx || !path || !cb) return LRGE_ERR_INVALID;
@@ -256,6 +266,18 @@ extern "C" int lrge_hip_read_records_gpu_ex(lrge_hip_ctx *ctx, const char *path,
     try {
         lrge::io::iter_records(path, [&](const std::string &n, const std::string &s) { cb(user, n.data(), (uint64_t)n.size(), s.data(), (uint64_t)s.size()); },
                                [&](const std::string &raw, std::string &data) -> bool {
+            if (lrge::io::detect_compression_format(raw) == lrge::io::CompressionFormat::Bzip2) {
+                if (!(flags & LRGE_GPU_INFLATE_BZIP2)) return false;
+                data.clear();
+                const int rc = bzip2_inflate_impl(ctx, (const uint8_t *)raw.data(), raw.size(), [](void *u, const void *b, uint64_t k) {
+                    ((std::string *)u)->append((const char *)b, (size_t)k);
+                    return 0;
+                }, &data, nullptr);
+                if (rc == LRGE_ERR_DEVICE) throw DeviceFail{rc};
+                if (rc != LRGE_OK) { data.clear(); return false; }     // not accepted by the device: the host path, with its messages
+                used = 1;
+                return true;
+            }
             std::vector<BgzfBlock> t;
             uint64_t total = 0;
             if (bgzf_scan_blocks((const uint8_t *)raw.data(), raw.size(), &t, &total)) {

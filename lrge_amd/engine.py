@@ -94,9 +94,24 @@ class Context:
         keys = ("members", "chunks", "speculative_starts", "rejected_starts", "redecoded_chunks", "overflow_retries", "bytes_out")
         return out, dict(zip(keys, list(st)))
 
+    def bzip2_inflate(self, data):
+        """A bzip2 buffer (one stream) decompressed on the device (lrge_hip_bzip2_inflate): bytes in, (bytes, dict of
+        lrge_hip_bzip2_stats) out.  Input the device does not accept (damage, a second stream, trailing bytes, a randomised
+        block) raises LrgeHipError with code ERR_PARSE."""
+        data = bytes(data)
+        parts = []
+
+        def sink(_user, p, n):
+            parts.append(C.string_at(p, n))
+            return 0
+        cb = _ffi.GZIP_SINK(sink)
+        st = (C.c_uint64 * len(_ffi.BZIP2_STAT_NAMES))()
+        self._check(self._lib.lrge_hip_bzip2_inflate(self.h, data, len(data), cb, None, C.cast(st, C.c_void_p)))
+        return b"".join(parts), dict(zip(_ffi.BZIP2_STAT_NAMES, list(st)))
+
     def open_reads(self, path_or_bytes, flags=_ffi.GPU_INFLATE_BGZF | _ffi.GPU_INFLATE_GZIP):
-        """A FASTA / FASTQ file (a path, or the bytes of the whole file) parsed on the device: plain, BGZF or any other gzip,
-        by `flags` (lrge_hip_reads_open*); | _ffi.GPU_INGEST_BAM takes unaligned BAM as well, | _ffi.GPU_INGEST_SAM unaligned SAM.  Returns a DeviceReads with names, lens and seqset().  Input the device does not
+        """A FASTA / FASTQ file (a path, or the bytes of the whole file) parsed on the device: plain, BGZF or any other gzip
+        (| _ffi.GPU_INFLATE_BZIP2: bzip2 as well), by `flags` (lrge_hip_reads_open*); | _ffi.GPU_INGEST_BAM takes unaligned BAM as well, | _ffi.GPU_INGEST_SAM unaligned SAM.  Returns a DeviceReads with names, lens and seqset().  Input the device does not
         prove raises UnprovenInput: read the file with the host readers (readio.load) instead."""
         return DeviceReads(self, path_or_bytes, flags)
 
