@@ -468,7 +468,17 @@ int  lrge_hip_bzip2_inflate(lrge_hip_ctx *ctx, const void *comp, uint64_t comp_l
    (default: half of the free device memory plus the context's idle arena bytes); the caller takes lrge_hip_read_records*, which
    parses the file or gives the reference's message.  LRGE_ERR_TOO_MANY: 2^32 records or more, or a sequence of 2^32 bases or
    more.  LRGE_ERR_IO: the file cannot be read.  An empty file is LRGE_OK with a count of 0.
-   lrge_hip_reads_count / _name_bytes / _text_bytes (io.rs:154-184): records, total identifier bytes, decompressed bytes.
+   | LRGE_GPU_INGEST_WINDOWED (k_fx_store): FASTA / FASTQ text larger than option INGEST_WINDOW_BYTES (default 1 GiB,
+   at most a quarter of INGEST_MAX_BYTES) passes through HBM in windows that are cut between records, and only the bases stay, dense
+   and in file order; INGEST_MAX_BYTES then bounds the bases plus the window, so a FASTQ about twice the cap can be taken.  The
+   records are those of the resident scan and of lrge_hip_read_records, or the call is LRGE_ERR_UNPROVEN (a window the scan does
+   not prove, a window of another format than the first, a window of 2^32 bytes or more, 2^32 records or 4 GiB of identifiers in
+   all); for text that is not well formed (empty
+   lines between records) the verdict may depend on the window.  Text within one window, BAM and SAM stay resident as without the flag.
+   lrge_hip_reads_count / _name_bytes / _text_bytes (io.rs:154-184): records, total identifier bytes, decompressed bytes (all
+   that was scanned, whether or not it stayed).
+   lrge_hip_reads_window_stats (io.rs:154-184): out[0] windows flushed (0: the text stayed resident), out[1] bases kept, out[2] the
+   largest window in bytes, out[3] bytes carried over cuts into the next window.
    lrge_hip_reads_table (io.rs:154-184): seq_len[n], name_off[n + 1] and the identifiers back to back in names[name_bytes]
    (identifier i is names[name_off[i], name_off[i + 1]); any of the three may be NULL).
    lrge_hip_reads_timings (io.rs:154-184): milliseconds of the open call -- text to HBM, record scan, identifiers and lengths to the
@@ -490,6 +500,7 @@ typedef struct lrge_hip_bam_stats {
 } lrge_hip_bam_stats;
 #define LRGE_GPU_INGEST_BAM 4
 #define LRGE_GPU_INGEST_SAM 8
+#define LRGE_GPU_INGEST_WINDOWED 32
 int      lrge_hip_reads_open(lrge_hip_ctx *ctx, const char *path, int flags, lrge_hip_reads **out);
 int      lrge_hip_reads_open_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, int flags, lrge_hip_reads **out);
 uint64_t lrge_hip_reads_count(const lrge_hip_reads *reads);
@@ -498,6 +509,7 @@ uint64_t lrge_hip_reads_text_bytes(const lrge_hip_reads *reads);
 int      lrge_hip_reads_table(const lrge_hip_reads *reads, uint32_t *seq_len, uint64_t *name_off, char *names);
 int      lrge_hip_reads_timings(const lrge_hip_reads *reads, float ms[4]);
 int      lrge_hip_reads_bam_stats(const lrge_hip_reads *reads, lrge_hip_bam_stats *out);
+int      lrge_hip_reads_window_stats(const lrge_hip_reads *reads, uint64_t out[4]);
 int      lrge_hip_seqset_from_reads(lrge_hip_ctx *ctx, const lrge_hip_reads *reads, const uint32_t *idx, uint32_t n,
                                     const uint32_t *name_rank, lrge_hip_seqset **out);
 void     lrge_hip_reads_free(lrge_hip_reads *reads);

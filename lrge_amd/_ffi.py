@@ -15,6 +15,7 @@ GPU_INFLATE_BGZF, GPU_INFLATE_GZIP = 1, 2
 GPU_INGEST_BAM = 4
 GPU_INGEST_SAM = 8
 GPU_INFLATE_BZIP2 = 16
+GPU_INGEST_WINDOWED = 32
 PRESET_AVA_ONT, PRESET_AVA_PB = 0, 1
 
 T_NAMES = ["pack", "sketch", "index_sort", "index_table", "qfilter", "lookup", "expand", "anchor_sort", "group",
@@ -37,7 +38,7 @@ EXPORTS = [
     "lrge_hip_bgzf_scan", "lrge_hip_bgzf_inflate", "lrge_hip_read_records_gpu",
     "lrge_hip_gzip_inflate", "lrge_hip_read_records_gpu_ex", "lrge_hip_bzip2_inflate",
     "lrge_hip_reads_open", "lrge_hip_reads_open_mem", "lrge_hip_reads_count", "lrge_hip_reads_name_bytes", "lrge_hip_reads_text_bytes",
-    "lrge_hip_reads_table", "lrge_hip_reads_timings", "lrge_hip_reads_bam_stats", "lrge_hip_seqset_from_reads", "lrge_hip_reads_free",
+    "lrge_hip_reads_table", "lrge_hip_reads_timings", "lrge_hip_reads_bam_stats", "lrge_hip_reads_window_stats", "lrge_hip_seqset_from_reads", "lrge_hip_reads_free",
     "lrge_hip_index_build", "lrge_hip_index_build_for", "lrge_hip_index_build_sharded", "lrge_hip_index_build_tsharded", "lrge_hip_last_shard_stats", "lrge_hip_index_free",
     "lrge_hip_comm_alltoallv", "lrge_hip_comm_rccl_ranks", "lrge_hip_comm_rccl_ops", "lrge_hip_comm_local_group_serialize", "lrge_hip_comm_local_turn",
     "lrge_hip_comm_busy_ms", "lrge_hip_comm_standin_ms",
@@ -114,6 +115,7 @@ def lib():
     L.lrge_hip_reads_table.argtypes = [vp, vp, vp, vp]
     L.lrge_hip_reads_timings.argtypes = [vp, C.POINTER(C.c_float * 4)]
     L.lrge_hip_reads_bam_stats.argtypes = [vp, C.POINTER(C.c_uint64 * len(BAM_STAT_NAMES))]
+    L.lrge_hip_reads_window_stats.argtypes = [vp, C.POINTER(C.c_uint64 * 4)]
     L.lrge_hip_seqset_from_reads.argtypes = [vp, vp, vp, C.c_uint32, vp, C.POINTER(vp)]
     L.lrge_hip_reads_free.argtypes = [vp]
     L.lrge_hip_reads_free.restype = None

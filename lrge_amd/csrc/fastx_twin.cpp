@@ -1,13 +1,15 @@
 // fastx_twin.cpp -- the host twin of the device record scan (k_fastx.h, host_fastx.inl; g++): the same passes over the same
 // core (fastx_core.h) run tile by tile on the CPU -- census, exclusive scans, table scatter, per-record rules, sequence gather --
 // with the tile size a parameter, so the CPU suite checks the algorithm against the host parser with records and lines
-// straddling tile edges (tests/test_fastx_twin.py).  TEST INFRASTRUCTURE, not part of the product library.
+// straddling tile edges (tests/test_fastx_twin.py); and the windowed ingest of fx_window.h over the same passes, with the window
+// and the appended piece as parameters (tests/test_fastx_window_twin.py).  TEST INFRASTRUCTURE, not part of the product library.
 #include <stdint.h>
 #include <string.h>
 
 #include <vector>
 
 #include "fastx_core.h"
+#include "fx_window.h"
 
 namespace {
 struct Parsed {
@@ -15,6 +17,8 @@ struct Parsed {
     std::vector<FxRec> recs;
 };
 Parsed g;
+// a window's request (fx_window.h): null for a text that is scanned whole
+struct Win { bool first, end; uint64_t cut; };
 
 // the masks of the 16-byte group at p (a multiple of 16), as a lane of the device passes forms them
 FxMasks group_at(const uint8_t *t, uint64_t n, uint64_t p) {
@@ -31,14 +35,23 @@ void scan_exclusive(std::vector<uint32_t> &v) {            // (wraps modulo 2^32
     uint32_t s = 0;
     for (uint32_t &x : v) { const uint32_t c = x; x = s; s += c; }
 }
-}  // namespace
 
-extern "C" {
+// the bases of record r of text t[0, n) appended to `out`, as the device copy forms them: the span in 16-byte groups, removed
+// bytes dropped
+void append_seq(const uint8_t *t, uint64_t n, const FxRec &r, std::vector<uint8_t> &out) {
+    const uint64_t a = r.seq_off, b = r.seq_off + r.seq_span;
+    for (uint64_t p = a & ~(uint64_t)15; p < b; p += 16) {
+        uint32_t keep = ~group_at(t, n, p).rem & valid_mask(n, p);
+        if (p < a) keep &= ~((1u << (a - p)) - 1);
+        if (b - p < 16) keep &= (1u << (b - p)) - 1;
+        for (; keep; keep &= keep - 1) out.push_back(t[p + (uint64_t)__builtin_ctz(keep)]);
+    }
+}
 
-// 0: proven (fastx_twin_count records), FX_UNPROVEN, FX_TOO_MANY.  `tile`: bytes per tile, a multiple of 16.
-int fastx_twin_parse(const uint8_t *t, uint64_t n, uint64_t tile) {
+// the passes over t[0, n) into `g`.  w: the scan of a window -- up to its cut (w->cut; 0: none yet, g stays empty) unless w->end
+int parse(const uint8_t *t, uint64_t n, uint64_t tile, Win *w) {
     g = Parsed();
-    if (tile < 16 || tile % 16) return -1;
+    if (w) w->cut = 0;
     const uint64_t n_tiles = (n + tile - 1) / tile;
     // pass 1: the census of every tile
     std::vector<uint32_t> c_lf(n_tiles), c_rem(n_tiles), c_hdr(n_tiles);
@@ -69,6 +82,7 @@ int fastx_twin_parse(const uint8_t *t, uint64_t n, uint64_t tile) {
     for (int i = 0; i < 4; ++i) c.head[i] = (uint64_t)i < n ? t[i] : 0;
     c.at_first = c.first < n ? t[c.first] : 0;
     c.tail = n ? t[n - 1] : 0;
+    if (w) fx_win_census(c, w->first);
     uint32_t verdict;
     const int fmt = fx_format(n, c, &verdict);
     if (verdict) return (int)verdict;
@@ -92,11 +106,18 @@ int fastx_twin_parse(const uint8_t *t, uint64_t n, uint64_t tile) {
                 for (uint32_t m = lf; m; m &= m - 1) ls[++r] = p + (uint64_t)__builtin_ctz(m) + 1;
             }
         }
-        uint64_t n_lines, n_rec;
+        uint64_t n_lines, n_rec, n_use = n, n_lf = c.n_lf;
         fx_fastq_shape(n, c, l0, l_last, &n_lines, &n_rec);
+        if (w && !w->end) {                                 // the prefix of whole groups, scanned as a text of its own
+            n_rec = fx_win_fastq_groups(c.n_lf, l0, l_last);
+            if (!n_rec) { g.fmt = FX_FMT_EMPTY; return 0; }
+            n_lf = n_lines = l0 + 4 * n_rec;
+            n_use = ls[n_lf];
+        }
         if (n_rec >> 32) return FX_TOO_MANY;
         g.recs.resize(n_rec);
-        for (uint64_t r = 0; r < n_rec; ++r) flags |= fx_fastq_record(t, n, ls.data(), c.n_lf, n_lines, l0, r, &g.recs[r]);
+        for (uint64_t r = 0; r < n_rec; ++r) flags |= fx_fastq_record(t, n_use, ls.data(), n_lf, n_lines, l0, r, &g.recs[r]);
+        if (w) w->cut = n_use;
     } else {
         // pass 2: where every header is and how many removed bytes lie in front of it
         std::vector<uint64_t> hpos(c.n_hdr);
@@ -113,11 +134,65 @@ int fastx_twin_parse(const uint8_t *t, uint64_t n, uint64_t tile) {
                 rem += (uint32_t)__builtin_popcount(m.rem);
             }
         }
-        g.recs.resize(c.n_hdr);
-        for (uint64_t i = 0; i < c.n_hdr; ++i) flags |= fx_fasta_record(t, n, hpos.data(), hrem.data(), c.n_hdr, c.n_rem, i, &g.recs[i]);
+        uint64_t n_rec = c.n_hdr, n_use = n, n_rem = c.n_rem;
+        if (w && !w->end) {                                 // the prefix in front of the last header, scanned as a text of its own
+            n_rec = c.n_hdr - 1;
+            n_use = hpos[n_rec]; n_rem = hrem[n_rec];
+            if (!n_use) { g.fmt = FX_FMT_EMPTY; return 0; }
+            if (!n_rec) g.fmt = FX_FMT_EMPTY;               // (the empty lines in front of the first header)
+        }
+        g.recs.resize(n_rec);
+        for (uint64_t i = 0; i < n_rec; ++i) flags |= fx_fasta_record(t, n_use, hpos.data(), hrem.data(), n_rec, n_rem, i, &g.recs[i]);
+        if (w) w->cut = n_use;
     }
-    if (flags) { g.recs.clear(); return flags & FX_UNPROVEN ? (int)FX_UNPROVEN : (int)FX_TOO_MANY; }
+    if (flags) { g.recs.clear(); if (w) w->cut = 0; return flags & FX_UNPROVEN ? (int)FX_UNPROVEN : (int)FX_TOO_MANY; }
     return 0;
+}
+
+// ---- the windowed ingest: fx_window.h over the passes above ----
+struct WinOut {
+    std::vector<FxRec> recs;            // name_off: in the whole text; seq_off: in `store`; seq_span = seq_len
+    std::vector<uint8_t> store;
+    FxWinStats st = {0, 0, 0, 0};
+    int fmt = FX_FMT_EMPTY;
+};
+WinOut gw;
+
+struct WinTwin {
+    std::vector<uint8_t> blk;
+    uint64_t tile, base = 0;            // base: where the block starts in the whole text
+    uint64_t len() const { return blk.size(); }
+    int resident_format(bool *yes) const { *yes = false; return 0; }
+    void resident_again() const {}
+    int unproven(const char *) const { return (int)FX_UNPROVEN; }
+    int flush(bool first, bool end, uint64_t *cut, int *fmt) {
+        Win w = {first, end, 0};
+        const int rc = parse(blk.data(), blk.size(), tile, &w);
+        if (rc) return rc;
+        *cut = end ? blk.size() : w.cut;
+        *fmt = g.fmt;
+        if (!*cut) return 0;
+        for (const FxRec &r : g.recs) {
+            gw.recs.push_back(FxRec{base + r.name_off, gw.store.size(), r.seq_len, r.name_len, r.seq_len});
+            append_seq(blk.data(), *cut, r, gw.store);
+        }
+        return 0;
+    }
+    int carry(uint64_t cut) {
+        blk.erase(blk.begin(), blk.begin() + (long)cut);
+        base += cut;
+        return 0;
+    }
+};
+}  // namespace
+
+extern "C" {
+
+// 0: proven (fastx_twin_count records), FX_UNPROVEN, FX_TOO_MANY.  `tile`: bytes per tile, a multiple of 16.
+int fastx_twin_parse(const uint8_t *t, uint64_t n, uint64_t tile) {
+    g = Parsed();
+    if (tile < 16 || tile % 16) return -1;
+    return parse(t, n, tile, nullptr);
 }
 
 uint64_t fastx_twin_count(void) { return g.recs.size(); }
@@ -127,16 +202,41 @@ void fastx_twin_table(FxRec *out) { if (!g.recs.empty()) memcpy(out, g.recs.data
 // the bases of record i into out[0, seq_len), as the device gather forms them: the span in 16-byte groups, removed bytes dropped;
 // returns how many bytes were written
 uint64_t fastx_twin_seq(const uint8_t *t, uint64_t n, uint64_t i, uint8_t *out) {
-    const FxRec &r = g.recs[i];
-    const uint64_t a = r.seq_off, b = r.seq_off + r.seq_span;
-    uint64_t w = 0;
-    for (uint64_t p = a & ~(uint64_t)15; p < b; p += 16) {
-        uint32_t keep = ~group_at(t, n, p).rem & valid_mask(n, p);
-        if (p < a) keep &= ~((1u << (a - p)) - 1);
-        if (b - p < 16) keep &= (1u << (b - p)) - 1;
-        for (; keep; keep &= keep - 1) out[w++] = t[p + (uint64_t)__builtin_ctz(keep)];
+    std::vector<uint8_t> s;
+    append_seq(t, n, g.recs[i], s);
+    if (!s.empty()) memcpy(out, s.data(), s.size());
+    return s.size();
+}
+
+// The text through the windows of fx_window.h: `piece` bytes appended per step, a flush once the block holds `window` bytes.
+// 0: proven, FX_UNPROVEN, FX_TOO_MANY; the records by fastx_twin_windowed_count / _table / _seq, the counts by _stats
+// (windows flushed first: 0 means the text ended before its first flush and was scanned whole, as without windows).
+int fastx_twin_windowed(const uint8_t *t, uint64_t n, uint64_t tile, uint64_t window, uint64_t piece) {
+    gw = WinOut();
+    if (tile < 16 || tile % 16 || !piece) return -1;
+    WinTwin b;
+    b.tile = tile;
+    FxWindow<WinTwin> win(b, window);
+    int rc = 0;
+    for (uint64_t p = 0; p < n && !rc; p += piece) {
+        b.blk.insert(b.blk.end(), t + p, t + (n - p < piece ? n : p + piece));
+        rc = win.step(false);
     }
-    return w;
+    uint64_t all = 0;
+    if (!rc) rc = win.st.windows ? win.step(true) : b.flush(true, true, &all, &win.fmt);         // (or the resident scan)
+    if (rc) { gw = WinOut(); return rc; }
+    gw.st = win.st; gw.st.bases = gw.store.size(); gw.fmt = win.fmt;
+    return 0;
+}
+
+uint64_t fastx_twin_windowed_count(void) { return gw.recs.size(); }
+int fastx_twin_windowed_format(void) { return gw.fmt; }
+void fastx_twin_windowed_table(FxRec *out) { if (!gw.recs.empty()) memcpy(out, gw.recs.data(), gw.recs.size() * sizeof(FxRec)); }
+void fastx_twin_windowed_stats(uint64_t out[4]) { out[0] = gw.st.windows; out[1] = gw.st.bases; out[2] = gw.st.max_window; out[3] = gw.st.carried; }
+uint64_t fastx_twin_windowed_seq(uint64_t i, uint8_t *out) {
+    const FxRec &r = gw.recs[i];
+    if (r.seq_len) memcpy(out, gw.store.data() + r.seq_off, r.seq_len);
+    return r.seq_len;
 }
 
 }  // extern "C"

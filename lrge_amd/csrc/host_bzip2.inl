@@ -132,7 +132,7 @@ struct BzDev : DevKeep {
         if (!ok(hipMemcpyAsync(crc_h, crc.p, (size_t)m * 4, hipMemcpyDeviceToHost, st))) return false;
         if (!lap.end()) return false;
         u8 *h_out = nullptr;
-        if (keep_on) keep_len += total;
+        if (keep_on) { keep_len += total; if (keep_flush && !keep_flush()) return false; }
         else {
             if (!(h_out = ctx_pin(1, std::max<u64>(1, total)))) return false;
             if (!ok(hipMemcpyAsync(h_out, dst, (size_t)total, hipMemcpyDeviceToHost, st))) return false;
@@ -182,12 +182,14 @@ extern "C" int lrge_hip_bzip2_inflate(lrge_hip_ctx *ctx, const void *comp, uint6
 }
 
 // bzip2 input whose text stays in HBM: the rounds of bz_run with BzDev writing every round's text behind the earlier rounds'
-// (DevKeep: keep_*).  LRGE_OK with the block in *d_text (the caller's now), LRGE_ERR_UNPROVEN, LRGE_ERR_DEVICE
-static int bzip2_inflate_to_device(lrge_hip_ctx *ctx, const uint8_t *comp, uint64_t comp_len, u64 max_bytes, u64 slack, u8 **d_text, u64 *n_text) {
+// (DevKeep: keep_*).  LRGE_OK with the block in *d_text (the caller's now), LRGE_ERR_UNPROVEN, LRGE_ERR_DEVICE.  run: the call is
+// windowed -- the block is flushed through the run whenever a round has been appended (DevKeep::keep_flush), as for gzip
+static int bzip2_inflate_to_device(lrge_hip_ctx *ctx, const uint8_t *comp, uint64_t comp_len, u64 max_bytes, u64 slack, u8 **d_text, u64 *n_text, FxWinRun *run) {
     BzStats st;
     u64 bad = 0;
     BzDev dev(ctx);
     dev.keep_on = true; dev.keep_max = max_bytes; dev.keep_slack = slack;
+    if (run) fx_win_attach(run, &dev);
     const int rc = bz_run(dev, comp, comp_len, ctx->opt_u64("BZIP2_ROUND_BLOCKS", 0), [&](const uint8_t *, uint64_t) { return true; }, st, &bad);
     (void)hipStreamSynchronize(ctx->stream);
     if (rc == BZ_RUN_OK) {
@@ -195,6 +197,7 @@ static int bzip2_inflate_to_device(lrge_hip_ctx *ctx, const uint8_t *comp, uint6
         *d_text = dev.keep; *n_text = dev.keep_len; dev.keep = nullptr;
         return LRGE_OK;
     }
+    if (run && fx_win_stopped(run)) return fx_win_stopped(run);
     if (dev.keep_over) { LRGE_SET_ERR(ctx, "reads_open: text above INGEST_MAX_BYTES (%llu)", (unsigned long long)max_bytes); return LRGE_ERR_UNPROVEN; }
     if (rc == BZ_RUN_DEVICE) {
         LRGE_SET_ERR(ctx, "reads_open: bzip2 inflate: %s", hipGetErrorString(dev.e != hipSuccess ? dev.e : hipErrorUnknown));

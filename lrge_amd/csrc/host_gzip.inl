@@ -47,12 +47,15 @@ struct DevKeep {
     // keep_max bytes stops the call with keep_over set.  The bytes count only when the call as a whole returns OK.
     bool keep_on = false, keep_over = false;
     u8 *keep = nullptr;
-    u64 keep_len = 0, keep_cap = 0, keep_max = 0, keep_hint = 0, keep_slack = 0;
+    u64 keep_len = 0, keep_cap = 0, keep_max = 0, keep_hint = 0, keep_slack = 0, keep_floor = (u64)1 << 20, keep_grow = 2;
+    // called wherever keep_len has grown, ordered on the main stream like the append itself: the windowed ingest (host_fastx.inl)
+    // takes whole records off the front of the block here.  false stops the call
+    std::function<bool()> keep_flush;
     bool keep_reserve(u64 more) {
         const u64 need = keep_len + more;
         if (need > keep_max) { keep_over = true; return false; }
         if (keep && need <= keep_cap) return true;
-        const u64 cap = std::min<u64>(keep_max, std::max<u64>(std::max<u64>(need, keep_hint), std::max<u64>(2 * keep_cap, (u64)1 << 20)));
+        const u64 cap = std::min<u64>(keep_max, std::max<u64>(std::max<u64>(need, keep_hint), std::max<u64>(keep_grow * keep_cap, keep_floor)));
         u8 *p = (u8 *)ctx->pool.alloc((size_t)(cap + keep_slack), &e);
         if (!p) return false;
         if (keep_len && !ok(hipMemcpyAsync(p, keep, (size_t)keep_len, hipMemcpyDeviceToDevice, ctx->stream))) { ctx->pool.release(p); return false; }
@@ -71,6 +74,14 @@ struct DevKeep {
         return ctx->gz_pin[i];
     }
 };
+
+}  // namespace
+// the windowed ingest (host_fastx.inl) attaches its run to a decoder's block before the first round; fx_win_stopped: the code the
+// run stopped the decoder with (its message restored), 0 if it did not
+struct FxWinRun;
+static void fx_win_attach(FxWinRun *run, DevKeep *blk);
+static int fx_win_stopped(FxWinRun *run);
+namespace {
 
 struct GzDev : DevKeep {
     GzBuf cand, tasks, res, sym, seg, links, tiles, windows, fsegs, seg_crc, err, out, carry, bigtab;
@@ -195,6 +206,7 @@ struct GzDev : DevKeep {
             if (!keep_reserve(out_bytes)) return false;
             if (out_bytes && !ok(hipMemcpyAsync(keep + keep_len, out.p, out_bytes, hipMemcpyDeviceToDevice, st))) return false;
             keep_len += out_bytes;
+            if (keep_flush && !keep_flush()) return false;
         }
         // the bytes travel on the side stream while the next round is staged and decoded (bytes_ready waits for them)
         if (!ok(hipEventRecord(ev_out, st)) || !ok(hipStreamWaitEvent(ctx->stream2, ev_out, 0))) return false;

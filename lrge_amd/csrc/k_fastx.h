@@ -11,6 +11,7 @@
 //   k_fx_records   one lane per record: the record table (FxRec, 32 B), lengths, verdict bits
 //   k_fx_names     identifiers compacted into one dense buffer
 //   k_fx_gather    one wavefront per selected read: its bases into one dense ASCII buffer, removed bytes dropped
+//   k_fx_store     windowed ingest: one wavefront per record of a window, its bases into the base store   (same copy)
 // The text buffer is allocated with FX_PAD bytes behind its end, so whole 16-byte groups (and the word behind an unaligned
 // source word of the gather) may be loaded; every byte at or past `n` is masked out before use.
 #pragma once
@@ -178,52 +179,59 @@ __global__ __launch_bounds__(FX_THREADS) void k_fx_names(const u8 *__restrict__ 
     for (u32 i = 0; i < k; ++i) d[i] = s[i];
 }
 
-// Read j of the selection (record idx[j]) to dense[boff[j], boff[j + 1]).  A single-line sequence (span == length) is copied
+// The bases of one record to d[0, seq_len), by one wavefront (`lane` of 64).  A single-line sequence (span == length) is copied
 // in aligned 4-byte words, each assembled from the two source words it overlaps; a multi-line one is compacted group by
 // group with a wave scan of the kept bytes.
-__global__ __launch_bounds__(64) void k_fx_gather(const u8 *__restrict__ t, u64 n, const FxRec *__restrict__ recs, const u32 *__restrict__ idx,
-                                                  const u64 *__restrict__ boff, u32 n_sel, u8 *__restrict__ dense) {
-    const u32 lane = threadIdx.x;
-    for (u32 j = blockIdx.x; j < n_sel; j += gridDim.x) {
-        const FxRec rec = recs[idx[j]];
-        u8 *d = dense + boff[j];
-        const u64 a = rec.seq_off, len = rec.seq_len;
-        if (rec.seq_span == len) {
-            const u8 *s = t + a;
-            u64 head = (4 - ((uintptr_t)d & 3)) & 3;
-            if (head > len) head = len;
-            if (lane < head) d[lane] = s[lane];
-            const u64 nw = (len - head) >> 2;
-            for (u64 w = lane; w < nw; w += 64) {
-                const uintptr_t sa = (uintptr_t)(s + head + 4 * w);
-                const u32 sh = (u32)(sa & 3) * 8;
-                const u32 *q = reinterpret_cast<const u32 *>(sa & ~(uintptr_t)3);
-                const u32 lo = q[0];
-                reinterpret_cast<u32 *>(d + head)[w] = sh ? (u32)((((u64)q[1] << 32) | lo) >> sh) : lo;
+__device__ __forceinline__ void fx_copy_bases(const u8 *__restrict__ t, u64 n, const FxRec &rec, u8 *__restrict__ d, u32 lane) {
+    const u64 a = rec.seq_off, len = rec.seq_len;
+    if (rec.seq_span == len) {
+        const u8 *s = t + a;
+        u64 head = (4 - ((uintptr_t)d & 3)) & 3;
+        if (head > len) head = len;
+        if (lane < head) d[lane] = s[lane];
+        const u64 nw = (len - head) >> 2;
+        for (u64 w = lane; w < nw; w += 64) {
+            const uintptr_t sa = (uintptr_t)(s + head + 4 * w);
+            const u32 sh = (u32)(sa & 3) * 8;
+            const u32 *q = reinterpret_cast<const u32 *>(sa & ~(uintptr_t)3);
+            const u32 lo = q[0];
+            reinterpret_cast<u32 *>(d + head)[w] = sh ? (u32)((((u64)q[1] << 32) | lo) >> sh) : lo;
+        }
+        for (u64 i = head + 4 * nw + lane; i < len; i += 64) d[i] = s[i];
+    } else {
+        const u64 b = a + rec.seq_span;
+        u64 done = 0;
+        for (u64 p0 = a & ~(u64)15; p0 < b; p0 += 64 * 16) {
+            const u64 p = p0 + (u64)lane * 16;
+            u32 keep = 0;
+            uint4 q = {0, 0, 0, 0};
+            if (p < b && p < n) {
+                q = *reinterpret_cast<const uint4 *>(t + p);
+                const u32 next = p + 16 < n ? t[p + 16] : FX_EOT;
+                keep = ~fx_group_masks(q.x, q.y, q.z, q.w, '\n', next, (u32)(n - p < 16 ? n - p : 16)).rem & fx_valid_mask(n, p);
+                if (p < a) keep &= ~((1u << (u32)(a - p)) - 1);
+                if (b - p < 16) keep &= (1u << (u32)(b - p)) - 1;
             }
-            for (u64 i = head + 4 * nw + lane; i < len; i += 64) d[i] = s[i];
-        } else {
-            const u64 b = a + rec.seq_span;
-            u64 done = 0;
-            for (u64 p0 = a & ~(u64)15; p0 < b; p0 += 64 * 16) {
-                const u64 p = p0 + (u64)lane * 16;
-                u32 keep = 0;
-                uint4 q = {0, 0, 0, 0};
-                if (p < b && p < n) {
-                    q = *reinterpret_cast<const uint4 *>(t + p);
-                    const u32 next = p + 16 < n ? t[p + 16] : FX_EOT;
-                    keep = ~fx_group_masks(q.x, q.y, q.z, q.w, '\n', next, (u32)(n - p < 16 ? n - p : 16)).rem & fx_valid_mask(n, p);
-                    if (p < a) keep &= ~((1u << (u32)(a - p)) - 1);
-                    if (b - p < 16) keep &= (1u << (u32)(b - p)) - 1;
-                }
-                const u32 cnt = (u32)__popc(keep), inc = wave_incl_scan_u32(cnt);
-                u64 o = done + inc - cnt;
-                const u32 w[4] = {q.x, q.y, q.z, q.w};
+            const u32 cnt = (u32)__popc(keep), inc = wave_incl_scan_u32(cnt);
+            u64 o = done + inc - cnt;
+            const u32 w[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
-                for (u32 i = 0; i < 16; ++i)
-                    if ((keep >> i) & 1) d[o++] = (u8)(w[i >> 2] >> ((i & 3) * 8));
-                done += (u32)__shfl((int)inc, 63, 64);
-            }
+            for (u32 i = 0; i < 16; ++i)
+                if ((keep >> i) & 1) d[o++] = (u8)(w[i >> 2] >> ((i & 3) * 8));
+            done += (u32)__shfl((int)inc, 63, 64);
         }
     }
+}
+
+// Read j of the selection (record idx[j]) to dense[boff[j], boff[j + 1]).
+__global__ __launch_bounds__(64) void k_fx_gather(const u8 *__restrict__ t, u64 n, const FxRec *__restrict__ recs, const u32 *__restrict__ idx,
+                                                  const u64 *__restrict__ boff, u32 n_sel, u8 *__restrict__ dense) {
+    for (u32 j = blockIdx.x; j < n_sel; j += gridDim.x) fx_copy_bases(t, n, recs[idx[j]], dense + boff[j], threadIdx.x);
+}
+
+// Windowed ingest (fx_window.h): every record of a window's prefix to store[dst[r], dst[r] + seq_len), all of
+// them in file order.  dst: the exclusive scan of the window's seq_len; `store` points behind the bases of the earlier windows.
+__global__ __launch_bounds__(64) void k_fx_store(const u8 *__restrict__ t, u64 n, const FxRec *__restrict__ recs, const u32 *__restrict__ dst, u64 n_rec,
+                                                 u8 *__restrict__ store) {
+    for (u64 r = blockIdx.x; r < n_rec; r += gridDim.x) fx_copy_bases(t, n, recs[r], store + dst[r], threadIdx.x);
 }

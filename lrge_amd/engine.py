@@ -111,7 +111,7 @@ class Context:
 
     def open_reads(self, path_or_bytes, flags=_ffi.GPU_INFLATE_BGZF | _ffi.GPU_INFLATE_GZIP):
         """A FASTA / FASTQ file (a path, or the bytes of the whole file) parsed on the device: plain, BGZF or any other gzip
-        (| _ffi.GPU_INFLATE_BZIP2: bzip2 as well), by `flags` (lrge_hip_reads_open*); | _ffi.GPU_INGEST_BAM takes unaligned BAM as well, | _ffi.GPU_INGEST_SAM unaligned SAM.  Returns a DeviceReads with names, lens and seqset().  Input the device does not
+        (| _ffi.GPU_INFLATE_BZIP2: bzip2 as well), by `flags` (lrge_hip_reads_open*); | _ffi.GPU_INGEST_BAM takes unaligned BAM as well, | _ffi.GPU_INGEST_SAM unaligned SAM; | _ffi.GPU_INGEST_WINDOWED lets FASTA / FASTQ text above option INGEST_WINDOW_BYTES pass through in windows with only the bases kept (DeviceReads.window_stats).  Returns a DeviceReads with names, lens and seqset().  Input the device does not
         prove raises UnprovenInput: read the file with the host readers (readio.load) instead."""
         return DeviceReads(self, path_or_bytes, flags)
 
@@ -295,6 +295,12 @@ class DeviceReads:
         a = (C.c_uint64 * len(_ffi.BAM_STAT_NAMES))()
         self.ctx._check(self.ctx._lib.lrge_hip_reads_bam_stats(self.h, C.byref(a)))
         return dict(zip(_ffi.BAM_STAT_NAMES, [int(x) for x in a]))
+
+    def window_stats(self):
+        """(windows flushed -- 0: the text stayed resident --, bases kept, largest window in bytes, bytes carried over cuts)"""
+        a = (C.c_uint64 * 4)()
+        self.ctx._check(self.ctx._lib.lrge_hip_reads_window_stats(self.h, C.byref(a)))
+        return tuple(int(x) for x in a)
 
     def seqset(self, idx, ranks=None):
         """reads idx (any order, repeats allowed) as a SeqSet; ranks as Context.upload"""

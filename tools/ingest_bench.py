@@ -6,6 +6,10 @@ unaligned SAM text (the "sam" kind: its record scan beside the FASTQ kind's, and
 the files of the kinds asked for are written.  Usage:
   python tools/ingest_bench.py [--gbases 1.08] [--dir /tmp] [--reps 5] [--kinds fq,bgzf.fq.gz,fq.gz,bam,sam]
                                [--bam-segments 262144,1048576,4194304] [--out profiles/ingest_bench.json]
+                               [--windowed [--window-mb 64]]
+--windowed: only the FASTQ kinds, and on each file the windowed device route (LRGE_GPU_INGEST_WINDOWED with option
+INGEST_WINDOW_BYTES = --window-mb) beside the resident device route, alternating in the same run; the result goes under the
+key "windowed" of --out, whose other entries are kept.
 
 Both routes are driven by a small C++ helper (compiled here with g++ against liblrge_hip.so), so that no Python callback sits
 in either clock.  Both start from the file's path with the file in the page cache and end when lrge_hip_seqset_wait has
@@ -61,7 +65,7 @@ extern "C" int route_host(lrge_hip_ctx *ctx, const char *path, int flags, double
 }
 // ms: open (stages[0..2]: text to HBM, record scan, identifiers and lengths), seqset of all reads + wait
 extern "C" int route_device(lrge_hip_ctx *ctx, const char *path, int flags, double ms[2], float stages[4], uint64_t *n_reads, uint64_t *n_bases, uint64_t *text_bytes,
-                            lrge_hip_bam_stats *bam) {
+                            lrge_hip_bam_stats *bam, uint64_t win[4]) {
     const double t0 = now();
     lrge_hip_reads *r = nullptr;
     int rc = lrge_hip_reads_open(ctx, path, flags, &r);
@@ -78,6 +82,7 @@ extern "C" int route_device(lrge_hip_ctx *ctx, const char *path, int flags, doub
     uint64_t b = 0; for (uint32_t l : len) b += l;
     lrge_hip_reads_timings(r, stages);
     if (lrge_hip_reads_bam_stats(r, bam)) *bam = lrge_hip_bam_stats{0, 0, 0, 0, 0, 0};
+    lrge_hip_reads_window_stats(r, win);
     *n_reads = n; *n_bases = b; *text_bytes = lrge_hip_reads_text_bytes(r);
     lrge_hip_seqset_free(s); lrge_hip_reads_free(r);
     ms[0] = t1 - t0; ms[1] = t2 - t1;
@@ -171,6 +176,44 @@ def write_files(d, parts, kinds):
     return paths, size
 
 
+def windowed_runs(a, ctx, H, kinds, paths, text_bytes):
+    """the resident and the windowed device route on every file, alternating; into the key "windowed" of a.out"""
+    out = {"window_bytes": a.window_mb << 20, "reps": a.reps, "text_bytes": text_bytes, "files": {}}
+    ctx.set_option("INGEST_WINDOW_BYTES", str(a.window_mb << 20))
+    for kind in kinds:
+        p = paths[kind]
+        with open(p, "rb") as fh:
+            while fh.read(64 << 20):
+                pass                                                  # page cache
+        runs = {"resident": [], "windowed": []}
+        seen = {}
+        for rep in range(a.reps + 1):
+            for route, flags in (("resident", 15), ("windowed", 15 | 32)):
+                ms2, st, nr, nb, tb, bs, win = (C.c_double * 2)(), (C.c_float * 4)(), C.c_uint64(), C.c_uint64(), C.c_uint64(), (C.c_uint64 * 6)(), (C.c_uint64 * 4)()
+                rc = H.route_device(ctx.h, p.encode(), flags, C.byref(ms2), C.byref(st), C.byref(nr), C.byref(nb), C.byref(tb), C.byref(bs), C.byref(win))
+                assert rc == 0, (kind, route, rc, ctx._lib.lrge_hip_last_error(ctx.h))
+                assert tb.value == text_bytes[kind] and seen.setdefault("reads", (nr.value, nb.value)) == (nr.value, nb.value)
+                assert (win[0] >= 1 and win[1] == nb.value) if route == "windowed" else win[0] == 0, (kind, route, list(win))   # (a gzip round may deliver all of the text: one window)
+                seen[route] = list(win)
+                if rep:                                                # (run 0 is the warm-up)
+                    runs[route].append(dict(open_ms=ms2[0], seqset_ms=ms2[1], total_ms=sum(ms2), text_ms=st[0], scan_ms=st[1], names_ms=st[2]))
+        med = lambda r, k: statistics.median(x[k] for x in runs[r])   # noqa: E731
+        rng = lambda r, k: (min(x[k] for x in runs[r]), max(x[k] for x in runs[r]))   # noqa: E731
+        f = dict(file_bytes=os.path.getsize(p), reads=seen["reads"][0], text_bytes=text_bytes[kind], store_bytes=seen["windowed"][1], windows=seen["windowed"][0],
+                 largest_window_bytes=seen["windowed"][2], carried_bytes=seen["windowed"][3], resident_route=runs["resident"], windowed_route=runs["windowed"])
+        for r in ("resident", "windowed"):
+            for k in ("open_ms", "scan_ms", "seqset_ms", "total_ms"):
+                f["%s_%s_median" % (r, k)] = med(r, k)
+                f["%s_%s_range" % (r, k)] = rng(r, k)
+        out["files"][kind] = f
+        print(kind, json.dumps({k: v for k, v in f.items() if not k.endswith("_route")}), flush=True)
+    ctx.set_option("INGEST_WINDOW_BYTES", None)
+    result = json.load(open(a.out)) if os.path.exists(a.out) else {}
+    result["windowed"] = out
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    json.dump(result, open(a.out, "w"), indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gbases", type=float, default=1.08)
@@ -179,6 +222,8 @@ def main():
     ap.add_argument("--kinds", default=",".join(KINDS))
     ap.add_argument("--bam-segments", default="262144,1048576,4194304")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ingest_bench.json"))
+    ap.add_argument("--windowed", action="store_true")
+    ap.add_argument("--window-mb", type=int, default=64)
     a = ap.parse_args()
     from lrge_amd import build as B, engine
     work = tempfile.mkdtemp(dir=a.dir, prefix="ingest_bench_")
@@ -189,14 +234,17 @@ def main():
                            "-L" + B.LIB_DIR, "-llrge_hip", "-Wl,-rpath," + B.LIB_DIR])
     parts = max(1, round(a.gbases * 1e9 * 2.02 / (256 << 20)))       # a record is 2 bytes per base and a header
     t0 = time.perf_counter()
-    kinds = [k for k in KINDS if k in a.kinds.split(",")]
+    kinds = [k for k in KINDS if k in a.kinds.split(",") and (not a.windowed or k in ("fq", "bgzf.fq.gz", "fq.gz"))]
     paths, text_bytes = write_files(work, parts, kinds)
     print("files written in %.0f s: %s text bytes" % (time.perf_counter() - t0, text_bytes), flush=True)
     ctx = engine.Context(0)
     H = C.CDLL(so)
     H.route_host.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_double * 3), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     H.route_device.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_double * 2), C.POINTER(C.c_float * 4), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
-                               C.POINTER(C.c_uint64), C.POINTER(C.c_uint64 * 6)]
+                               C.POINTER(C.c_uint64), C.POINTER(C.c_uint64 * 6), C.POINTER(C.c_uint64 * 4)]
+    if a.windowed:
+        windowed_runs(a, ctx, H, kinds, paths, text_bytes)
+        kinds = []
     result = {"text_bytes": text_bytes, "reps": a.reps, "files": {}}
     # (a BAM run per segment size: the host route it is compared with does not depend on the option, and is timed beside each)
     work_list = [(k, k, None) for k in kinds if k != "bam"] + [("bam", "bam@%d" % int(S), int(S)) for S in a.bam_segments.split(",") if "bam" in kinds]
@@ -212,7 +260,7 @@ def main():
             rc = H.route_host(ctx.h, p.encode(), 3, C.byref(ms3), C.byref(nr), C.byref(nb))
             assert rc == 0, (kind, rc)
             ms2, st, nr2, nb2, tb, bs = (C.c_double * 2)(), (C.c_float * 4)(), C.c_uint64(), C.c_uint64(), C.c_uint64(), (C.c_uint64 * 6)()
-            rc = H.route_device(ctx.h, p.encode(), 15, C.byref(ms2), C.byref(st), C.byref(nr2), C.byref(nb2), C.byref(tb), C.byref(bs))
+            rc = H.route_device(ctx.h, p.encode(), 15, C.byref(ms2), C.byref(st), C.byref(nr2), C.byref(nb2), C.byref(tb), C.byref(bs), C.byref((C.c_uint64 * 4)()))
             assert rc == 0, (kind, rc, ctx._lib.lrge_hip_last_error(ctx.h))
             assert (nr.value, nb.value) == (nr2.value, nb2.value) and tb.value == text_bytes[kind]
             if rep:                                                    # (run 0 is the warm-up)
@@ -231,7 +279,10 @@ def main():
         print(label, json.dumps({k: v for k, v in f.items() if not k.endswith("_route")}), flush=True)
     ctx.close()
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    json.dump(result, open(a.out, "w"), indent=1)
+    if not a.windowed:
+        if os.path.exists(a.out) and "windowed" in json.load(open(a.out)):
+            result["windowed"] = json.load(open(a.out))["windowed"]
+        json.dump(result, open(a.out, "w"), indent=1)
     for p in list(paths.values()) + [src, so]:
         os.remove(p)
     os.rmdir(work)
