@@ -475,16 +475,24 @@ int  lrge_hip_bzip2_inflate(lrge_hip_ctx *ctx, const void *comp, uint64_t comp_l
    not prove, a window of another format than the first, a window of 2^32 bytes or more, 2^32 records or 4 GiB of identifiers in
    all); for text that is not well formed (empty
    lines between records) the verdict may depend on the window.  Text within one window, BAM and SAM stay resident as without the flag.
+   | LRGE_GPU_INGEST_WINDOWED_ALN (k_bam_spans, k_bam_store; effective only beside LRGE_GPU_INGEST_WINDOWED and the
+   format's own flag): unaligned BAM and SAM above INGEST_WINDOW_BYTES pass through in windows too.  A BAM window is cut at the
+   first record start of the chain proven from its front that the block does not hold whole, a SAM window directly behind its
+   last line feed.  BAM's bases stay packed as the file has them, 4 bits each, (l_seq + 1) / 2 bytes a record; SAM's stay as
+   ASCII.  The same outcomes: the records of lrge_hip_read_records, or LRGE_ERR_UNPROVEN for the whole call (a mapped record in
+   any window leaves no earlier record behind).
    lrge_hip_reads_count / _name_bytes / _text_bytes (io.rs:154-184): records, total identifier bytes, decompressed bytes (all
    that was scanned, whether or not it stayed).
-   lrge_hip_reads_window_stats (io.rs:154-184): out[0] windows flushed (0: the text stayed resident), out[1] bases kept, out[2] the
-   largest window in bytes, out[3] bytes carried over cuts into the next window.
+   lrge_hip_reads_window_stats (io.rs:154-184): out[0] windows flushed (0: the text stayed resident), out[1] bytes in the store (the
+   bases for FASTA / FASTQ / SAM, the packed bytes of the records for BAM), out[2] the largest window in bytes, out[3] bytes
+   carried over cuts into the next window.
    lrge_hip_reads_table (io.rs:154-184): seq_len[n], name_off[n + 1] and the identifiers back to back in names[name_bytes]
    (identifier i is names[name_off[i], name_off[i + 1]); any of the three may be NULL).
    lrge_hip_reads_timings (io.rs:154-184): milliseconds of the open call -- text to HBM, record scan, identifiers and lengths to the
    host, total (for BAM the record scan covers the candidate search, the walks, the repair rounds and the table).
    lrge_hip_reads_bam_stats (io.rs:154-184): the counts of the BAM record scan of `reads` (option BAM_SEGMENT_BYTES, default 256 KiB,
-   at least 64, sets the segment); LRGE_ERR_INVALID when `reads` was not scanned as BAM.
+   at least 64, sets the segment), for a windowed handle summed over its windows (the segments of a window start at its front,
+   and those behind its cut do not count); LRGE_ERR_INVALID when `reads` was not scanned as BAM.
    lrge_hip_seqset_from_reads (twoset.rs:122-201): reads idx[0..n) of `reads`, in that order (any order, repeats allowed; an entry
    out of range is LRGE_ERR_INVALID), as an ordinary read set: their bases are gathered on the device and packed by the
    device-source path of lrge_hip_seqset_upload, so the set is bit-identical to an upload of the same sequences.  name_rank as
@@ -501,6 +509,7 @@ typedef struct lrge_hip_bam_stats {
 #define LRGE_GPU_INGEST_BAM 4
 #define LRGE_GPU_INGEST_SAM 8
 #define LRGE_GPU_INGEST_WINDOWED 32
+#define LRGE_GPU_INGEST_WINDOWED_ALN 64
 int      lrge_hip_reads_open(lrge_hip_ctx *ctx, const char *path, int flags, lrge_hip_reads **out);
 int      lrge_hip_reads_open_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, int flags, lrge_hip_reads **out);
 uint64_t lrge_hip_reads_count(const lrge_hip_reads *reads);

@@ -76,7 +76,8 @@ struct Ctx {
 }  // namespace detail
 
 // The records of one FASTA / FASTQ file (or, with | LRGE_GPU_INGEST_BAM / LRGE_GPU_INGEST_SAM, one unaligned BAM / SAM) parsed on the device;
-// | LRGE_GPU_INGEST_WINDOWED: FASTA / FASTQ text above option INGEST_WINDOW_BYTES passes through in windows and only the bases stay
+// | LRGE_GPU_INGEST_WINDOWED: FASTA / FASTQ text above option INGEST_WINDOW_BYTES passes through in windows and only the bases stay;
+// | LRGE_GPU_INGEST_WINDOWED_ALN beside it and the format's flag: unaligned BAM (its bases kept packed) and SAM as well
 // (lrge_hip_reads_open, io.rs:154-184): identifiers and lengths on
 // the host, the bases resident in HBM as text.  Owns its context; the strategies built on it run in that context and take
 // their read sets with lrge_hip_seqset_from_reads.  open() gives nullptr for input the device does not prove (and for a file
@@ -86,7 +87,7 @@ struct DeviceReads {
     lrge_hip_reads *h = nullptr;
     std::vector<std::string> names;
     std::vector<uint32_t> lens;
-    uint64_t window_stats[4] = {0, 0, 0, 0};   // lrge_hip_reads_window_stats: windows flushed (0: resident), bases kept, largest window, bytes carried
+    uint64_t window_stats[4] = {0, 0, 0, 0};   // lrge_hip_reads_window_stats: windows flushed (0: resident), bytes in the store (BAM: packed bases), largest window, bytes carried
     DeviceReads() = default;
     DeviceReads(const DeviceReads &) = delete;
     DeviceReads &operator=(const DeviceReads &) = delete;

@@ -16,6 +16,7 @@ GPU_INGEST_BAM = 4
 GPU_INGEST_SAM = 8
 GPU_INFLATE_BZIP2 = 16
 GPU_INGEST_WINDOWED = 32
+GPU_INGEST_WINDOWED_ALN = 64
 PRESET_AVA_ONT, PRESET_AVA_PB = 0, 1
 
 T_NAMES = ["pack", "sketch", "index_sort", "index_table", "qfilter", "lookup", "expand", "anchor_sort", "group",

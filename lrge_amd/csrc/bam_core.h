@@ -16,6 +16,12 @@
 #define FX_FMT_BAM 3
 #define BAM_UNPROVEN FX_UNPROVEN
 #define BAM_NONE (~(uint64_t)0)            // no candidate in a segment; the landing of a walk that met a record it refuses
+// A window of the windowed ingest (fx_window.h) ends somewhere inside a record.  There the walks run in tail
+// mode: a record start that is only *incomplete* -- fewer than 4 bytes are left, or a block size of 32 or more reaches past the
+// end -- ends the walk with the landing BAM_TAIL | start.  Everything else bam_record refuses stays refused (a block size below
+// 32 is judged as soon as its four bytes are there).  Offsets are below 2^63, and BAM_NONE is never taken for a tail landing.
+#define BAM_TAIL ((uint64_t)1 << 63)
+#define BAM_SHORT 4u                       // beside BAM_UNPROVEN in a header's verdict: it failed only for lack of bytes
 
 // one segment: where its walk started (BAM_NONE: no walk), the records that start in it, and the first record start at or
 // behind its end that the walk reached (n at the exact end of the text)
@@ -49,22 +55,36 @@ FX_HD uint32_t bam_record(const uint8_t *t, uint64_t n, uint64_t off, FxRec *rec
     return 0;
 }
 
+// the record start at `off` <= n is incomplete: more bytes may still make it a record (or show that it is none)
+FX_HD bool bam_incomplete(const uint8_t *t, uint64_t n, uint64_t off) {
+    if (n - off < 4) return true;
+    const int32_t block = (int32_t)bam_u32(t, off);
+    return block >= 32 && n - off - 4 < (uint64_t)block;
+}
+
 // the header: magic, l_text, text, n_ref, then l_name, name, l_ref of every reference, with the host's bounds (a negative n_ref
-// is no reference, as there).  0 with *hdr_end the offset of the first record, or BAM_UNPROVEN.
+// is no reference, as there).  0 with *hdr_end the offset of the first record, or BAM_UNPROVEN; BAM_UNPROVEN | BAM_SHORT when
+// every field that is there passes and the text ends inside the header (a window's caller waits for more; any other has
+// BAM_UNPROVEN in it and needs no second look).
 FX_HD uint32_t bam_header(const uint8_t *t, uint64_t n, uint64_t *hdr_end) {
-    if (n < 8 || t[0] != 'B' || t[1] != 'A' || t[2] != 'M' || t[3] != 1) return BAM_UNPROVEN;
+    const uint8_t magic[4] = {'B', 'A', 'M', 1};
+    for (uint64_t i = 0; i < 4 && i < n; ++i)
+        if (t[i] != magic[i]) return BAM_UNPROVEN;
+    if (n < 8) return BAM_UNPROVEN | BAM_SHORT;
     const int32_t l_text = (int32_t)bam_u32(t, 4);
     uint64_t off = 8;
-    if (l_text < 0 || n - off < (uint64_t)l_text) return BAM_UNPROVEN;
+    if (l_text < 0) return BAM_UNPROVEN;
+    if (n - off < (uint64_t)l_text) return BAM_UNPROVEN | BAM_SHORT;
     off += (uint64_t)l_text;
-    if (n - off < 4) return BAM_UNPROVEN;
+    if (n - off < 4) return BAM_UNPROVEN | BAM_SHORT;
     const int32_t n_ref = (int32_t)bam_u32(t, off);
     off += 4;
     for (int32_t r = 0; r < n_ref; ++r) {
-        if (n - off < 4) return BAM_UNPROVEN;
+        if (n - off < 4) return BAM_UNPROVEN | BAM_SHORT;
         const int32_t l_name = (int32_t)bam_u32(t, off);
         off += 4;
-        if (l_name < 0 || n - off < (uint64_t)l_name + 4) return BAM_UNPROVEN;
+        if (l_name < 0) return BAM_UNPROVEN;
+        if (n - off < (uint64_t)l_name + 4) return BAM_UNPROVEN | BAM_SHORT;
         off += (uint64_t)l_name + 4;
     }
     *hdr_end = off;
@@ -73,7 +93,8 @@ FX_HD uint32_t bam_header(const uint8_t *t, uint64_t n, uint64_t *hdr_end) {
 
 // A candidate for a speculative start: a record by bam_record that carries what every writer of unaligned BAM puts into the
 // four position fields (refID, pos, next_refID, next_pos = -1), followed by another such record or by the end of the text.
-// Correctness never rests on this: a candidate counts only once the chain from the header has reached it.
+// Correctness never rests on this: a candidate counts only once the chain from the header has reached it.  In a window n is
+// the block's end, taken as the end of the text: a candidate whose own record or whose successor the block cuts off is rejected.
 FX_HD bool bam_candidate_one(const uint8_t *t, uint64_t n, uint64_t off, uint64_t *next) {
     FxRec r;
     if (bam_record(t, n, off, &r, next)) return false;
@@ -88,15 +109,19 @@ FX_HD bool bam_plausible(const uint8_t *t, uint64_t n, uint64_t off) {
 FX_HD uint64_t bam_seg_begin(uint64_t hdr_end, uint64_t S, uint64_t s) { return hdr_end + s * S; }
 FX_HD uint64_t bam_seg_end(uint64_t hdr_end, uint64_t S, uint64_t n, uint64_t s) { return n - hdr_end - s * S <= S ? n : hdr_end + (s + 1) * S; }
 
-// the walk of one segment from `start` (>= the segment's begin): follows the chain until it reaches the segment's end
-FX_HD BamSeg bam_walk(const uint8_t *t, uint64_t n, uint64_t start, uint64_t end) {
+// the walk of one segment from `start` (>= the segment's begin): follows the chain until it reaches the segment's end.
+// tail: an incomplete record start ends the walk with a tail landing instead of none
+FX_HD BamSeg bam_walk(const uint8_t *t, uint64_t n, uint64_t start, uint64_t end, bool tail = false) {
     BamSeg g = {start, 0, BAM_NONE};
     if (start == BAM_NONE) return g;
     uint64_t off = start;
     while (off < end) {
         FxRec r;
         uint64_t next;
-        if (bam_record(t, n, off, &r, &next)) return g;
+        if (bam_record(t, n, off, &r, &next)) {
+            if (tail && bam_incomplete(t, n, off)) g.landing = BAM_TAIL | off;
+            return g;
+        }
         ++g.count;
         off = next;
     }

@@ -1,6 +1,9 @@
 // fx_window.h -- FASTA / FASTQ text that passes through one block in windows while only the bases stay:
 // the cut rule and the driver of the windows, shared by the device (host_fastx.inl; hipcc) and the host twin (fastx_twin.cpp;
 // g++).  The backend supplies the block and the record scan; the rules of the scan itself are those of fastx_core.h.
+// The same driver carries unaligned BAM and SAM (bam_twin.cpp, sam_twin.cpp): only the cut differs -- the
+// first incomplete record start of the proven chain (bam_round.h), the offset behind the last line feed (host_sam.inl) -- and
+// the prefix is a complete run of records or lines in the same sense.
 //
 // Text is appended to the block piece by piece.  Once the block holds `window` bytes the driver asks for a cut: an offset
 // directly behind a line feed such that the prefix [0, cut), taken as a complete text, is proven by the record scan.  The
@@ -42,8 +45,10 @@ static inline void fx_win_census(FxCensus &c, bool first) {
 // Backend B:
 //   uint64_t len()                                          bytes in the block
 //   int resident_format(bool *yes)                          *yes: the first four bytes are a format that is not windowed (BAM,
-//                                                           SAM with their flags): the block stays resident from here on
-//                                                           (resident_again() tells the backend).  0 or the backend's code
+//                                                           SAM with their flags but without the flag that windows them): the
+//                                                           block stays resident from here on (resident_again() tells the
+//                                                           backend).  Called once, before the first flush: a backend that
+//                                                           scans several formats fixes the run's here.  0 or the backend's code
 //   void resident_again()                                   the windows are off: the block grows as a resident text does
 //   int flush(bool first, bool end, uint64_t *cut, int *fmt)  the record scan of the block.  end: all of it as a complete text
 //                                                           (*cut = len).  Otherwise up to the cut of the rules above (*cut = 0:

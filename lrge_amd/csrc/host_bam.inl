@@ -31,12 +31,13 @@ struct BamDev {
         *he = hdr.hdr_end; *verdict = hdr.verdict;
         return LRGE_OK;
     }
-    int round0(u64 he, u64 seg_bytes, u64 n_seg, u64 *cand, BamSeg *seg) {
-        hdr_end = he; S = seg_bytes;
+    u32 tail = 0;                                                       // (round0 sets it: a window's walks, bam_core.h)
+    int round0(u64 he, u64 seg_bytes, u64 n_seg, bool tail_mode, u64 *cand, BamSeg *seg) {
+        hdr_end = he; S = seg_bytes; tail = tail_mode;
         if (!(d_cand = sc.get<u64>(n_seg)) || !(d_seg = sc.get<BamSeg>(n_seg)) || !(d_list = sc.get<u32>(n_seg)) || !(d_from = sc.get<u64>(n_seg + 1))) return LRGE_ERR_DEVICE;
         hipLaunchKernelGGL(k_bam_find, dim3((u32)n_seg), dim3(64), 0, st, t, n, hdr_end, S, d_cand);
         KCHK(ctx);
-        hipLaunchKernelGGL(k_bam_walk, bam_walker_grid(ctx, n_seg), dim3(64), 0, st, t, n, hdr_end, S, (const u32 *)nullptr, (const u64 *)nullptr, (const u64 *)d_cand, n_seg, d_seg);
+        hipLaunchKernelGGL(k_bam_walk, bam_walker_grid(ctx, n_seg), dim3(64), 0, st, t, n, hdr_end, S, (const u32 *)nullptr, (const u64 *)nullptr, (const u64 *)d_cand, n_seg, tail, d_seg);
         KCHK(ctx);
         HIPCHK(ctx, hipMemcpyAsync(cand, d_cand, (size_t)n_seg * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(ctx, hipMemcpyAsync(seg, d_seg, (size_t)n_seg * sizeof(BamSeg), hipMemcpyDeviceToHost, st));
@@ -46,13 +47,13 @@ struct BamDev {
     int rewalk(const u32 *list, const u64 *from, u64 k, BamSeg *got) {
         HIPCHK(ctx, hipMemcpyAsync(d_list, list, (size_t)k * 4, hipMemcpyHostToDevice, st));
         HIPCHK(ctx, hipMemcpyAsync(d_from, from, (size_t)k * 8, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_bam_walk, bam_walker_grid(ctx, k), dim3(64), 0, st, t, n, hdr_end, S, (const u32 *)d_list, (const u64 *)d_from, (const u64 *)nullptr, k, d_seg);
+        hipLaunchKernelGGL(k_bam_walk, bam_walker_grid(ctx, k), dim3(64), 0, st, t, n, hdr_end, S, (const u32 *)d_list, (const u64 *)d_from, (const u64 *)nullptr, k, tail, d_seg);
         KCHK(ctx);
         HIPCHK(ctx, hipMemcpyAsync(got, d_seg, (size_t)k * sizeof(BamSeg), hipMemcpyDeviceToHost, st));
         HIPCHK(ctx, hipStreamSynchronize(st));
         return LRGE_OK;
     }
-    int records(const u64 *start, const u64 *base, u64 n_seg, u64 n_rec, u32 *flags, u64 *name_bytes) {
+    int records(const u64 *start, const u64 *base, u64 n_seg, u64 n_rec, u64 cut, u32 *flags, u64 *name_bytes) {
         hipError_t e = hipSuccess;
         if (!(R->d_recs = (FxRec *)ctx->pool.alloc((size_t)std::max<u64>(1, n_rec) * sizeof(FxRec), &e))) {
             LRGE_SET_ERR(ctx, "reads_open: record table: %s", hipGetErrorString(e));
@@ -63,7 +64,7 @@ struct BamDev {
         HIPCHK(ctx, hipMemsetAsync(d_flags, 0, 16, st));
         HIPCHK(ctx, hipMemcpyAsync(d_cand, start, (size_t)n_seg * 8, hipMemcpyHostToDevice, st));
         HIPCHK(ctx, hipMemcpyAsync(d_from, base, ((size_t)n_seg + 1) * 8, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_bam_records, bam_walker_grid(ctx, n_seg), dim3(64), 0, st, t, n, hdr_end, S, (const u64 *)d_cand, (const u64 *)d_from, n_seg, R->d_recs, d_seq_len,
+        hipLaunchKernelGGL(k_bam_records, bam_walker_grid(ctx, n_seg), dim3(64), 0, st, t, n, hdr_end, S, (const u64 *)d_cand, (const u64 *)d_from, n_seg, cut, R->d_recs, d_seq_len,
                            d_name_len, (u32 *)d_flags, (unsigned long long *)(d_flags + 1));
         KCHK(ctx);
         u64 f[2] = {0, 0};
@@ -75,20 +76,24 @@ struct BamDev {
 };
 }  // namespace
 
-static int bam_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R) {
+// w: the text is a window (fx_window.h) -- only the first has a header, one that is not the last is scanned
+// up to its cut (w->cut; 0: there is none yet), and the packed bases of its records go to the store
+static int bam_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R, FxWinScan *w) {
     Scratch sc(ctx);
     R->name_off.assign(1, 0);
     BamDev dev{ctx, R, sc, R->d_text, R->n_text, ctx->stream};
     const u64 S = std::max<u64>(64, ctx->opt_u64("BAM_SEGMENT_BYTES", (u64)256 << 10));
     u64 n_rec = 0, name_bytes = 0;
     const char *refused = nullptr;
-    const int v = bam_run(dev, R->n_text, S, &R->bam, &n_rec, &name_bytes, &refused);
+    const int v = bam_run(dev, R->n_text, S, &R->bam, &n_rec, &name_bytes, &refused, !w || w->first, w && !w->end ? &w->cut : nullptr);
     if (v == BAM_RUN_DEVICE) return LRGE_ERR_DEVICE;                   // (the step that failed has left its message)
     if (v) return fx_verdict_rc(ctx, (u32)v, refused);
     R->fmt = FX_FMT_BAM;                                                // (a refused file leaves no read set, so no format either)
-    if (!n_rec) return LRGE_OK;                                         // the header ends the text
+    if (!n_rec) return LRGE_OK;                                         // the header ends the text, or the window has no whole record yet
     if (name_bytes >> 32) return fx_verdict_rc(ctx, FX_UNPROVEN, "4 GiB of identifiers or more");
-    return fx_tables_to_host(ctx, R, sc, n_rec, dev.d_seq_len, dev.d_name_len, name_bytes);
+    const int rc = fx_tables_to_host(ctx, R, sc, n_rec, dev.d_seq_len, dev.d_name_len, name_bytes);
+    if (rc || !w) return rc;
+    return w->dev->store_window(sc, *R, dev.d_seq_len, R->n_text);
 }
 
 extern "C" int lrge_hip_reads_bam_stats(const lrge_hip_reads *r, lrge_hip_bam_stats *out) {

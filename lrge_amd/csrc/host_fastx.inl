@@ -5,7 +5,8 @@
 // into dense ASCII for the device-source pack of host_seqset.inl.  Whatever the scan cannot prove is LRGE_ERR_UNPROVEN: the
 // caller takes lrge_hip_read_records*, which parses the file or reports it with the reference's messages.  With
 // LRGE_GPU_INGEST_WINDOWED FASTA / FASTQ text larger than option INGEST_WINDOW_BYTES passes through HBM in windows and only the
-// bases stay (fx_window.h).  Included into lrge_hip.hip.
+// bases stay (fx_window.h); with LRGE_GPU_INGEST_WINDOWED_ALN beside it so does unaligned BAM and SAM, BAM's
+// bases staying packed.  Included into lrge_hip.hip.
 
 #include "fx_window.h"
 
@@ -18,8 +19,8 @@ struct lrge_hip_reads {
     std::vector<u64> name_off;                  // [n + 1]
     std::string names;
     float ms[4] = {0, 0, 0, 0};                 // text to HBM, record scan, identifiers and lengths to the host, the whole call
-    BamStats bam = {0, 0, 0, 0, 0, 0};          // fmt == FX_FMT_BAM: the counts of the record scan (lrge_hip_reads_bam_stats)
-    u64 text_bytes = 0;                         // the decompressed text that was scanned (windowed: d_text holds its bases only)
+    BamStats bam = {0, 0, 0, 0, 0, 0};          // fmt == FX_FMT_BAM: the counts of the record scan, summed over the windows (lrge_hip_reads_bam_stats)
+    u64 text_bytes = 0;                         // the decompressed text that was scanned (windowed: d_text holds its bases only, BAM's packed)
     FxWinStats win = {0, 0, 0, 0};              // lrge_hip_reads_window_stats
 };
 
@@ -76,11 +77,17 @@ static void fx_sniff_bam_sam(int flags, const u8 head[4], u64 n, bool *is_bam, b
     *is_sam = (flags & LRGE_GPU_INGEST_SAM) && n >= 3 && sam_sniff(head, n);
 }
 
+// BAM and SAM that stay resident: all of them, unless the caller asked for their windows as well
+static bool fx_stays_resident(int flags, bool is_bam, bool is_sam) { return (is_bam || is_sam) && !(flags & LRGE_GPU_INGEST_WINDOWED_ALN); }
+
 // ---- windowed ingest: the device backend of fx_window.h ----
 struct FxWinDev;
-// the scan of one window (fx_parse_device): up to its cut (left in `cut`; 0: there is none yet) unless `end`
+// the scan of one window (fx_parse_device, bam_parse_device, sam_parse_device): up to its cut (left in `cut`; 0: there is none
+// yet) unless `end`
 struct FxWinScan { FxWinDev *dev; bool first, end; u64 cut; };
 static int fx_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R, FxWinScan *w = nullptr);
+static int bam_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R, FxWinScan *w = nullptr);
+static int sam_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R, FxWinScan *w = nullptr);
 
 struct FxWinDev {
     lrge_hip_ctx *ctx;
@@ -88,7 +95,8 @@ struct FxWinDev {
     int flags;
     u64 cap;                                    // INGEST_MAX_BYTES: the block and the store together
     DevKeep *blk = nullptr;                     // the block the text is appended to (a decoder's own, or one of the call)
-    DevKeep store;                              // the bases of the records flushed so far, dense, in file order
+    DevKeep store;                              // the bases of the records flushed so far, dense, in file order (BAM: packed, a record starts on a byte)
+    int kind = FX_FMT_EMPTY;                    // FX_FMT_BAM / FX_FMT_SAM: the run is that format's, by the sniff of its first bytes; else FASTA / FASTQ
     u64 through = 0;                            // text bytes cut off the block so far
     double ms_scan = 0, ms_names = 0;
     int rc = LRGE_OK;                           // what stopped the windows, with its message (a decoder's hook can only say "stop")
@@ -99,8 +107,9 @@ struct FxWinDev {
     }
     u64 len() const { return blk->keep_len; }
     int unproven(const char *what) { LRGE_SET_ERR(ctx, "reads_open: not proven on the device (%s)", what); return LRGE_ERR_UNPROVEN; }
-    // BAM and SAM with their flags are not windowed: their scans need the whole text.  (Plain and BGZF input is sniffed before a
-    // window is set up, lrge_hip_reads_open_mem; this is the sniff of the round decoders, whose first bytes arrive with a round.)
+    // BAM and SAM with their flags are not windowed unless LRGE_GPU_INGEST_WINDOWED_ALN says so; with it this sniff, the first
+    // window's, makes the run a BAM or SAM run: a later window is never sniffed.  (Plain and BGZF input is sniffed before a
+    // window is set up as well, lrge_hip_reads_open_mem; the round decoders' first bytes arrive with a round.)
     int resident_format(bool *yes) {
         *yes = false;
         if (!(flags & (LRGE_GPU_INGEST_BAM | LRGE_GPU_INGEST_SAM))) return LRGE_OK;
@@ -109,7 +118,8 @@ struct FxWinDev {
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         bool is_bam, is_sam;
         fx_sniff_bam_sam(flags, head, blk->keep_len, &is_bam, &is_sam);
-        *yes = is_bam || is_sam;
+        *yes = fx_stays_resident(flags, is_bam, is_sam);
+        if (!*yes) kind = is_bam ? FX_FMT_BAM : is_sam ? FX_FMT_SAM : FX_FMT_EMPTY;
         return LRGE_OK;
     }
     // the growth rule a resident text has without the flag (attach() had made the block a window's)
@@ -120,11 +130,12 @@ struct FxWinDev {
         W.ctx = ctx; W.d_text = blk->keep; W.n_text = blk->keep_len;
         FxWinScan w = {this, first, end, 0};
         const double t0 = fx_now_ms();
-        const int prc = fx_parse_device(ctx, &W, &w);
+        const int prc = kind == FX_FMT_BAM ? bam_parse_device(ctx, &W, &w) : kind == FX_FMT_SAM ? sam_parse_device(ctx, &W, &w) : fx_parse_device(ctx, &W, &w);
         ctx->pool.release(W.d_recs);
         ms_names += W.ms[2]; ms_scan += fx_now_ms() - t0 - W.ms[2];
         if (prc) return prc;
         *cut = end ? W.n_text : w.cut; *fmt = W.fmt;
+        if (*cut) { u64 *sum = &R->bam.segments; const u64 *add = &W.bam.segments; for (int i = 0; i < 6; ++i) sum[i] += add[i]; }
         if (!*cut || !W.n) return LRGE_OK;
         if ((R->n + W.n) >> 32) return fx_verdict_rc(ctx, FX_UNPROVEN, "2^32 records or more");
         if ((R->names.size() + W.names.size()) >> 32) return fx_verdict_rc(ctx, FX_UNPROVEN, "4 GiB of identifiers or more");
@@ -135,10 +146,13 @@ struct FxWinDev {
         R->n += W.n;
         return LRGE_OK;
     }
-    // the bases of the window's records (table W.d_recs, lengths d_seq_len) behind those of the earlier windows
+    // the bases of the window's records (table W.d_recs, lengths d_seq_len) behind those of the earlier windows; BAM: the packed
+    // bytes, (seq_len + 1) / 2 a record
     int store_window(Scratch &sc, const lrge_hip_reads &W, const u32 *d_seq_len, u64 n_use) {
+        const bool packed = W.fmt == FX_FMT_BAM;
         u64 sum = 0;
-        for (u32 l : W.seq_len) sum += l;
+        for (u32 l : W.seq_len) sum += packed ? ((u64)l + 1) / 2 : l;
+        if (sum >> 32) return fx_verdict_rc(ctx, FX_UNPROVEN, "a window of 2^32 bytes or more");      // (never: the window is below that)
         // the store doubles while that leaves the block room to double as well; close to the cap it grows by an eighth
         const u64 need = store.keep_len + sum, room = cap > blk->keep_cap ? cap - blk->keep_cap : 0, soft = cap > 2 * blk->keep_cap ? cap - 2 * blk->keep_cap : 0;
         store.keep_max = need <= soft ? soft : std::min<u64>(room, need + need / 8);
@@ -150,10 +164,19 @@ struct FxWinDev {
         blk->keep_max = cap > store.keep_cap ? cap - store.keep_cap : 0;
         if (W.n) {
             ALLOC_OR_FAIL(d_dst, sc, u32, W.n);
+            const dim3 grid((u32)std::min<u64>(W.n, (u64)ctx->n_cu * 32));
+            if (packed) {
+                hipLaunchKernelGGL(k_bam_spans, dim3((u32)div_up(W.n, 256)), dim3(256), 0, ctx->stream, d_seq_len, W.n, d_dst);
+                KCHK(ctx);
+                d_seq_len = d_dst;                               // (the scan runs in place, as the record scans' do)
+            }
             const int src = scan_exclusive_u32(ctx, sc, d_seq_len, d_dst, W.n, nullptr);
             if (src) return src;
-            hipLaunchKernelGGL(k_fx_store, dim3((u32)std::min<u64>(W.n, (u64)ctx->n_cu * 32)), dim3(64), 0, ctx->stream, (const u8 *)W.d_text, n_use, (const FxRec *)W.d_recs,
-                               (const u32 *)d_dst, W.n, store.keep + store.keep_len);
+            if (packed)
+                hipLaunchKernelGGL(k_bam_store, grid, dim3(64), 0, ctx->stream, (const u8 *)W.d_text, (const FxRec *)W.d_recs, (const u32 *)d_dst, W.n, store.keep + store.keep_len);
+            else
+                hipLaunchKernelGGL(k_fx_store, grid, dim3(64), 0, ctx->stream, (const u8 *)W.d_text, n_use, (const FxRec *)W.d_recs, (const u32 *)d_dst, W.n,
+                                   store.keep + store.keep_len);
             KCHK(ctx);
         }
         store.keep_len += sum;
@@ -213,8 +236,13 @@ struct FxWinRun {
         if (rc) return rc;
         if (!dev.store.keep && !dev.store.keep_reserve(0)) { LRGE_SET_ERR(ctx, "reads_open: device allocation failed"); return LRGE_ERR_DEVICE; }
         std::vector<FxRec> tab((size_t)R->n);
+        const bool packed = win.fmt == FX_FMT_BAM;              // (the gather of BAM reads its records' spans as it reads the text)
         u64 o = 0;
-        for (u64 i = 0; i < R->n; ++i) { tab[i] = FxRec{0, o, R->seq_len[i], (u32)(R->name_off[i + 1] - R->name_off[i]), R->seq_len[i]}; o += R->seq_len[i]; }
+        for (u64 i = 0; i < R->n; ++i) {
+            const u64 span = packed ? ((u64)R->seq_len[i] + 1) / 2 : R->seq_len[i];
+            tab[i] = FxRec{0, o, span, (u32)(R->name_off[i + 1] - R->name_off[i]), R->seq_len[i]};
+            o += span;
+        }
         hipError_t e = hipSuccess;
         if (!(R->d_recs = (FxRec *)ctx->pool.alloc(std::max<size_t>(1, tab.size()) * sizeof(FxRec), &e))) { LRGE_SET_ERR(ctx, "reads_open: record table: %s", hipGetErrorString(e)); return LRGE_ERR_DEVICE; }
         if (!tab.empty()) HIPCHK(ctx, hipMemcpyAsync(R->d_recs, tab.data(), tab.size() * sizeof(FxRec), hipMemcpyHostToDevice, ctx->stream));
@@ -406,8 +434,9 @@ extern "C" int lrge_hip_reads_open_mem(lrge_hip_ctx *ctx, const void *file_bytes
         if (bgzf_scan_blocks(d, len, &t, &total)) {
             if (!(flags & LRGE_GPU_INFLATE_BGZF)) { ctx->err = "reads_open: BGZF input without LRGE_GPU_INFLATE_BGZF"; return LRGE_ERR_UNPROVEN; }
             BgzfBad bad;                        // the chunk pipeline of host_inflate.inl, decoding into the block
-            // BAM and SAM with their flags are not windowed: the first blocks that hold four bytes of text are decoded for the sniff,
-            // and such a file takes the resident branch below exactly as without the windowed flag
+            // BAM and SAM with their flags are not windowed without LRGE_GPU_INGEST_WINDOWED_ALN: the first blocks that hold four
+            // bytes of text are decoded for the sniff, and such a file takes the resident branch below exactly as without the
+            // windowed flag
             bool windowed = run && total > window;
             if (windowed && (flags & (LRGE_GPU_INGEST_BAM | LRGE_GPU_INGEST_SAM))) {
                 std::vector<BgzfBlock> first;
@@ -423,7 +452,7 @@ extern "C" int lrge_hip_reads_open_mem(lrge_hip_ctx *ctx, const void *file_bytes
                 HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
                 bool is_bam, is_sam;
                 fx_sniff_bam_sam(flags, head, total, &is_bam, &is_sam);
-                windowed = !is_bam && !is_sam;
+                windowed = !fx_stays_resident(flags, is_bam, is_sam);
             }
             if (windowed) {
                 // runs of blocks of a window's size, each decoded behind the tail the window before it left
@@ -464,8 +493,8 @@ extern "C" int lrge_hip_reads_open_mem(lrge_hip_ctx *ctx, const void *file_bytes
                (b(0) == 0xfd && b(1) == 0x37 && b(2) == 0x7a && b(3) == 0x58 && b(4) == 0x5a)) {
         ctx->err = "reads_open: bzip2, zstd and xz input is decompressed on the host";
         return LRGE_ERR_UNPROVEN;
-    } else if (run && len > window && [&] { bool is_bam, is_sam; fx_sniff_bam_sam(flags, d, len, &is_bam, &is_sam); return !is_bam && !is_sam; }()) {
-        run->attach(&blk);                      // copies of a window's size (BAM and SAM with their flags: the resident branch below)
+    } else if (run && len > window && [&] { bool is_bam, is_sam; fx_sniff_bam_sam(flags, d, len, &is_bam, &is_sam); return !fx_stays_resident(flags, is_bam, is_sam); }()) {
+        run->attach(&blk);                      // copies of a window's size (BAM and SAM that stay resident: the branch below)
         for (u64 off = 0; off < len; off += window) {
             const u64 m = std::min<u64>(window, len - off);
             const int rc = blk_room(m);
@@ -490,7 +519,7 @@ extern "C" int lrge_hip_reads_open_mem(lrge_hip_ctx *ctx, const void *file_bytes
         const int rc = run->finish(rest, n_rest);
         if (rc) return rc;
         R->ms[3] = (float)(fx_now_ms() - t0); R->ms[0] = R->ms[3] - R->ms[1] - R->ms[2];
-        if (ctx->opt("VERBOSE")) fprintf(stderr, "[lrge_hip] reads_open: %llu text bytes in %llu windows, %llu records, %llu bases kept; record scan %.2f ms, identifiers and lengths %.2f ms\n",
+        if (ctx->opt("VERBOSE")) fprintf(stderr, "[lrge_hip] reads_open: %llu text bytes in %llu windows, %llu records, %llu store bytes; record scan %.2f ms, identifiers and lengths %.2f ms\n",
                                         (unsigned long long)R->text_bytes, (unsigned long long)R->win.windows, (unsigned long long)R->n, (unsigned long long)R->n_text, R->ms[1], R->ms[2]);
         *out = guard.release();
         return LRGE_OK;

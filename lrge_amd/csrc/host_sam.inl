@@ -2,9 +2,12 @@
 // scatter passes of the FASTQ scan, a mark and a rank per line, then a wavefront per record line.  Included into host_fastx.inl,
 // whose tail (fx_tables_to_host) brings the identifiers and the lengths down.
 
-// the caller has seen the SAM magic at the start of R->d_text
-static int sam_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R) {
-    const u64 n = R->n_text;
+// the caller has seen the SAM magic at the start of R->d_text, or of the first window.
+// w: the text is a window (fx_window.h).  One that is not the last is cut directly behind its last line feed
+// (w->cut; 0: it has none yet) and the prefix is scanned as a complete text of that size with the window's own line table: all
+// its line feeds lie in the prefix, whose last line is the empty one behind the cut.  The bases go to the store.
+static int sam_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R, FxWinScan *w) {
+    u64 n = R->n_text;
     const u8 *t = R->d_text;
     R->name_off.assign(1, 0);
     hipStream_t st = ctx->stream;
@@ -38,6 +41,12 @@ static int sam_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R) {
     hipLaunchKernelGGL(k_fx_scatter, dim3((u32)n_tiles), dim3(FX_THREADS), 0, st, t, n, (int)FX_FMT_FASTQ, (const u32 *)c_lf, (const u32 *)c_rem, (const u32 *)c_hdr, c.first,
                        c.last, ls, d_lines, (u64 *)nullptr, (u32 *)nullptr);
     KCHK(ctx);
+    if (w && !w->end) {
+        if (!c.n_lf) { R->fmt = FX_FMT_SAM; return LRGE_OK; }
+        HIPCHK(ctx, ctx->d2h(&n, ls + c.n_lf, 8, st));
+        HIPCHK(ctx, ctx->d2h_sync(st));
+        w->cut = n;
+    }
     // which lines carry a record, and the rank of each
     ALLOC_OR_FAIL(d_mark, sc, u32, n_lines);
     ALLOC_OR_FAIL(d_rank, sc, u32, n_lines);
@@ -64,5 +73,6 @@ static int sam_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R) {
     if ((u32)flags[0]) return fx_verdict_rc(ctx, (u32)flags[0], "a SAM record line outside the strict form");
     if (flags[1] >> 32) return fx_verdict_rc(ctx, FX_UNPROVEN, "4 GiB of identifiers or more");
     R->fmt = FX_FMT_SAM;                                    // (a refused file leaves no read set, so no format either)
-    return fx_tables_to_host(ctx, R, sc, n_rec, d_seq_len, d_name_len, flags[1]);
+    if ((rc = fx_tables_to_host(ctx, R, sc, n_rec, d_seq_len, d_name_len, flags[1])) || !w) return rc;
+    return w->dev->store_window(sc, *R, d_seq_len, n);
 }

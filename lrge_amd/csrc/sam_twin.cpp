@@ -1,7 +1,9 @@
 // sam_twin.cpp -- the host twin of the device SAM record scan (k_sam.h, host_sam.inl; g++): the same passes over the same core
 // (sam_core.h, fastx_core.h) as loops on the CPU -- line starts from 16-byte groups, a mark and a rank per line, then every
 // record line in steps of SAM_STEP bytes, 64 "lanes" of one 16-byte group each, the tabs ranked by an inclusive scan of the
-// lanes' popcounts -- so the CPU suite checks the stepping against the host parser (tests/test_sam_twin.py).
+// lanes' popcounts -- so the CPU suite checks the stepping against the host parser (tests/test_sam_twin.py); and the windowed
+// ingest of fx_window.h over the same passes, with the window and the appended piece as parameters
+// (tests/test_sam_window_twin.py).
 // TEST INFRASTRUCTURE, not part of the product library.
 #include <stdint.h>
 #include <string.h>
@@ -9,6 +11,7 @@
 #include <vector>
 
 #include "sam_core.h"
+#include "fx_window.h"
 
 namespace {
 std::vector<FxRec> g_recs;
@@ -49,14 +52,13 @@ uint32_t record_line(const uint8_t *t, uint64_t n, uint64_t a, uint64_t e, FxRec
     }
     return seen < 10 ? FX_UNPROVEN : sam_record(t, a, tab[0], tab[1], tab[2], tab[3], rec);
 }
-}  // namespace
 
-extern "C" {
-
-// 0: proven (sam_twin_count records), FX_UNPROVEN (text without the SAM magic included), FX_TOO_MANY
-int sam_twin_parse(const uint8_t *t, uint64_t n) {
+// the passes over t[0, n), which the caller has found to be SAM, into g_recs.  cut != nullptr: the text is a window that is not
+// the last -- the prefix directly behind its last line feed (*cut; 0: it has none yet) is scanned as a complete text of that
+// size, with the window's own line table
+int parse(const uint8_t *t, uint64_t n, uint64_t *cut) {
     g_recs.clear();
-    if (!sam_sniff(t, n)) return FX_UNPROVEN;
+    if (cut) *cut = 0;
     // the line starts, group by group as k_fx_census / k_fx_scatter find them
     std::vector<uint64_t> ls(1, 0);
     for (uint64_t p = 0; p < n; p += 16) {
@@ -73,6 +75,10 @@ int sam_twin_parse(const uint8_t *t, uint64_t n) {
     if (!verdict && (c.n_lf + 1) >> 32) verdict = FX_UNPROVEN;
     if (verdict) return (int)verdict;
     const uint64_t n_lines = c.n_lf + 1;
+    if (cut) {
+        if (!c.n_lf) return 0;
+        *cut = n = ls[c.n_lf];
+    }
     // marks, and their exclusive scan
     std::vector<uint32_t> mark(n_lines), rank(n_lines);
     uint32_t n_rec = 0;
@@ -96,8 +102,85 @@ int sam_twin_parse(const uint8_t *t, uint64_t n) {
         flags |= v; name_bytes += rec.name_len;
     }
     if (!flags && name_bytes >> 32) flags = FX_UNPROVEN;
-    if (flags) { g_recs.clear(); return flags & FX_UNPROVEN ? (int)FX_UNPROVEN : (int)FX_TOO_MANY; }
+    if (flags) { g_recs.clear(); if (cut) *cut = 0; return flags & FX_UNPROVEN ? (int)FX_UNPROVEN : (int)FX_TOO_MANY; }
     return 0;
+}
+
+// ---- the windowed ingest: fx_window.h over the passes above ----
+struct WinOut {
+    std::vector<FxRec> recs;            // name_off: in the whole text; seq_off: in `store`; seq_span = seq_len
+    std::vector<uint8_t> store;
+    FxWinStats st = {0, 0, 0, 0};
+};
+WinOut gw;
+
+struct WinTwin {
+    std::vector<uint8_t> blk;
+    uint64_t base = 0;                  // where the block starts in the whole text
+    uint64_t len() const { return blk.size(); }
+    int resident_format(bool *yes) const { *yes = false; return 0; }
+    void resident_again() const {}
+    int unproven(const char *) const { return (int)FX_UNPROVEN; }
+    int flush(bool first, bool end, uint64_t *cut, int *fmt) {
+        if (first && !sam_sniff(blk.data(), blk.size())) return (int)FX_UNPROVEN;     // (later windows are SAM by the run, not by their first bytes)
+        uint64_t c = 0;
+        const int rc = parse(blk.data(), blk.size(), end ? nullptr : &c);
+        if (rc) return rc;
+        *cut = end ? blk.size() : c;
+        *fmt = FX_FMT_SAM;
+        if (!*cut) return 0;
+        for (const FxRec &r : g_recs) {
+            gw.recs.push_back(FxRec{base + r.name_off, gw.store.size(), r.seq_len, r.name_len, r.seq_len});
+            gw.store.insert(gw.store.end(), blk.data() + r.seq_off, blk.data() + r.seq_off + r.seq_len);
+        }
+        return 0;
+    }
+    int carry(uint64_t cut) {
+        blk.erase(blk.begin(), blk.begin() + (long)cut);
+        base += cut;
+        return 0;
+    }
+};
+}  // namespace
+
+extern "C" {
+
+// 0: proven (sam_twin_count records), FX_UNPROVEN (text without the SAM magic included), FX_TOO_MANY
+int sam_twin_parse(const uint8_t *t, uint64_t n) {
+    g_recs.clear();
+    if (!sam_sniff(t, n)) return FX_UNPROVEN;
+    return parse(t, n, nullptr);
+}
+
+// The text through the windows of fx_window.h: `piece` bytes appended per step, a flush once the block holds `window` bytes (the
+// driver waits for the four bytes of the sniff).  0: proven, FX_UNPROVEN, FX_TOO_MANY; the records by sam_twin_windowed_count /
+// _table / _seq, the counts by _stats (windows flushed first: 0 means the text ended before its first flush and was scanned
+// whole, as without windows, and no store was kept)
+int sam_twin_windowed(const uint8_t *t, uint64_t n, uint64_t window, uint64_t piece) {
+    gw = WinOut();
+    if (!piece) return -1;
+    WinTwin b;
+    FxWindow<WinTwin> win(b, window);
+    int rc = 0;
+    for (uint64_t p = 0; p < n && !rc; p += piece) {
+        b.blk.insert(b.blk.end(), t + p, t + (n - p < piece ? n : p + piece));
+        rc = win.step(false);
+    }
+    uint64_t all = 0;
+    if (!rc) rc = win.st.windows ? win.step(true) : b.flush(true, true, &all, &win.fmt);         // (or the resident scan)
+    if (rc) { gw = WinOut(); return rc; }
+    gw.st = win.st; gw.st.bases = win.st.windows ? gw.store.size() : 0;
+    return 0;
+}
+
+uint64_t sam_twin_windowed_count(void) { return gw.recs.size(); }
+void sam_twin_windowed_table(FxRec *out) { if (!gw.recs.empty()) memcpy(out, gw.recs.data(), gw.recs.size() * sizeof(FxRec)); }
+void sam_twin_windowed_stats(uint64_t out[4]) { out[0] = gw.st.windows; out[1] = gw.st.bases; out[2] = gw.st.max_window; out[3] = gw.st.carried; }
+uint64_t sam_twin_windowed_store(uint8_t *out) { if (out && !gw.store.empty()) memcpy(out, gw.store.data(), gw.store.size()); return gw.store.size(); }
+uint64_t sam_twin_windowed_seq(uint64_t i, uint8_t *out) {
+    const FxRec &r = gw.recs[i];
+    if (r.seq_len) memcpy(out, gw.store.data() + r.seq_off, r.seq_len);
+    return r.seq_len;
 }
 
 uint64_t sam_twin_count(void) { return g_recs.size(); }

@@ -111,7 +111,7 @@ class Context:
 
     def open_reads(self, path_or_bytes, flags=_ffi.GPU_INFLATE_BGZF | _ffi.GPU_INFLATE_GZIP):
         """A FASTA / FASTQ file (a path, or the bytes of the whole file) parsed on the device: plain, BGZF or any other gzip
-        (| _ffi.GPU_INFLATE_BZIP2: bzip2 as well), by `flags` (lrge_hip_reads_open*); | _ffi.GPU_INGEST_BAM takes unaligned BAM as well, | _ffi.GPU_INGEST_SAM unaligned SAM; | _ffi.GPU_INGEST_WINDOWED lets FASTA / FASTQ text above option INGEST_WINDOW_BYTES pass through in windows with only the bases kept (DeviceReads.window_stats).  Returns a DeviceReads with names, lens and seqset().  Input the device does not
+        (| _ffi.GPU_INFLATE_BZIP2: bzip2 as well), by `flags` (lrge_hip_reads_open*); | _ffi.GPU_INGEST_BAM takes unaligned BAM as well, | _ffi.GPU_INGEST_SAM unaligned SAM; | _ffi.GPU_INGEST_WINDOWED lets FASTA / FASTQ text above option INGEST_WINDOW_BYTES pass through in windows with only the bases kept (DeviceReads.window_stats), and | _ffi.GPU_INGEST_WINDOWED_ALN beside it and the format's own flag does the same for unaligned BAM (its bases kept packed, 4 bits each) and SAM.  Returns a DeviceReads with names, lens and seqset().  Input the device does not
         prove raises UnprovenInput: read the file with the host readers (readio.load) instead."""
         return DeviceReads(self, path_or_bytes, flags)
 
@@ -291,13 +291,15 @@ class DeviceReads:
 
     @property
     def bam_stats(self):
-        """the counts of the BAM record scan (lrge_hip_bam_stats) as a dict; raises when the input was not scanned as BAM"""
+        """the counts of the BAM record scan (lrge_hip_bam_stats) as a dict, summed over the windows of a windowed open; raises when the
+        input was not scanned as BAM"""
         a = (C.c_uint64 * len(_ffi.BAM_STAT_NAMES))()
         self.ctx._check(self.ctx._lib.lrge_hip_reads_bam_stats(self.h, C.byref(a)))
         return dict(zip(_ffi.BAM_STAT_NAMES, [int(x) for x in a]))
 
     def window_stats(self):
-        """(windows flushed -- 0: the text stayed resident --, bases kept, largest window in bytes, bytes carried over cuts)"""
+        """(windows flushed -- 0: the text stayed resident --, bytes in the store: the bases, for BAM their packed bytes --, largest window
+        in bytes, bytes carried over cuts)"""
         a = (C.c_uint64 * 4)()
         self.ctx._check(self.ctx._lib.lrge_hip_reads_window_stats(self.h, C.byref(a)))
         return tuple(int(x) for x in a)

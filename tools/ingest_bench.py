@@ -6,10 +6,11 @@ unaligned SAM text (the "sam" kind: its record scan beside the FASTQ kind's, and
 the files of the kinds asked for are written.  Usage:
   python tools/ingest_bench.py [--gbases 1.08] [--dir /tmp] [--reps 5] [--kinds fq,bgzf.fq.gz,fq.gz,bam,sam]
                                [--bam-segments 262144,1048576,4194304] [--out profiles/ingest_bench.json]
-                               [--windowed [--window-mb 64]]
---windowed: only the FASTQ kinds, and on each file the windowed device route (LRGE_GPU_INGEST_WINDOWED with option
-INGEST_WINDOW_BYTES = --window-mb) beside the resident device route, alternating in the same run; the result goes under the
-key "windowed" of --out, whose other entries are kept.
+                               [--windowed [--window-mb 64[,1024]]]
+--windowed: on each file the windowed device route (LRGE_GPU_INGEST_WINDOWED | LRGE_GPU_INGEST_WINDOWED_ALN with option
+INGEST_WINDOW_BYTES = --window-mb, one run per size of the list on the same files) beside the resident device route, alternating in the same run; the result of the FASTQ kinds
+goes under the key "windowed" of --out, that of the kinds bam and sam under "windowed_aln" / "<window-mb>"; the other entries are
+kept.  (To compare with another build of the library, run the same command there: the resident route is timed in every run.)
 
 Both routes are driven by a small C++ helper (compiled here with g++ against liblrge_hip.so), so that no Python callback sits
 in either clock.  Both start from the file's path with the file in the page cache and end when lrge_hip_seqset_wait has
@@ -176,9 +177,10 @@ def write_files(d, parts, kinds):
     return paths, size
 
 
-def windowed_runs(a, ctx, H, kinds, paths, text_bytes):
-    """the resident and the windowed device route on every file, alternating; into the key "windowed" of a.out"""
-    out = {"window_bytes": a.window_mb << 20, "reps": a.reps, "text_bytes": text_bytes, "files": {}}
+def windowed_runs(a, ctx, H, kinds, paths, text_bytes, aln):
+    """the resident and the windowed device route on every file, alternating; into the key "windowed" of a.out, or (aln: the kinds
+    bam and sam) into "windowed_aln" / "<window-mb>" of it"""
+    out = {"window_bytes": a.window_mb << 20, "reps": a.reps, "text_bytes": {k: text_bytes[k] for k in kinds}, "files": {}}
     ctx.set_option("INGEST_WINDOW_BYTES", str(a.window_mb << 20))
     for kind in kinds:
         p = paths[kind]
@@ -188,12 +190,13 @@ def windowed_runs(a, ctx, H, kinds, paths, text_bytes):
         runs = {"resident": [], "windowed": []}
         seen = {}
         for rep in range(a.reps + 1):
-            for route, flags in (("resident", 15), ("windowed", 15 | 32)):
+            for route, flags in (("resident", 15), ("windowed", 15 | 32 | 64)):
                 ms2, st, nr, nb, tb, bs, win = (C.c_double * 2)(), (C.c_float * 4)(), C.c_uint64(), C.c_uint64(), C.c_uint64(), (C.c_uint64 * 6)(), (C.c_uint64 * 4)()
                 rc = H.route_device(ctx.h, p.encode(), flags, C.byref(ms2), C.byref(st), C.byref(nr), C.byref(nb), C.byref(tb), C.byref(bs), C.byref(win))
                 assert rc == 0, (kind, route, rc, ctx._lib.lrge_hip_last_error(ctx.h))
                 assert tb.value == text_bytes[kind] and seen.setdefault("reads", (nr.value, nb.value)) == (nr.value, nb.value)
-                assert (win[0] >= 1 and win[1] == nb.value) if route == "windowed" else win[0] == 0, (kind, route, list(win))   # (a gzip round may deliver all of the text: one window)
+                store = (nb.value + 1) // 2 if kind == "bam" else nb.value                # (bam: packed, a pad nibble per odd read)
+                assert (win[0] >= 1 and store <= win[1] <= store + nr.value) if route == "windowed" else win[0] == 0, (kind, route, list(win))   # (a gzip round may deliver all of the text: one window)
                 seen[route] = list(win)
                 if rep:                                                # (run 0 is the warm-up)
                     runs[route].append(dict(open_ms=ms2[0], seqset_ms=ms2[1], total_ms=sum(ms2), text_ms=st[0], scan_ms=st[1], names_ms=st[2]))
@@ -202,14 +205,17 @@ def windowed_runs(a, ctx, H, kinds, paths, text_bytes):
         f = dict(file_bytes=os.path.getsize(p), reads=seen["reads"][0], text_bytes=text_bytes[kind], store_bytes=seen["windowed"][1], windows=seen["windowed"][0],
                  largest_window_bytes=seen["windowed"][2], carried_bytes=seen["windowed"][3], resident_route=runs["resident"], windowed_route=runs["windowed"])
         for r in ("resident", "windowed"):
-            for k in ("open_ms", "scan_ms", "seqset_ms", "total_ms"):
+            for k in ("open_ms", "text_ms", "scan_ms", "seqset_ms", "total_ms"):
                 f["%s_%s_median" % (r, k)] = med(r, k)
                 f["%s_%s_range" % (r, k)] = rng(r, k)
         out["files"][kind] = f
         print(kind, json.dumps({k: v for k, v in f.items() if not k.endswith("_route")}), flush=True)
     ctx.set_option("INGEST_WINDOW_BYTES", None)
     result = json.load(open(a.out)) if os.path.exists(a.out) else {}
-    result["windowed"] = out
+    if aln:
+        result.setdefault("windowed_aln", {})[str(a.window_mb)] = out
+    else:
+        result["windowed"] = out
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     json.dump(result, open(a.out, "w"), indent=1)
 
@@ -223,7 +229,7 @@ def main():
     ap.add_argument("--bam-segments", default="262144,1048576,4194304")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ingest_bench.json"))
     ap.add_argument("--windowed", action="store_true")
-    ap.add_argument("--window-mb", type=int, default=64)
+    ap.add_argument("--window-mb", default="64")
     a = ap.parse_args()
     from lrge_amd import build as B, engine
     work = tempfile.mkdtemp(dir=a.dir, prefix="ingest_bench_")
@@ -234,7 +240,7 @@ def main():
                            "-L" + B.LIB_DIR, "-llrge_hip", "-Wl,-rpath," + B.LIB_DIR])
     parts = max(1, round(a.gbases * 1e9 * 2.02 / (256 << 20)))       # a record is 2 bytes per base and a header
     t0 = time.perf_counter()
-    kinds = [k for k in KINDS if k in a.kinds.split(",") and (not a.windowed or k in ("fq", "bgzf.fq.gz", "fq.gz"))]
+    kinds = [k for k in KINDS if k in a.kinds.split(",")]
     paths, text_bytes = write_files(work, parts, kinds)
     print("files written in %.0f s: %s text bytes" % (time.perf_counter() - t0, text_bytes), flush=True)
     ctx = engine.Context(0)
@@ -243,7 +249,12 @@ def main():
     H.route_device.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_double * 2), C.POINTER(C.c_float * 4), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                C.POINTER(C.c_uint64), C.POINTER(C.c_uint64 * 6), C.POINTER(C.c_uint64 * 4)]
     if a.windowed:
-        windowed_runs(a, ctx, H, kinds, paths, text_bytes)
+        for mb in a.window_mb.split(","):
+            a.window_mb = int(mb)
+            for aln in (False, True):
+                part = [k for k in kinds if (k in ("bam", "sam")) == aln]
+                if part:
+                    windowed_runs(a, ctx, H, part, paths, text_bytes, aln)
         kinds = []
     result = {"text_bytes": text_bytes, "reps": a.reps, "files": {}}
     # (a BAM run per segment size: the host route it is compared with does not depend on the option, and is timed beside each)
@@ -280,8 +291,9 @@ def main():
     ctx.close()
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     if not a.windowed:
-        if os.path.exists(a.out) and "windowed" in json.load(open(a.out)):
-            result["windowed"] = json.load(open(a.out))["windowed"]
+        for key in ("windowed", "windowed_aln"):
+            if os.path.exists(a.out) and key in json.load(open(a.out)):
+                result[key] = json.load(open(a.out))[key]
         json.dump(result, open(a.out, "w"), indent=1)
     for p in list(paths.values()) + [src, so]:
         os.remove(p)

@@ -107,7 +107,7 @@ int main(int argc, char **argv) {
         // --gpu-ingest: input the device does not prove takes the usual route below, which parses it or reports it
         std::unique_ptr<lrge::DeviceReads> dev;
         if (gpu_ingest) {
-            dev = lrge::DeviceReads::open(input, LRGE_GPU_INFLATE_BGZF | LRGE_GPU_INFLATE_GZIP | LRGE_GPU_INGEST_BAM | LRGE_GPU_INGEST_SAM | LRGE_GPU_INGEST_WINDOWED | (gpu_bzip2 ? LRGE_GPU_INFLATE_BZIP2 : 0), device);
+            dev = lrge::DeviceReads::open(input, LRGE_GPU_INFLATE_BGZF | LRGE_GPU_INFLATE_GZIP | LRGE_GPU_INGEST_BAM | LRGE_GPU_INGEST_SAM | LRGE_GPU_INGEST_WINDOWED | LRGE_GPU_INGEST_WINDOWED_ALN | (gpu_bzip2 ? LRGE_GPU_INFLATE_BZIP2 : 0), device);
             if (info) fprintf(stderr, "[INFO] gpu-ingest: %s\n", dev ? "device" : "host");
             if (dev && dev->names.empty()) throw lrge::LrgeError(LRGE_ERR_IO, "IO error: Is the file empty?");
         }
