@@ -11,8 +11,9 @@
 #include <vector>
 
 #include "bam_round.h"
-#include "fx_window.h"
+#include "win_twin.h"
 
+namespace bam_twin {             // (a name of its own: tools/window_twin_check.cpp holds the three twins in one translation unit)
 namespace {
 struct Parsed {
     std::vector<uint8_t> text;          // a copy with slack behind it, as the device buffer has (the gather's word loads)
@@ -56,52 +57,42 @@ struct Twin {
     }
 };
 
-// ---- the windowed ingest: fx_window.h over the passes above ----
-struct WinOut {
-    std::vector<FxRec> recs;            // name_off: in the whole text; seq_off: in `store`; seq_span = (seq_len + 1) / 2
-    std::vector<uint8_t> store;         // the packed bytes of every record, dense, as k_bam_store leaves them (PAD of slack behind)
-    FxWinStats st = {0, 0, 0, 0};
-    BamStats bam = {0, 0, 0, 0, 0, 0};
-    uint64_t scans = 0;                 // record scans run, with or without a cut
-    uint64_t store_bytes = 0;
-};
-WinOut gw;
+// bam_run over a copy of the text into `g`: 0, BAM_UNPROVEN (any bits of the table step included), FX_TOO_MANY
+int run(const uint8_t *text, uint64_t n, uint64_t S, bool first = true, uint64_t *cut = nullptr) {
+    g = Parsed();
+    g.text.assign(n + PAD, 0);
+    if (n) memcpy(g.text.data(), text, n);
+    Twin be = {g.text.data(), n, 0, 0};
+    uint64_t n_rec = 0, name_bytes = 0;
+    const char *refused = nullptr;
+    const int rc = bam_run(be, n, S, &g.st, &n_rec, &name_bytes, &refused, first, cut);
+    return rc > 0 && rc != (int)FX_TOO_MANY ? (int)BAM_UNPROVEN : rc;
+}
 
-struct WinTwin {
-    std::vector<uint8_t> blk;
-    uint64_t S, base = 0;               // base: where the block starts in the whole text
-    uint64_t len() const { return blk.size(); }
-    int resident_format(bool *yes) const { *yes = false; return 0; }
-    void resident_again() const {}
-    int unproven(const char *) const { return (int)BAM_UNPROVEN; }
-    int flush(bool first, bool end, uint64_t *cut, int *fmt) {
-        const uint64_t n = blk.size();
-        g = Parsed();
-        g.text.assign(n + PAD, 0);
-        if (n) memcpy(g.text.data(), blk.data(), n);
-        Twin be = {g.text.data(), n, 0, 0};
-        uint64_t n_rec = 0, name_bytes = 0, c = 0;
-        const char *refused = nullptr;
-        ++gw.scans;
-        const int rc = bam_run(be, n, S, &g.st, &n_rec, &name_bytes, &refused, first, end ? nullptr : &c);
-        if (rc) return rc > 0 && rc != (int)FX_TOO_MANY ? (int)BAM_UNPROVEN : rc;
-        *cut = end ? n : c;
+// ---- the windowed ingest: win_twin.h over the passes above ----
+// (the store holds the packed bytes of every record, as k_bam_store leaves them, with PAD of slack behind; seq_span = (seq_len + 1) / 2)
+WinTwinOut gw;
+BamStats gw_bam = {0, 0, 0, 0, 0, 0};   // summed over the windows
+uint64_t gw_scans = 0, gw_store_bytes = 0;       // record scans run, with or without a cut; the store without its slack
+
+struct Scan {
+    uint64_t S;
+    int scan(const std::vector<uint8_t> &blk, bool first, bool end, uint64_t *cut, int *fmt) {
+        uint64_t c = 0;
+        ++gw_scans;
+        const int rc = run(blk.data(), blk.size(), S, first, end ? nullptr : &c);
+        if (rc) return rc;
+        *cut = end ? blk.size() : c;
         *fmt = FX_FMT_BAM;
         if (!*cut) return 0;
-        uint64_t *sum = &gw.bam.segments;
+        uint64_t *sum = &gw_bam.segments;
         const uint64_t *add = &g.st.segments;
         for (int i = 0; i < 6; ++i) sum[i] += add[i];
-        for (uint64_t i = 0; i < n_rec; ++i) {
-            const FxRec &r = g.recs[i];
-            gw.recs.push_back(FxRec{base + r.name_off, gw.store.size(), r.seq_span, r.name_len, r.seq_len});
-            gw.store.insert(gw.store.end(), g.text.data() + r.seq_off, g.text.data() + r.seq_off + r.seq_span);
-        }
         return 0;
     }
-    int carry(uint64_t cut) {
-        blk.erase(blk.begin(), blk.begin() + (long)cut);
-        base += cut;
-        return 0;
+    const std::vector<FxRec> &recs() const { return g.recs; }
+    void append(const std::vector<uint8_t> &, uint64_t, const FxRec &r, std::vector<uint8_t> &store) const {
+        store.insert(store.end(), g.text.data() + r.seq_off, g.text.data() + r.seq_off + r.seq_span);
     }
 };
 
@@ -126,14 +117,9 @@ extern "C" {
 int bam_twin_parse(const uint8_t *text, uint64_t n, uint64_t S) {
     g = Parsed();
     if (S < 64) return -1;
-    g.text.assign(n + PAD, 0);
-    if (n) memcpy(g.text.data(), text, n);
-    Twin be = {g.text.data(), n, 0, 0};
-    uint64_t n_rec = 0, name_bytes = 0;
-    const char *refused = nullptr;
-    const int rc = bam_run(be, n, S, &g.st, &n_rec, &name_bytes, &refused);
+    const int rc = run(text, n, S);
     if (rc) g.recs.clear();
-    return rc > 0 && rc != (int)FX_TOO_MANY ? (int)BAM_UNPROVEN : rc;       // (any bits of the table step are unproven, as before)
+    return rc;
 }
 
 uint64_t bam_twin_count(void) { return g.recs.size(); }
@@ -148,39 +134,30 @@ uint64_t bam_twin_seq(uint64_t i, uint32_t misalign, uint8_t *out) {
     return gather(g.text.data() + r.seq_off, r.seq_len, misalign, out);
 }
 
-// The text through the windows of fx_window.h: `piece` bytes appended per step, a flush once the block holds `window` bytes.
-// 0: proven, BAM_UNPROVEN, FX_TOO_MANY; the records by bam_twin_windowed_count / _table / _seq (the same gather, applied to the
-// store), the store by _store, the counts by _stats (windows flushed first: 0 means the text ended before its first flush and
-// was scanned whole, as without windows; out[4]: record scans run) and _bam_stats (summed over the windows).
+// The text through the windows of fx_window.h (win_twin_run).  0: proven, BAM_UNPROVEN, FX_TOO_MANY; the records by
+// bam_twin_windowed_count / _table / _seq (the same gather, applied to the store), the store by _store, the counts by _stats
+// (windows flushed first: 0 means the text ended before its first flush and was scanned whole, as without windows, with no store
+// as on the device; out[4]: record scans run, kept across a refused run) and _bam_stats (summed over the windows).
 int bam_twin_windowed(const uint8_t *text, uint64_t n, uint64_t S, uint64_t window, uint64_t piece) {
-    gw = WinOut();
+    gw = WinTwinOut(); gw_bam = BamStats{0, 0, 0, 0, 0, 0}; gw_scans = gw_store_bytes = 0;
     if (S < 64 || !piece) return -1;
-    WinTwin b;
-    b.S = S;
-    FxWindow<WinTwin> win(b, window);
-    int rc = 0;
-    for (uint64_t p = 0; p < n && !rc; p += piece) {
-        b.blk.insert(b.blk.end(), text + p, text + (n - p < piece ? n : p + piece));
-        rc = win.step(false);
-    }
-    uint64_t all = 0;
-    if (!rc) rc = win.st.windows ? win.step(true) : b.flush(true, true, &all, &win.fmt);         // (or the resident scan)
-    const uint64_t scans = gw.scans;
-    if (rc) { gw = WinOut(); gw.scans = scans; return rc; }
-    gw.store_bytes = gw.store.size();
-    gw.st = win.st; gw.st.bases = win.st.windows ? gw.store_bytes : 0;      // (resident: no store, as on the device)
-    gw.store.resize(gw.store_bytes + PAD, 0);
+    Scan sc = {S};
+    const int rc = win_twin_run(sc, text, n, window, piece, false, gw);
+    if (rc) { gw_bam = BamStats{0, 0, 0, 0, 0, 0}; return rc; }
+    gw_store_bytes = gw.store.size();
+    gw.store.resize(gw_store_bytes + PAD, 0);
     return 0;
 }
 
 uint64_t bam_twin_windowed_count(void) { return gw.recs.size(); }
-void bam_twin_windowed_table(FxRec *out) { if (!gw.recs.empty()) memcpy(out, gw.recs.data(), gw.recs.size() * sizeof(FxRec)); }
-void bam_twin_windowed_stats(uint64_t out[5]) { out[0] = gw.st.windows; out[1] = gw.st.bases; out[2] = gw.st.max_window; out[3] = gw.st.carried; out[4] = gw.scans; }
-void bam_twin_windowed_bam_stats(BamStats *out) { *out = gw.bam; }
-uint64_t bam_twin_windowed_store(uint8_t *out) { if (out && gw.store_bytes) memcpy(out, gw.store.data(), gw.store_bytes); return gw.store_bytes; }
+void bam_twin_windowed_table(FxRec *out) { gw.table(out); }
+void bam_twin_windowed_stats(uint64_t out[5]) { gw.stats(out); out[4] = gw_scans; }
+void bam_twin_windowed_bam_stats(BamStats *out) { *out = gw_bam; }
+uint64_t bam_twin_windowed_store(uint8_t *out) { return gw.store_to(out, gw_store_bytes); }
 uint64_t bam_twin_windowed_seq(uint64_t i, uint32_t misalign, uint8_t *out) {
     const FxRec &r = gw.recs[i];
     return gather(gw.store.data() + r.seq_off, r.seq_len, misalign, out);
 }
 
 }  // extern "C"
+}  // namespace bam_twin

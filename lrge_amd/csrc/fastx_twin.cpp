@@ -9,8 +9,9 @@
 #include <vector>
 
 #include "fastx_core.h"
-#include "fx_window.h"
+#include "win_twin.h"
 
+namespace fastx_twin {           // (a name of its own: tools/window_twin_check.cpp holds the three twins in one translation unit)
 namespace {
 struct Parsed {
     int fmt = FX_FMT_EMPTY;
@@ -149,41 +150,20 @@ int parse(const uint8_t *t, uint64_t n, uint64_t tile, Win *w) {
     return 0;
 }
 
-// ---- the windowed ingest: fx_window.h over the passes above ----
-struct WinOut {
-    std::vector<FxRec> recs;            // name_off: in the whole text; seq_off: in `store`; seq_span = seq_len
-    std::vector<uint8_t> store;
-    FxWinStats st = {0, 0, 0, 0};
-    int fmt = FX_FMT_EMPTY;
-};
-WinOut gw;
-
-struct WinTwin {
-    std::vector<uint8_t> blk;
-    uint64_t tile, base = 0;            // base: where the block starts in the whole text
-    uint64_t len() const { return blk.size(); }
-    int resident_format(bool *yes) const { *yes = false; return 0; }
-    void resident_again() const {}
-    int unproven(const char *) const { return (int)FX_UNPROVEN; }
-    int flush(bool first, bool end, uint64_t *cut, int *fmt) {
+// ---- the windowed ingest: win_twin.h over the passes above ----
+struct Scan {
+    uint64_t tile;
+    int scan(const std::vector<uint8_t> &blk, bool first, bool end, uint64_t *cut, int *fmt) {
         Win w = {first, end, 0};
         const int rc = parse(blk.data(), blk.size(), tile, &w);
-        if (rc) return rc;
         *cut = end ? blk.size() : w.cut;
         *fmt = g.fmt;
-        if (!*cut) return 0;
-        for (const FxRec &r : g.recs) {
-            gw.recs.push_back(FxRec{base + r.name_off, gw.store.size(), r.seq_len, r.name_len, r.seq_len});
-            append_seq(blk.data(), *cut, r, gw.store);
-        }
-        return 0;
+        return rc;
     }
-    int carry(uint64_t cut) {
-        blk.erase(blk.begin(), blk.begin() + (long)cut);
-        base += cut;
-        return 0;
-    }
+    const std::vector<FxRec> &recs() const { return g.recs; }
+    void append(const std::vector<uint8_t> &blk, uint64_t cut, const FxRec &r, std::vector<uint8_t> &store) const { append_seq(blk.data(), cut, r, store); }
 };
+WinTwinOut gw;
 }  // namespace
 
 extern "C" {
@@ -208,35 +188,21 @@ uint64_t fastx_twin_seq(const uint8_t *t, uint64_t n, uint64_t i, uint8_t *out) 
     return s.size();
 }
 
-// The text through the windows of fx_window.h: `piece` bytes appended per step, a flush once the block holds `window` bytes.
-// 0: proven, FX_UNPROVEN, FX_TOO_MANY; the records by fastx_twin_windowed_count / _table / _seq, the counts by _stats
-// (windows flushed first: 0 means the text ended before its first flush and was scanned whole, as without windows).
+// The text through the windows of fx_window.h (win_twin_run).  0: proven, FX_UNPROVEN, FX_TOO_MANY; the records by
+// fastx_twin_windowed_count / _table / _seq, the counts by _stats (windows flushed first: 0 means the text ended before its first
+// flush and was scanned whole, as without windows; the bases are counted all the same).
 int fastx_twin_windowed(const uint8_t *t, uint64_t n, uint64_t tile, uint64_t window, uint64_t piece) {
-    gw = WinOut();
+    gw = WinTwinOut();
     if (tile < 16 || tile % 16 || !piece) return -1;
-    WinTwin b;
-    b.tile = tile;
-    FxWindow<WinTwin> win(b, window);
-    int rc = 0;
-    for (uint64_t p = 0; p < n && !rc; p += piece) {
-        b.blk.insert(b.blk.end(), t + p, t + (n - p < piece ? n : p + piece));
-        rc = win.step(false);
-    }
-    uint64_t all = 0;
-    if (!rc) rc = win.st.windows ? win.step(true) : b.flush(true, true, &all, &win.fmt);         // (or the resident scan)
-    if (rc) { gw = WinOut(); return rc; }
-    gw.st = win.st; gw.st.bases = gw.store.size(); gw.fmt = win.fmt;
-    return 0;
+    Scan sc = {tile};
+    return win_twin_run(sc, t, n, window, piece, true, gw);
 }
 
 uint64_t fastx_twin_windowed_count(void) { return gw.recs.size(); }
 int fastx_twin_windowed_format(void) { return gw.fmt; }
-void fastx_twin_windowed_table(FxRec *out) { if (!gw.recs.empty()) memcpy(out, gw.recs.data(), gw.recs.size() * sizeof(FxRec)); }
-void fastx_twin_windowed_stats(uint64_t out[4]) { out[0] = gw.st.windows; out[1] = gw.st.bases; out[2] = gw.st.max_window; out[3] = gw.st.carried; }
-uint64_t fastx_twin_windowed_seq(uint64_t i, uint8_t *out) {
-    const FxRec &r = gw.recs[i];
-    if (r.seq_len) memcpy(out, gw.store.data() + r.seq_off, r.seq_len);
-    return r.seq_len;
-}
+void fastx_twin_windowed_table(FxRec *out) { gw.table(out); }
+void fastx_twin_windowed_stats(uint64_t out[4]) { gw.stats(out); }
+uint64_t fastx_twin_windowed_seq(uint64_t i, uint8_t *out) { return gw.seq(i, out); }
 
 }  // extern "C"
+}  // namespace fastx_twin

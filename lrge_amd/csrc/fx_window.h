@@ -44,12 +44,12 @@ static inline void fx_win_census(FxCensus &c, bool first) {
 
 // Backend B:
 //   uint64_t len()                                          bytes in the block
-//   int resident_format(bool *yes)                          *yes: the first four bytes are a format that is not windowed (BAM,
-//                                                           SAM with their flags but without the flag that windows them): the
-//                                                           block stays resident from here on (resident_again() tells the
-//                                                           backend).  Called once, before the first flush: a backend that
-//                                                           scans several formats fixes the run's here.  0 or the backend's code
-//   void resident_again()                                   the windows are off: the block grows as a resident text does
+//   int resident_format(bool *yes)                          the sniff of the block's first four bytes.  Called once, before the
+//                                                           first flush: a backend that scans several formats fixes the run's
+//                                                           here.  *yes: the format is not windowed (BAM, SAM with their flags
+//                                                           but without the flag that windows them) -- the driver is off from
+//                                                           here on, and the backend lets the block grow as a resident text
+//                                                           does.  0 or the backend's code
 //   int flush(bool first, bool end, uint64_t *cut, int *fmt)  the record scan of the block.  end: all of it as a complete text
 //                                                           (*cut = len).  Otherwise up to the cut of the rules above (*cut = 0:
 //                                                           there is none yet, nothing was taken).  The records found are
@@ -75,7 +75,7 @@ template <class B> struct FxWindow {
             bool yes = false;
             const int src = b.resident_format(&yes);
             if (src) return src;
-            if (yes) { off = true; b.resident_again(); return 0; }
+            if (yes) { off = true; return 0; }
         }
         if (len >> 32) return b.unproven("a window of 2^32 bytes or more");
         uint64_t cut = 0;

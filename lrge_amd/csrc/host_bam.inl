@@ -54,11 +54,8 @@ struct BamDev {
         return LRGE_OK;
     }
     int records(const u64 *start, const u64 *base, u64 n_seg, u64 n_rec, u64 cut, u32 *flags, u64 *name_bytes) {
-        hipError_t e = hipSuccess;
-        if (!(R->d_recs = (FxRec *)ctx->pool.alloc((size_t)std::max<u64>(1, n_rec) * sizeof(FxRec), &e))) {
-            LRGE_SET_ERR(ctx, "reads_open: record table: %s", hipGetErrorString(e));
-            return LRGE_ERR_DEVICE;
-        }
+        const int rc = fx_alloc_recs(ctx, R, std::max<u64>(1, n_rec));
+        if (rc) return rc;
         if (!(d_seq_len = sc.get<u32>(std::max<u64>(1, n_rec))) || !(d_name_len = sc.get<u32>(std::max<u64>(1, n_rec)))) return LRGE_ERR_DEVICE;
         ALLOC_OR_FAIL(d_flags, sc, u64, 2);                   // [0]: verdict bits (low word), [1]: identifier bytes
         HIPCHK(ctx, hipMemsetAsync(d_flags, 0, 16, st));

@@ -1,10 +1,12 @@
 // host_bzip2.inl -- bzip2 decompressed on the device (k_bzip2.h): the backend that bz_round.h's bz_run drives and
-// the C entry point.  Included into lrge_hip.hip behind host_gzip.inl (DevKeep, GzBuf).
+// the C entry point.  Included into lrge_hip.hip behind host_gzip.inl (GzBuf).
 //
 // The compressed bytes go up once and stay for the call (they are a fraction of the text).  Option BZIP2_ROUND_BLOCKS: the
 // candidates decoded per round; its default is what half of the arena's idle bytes plus the device's free bytes hold at
 // bz_candidate_bytes per candidate, at most BZ_ROUND_MAX.  Option BZIP2_TIMING: the stages are separated by synchronisations and
 // their times are printed to stderr when the call ends (tools/bzip2_bench.py).
+
+#include "dev_keep.h"
 
 static const char *bz_status_name(int s) {
     switch (s) {
@@ -179,31 +181,4 @@ extern "C" int lrge_hip_bzip2_inflate(lrge_hip_ctx *ctx, const void *comp, uint6
     if (stats) memset(stats, 0, sizeof *stats);
     if (!ctx || !sink || (!comp && comp_len)) return LRGE_ERR_INVALID;
     return bzip2_inflate_impl(ctx, (const uint8_t *)comp, comp_len, sink, user, stats);
-}
-
-// bzip2 input whose text stays in HBM: the rounds of bz_run with BzDev writing every round's text behind the earlier rounds'
-// (DevKeep: keep_*).  LRGE_OK with the block in *d_text (the caller's now), LRGE_ERR_UNPROVEN, LRGE_ERR_DEVICE.  run: the call is
-// windowed -- the block is flushed through the run whenever a round has been appended (DevKeep::keep_flush), as for gzip
-static int bzip2_inflate_to_device(lrge_hip_ctx *ctx, const uint8_t *comp, uint64_t comp_len, u64 max_bytes, u64 slack, u8 **d_text, u64 *n_text, FxWinRun *run) {
-    BzStats st;
-    u64 bad = 0;
-    BzDev dev(ctx);
-    dev.keep_on = true; dev.keep_max = max_bytes; dev.keep_slack = slack;
-    if (run) fx_win_attach(run, &dev);
-    const int rc = bz_run(dev, comp, comp_len, ctx->opt_u64("BZIP2_ROUND_BLOCKS", 0), [&](const uint8_t *, uint64_t) { return true; }, st, &bad);
-    (void)hipStreamSynchronize(ctx->stream);
-    if (rc == BZ_RUN_OK) {
-        if (!dev.keep && !dev.keep_reserve(0)) { LRGE_SET_ERR(ctx, "reads_open: device allocation failed"); return LRGE_ERR_DEVICE; }
-        *d_text = dev.keep; *n_text = dev.keep_len; dev.keep = nullptr;
-        return LRGE_OK;
-    }
-    if (run && fx_win_stopped(run)) return fx_win_stopped(run);
-    if (dev.keep_over) { LRGE_SET_ERR(ctx, "reads_open: text above INGEST_MAX_BYTES (%llu)", (unsigned long long)max_bytes); return LRGE_ERR_UNPROVEN; }
-    if (rc == BZ_RUN_DEVICE) {
-        LRGE_SET_ERR(ctx, "reads_open: bzip2 inflate: %s", hipGetErrorString(dev.e != hipSuccess ? dev.e : hipErrorUnknown));
-        (void)hipGetLastError();
-        return LRGE_ERR_DEVICE;
-    }
-    LRGE_SET_ERR(ctx, "reads_open: bzip2 data not accepted by the device (%s near file offset %llu)", bz_status_name(rc), (unsigned long long)bad);
-    return LRGE_ERR_UNPROVEN;
 }

@@ -7,7 +7,10 @@
 // LRGE_GPU_INGEST_WINDOWED FASTA / FASTQ text larger than option INGEST_WINDOW_BYTES passes through HBM in windows and only the
 // bases stay (fx_window.h); with LRGE_GPU_INGEST_WINDOWED_ALN beside it so does unaligned BAM and SAM, BAM's
 // bases staying packed.  Included into lrge_hip.hip.
+// A call (lrge_hip_reads_open_mem) is one source (fx_src_raw, _bgzf, _gzip, _bzip2), which brings the text to the sink (FxSink) resident
+// or through the windows of the sink's FxWinRun, and one record scan (fx_parse_kind), chosen by the sniff (fx_kind).
 
+#include "dev_keep.h"
 #include "fx_window.h"
 
 struct lrge_hip_reads {
@@ -32,15 +35,29 @@ static u64 ingest_cap(lrge_hip_ctx *ctx) {
     return ctx->opt_u64("INGEST_MAX_BYTES", ((u64)mfree + ctx->pool.idle()) / 2);       // (the batch planner's accounting: idle arena bytes are reusable)
 }
 
-static int fx_over_cap_rc(lrge_hip_ctx *ctx, u64 cap) {
-    LRGE_SET_ERR(ctx, "reads_open: text above INGEST_MAX_BYTES (%llu)", (unsigned long long)cap);
-    return LRGE_ERR_UNPROVEN;
-}
-
 static int fx_verdict_rc(lrge_hip_ctx *ctx, u32 verdict, const char *what) {
     if (verdict & FX_UNPROVEN) { LRGE_SET_ERR(ctx, "reads_open: not proven on the device (%s)", what); return LRGE_ERR_UNPROVEN; }
     LRGE_SET_ERR(ctx, "reads_open: 2^32 records or a sequence of 2^32 bases (%s)", what);
     return LRGE_ERR_TOO_MANY;
+}
+
+// the record table of n records in R->d_recs
+static int fx_alloc_recs(lrge_hip_ctx *ctx, lrge_hip_reads *R, u64 n) {
+    hipError_t e = hipSuccess;
+    if ((R->d_recs = (FxRec *)ctx->pool.alloc((size_t)n * sizeof(FxRec), &e))) return LRGE_OK;
+    LRGE_SET_ERR(ctx, "reads_open: record table: %s", hipGetErrorString(e));
+    return LRGE_ERR_DEVICE;
+}
+
+// behind the kernel that fills the record table: its verdict bits ([0], low word) and the identifier bytes ([1]) come back
+static int fx_flags_back(lrge_hip_ctx *ctx, const u64 *d_flags, const char *outside, u64 *name_bytes) {
+    u64 flags[2] = {0, 0};
+    HIPCHK(ctx, ctx->d2h(flags, d_flags, sizeof flags, ctx->stream));
+    HIPCHK(ctx, ctx->d2h_sync(ctx->stream));
+    if ((u32)flags[0]) return fx_verdict_rc(ctx, (u32)flags[0], outside);
+    if (flags[1] >> 32) return fx_verdict_rc(ctx, FX_UNPROVEN, "4 GiB of identifiers or more");
+    *name_bytes = flags[1];
+    return LRGE_OK;
 }
 
 // identifiers and lengths to the host, behind a record scan that left the table in R->d_recs, the lengths in d_seq_len /
@@ -71,23 +88,36 @@ static int fx_tables_to_host(lrge_hip_ctx *ctx, lrge_hip_reads *R, Scratch &sc, 
     return LRGE_OK;
 }
 
-// BAM and SAM by their magic, when the caller asked for them (head: the first min(4, n) text bytes)
-static void fx_sniff_bam_sam(int flags, const u8 head[4], u64 n, bool *is_bam, bool *is_sam) {
-    *is_bam = (flags & LRGE_GPU_INGEST_BAM) && n >= 4 && head[0] == 'B' && head[1] == 'A' && head[2] == 'M' && head[3] == 1;
-    *is_sam = (flags & LRGE_GPU_INGEST_SAM) && n >= 3 && sam_sniff(head, n);
+// ---- the sniff: which record scan a text takes ----
+// by its first min(4, n) bytes: FX_FMT_BAM and FX_FMT_SAM by their magic, when the caller asked for them; else FX_FMT_EMPTY --
+// FASTA or FASTQ, which the record scan tells apart
+static int fx_sniff(int flags, const u8 *head, u64 n) {
+    if ((flags & LRGE_GPU_INGEST_BAM) && n >= 4 && head[0] == 'B' && head[1] == 'A' && head[2] == 'M' && head[3] == 1) return FX_FMT_BAM;
+    return (flags & LRGE_GPU_INGEST_SAM) && n >= 3 && sam_sniff(head, n) ? FX_FMT_SAM : FX_FMT_EMPTY;
 }
 
-// BAM and SAM that stay resident: all of them, unless the caller asked for their windows as well
-static bool fx_stays_resident(int flags, bool is_bam, bool is_sam) { return (is_bam || is_sam) && !(flags & LRGE_GPU_INGEST_WINDOWED_ALN); }
+// the kind of a text of n bytes, after obtaining those bytes: the file's own when they are the text (host), else four bytes
+// copied from the block d_text.  Nothing is copied for a caller who asked for neither BAM nor SAM, or for a text below either magic
+static int fx_kind(lrge_hip_ctx *ctx, int flags, const u8 *host, const u8 *d_text, u64 n, int *kind) {
+    *kind = FX_FMT_EMPTY;
+    if (!(flags & (LRGE_GPU_INGEST_BAM | LRGE_GPU_INGEST_SAM)) || n < 3) return LRGE_OK;
+    u8 head[4] = {0, 0, 0, 0};
+    const size_t k = (size_t)std::min<u64>(4, n);
+    if (host) memcpy(head, host, k);
+    else { HIPCHK(ctx, hipMemcpyAsync(head, d_text, k, hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); }
+    *kind = fx_sniff(flags, head, n);
+    return LRGE_OK;
+}
+
+// BAM and SAM stay resident unless the caller asked for their windows as well
+static bool fx_kind_windowed(int flags, int kind) { return kind == FX_FMT_EMPTY || (flags & LRGE_GPU_INGEST_WINDOWED_ALN); }
 
 // ---- windowed ingest: the device backend of fx_window.h ----
 struct FxWinDev;
-// the scan of one window (fx_parse_device, bam_parse_device, sam_parse_device): up to its cut (left in `cut`; 0: there is none
-// yet) unless `end`
+// the scan of one window (fx_parse_kind): up to its cut (left in `cut`; 0: there is none yet) unless `end`
 struct FxWinScan { FxWinDev *dev; bool first, end; u64 cut; };
-static int fx_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R, FxWinScan *w = nullptr);
-static int bam_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R, FxWinScan *w = nullptr);
-static int sam_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R, FxWinScan *w = nullptr);
+// the record scan of R->d_text by its kind (fx_kind): bam_parse_device, sam_parse_device or fx_parse_device
+static int fx_parse_kind(lrge_hip_ctx *ctx, lrge_hip_reads *R, int kind, FxWinScan *w = nullptr);
 
 struct FxWinDev {
     lrge_hip_ctx *ctx;
@@ -107,30 +137,24 @@ struct FxWinDev {
     }
     u64 len() const { return blk->keep_len; }
     int unproven(const char *what) { LRGE_SET_ERR(ctx, "reads_open: not proven on the device (%s)", what); return LRGE_ERR_UNPROVEN; }
-    // BAM and SAM with their flags are not windowed unless LRGE_GPU_INGEST_WINDOWED_ALN says so; with it this sniff, the first
-    // window's, makes the run a BAM or SAM run: a later window is never sniffed.  (Plain and BGZF input is sniffed before a
-    // window is set up as well, lrge_hip_reads_open_mem; the round decoders' first bytes arrive with a round.)
+    // the sniff of the first window makes the run a BAM or SAM run: a later window is never sniffed.  BAM and SAM that stay
+    // resident turn the windows off: the block takes back the growth rule a resident text has without the flag (attach() had made it
+    // a window's; keep_flush stays: it is running, and the driver returns at once from now on).  (Plain and BGZF input is sniffed
+    // before a window is set up as well, FxSink::windowed; the round decoders' first bytes arrive with a round.)
+    u64 was_hint = 0, was_floor = 0, was_grow = 2;
     int resident_format(bool *yes) {
         *yes = false;
-        if (!(flags & (LRGE_GPU_INGEST_BAM | LRGE_GPU_INGEST_SAM))) return LRGE_OK;
-        u8 head[4] = {0, 0, 0, 0};
-        HIPCHK(ctx, hipMemcpyAsync(head, blk->keep, (size_t)std::min<u64>(4, blk->keep_len), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        bool is_bam, is_sam;
-        fx_sniff_bam_sam(flags, head, blk->keep_len, &is_bam, &is_sam);
-        *yes = fx_stays_resident(flags, is_bam, is_sam);
-        if (!*yes) kind = is_bam ? FX_FMT_BAM : is_sam ? FX_FMT_SAM : FX_FMT_EMPTY;
+        const int rc = fx_kind(ctx, flags, nullptr, blk->keep, blk->keep_len, &kind);
+        if (rc) return rc;
+        if ((*yes = !fx_kind_windowed(flags, kind))) { blk->keep_hint = was_hint; blk->keep_floor = was_floor; blk->keep_grow = was_grow; blk->keep_max = cap; }
         return LRGE_OK;
     }
-    // the growth rule a resident text has without the flag (attach() had made the block a window's)
-    u64 was_hint = 0, was_floor = 0, was_grow = 2;
-    void resident_again() { blk->keep_hint = was_hint; blk->keep_floor = was_floor; blk->keep_grow = was_grow; blk->keep_max = cap; }     // (keep_flush stays: it is running, and the driver returns at once from now on)
     int flush(bool first, bool end, u64 *cut, int *fmt) {
         lrge_hip_reads W;                       // the window as a text of its own; the block stays the decoder's
         W.ctx = ctx; W.d_text = blk->keep; W.n_text = blk->keep_len;
         FxWinScan w = {this, first, end, 0};
         const double t0 = fx_now_ms();
-        const int prc = kind == FX_FMT_BAM ? bam_parse_device(ctx, &W, &w) : kind == FX_FMT_SAM ? sam_parse_device(ctx, &W, &w) : fx_parse_device(ctx, &W, &w);
+        const int prc = fx_parse_kind(ctx, &W, kind, &w);
         ctx->pool.release(W.d_recs);
         ms_names += W.ms[2]; ms_scan += fx_now_ms() - t0 - W.ms[2];
         if (prc) return prc;
@@ -224,13 +248,14 @@ struct FxWinRun {
         b->keep_flush = [this] { return appended(); };
     }
     int stopped() { if (dev.rc) dev.ctx->err = dev.msg; return dev.rc; }
-    // the input is over and windows were flushed: what is left in the block (d_text, the run's now) is the last window; the
-    // store becomes the handle's text, with a record table of its own
-    int finish(u8 *d_text, u64 n_text) {
+    // the input is over and windows were flushed: what is left in the block (the handle's text so far, the run's now) is the
+    // last window; the store becomes the handle's text, with a record table of its own
+    int finish() {
         lrge_hip_ctx *ctx = dev.ctx;
         lrge_hip_reads *R = dev.R;
         DevKeep last(ctx);
-        last.keep = d_text; last.keep_len = n_text; last.keep_cap = n_text;
+        const u64 n_text = last.keep_len = last.keep_cap = R->n_text;
+        last.keep = R->d_text; R->d_text = nullptr; R->n_text = 0;
         dev.blk = &last;
         int rc = win.step(true);
         if (rc) return rc;
@@ -243,8 +268,7 @@ struct FxWinRun {
             tab[i] = FxRec{0, o, span, (u32)(R->name_off[i + 1] - R->name_off[i]), R->seq_len[i]};
             o += span;
         }
-        hipError_t e = hipSuccess;
-        if (!(R->d_recs = (FxRec *)ctx->pool.alloc(std::max<size_t>(1, tab.size()) * sizeof(FxRec), &e))) { LRGE_SET_ERR(ctx, "reads_open: record table: %s", hipGetErrorString(e)); return LRGE_ERR_DEVICE; }
+        if ((rc = fx_alloc_recs(ctx, R, std::max<u64>(1, R->n)))) return rc;
         if (!tab.empty()) HIPCHK(ctx, hipMemcpyAsync(R->d_recs, tab.data(), tab.size() * sizeof(FxRec), hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         R->d_text = dev.store.keep; R->n_text = dev.store.keep_len; dev.store.keep = nullptr;
@@ -256,8 +280,23 @@ struct FxWinRun {
     }
 };
 
-static void fx_win_attach(FxWinRun *run, DevKeep *blk) { run->attach(blk); }
-static int fx_win_stopped(FxWinRun *run) { return run->stopped(); }
+// the prologue of the scans that work on lines (FASTA / FASTQ, SAM): the census of every tile of t[0, n) and its summary
+struct FxTiles { u64 n_tiles; u32 *c_lf, *c_rem, *c_hdr; FxSummary hs; };
+static int fx_census_device(lrge_hip_ctx *ctx, Scratch &sc, const u8 *t, u64 n, FxTiles *o) {
+    hipStream_t st = ctx->stream;
+    ctx->pin_items.clear(); ctx->pin_used = 0;
+    const u64 n_tiles = o->n_tiles = div_up(n, FX_TILE);
+    if (n_tiles >> 31) return fx_verdict_rc(ctx, FX_UNPROVEN, "text of 8 TiB or more");
+    if (!(o->c_lf = sc.get<u32>(n_tiles)) || !(o->c_rem = sc.get<u32>(n_tiles)) || !(o->c_hdr = sc.get<u32>(n_tiles))) return LRGE_ERR_DEVICE;
+    ALLOC_OR_FAIL(d_sum, sc, FxSummary, 1);
+    hipLaunchKernelGGL(k_fx_census, dim3((u32)n_tiles), dim3(FX_THREADS), 0, st, t, n, o->c_lf, o->c_rem, o->c_hdr);
+    KCHK(ctx);
+    hipLaunchKernelGGL(k_fx_summary, dim3(1), dim3(FX_THREADS), 0, st, t, n, (const u32 *)o->c_lf, (const u32 *)o->c_rem, (const u32 *)o->c_hdr, n_tiles, d_sum);
+    KCHK(ctx);
+    HIPCHK(ctx, ctx->d2h(&o->hs, d_sum, sizeof o->hs, st));
+    HIPCHK(ctx, ctx->d2h_sync(st));
+    return LRGE_OK;
+}
 
 // the record scan over R->d_text: fills the table, the lengths and the identifiers.  w: the text is a window (fx_window.h) --
 // scanned up to its cut unless it is the last, its bases copied to the store
@@ -268,20 +307,10 @@ static int fx_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R, FxWinScan *w) {
     if (n == 0) return LRGE_OK;
     hipStream_t st = ctx->stream;
     Scratch sc(ctx);
-    ctx->pin_items.clear(); ctx->pin_used = 0;
-    const u64 n_tiles = div_up(n, FX_TILE);
-    if (n_tiles >> 31) return fx_verdict_rc(ctx, FX_UNPROVEN, "text of 8 TiB or more");
-    ALLOC_OR_FAIL(c_lf, sc, u32, n_tiles);
-    ALLOC_OR_FAIL(c_rem, sc, u32, n_tiles);
-    ALLOC_OR_FAIL(c_hdr, sc, u32, n_tiles);
-    ALLOC_OR_FAIL(d_sum, sc, FxSummary, 1);
-    hipLaunchKernelGGL(k_fx_census, dim3((u32)n_tiles), dim3(FX_THREADS), 0, st, t, n, c_lf, c_rem, c_hdr);
-    KCHK(ctx);
-    hipLaunchKernelGGL(k_fx_summary, dim3(1), dim3(FX_THREADS), 0, st, t, n, (const u32 *)c_lf, (const u32 *)c_rem, (const u32 *)c_hdr, n_tiles, d_sum);
-    KCHK(ctx);
-    FxSummary hs;
-    HIPCHK(ctx, ctx->d2h(&hs, d_sum, sizeof hs, st));
-    HIPCHK(ctx, ctx->d2h_sync(st));
+    FxTiles tl;
+    int rc = fx_census_device(ctx, sc, t, n, &tl);
+    if (rc) return rc;
+    const auto &[n_tiles, c_lf, c_rem, c_hdr, hs] = tl;
     FxCensus c;
     c.n_lf = hs.n_lf; c.n_rem = hs.n_rem; c.n_hdr = hs.n_hdr; c.first = hs.first; c.last = hs.last;
     for (int i = 0; i < 4; ++i) c.head[i] = (u8)(hs.head >> (8 * i));
@@ -298,7 +327,6 @@ static int fx_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R, FxWinScan *w) {
     u64 n_rec = 0, n_lines = 0, l0 = 0;
     u64 n_use = n, n_lf = c.n_lf, n_rem = c.n_rem;         // a window's prefix is scanned as a text of its own: its size and counts
     const bool to_cut = w && !w->end;
-    int rc;
     if (fmt == FX_FMT_FASTQ) {
         if ((rc = scan_exclusive_u32(ctx, sc, c_lf, c_lf, n_tiles, nullptr))) return rc;
         if (!(ls = sc.get<u64>(c.n_lf + 1)) || !(d_lines = sc.get<u64>(2))) return LRGE_ERR_DEVICE;
@@ -335,8 +363,7 @@ static int fx_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R, FxWinScan *w) {
     }
     if (w) w->cut = n_use;
     if (n_rec >> 32) return fx_verdict_rc(ctx, FX_TOO_MANY, "records");
-    hipError_t e = hipSuccess;
-    if (!(R->d_recs = (FxRec *)ctx->pool.alloc((size_t)n_rec * sizeof(FxRec), &e))) { LRGE_SET_ERR(ctx, "reads_open: record table: %s", hipGetErrorString(e)); return LRGE_ERR_DEVICE; }
+    if ((rc = fx_alloc_recs(ctx, R, n_rec))) return rc;
     ALLOC_OR_FAIL(d_seq_len, sc, u32, n_rec);
     ALLOC_OR_FAIL(d_name_len, sc, u32, n_rec);
     ALLOC_OR_FAIL(d_flags, sc, u64, 2);                   // [0]: verdict bits (low word), [1]: identifier bytes
@@ -345,47 +372,210 @@ static int fx_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R, FxWinScan *w) {
     hipLaunchKernelGGL(k_fx_records, dim3(rec_blocks), dim3(FX_THREADS), 0, st, t, n_use, fmt, n_rec, (const u64 *)ls, n_lf, n_lines, l0, (const u64 *)hpos, (const u32 *)hrem,
                        n_rem, R->d_recs, d_seq_len, d_name_len, (u32 *)d_flags, (unsigned long long *)(d_flags + 1));
     KCHK(ctx);
-    u64 flags[2] = {0, 0};
-    HIPCHK(ctx, ctx->d2h(flags, d_flags, sizeof flags, st));
-    HIPCHK(ctx, ctx->d2h_sync(st));
-    if ((u32)flags[0]) return fx_verdict_rc(ctx, (u32)flags[0], "a record outside the strict form");
-    if (flags[1] >> 32) return fx_verdict_rc(ctx, FX_UNPROVEN, "4 GiB of identifiers or more");
-    if ((rc = fx_tables_to_host(ctx, R, sc, n_rec, d_seq_len, d_name_len, flags[1])) || !w) return rc;
+    u64 name_bytes = 0;
+    if ((rc = fx_flags_back(ctx, d_flags, "a record outside the strict form", &name_bytes))) return rc;
+    if ((rc = fx_tables_to_host(ctx, R, sc, n_rec, d_seq_len, d_name_len, name_bytes)) || !w) return rc;
     return w->dev->store_window(sc, *R, d_seq_len, n_use);
 }
 
 #include "host_bam.inl"      // bam_parse_device: the same for unaligned BAM (needs the struct and the tail above)
 #include "host_sam.inl"      // sam_parse_device: the same for unaligned SAM
 
-// ---- text that stays in HBM ----
-// any other gzip input: the rounds of gz_run with GzDev keeping every round's bytes on the device (host_gzip.inl: keep_*).
-// LRGE_OK with the block in *d_text (the caller's now), LRGE_ERR_UNPROVEN, LRGE_ERR_DEVICE
-// run: the call is windowed -- the block is flushed through run->win whenever a round has been appended (DevKeep::keep_flush)
-static int gzip_inflate_to_device(lrge_hip_ctx *ctx, const uint8_t *comp, uint64_t comp_len, u64 max_bytes, u8 **d_text, u64 *n_text, FxWinRun *run) {
-    const GzCfg cfg = gz_cfg(ctx);
-    GzStats st;
+static int fx_parse_kind(lrge_hip_ctx *ctx, lrge_hip_reads *R, int kind, FxWinScan *w) {
+    return kind == FX_FMT_BAM ? bam_parse_device(ctx, R, w) : kind == FX_FMT_SAM ? sam_parse_device(ctx, R, w) : fx_parse_device(ctx, R, w);
+}
+
+// ---- the sink: where every source leaves the text ----
+// The text ends up in R->d_text / R->n_text: all of it (resident), or what is left behind the last flushed window.  A source that
+// has no block of its own appends to `blk`; a decoder appends to its own (fx_inflate_to_device).  INGEST_MAX_BYTES bounds either.
+struct FxSink {
+    lrge_hip_ctx *ctx;
+    lrge_hip_reads *R;
+    int flags;
+    u64 cap, window;
+    std::unique_ptr<FxWinRun> run;              // LRGE_GPU_INGEST_WINDOWED: text larger than a window passes through the block in windows (fx_window.h)
+    DevKeep blk;
+    const u8 *host_text = nullptr;              // the file's bytes, when they are the text
+    FxSink(lrge_hip_ctx *c, lrge_hip_reads *r, int f) : ctx(c), R(r), flags(f), cap(ingest_cap(c)),
+        window(std::max<u64>(1, c->opt_u64("INGEST_WINDOW_BYTES", std::min<u64>((u64)1 << 30, cap / 4)))), blk(c) {
+        if (flags & LRGE_GPU_INGEST_WINDOWED) run.reset(new FxWinRun(ctx, R, flags, cap, window));
+        blk.keep_on = true; blk.keep_max = cap; blk.keep_slack = FX_PAD;
+    }
+    int over_cap() { LRGE_SET_ERR(ctx, "reads_open: text above INGEST_MAX_BYTES (%llu)", (unsigned long long)cap); return LRGE_ERR_UNPROVEN; }
+    // does a text of n bytes go through windows in `blk`?  kind_of(int *kind): the sniff of its first bytes (fx_kind), asked for
+    // only where it decides: BAM and SAM that stay resident take the resident route exactly as without the windowed flag
+    template <class F> int windowed(u64 n, F kind_of, bool *yes) {
+        *yes = false;
+        if (!run || n <= window) return LRGE_OK;
+        int kind = FX_FMT_EMPTY;
+        if (flags & (LRGE_GPU_INGEST_BAM | LRGE_GPU_INGEST_SAM)) { const int rc = kind_of(&kind); if (rc) return rc; }
+        if ((*yes = fx_kind_windowed(flags, kind))) run->attach(&blk);
+        return LRGE_OK;
+    }
+    // room for `more` bytes behind what blk holds
+    int room(u64 more) {
+        // (a block that moved was copied on the main stream, and its old bytes are the pool's again: other streams draw from it)
+        if (blk.keep_reserve(more)) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); return LRGE_OK; }
+        if (blk.keep_over) return over_cap();
+        LRGE_SET_ERR(ctx, "reads_open: device allocation of %llu bytes failed: %s", (unsigned long long)more, hipGetErrorString(blk.e));
+        return LRGE_ERR_DEVICE;
+    }
+    // behind every append to blk: the windows' turn; not 0: the code they stopped the call with
+    int appended() { return run->appended() ? (int)LRGE_OK : run->stopped(); }
+    // a resident text of `bytes` bytes: its block, the handle's from the start
+    int resident(u64 bytes) {
+        if (bytes > cap) return over_cap();
+        hipError_t e = hipSuccess;
+        R->n_text = bytes;
+        if ((R->d_text = (u8 *)ctx->pool.alloc((size_t)bytes + FX_PAD, &e))) return LRGE_OK;
+        LRGE_SET_ERR(ctx, "reads_open: device allocation of %llu bytes failed: %s", (unsigned long long)bytes, hipGetErrorString(e));
+        return LRGE_ERR_DEVICE;
+    }
+    // the text is complete in block b: it becomes the handle's
+    void hand_over(DevKeep &b) { R->d_text = b.keep; R->n_text = b.keep_len; b.keep = nullptr; }
+};
+
+// ---- the sources ----  the file's bytes are the text: one copy, or copies of a window's size
+static int fx_src_raw(FxSink &s, const u8 *d, u64 len) {
+    lrge_hip_ctx *ctx = s.ctx;
+    s.host_text = d;
+    bool windowed;
+    int rc = s.windowed(len, [&](int *kind) { return fx_kind(ctx, s.flags, d, nullptr, len, kind); }, &windowed);
+    if (rc) return rc;
+    if (!windowed) {
+        if ((rc = s.resident(len))) return rc;
+        if (len) HIPCHK(ctx, hipMemcpyAsync(s.R->d_text, d, (size_t)len, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        return LRGE_OK;
+    }
+    for (u64 off = 0; off < len; off += s.window) {
+        const u64 m = std::min<u64>(s.window, len - off);
+        if ((rc = s.room(m))) return rc;
+        HIPCHK(ctx, hipMemcpyAsync(s.blk.keep + s.blk.keep_len, d + off, (size_t)m, hipMemcpyHostToDevice, ctx->stream));
+        s.blk.keep_len += m;
+        if ((rc = s.appended())) return rc;
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    s.hand_over(s.blk);
+    return LRGE_OK;
+}
+
+// blocks `t` of BGZF file d decoded to dst + their o_off by the chunk pipeline of host_inflate.inl, every block checked
+static int fx_bgzf_decode(lrge_hip_ctx *ctx, const u8 *d, const std::vector<BgzfBlock> &t, u8 *dst) {
+    BgzfBad bad;
+    const int rc = bgzf_inflate_chunks(ctx, d, t, nullptr, dst, "reads_open: bgzf inflate", &bad);
+    if (rc) return rc;
+    if (bad.status != INF_OK) { ctx->err = "reads_open: a BGZF block failed its checks"; return LRGE_ERR_UNPROVEN; }
+    return LRGE_OK;
+}
+
+// BGZF (block table t, `total` text bytes): all blocks in one run of the pipeline, or runs of a window's size
+static int fx_src_bgzf(FxSink &s, const u8 *d, const std::vector<BgzfBlock> &t, u64 total) {
+    lrge_hip_ctx *ctx = s.ctx;
+    if (!(s.flags & LRGE_GPU_INFLATE_BGZF)) { ctx->err = "reads_open: BGZF input without LRGE_GPU_INFLATE_BGZF"; return LRGE_ERR_UNPROVEN; }
+    bool windowed;
+    int rc = s.windowed(total, [&](int *kind) -> int {      // the first blocks that hold four bytes of text are decoded for the sniff
+        std::vector<BgzfBlock> first;
+        u64 bytes = 0;
+        for (size_t i = 0; i < t.size() && bytes < 4; ++i) { first.push_back(t[i]); bytes += t[i].isize; }
+        Scratch sc(ctx);
+        ALLOC_OR_FAIL(d_first, sc, u8, bytes + FX_PAD);
+        const int drc = fx_bgzf_decode(ctx, d, first, d_first);
+        return drc ? drc : fx_kind(ctx, s.flags, nullptr, d_first, total, kind);
+    }, &windowed);
+    if (rc) return rc;
+    if (!windowed) return (rc = s.resident(total)) ? rc : fx_bgzf_decode(ctx, d, t, s.R->d_text);
+    // runs of blocks of a window's size, each decoded behind the tail the window before it left
+    for (size_t i = 0, j; i < t.size(); i = j) {
+        std::vector<BgzfBlock> part;
+        u64 bytes = 0;
+        for (j = i; j < t.size() && (j == i || bytes < s.window); ++j) {
+            part.push_back(t[j]);
+            part.back().o_off = s.blk.keep_len + bytes;
+            bytes += t[j].isize;
+        }
+        if ((rc = s.room(bytes)) || (rc = fx_bgzf_decode(ctx, d, part, s.blk.keep))) return rc;
+        s.blk.keep_len += bytes;
+        if ((rc = s.appended())) return rc;
+    }
+    s.hand_over(s.blk);
+    return LRGE_OK;
+}
+
+// gzip and bzip2: the rounds of the decoder's driver (run(&bad): gz_run, bz_run) with the decoder `dev` (GzDev, BzDev) keeping
+// every round's text in its own block (dev_keep.h), which becomes the handle's.  A windowed call flushes that block through the
+// sink's run whenever a round has been appended (DevKeep::keep_flush); whether its windows stay on is the first flush's sniff.
+// refused: the message for a stream the decoder does not take, with status(rc) and the file offset
+static_assert((int)GZ_RUN_OK == (int)BZ_RUN_OK && (int)GZ_RUN_DEVICE == (int)BZ_RUN_DEVICE, "one set of driver codes");
+template <class Dev, class Run, class Status>
+static int fx_inflate_to_device(FxSink &s, Dev &dev, Run run, const char *codec, const char *refused, Status status) {
+    lrge_hip_ctx *ctx = s.ctx;
     u64 bad = 0;
-    GzDev dev(ctx, cfg);
-    dev.keep_on = true; dev.keep_max = max_bytes; dev.keep_slack = FX_PAD;
-    // a first size: the last member's ISIZE (the whole text of a single-member file below 4 GiB); later rounds grow the block
-    if (comp_len >= 18) dev.keep_hint = std::min<u64>(max_bytes, bgzf_u32(comp + comp_len - 4));
-    if (run) fx_win_attach(run, &dev);
-    const int rc = dev.e == hipSuccess ? gz_run(dev, comp, comp_len, cfg, [&](const uint8_t *, uint64_t) { return true; }, st, &bad) : (int)GZ_RUN_DEVICE;
+    dev.keep_on = true; dev.keep_max = s.cap; dev.keep_slack = FX_PAD;
+    if (s.run) s.run->attach(&dev);
+    const int rc = dev.e == hipSuccess ? run(&bad) : (int)GZ_RUN_DEVICE;
     (void)hipStreamSynchronize(ctx->stream);
     if (rc == GZ_RUN_OK) {
         if (!dev.keep && !dev.keep_reserve(0)) { LRGE_SET_ERR(ctx, "reads_open: device allocation failed"); return LRGE_ERR_DEVICE; }
-        *d_text = dev.keep; *n_text = dev.keep_len; dev.keep = nullptr;
+        s.hand_over(dev);
         return LRGE_OK;
     }
-    if (run && fx_win_stopped(run)) return fx_win_stopped(run);
-    if (dev.keep_over) return fx_over_cap_rc(ctx, max_bytes);
+    if (s.run && s.run->stopped()) return s.run->stopped();
+    if (dev.keep_over) return s.over_cap();
     if (rc == GZ_RUN_DEVICE) {
-        LRGE_SET_ERR(ctx, "reads_open: gzip inflate: %s", hipGetErrorString(dev.e != hipSuccess ? dev.e : hipErrorUnknown));
+        LRGE_SET_ERR(ctx, "reads_open: %s inflate: %s", codec, hipGetErrorString(dev.e != hipSuccess ? dev.e : hipErrorUnknown));
         (void)hipGetLastError();
         return LRGE_ERR_DEVICE;
     }
-    LRGE_SET_ERR(ctx, "reads_open: gzip data not proven on the device (status %d near file offset %llu)", rc, (unsigned long long)bad);
+    LRGE_SET_ERR(ctx, refused, status(rc), (unsigned long long)bad);
     return LRGE_ERR_UNPROVEN;
+}
+
+// any other gzip input
+static int fx_src_gzip(FxSink &s, const u8 *d, u64 len) {
+    lrge_hip_ctx *ctx = s.ctx;
+    if (!(s.flags & LRGE_GPU_INFLATE_GZIP)) { ctx->err = "reads_open: gzip input without LRGE_GPU_INFLATE_GZIP"; return LRGE_ERR_UNPROVEN; }
+    const GzCfg cfg = gz_cfg(ctx);
+    GzStats st;
+    GzDev dev(ctx, cfg);
+    // a first size: the last member's ISIZE (the whole text of a single-member file below 4 GiB); later rounds grow the block
+    if (len >= 18) dev.keep_hint = std::min<u64>(s.cap, bgzf_u32(d + len - 4));
+    return fx_inflate_to_device(s, dev, [&](u64 *bad) { return gz_run(dev, d, len, cfg, [](const uint8_t *, uint64_t) { return true; }, st, bad); }, "gzip",
+                                "reads_open: gzip data not proven on the device (status %d near file offset %llu)", [](int rc) { return rc; });
+}
+
+static int fx_src_bzip2(FxSink &s, const u8 *d, u64 len) {
+    BzStats st;
+    BzDev dev(s.ctx);
+    return fx_inflate_to_device(s, dev, [&](u64 *bad) { return bz_run(dev, d, len, s.ctx->opt_u64("BZIP2_ROUND_BLOCKS", 0), [](const uint8_t *, uint64_t) { return true; }, st, bad); },
+                                "bzip2", "reads_open: bzip2 data not accepted by the device (%s near file offset %llu)", bz_status_name);
+}
+
+// ---- the two ends of a call ----  windows were flushed: the rest of the block is the last, the store the handle's text
+static int fx_finish_windowed(FxSink &s, double t0) {
+    lrge_hip_reads *R = s.R;
+    const int rc = s.run->finish();
+    if (rc) return rc;
+    R->ms[3] = (float)(fx_now_ms() - t0); R->ms[0] = R->ms[3] - R->ms[1] - R->ms[2];
+    if (s.ctx->opt("VERBOSE")) fprintf(stderr, "[lrge_hip] reads_open: %llu text bytes in %llu windows, %llu records, %llu store bytes; record scan %.2f ms, identifiers and lengths %.2f ms\n",
+                                       (unsigned long long)R->text_bytes, (unsigned long long)R->win.windows, (unsigned long long)R->n, (unsigned long long)R->n_text, R->ms[1], R->ms[2]);
+    return LRGE_OK;
+}
+
+// the text is resident: its kind by the sniff (the first bytes are here already for raw input), and the record scan over all of it
+static int fx_finish_resident(FxSink &s, double t0) {
+    lrge_hip_ctx *ctx = s.ctx;
+    lrge_hip_reads *R = s.R;
+    R->text_bytes = R->n_text;
+    const double t1 = fx_now_ms();
+    int kind;
+    int rc = fx_kind(ctx, s.flags, s.host_text, R->d_text, R->n_text, &kind);
+    if (rc || (rc = fx_parse_kind(ctx, R, kind))) return rc;
+    const double t2 = fx_now_ms();
+    R->ms[0] = (float)(t1 - t0); R->ms[1] = (float)(t2 - t1) - R->ms[2]; R->ms[3] = (float)(t2 - t0);
+    if (ctx->opt("VERBOSE")) fprintf(stderr, "[lrge_hip] reads_open: %llu text bytes, %llu records; text to HBM %.2f ms, record scan %.2f ms, identifiers and lengths %.2f ms\n",
+                                    (unsigned long long)R->n_text, (unsigned long long)R->n, R->ms[0], R->ms[1], R->ms[2]);
+    return LRGE_OK;
 }
 
 extern "C" void lrge_hip_reads_free(lrge_hip_reads *r) {
@@ -403,144 +593,22 @@ extern "C" int lrge_hip_reads_open_mem(lrge_hip_ctx *ctx, const void *file_bytes
     const double t0 = fx_now_ms();
     const u8 *d = (const u8 *)file_bytes;
     std::unique_ptr<lrge_hip_reads, void (*)(lrge_hip_reads *)> guard(new lrge_hip_reads(), lrge_hip_reads_free);
-    lrge_hip_reads *R = guard.get();
-    R->ctx = ctx;
-    const u64 cap = ingest_cap(ctx);
-    // LRGE_GPU_INGEST_WINDOWED: text larger than a window passes through the block in windows (fx_window.h)
-    const u64 window = std::max<u64>(1, ctx->opt_u64("INGEST_WINDOW_BYTES", std::min<u64>((u64)1 << 30, cap / 4)));
-    std::unique_ptr<FxWinRun> run;
-    if (flags & LRGE_GPU_INGEST_WINDOWED) run.reset(new FxWinRun(ctx, R, flags, cap, window));
-    // a source of the windowed call that appends to a block of the call's own: room for `more` bytes behind what it holds
-    DevKeep blk(ctx);
-    blk.keep_on = true; blk.keep_max = cap; blk.keep_slack = FX_PAD;
-    auto blk_room = [&](u64 more) -> int {
-        // (a block that moved was copied on the main stream, and its old bytes are the pool's again: other streams draw from it)
-        if (blk.keep_reserve(more)) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); return LRGE_OK; }
-        if (blk.keep_over) return fx_over_cap_rc(ctx, cap);
-        LRGE_SET_ERR(ctx, "reads_open: device allocation of %llu bytes failed: %s", (unsigned long long)more, hipGetErrorString(blk.e));
-        return LRGE_ERR_DEVICE;
-    };
-    hipError_t e = hipSuccess;
-    auto text_block = [&](u64 bytes) -> bool {
-        R->d_text = (u8 *)ctx->pool.alloc((size_t)bytes + FX_PAD, &e);
-        if (!R->d_text) LRGE_SET_ERR(ctx, "reads_open: device allocation of %llu bytes failed: %s", (unsigned long long)bytes, hipGetErrorString(e));
-        return R->d_text != nullptr;
-    };
+    guard->ctx = ctx;
+    FxSink s(ctx, guard.get(), flags);
+    // the source, by the file's magic
     const auto b = [&](u64 i) -> u32 { return i < len ? d[i] : 0x100u; };
-    bool raw_text = false;                      // the file's bytes are the text
-    if (b(0) == 0x1f && b(1) == 0x8b) {
-        std::vector<BgzfBlock> t;
-        uint64_t total = 0;
-        if (bgzf_scan_blocks(d, len, &t, &total)) {
-            if (!(flags & LRGE_GPU_INFLATE_BGZF)) { ctx->err = "reads_open: BGZF input without LRGE_GPU_INFLATE_BGZF"; return LRGE_ERR_UNPROVEN; }
-            BgzfBad bad;                        // the chunk pipeline of host_inflate.inl, decoding into the block
-            // BAM and SAM with their flags are not windowed without LRGE_GPU_INGEST_WINDOWED_ALN: the first blocks that hold four
-            // bytes of text are decoded for the sniff, and such a file takes the resident branch below exactly as without the
-            // windowed flag
-            bool windowed = run && total > window;
-            if (windowed && (flags & (LRGE_GPU_INGEST_BAM | LRGE_GPU_INGEST_SAM))) {
-                std::vector<BgzfBlock> first;
-                u64 bytes = 0;
-                for (size_t i = 0; i < t.size() && bytes < 4; ++i) { first.push_back(t[i]); bytes += t[i].isize; }
-                Scratch sc(ctx);
-                ALLOC_OR_FAIL(d_first, sc, u8, bytes + FX_PAD);
-                const int rc = bgzf_inflate_chunks(ctx, d, first, nullptr, d_first, "reads_open: bgzf inflate", &bad);
-                if (rc) return rc;
-                if (bad.status != INF_OK) { ctx->err = "reads_open: a BGZF block failed its checks"; return LRGE_ERR_UNPROVEN; }
-                u8 head[4] = {0, 0, 0, 0};
-                HIPCHK(ctx, hipMemcpyAsync(head, d_first, (size_t)std::min<u64>(4, bytes), hipMemcpyDeviceToHost, ctx->stream));
-                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-                bool is_bam, is_sam;
-                fx_sniff_bam_sam(flags, head, total, &is_bam, &is_sam);
-                windowed = !fx_stays_resident(flags, is_bam, is_sam);
-            }
-            if (windowed) {
-                // runs of blocks of a window's size, each decoded behind the tail the window before it left
-                run->attach(&blk);
-                for (size_t i = 0, j; i < t.size(); i = j) {
-                    std::vector<BgzfBlock> part;
-                    u64 bytes = 0;
-                    for (j = i; j < t.size() && (j == i || bytes < window); ++j) {
-                        part.push_back(t[j]);
-                        part.back().o_off = blk.keep_len + bytes;
-                        bytes += t[j].isize;
-                    }
-                    int rc = blk_room(bytes);
-                    if (rc) return rc;
-                    if ((rc = bgzf_inflate_chunks(ctx, d, part, nullptr, blk.keep, "reads_open: bgzf inflate", &bad))) return rc;
-                    if (bad.status != INF_OK) { ctx->err = "reads_open: a BGZF block failed its checks"; return LRGE_ERR_UNPROVEN; }
-                    blk.keep_len += bytes;
-                    if (!run->appended()) return run->stopped();
-                }
-                R->d_text = blk.keep; R->n_text = blk.keep_len; blk.keep = nullptr;
-            } else {
-                if (total > cap) return fx_over_cap_rc(ctx, cap);
-                if (!text_block(total)) return LRGE_ERR_DEVICE;
-                const int rc = bgzf_inflate_chunks(ctx, d, t, nullptr, R->d_text, "reads_open: bgzf inflate", &bad);
-                if (rc) return rc;
-                if (bad.status != INF_OK) { ctx->err = "reads_open: a BGZF block failed its checks"; return LRGE_ERR_UNPROVEN; }
-                R->n_text = total;
-            }
-        } else {
-            if (!(flags & LRGE_GPU_INFLATE_GZIP)) { ctx->err = "reads_open: gzip input without LRGE_GPU_INFLATE_GZIP"; return LRGE_ERR_UNPROVEN; }
-            const int rc = gzip_inflate_to_device(ctx, d, len, cap, &R->d_text, &R->n_text, run.get());
-            if (rc) return rc;
-        }
-    } else if (b(0) == 0x42 && b(1) == 0x5a && (flags & LRGE_GPU_INFLATE_BZIP2)) {
-        const int rc = bzip2_inflate_to_device(ctx, d, len, cap, FX_PAD, &R->d_text, &R->n_text, run.get());
-        if (rc) return rc;
-    } else if ((b(0) == 0x42 && b(1) == 0x5a) || (b(0) == 0x28 && b(1) == 0xb5 && b(2) == 0x2f && b(3) == 0xfd) ||
-               (b(0) == 0xfd && b(1) == 0x37 && b(2) == 0x7a && b(3) == 0x58 && b(4) == 0x5a)) {
+    std::vector<BgzfBlock> t;
+    uint64_t total = 0;
+    int rc;
+    if (b(0) == 0x1f && b(1) == 0x8b) rc = bgzf_scan_blocks(d, len, &t, &total) ? fx_src_bgzf(s, d, t, total) : fx_src_gzip(s, d, len);
+    else if (b(0) == 0x42 && b(1) == 0x5a && (flags & LRGE_GPU_INFLATE_BZIP2)) rc = fx_src_bzip2(s, d, len);
+    else if ((b(0) == 0x42 && b(1) == 0x5a) || (b(0) == 0x28 && b(1) == 0xb5 && b(2) == 0x2f && b(3) == 0xfd) ||
+             (b(0) == 0xfd && b(1) == 0x37 && b(2) == 0x7a && b(3) == 0x58 && b(4) == 0x5a)) {
         ctx->err = "reads_open: bzip2, zstd and xz input is decompressed on the host";
-        return LRGE_ERR_UNPROVEN;
-    } else if (run && len > window && [&] { bool is_bam, is_sam; fx_sniff_bam_sam(flags, d, len, &is_bam, &is_sam); return !fx_stays_resident(flags, is_bam, is_sam); }()) {
-        run->attach(&blk);                      // copies of a window's size (BAM and SAM that stay resident: the branch below)
-        for (u64 off = 0; off < len; off += window) {
-            const u64 m = std::min<u64>(window, len - off);
-            const int rc = blk_room(m);
-            if (rc) return rc;
-            HIPCHK(ctx, hipMemcpyAsync(blk.keep + blk.keep_len, d + off, (size_t)m, hipMemcpyHostToDevice, ctx->stream));
-            blk.keep_len += m;
-            if (!run->appended()) return run->stopped();
-        }
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        R->d_text = blk.keep; R->n_text = blk.keep_len; blk.keep = nullptr; raw_text = !run->win.st.windows;
-    } else {
-        if (len > cap) return fx_over_cap_rc(ctx, cap);
-        if (!text_block(len)) return LRGE_ERR_DEVICE;
-        if (len) HIPCHK(ctx, hipMemcpyAsync(R->d_text, d, (size_t)len, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        R->n_text = len; raw_text = true;
-    }
-    if (run && run->win.st.windows) {           // windows were flushed: the rest of the block is the last, the store the handle's text
-        u8 *rest = R->d_text;
-        const u64 n_rest = R->n_text;
-        R->d_text = nullptr; R->n_text = 0;
-        const int rc = run->finish(rest, n_rest);
-        if (rc) return rc;
-        R->ms[3] = (float)(fx_now_ms() - t0); R->ms[0] = R->ms[3] - R->ms[1] - R->ms[2];
-        if (ctx->opt("VERBOSE")) fprintf(stderr, "[lrge_hip] reads_open: %llu text bytes in %llu windows, %llu records, %llu store bytes; record scan %.2f ms, identifiers and lengths %.2f ms\n",
-                                        (unsigned long long)R->text_bytes, (unsigned long long)R->win.windows, (unsigned long long)R->n, (unsigned long long)R->n_text, R->ms[1], R->ms[2]);
-        *out = guard.release();
-        return LRGE_OK;
-    }
-    R->text_bytes = R->n_text;
-    const double t1 = fx_now_ms();
-    // BAM and SAM by their magic, when the caller asked for them: the first text bytes are here already for raw input
-    bool is_bam = false, is_sam = false;
-    if ((flags & (LRGE_GPU_INGEST_BAM | LRGE_GPU_INGEST_SAM)) && R->n_text >= 3) {
-        u8 head[4] = {0, 0, 0, 0};
-        const size_t k = (size_t)std::min<u64>(4, R->n_text);
-        if (raw_text) memcpy(head, d, k);
-        else { HIPCHK(ctx, hipMemcpyAsync(head, R->d_text, k, hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); }
-        fx_sniff_bam_sam(flags, head, R->n_text, &is_bam, &is_sam);
-    }
-    const int rc = is_bam ? bam_parse_device(ctx, R) : is_sam ? sam_parse_device(ctx, R) : fx_parse_device(ctx, R);
+        rc = LRGE_ERR_UNPROVEN;
+    } else rc = fx_src_raw(s, d, len);
     if (rc) return rc;
-    const double t2 = fx_now_ms();
-    R->ms[0] = (float)(t1 - t0); R->ms[1] = (float)(t2 - t1) - R->ms[2]; R->ms[3] = (float)(t2 - t0);
-    if (ctx->opt("VERBOSE")) fprintf(stderr, "[lrge_hip] reads_open: %llu text bytes, %llu records; text to HBM %.2f ms, record scan %.2f ms, identifiers and lengths %.2f ms\n",
-                                    (unsigned long long)R->n_text, (unsigned long long)R->n, R->ms[0], R->ms[1], R->ms[2]);
+    if ((rc = s.run && s.run->win.st.windows ? fx_finish_windowed(s, t0) : fx_finish_resident(s, t0))) return rc;
     *out = guard.release();
     return LRGE_OK;
 }

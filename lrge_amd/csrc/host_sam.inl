@@ -12,21 +12,11 @@ static int sam_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R, FxWinScan *w) 
     R->name_off.assign(1, 0);
     hipStream_t st = ctx->stream;
     Scratch sc(ctx);
-    ctx->pin_items.clear(); ctx->pin_used = 0;
-    const u64 n_tiles = div_up(n, FX_TILE);
-    if (n_tiles >> 31) return fx_verdict_rc(ctx, FX_UNPROVEN, "text of 8 TiB or more");
     // the line starts, as for FASTQ
-    ALLOC_OR_FAIL(c_lf, sc, u32, n_tiles);
-    ALLOC_OR_FAIL(c_rem, sc, u32, n_tiles);
-    ALLOC_OR_FAIL(c_hdr, sc, u32, n_tiles);
-    ALLOC_OR_FAIL(d_sum, sc, FxSummary, 1);
-    hipLaunchKernelGGL(k_fx_census, dim3((u32)n_tiles), dim3(FX_THREADS), 0, st, t, n, c_lf, c_rem, c_hdr);
-    KCHK(ctx);
-    hipLaunchKernelGGL(k_fx_summary, dim3(1), dim3(FX_THREADS), 0, st, t, n, (const u32 *)c_lf, (const u32 *)c_rem, (const u32 *)c_hdr, n_tiles, d_sum);
-    KCHK(ctx);
-    FxSummary hs;
-    HIPCHK(ctx, ctx->d2h(&hs, d_sum, sizeof hs, st));
-    HIPCHK(ctx, ctx->d2h_sync(st));
+    FxTiles tl;
+    int rc = fx_census_device(ctx, sc, t, n, &tl);
+    if (rc) return rc;
+    const auto &[n_tiles, c_lf, c_rem, c_hdr, hs] = tl;
     FxCensus c;
     memset(&c, 0, sizeof c);
     c.n_lf = hs.n_lf; c.first = hs.first; c.last = hs.last;
@@ -34,7 +24,6 @@ static int sam_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R, FxWinScan *w) 
     if (!verdict && (c.n_lf + 1) >> 32) verdict = FX_UNPROVEN;
     if (verdict) return fx_verdict_rc(ctx, verdict, "line count");
     const u64 n_lines = c.n_lf + 1;                         // (the last one is empty when the text ends with a line feed)
-    int rc;
     if ((rc = scan_exclusive_u32(ctx, sc, c_lf, c_lf, n_tiles, nullptr))) return rc;
     ALLOC_OR_FAIL(ls, sc, u64, n_lines);
     ALLOC_OR_FAIL(d_lines, sc, u64, 2);
@@ -55,24 +44,19 @@ static int sam_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R, FxWinScan *w) 
     hipLaunchKernelGGL(k_sam_mark, dim3((u32)div_up(n_lines, SAM_THREADS)), dim3(SAM_THREADS), 0, st, t, n, (const u64 *)ls, c.n_lf, n_lines, d_mark);
     KCHK(ctx);
     if ((rc = scan_exclusive_u32(ctx, sc, d_mark, d_rank, n_lines, (u32 *)(d_flags + 2)))) return rc;
-    u64 flags[3] = {0, 0, 0};
-    HIPCHK(ctx, ctx->d2h(flags + 2, d_flags + 2, 8, st));
+    u64 n_rec = 0, name_bytes = 0;
+    HIPCHK(ctx, ctx->d2h(&n_rec, d_flags + 2, 8, st));
     HIPCHK(ctx, ctx->d2h_sync(st));
-    const u64 n_rec = flags[2];
     if (!n_rec) { R->fmt = FX_FMT_SAM; return LRGE_OK; }    // header lines only: the host returns no record
-    hipError_t e = hipSuccess;
-    if (!(R->d_recs = (FxRec *)ctx->pool.alloc((size_t)n_rec * sizeof(FxRec), &e))) { LRGE_SET_ERR(ctx, "reads_open: record table: %s", hipGetErrorString(e)); return LRGE_ERR_DEVICE; }
+    if ((rc = fx_alloc_recs(ctx, R, n_rec))) return rc;
     ALLOC_OR_FAIL(d_seq_len, sc, u32, n_rec);
     ALLOC_OR_FAIL(d_name_len, sc, u32, n_rec);
     const u32 grid = (u32)std::min<u64>(div_up(n_lines, SAM_WAVES), (u64)ctx->n_cu * 8);
     hipLaunchKernelGGL(k_sam_records, dim3(grid), dim3(SAM_THREADS), 0, st, t, n, (const u64 *)ls, c.n_lf, n_lines, (const u32 *)d_mark, (const u32 *)d_rank, R->d_recs,
                        d_seq_len, d_name_len, (u32 *)d_flags, (unsigned long long *)(d_flags + 1));
     KCHK(ctx);
-    HIPCHK(ctx, ctx->d2h(flags, d_flags, 16, st));
-    HIPCHK(ctx, ctx->d2h_sync(st));
-    if ((u32)flags[0]) return fx_verdict_rc(ctx, (u32)flags[0], "a SAM record line outside the strict form");
-    if (flags[1] >> 32) return fx_verdict_rc(ctx, FX_UNPROVEN, "4 GiB of identifiers or more");
+    if ((rc = fx_flags_back(ctx, d_flags, "a SAM record line outside the strict form", &name_bytes))) return rc;
     R->fmt = FX_FMT_SAM;                                    // (a refused file leaves no read set, so no format either)
-    if ((rc = fx_tables_to_host(ctx, R, sc, n_rec, d_seq_len, d_name_len, flags[1])) || !w) return rc;
+    if ((rc = fx_tables_to_host(ctx, R, sc, n_rec, d_seq_len, d_name_len, name_bytes)) || !w) return rc;
     return w->dev->store_window(sc, *R, d_seq_len, n);
 }

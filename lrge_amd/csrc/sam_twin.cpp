@@ -11,8 +11,9 @@
 #include <vector>
 
 #include "sam_core.h"
-#include "fx_window.h"
+#include "win_twin.h"
 
+namespace sam_twin {             // (a name of its own: tools/window_twin_check.cpp holds the three twins in one translation unit)
 namespace {
 std::vector<FxRec> g_recs;
 
@@ -106,41 +107,22 @@ int parse(const uint8_t *t, uint64_t n, uint64_t *cut) {
     return 0;
 }
 
-// ---- the windowed ingest: fx_window.h over the passes above ----
-struct WinOut {
-    std::vector<FxRec> recs;            // name_off: in the whole text; seq_off: in `store`; seq_span = seq_len
-    std::vector<uint8_t> store;
-    FxWinStats st = {0, 0, 0, 0};
-};
-WinOut gw;
-
-struct WinTwin {
-    std::vector<uint8_t> blk;
-    uint64_t base = 0;                  // where the block starts in the whole text
-    uint64_t len() const { return blk.size(); }
-    int resident_format(bool *yes) const { *yes = false; return 0; }
-    void resident_again() const {}
-    int unproven(const char *) const { return (int)FX_UNPROVEN; }
-    int flush(bool first, bool end, uint64_t *cut, int *fmt) {
+// ---- the windowed ingest: win_twin.h over the passes above ----
+struct Scan {
+    int scan(const std::vector<uint8_t> &blk, bool first, bool end, uint64_t *cut, int *fmt) {
         if (first && !sam_sniff(blk.data(), blk.size())) return (int)FX_UNPROVEN;     // (later windows are SAM by the run, not by their first bytes)
         uint64_t c = 0;
         const int rc = parse(blk.data(), blk.size(), end ? nullptr : &c);
-        if (rc) return rc;
         *cut = end ? blk.size() : c;
         *fmt = FX_FMT_SAM;
-        if (!*cut) return 0;
-        for (const FxRec &r : g_recs) {
-            gw.recs.push_back(FxRec{base + r.name_off, gw.store.size(), r.seq_len, r.name_len, r.seq_len});
-            gw.store.insert(gw.store.end(), blk.data() + r.seq_off, blk.data() + r.seq_off + r.seq_len);
-        }
-        return 0;
+        return rc;
     }
-    int carry(uint64_t cut) {
-        blk.erase(blk.begin(), blk.begin() + (long)cut);
-        base += cut;
-        return 0;
+    const std::vector<FxRec> &recs() const { return g_recs; }
+    void append(const std::vector<uint8_t> &blk, uint64_t, const FxRec &r, std::vector<uint8_t> &store) const {
+        store.insert(store.end(), blk.data() + r.seq_off, blk.data() + r.seq_off + r.seq_len);
     }
 };
+WinTwinOut gw;
 }  // namespace
 
 extern "C" {
@@ -152,38 +134,24 @@ int sam_twin_parse(const uint8_t *t, uint64_t n) {
     return parse(t, n, nullptr);
 }
 
-// The text through the windows of fx_window.h: `piece` bytes appended per step, a flush once the block holds `window` bytes (the
-// driver waits for the four bytes of the sniff).  0: proven, FX_UNPROVEN, FX_TOO_MANY; the records by sam_twin_windowed_count /
-// _table / _seq, the counts by _stats (windows flushed first: 0 means the text ended before its first flush and was scanned
-// whole, as without windows, and no store was kept)
+// The text through the windows of fx_window.h (win_twin_run; the driver waits for the four bytes of the sniff).  0: proven,
+// FX_UNPROVEN, FX_TOO_MANY; the records by sam_twin_windowed_count / _table / _seq, the counts by _stats (windows flushed first: 0
+// means the text ended before its first flush and was scanned whole, as without windows, and no store was kept)
 int sam_twin_windowed(const uint8_t *t, uint64_t n, uint64_t window, uint64_t piece) {
-    gw = WinOut();
+    gw = WinTwinOut();
     if (!piece) return -1;
-    WinTwin b;
-    FxWindow<WinTwin> win(b, window);
-    int rc = 0;
-    for (uint64_t p = 0; p < n && !rc; p += piece) {
-        b.blk.insert(b.blk.end(), t + p, t + (n - p < piece ? n : p + piece));
-        rc = win.step(false);
-    }
-    uint64_t all = 0;
-    if (!rc) rc = win.st.windows ? win.step(true) : b.flush(true, true, &all, &win.fmt);         // (or the resident scan)
-    if (rc) { gw = WinOut(); return rc; }
-    gw.st = win.st; gw.st.bases = win.st.windows ? gw.store.size() : 0;
-    return 0;
+    Scan sc;
+    return win_twin_run(sc, t, n, window, piece, false, gw);
 }
 
 uint64_t sam_twin_windowed_count(void) { return gw.recs.size(); }
-void sam_twin_windowed_table(FxRec *out) { if (!gw.recs.empty()) memcpy(out, gw.recs.data(), gw.recs.size() * sizeof(FxRec)); }
-void sam_twin_windowed_stats(uint64_t out[4]) { out[0] = gw.st.windows; out[1] = gw.st.bases; out[2] = gw.st.max_window; out[3] = gw.st.carried; }
-uint64_t sam_twin_windowed_store(uint8_t *out) { if (out && !gw.store.empty()) memcpy(out, gw.store.data(), gw.store.size()); return gw.store.size(); }
-uint64_t sam_twin_windowed_seq(uint64_t i, uint8_t *out) {
-    const FxRec &r = gw.recs[i];
-    if (r.seq_len) memcpy(out, gw.store.data() + r.seq_off, r.seq_len);
-    return r.seq_len;
-}
+void sam_twin_windowed_table(FxRec *out) { gw.table(out); }
+void sam_twin_windowed_stats(uint64_t out[4]) { gw.stats(out); }
+uint64_t sam_twin_windowed_store(uint8_t *out) { return gw.store_to(out, gw.store.size()); }
+uint64_t sam_twin_windowed_seq(uint64_t i, uint8_t *out) { return gw.seq(i, out); }
 
 uint64_t sam_twin_count(void) { return g_recs.size(); }
 void sam_twin_table(FxRec *out) { if (!g_recs.empty()) memcpy(out, g_recs.data(), g_recs.size() * sizeof(FxRec)); }
 
 }  // extern "C"
+}  // namespace sam_twin
