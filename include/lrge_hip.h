@@ -523,6 +523,31 @@ int      lrge_hip_seqset_from_reads(lrge_hip_ctx *ctx, const lrge_hip_reads *rea
                                     const uint32_t *name_rank, lrge_hip_seqset **out);
 void     lrge_hip_reads_free(lrge_hip_reads *reads);
 
+/* Identifier ranks on the device (k_nl_key, k_nl_heads, k_nl_starts, k_nl_rank between radix_sort_pairs and
+   scan_exclusive_u32): the `name_rank` every upload takes, i.e. the stand-in for the reference's name comparisons -- the duplicate
+   check of all-vs-all (ava.rs:195-199), the self-overlap test and the pair key (ava.rs:369-382), the target names counted once per
+   query and the duplicate check of the inverse direction (twoset.rs:286-302, 439-449) -- computed by a fixed number of stable LSD
+   sorts instead of a comparison sort on one host thread.
+   lrge_hip_name_ranks (ava.rs:369-382): `names` and name_off[n_names + 1] are laid out as lrge_hip_reads_table returns them
+   (identifier i is names[name_off[i], name_off[i + 1])).  idx[0..n): the selected identifiers (any order, repeats allowed); idx == NULL
+   means every identifier in order, and n must then equal n_names (else LRGE_ERR_INVALID; n == 0 is an empty selection either way).  rank_out[i]: the rank of idx[i] among
+   the n selected entries -- the number of selected entries whose identifier is strictly smaller, byte-wise on unsigned bytes, a
+   proper prefix being smaller; equal identifiers (a repeated index included) share a rank.  Two sets that meet in one call are
+   ranked by concatenating their index lists, queries then targets, and splitting rank_out.  The host gathers only the selected
+   identifiers into one padded block, so the transfer is proportional to the selection, not to the file; one sort by length and
+   one 64-bit sort per 8 bytes of the longest selected identifier follow, and the ranks come back in one transfer at the end.
+   n < 2 returns without touching the device.  stats (may be NULL): [0] sorts run, [1] W = ceil(longest selected identifier / 8),
+   [2] distinct identifiers among the selection, [3] microseconds of the call.
+   LRGE_ERR_TOO_MANY: n >= 2^32.  LRGE_ERR_INVALID: an idx entry out of range, offsets that are not monotone, an identifier of 2^32
+   bytes or more.  LRGE_ERR_UNPROVEN: the longest selected identifier exceeds option NAME_RANK_MAX_BYTES (default 256: the cost is
+   W + 1 sorts of all entries, so one long identifier must not stretch it without bound); the caller takes its host sort.
+   LRGE_ERR_DEVICE: a runtime failure, memory that cannot be had.
+   lrge_hip_reads_name_ranks (twoset.rs:286-302, 439-449): the same over the identifiers a lrge_hip_reads handle keeps on the host
+   (resident or windowed alike), in the handle's own context; idx indexes the handle's records. */
+int  lrge_hip_name_ranks(lrge_hip_ctx *ctx, const char *names, const uint64_t *name_off, uint64_t n_names,
+                         const uint32_t *idx, uint64_t n, uint32_t *rank_out, uint64_t stats[4]);
+int  lrge_hip_reads_name_ranks(const lrge_hip_reads *reads, const uint32_t *idx, uint64_t n, uint32_t *rank_out, uint64_t stats[4]);
+
 /* Host only: which side packs the reads of a set that starts in host memory when `ranks_on_host` ranks share this host's CPUs (option
    LRGE_HIP_RANKS_ON_HOST, set by the launcher; LRGE_HIP_PACK = host | device overrides): 1 = the host (2-bit pack with AVX2, packed words
    over PCIe), 0 = the device (ASCII over the rank's own PCIe link, k_pack).  *granted_cpus (may be NULL) receives the CPUs the host

@@ -150,6 +150,36 @@ inline std::vector<std::vector<uint32_t>> name_ranks(const std::vector<std::vect
     }
     return out;
 }
+// the same ranks computed on the device (lrge_hip_name_ranks): the names of all lists back to back, ranked as
+// one selection and split again.  A name the device form does not take throws LrgeError with code LRGE_ERR_UNPROVEN.
+inline std::vector<std::vector<uint32_t>> name_ranks_device(Ctx &c, const std::vector<std::vector<const std::string *>> &lists) {
+    std::string blob;
+    std::vector<uint64_t> off(1, 0);
+    for (auto &l : lists) for (auto *s : l) { blob += *s; off.push_back(blob.size()); }
+    const uint64_t n = off.size() - 1;
+    std::vector<uint32_t> ranks(n ? n : 1);
+    c.check(lrge_hip_name_ranks(c.h, blob.data(), off.data(), n, nullptr, n, ranks.data(), nullptr));
+    std::vector<std::vector<uint32_t>> out(lists.size());
+    size_t k = 0;
+    for (size_t l = 0; l < lists.size(); ++l) { out[l].assign(ranks.begin() + (std::ptrdiff_t)k, ranks.begin() + (std::ptrdiff_t)(k + lists[l].size())); k += lists[l].size(); }
+    return out;
+}
+// what a strategy calls: the device form when asked for, the host sort when not or when the device form hands the names back
+// (LRGE_ERR_UNPROVEN only); note (may be empty) hears which of the two ran
+inline std::vector<std::vector<uint32_t>> name_ranks_by(Ctx &c, bool on_device, const std::function<void(bool)> &note,
+                                                        const std::vector<std::vector<const std::string *>> &lists) {
+    if (on_device) {
+        try {
+            auto r = name_ranks_device(c, lists);
+            if (note) note(true);
+            return r;
+        } catch (const LrgeError &e) {
+            if (e.code != LRGE_ERR_UNPROVEN) throw;
+        }
+        if (note) note(false);
+    }
+    return name_ranks(lists);
+}
 // lib.rs:189-204: StdRng::seed_from_u64 + rand::seq::index::sample, restated in lrge_rand.hpp
 using ::lrge::unique_random_set;
 }  // namespace detail
@@ -236,6 +266,8 @@ public:
     int device = 0;
     std::vector<std::string> warnings;
     std::vector<std::string> *paf_sink = nullptr;   // when set, receives the lines of overlaps.paf (the reference always writes it)
+    bool device_name_ranks = false;                 // name ranks by lrge_hip_name_ranks (opt-in; the host sort when the device hands them back)
+    std::function<void(bool)> name_ranks_note;      // hears whether the device (true) or the host computed them, when device_name_ranks is set
 
     explicit TwoSetStrategy(const Reads &r) : input(&r) {}
     explicit TwoSetStrategy(const DeviceReads &r) : dev_input(&r) {}
@@ -276,9 +308,9 @@ public:
         std::vector<const std::string *> tn, ts, qn, qs;
         for (size_t i : t) { tn.push_back(&names_in()[i]); if (input) ts.push_back(&input->seqs[i]); }
         for (size_t i : q) { qn.push_back(&names_in()[i]); if (input) qs.push_back(&input->seqs[i]); }
-        auto ranks = detail::name_ranks({qn, tn});
         std::shared_ptr<detail::Ctx> ctx_own = dev_input ? dev_input->ctx : std::make_shared<detail::Ctx>(device);
         detail::Ctx &ctx = *ctx_own;
+        auto ranks = detail::name_ranks_by(ctx, device_name_ranks, name_ranks_note, {qn, tn});
         detail::SeqSet Q(ctx, dev_input, q, qs, ranks[0]), T(ctx, dev_input, t, ts, ranks[1]);
         const int preset = platform == Platform::PacBio ? LRGE_PRESET_AVA_PB : LRGE_PRESET_AVA_ONT;
         lrge_hip_params p{remove_internal ? 1 : 0, max_overhang_ratio};
@@ -311,7 +343,9 @@ class Builder {   // twoset/builder.rs:22-185
     std::optional<uint64_t> seed_;
     Platform platform_ = Platform::Nanopore;
     int device_ = 0;
+    bool device_name_ranks_ = false;
 public:
+    Builder &device_name_ranks(bool f) { device_name_ranks_ = f; return *this; }
     Builder &target_num_reads(size_t n) { t_ = n; return *this; }
     Builder &query_num_reads(size_t n) { q_ = n; return *this; }
     Builder &remove_internal(bool f, float ratio) { remove_internal_ = f; if (f) ratio_ = ratio; return *this; }
@@ -325,6 +359,7 @@ public:
     TwoSetStrategy configure(TwoSetStrategy s) const {
         s.target_num_reads = t_; s.query_num_reads = q_; s.remove_internal = remove_internal_; s.max_overhang_ratio = ratio_;
         s.use_min_ref = use_min_ref_; s.threads = threads_; s.seed = seed_; s.platform = platform_; s.device = device_;
+        s.device_name_ranks = device_name_ranks_;
         return s;
     }
 };
@@ -348,6 +383,8 @@ public:
     int device = 0;
     std::vector<std::string> warnings;
     std::vector<std::string> *paf_sink = nullptr;
+    bool device_name_ranks = false;                 // as TwoSetStrategy::device_name_ranks
+    std::function<void(bool)> name_ranks_note;
 
     explicit AvaStrategy(const Reads &r) : input(&r) {}
     explicit AvaStrategy(const DeviceReads &r) : dev_input(&r) {}
@@ -372,9 +409,9 @@ public:
             num_bases += dev_input ? dev_input->lens[i] : input->seqs[i].size();
         }
         // ava.rs:369-382 + :165-366
-        auto ranks = detail::name_ranks({rn});
         std::shared_ptr<detail::Ctx> ctx_own = dev_input ? dev_input->ctx : std::make_shared<detail::Ctx>(device);
         detail::Ctx &ctx = *ctx_own;
+        auto ranks = detail::name_ranks_by(ctx, device_name_ranks, name_ranks_note, {rn});
         detail::SeqSet R(ctx, dev_input, ri, rs, ranks[0]);
         const int preset = platform == Platform::PacBio ? LRGE_PRESET_AVA_PB : LRGE_PRESET_AVA_ONT;
         ctx.check(lrge_hip_seqset_presketch(ctx.h, R.h, preset));
@@ -400,7 +437,9 @@ class Builder {   // ava/builder.rs:19-153
     std::optional<uint64_t> seed_;
     Platform platform_ = Platform::Nanopore;
     int device_ = 0;
+    bool device_name_ranks_ = false;
 public:
+    Builder &device_name_ranks(bool f) { device_name_ranks_ = f; return *this; }
     Builder &num_reads(size_t n) { n_ = n; return *this; }
     Builder &remove_internal(bool f, float ratio) { remove_internal_ = f; if (f) ratio_ = ratio; return *this; }
     Builder &threads(size_t n) { threads_ = n; return *this; }
@@ -412,6 +451,7 @@ public:
     AvaStrategy configure(AvaStrategy s) const {
         s.num_reads = n_; s.remove_internal = remove_internal_; s.max_overhang_ratio = ratio_; s.threads = threads_;
         s.seed = seed_; s.platform = platform_; s.device = device_;
+        s.device_name_ranks = device_name_ranks_;
         return s;
     }
 };

@@ -40,6 +40,7 @@ EXPORTS = [
     "lrge_hip_gzip_inflate", "lrge_hip_read_records_gpu_ex", "lrge_hip_bzip2_inflate",
     "lrge_hip_reads_open", "lrge_hip_reads_open_mem", "lrge_hip_reads_count", "lrge_hip_reads_name_bytes", "lrge_hip_reads_text_bytes",
     "lrge_hip_reads_table", "lrge_hip_reads_timings", "lrge_hip_reads_bam_stats", "lrge_hip_reads_window_stats", "lrge_hip_seqset_from_reads", "lrge_hip_reads_free",
+    "lrge_hip_name_ranks", "lrge_hip_reads_name_ranks",
     "lrge_hip_index_build", "lrge_hip_index_build_for", "lrge_hip_index_build_sharded", "lrge_hip_index_build_tsharded", "lrge_hip_last_shard_stats", "lrge_hip_index_free",
     "lrge_hip_comm_alltoallv", "lrge_hip_comm_rccl_ranks", "lrge_hip_comm_rccl_ops", "lrge_hip_comm_local_group_serialize", "lrge_hip_comm_local_turn",
     "lrge_hip_comm_busy_ms", "lrge_hip_comm_standin_ms",
@@ -118,6 +119,8 @@ def lib():
     L.lrge_hip_reads_bam_stats.argtypes = [vp, C.POINTER(C.c_uint64 * len(BAM_STAT_NAMES))]
     L.lrge_hip_reads_window_stats.argtypes = [vp, C.POINTER(C.c_uint64 * 4)]
     L.lrge_hip_seqset_from_reads.argtypes = [vp, vp, vp, C.c_uint32, vp, C.POINTER(vp)]
+    L.lrge_hip_name_ranks.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp]
+    L.lrge_hip_reads_name_ranks.argtypes = [vp, vp, C.c_uint64, vp, vp]
     L.lrge_hip_reads_free.argtypes = [vp]
     L.lrge_hip_reads_free.restype = None
     L.lrge_hip_pack_choice.argtypes = [C.c_int, C.POINTER(C.c_double)]

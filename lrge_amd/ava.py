@@ -5,7 +5,7 @@ import numpy as np
 
 from . import _ffi, engine, readio
 from .estimate import Estimate, LrgeError
-from .twoset import PLATFORM_PRESET, unique_random_set
+from .twoset import PLATFORM_PRESET, ranks_for, unique_random_set
 
 log = logging.getLogger("lrge_amd")
 
@@ -19,6 +19,7 @@ class Builder:
         self._n = DEFAULT_AVA_NUM_READS
         self._remove_internal, self._ratio = False, 0.2
         self._threads, self._tmpdir, self._seed, self._platform, self._device = 1, None, None, "ont", 0
+        self._device_name_ranks = False
 
     def num_reads(self, n): self._n = int(n); return self
     def remove_internal(self, flag, max_overhang_ratio=0.2):
@@ -31,14 +32,17 @@ class Builder:
     def seed(self, s): self._seed = s; return self
     def platform(self, p): self._platform = str(p).lower(); return self
     def device(self, d): self._device = int(d); return self
+    def device_name_ranks(self, flag): self._device_name_ranks = bool(flag); return self   # name ranks by Context.name_ranks (opt-in)
 
     def build(self, input_):
         return AvaStrategy(input_, self)
 
 
 class AvaStrategy(Estimate):
-    def __init__(self, input_, builder=None):
+    def __init__(self, input_, builder=None, device_name_ranks=None):
         b = builder or Builder()
+        self.device_name_ranks = b._device_name_ranks if device_name_ranks is None else bool(device_name_ranks)
+        self.name_ranks_by = None
         self.input, self.num_reads = input_, b._n
         self.remove_internal, self.max_overhang_ratio = b._remove_internal, b._ratio
         self.threads, self.seed, self.platform, self.device = b._threads, b._seed, b._platform, b._device
@@ -70,7 +74,7 @@ class AvaStrategy(Estimate):
         ctx = engine.Context(self.device)
         R = ix = None
         try:
-            (ranks,) = engine.name_ranks(rn)
+            (ranks,), self.name_ranks_by = ranks_for(ctx, self.device_name_ranks, rn)
             R = ctx.upload(*readio.pack(rs), ranks)
             try:
                 R.presketch(preset)

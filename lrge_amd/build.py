@@ -46,6 +46,7 @@ BAM_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_bam_twin.so")
 SAM_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_sam_twin.so")
 NAMES_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_names_twin.so")
 BZIP2_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_bzip2_twin.so")
+NAMES_LSD_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_names_lsd_twin.so")
 
 
 def _build_twin(out, main, force):
@@ -59,14 +60,16 @@ def _build_twin(out, main, force):
 
 
 def build_twin(force=False):
-    """The host twins, all seven: of k_inflate (csrc/inflate_twin.cpp, the same bit-level core), and of the speculative gzip
+    """The host twins, all eight: of k_inflate (csrc/inflate_twin.cpp, the same bit-level core), and of the speculative gzip
     decode (build_gzip_twin), of the FASTA / FASTQ record scan (build_fastx_twin), of the BAM record scan (build_bam_twin), of
-    the SAM record scan (build_sam_twin), of the identifier ranking (build_names_twin) and of the bzip2 decode (build_bzip2_twin)."""
+    the SAM record scan (build_sam_twin), of the identifier ranking by refinement (build_names_twin) and by fixed LSD passes (build_names_lsd_twin)
+    and of the bzip2 decode (build_bzip2_twin)."""
     build_gzip_twin(force)
     build_fastx_twin(force)
     build_bam_twin(force)
     build_sam_twin(force)
     build_names_twin(force)
+    build_names_lsd_twin(force)
     build_bzip2_twin(force)
     return _build_twin(TWIN_PATH, "inflate_twin.cpp", force)
 
@@ -94,6 +97,12 @@ def build_sam_twin(force=False):
 def build_names_twin(force=False):
     """The identifier ranking by radix refinement as host code (csrc/names_twin.cpp over csrc/name_core.h)."""
     return _build_twin(NAMES_TWIN_PATH, "names_twin.cpp", force)
+
+
+def build_names_lsd_twin(force=False):
+    """The host twin of the device identifier ranking (csrc/names_lsd_twin.cpp over csrc/name_lsd.h and the pass loop of
+    csrc/name_lsd_round.h), and the host sort it is measured against (names_lsd_host_sort_ranks)."""
+    return _build_twin(NAMES_LSD_TWIN_PATH, "names_lsd_twin.cpp", force)
 
 
 def build_bzip2_twin(force=False):

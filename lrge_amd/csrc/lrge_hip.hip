@@ -231,3 +231,4 @@ extern "C" int lrge_hip_last_counters(const lrge_hip_ctx *ctx, uint64_t c[LRGE_C
 #include "host_gzip.inl"
 #include "host_bzip2.inl"
 #include "host_fastx.inl"
+#include "host_names.inl"

@@ -115,6 +115,45 @@ class Context:
         prove raises UnprovenInput: read the file with the host readers (readio.load) instead."""
         return DeviceReads(self, path_or_bytes, flags)
 
+    def _name_ranks(self, blob, name_off, n_names, idx_lists):
+        """lrge_hip_name_ranks over a table of identifiers; idx_lists None: every identifier in order, as one list"""
+        if idx_lists is None:
+            idx, n, sizes = None, n_names, [n_names]
+        else:
+            parts = [np.ascontiguousarray(ix, dtype=np.uint32).ravel() for ix in idx_lists]
+            sizes = [int(p.size) for p in parts]
+            idx = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint32)
+            n = int(idx.size)
+        out = np.zeros(max(n, 1), dtype=np.uint32)
+        st = (C.c_uint64 * 4)()
+        rc = self._lib.lrge_hip_name_ranks(self.h, blob, name_off.ctypes.data, n_names, None if idx is None or not n else idx.ctypes.data, n,
+                                           out.ctypes.data, C.cast(st, C.c_void_p))
+        if rc == _ffi.ERR_UNPROVEN:
+            raise UnprovenInput(rc, self._lib.lrge_hip_last_error(self.h).decode())
+        self._check(rc)
+        self.name_rank_stats = dict(zip(("sorts", "words", "distinct", "us"), [int(x) for x in st]))
+        res, k = [], 0
+        for m in sizes:
+            res.append(out[k:k + m].copy())
+            k += m
+        return res
+
+    def name_ranks(self, *name_lists):
+        """engine.name_ranks on the device (lrge_hip_name_ranks): byte-wise ranks over the union of several name
+        lists, equal names sharing a rank; one uint32 array per input list.  A name above option NAME_RANK_MAX_BYTES (default
+        256) raises UnprovenInput: take engine.name_ranks.  `name_rank_stats` holds the call's sorts, words, distinct names and
+        microseconds."""
+        allnames = [n if isinstance(n, bytes) else n.encode() for lst in name_lists for n in lst]
+        off = np.zeros(len(allnames) + 1, dtype=np.uint64)
+        if allnames:
+            np.cumsum(np.fromiter(map(len, allnames), dtype=np.uint64, count=len(allnames)), out=off[1:])
+        (ranks,) = self._name_ranks(b"".join(allnames), off, len(allnames), None)
+        out, k = [], 0
+        for lst in name_lists:
+            out.append(ranks[k:k + len(lst)].copy())
+            k += len(lst)
+        return out
+
     def set_timer_level(self, level):
         """0 = call total + chain stage only, 1 = every stage, 2 (default) = also every k_rs_scatter launch."""
         self._check(self._lib.lrge_hip_set_timer_level(self.h, int(level)))
@@ -303,6 +342,12 @@ class DeviceReads:
         a = (C.c_uint64 * 4)()
         self.ctx._check(self.ctx._lib.lrge_hip_reads_window_stats(self.h, C.byref(a)))
         return tuple(int(x) for x in a)
+
+    def name_ranks(self, *idx_lists):
+        """engine.name_ranks of the reads in idx_lists (each any order, repeats allowed) on the device, ranked together: one
+        uint32 array per list (Context.name_ranks; from the identifier table as it came back, `names` is not built).  A selected
+        identifier above option NAME_RANK_MAX_BYTES raises UnprovenInput."""
+        return self.ctx._name_ranks(self._blob, self.name_off, self.n, idx_lists)
 
     def seqset(self, idx, ranks=None):
         """reads idx (any order, repeats allowed) as a SeqSet; ranks as Context.upload"""

@@ -45,6 +45,7 @@ class Builder:
         self._remove_internal, self._ratio = False, 0.2
         self._use_min_ref, self._threads, self._tmpdir, self._seed = False, 1, None, None
         self._platform, self._device = "ont", 0
+        self._device_name_ranks = False
 
     def target_num_reads(self, n): self._t = int(n); return self
     def query_num_reads(self, n): self._q = int(n); return self
@@ -59,14 +60,28 @@ class Builder:
     def seed(self, s): self._seed = s; return self
     def platform(self, p): self._platform = str(p).lower(); return self
     def device(self, d): self._device = int(d); return self
+    def device_name_ranks(self, flag): self._device_name_ranks = bool(flag); return self   # name ranks by Context.name_ranks (opt-in)
 
     def build(self, input_):
         return TwoSetStrategy(input_, self)
 
 
+def ranks_for(ctx, device_name_ranks, *name_lists):
+    """engine.name_ranks, or with device_name_ranks the device form (Context.name_ranks), which hands a name it does not take
+    (UnprovenInput: above NAME_RANK_MAX_BYTES) back to the host sort; (ranks, "device" | "host")"""
+    if device_name_ranks:
+        try:
+            return ctx.name_ranks(*name_lists), "device"
+        except _ffi.UnprovenInput:
+            pass
+    return engine.name_ranks(*name_lists), "host"
+
+
 class TwoSetStrategy(Estimate):
-    def __init__(self, input_, builder=None):
+    def __init__(self, input_, builder=None, device_name_ranks=None):
         b = builder or Builder()
+        self.device_name_ranks = b._device_name_ranks if device_name_ranks is None else bool(device_name_ranks)
+        self.name_ranks_by = None
         self.input = input_
         self.target_num_reads, self.query_num_reads = b._t, b._q
         self.remove_internal, self.max_overhang_ratio = b._remove_internal, b._ratio
@@ -109,7 +124,7 @@ class TwoSetStrategy(Estimate):
         ctx = engine.Context(self.device)
         Q = T = ix = None
         try:
-            qr, tr = engine.name_ranks(qn, tn)
+            (qr, tr), self.name_ranks_by = ranks_for(ctx, self.device_name_ranks, qn, tn)
             Q = ctx.upload(*readio.pack(qs), qr)
             T = ctx.upload(*readio.pack(ts), tr)
             try:

@@ -60,7 +60,7 @@ int main(int argc, char **argv) {
     bool T_set = false, Q_set = false, filter = false, with_inf = false, precise = false, use_min_ref = false, honour_platform = false;
     float q1 = lrge::LOWER_QUANTILE, q3 = lrge::UPPER_QUANTILE, ratio = 0.2f;
     size_t threads = 1; std::optional<uint64_t> seed; int quiet = 0, verbose = 0, device = 0;
-    bool keep_temp = false, dump_records = false, gpu_inflate = false, gpu_gzip = false, gpu_bzip2 = false, gpu_ingest = false; std::string temp_dir;
+    bool keep_temp = false, dump_records = false, gpu_inflate = false, gpu_gzip = false, gpu_bzip2 = false, gpu_ingest = false, gpu_names = false; std::string temp_dir;
     auto need = [&](int &i) -> const char * { if (i + 1 >= argc) { fprintf(stderr, "error: missing value for %s\n", argv[i]); exit(2); } return argv[++i]; };
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -86,6 +86,7 @@ int main(int argc, char **argv) {
         else if (a == "--gpu-gzip") gpu_gzip = true;             // every gzip input (plain, multi-member, BGZF) decompressed on --device
         else if (a == "--gpu-bzip2") gpu_bzip2 = true;           // bzip2 input decompressed on --device (with --gpu-ingest: kept in HBM)
         else if (a == "--gpu-ingest") { gpu_ingest = true; gpu_gzip = true; }   // FASTA / FASTQ / unaligned BAM / unaligned SAM parsed on --device too: the bases never reach host memory (implies --gpu-gzip)
+        else if (a == "--gpu-names") gpu_names = true;           // identifier ranks computed on --device (lrge_hip_name_ranks); not implied by --gpu-ingest
         else if (a == "--dump-records") dump_records = true;   // host-only: print "id<TAB>sequence" per record and exit (tests)
         else if (a == "-q" || a == "--quiet") ++quiet; else if (a == "-qq") quiet += 2; else if (a == "-qqq") quiet += 3;
         else if (a == "-v" || a == "--verbose") ++verbose; else if (a == "-vv") verbose += 2;
@@ -117,16 +118,19 @@ int main(int argc, char **argv) {
         lrge::twoset::TwoSetStrategy ts = dev ? lrge::twoset::TwoSetStrategy(*dev) : lrge::twoset::TwoSetStrategy(reads);
         lrge::ava::AvaStrategy as = dev ? lrge::ava::AvaStrategy(*dev) : lrge::ava::AvaStrategy(reads);
         lrge::Estimate *st;
+        const std::function<void(bool)> names_note = [&](bool on_device) { if (info) fprintf(stderr, "[INFO] gpu-names: %s\n", on_device ? "device" : "host"); };
         if (N) {
             if (info) fprintf(stderr, "[INFO] Running all-vs-all strategy with %zu reads\n", *N);
-            const auto b = lrge::ava::Builder().num_reads(*N).remove_internal(filter, ratio).threads(threads).seed(seed).platform(pf).device(device);
+            const auto b = lrge::ava::Builder().num_reads(*N).remove_internal(filter, ratio).threads(threads).seed(seed).platform(pf).device(device).device_name_ranks(gpu_names);
             as = dev ? b.build(*dev) : b.build(reads);
+            as.name_ranks_note = names_note;
             st = &as;
         } else {
             if (info) fprintf(stderr, "[INFO] Running two-set strategy with %zu target reads and %zu query reads\n", *T, *Q);
             const auto b = lrge::twoset::Builder().target_num_reads(*T).query_num_reads(*Q).remove_internal(filter, ratio).use_min_ref(use_min_ref)
-                               .threads(threads).seed(seed).platform(pf).device(device);
+                               .threads(threads).seed(seed).platform(pf).device(device).device_name_ranks(gpu_names);
             ts = dev ? b.build(*dev) : b.build(reads);
+            ts.name_ranks_note = names_note;
             st = &ts;
         }
         std::vector<std::string> paf;
