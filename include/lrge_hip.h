@@ -448,13 +448,50 @@ typedef struct lrge_hip_bzip2_stats {
 int  lrge_hip_bzip2_inflate(lrge_hip_ctx *ctx, const void *comp, uint64_t comp_len, int (*sink)(void *user, const void *bytes, uint64_t n),
                             void *user, lrge_hip_bzip2_stats *stats);
 
+/* Zstandard decompressed on the device (k_zs_heads, k_zs_literals, k_zs_sequences, k_zs_execute, k_zs_resolve,
+   k_zs_xxh64): the host hops over frame and block headers; the blocks of a round are entropy-decoded in parallel, every table
+   rebuilt from the block that states it; the round's blocks are executed at once, a byte whose source lies in front of its block
+   is recorded and read once the blocks in front are final; a frame's content checksum is XXH64 over its text.
+   lrge_hip_zstd_inflate has the contract of lrge_hip_bzip2_inflate: the bytes arrive in order through `sink` (a nonzero return
+   stops the call with LRGE_ERR_IO); on a non-OK return the bytes delivered so far are void; there is no host fall-back inside the
+   call.  The device accepts a subset of what the host reader takes, and returns the same bytes: one or more frames back to back,
+   skippable frames between them, with or without Frame_Content_Size, window descriptor and checksum; raw, RLE and compressed
+   blocks; every literals type and sequence mode.  LRGE_ERR_PARSE (the message names a byte offset): a dictionary ID other than 0,
+   a reserved bit, block type 3, a block or its output above Block_Maximum_Size, a window above 2^27 bytes, an accuracy log above
+   the format's limits, Huffman weights that do not sum to a power of two, a bitstream that is not consumed exactly, treeless
+   literals or a repeat mode with nothing in front of it in the frame, too few literals, an offset of 0, beyond the frame's bytes
+   or beyond the window, a content-size mismatch, a wrong checksum, a truncated file, bytes behind the last frame.
+   LRGE_ERR_TOO_MANY: the text of the call does not fit the device budget (the default of INGEST_MAX_BYTES: half of the free device
+   memory plus the context's idle arena bytes; the text stays on the device until the call ends, because a match may reach back
+   through the whole frame); the caller takes the host.  LRGE_ERR_DEVICE: a runtime failure.  Options ZSTD_ROUND_BLOCKS: blocks
+   decoded per round (default: what half of the free device memory plus the idle arena bytes holds, at most 4096); ZSTD_CHECKSUM
+   (default 1): 0 skips the checksums.  *stats (may be NULL) receives the counts of the call.
+   lrge_hip_read_records_gpu_ex | LRGE_GPU_INFLATE_ZSTD sends Zstandard input to this decoder and falls back to the unchanged host
+   path for anything it does not accept; lrge_hip_reads_open* | LRGE_GPU_INFLATE_ZSTD keeps the text in HBM.  Known limit: zstd
+   input is never windowed -- LRGE_GPU_INGEST_WINDOWED leaves it resident, and text above INGEST_MAX_BYTES is LRGE_ERR_UNPROVEN. */
+typedef struct lrge_hip_zstd_stats {
+    uint64_t frames;              /* Zstandard frames */
+    uint64_t skippable_frames;    /* skippable frames hopped over */
+    uint64_t blocks;              /* blocks of every type */
+    uint64_t raw_blocks;
+    uint64_t rle_blocks;
+    uint64_t sequences;           /* Number_of_Sequences summed over the compressed blocks */
+    uint64_t checksums_checked;   /* frames whose content checksum was computed and compared (0 with ZSTD_CHECKSUM=0) */
+    uint64_t rounds;              /* rounds of at most ZSTD_ROUND_BLOCKS blocks */
+    uint64_t bytes_out;           /* decompressed bytes */
+    uint64_t checksum_us;         /* microseconds spent in k_zs_xxh64, launch to result */
+} lrge_hip_zstd_stats;
+#define LRGE_GPU_INFLATE_ZSTD 128
+int  lrge_hip_zstd_inflate(lrge_hip_ctx *ctx, const void *comp, uint64_t comp_len, int (*sink)(void *user, const void *bytes, uint64_t n),
+                           void *user, lrge_hip_zstd_stats *stats);
+
 /* Read sets built on the device from FASTA / FASTQ text (k_fx_census, k_fx_summary, k_fx_scatter, k_fx_records,
    k_fx_names, k_fx_gather) and from unaligned BAM (k_bam_header, k_bam_find, k_bam_walk, k_bam_records,
    k_bam_gather; SAM, DESIGN section 14: k_sam_mark, k_sam_records): the device-side form of the record reader (io.rs:154-184) and of the read selection that feeds the
    strategies (twoset.rs:122-201).  The file's bytes are decompressed into HBM and stay there; the records are found there; only
    the identifiers and the sequence lengths come back.
    lrge_hip_reads_open (io.rs:154-184) reads `path` into memory and calls lrge_hip_reads_open_mem (io.rs:154-184), which takes the
-   bytes of a whole file.  `flags`: LRGE_GPU_INFLATE_BGZF | LRGE_GPU_INFLATE_GZIP | LRGE_GPU_INFLATE_BZIP2 choose the device decoders as in
+   bytes of a whole file.  `flags`: LRGE_GPU_INFLATE_BGZF | LRGE_GPU_INFLATE_GZIP | LRGE_GPU_INFLATE_BZIP2 | LRGE_GPU_INFLATE_ZSTD choose the device decoders as in
    lrge_hip_read_records_gpu_ex; with neither, only uncompressed input is taken.  | LRGE_GPU_INGEST_BAM: text that starts with
    the BAM magic is scanned as unaligned BAM (every record with flag 4, found by a speculative walk of the length chain that
    is proven from the end of the header); without the flag BAM is unproven, as it was before the flag existed.
@@ -464,7 +501,7 @@ int  lrge_hip_bzip2_inflate(lrge_hip_ctx *ctx, const void *comp, uint64_t comp_l
    and produces no parse error of its own -- anything but FASTA, strict four-line FASTQ or (with its flag) well-formed unaligned
    BAM (an empty line between records, a truncated record, a missing '+', CRAM, BAM without LRGE_GPU_INGEST_BAM, a BAM
    with a mapped record, a damaged header or record, or bytes behind the last record, SAM without LRGE_GPU_INGEST_SAM, a SAM
-   record line with fewer than ten tabs, with a flag that is not plain digits or with a mapped flag), a compressed format without its flag or other than gzip and (with LRGE_GPU_INFLATE_BZIP2) bzip2, a damaged gzip file, a bzip2 file the device decoder does not accept, text above option INGEST_MAX_BYTES
+   record line with fewer than ten tabs, with a flag that is not plain digits or with a mapped flag), a compressed format without its flag or other than gzip, (with LRGE_GPU_INFLATE_BZIP2) bzip2 and (with LRGE_GPU_INFLATE_ZSTD) Zstandard, a damaged gzip file, a bzip2 or Zstandard file the device decoder does not accept, text above option INGEST_MAX_BYTES
    (default: half of the free device memory plus the context's idle arena bytes); the caller takes lrge_hip_read_records*, which
    parses the file or gives the reference's message.  LRGE_ERR_TOO_MANY: 2^32 records or more, or a sequence of 2^32 bases or
    more.  LRGE_ERR_IO: the file cannot be read.  An empty file is LRGE_OK with a count of 0.
@@ -474,7 +511,7 @@ int  lrge_hip_bzip2_inflate(lrge_hip_ctx *ctx, const void *comp, uint64_t comp_l
    records are those of the resident scan and of lrge_hip_read_records, or the call is LRGE_ERR_UNPROVEN (a window the scan does
    not prove, a window of another format than the first, a window of 2^32 bytes or more, 2^32 records or 4 GiB of identifiers in
    all); for text that is not well formed (empty
-   lines between records) the verdict may depend on the window.  Text within one window, BAM and SAM stay resident as without the flag.
+   lines between records) the verdict may depend on the window.  Text within one window, BAM and SAM stay resident as without the flag; so does Zstandard text of any size (a known limit: its matches need the earlier text).
    | LRGE_GPU_INGEST_WINDOWED_ALN (k_bam_spans, k_bam_store; effective only beside LRGE_GPU_INGEST_WINDOWED and the
    format's own flag): unaligned BAM and SAM above INGEST_WINDOW_BYTES pass through in windows too.  A BAM window is cut at the
    first record start of the chain proven from its front that the block does not hold whole, a SAM window directly behind its

@@ -47,6 +47,7 @@ SAM_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_sam_twin.so")
 NAMES_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_names_twin.so")
 BZIP2_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_bzip2_twin.so")
 NAMES_LSD_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_names_lsd_twin.so")
+ZSTD_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_zstd_twin.so")
 
 
 def _build_twin(out, main, force):
@@ -60,10 +61,10 @@ def _build_twin(out, main, force):
 
 
 def build_twin(force=False):
-    """The host twins, all eight: of k_inflate (csrc/inflate_twin.cpp, the same bit-level core), and of the speculative gzip
+    """The host twins, all nine: of k_inflate (csrc/inflate_twin.cpp, the same bit-level core), and of the speculative gzip
     decode (build_gzip_twin), of the FASTA / FASTQ record scan (build_fastx_twin), of the BAM record scan (build_bam_twin), of
     the SAM record scan (build_sam_twin), of the identifier ranking by refinement (build_names_twin) and by fixed LSD passes (build_names_lsd_twin)
-    and of the bzip2 decode (build_bzip2_twin)."""
+    and of the bzip2 decode (build_bzip2_twin) and the Zstandard decode (build_zstd_twin)."""
     build_gzip_twin(force)
     build_fastx_twin(force)
     build_bam_twin(force)
@@ -71,6 +72,7 @@ def build_twin(force=False):
     build_names_twin(force)
     build_names_lsd_twin(force)
     build_bzip2_twin(force)
+    build_zstd_twin(force)
     return _build_twin(TWIN_PATH, "inflate_twin.cpp", force)
 
 
@@ -108,6 +110,11 @@ def build_names_lsd_twin(force=False):
 def build_bzip2_twin(force=False):
     """The host twin of the block-parallel bzip2 decode (csrc/bz_twin.cpp): the same core and the same driver of the rounds."""
     return _build_twin(BZIP2_TWIN_PATH, "bz_twin.cpp", force)
+
+
+def build_zstd_twin(force=False):
+    """The host twin of the block-parallel Zstandard decode (csrc/zs_twin.cpp): the same core and the same driver of the rounds."""
+    return _build_twin(ZSTD_TWIN_PATH, "zs_twin.cpp", force)
 
 
 CLI_PATH = os.path.join(LIB_DIR, "lrge-hip")

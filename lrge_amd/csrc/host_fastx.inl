@@ -1,6 +1,6 @@
 // host_fastx.inl -- read sets built on the device from FASTA / FASTQ text (k_fastx.h), from unaligned BAM
 // (k_bam.h, host_bam.inl) and from unaligned SAM (k_sam.h, host_sam.inl): the text reaches HBM
-// decompressed (BGZF chunks decoded into one block by the pipeline of host_inflate.inl, the gzip and bzip2 rounds appended device-to-device, plain input copied once), the
+// decompressed (BGZF chunks decoded into one block by the pipeline of host_inflate.inl, the gzip, bzip2 and Zstandard rounds appended device-to-device, plain input copied once), the
 // record scan runs there, only identifiers and lengths come back, and lrge_hip_seqset_from_reads gathers the selected reads
 // into dense ASCII for the device-source pack of host_seqset.inl.  Whatever the scan cannot prove is LRGE_ERR_UNPROVEN: the
 // caller takes lrge_hip_read_records*, which parses the file or reports it with the reference's messages.  With
@@ -506,7 +506,7 @@ static int fx_src_bgzf(FxSink &s, const u8 *d, const std::vector<BgzfBlock> &t, 
 // every round's text in its own block (dev_keep.h), which becomes the handle's.  A windowed call flushes that block through the
 // sink's run whenever a round has been appended (DevKeep::keep_flush); whether its windows stay on is the first flush's sniff.
 // refused: the message for a stream the decoder does not take, with status(rc) and the file offset
-static_assert((int)GZ_RUN_OK == (int)BZ_RUN_OK && (int)GZ_RUN_DEVICE == (int)BZ_RUN_DEVICE, "one set of driver codes");
+static_assert((int)GZ_RUN_OK == (int)BZ_RUN_OK && (int)GZ_RUN_DEVICE == (int)BZ_RUN_DEVICE && (int)GZ_RUN_OK == (int)ZS_RUN_OK && (int)GZ_RUN_DEVICE == (int)ZS_RUN_DEVICE, "one set of driver codes");
 template <class Dev, class Run, class Status>
 static int fx_inflate_to_device(FxSink &s, Dev &dev, Run run, const char *codec, const char *refused, Status status) {
     lrge_hip_ctx *ctx = s.ctx;
@@ -549,6 +549,20 @@ static int fx_src_bzip2(FxSink &s, const u8 *d, u64 len) {
     BzDev dev(s.ctx);
     return fx_inflate_to_device(s, dev, [&](u64 *bad) { return bz_run(dev, d, len, s.ctx->opt_u64("BZIP2_ROUND_BLOCKS", 0), [](const uint8_t *, uint64_t) { return true; }, st, bad); },
                                 "bzip2", "reads_open: bzip2 data not accepted by the device (%s near file offset %llu)", bz_status_name);
+}
+
+// Zstandard: a match reaches back through the frame's earlier text, so the text is never windowed: with LRGE_GPU_INGEST_WINDOWED too
+// it is taken resident, within INGEST_MAX_BYTES
+static int fx_src_zstd(FxSink &s, const u8 *d, u64 len) {
+    ZsStats st;
+    ZsDev dev(s.ctx);
+    dev.to_host = false;
+    s.run.reset();
+    const int rc = fx_inflate_to_device(s, dev, [&](u64 *bad) {
+        return zs_run(dev, d, len, s.ctx->opt_u64("ZSTD_ROUND_BLOCKS", 0), zs_checksum_on(s.ctx), [](const uint8_t *, uint64_t) { return true; }, st, bad);
+    }, "zstd", "reads_open: zstd data not accepted by the device (%s near file offset %llu)", zs_status_name);
+    if (s.ctx->opt("VERBOSE")) fprintf(stderr, "[lrge_hip] reads_open: zstd content checksums %.2f ms of the text-to-HBM share\n", dev.ms[5]);
+    return rc;
 }
 
 // ---- the two ends of a call ----  windows were flushed: the rest of the block is the last, the store the handle's text
@@ -602,6 +616,7 @@ extern "C" int lrge_hip_reads_open_mem(lrge_hip_ctx *ctx, const void *file_bytes
     int rc;
     if (b(0) == 0x1f && b(1) == 0x8b) rc = bgzf_scan_blocks(d, len, &t, &total) ? fx_src_bgzf(s, d, t, total) : fx_src_gzip(s, d, len);
     else if (b(0) == 0x42 && b(1) == 0x5a && (flags & LRGE_GPU_INFLATE_BZIP2)) rc = fx_src_bzip2(s, d, len);
+    else if (b(0) == 0x28 && b(1) == 0xb5 && b(2) == 0x2f && b(3) == 0xfd && (flags & LRGE_GPU_INFLATE_ZSTD)) rc = fx_src_zstd(s, d, len);
     else if ((b(0) == 0x42 && b(1) == 0x5a) || (b(0) == 0x28 && b(1) == 0xb5 && b(2) == 0x2f && b(3) == 0xfd) ||
              (b(0) == 0xfd && b(1) == 0x37 && b(2) == 0x7a && b(3) == 0x58 && b(4) == 0x5a)) {
         ctx->err = "reads_open: bzip2, zstd and xz input is decompressed on the host";

@@ -221,6 +221,9 @@ extern "C" int lrge_hip_gzip_inflate(lrge_hip_ctx *ctx, const void *comp, uint64
 // (host_bzip2.inl)
 static int bzip2_inflate_impl(lrge_hip_ctx *ctx, const uint8_t *comp, uint64_t comp_len, int (*sink)(void *, const void *, uint64_t), void *user,
                               lrge_hip_bzip2_stats *stats);
+// (host_zstd.inl)
+static int zstd_inflate_impl(lrge_hip_ctx *ctx, const uint8_t *comp, uint64_t comp_len, int (*sink)(void *, const void *, uint64_t), void *user,
+                             lrge_hip_zstd_stats *stats);
 
 extern "C" int lrge_hip_read_records_gpu_ex(lrge_hip_ctx *ctx, const char *path, int flags,
                                             void (*cb)(void *, const char *, uint64_t, const char *, uint64_t), void *user, int *used_device) {
@@ -235,6 +238,18 @@ extern "C" int lrge_hip_read_records_gpu_ex(lrge_hip_ctx *ctx, const char *path,
                 if (!(flags & LRGE_GPU_INFLATE_BZIP2)) return false;
                 data.clear();
                 const int rc = bzip2_inflate_impl(ctx, (const uint8_t *)raw.data(), raw.size(), [](void *u, const void *b, uint64_t k) {
+                    ((std::string *)u)->append((const char *)b, (size_t)k);
+                    return 0;
+                }, &data, nullptr);
+                if (rc == LRGE_ERR_DEVICE) throw DeviceFail{rc};
+                if (rc != LRGE_OK) { data.clear(); return false; }     // not accepted by the device: the host path, with its messages
+                used = 1;
+                return true;
+            }
+            if (lrge::io::detect_compression_format(raw) == lrge::io::CompressionFormat::Zstd) {
+                if (!(flags & LRGE_GPU_INFLATE_ZSTD)) return false;
+                data.clear();
+                const int rc = zstd_inflate_impl(ctx, (const uint8_t *)raw.data(), raw.size(), [](void *u, const void *b, uint64_t k) {
                     ((std::string *)u)->append((const char *)b, (size_t)k);
                     return 0;
                 }, &data, nullptr);

@@ -1,0 +1,187 @@
+// host_zstd.inl -- Zstandard decompressed on the device (k_zstd.h): the backend that zs_round.h's zs_run drives
+// and the C entry point.  Included into lrge_hip.hip behind host_gzip.inl (DevKeep, GzBuf).
+//
+// The compressed bytes go up once and stay for the call.  The text of the whole call stays in the backend's DevKeep block: a match
+// reaches back through every earlier block of its frame, and a later round reads the bytes of the rounds before.  Option
+// ZSTD_ROUND_BLOCKS: the blocks decoded per round; its default is what half of the arena's idle bytes plus the device's free bytes
+// hold at zs_block_bytes plus the text per block, at most ZS_ROUND_MAX.  Option ZSTD_CHECKSUM (default 1): 0 skips XXH64.  Option
+// ZSTD_TIMING: the stages are separated by synchronisations and their times are printed to stderr when the call ends
+// (tools/zstd_bench.py); the checksum's time is always measured, its launch is followed by the read of its word anyway.
+
+static const char *zs_status_name(int s) {
+    switch (s) {
+    case ZS_E_MAGIC: return "no frame magic where a frame must start";
+    case ZS_E_INPUT: return "unexpected end of compressed data";
+    case ZS_E_RESERVED: return "a reserved bit is set";
+    case ZS_E_DICT: return "a dictionary ID other than 0";
+    case ZS_E_WINDOW: return "a window above 2^27 bytes";
+    case ZS_E_BLOCK_TYPE: return "block type 3";
+    case ZS_E_BLOCK_SIZE: return "a block above Block_Maximum_Size";
+    case ZS_E_LIT_HEADER: return "a literals section that does not fit its block";
+    case ZS_E_ACCURACY: return "an accuracy log above the format's limit";
+    case ZS_E_FSE: return "an invalid FSE table description";
+    case ZS_E_WEIGHTS: return "invalid Huffman weights";
+    case ZS_E_BITSTREAM: return "a bitstream not consumed exactly";
+    case ZS_E_NO_TABLE: return "treeless literals or a repeat mode with no table in front";
+    case ZS_E_SYMBOL: return "a symbol above its alphabet";
+    case ZS_E_LITERALS: return "more literals asked for than the block has";
+    case ZS_E_OFFSET: return "an offset of 0, beyond the frame's bytes or beyond the window";
+    case ZS_E_CONTENT_SIZE: return "Frame_Content_Size mismatch";
+    case ZS_E_CHECKSUM: return "content checksum mismatch";
+    case ZS_E_SEQ_HEADER: return "a sequences section that does not fit its block";
+    case ZS_E_TOO_BIG: return "the text does not fit the device budget";
+    default: return "unknown status";
+    }
+}
+
+namespace {
+struct ZsDev : DevKeep {
+    GzBuf in, blocks, hbuf, lit, seq, res, status, org, groups, hash;
+    u64 n = 0;
+    bool timing = false, to_host = true;
+    double ms[6] = {0, 0, 0, 0, 0, 0};                           // heads, literals, sequences, execute, resolve, checksum
+    explicit ZsDev(lrge_hip_ctx *c) : DevKeep(c) {
+        for (GzBuf *b : {&in, &blocks, &hbuf, &lit, &seq, &res, &status, &org, &groups, &hash}) b->ctx = c;
+        timing = c->opt("ZSTD_TIMING") != nullptr;
+        keep_on = true;
+    }
+    ~ZsDev() { (void)hipStreamSynchronize(ctx->stream); }
+    struct Lap {
+        ZsDev &d; int slot; bool on; double t0;
+        Lap(ZsDev &dev, int s, bool always = false) : d(dev), slot(s), on(dev.timing || always), t0(on ? DevPool::now_ms() : 0) {}
+        bool end() { if (!on) return true; const bool r = d.sync(); d.ms[slot] += DevPool::now_ms() - t0; return r; }
+    };
+    bool over() const { return keep_over; }
+    bool load(const uint8_t *d, uint64_t len) {
+        n = len;
+        if (!in.need((size_t)len + ZS_PAD, &e)) return false;
+        if (!ok(hipMemsetAsync(in.as<u8>() + len, 0, ZS_PAD, ctx->stream))) return false;
+        if (len && !ok(hipMemcpyAsync(in.p, d, (size_t)len, hipMemcpyHostToDevice, ctx->stream))) return false;
+        return sync();
+    }
+    uint32_t default_round() {
+        size_t mfree = 0, mtot = 0;
+        if (hipMemGetInfo(&mfree, &mtot) != hipSuccess) { (void)hipGetLastError(); mfree = 0; }
+        return (uint32_t)std::min<u64>(ZS_ROUND_MAX, std::max<u64>(1, ((u64)mfree + ctx->pool.idle()) / 2 / (zs_block_bytes() + ZS_BLOCK_MAX)));
+    }
+    bool put_blocks(const ZsBlock *b, uint32_t k) {
+        return blocks.need((size_t)k * sizeof(ZsBlock), &e) && ok(hipMemcpyAsync(blocks.p, b, (size_t)k * sizeof(ZsBlock), hipMemcpyHostToDevice, ctx->stream));
+    }
+    bool heads(ZsBlock *b, uint32_t k) {
+        Lap lap(*this, 0);
+        if (!put_blocks(b, k) || !hbuf.need((size_t)k * sizeof(ZsHead), &e)) return false;
+        hipLaunchKernelGGL(k_zs_heads, dim3((u32)div_up(k, 64)), dim3(64), 0, ctx->stream, in.as<const u8>(), blocks.as<const ZsBlock>(), k, hbuf.as<ZsHead>());
+        if (!ok(hipGetLastError())) return false;
+        std::vector<ZsHead> h(k);
+        if (!ok(hipMemcpyAsync(h.data(), hbuf.p, (size_t)k * sizeof(ZsHead), hipMemcpyDeviceToHost, ctx->stream)) || !sync()) return false;
+        for (uint32_t j = 0; j < k; ++j) if (b[j].type == 2) b[j].h = h[j];
+        return lap.end();
+    }
+    bool entropy(const ZsBlock *b, uint32_t k, uint64_t lit_bytes, uint64_t n_seq, uint32_t *lit_status, ZsSeqRes *r) {
+        hipStream_t st = ctx->stream;
+        if (!put_blocks(b, k) || !lit.need((size_t)lit_bytes + 16, &e) || !seq.need((size_t)(n_seq + 1) * sizeof(ZsSeq), &e) || !res.need((size_t)k * sizeof(ZsSeqRes), &e) ||
+            !status.need((size_t)k * 4, &e))
+            return false;
+        if (!ok(hipMemsetAsync(status.p, 0, (size_t)k * 4, st)) || !ok(hipMemsetAsync(res.p, 0, (size_t)k * sizeof(ZsSeqRes), st))) return false;
+        {
+            Lap lap(*this, 1);
+            hipLaunchKernelGGL(k_zs_literals, dim3(k), dim3(64), 0, st, in.as<const u8>(), n, blocks.as<const ZsBlock>(), k, lit.as<u8>(), status.as<u32>());
+            if (!ok(hipGetLastError()) || !lap.end()) return false;
+        }
+        Lap lap(*this, 2);
+        hipLaunchKernelGGL(k_zs_sequences, dim3(k), dim3(64), 0, st, in.as<const u8>(), n, blocks.as<const ZsBlock>(), k, seq.as<ZsSeq>(), res.as<ZsSeqRes>());
+        if (!ok(hipGetLastError())) return false;
+        if (!ok(hipMemcpyAsync(lit_status, status.p, (size_t)k * 4, hipMemcpyDeviceToHost, st)) || !ok(hipMemcpyAsync(r, res.p, (size_t)k * sizeof(ZsSeqRes), hipMemcpyDeviceToHost, st)) ||
+            !sync())
+            return false;
+        return lap.end();
+    }
+    bool reserve(uint64_t bytes) { return keep_reserve(bytes); }
+    bool execute(const ZsBlock *b, uint32_t k, const uint32_t *group, uint32_t n_groups, uint64_t bytes, uint32_t *st_h) {
+        hipStream_t st = ctx->stream;
+        if (!put_blocks(b, k) || !org.need((size_t)(bytes + 1) * 4, &e) || !groups.need((size_t)(n_groups + 1) * 4, &e) || !status.need((size_t)k * 4, &e)) return false;
+        if (!ok(hipMemcpyAsync(groups.p, group, (size_t)(n_groups + 1) * 4, hipMemcpyHostToDevice, st)) || !ok(hipMemsetAsync(status.p, 0, (size_t)k * 4, st))) return false;
+        const u64 base = keep_len;
+        {
+            Lap lap(*this, 3);
+            hipLaunchKernelGGL(k_zs_execute, dim3(k), dim3(64), 0, st, in.as<const u8>(), blocks.as<const ZsBlock>(), k, lit.as<const u8>(), seq.as<const ZsSeq>(), keep, org.as<u32>(),
+                               base, status.as<u32>());
+            if (!ok(hipGetLastError())) return false;
+            if (!ok(hipMemcpyAsync(st_h, status.p, (size_t)k * 4, hipMemcpyDeviceToHost, st)) || !sync() || !lap.end()) return false;
+        }
+        for (uint32_t j = 0; j < k; ++j) if (st_h[j]) return true;         // (no block's origins are resolved when one of them is damaged)
+        Lap lap(*this, 4);
+        hipLaunchKernelGGL(k_zs_resolve, dim3(n_groups), dim3(ZS_RESOLVE_THREADS), 0, st, blocks.as<const ZsBlock>(), groups.as<const u32>(), keep, org.as<const u32>(), base);
+        if (!ok(hipGetLastError()) || !lap.end()) return false;
+        keep_len += bytes;
+        return true;
+    }
+    bool xxh64(const uint64_t *at, const uint64_t *len, uint32_t m, uint64_t *h) {
+        Lap lap(*this, 5, true);
+        std::vector<u64> span(2 * (size_t)m);
+        for (uint32_t i = 0; i < m; ++i) { span[2 * i] = at[i]; span[2 * i + 1] = len[i]; }
+        if (!hash.need((size_t)m * 24, &e)) return false;
+        if (!ok(hipMemcpyAsync(hash.p, span.data(), (size_t)m * 16, hipMemcpyHostToDevice, ctx->stream))) return false;
+        hipLaunchKernelGGL(k_zs_xxh64, dim3(m), dim3(64), 0, ctx->stream, (const u8 *)keep, hash.as<const u64>(), hash.as<u64>() + 2 * (size_t)m);
+        if (!ok(hipGetLastError())) return false;
+        if (!ok(hipMemcpyAsync(h, hash.as<u64>() + 2 * (size_t)m, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream)) || !sync()) return false;
+        return lap.end();
+    }
+    const uint8_t *bytes(uint64_t at, uint64_t len) {
+        if (!to_host) return keep ? keep : (const uint8_t *)this;      // (the text stays: the sink does not read it)
+        u8 *h = ctx_pin(1, std::max<u64>(1, len));
+        if (!h) return nullptr;
+        if (!ok(hipMemcpyAsync(h, keep + at, (size_t)len, hipMemcpyDeviceToHost, ctx->stream)) || !sync()) return nullptr;
+        return h;
+    }
+};
+
+static bool zs_checksum_on(lrge_hip_ctx *ctx) { return ctx->opt_u64("ZSTD_CHECKSUM", 1) != 0; }
+static void zs_stats_out(const ZsStats &st, const ZsDev &dev, lrge_hip_zstd_stats *o) {
+    if (!o) return;
+    o->frames = st.frames; o->skippable_frames = st.skippable; o->blocks = st.blocks; o->raw_blocks = st.raw_blocks; o->rle_blocks = st.rle_blocks;
+    o->sequences = st.sequences; o->checksums_checked = st.checksums_checked; o->rounds = st.rounds; o->bytes_out = st.bytes_out;
+    o->checksum_us = (uint64_t)(dev.ms[5] * 1000.0);
+}
+}  // namespace
+
+// the whole zstd buffer through `sink`; LRGE_ERR_PARSE / TOO_MANY / DEVICE as lrge_hip_zstd_inflate
+static int zstd_inflate_impl(lrge_hip_ctx *ctx, const uint8_t *comp, uint64_t comp_len, int (*sink)(void *, const void *, uint64_t), void *user,
+                             lrge_hip_zstd_stats *stats) {
+    (void)hipSetDevice(ctx->device);
+    ZsStats st;
+    u64 bad = 0;
+    bool sink_stop = false;
+    int rc;
+    {
+        ZsDev dev(ctx);
+        size_t mfree = 0, mtot = 0;
+        if (hipMemGetInfo(&mfree, &mtot) != hipSuccess) { (void)hipGetLastError(); mfree = 0; }
+        dev.keep_max = ((u64)mfree + ctx->pool.idle()) / 2;            // (the ingest cap's default: host_fastx.inl)
+        rc = zs_run(dev, comp, comp_len, ctx->opt_u64("ZSTD_ROUND_BLOCKS", 0), zs_checksum_on(ctx), [&](const uint8_t *b, uint64_t k) {
+            if (sink(user, b, k) != 0) { sink_stop = true; return false; }
+            return true;
+        }, st, &bad);
+        if (rc == ZS_RUN_DEVICE && !sink_stop) {
+            LRGE_SET_ERR(ctx, "zstd inflate: %s", hipGetErrorString(dev.e != hipSuccess ? dev.e : hipErrorUnknown));
+            (void)hipGetLastError();
+        }
+        (void)hipStreamSynchronize(ctx->stream);
+        if (dev.timing) fprintf(stderr, "[lrge_hip] zstd stages ms: heads %.3f literals %.3f sequences %.3f execute %.3f resolve %.3f checksum %.3f\n", dev.ms[0], dev.ms[1],
+                                dev.ms[2], dev.ms[3], dev.ms[4], dev.ms[5]);
+        zs_stats_out(st, dev, stats);
+    }
+    if (rc == ZS_RUN_OK) return LRGE_OK;
+    if (sink_stop) { ctx->err = "zstd inflate: the sink stopped the call"; return LRGE_ERR_IO; }
+    if (rc == ZS_RUN_DEVICE) return LRGE_ERR_DEVICE;
+    if (rc == ZS_E_TOO_BIG) { ctx->err = "zstd inflate: the text does not fit the device budget"; return LRGE_ERR_TOO_MANY; }
+    LRGE_SET_ERR(ctx, "zstd data at file offset %llu: %s", (unsigned long long)bad, zs_status_name(rc));
+    return LRGE_ERR_PARSE;
+}
+
+extern "C" int lrge_hip_zstd_inflate(lrge_hip_ctx *ctx, const void *comp, uint64_t comp_len, int (*sink)(void *user, const void *bytes, uint64_t n),
+                                     void *user, lrge_hip_zstd_stats *stats) {
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (!ctx || !sink || (!comp && comp_len)) return LRGE_ERR_INVALID;
+    return zstd_inflate_impl(ctx, (const uint8_t *)comp, comp_len, sink, user, stats);
+}
