@@ -485,13 +485,55 @@ typedef struct lrge_hip_zstd_stats {
 int  lrge_hip_zstd_inflate(lrge_hip_ctx *ctx, const void *comp, uint64_t comp_len, int (*sink)(void *user, const void *bytes, uint64_t n),
                            void *user, lrge_hip_zstd_stats *stats);
 
+/* xz decompressed on the device (k_xz_decode, k_xz_check): the host walks the stream footers, the indexes, the
+   block headers and the LZMA2 chunk headers, which gives every block's place in the text before a byte is decoded and verifies
+   the whole container; the blocks of a round are decoded at once, one wavefront per block, the adaptive range decoder serial
+   inside a block; a block's check is CRC32 or CRC64 over its text.
+   lrge_hip_xz_inflate has the contract of lrge_hip_zstd_inflate: the bytes arrive in order through `sink` (a nonzero return stops
+   the call with LRGE_ERR_IO); on a non-OK return the bytes delivered so far are void; there is no host fall-back inside the call.
+   The device accepts a subset of what the host reader takes (liblzma with LZMA_CONCATENATED), and returns the same bytes: one or
+   more streams, stream padding in multiples of four bytes between and behind them, streams of no block, block headers with or
+   without the size fields, the filter chain of LZMA2 alone at any dictionary size, the checks none, CRC32 and CRC64, every LZMA2
+   control byte.  LRGE_ERR_PARSE (`xz data at file offset N: <status name>`): another filter or more than one, a SHA-256 or
+   reserved check, reserved bits, a wrong header, footer, index or block header CRC32, flags that differ, a bad index or padding,
+   sizes that do not agree, a first chunk without a dictionary reset, an LZMA chunk with no properties in force, lc + lp > 4, a
+   distance beyond the dictionary or its size, the end marker, a match that crosses its chunk, a range decoder whose first byte is
+   not 0 or that does not end with code 0 exactly at the chunk's compressed size, a wrong check, truncation, bytes that are neither
+   a stream nor padding, fewer blocks than XZ_MIN_BLOCKS.  LRGE_ERR_TOO_MANY: the text of one round does not fit the device budget
+   (half of the free device memory plus the context's idle arena bytes); the caller takes the host.  LRGE_ERR_DEVICE: a runtime
+   failure.  Options XZ_ROUND_BLOCKS: blocks decoded per round (default: what half of the free device memory plus the idle arena
+   bytes holds, at most 4096); XZ_LAUNCH_BYTES: the text a block may produce per kernel launch, in whole chunks, one chunk at
+   least (default 2 MiB, the format's largest chunk, so no launch runs longer than one chunk per wavefront); XZ_CHECK (default 1):
+   0 skips the block checks; XZ_MIN_BLOCKS (default 64, the measured
+   break-even against liblzma on one thread: BASELINE section 13): a file with fewer blocks is refused.  *stats (may be NULL) receives the
+   counts of the call.  lrge_hip_read_records_gpu_ex | LRGE_GPU_INFLATE_XZ sends xz input to this decoder and falls back to the
+   unchanged host path for anything it does not accept; lrge_hip_reads_open* | LRGE_GPU_INFLATE_XZ keeps the text in HBM, and with
+   LRGE_GPU_INGEST_WINDOWED every finished round passes through the windows (a block needs no earlier text).  Not verified: text
+   of 4 GiB or more. */
+typedef struct lrge_hip_xz_stats {
+    uint64_t streams;             /* .xz streams */
+    uint64_t blocks;              /* blocks decoded */
+    uint64_t chunks;              /* LZMA2 chunks of the file */
+    uint64_t raw_chunks;          /* of them uncompressed chunks */
+    uint64_t checks_checked;      /* blocks whose CRC32 / CRC64 was computed and compared (0 with XZ_CHECK=0) */
+    uint64_t rounds;              /* rounds of at most XZ_ROUND_BLOCKS blocks */
+    uint64_t launches;            /* launches of k_xz_decode */
+    uint64_t bytes_out;           /* decompressed bytes */
+    uint64_t check_us;            /* microseconds spent in k_xz_check, launch to result */
+    uint64_t decode_us;           /* microseconds spent in k_xz_decode, launch to result */
+    uint64_t walk_us;             /* microseconds of the host's walk over the container */
+} lrge_hip_xz_stats;
+#define LRGE_GPU_INFLATE_XZ 256
+int  lrge_hip_xz_inflate(lrge_hip_ctx *ctx, const void *comp, uint64_t comp_len, int (*sink)(void *user, const void *bytes, uint64_t n),
+                         void *user, lrge_hip_xz_stats *stats);
+
 /* Read sets built on the device from FASTA / FASTQ text (k_fx_census, k_fx_summary, k_fx_scatter, k_fx_records,
    k_fx_names, k_fx_gather) and from unaligned BAM (k_bam_header, k_bam_find, k_bam_walk, k_bam_records,
    k_bam_gather; SAM, DESIGN section 14: k_sam_mark, k_sam_records): the device-side form of the record reader (io.rs:154-184) and of the read selection that feeds the
    strategies (twoset.rs:122-201).  The file's bytes are decompressed into HBM and stay there; the records are found there; only
    the identifiers and the sequence lengths come back.
    lrge_hip_reads_open (io.rs:154-184) reads `path` into memory and calls lrge_hip_reads_open_mem (io.rs:154-184), which takes the
-   bytes of a whole file.  `flags`: LRGE_GPU_INFLATE_BGZF | LRGE_GPU_INFLATE_GZIP | LRGE_GPU_INFLATE_BZIP2 | LRGE_GPU_INFLATE_ZSTD choose the device decoders as in
+   bytes of a whole file.  `flags`: LRGE_GPU_INFLATE_BGZF | LRGE_GPU_INFLATE_GZIP | LRGE_GPU_INFLATE_BZIP2 | LRGE_GPU_INFLATE_ZSTD | LRGE_GPU_INFLATE_XZ choose the device decoders as in
    lrge_hip_read_records_gpu_ex; with neither, only uncompressed input is taken.  | LRGE_GPU_INGEST_BAM: text that starts with
    the BAM magic is scanned as unaligned BAM (every record with flag 4, found by a speculative walk of the length chain that
    is proven from the end of the header); without the flag BAM is unproven, as it was before the flag existed.
@@ -501,7 +543,7 @@ int  lrge_hip_zstd_inflate(lrge_hip_ctx *ctx, const void *comp, uint64_t comp_le
    and produces no parse error of its own -- anything but FASTA, strict four-line FASTQ or (with its flag) well-formed unaligned
    BAM (an empty line between records, a truncated record, a missing '+', CRAM, BAM without LRGE_GPU_INGEST_BAM, a BAM
    with a mapped record, a damaged header or record, or bytes behind the last record, SAM without LRGE_GPU_INGEST_SAM, a SAM
-   record line with fewer than ten tabs, with a flag that is not plain digits or with a mapped flag), a compressed format without its flag or other than gzip, (with LRGE_GPU_INFLATE_BZIP2) bzip2 and (with LRGE_GPU_INFLATE_ZSTD) Zstandard, a damaged gzip file, a bzip2 or Zstandard file the device decoder does not accept, text above option INGEST_MAX_BYTES
+   record line with fewer than ten tabs, with a flag that is not plain digits or with a mapped flag), a compressed format without its flag or other than gzip, (with LRGE_GPU_INFLATE_BZIP2) bzip2, (with LRGE_GPU_INFLATE_ZSTD) Zstandard and (with LRGE_GPU_INFLATE_XZ) xz, a damaged gzip file, a bzip2, Zstandard or xz file the device decoder does not accept, text above option INGEST_MAX_BYTES
    (default: half of the free device memory plus the context's idle arena bytes); the caller takes lrge_hip_read_records*, which
    parses the file or gives the reference's message.  LRGE_ERR_TOO_MANY: 2^32 records or more, or a sequence of 2^32 bases or
    more.  LRGE_ERR_IO: the file cannot be read.  An empty file is LRGE_OK with a count of 0.

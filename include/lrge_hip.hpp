@@ -78,7 +78,7 @@ struct Ctx {
 // The records of one FASTA / FASTQ file (or, with | LRGE_GPU_INGEST_BAM / LRGE_GPU_INGEST_SAM, one unaligned BAM / SAM) parsed on the device;
 // | LRGE_GPU_INGEST_WINDOWED: FASTA / FASTQ text above option INGEST_WINDOW_BYTES passes through in windows and only the bases stay;
 // | LRGE_GPU_INGEST_WINDOWED_ALN beside it and the format's flag: unaligned BAM (its bases kept packed) and SAM as well;
-// | LRGE_GPU_INFLATE_BZIP2, | LRGE_GPU_INFLATE_ZSTD: bzip2 and Zstandard input decompressed on the device too (Zstandard text is never windowed)
+// | LRGE_GPU_INFLATE_BZIP2, | LRGE_GPU_INFLATE_ZSTD, | LRGE_GPU_INFLATE_XZ: bzip2, Zstandard and xz input decompressed on the device too (Zstandard text is never windowed)
 // (lrge_hip_reads_open, io.rs:154-184): identifiers and lengths on
 // the host, the bases resident in HBM as text.  Owns its context; the strategies built on it run in that context and take
 // their read sets with lrge_hip_seqset_from_reads.  open() gives nullptr for input the device does not prove (and for a file
@@ -190,6 +190,7 @@ using ::lrge::unique_random_set;
 // device failure throws.  The hook owns a context on `device` for as long as it lives.
 namespace detail {
 inline bool is_zstd(const std::string &raw) { return raw.size() >= 4 && (unsigned char)raw[0] == 0x28 && (unsigned char)raw[1] == 0xb5 && (unsigned char)raw[2] == 0x2f && (unsigned char)raw[3] == 0xfd; }
+inline bool is_xz(const std::string &raw) { return raw.size() >= 6 && std::memcmp(raw.data(), "\xfd" "7zXZ\0", 6) == 0; }
 inline bool is_bzip2(const std::string &raw) { return raw.size() >= 2 && raw[0] == 0x42 && raw[1] == 0x5a; }   // (lrge_io.hpp: detect_compression_format)
 inline bool bgzf_inflate_with(Ctx &ctx, const std::string &raw, std::string &out) {
     uint64_t total = 0;
@@ -213,7 +214,7 @@ inline std::function<bool(const std::string &, std::string &)> bgzf_inflater(int
 inline std::function<bool(const std::string &, std::string &)> gzip_inflater(int device) {
     auto ctx = std::make_shared<detail::Ctx>(device);            // one context for both device paths
     return [ctx](const std::string &raw, std::string &out) -> bool {
-        if (detail::is_bzip2(raw) || detail::is_zstd(raw)) return false;
+        if (detail::is_bzip2(raw) || detail::is_zstd(raw) || detail::is_xz(raw)) return false;
         if (lrge_hip_bgzf_scan(raw.data(), raw.size(), nullptr, nullptr) == LRGE_OK) return detail::bgzf_inflate_with(*ctx, raw, out);
         out.clear();
         const int rc = lrge_hip_gzip_inflate(ctx->h, raw.data(), raw.size(), [](void *u, const void *b, uint64_t n) {
@@ -253,6 +254,24 @@ inline std::function<bool(const std::string &, std::string &)> zstd_inflater(int
         if (!detail::is_zstd(raw)) return other ? other(raw, out) : false;
         out.clear();
         const int rc = lrge_hip_zstd_inflate(ctx->h, raw.data(), raw.size(), [](void *u, const void *b, uint64_t n) {
+            static_cast<std::string *>(u)->append(static_cast<const char *>(b), (size_t)n);
+            return 0;
+        }, &out, nullptr);
+        if (rc == LRGE_ERR_PARSE || rc == LRGE_ERR_TOO_MANY) { out.clear(); return false; }
+        ctx->check(rc);
+        return true;
+    };
+}
+
+// xz input decompressed on the device (lrge_hip_xz_inflate); every other input goes to `other` when one is given (zstd_inflater,
+// bzip2_inflater, gzip_inflater, bgzf_inflater).  False (the host path decompresses, with its messages) for input the device
+// does not accept or that does not fit its budget; a device failure throws.
+inline std::function<bool(const std::string &, std::string &)> xz_inflater(int device, std::function<bool(const std::string &, std::string &)> other = nullptr) {
+    auto ctx = std::make_shared<detail::Ctx>(device);
+    return [ctx, other](const std::string &raw, std::string &out) -> bool {
+        if (!detail::is_xz(raw)) return other ? other(raw, out) : false;
+        out.clear();
+        const int rc = lrge_hip_xz_inflate(ctx->h, raw.data(), raw.size(), [](void *u, const void *b, uint64_t n) {
             static_cast<std::string *>(u)->append(static_cast<const char *>(b), (size_t)n);
             return 0;
         }, &out, nullptr);

@@ -337,7 +337,7 @@ inline void iter_records(const std::string &path, const Callback &cb) {   // io.
     }
 }
 
-// The same records, with a hook that may decompress gzip, bzip2 or Zstandard input itself (lrge_hip.hpp: the device's decoders).  The hook
+// The same records, with a hook that may decompress gzip, bzip2, Zstandard or xz input itself (lrge_hip.hpp: the device's decoders).  The hook
 // gets the file's bytes; it returns true with the decompressed bytes in `out`, or false, and the host path decompresses.
 using Inflater = std::function<bool(const std::string &raw, std::string &out)>;
 
@@ -345,7 +345,7 @@ inline void iter_records(const std::string &path, const Callback &cb, const Infl
     const std::string raw = slurp(path);
     std::string data;
     const CompressionFormat fmt = detect_compression_format(raw);
-    if (!(inflate && (fmt == CompressionFormat::Gzip || fmt == CompressionFormat::Bzip2 || fmt == CompressionFormat::Zstd) && inflate(raw, data))) data = decompress(raw);
+    if (!(inflate && (fmt == CompressionFormat::Gzip || fmt == CompressionFormat::Bzip2 || fmt == CompressionFormat::Zstd || fmt == CompressionFormat::Xz) && inflate(raw, data))) data = decompress(raw);
     switch (sniff(data)) {
     case Kind::Bam: detail::parse_bam(data, cb); break;
     case Kind::Sam: detail::parse_sam(data, cb); break;

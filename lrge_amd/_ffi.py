@@ -16,6 +16,7 @@ GPU_INGEST_BAM = 4
 GPU_INGEST_SAM = 8
 GPU_INFLATE_BZIP2 = 16
 GPU_INFLATE_ZSTD = 128
+GPU_INFLATE_XZ = 256
 GPU_INGEST_WINDOWED = 32
 GPU_INGEST_WINDOWED_ALN = 64
 PRESET_AVA_ONT, PRESET_AVA_PB = 0, 1
@@ -30,9 +31,11 @@ C_NAMES = ["query_bases", "query_minimizers", "anchors", "groups", "groups_chain
 BZIP2_STAT_NAMES = ["blocks", "candidates", "rejected_candidates", "rounds", "bytes_out"]   # lrge_hip_bzip2_stats
 ZSTD_STAT_NAMES = ["frames", "skippable_frames", "blocks", "raw_blocks", "rle_blocks", "sequences", "checksums_checked", "rounds", "bytes_out",
                    "checksum_us"]   # lrge_hip_zstd_stats
+XZ_STAT_NAMES = ["streams", "blocks", "chunks", "raw_chunks", "checks_checked", "rounds", "launches", "bytes_out", "check_us", "decode_us",
+                 "walk_us"]   # lrge_hip_xz_stats
 BAM_STAT_NAMES = ["segments", "empty_segments", "speculative_starts", "rejected_starts", "repair_rounds", "rewalked_segments"]   # lrge_hip_bam_stats
 
-# int (*sink)(void *user, const void *bytes, uint64_t n) of lrge_hip_gzip_inflate, lrge_hip_bzip2_inflate and lrge_hip_zstd_inflate
+# int (*sink)(void *user, const void *bytes, uint64_t n) of lrge_hip_gzip_inflate, lrge_hip_bzip2_inflate, lrge_hip_zstd_inflate and lrge_hip_xz_inflate
 GZIP_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)
 
 EXPORTS = [
@@ -40,7 +43,7 @@ EXPORTS = [
     "lrge_hip_seqset_upload", "lrge_hip_seqset_upload_async", "lrge_hip_seqset_wait", "lrge_hip_host_alloc",
     "lrge_hip_host_free", "lrge_hip_seqset_free", "lrge_hip_seqset_size", "lrge_hip_seqset_presketch", "lrge_hip_seqset_presketch_sharded", "lrge_hip_pack_choice", "lrge_hip_read_records",
     "lrge_hip_bgzf_scan", "lrge_hip_bgzf_inflate", "lrge_hip_read_records_gpu",
-    "lrge_hip_gzip_inflate", "lrge_hip_read_records_gpu_ex", "lrge_hip_bzip2_inflate", "lrge_hip_zstd_inflate",
+    "lrge_hip_gzip_inflate", "lrge_hip_read_records_gpu_ex", "lrge_hip_bzip2_inflate", "lrge_hip_zstd_inflate", "lrge_hip_xz_inflate",
     "lrge_hip_reads_open", "lrge_hip_reads_open_mem", "lrge_hip_reads_count", "lrge_hip_reads_name_bytes", "lrge_hip_reads_text_bytes",
     "lrge_hip_reads_table", "lrge_hip_reads_timings", "lrge_hip_reads_bam_stats", "lrge_hip_reads_window_stats", "lrge_hip_seqset_from_reads", "lrge_hip_reads_free",
     "lrge_hip_name_ranks", "lrge_hip_reads_name_ranks",
@@ -114,6 +117,7 @@ def lib():
     L.lrge_hip_gzip_inflate.argtypes = [vp, vp, C.c_uint64, GZIP_SINK, vp, vp]
     L.lrge_hip_bzip2_inflate.argtypes = [vp, vp, C.c_uint64, GZIP_SINK, vp, vp]
     L.lrge_hip_zstd_inflate.argtypes = [vp, vp, C.c_uint64, GZIP_SINK, vp, vp]
+    L.lrge_hip_xz_inflate.argtypes = [vp, vp, C.c_uint64, GZIP_SINK, vp, vp]
     L.lrge_hip_reads_open.argtypes = [vp, C.c_char_p, C.c_int, C.POINTER(vp)]
     L.lrge_hip_reads_open_mem.argtypes = [vp, vp, C.c_uint64, C.c_int, C.POINTER(vp)]
     for f in (L.lrge_hip_reads_count, L.lrge_hip_reads_name_bytes, L.lrge_hip_reads_text_bytes):

@@ -48,6 +48,7 @@ NAMES_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_names_twin.so")
 BZIP2_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_bzip2_twin.so")
 NAMES_LSD_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_names_lsd_twin.so")
 ZSTD_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_zstd_twin.so")
+XZ_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_xz_twin.so")
 
 
 def _build_twin(out, main, force):
@@ -61,10 +62,10 @@ def _build_twin(out, main, force):
 
 
 def build_twin(force=False):
-    """The host twins, all nine: of k_inflate (csrc/inflate_twin.cpp, the same bit-level core), and of the speculative gzip
+    """The host twins, all ten: of k_inflate (csrc/inflate_twin.cpp, the same bit-level core), and of the speculative gzip
     decode (build_gzip_twin), of the FASTA / FASTQ record scan (build_fastx_twin), of the BAM record scan (build_bam_twin), of
     the SAM record scan (build_sam_twin), of the identifier ranking by refinement (build_names_twin) and by fixed LSD passes (build_names_lsd_twin)
-    and of the bzip2 decode (build_bzip2_twin) and the Zstandard decode (build_zstd_twin)."""
+    and of the bzip2 decode (build_bzip2_twin), the Zstandard decode (build_zstd_twin) and the xz decode (build_xz_twin)."""
     build_gzip_twin(force)
     build_fastx_twin(force)
     build_bam_twin(force)
@@ -73,6 +74,7 @@ def build_twin(force=False):
     build_names_lsd_twin(force)
     build_bzip2_twin(force)
     build_zstd_twin(force)
+    build_xz_twin(force)
     return _build_twin(TWIN_PATH, "inflate_twin.cpp", force)
 
 
@@ -115,6 +117,11 @@ def build_bzip2_twin(force=False):
 def build_zstd_twin(force=False):
     """The host twin of the block-parallel Zstandard decode (csrc/zs_twin.cpp): the same core and the same driver of the rounds."""
     return _build_twin(ZSTD_TWIN_PATH, "zs_twin.cpp", force)
+
+
+def build_xz_twin(force=False):
+    """The host twin of the block-parallel xz decode (csrc/xz_twin.cpp): the same core and the same driver of the rounds."""
+    return _build_twin(XZ_TWIN_PATH, "xz_twin.cpp", force)
 
 
 CLI_PATH = os.path.join(LIB_DIR, "lrge-hip")

@@ -502,11 +502,12 @@ static int fx_src_bgzf(FxSink &s, const u8 *d, const std::vector<BgzfBlock> &t, 
     return LRGE_OK;
 }
 
-// gzip and bzip2: the rounds of the decoder's driver (run(&bad): gz_run, bz_run) with the decoder `dev` (GzDev, BzDev) keeping
+// gzip, bzip2, Zstandard and xz: the rounds of the decoder's driver (run(&bad): gz_run, bz_run, zs_run, xz_run) with the decoder `dev` keeping
 // every round's text in its own block (dev_keep.h), which becomes the handle's.  A windowed call flushes that block through the
 // sink's run whenever a round has been appended (DevKeep::keep_flush); whether its windows stay on is the first flush's sniff.
 // refused: the message for a stream the decoder does not take, with status(rc) and the file offset
-static_assert((int)GZ_RUN_OK == (int)BZ_RUN_OK && (int)GZ_RUN_DEVICE == (int)BZ_RUN_DEVICE && (int)GZ_RUN_OK == (int)ZS_RUN_OK && (int)GZ_RUN_DEVICE == (int)ZS_RUN_DEVICE, "one set of driver codes");
+static_assert((int)GZ_RUN_OK == (int)BZ_RUN_OK && (int)GZ_RUN_DEVICE == (int)BZ_RUN_DEVICE && (int)GZ_RUN_OK == (int)ZS_RUN_OK && (int)GZ_RUN_DEVICE == (int)ZS_RUN_DEVICE &&
+              (int)GZ_RUN_OK == (int)XZ_RUN_OK && (int)GZ_RUN_DEVICE == (int)XZ_RUN_DEVICE, "one set of driver codes");
 template <class Dev, class Run, class Status>
 static int fx_inflate_to_device(FxSink &s, Dev &dev, Run run, const char *codec, const char *refused, Status status) {
     lrge_hip_ctx *ctx = s.ctx;
@@ -565,6 +566,17 @@ static int fx_src_zstd(FxSink &s, const u8 *d, u64 len) {
     return rc;
 }
 
+// xz: a block needs no earlier text, so a windowed call flushes every finished round through the sink's windows, as for bzip2
+static int fx_src_xz(FxSink &s, const u8 *d, u64 len) {
+    XzStats st;
+    XzDev dev(s.ctx);
+    dev.to_host = false;
+    const int rc = fx_inflate_to_device(s, dev, [&](u64 *bad) { return xz_run(dev, d, len, xz_cfg(s.ctx), [](const uint8_t *, uint64_t) { return true; }, st, bad); },
+                                        "xz", "reads_open: xz data not accepted by the device (%s near file offset %llu)", xz_status_name);
+    if (s.ctx->opt("VERBOSE")) fprintf(stderr, "[lrge_hip] reads_open: xz decode %.2f ms, block checks %.2f ms of the text-to-HBM share\n", dev.ms[1], dev.ms[2]);
+    return rc;
+}
+
 // ---- the two ends of a call ----  windows were flushed: the rest of the block is the last, the store the handle's text
 static int fx_finish_windowed(FxSink &s, double t0) {
     lrge_hip_reads *R = s.R;
@@ -617,6 +629,7 @@ extern "C" int lrge_hip_reads_open_mem(lrge_hip_ctx *ctx, const void *file_bytes
     if (b(0) == 0x1f && b(1) == 0x8b) rc = bgzf_scan_blocks(d, len, &t, &total) ? fx_src_bgzf(s, d, t, total) : fx_src_gzip(s, d, len);
     else if (b(0) == 0x42 && b(1) == 0x5a && (flags & LRGE_GPU_INFLATE_BZIP2)) rc = fx_src_bzip2(s, d, len);
     else if (b(0) == 0x28 && b(1) == 0xb5 && b(2) == 0x2f && b(3) == 0xfd && (flags & LRGE_GPU_INFLATE_ZSTD)) rc = fx_src_zstd(s, d, len);
+    else if (b(0) == 0xfd && b(1) == 0x37 && b(2) == 0x7a && b(3) == 0x58 && b(4) == 0x5a && b(5) == 0x00 && (flags & LRGE_GPU_INFLATE_XZ)) rc = fx_src_xz(s, d, len);
     else if ((b(0) == 0x42 && b(1) == 0x5a) || (b(0) == 0x28 && b(1) == 0xb5 && b(2) == 0x2f && b(3) == 0xfd) ||
              (b(0) == 0xfd && b(1) == 0x37 && b(2) == 0x7a && b(3) == 0x58 && b(4) == 0x5a)) {
         ctx->err = "reads_open: bzip2, zstd and xz input is decompressed on the host";

@@ -224,6 +224,9 @@ static int bzip2_inflate_impl(lrge_hip_ctx *ctx, const uint8_t *comp, uint64_t c
 // (host_zstd.inl)
 static int zstd_inflate_impl(lrge_hip_ctx *ctx, const uint8_t *comp, uint64_t comp_len, int (*sink)(void *, const void *, uint64_t), void *user,
                              lrge_hip_zstd_stats *stats);
+// (host_xz.inl)
+static int xz_inflate_impl(lrge_hip_ctx *ctx, const uint8_t *comp, uint64_t comp_len, int (*sink)(void *, const void *, uint64_t), void *user,
+                           lrge_hip_xz_stats *stats);
 
 extern "C" int lrge_hip_read_records_gpu_ex(lrge_hip_ctx *ctx, const char *path, int flags,
                                             void (*cb)(void *, const char *, uint64_t, const char *, uint64_t), void *user, int *used_device) {
@@ -250,6 +253,18 @@ extern "C" int lrge_hip_read_records_gpu_ex(lrge_hip_ctx *ctx, const char *path,
                 if (!(flags & LRGE_GPU_INFLATE_ZSTD)) return false;
                 data.clear();
                 const int rc = zstd_inflate_impl(ctx, (const uint8_t *)raw.data(), raw.size(), [](void *u, const void *b, uint64_t k) {
+                    ((std::string *)u)->append((const char *)b, (size_t)k);
+                    return 0;
+                }, &data, nullptr);
+                if (rc == LRGE_ERR_DEVICE) throw DeviceFail{rc};
+                if (rc != LRGE_OK) { data.clear(); return false; }     // not accepted by the device: the host path, with its messages
+                used = 1;
+                return true;
+            }
+            if (lrge::io::detect_compression_format(raw) == lrge::io::CompressionFormat::Xz) {
+                if (!(flags & LRGE_GPU_INFLATE_XZ)) return false;
+                data.clear();
+                const int rc = xz_inflate_impl(ctx, (const uint8_t *)raw.data(), raw.size(), [](void *u, const void *b, uint64_t k) {
                     ((std::string *)u)->append((const char *)b, (size_t)k);
                     return 0;
                 }, &data, nullptr);

@@ -30,6 +30,7 @@
 #include "k_gzip.h"
 #include "k_bzip2.h"
 #include "k_zstd.h"
+#include "k_xz.h"
 #include "k_fastx.h"
 #include "k_bam.h"
 #include "k_sam.h"
@@ -232,5 +233,6 @@ extern "C" int lrge_hip_last_counters(const lrge_hip_ctx *ctx, uint64_t c[LRGE_C
 #include "host_gzip.inl"
 #include "host_bzip2.inl"
 #include "host_zstd.inl"
+#include "host_xz.inl"
 #include "host_fastx.inl"
 #include "host_names.inl"

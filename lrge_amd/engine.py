@@ -124,9 +124,25 @@ class Context:
         self._check(self._lib.lrge_hip_zstd_inflate(self.h, data, len(data), cb, None, C.cast(st, C.c_void_p)))
         return b"".join(parts), dict(zip(_ffi.ZSTD_STAT_NAMES, list(st)))
 
+    def xz_inflate(self, data):
+        """An .xz buffer (streams and stream padding back to back) decompressed on the device (lrge_hip_xz_inflate): bytes in,
+        (bytes, dict of lrge_hip_xz_stats) out.  Input the device does not accept (damage, a filter other than LZMA2, a SHA-256
+        check, trailing bytes, fewer blocks than option XZ_MIN_BLOCKS) raises LrgeHipError with code ERR_PARSE; a round's text
+        above the device budget ERR_TOO_MANY."""
+        data = bytes(data)
+        parts = []
+
+        def sink(_user, p, n):
+            parts.append(C.string_at(p, n))
+            return 0
+        cb = _ffi.GZIP_SINK(sink)
+        st = (C.c_uint64 * len(_ffi.XZ_STAT_NAMES))()
+        self._check(self._lib.lrge_hip_xz_inflate(self.h, data, len(data), cb, None, C.cast(st, C.c_void_p)))
+        return b"".join(parts), dict(zip(_ffi.XZ_STAT_NAMES, list(st)))
+
     def open_reads(self, path_or_bytes, flags=_ffi.GPU_INFLATE_BGZF | _ffi.GPU_INFLATE_GZIP):
         """A FASTA / FASTQ file (a path, or the bytes of the whole file) parsed on the device: plain, BGZF or any other gzip
-        (| _ffi.GPU_INFLATE_BZIP2: bzip2 as well; | _ffi.GPU_INFLATE_ZSTD: Zstandard as well, always resident), by `flags` (lrge_hip_reads_open*); | _ffi.GPU_INGEST_BAM takes unaligned BAM as well, | _ffi.GPU_INGEST_SAM unaligned SAM; | _ffi.GPU_INGEST_WINDOWED lets FASTA / FASTQ text above option INGEST_WINDOW_BYTES pass through in windows with only the bases kept (DeviceReads.window_stats), and | _ffi.GPU_INGEST_WINDOWED_ALN beside it and the format's own flag does the same for unaligned BAM (its bases kept packed, 4 bits each) and SAM.  Returns a DeviceReads with names, lens and seqset().  Input the device does not
+        (| _ffi.GPU_INFLATE_BZIP2: bzip2 as well; | _ffi.GPU_INFLATE_ZSTD: Zstandard as well, always resident; | _ffi.GPU_INFLATE_XZ: xz as well), by `flags` (lrge_hip_reads_open*); | _ffi.GPU_INGEST_BAM takes unaligned BAM as well, | _ffi.GPU_INGEST_SAM unaligned SAM; | _ffi.GPU_INGEST_WINDOWED lets FASTA / FASTQ text above option INGEST_WINDOW_BYTES pass through in windows with only the bases kept (DeviceReads.window_stats), and | _ffi.GPU_INGEST_WINDOWED_ALN beside it and the format's own flag does the same for unaligned BAM (its bases kept packed, 4 bits each) and SAM.  Returns a DeviceReads with names, lens and seqset().  Input the device does not
         prove raises UnprovenInput: read the file with the host readers (readio.load) instead."""
         return DeviceReads(self, path_or_bytes, flags)
 

@@ -13,15 +13,16 @@
 #include "../include/lrge_hip.hpp"
 #include "../include/lrge_io.hpp"
 
-static lrge::Reads load_reads(const std::string &path, bool gpu_inflate, bool gpu_gzip, bool gpu_bzip2, bool gpu_zstd, int device) {   // io.rs:154-184 via include/lrge_io.hpp
+static lrge::Reads load_reads(const std::string &path, bool gpu_inflate, bool gpu_gzip, bool gpu_bzip2, bool gpu_zstd, bool gpu_xz, int device) {   // io.rs:154-184 via include/lrge_io.hpp
     lrge::Reads r;
     try {
         auto add = [&](const std::string &name, const std::string &seq) { r.names.push_back(name); r.seqs.push_back(seq); };
-        if (gpu_zstd) lrge::io::iter_records(path, add, lrge::zstd_inflater(device, gpu_bzip2 ? lrge::bzip2_inflater(device, gpu_gzip ? lrge::gzip_inflater(device) : gpu_inflate ? lrge::bgzf_inflater(device) : nullptr)
-                                                                                          : gpu_gzip ? lrge::gzip_inflater(device) : gpu_inflate ? lrge::bgzf_inflater(device) : nullptr));   // Zstandard on the device, the rest as the other flags say
-        else if (gpu_bzip2) lrge::io::iter_records(path, add, lrge::bzip2_inflater(device, gpu_gzip ? lrge::gzip_inflater(device) : gpu_inflate ? lrge::bgzf_inflater(device) : nullptr));   // bzip2 on the device, gzip as the other flags say
-        else if (gpu_gzip) lrge::io::iter_records(path, add, lrge::gzip_inflater(device));     // every gzip input on the device
-        else if (gpu_inflate) lrge::io::iter_records(path, add, lrge::bgzf_inflater(device));   // BGZF decompressed on the device
+        // gzip as its two flags say (every gzip input, or BGZF alone), then bzip2, Zstandard and xz in front of it, each on the device by its own flag
+        std::function<bool(const std::string &, std::string &)> hook = gpu_gzip ? lrge::gzip_inflater(device) : gpu_inflate ? lrge::bgzf_inflater(device) : nullptr;
+        if (gpu_bzip2) hook = lrge::bzip2_inflater(device, hook);
+        if (gpu_zstd) hook = lrge::zstd_inflater(device, hook);
+        if (gpu_xz) hook = lrge::xz_inflater(device, hook);
+        if (hook) lrge::io::iter_records(path, add, hook);
         else lrge::io::iter_records(path, add);
     } catch (const lrge::io::IoError &e) {
         throw lrge::LrgeError(LRGE_ERR_IO, e.what());
@@ -62,7 +63,7 @@ int main(int argc, char **argv) {
     bool T_set = false, Q_set = false, filter = false, with_inf = false, precise = false, use_min_ref = false, honour_platform = false;
     float q1 = lrge::LOWER_QUANTILE, q3 = lrge::UPPER_QUANTILE, ratio = 0.2f;
     size_t threads = 1; std::optional<uint64_t> seed; int quiet = 0, verbose = 0, device = 0;
-    bool keep_temp = false, dump_records = false, gpu_inflate = false, gpu_gzip = false, gpu_bzip2 = false, gpu_zstd = false, gpu_ingest = false, gpu_names = false; std::string temp_dir;
+    bool keep_temp = false, dump_records = false, gpu_inflate = false, gpu_gzip = false, gpu_bzip2 = false, gpu_zstd = false, gpu_xz = false, gpu_ingest = false, gpu_names = false; std::string temp_dir;
     auto need = [&](int &i) -> const char * { if (i + 1 >= argc) { fprintf(stderr, "error: missing value for %s\n", argv[i]); exit(2); } return argv[++i]; };
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -86,6 +87,7 @@ int main(int argc, char **argv) {
         else if (a == "--device") device = atoi(need(i));
         else if (a == "--gpu-inflate") gpu_inflate = true;       // BGZF input (BAM, bgzip FASTQ) decompressed on --device
         else if (a == "--gpu-gzip") gpu_gzip = true;             // every gzip input (plain, multi-member, BGZF) decompressed on --device
+        else if (a == "--gpu-xz") gpu_xz = true;                 // xz input decompressed on --device (with --gpu-ingest: kept in HBM); not implied by --gpu-ingest
         else if (a == "--gpu-zstd") gpu_zstd = true;             // Zstandard input decompressed on --device (with --gpu-ingest: kept in HBM); not implied by --gpu-ingest
         else if (a == "--gpu-bzip2") gpu_bzip2 = true;           // bzip2 input decompressed on --device (with --gpu-ingest: kept in HBM)
         else if (a == "--gpu-ingest") { gpu_ingest = true; gpu_gzip = true; }   // FASTA / FASTQ / unaligned BAM / unaligned SAM parsed on --device too: the bases never reach host memory (implies --gpu-gzip)
@@ -111,12 +113,12 @@ int main(int argc, char **argv) {
         // --gpu-ingest: input the device does not prove takes the usual route below, which parses it or reports it
         std::unique_ptr<lrge::DeviceReads> dev;
         if (gpu_ingest) {
-            dev = lrge::DeviceReads::open(input, LRGE_GPU_INFLATE_BGZF | LRGE_GPU_INFLATE_GZIP | LRGE_GPU_INGEST_BAM | LRGE_GPU_INGEST_SAM | LRGE_GPU_INGEST_WINDOWED | LRGE_GPU_INGEST_WINDOWED_ALN | (gpu_bzip2 ? LRGE_GPU_INFLATE_BZIP2 : 0) | (gpu_zstd ? LRGE_GPU_INFLATE_ZSTD : 0), device);
+            dev = lrge::DeviceReads::open(input, LRGE_GPU_INFLATE_BGZF | LRGE_GPU_INFLATE_GZIP | LRGE_GPU_INGEST_BAM | LRGE_GPU_INGEST_SAM | LRGE_GPU_INGEST_WINDOWED | LRGE_GPU_INGEST_WINDOWED_ALN | (gpu_bzip2 ? LRGE_GPU_INFLATE_BZIP2 : 0) | (gpu_zstd ? LRGE_GPU_INFLATE_ZSTD : 0) | (gpu_xz ? LRGE_GPU_INFLATE_XZ : 0), device);
             if (info) fprintf(stderr, "[INFO] gpu-ingest: %s\n", dev ? "device" : "host");
             if (dev && dev->names.empty()) throw lrge::LrgeError(LRGE_ERR_IO, "IO error: Is the file empty?");
         }
         lrge::Reads reads;
-        if (!dev) reads = load_reads(input, gpu_inflate, gpu_gzip, gpu_bzip2, gpu_zstd, device);
+        if (!dev) reads = load_reads(input, gpu_inflate, gpu_gzip, gpu_bzip2, gpu_zstd, gpu_xz, device);
         const lrge::Platform pf = (honour_platform && platform == "pb") ? lrge::Platform::PacBio : lrge::Platform::Nanopore;
         lrge::twoset::TwoSetStrategy ts = dev ? lrge::twoset::TwoSetStrategy(*dev) : lrge::twoset::TwoSetStrategy(reads);
         lrge::ava::AvaStrategy as = dev ? lrge::ava::AvaStrategy(*dev) : lrge::ava::AvaStrategy(reads);
