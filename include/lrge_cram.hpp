@@ -697,9 +697,68 @@ inline CompressionHeader read_compression_header(const std::string &d) {
 
 using Callback = std::function<void(const std::string &name, const std::string &seq)>;
 
-// every record of the file: callback(read name, bases); a mapped record throws Err(mapped_msg)
-inline void parse(const std::string &file, const Callback &cb, const char *mapped_msg) {
-    Cursor f((const unsigned char *)file.data(), file.size());
+// ---- what the record loop does with a record's bases ----
+// ReadBases: the reader's own -- every base through the BA encoding, whatever that is.
+struct ReadBases {
+    void container(const CompressionHeader &) {}
+    void slice(const std::vector<Block> &) {}
+    void bases(Slice &S, const CompressionHeader &H, int32_t cf, int32_t rl, std::string &seq) {
+        if (!(cf & 0x8)) { const Encoding &ba = H.series("BA"); seq.clear(); seq.reserve((size_t)std::min<int32_t>(rl, 1 << 20)); for (int32_t i = 0; i < rl; ++i) seq.push_back((char)S.read_byte(ba)); }
+    }
+    void slice_end() {}
+};
+// WalkBases: the device ingest's (lrge_amd/csrc/cram_round.h) -- no base is read and the BA block is never
+// decompressed here; a record becomes (slice, offset in that slice's BA block, length) and the walk proves the layout that makes those
+// offsets the record's bases: BA is EXTERNAL, nothing else reads its block, a slice has one such block, and the lengths of a slice's
+// records add up to exactly that block's raw size.  What is not so is an Err that names it.
+struct WalkBases {
+    struct Rec { uint32_t slice; uint64_t off; uint32_t len; };
+    struct BaBlock { const unsigned char *data = nullptr; size_t size = 0; int method = 0; int64_t raw_size = 0; };
+    std::vector<Rec> recs;
+    std::vector<BaBlock> ba;           // one per slice (size 0, raw_size 0: the slice has no BA block)
+    uint64_t containers = 0;
+    int32_t ba_id = -1;
+    uint64_t cur = 0;
+    static void refs(const Encoding &e, std::set<int32_t> &out) {
+        if (e.id == 1 || e.id == 5) out.insert(e.ext_id);
+        if (e.id == 4) { refs(*e.len_enc, out); refs(*e.val_enc, out); }
+    }
+    void container(const CompressionHeader &H) {
+        ++containers;
+        const Encoding &e = H.series("BA");
+        if (e.id != 1) throw Err("CRAM: the BA series is not EXTERNAL (encoding " + std::to_string(e.id) + ")");
+        if (!H.rn_preserved) throw Err("CRAM: read names are not preserved (RN)");
+        ba_id = e.ext_id;
+        std::set<int32_t> other;
+        for (const auto &kv : H.ds) if (kv.first != "BA") refs(kv.second, other);
+        for (const auto &kv : H.tags) refs(kv.second, other);
+        if (other.count(ba_id)) throw Err("CRAM: the BA block (content id " + std::to_string(ba_id) + ") is shared with another series");
+    }
+    void slice(const std::vector<Block> &blocks) {
+        BaBlock b;
+        int seen = 0;
+        for (const Block &k : blocks) if (k.content_type == 4 && k.content_id == ba_id) {
+            if (seen++) throw Err("CRAM: a slice holds two blocks with the BA content id");
+            if (k.raw_size < 0) throw Err("CRAM: a BA block of negative size");
+            b.data = k.data; b.size = k.size; b.method = k.method; b.raw_size = k.raw_size;
+        }
+        ba.push_back(b); cur = 0;
+    }
+    void bases(Slice &, const CompressionHeader &, int32_t cf, int32_t rl, std::string &) {
+        if (ba.size() >> 32) throw Err("CRAM: 2^32 slices or more");
+        if (cf & 0x8) { recs.push_back(Rec{(uint32_t)(ba.size() - 1), cur, 0}); return; }
+        recs.push_back(Rec{(uint32_t)(ba.size() - 1), cur, (uint32_t)rl});
+        cur += (uint64_t)rl;
+    }
+    void slice_end() {
+        if ((int64_t)cur != ba.back().raw_size)
+            throw Err("CRAM: the read lengths of a slice (" + std::to_string(cur) + ") do not add up to its BA block's size (" + std::to_string(ba.back().raw_size) + ")");
+    }
+};
+
+// every record of the file: callback(read name, bases as `pol` leaves them); a mapped record throws Err(mapped_msg)
+template <class Bases> inline void parse_with(const unsigned char *file, size_t file_size, const Callback &cb, const char *mapped_msg, Bases &pol) {
+    Cursor f(file, file_size);
     if (f.left() < 26 || std::memcmp(f.p, "CRAM", 4) != 0) throw Err("not a CRAM file");
     const int major = f.p[4], minor = f.p[5];
     if (major != 3 && major != 2) throw Err("CRAM version " + std::to_string(major) + "." + std::to_string(minor) + " is not supported (2.x / 3.x)");
@@ -722,6 +781,7 @@ inline void parse(const std::string &file, const Callback &cb, const char *mappe
         Block chb = read_block(c, major);
         if (chb.content_type != 1) throw Err("CRAM: a data container must start with its compression header");
         const CompressionHeader H = read_compression_header(chb.get());
+        pol.container(H);
         while (c.left() > 0) {
             Block shb = read_block(c, major);
             if (shb.content_type != 2) throw Err("CRAM: expected a slice header block");
@@ -734,6 +794,7 @@ inline void parse(const std::string &file, const Callback &cb, const char *mappe
             std::vector<Block> blocks((size_t)std::max(0, s_nblocks));
             Slice S; S.lazy = H.lazy;
             for (int32_t i = 0; i < s_nblocks; ++i) blocks[(size_t)i] = read_block(c, major);
+            pol.slice(blocks);
             for (Block &b : blocks) {
                 if (b.content_type == 5) S.core.s = &b.get();
                 else if (b.content_type == 4) S.ext[b.content_id] = &b;
@@ -762,7 +823,7 @@ inline void parse(const std::string &file, const Callback &cb, const char *mappe
                 if (!(bf & 0x4)) throw Err(mapped_msg);                       // io.rs:162-167: mapped records are refused
                 if (rl < 0) throw Err("CRAM: negative read length");
                 seq.clear();
-                if (!(cf & 0x8)) { const Encoding &ba = H.series("BA"); seq.clear(); seq.reserve((size_t)std::min<int32_t>(rl, 1 << 20)); for (int32_t i = 0; i < rl; ++i) seq.push_back((char)S.read_byte(ba)); }
+                pol.bases(S, H, cf, rl, seq);
                 if (cf & 0x1) {       // qualities: skipped -- without touching their block when it is theirs alone (any codec will do then)
                     const Encoding &qs = H.series("QS");
                     if (!(qs.id == 1 && S.lazy.count(qs.ext_id))) for (int32_t i = 0; i < rl; ++i) (void)S.read_byte(qs);
@@ -770,8 +831,14 @@ inline void parse(const std::string &file, const Callback &cb, const char *mappe
                 if (name == "*") name.clear();
                 cb(name, seq);
             }
+            pol.slice_end();
         }
     }
+}
+
+inline void parse(const std::string &file, const Callback &cb, const char *mapped_msg) {
+    ReadBases pol;
+    parse_with((const unsigned char *)file.data(), file.size(), cb, mapped_msg, pol);
 }
 
 }  // namespace cram

@@ -541,7 +541,7 @@ int  lrge_hip_xz_inflate(lrge_hip_ctx *ctx, const void *comp, uint64_t comp_len,
    empty nor starts with '@' has ten tabs and a flag of 1 to 9 digits with bit 2 set); without the flag SAM is unproven.  The records
    equal those of lrge_hip_read_records on the same file, one for one.  LRGE_ERR_UNPROVEN: the device does not prove this input
    and produces no parse error of its own -- anything but FASTA, strict four-line FASTQ or (with its flag) well-formed unaligned
-   BAM (an empty line between records, a truncated record, a missing '+', CRAM, BAM without LRGE_GPU_INGEST_BAM, a BAM
+   BAM (an empty line between records, a truncated record, a missing '+', CRAM without LRGE_GPU_INGEST_CRAM or in a layout that flag does not prove (below), BAM without LRGE_GPU_INGEST_BAM, a BAM
    with a mapped record, a damaged header or record, or bytes behind the last record, SAM without LRGE_GPU_INGEST_SAM, a SAM
    record line with fewer than ten tabs, with a flag that is not plain digits or with a mapped flag), a compressed format without its flag or other than gzip, (with LRGE_GPU_INFLATE_BZIP2) bzip2, (with LRGE_GPU_INFLATE_ZSTD) Zstandard and (with LRGE_GPU_INFLATE_XZ) xz, a damaged gzip file, a bzip2, Zstandard or xz file the device decoder does not accept, text above option INGEST_MAX_BYTES
    (default: half of the free device memory plus the context's idle arena bytes); the caller takes lrge_hip_read_records*, which
@@ -601,6 +601,50 @@ int      lrge_hip_reads_window_stats(const lrge_hip_reads *reads, uint64_t out[4
 int      lrge_hip_seqset_from_reads(lrge_hip_ctx *ctx, const lrge_hip_reads *reads, const uint32_t *idx, uint32_t n,
                                     const uint32_t *name_rank, lrge_hip_seqset **out);
 void     lrge_hip_reads_free(lrge_hip_reads *reads);
+
+/* Read sets built on the device from unaligned CRAM 3.0 / 3.1 (k_rans_decode): | LRGE_GPU_INGEST_CRAM (opt-in:
+   no other flag implies it, and without it every call does what it did) sends input that starts with "CRAM" to a host walk of the
+   containers -- the record loop of lrge_hip_read_records under a policy that reads no base, so identifiers, lengths and flags are
+   the host reader's one for one -- and to a device decode of the BA (bases) block of every slice, straight into the dense base
+   store a windowed FASTA handle has: lrge_hip_reads_count / _table / _timings / lrge_hip_seqset_from_reads /
+   lrge_hip_reads_name_ranks work unchanged, text_bytes is the sum of the BA raw sizes, window_stats()[0] is 0.  Taken on the
+   device: raw BA blocks, rANS 4x8 (orders 0 and 1), rANS Nx16 (orders 0 and 1, 4 or 32 states, shift 1..12, CAT, NOSZ, PACK, RLE,
+   PACK with RLE).  LRGE_ERR_UNPROVEN, with a text that names the reason, and never a parse error of its own: BA not EXTERNAL, its
+   content id read by another series or tag, two BA blocks in a slice, read lengths of a slice that do not add up to the BA block's
+   raw size, RN not preserved, a mapped record (the reference's message), a BA block in gzip, bzip2, lzma, arith, fqzcomp, tok3 or
+   in the STRIPE form of rANS Nx16, a rANS 4x8 table whose frequencies do not sum to 4096 (the host reader tolerates a short one)
+   or that lists a symbol twice, any error the host reader raises during the walk, a block whose status is not OK on the device
+   (compressed data exhausted, a state below the lower bound, a bad end state, an order-1 context without a table, run lengths that
+   do not fit), fewer BA blocks than option CRAM_MIN_BLOCKS (default 32: the measured break-even against lrge_hip_read_records plus an upload, rounded up to a power of two), bases plus
+   one round above INGEST_MAX_BYTES; compressed input is not looked into for a CRAM (it takes the route it took, and CRAM text is
+   unproven there).  LRGE_ERR_TOO_MANY: 2^32 records or more.  Option CRAM_ROUND_BYTES (default 256 MiB): the BA blocks whose
+   compressed bytes fit go up and are decoded by one launch; only the BA byte ranges are uploaded.
+   lrge_hip_reads_cram_stats: the counts of the call; LRGE_ERR_INVALID for a handle that was not opened as CRAM.
+   lrge_hip_rans_decode: n independent streams of comp, stream i = (method 0 raw / 4 rANS 4x8 / 5 rANS Nx16, offset, length, raw
+   size) as a CRAM block body, decoded into out, stream i at the sum of the raw sizes before it (out_cap at least their sum);
+   streams[i].status: 0, one of the block statuses 1..5 (exhausted, state, end, no table, runs), or 16: the stream head was refused
+   on the host (lrge_hip_last_error keeps the first reason); the bytes of such a stream are zero.  LRGE_ERR_INVALID: a stream
+   outside comp, a raw size of 2^31 or more, out_cap too small. */
+typedef struct lrge_hip_cram_stats {
+    uint64_t containers;          /* data containers */
+    uint64_t slices;
+    uint64_t records;
+    uint64_t ba_raw;              /* BA blocks stored raw (copied) */
+    uint64_t ba_rans4x8;
+    uint64_t ba_ransnx16;
+    uint64_t order1_blocks;       /* entropy-coded blocks of order 1 */
+    uint64_t global_table_blocks; /* blocks whose model did not fit LDS: its frequencies were read from global memory */
+    uint64_t comp_bytes;          /* the BA blocks' compressed bytes: all that was uploaded of the file */
+    uint64_t raw_bytes;           /* the bases */
+    uint64_t rounds;              /* launches of k_rans_decode */
+    uint64_t walk_us;             /* microseconds of the host walk */
+    uint64_t decode_us;           /* microseconds of the rounds: upload, launch, status words back */
+} lrge_hip_cram_stats;
+typedef struct lrge_hip_rans_stream { uint64_t offset; uint32_t length, raw_size, method, status; } lrge_hip_rans_stream;
+#define LRGE_GPU_INGEST_CRAM 512
+int      lrge_hip_reads_cram_stats(const lrge_hip_reads *reads, lrge_hip_cram_stats *out);
+int      lrge_hip_rans_decode(lrge_hip_ctx *ctx, const void *comp, uint64_t comp_len, lrge_hip_rans_stream *streams, uint32_t n, void *out,
+                              uint64_t out_cap, lrge_hip_cram_stats *stats);
 
 /* Identifier ranks on the device (k_nl_key, k_nl_heads, k_nl_starts, k_nl_rank between radix_sort_pairs and
    scan_exclusive_u32): the `name_rank` every upload takes, i.e. the stand-in for the reference's name comparisons -- the duplicate

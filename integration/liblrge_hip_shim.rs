@@ -61,12 +61,18 @@ pub const LRGE_PRESET_AVA_PB: c_int = 1; //  Preset::AvaPb  (preset.rs:24)
 pub const LRGE_GPU_INGEST_SAM: c_int = 8; // lrge_hip_reads_open*: unaligned SAM scanned on the device (io.rs:92-96)
 pub const LRGE_GPU_INGEST_WINDOWED_ALN: c_int = 64; // beside LRGE_GPU_INGEST_WINDOWED and the format's flag: unaligned BAM / SAM in windows too (io.rs:154-184)
 pub const LRGE_GPU_INGEST_WINDOWED: c_int = 32; // lrge_hip_reads_open*: FASTA / FASTQ above the text cap in windows, only the bases kept (io.rs:154-184)
+pub const LRGE_GPU_INGEST_CRAM: c_int = 512; // lrge_hip_reads_open*: unaligned CRAM, its base blocks decoded on the device (io.rs:93, 154-184); opt-in
 pub const LRGE_GPU_INFLATE_XZ: c_int = 256; // lrge_hip_reads_open* / lrge_hip_read_records_gpu_ex: xz decompressed on the device (io.rs:36-63)
 pub const LRGE_GPU_INFLATE_ZSTD: c_int = 128; // lrge_hip_reads_open* / lrge_hip_read_records_gpu_ex: Zstandard decompressed on the device (io.rs:36-63)
 pub const LRGE_GPU_INFLATE_BZIP2: c_int = 16; // lrge_hip_reads_open* / lrge_hip_read_records_gpu_ex: bzip2 decompressed on the device (io.rs:36-63)
 
 extern "C" {
     fn lrge_hip_ctx_create(device: c_int, out: *mut *mut lrge_hip_ctx) -> c_int;
+    // the CRAM device ingest (LRGE_GPU_INGEST_CRAM): the counts of an opened handle (13 words, lrge_hip_cram_stats), and the batch decode of
+    // rANS streams (24-byte records: offset u64, length, raw size, method, status u32)
+    fn lrge_hip_reads_cram_stats(reads: *const c_void, out: *mut c_void) -> c_int;
+    fn lrge_hip_rans_decode(ctx: *mut lrge_hip_ctx, comp: *const c_void, comp_len: u64, streams: *mut c_void, n: u32, out: *mut c_void,
+                            out_cap: u64, stats: *mut c_void) -> c_int;
     fn lrge_hip_ctx_destroy(ctx: *mut lrge_hip_ctx);
     fn lrge_hip_last_error(ctx: *const lrge_hip_ctx) -> *const c_char;
     fn lrge_hip_seqset_upload(ctx: *mut lrge_hip_ctx, bases: *const c_char, offsets: *const u64, n: u32,

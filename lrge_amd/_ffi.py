@@ -17,6 +17,7 @@ GPU_INGEST_SAM = 8
 GPU_INFLATE_BZIP2 = 16
 GPU_INFLATE_ZSTD = 128
 GPU_INFLATE_XZ = 256
+GPU_INGEST_CRAM = 512
 GPU_INGEST_WINDOWED = 32
 GPU_INGEST_WINDOWED_ALN = 64
 PRESET_AVA_ONT, PRESET_AVA_PB = 0, 1
@@ -33,6 +34,8 @@ ZSTD_STAT_NAMES = ["frames", "skippable_frames", "blocks", "raw_blocks", "rle_bl
                    "checksum_us"]   # lrge_hip_zstd_stats
 XZ_STAT_NAMES = ["streams", "blocks", "chunks", "raw_chunks", "checks_checked", "rounds", "launches", "bytes_out", "check_us", "decode_us",
                  "walk_us"]   # lrge_hip_xz_stats
+CRAM_STAT_NAMES = ["containers", "slices", "records", "ba_raw", "ba_rans4x8", "ba_ransnx16", "order1_blocks", "global_table_blocks", "comp_bytes", "raw_bytes",
+                   "rounds", "walk_us", "decode_us"]   # lrge_hip_cram_stats
 BAM_STAT_NAMES = ["segments", "empty_segments", "speculative_starts", "rejected_starts", "repair_rounds", "rewalked_segments"]   # lrge_hip_bam_stats
 
 # int (*sink)(void *user, const void *bytes, uint64_t n) of lrge_hip_gzip_inflate, lrge_hip_bzip2_inflate, lrge_hip_zstd_inflate and lrge_hip_xz_inflate
@@ -45,7 +48,7 @@ EXPORTS = [
     "lrge_hip_bgzf_scan", "lrge_hip_bgzf_inflate", "lrge_hip_read_records_gpu",
     "lrge_hip_gzip_inflate", "lrge_hip_read_records_gpu_ex", "lrge_hip_bzip2_inflate", "lrge_hip_zstd_inflate", "lrge_hip_xz_inflate",
     "lrge_hip_reads_open", "lrge_hip_reads_open_mem", "lrge_hip_reads_count", "lrge_hip_reads_name_bytes", "lrge_hip_reads_text_bytes",
-    "lrge_hip_reads_table", "lrge_hip_reads_timings", "lrge_hip_reads_bam_stats", "lrge_hip_reads_window_stats", "lrge_hip_seqset_from_reads", "lrge_hip_reads_free",
+    "lrge_hip_reads_table", "lrge_hip_reads_timings", "lrge_hip_reads_bam_stats", "lrge_hip_reads_window_stats", "lrge_hip_reads_cram_stats", "lrge_hip_rans_decode", "lrge_hip_seqset_from_reads", "lrge_hip_reads_free",
     "lrge_hip_name_ranks", "lrge_hip_reads_name_ranks",
     "lrge_hip_index_build", "lrge_hip_index_build_for", "lrge_hip_index_build_sharded", "lrge_hip_index_build_tsharded", "lrge_hip_last_shard_stats", "lrge_hip_index_free",
     "lrge_hip_comm_alltoallv", "lrge_hip_comm_rccl_ranks", "lrge_hip_comm_rccl_ops", "lrge_hip_comm_local_group_serialize", "lrge_hip_comm_local_turn",
@@ -59,6 +62,11 @@ EXPORTS = [
     "lrge_hip_sketch_dump", "lrge_hip_index_dump", "lrge_hip_anchors_dump",
     "lrge_hip_set_timer_level", "lrge_hip_last_timings", "lrge_hip_last_counters", "lrge_hip_version",
 ]
+
+
+class RansStream(C.Structure):
+    """lrge_hip_rans_stream"""
+    _fields_ = [("offset", C.c_uint64), ("length", C.c_uint32), ("raw_size", C.c_uint32), ("method", C.c_uint32), ("status", C.c_uint32)]
 
 
 class Params(C.Structure):
@@ -126,6 +134,8 @@ def lib():
     L.lrge_hip_reads_timings.argtypes = [vp, C.POINTER(C.c_float * 4)]
     L.lrge_hip_reads_bam_stats.argtypes = [vp, C.POINTER(C.c_uint64 * len(BAM_STAT_NAMES))]
     L.lrge_hip_reads_window_stats.argtypes = [vp, C.POINTER(C.c_uint64 * 4)]
+    L.lrge_hip_reads_cram_stats.argtypes = [vp, C.POINTER(C.c_uint64 * len(CRAM_STAT_NAMES))]
+    L.lrge_hip_rans_decode.argtypes = [vp, vp, C.c_uint64, C.POINTER(RansStream), C.c_uint32, vp, C.c_uint64, vp]
     L.lrge_hip_seqset_from_reads.argtypes = [vp, vp, vp, C.c_uint32, vp, C.POINTER(vp)]
     L.lrge_hip_name_ranks.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp]
     L.lrge_hip_reads_name_ranks.argtypes = [vp, vp, C.c_uint64, vp, vp]

@@ -49,23 +49,25 @@ BZIP2_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_bzip2_twin.so")
 NAMES_LSD_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_names_lsd_twin.so")
 ZSTD_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_zstd_twin.so")
 XZ_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_xz_twin.so")
+CRAM_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_cram_twin.so")
 
 
-def _build_twin(out, main, force):
+def _build_twin(out, main, force, libs=()):
     """One host twin (g++) of csrc/<main>, for the CPU suite.  It is stale when any source of the main library is newer,
     whichever headers it includes today: a rebuild takes seconds, a stale twin gives a wrong test result."""
     os.makedirs(LIB_DIR, exist_ok=True)
     if not force and os.path.exists(out) and os.path.getmtime(out) >= _newest(_sources()):
         return out
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-fPIC", "-shared", "-o", out, os.path.join(CSRC, main)])
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-fPIC", "-shared", "-o", out, os.path.join(CSRC, main)] + list(libs))
     return out
 
 
 def build_twin(force=False):
-    """The host twins, all ten: of k_inflate (csrc/inflate_twin.cpp, the same bit-level core), and of the speculative gzip
+    """The host twins, all eleven: of k_inflate (csrc/inflate_twin.cpp, the same bit-level core), and of the speculative gzip
     decode (build_gzip_twin), of the FASTA / FASTQ record scan (build_fastx_twin), of the BAM record scan (build_bam_twin), of
     the SAM record scan (build_sam_twin), of the identifier ranking by refinement (build_names_twin) and by fixed LSD passes (build_names_lsd_twin)
-    and of the bzip2 decode (build_bzip2_twin), the Zstandard decode (build_zstd_twin) and the xz decode (build_xz_twin)."""
+    and of the bzip2 decode (build_bzip2_twin), the Zstandard decode (build_zstd_twin) and the xz decode (build_xz_twin), and of the CRAM base-block ingest (build_cram_twin)."""
+    build_cram_twin(force)
     build_gzip_twin(force)
     build_fastx_twin(force)
     build_bam_twin(force)
@@ -122,6 +124,12 @@ def build_zstd_twin(force=False):
 def build_xz_twin(force=False):
     """The host twin of the block-parallel xz decode (csrc/xz_twin.cpp): the same core and the same driver of the rounds."""
     return _build_twin(XZ_TWIN_PATH, "xz_twin.cpp", force)
+
+
+def build_cram_twin(force=False):
+    """The host twin of the CRAM device ingest (csrc/cram_twin.cpp): the same walk, stream heads, rounds and block decode.  It
+    includes the host readers (include/lrge_io.hpp), hence zlib and libdl."""
+    return _build_twin(CRAM_TWIN_PATH, "cram_twin.cpp", force, libs=("-lz", "-ldl"))
 
 
 CLI_PATH = os.path.join(LIB_DIR, "lrge-hip")

@@ -1,5 +1,6 @@
 // host_fastx.inl -- read sets built on the device from FASTA / FASTQ text (k_fastx.h), from unaligned BAM
-// (k_bam.h, host_bam.inl) and from unaligned SAM (k_sam.h, host_sam.inl): the text reaches HBM
+// (k_bam.h, host_bam.inl), from unaligned SAM (k_sam.h, host_sam.inl) and, without any text, from
+// unaligned CRAM (k_cram.h, host_cram.inl): the text reaches HBM
 // decompressed (BGZF chunks decoded into one block by the pipeline of host_inflate.inl, the gzip, bzip2 and Zstandard rounds appended device-to-device, plain input copied once), the
 // record scan runs there, only identifiers and lengths come back, and lrge_hip_seqset_from_reads gathers the selected reads
 // into dense ASCII for the device-source pack of host_seqset.inl.  Whatever the scan cannot prove is LRGE_ERR_UNPROVEN: the
@@ -12,6 +13,7 @@
 
 #include "dev_keep.h"
 #include "fx_window.h"
+#include "cram_round.h"
 
 struct lrge_hip_reads {
     lrge_hip_ctx *ctx = nullptr;
@@ -25,6 +27,8 @@ struct lrge_hip_reads {
     BamStats bam = {0, 0, 0, 0, 0, 0};          // fmt == FX_FMT_BAM: the counts of the record scan, summed over the windows (lrge_hip_reads_bam_stats)
     u64 text_bytes = 0;                         // the decompressed text that was scanned (windowed: d_text holds its bases only, BAM's packed)
     FxWinStats win = {0, 0, 0, 0};              // lrge_hip_reads_window_stats
+    bool is_cram = false;                       // opened from unaligned CRAM (host_cram.inl): d_text is a base store, as a windowed FASTA handle's
+    CramStats cram;                             // lrge_hip_reads_cram_stats
 };
 
 static double fx_now_ms() { return DevPool::now_ms(); }
@@ -577,6 +581,8 @@ static int fx_src_xz(FxSink &s, const u8 *d, u64 len) {
     return rc;
 }
 
+#include "host_cram.inl"     // fx_open_cram: unaligned CRAM under LRGE_GPU_INGEST_CRAM (needs the struct, ingest_cap and fx_alloc_recs above)
+
 // ---- the two ends of a call ----  windows were flushed: the rest of the block is the last, the store the handle's text
 static int fx_finish_windowed(FxSink &s, double t0) {
     lrge_hip_reads *R = s.R;
@@ -620,9 +626,16 @@ extern "C" int lrge_hip_reads_open_mem(lrge_hip_ctx *ctx, const void *file_bytes
     const u8 *d = (const u8 *)file_bytes;
     std::unique_ptr<lrge_hip_reads, void (*)(lrge_hip_reads *)> guard(new lrge_hip_reads(), lrge_hip_reads_free);
     guard->ctx = ctx;
+    const auto b = [&](u64 i) -> u32 { return i < len ? d[i] : 0x100u; };
+    // unaligned CRAM, for the caller who asked for it: a host walk and a device decode of the base blocks, no text and no record scan
+    if ((flags & LRGE_GPU_INGEST_CRAM) && b(0) == 'C' && b(1) == 'R' && b(2) == 'A' && b(3) == 'M') {
+        const int crc = fx_open_cram(ctx, guard.get(), d, len, t0);
+        if (crc) return crc;
+        *out = guard.release();
+        return LRGE_OK;
+    }
     FxSink s(ctx, guard.get(), flags);
     // the source, by the file's magic
-    const auto b = [&](u64 i) -> u32 { return i < len ? d[i] : 0x100u; };
     std::vector<BgzfBlock> t;
     uint64_t total = 0;
     int rc;

@@ -31,6 +31,7 @@
 #include "k_bzip2.h"
 #include "k_zstd.h"
 #include "k_xz.h"
+#include "k_cram.h"
 #include "k_fastx.h"
 #include "k_bam.h"
 #include "k_sam.h"

@@ -140,9 +140,30 @@ class Context:
         self._check(self._lib.lrge_hip_xz_inflate(self.h, data, len(data), cb, None, C.cast(st, C.c_void_p)))
         return b"".join(parts), dict(zip(_ffi.XZ_STAT_NAMES, list(st)))
 
+    def rans_decode(self, streams, comp=None):
+        """A batch of independent rANS streams decoded on the device (lrge_hip_rans_decode, the unit of the CRAM ingest).  streams:
+        [(method, bytes, raw size)] (method 0: stored, 4: rANS 4x8, 5: rANS Nx16; the bytes are a CRAM block's body).  Returns
+        ([output bytes per stream], [status per stream], dict of lrge_hip_cram_stats); status 16: the stream head was refused on
+        the host, `rans_why` holds the first such reason."""
+        body = bytearray()
+        arr = (_ffi.RansStream * max(1, len(streams)))()
+        for i, (method, data, raw) in enumerate(streams):
+            arr[i] = _ffi.RansStream(len(body), len(data), int(raw), int(method), 0)
+            body += data
+        total = sum(int(r) for _, _, r in streams)
+        out = C.create_string_buffer(max(1, total))
+        st = (C.c_uint64 * len(_ffi.CRAM_STAT_NAMES))()
+        self._check(self._lib.lrge_hip_rans_decode(self.h, bytes(body), len(body), arr, len(streams), out, total, C.cast(st, C.c_void_p)))
+        self.rans_why = self._lib.lrge_hip_last_error(self.h).decode()
+        raw, outs, o = out.raw, [], 0
+        for _, _, r in streams:
+            outs.append(raw[o:o + int(r)])
+            o += int(r)
+        return outs, [int(arr[i].status) for i in range(len(streams))], dict(zip(_ffi.CRAM_STAT_NAMES, [int(x) for x in st]))
+
     def open_reads(self, path_or_bytes, flags=_ffi.GPU_INFLATE_BGZF | _ffi.GPU_INFLATE_GZIP):
         """A FASTA / FASTQ file (a path, or the bytes of the whole file) parsed on the device: plain, BGZF or any other gzip
-        (| _ffi.GPU_INFLATE_BZIP2: bzip2 as well; | _ffi.GPU_INFLATE_ZSTD: Zstandard as well, always resident; | _ffi.GPU_INFLATE_XZ: xz as well), by `flags` (lrge_hip_reads_open*); | _ffi.GPU_INGEST_BAM takes unaligned BAM as well, | _ffi.GPU_INGEST_SAM unaligned SAM; | _ffi.GPU_INGEST_WINDOWED lets FASTA / FASTQ text above option INGEST_WINDOW_BYTES pass through in windows with only the bases kept (DeviceReads.window_stats), and | _ffi.GPU_INGEST_WINDOWED_ALN beside it and the format's own flag does the same for unaligned BAM (its bases kept packed, 4 bits each) and SAM.  Returns a DeviceReads with names, lens and seqset().  Input the device does not
+        (| _ffi.GPU_INFLATE_BZIP2: bzip2 as well; | _ffi.GPU_INFLATE_ZSTD: Zstandard as well, always resident; | _ffi.GPU_INFLATE_XZ: xz as well), by `flags` (lrge_hip_reads_open*); | _ffi.GPU_INGEST_BAM takes unaligned BAM as well, | _ffi.GPU_INGEST_SAM unaligned SAM, | _ffi.GPU_INGEST_CRAM (opt-in, implied by nothing) unaligned CRAM with its base blocks decoded on the device (DeviceReads.cram_stats); | _ffi.GPU_INGEST_WINDOWED lets FASTA / FASTQ text above option INGEST_WINDOW_BYTES pass through in windows with only the bases kept (DeviceReads.window_stats), and | _ffi.GPU_INGEST_WINDOWED_ALN beside it and the format's own flag does the same for unaligned BAM (its bases kept packed, 4 bits each) and SAM.  Returns a DeviceReads with names, lens and seqset().  Input the device does not
         prove raises UnprovenInput: read the file with the host readers (readio.load) instead."""
         return DeviceReads(self, path_or_bytes, flags)
 
@@ -366,6 +387,12 @@ class DeviceReads:
         a = (C.c_uint64 * len(_ffi.BAM_STAT_NAMES))()
         self.ctx._check(self.ctx._lib.lrge_hip_reads_bam_stats(self.h, C.byref(a)))
         return dict(zip(_ffi.BAM_STAT_NAMES, [int(x) for x in a]))
+
+    def cram_stats(self):
+        """the counts of a handle opened from unaligned CRAM (lrge_hip_cram_stats) as a dict; raises when the input was not CRAM"""
+        a = (C.c_uint64 * len(_ffi.CRAM_STAT_NAMES))()
+        self.ctx._check(self.ctx._lib.lrge_hip_reads_cram_stats(self.h, C.byref(a)))
+        return dict(zip(_ffi.CRAM_STAT_NAMES, [int(x) for x in a]))
 
     def window_stats(self):
         """(windows flushed -- 0: the text stayed resident --, bytes in the store: the bases, for BAM their packed bytes --, largest window

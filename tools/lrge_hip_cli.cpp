@@ -63,7 +63,7 @@ int main(int argc, char **argv) {
     bool T_set = false, Q_set = false, filter = false, with_inf = false, precise = false, use_min_ref = false, honour_platform = false;
     float q1 = lrge::LOWER_QUANTILE, q3 = lrge::UPPER_QUANTILE, ratio = 0.2f;
     size_t threads = 1; std::optional<uint64_t> seed; int quiet = 0, verbose = 0, device = 0;
-    bool keep_temp = false, dump_records = false, gpu_inflate = false, gpu_gzip = false, gpu_bzip2 = false, gpu_zstd = false, gpu_xz = false, gpu_ingest = false, gpu_names = false; std::string temp_dir;
+    bool keep_temp = false, dump_records = false, gpu_inflate = false, gpu_gzip = false, gpu_bzip2 = false, gpu_zstd = false, gpu_xz = false, gpu_cram = false, gpu_ingest = false, gpu_names = false; std::string temp_dir;
     auto need = [&](int &i) -> const char * { if (i + 1 >= argc) { fprintf(stderr, "error: missing value for %s\n", argv[i]); exit(2); } return argv[++i]; };
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -88,6 +88,7 @@ int main(int argc, char **argv) {
         else if (a == "--gpu-inflate") gpu_inflate = true;       // BGZF input (BAM, bgzip FASTQ) decompressed on --device
         else if (a == "--gpu-gzip") gpu_gzip = true;             // every gzip input (plain, multi-member, BGZF) decompressed on --device
         else if (a == "--gpu-xz") gpu_xz = true;                 // xz input decompressed on --device (with --gpu-ingest: kept in HBM); not implied by --gpu-ingest
+        else if (a == "--gpu-cram") gpu_cram = true;             // beside --gpu-ingest: unaligned CRAM walked on the host, its base blocks decoded on --device; not implied by --gpu-ingest
         else if (a == "--gpu-zstd") gpu_zstd = true;             // Zstandard input decompressed on --device (with --gpu-ingest: kept in HBM); not implied by --gpu-ingest
         else if (a == "--gpu-bzip2") gpu_bzip2 = true;           // bzip2 input decompressed on --device (with --gpu-ingest: kept in HBM)
         else if (a == "--gpu-ingest") { gpu_ingest = true; gpu_gzip = true; }   // FASTA / FASTQ / unaligned BAM / unaligned SAM parsed on --device too: the bases never reach host memory (implies --gpu-gzip)
@@ -113,7 +114,7 @@ int main(int argc, char **argv) {
         // --gpu-ingest: input the device does not prove takes the usual route below, which parses it or reports it
         std::unique_ptr<lrge::DeviceReads> dev;
         if (gpu_ingest) {
-            dev = lrge::DeviceReads::open(input, LRGE_GPU_INFLATE_BGZF | LRGE_GPU_INFLATE_GZIP | LRGE_GPU_INGEST_BAM | LRGE_GPU_INGEST_SAM | LRGE_GPU_INGEST_WINDOWED | LRGE_GPU_INGEST_WINDOWED_ALN | (gpu_bzip2 ? LRGE_GPU_INFLATE_BZIP2 : 0) | (gpu_zstd ? LRGE_GPU_INFLATE_ZSTD : 0) | (gpu_xz ? LRGE_GPU_INFLATE_XZ : 0), device);
+            dev = lrge::DeviceReads::open(input, LRGE_GPU_INFLATE_BGZF | LRGE_GPU_INFLATE_GZIP | LRGE_GPU_INGEST_BAM | LRGE_GPU_INGEST_SAM | LRGE_GPU_INGEST_WINDOWED | LRGE_GPU_INGEST_WINDOWED_ALN | (gpu_bzip2 ? LRGE_GPU_INFLATE_BZIP2 : 0) | (gpu_zstd ? LRGE_GPU_INFLATE_ZSTD : 0) | (gpu_xz ? LRGE_GPU_INFLATE_XZ : 0) | (gpu_cram ? LRGE_GPU_INGEST_CRAM : 0), device);
             if (info) fprintf(stderr, "[INFO] gpu-ingest: %s\n", dev ? "device" : "host");
             if (dev && dev->names.empty()) throw lrge::LrgeError(LRGE_ERR_IO, "IO error: Is the file empty?");
         }
