@@ -602,6 +602,35 @@ int      lrge_hip_seqset_from_reads(lrge_hip_ctx *ctx, const lrge_hip_reads *rea
                                     const uint32_t *name_rank, lrge_hip_seqset **out);
 void     lrge_hip_reads_free(lrge_hip_reads *reads);
 
+/* The device ingest of a sample (k_fx_bases, k_fx_pick, k_fx_keep): the tool never uses more than a sample of
+   its input, so the reference reads the file twice -- count_records (io.rs:140-145) gives n, unique_random_set (lib.rs:189-204)
+   draws the indices, and a second pass writes only the drawn reads (twoset.rs:122-201).  These entries are the two passes on the
+   device, for FASTA / FASTQ text from every source whose text passes through windows (plain, BGZF, gzip, bzip2, xz).  In both the
+   whole text goes through the windows of INGEST_WINDOW_BYTES with the cuts of lrge_hip_reads_open* | LRGE_GPU_INGEST_WINDOWED,
+   with or without that flag, and every window is proven by the record scan; a text within one window is the last window.
+   lrge_hip_reads_census* (replaces io.rs:140-145): nothing is stored and no identifier leaves the device.  out[0] records, out[1]
+   the sum of their sequence lengths, out[2] text bytes, out[3] windows flushed.  The count is that of lrge_hip_read_records on
+   the same bytes, or the call is LRGE_ERR_UNPROVEN.
+   lrge_hip_reads_open_selected* (replaces twoset.rs:122-201 behind lib.rs:189-204): sel[0, k) are strictly ascending record
+   ordinals (file order, 0-based).  Only their identifiers come to the host and only their bases go to the store: the handle is
+   an ordinary windowed-store handle of k reads in file order, read j being record sel[j] of lrge_hip_read_records, and
+   lrge_hip_reads_count (k) / _table / _timings / _window_stats / _name_ranks / lrge_hip_seqset_from_reads (indices 0..k-1) /
+   lrge_hip_reads_free work unchanged.  INGEST_MAX_BYTES bounds the chosen bases plus the block; 2^32 records and a window of 2^32
+   bytes are LRGE_ERR_UNPROVEN as for the windowed open, 4 GiB of identifiers counts the chosen ones only.  k = 0 is legal: an
+   empty handle, and the pass still proves the file.  LRGE_ERR_INVALID, before any handle is handed out: ordinals that are not
+   strictly ascending; an ordinal at or above the number of records the pass saw (the message names the ordinal and the count).
+   LRGE_ERR_UNPROVEN for both, whatever the flags: text whose first bytes say BAM, SAM or CRAM ("selected ingest takes FASTA /
+   FASTQ only"), Zstandard input (its text is never windowed); everything else as lrge_hip_reads_open*.
+   lrge_hip_reads_select_stats: out[0] records seen, out[1] records kept, out[2] sequence bases seen, out[3] bases kept by the
+   pass that made the handle; zeros for a handle of lrge_hip_reads_open*. */
+int      lrge_hip_reads_census(lrge_hip_ctx *ctx, const char *path, int flags, uint64_t out[4]);
+int      lrge_hip_reads_census_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, int flags, uint64_t out[4]);
+int      lrge_hip_reads_open_selected(lrge_hip_ctx *ctx, const char *path, int flags, const uint32_t *sel, uint32_t k,
+                                      lrge_hip_reads **out);
+int      lrge_hip_reads_open_selected_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, int flags, const uint32_t *sel,
+                                          uint32_t k, lrge_hip_reads **out);
+int      lrge_hip_reads_select_stats(const lrge_hip_reads *reads, uint64_t out[4]);
+
 /* Read sets built on the device from unaligned CRAM 3.0 / 3.1 (k_rans_decode): | LRGE_GPU_INGEST_CRAM (opt-in:
    no other flag implies it, and without it every call does what it did) sends input that starts with "CRAM" to a host walk of the
    containers -- the record loop of lrge_hip_read_records under a policy that reads no base, so identifiers, lengths and flags are

@@ -100,14 +100,69 @@ struct DeviceReads {
         const int rc = lrge_hip_reads_open(r->ctx->h, path.c_str(), flags, &r->h);
         if (rc == LRGE_ERR_UNPROVEN || rc == LRGE_ERR_IO) return nullptr;
         r->ctx->check(rc);
-        r->ctx->check(lrge_hip_reads_window_stats(r->h, r->window_stats));
-        const uint64_t n = lrge_hip_reads_count(r->h);
+        r->tables();
+        return r;
+    }
+    // The device ingest of a sample.  census: the count pass (lrge_hip_reads_census, io.rs:140-145) -- out =
+    // {records, sequence bases, text bytes, windows}; false for input the device does not prove or cannot read, as open()'s
+    // nullptr.  `ctx`: a context to run in (none: one is made on `device`)
+    static bool census(const std::string &path, int flags, int device, uint64_t out[4], std::shared_ptr<detail::Ctx> ctx = nullptr) {
+        if (!ctx) ctx = std::make_shared<detail::Ctx>(device);
+        const int rc = lrge_hip_reads_census(ctx->h, path.c_str(), flags, out);
+        if (rc == LRGE_ERR_UNPROVEN || rc == LRGE_ERR_IO) return false;
+        ctx->check(rc);
+        return true;
+    }
+    // open_selected: the pass that keeps records sel (strictly ascending ordinals; lrge_hip_reads_open_selected, twoset.rs:122-201):
+    // a DeviceReads of sel.size() reads in file order, select_stats filled; nullptr as open()
+    static std::unique_ptr<DeviceReads> open_selected(const std::string &path, int flags, const std::vector<uint32_t> &sel, int device = 0,
+                                                      std::shared_ptr<detail::Ctx> ctx = nullptr) {
+        auto r = std::make_unique<DeviceReads>();
+        r->ctx = ctx ? ctx : std::make_shared<detail::Ctx>(device);
+        const int rc = lrge_hip_reads_open_selected(r->ctx->h, path.c_str(), flags, sel.data(), (uint32_t)sel.size(), &r->h);
+        if (rc == LRGE_ERR_UNPROVEN || rc == LRGE_ERR_IO) return nullptr;
+        r->ctx->check(rc);
+        r->ctx->check(lrge_hip_reads_select_stats(r->h, r->select_stats));
+        r->tables();
+        return r;
+    }
+    uint64_t select_stats[4] = {0, 0, 0, 0};   // lrge_hip_reads_select_stats: records seen, kept, sequence bases seen, kept (open_selected)
+private:
+    void tables() {
+        ctx->check(lrge_hip_reads_window_stats(h, window_stats));
+        const uint64_t n = lrge_hip_reads_count(h);
         std::vector<uint64_t> off(n + 1);
-        std::string blob(lrge_hip_reads_name_bytes(r->h), '\0');
-        r->lens.resize(n);
-        r->ctx->check(lrge_hip_reads_table(r->h, r->lens.data(), off.data(), blob.empty() ? nullptr : &blob[0]));
-        r->names.reserve(n);
-        for (uint64_t i = 0; i < n; ++i) r->names.emplace_back(blob, off[i], off[i + 1] - off[i]);
+        std::string blob(lrge_hip_reads_name_bytes(h), '\0');
+        lens.resize(n);
+        ctx->check(lrge_hip_reads_table(h, lens.data(), off.data(), blob.empty() ? nullptr : &blob[0]));
+        names.reserve(n);
+        for (uint64_t i = 0; i < n; ++i) names.emplace_back(blob, off[i], off[i + 1] - off[i]);
+    }
+};
+
+// The input of a strategy that takes only its sample through the device: the census gives n, the strategy
+// applies the reference's checks to it and draws its indices exactly as on a DeviceReads, and only the drawn reads are opened
+// (DeviceReads::open_selected).  The estimate is bit for bit that of the same run through DeviceReads::open.
+struct SampledSource {
+    std::string path;
+    int flags = LRGE_GPU_INFLATE_BGZF | LRGE_GPU_INFLATE_GZIP, device = 0;
+    std::shared_ptr<detail::Ctx> ctx;           // made by census(); the strategy runs in it
+    uint64_t counts[4] = {0, 0, 0, 0};          // the census: records, sequence bases, text bytes, windows
+    bool counted = false;
+    // the count pass, once; false: the device does not prove this input -- take DeviceReads::open, then the host readers
+    bool census() {
+        if (counted) return true;
+        if (!ctx) ctx = std::make_shared<detail::Ctx>(device);
+        return counted = DeviceReads::census(path, flags, device, counts, ctx);
+    }
+    // the drawn ordinals (any order) opened in file order; the pass must see the census's records
+    std::shared_ptr<DeviceReads> open(const std::vector<uint32_t> &idx, std::vector<uint32_t> *ascending) {
+        *ascending = idx;
+        std::sort(ascending->begin(), ascending->end());
+        std::shared_ptr<DeviceReads> r = DeviceReads::open_selected(path, flags, *ascending, device, ctx);
+        if (!r) throw LrgeError(LRGE_ERR_UNPROVEN, std::string("sampled ingest: ") + lrge_hip_last_error(ctx->h));
+        if (r->select_stats[0] != counts[0])
+            throw LrgeError(LRGE_ERR_IO, "IO error: the input changed between the count and the selection (" + std::to_string(counts[0]) + " records, then " + std::to_string(r->select_stats[0]) + ")");
         return r;
     }
 };
@@ -311,12 +366,16 @@ public:
 
     explicit TwoSetStrategy(const Reads &r) : input(&r) {}
     explicit TwoSetStrategy(const DeviceReads &r) : dev_input(&r) {}
+    SampledSource *sampled = nullptr;         // set instead of either: split_fastq counts, draws and opens only the drawn reads, which become dev_input
+    std::shared_ptr<DeviceReads> sampled_reads;
+    explicit TwoSetStrategy(SampledSource &s) : sampled(&s) {}
     const std::vector<std::string> &names_in() const { return dev_input ? dev_input->names : input->names; }
     size_t len_in(size_t i) const { return dev_input ? dev_input->lens[i] : input->seqs[i].size(); }
 
     // twoset.rs:122-201
     std::tuple<std::vector<size_t>, std::vector<size_t>, float> split_fastq() {
-        const size_t n = names_in().size();
+        if (sampled && !sampled->census()) throw LrgeError(LRGE_ERR_UNPROVEN, std::string("sampled ingest: ") + lrge_hip_last_error(sampled->ctx->h));
+        const size_t n = sampled ? (size_t)sampled->counts[0] : names_in().size();
         if (n > 0xFFFFFFFFull) throw LrgeError(LRGE_ERR_TOO_MANY, "Number of reads in input file exceeds maximum allowed value");
         size_t n_req = target_num_reads + query_num_reads;
         if (n <= query_num_reads)
@@ -334,6 +393,15 @@ public:
         std::unordered_set<uint32_t> tset(idx.end() - (std::ptrdiff_t)target_num_reads, idx.end()),
             qset(idx.begin(), idx.end() - (std::ptrdiff_t)target_num_reads);
         std::vector<size_t> t, q;
+        if (sampled) {                     // only the drawn reads are opened: read j of the handle is record asc[j], and the lists are renumbered into 0..k-1
+            std::vector<uint32_t> asc;
+            sampled_reads = sampled->open(idx, &asc);
+            dev_input = sampled_reads.get();
+            for (size_t j = 0; j < asc.size(); ++j) {   // file order, like iter_records
+                if (tset.count(asc[j])) { t.push_back(j); target_num_bases += len_in(j); }
+                else { q.push_back(j); query_num_bases += len_in(j); }
+            }
+        } else
         for (size_t i = 0; i < n; ++i) {   // file order, like iter_records
             if (tset.count((uint32_t)i)) { t.push_back(i); target_num_bases += len_in(i); }
             else if (qset.count((uint32_t)i)) { q.push_back(i); query_num_bases += len_in(i); }
@@ -396,6 +464,7 @@ public:
     Builder &device(int d) { device_ = d; return *this; }
     TwoSetStrategy build(const Reads &input) const { return configure(TwoSetStrategy(input)); }
     TwoSetStrategy build(const DeviceReads &input) const { return configure(TwoSetStrategy(input)); }
+    TwoSetStrategy build(SampledSource &input) const { return configure(TwoSetStrategy(input)); }
     TwoSetStrategy configure(TwoSetStrategy s) const {
         s.target_num_reads = t_; s.query_num_reads = q_; s.remove_internal = remove_internal_; s.max_overhang_ratio = ratio_;
         s.use_min_ref = use_min_ref_; s.threads = threads_; s.seed = seed_; s.platform = platform_; s.device = device_;
@@ -428,11 +497,14 @@ public:
 
     explicit AvaStrategy(const Reads &r) : input(&r) {}
     explicit AvaStrategy(const DeviceReads &r) : dev_input(&r) {}
+    SampledSource *sampled = nullptr;         // as TwoSetStrategy::sampled
+    std::shared_ptr<DeviceReads> sampled_reads;
+    explicit AvaStrategy(SampledSource &s) : sampled(&s) {}
 
     std::pair<std::vector<float>, uint32_t> generate_estimates() override {
         // ava.rs:108-161
-        const std::vector<std::string> &names = dev_input ? dev_input->names : input->names;
-        const size_t n = names.size();
+        if (sampled && !sampled->census()) throw LrgeError(LRGE_ERR_UNPROVEN, std::string("sampled ingest: ") + lrge_hip_last_error(sampled->ctx->h));
+        const size_t n = sampled ? (size_t)sampled->counts[0] : (dev_input ? dev_input->names : input->names).size();
         if (n > 0xFFFFFFFFull) throw LrgeError(LRGE_ERR_TOO_MANY, "Number of reads in input file exceeds maximum allowed value");
         if (n < num_reads) {
             warnings.push_back("Number of reads in input file (" + std::to_string(n) + ") is less than the number requested (" +
@@ -443,6 +515,14 @@ public:
         std::unordered_set<uint32_t> keep(idx.begin(), idx.end());
         std::vector<const std::string *> rn, rs;
         std::vector<size_t> ri;
+        if (sampled) {                     // only the drawn reads are opened, in file order: all of the handle's reads are the sample
+            std::vector<uint32_t> asc;
+            sampled_reads = sampled->open(idx, &asc);
+            dev_input = sampled_reads.get();
+            for (size_t j = 0; j < asc.size(); ++j) { rn.push_back(&dev_input->names[j]); ri.push_back(j); num_bases += dev_input->lens[j]; }
+        }
+        const std::vector<std::string> &names = sampled ? dev_input->names : dev_input ? dev_input->names : input->names;
+        if (!sampled)
         for (size_t i = 0; i < n; ++i) if (keep.count((uint32_t)i)) {
             rn.push_back(&names[i]); ri.push_back(i);
             if (input) rs.push_back(&input->seqs[i]);
@@ -488,6 +568,7 @@ public:
     Builder &device(int d) { device_ = d; return *this; }
     AvaStrategy build(const Reads &input) const { return configure(AvaStrategy(input)); }
     AvaStrategy build(const DeviceReads &input) const { return configure(AvaStrategy(input)); }
+    AvaStrategy build(SampledSource &input) const { return configure(AvaStrategy(input)); }
     AvaStrategy configure(AvaStrategy s) const {
         s.num_reads = n_; s.remove_internal = remove_internal_; s.max_overhang_ratio = ratio_; s.threads = threads_;
         s.seed = seed_; s.platform = platform_; s.device = device_;

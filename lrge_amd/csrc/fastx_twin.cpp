@@ -198,6 +198,34 @@ int fastx_twin_windowed(const uint8_t *t, uint64_t n, uint64_t tile, uint64_t wi
     return win_twin_run(sc, t, n, window, piece, true, gw);
 }
 
+// The same text in the two passes of the selected ingest.  fastx_twin_census keeps nothing: out = {records,
+// sequence bases, text bytes, windows flushed}.  fastx_twin_selected keeps records sel[0, k) (strictly ascending ordinals): the
+// accessors below read its result as they read fastx_twin_windowed's, fastx_twin_select_stats what the run saw and kept.
+// 0, FX_UNPROVEN, FX_TOO_MANY, or WIN_TWIN_INVALID for a selection that is not ascending or reaches past the records
+int fastx_twin_census(const uint8_t *t, uint64_t n, uint64_t tile, uint64_t window, uint64_t piece, uint64_t out[4]) {
+    gw = WinTwinOut();
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (tile < 16 || tile % 16 || !piece) return -1;
+    Scan sc = {tile};
+    const int rc = win_twin_run(sc, t, n, window, piece, true, gw, FX_KEEP_NONE);
+    if (!rc) { out[0] = gw.sel.seen; out[1] = gw.sel.bases_seen; out[2] = n; out[3] = gw.st.windows; }
+    return rc;
+}
+
+int fastx_twin_selected(const uint8_t *t, uint64_t n, uint64_t tile, uint64_t window, uint64_t piece, const uint32_t *sel, uint64_t k) {
+    gw = WinTwinOut();
+    if (tile < 16 || tile % 16 || !piece) return -1;
+    Scan sc = {tile};
+    return win_twin_run(sc, t, n, window, piece, true, gw, FX_KEEP_SEL, sel, k);
+}
+
+void fastx_twin_select_stats(uint64_t out[4]) { gw.select_stats(out); }
+// the dense store of the kept bases, bytes [0, fastx_twin_windowed_stats()[1])
+uint64_t fastx_twin_windowed_store(uint8_t *out, uint64_t bytes) { return gw.store_to(out, bytes < gw.store.size() ? bytes : gw.store.size()); }
+
+// the records of every window of the last run, in order (at most `cap` are written); returns how many windows took records or a cut
+uint64_t fastx_twin_windowed_cuts(uint64_t *out, uint64_t cap) { return gw.cuts(out, cap); }
+
 uint64_t fastx_twin_windowed_count(void) { return gw.recs.size(); }
 int fastx_twin_windowed_format(void) { return gw.fmt; }
 void fastx_twin_windowed_table(FxRec *out) { gw.table(out); }

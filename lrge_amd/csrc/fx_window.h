@@ -37,6 +37,32 @@ static inline uint64_t fx_win_fastq_groups(uint64_t n_lf, uint64_t l0, uint64_t 
     return a < b ? a : b;
 }
 
+// What a run keeps of the records it proves.  Every mode passes the same text through the same windows with
+// the same cuts and proves every window; the mode decides only what leaves the block.
+//   FX_KEEP_ALL   identifiers and lengths to the host, bases to the store (every call before the selected ingest)
+//   FX_KEEP_NONE  nothing: the records and their bases are counted (the census pass)
+//   FX_KEEP_SEL   those of a strictly ascending list of record ordinals (file order, 0-based)
+enum FxKeepMode { FX_KEEP_ALL = 0, FX_KEEP_NONE = 1, FX_KEEP_SEL = 2 };
+// records seen, records kept, sequence bases seen, bases kept
+struct FxSelStats { uint64_t seen, kept, bases_seen, bases_kept; };
+
+// is sel[0, k) strictly ascending?
+static inline bool fx_sel_ascending(const uint32_t *sel, uint64_t k) {
+    for (uint64_t i = 1; i < k; ++i) if (sel[i] <= sel[i - 1]) return false;
+    return true;
+}
+
+// The slice of a selection that falls into one window: the window holds the records [r0, r0 + n_rec), sel[0, k) is strictly
+// ascending and sel[0, a) lies below r0 (the windows before took it).  Returns b: sel[a, b) are the window's, sel[b] is a later one's.
+static inline uint64_t fx_sel_slice(const uint32_t *sel, uint64_t k, uint64_t a, uint64_t r0, uint64_t n_rec) {
+    uint64_t lo = a, hi = k;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if ((uint64_t)sel[mid] < r0 + n_rec) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
 // the sniff for BAM, CRAM and SAM (fx_format) belongs to the first window: a read named HD.., SQ.. or RG.. may start a later one
 static inline void fx_win_census(FxCensus &c, bool first) {
     if (!first) c.head[0] = c.head[1] = c.head[2] = c.head[3] = 0;

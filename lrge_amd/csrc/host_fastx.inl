@@ -7,7 +7,8 @@
 // caller takes lrge_hip_read_records*, which parses the file or reports it with the reference's messages.  With
 // LRGE_GPU_INGEST_WINDOWED FASTA / FASTQ text larger than option INGEST_WINDOW_BYTES passes through HBM in windows and only the
 // bases stay (fx_window.h); with LRGE_GPU_INGEST_WINDOWED_ALN beside it so does unaligned BAM and SAM, BAM's
-// bases staying packed.  Included into lrge_hip.hip.
+// bases staying packed.  lrge_hip_reads_census* and lrge_hip_reads_open_selected* pass FASTA / FASTQ text through
+// the same windows and keep nothing, or only the records of a list of ordinals (FxKeepMode).  Included into lrge_hip.hip.
 // A call (lrge_hip_reads_open_mem) is one source (fx_src_raw, _bgzf, _gzip, _bzip2), which brings the text to the sink (FxSink) resident
 // or through the windows of the sink's FxWinRun, and one record scan (fx_parse_kind), chosen by the sniff (fx_kind).
 
@@ -29,6 +30,7 @@ struct lrge_hip_reads {
     FxWinStats win = {0, 0, 0, 0};              // lrge_hip_reads_window_stats
     bool is_cram = false;                       // opened from unaligned CRAM (host_cram.inl): d_text is a base store, as a windowed FASTA handle's
     CramStats cram;                             // lrge_hip_reads_cram_stats
+    FxSelStats sel = {0, 0, 0, 0};              // lrge_hip_reads_select_stats: the pass of lrge_hip_reads_open_selected* (a window: what it adds)
 };
 
 static double fx_now_ms() { return DevPool::now_ms(); }
@@ -54,13 +56,15 @@ static int fx_alloc_recs(lrge_hip_ctx *ctx, lrge_hip_reads *R, u64 n) {
 }
 
 // behind the kernel that fills the record table: its verdict bits ([0], low word) and the identifier bytes ([1]) come back
-static int fx_flags_back(lrge_hip_ctx *ctx, const u64 *d_flags, const char *outside, u64 *name_bytes) {
-    u64 flags[2] = {0, 0};
-    HIPCHK(ctx, ctx->d2h(flags, d_flags, sizeof flags, ctx->stream));
+// (bases: d_flags has a third word, the sum of the sequence lengths by k_fx_bases, which comes back in the same copy)
+static int fx_flags_back(lrge_hip_ctx *ctx, const u64 *d_flags, const char *outside, u64 *name_bytes, u64 *bases = nullptr) {
+    u64 flags[3] = {0, 0, 0};
+    HIPCHK(ctx, ctx->d2h(flags, d_flags, bases ? 24 : 16, ctx->stream));
     HIPCHK(ctx, ctx->d2h_sync(ctx->stream));
     if ((u32)flags[0]) return fx_verdict_rc(ctx, (u32)flags[0], outside);
     if (flags[1] >> 32) return fx_verdict_rc(ctx, FX_UNPROVEN, "4 GiB of identifiers or more");
     *name_bytes = flags[1];
+    if (bases) *bases = flags[2];
     return LRGE_OK;
 }
 
@@ -135,12 +139,37 @@ struct FxWinDev {
     double ms_scan = 0, ms_names = 0;
     int rc = LRGE_OK;                           // what stopped the windows, with its message (a decoder's hook can only say "stop")
     std::string msg;
+    // what the run keeps (fx_window.h).  FX_KEEP_SEL: sel[0, k), strictly ascending, on the host and -- uploaded
+    // once -- in d_sel; sel[0, at) lay in the windows flushed so far, whose records are R->sel.seen
+    FxKeepMode mode = FX_KEEP_ALL;
+    const u32 *sel = nullptr;
+    u32 *d_sel = nullptr;
+    u64 k = 0, at = 0;
     FxWinDev(lrge_hip_ctx *c, lrge_hip_reads *r, int f, u64 cap_) : ctx(c), R(r), flags(f), cap(cap_), store(c) {
         store.keep_on = true; store.keep_slack = FX_PAD; store.keep_floor = 0;      // (block and store share one budget: neither takes more than it needs or doubles to)
         R->name_off.assign(1, 0);
     }
+    ~FxWinDev() { ctx->pool.release(d_sel); }
+    int select(FxKeepMode m, const u32 *s, u64 n) {
+        mode = m; sel = s; k = n;
+        if (m != FX_KEEP_SEL || !n) return LRGE_OK;
+        hipError_t e = hipSuccess;
+        if (!(d_sel = (u32 *)ctx->pool.alloc((size_t)n * 4, &e))) { LRGE_SET_ERR(ctx, "reads_open_selected: selection: %s", hipGetErrorString(e)); return LRGE_ERR_DEVICE; }
+        HIPCHK(ctx, hipMemcpyAsync(d_sel, s, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));            // (the caller's list is pageable: its copy is done)
+        return LRGE_OK;
+    }
     u64 len() const { return blk->keep_len; }
     int unproven(const char *what) { LRGE_SET_ERR(ctx, "reads_open: not proven on the device (%s)", what); return LRGE_ERR_UNPROVEN; }
+    // the census and the selected open take FASTA / FASTQ, whatever flags came with the call: the sniff of the text's first bytes
+    int selected_format() {
+        u8 head[4] = {0, 0, 0, 0};
+        const u64 n = blk->keep_len;
+        if (n) { HIPCHK(ctx, hipMemcpyAsync(head, blk->keep, (size_t)std::min<u64>(4, n), hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); }
+        if (fx_sniff(LRGE_GPU_INGEST_BAM | LRGE_GPU_INGEST_SAM, head, n) == FX_FMT_EMPTY && !(n >= 4 && !memcmp(head, "CRAM", 4))) return LRGE_OK;
+        ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only";
+        return LRGE_ERR_UNPROVEN;
+    }
     // the sniff of the first window makes the run a BAM or SAM run: a later window is never sniffed.  BAM and SAM that stay
     // resident turn the windows off: the block takes back the growth rule a resident text has without the flag (attach() had made it
     // a window's; keep_flush stays: it is running, and the driver returns at once from now on).  (Plain and BGZF input is sniffed
@@ -148,6 +177,7 @@ struct FxWinDev {
     u64 was_hint = 0, was_floor = 0, was_grow = 2;
     int resident_format(bool *yes) {
         *yes = false;
+        if (mode != FX_KEEP_ALL) return selected_format();
         const int rc = fx_kind(ctx, flags, nullptr, blk->keep, blk->keep_len, &kind);
         if (rc) return rc;
         if ((*yes = !fx_kind_windowed(flags, kind))) { blk->keep_hint = was_hint; blk->keep_floor = was_floor; blk->keep_grow = was_grow; blk->keep_max = cap; }
@@ -164,6 +194,12 @@ struct FxWinDev {
         if (prc) return prc;
         *cut = end ? W.n_text : w.cut; *fmt = W.fmt;
         if (*cut) { u64 *sum = &R->bam.segments; const u64 *add = &W.bam.segments; for (int i = 0; i < 6; ++i) sum[i] += add[i]; }
+        if (*cut && mode != FX_KEEP_ALL) {        // (W.n, W.names and W.seq_len: the chosen records of the window, W.sel: all of them)
+            if ((R->sel.seen + W.sel.seen) >> 32) return fx_verdict_rc(ctx, FX_UNPROVEN, "2^32 records or more");
+            R->sel.seen += W.sel.seen; R->sel.bases_seen += W.sel.bases_seen;
+            R->sel.kept += W.sel.kept; R->sel.bases_kept += W.sel.bases_kept;
+            at += W.sel.kept;
+        }
         if (!*cut || !W.n) return LRGE_OK;
         if ((R->n + W.n) >> 32) return fx_verdict_rc(ctx, FX_UNPROVEN, "2^32 records or more");
         if ((R->names.size() + W.names.size()) >> 32) return fx_verdict_rc(ctx, FX_UNPROVEN, "4 GiB of identifiers or more");
@@ -174,13 +210,8 @@ struct FxWinDev {
         R->n += W.n;
         return LRGE_OK;
     }
-    // the bases of the window's records (table W.d_recs, lengths d_seq_len) behind those of the earlier windows; BAM: the packed
-    // bytes, (seq_len + 1) / 2 a record
-    int store_window(Scratch &sc, const lrge_hip_reads &W, const u32 *d_seq_len, u64 n_use) {
-        const bool packed = W.fmt == FX_FMT_BAM;
-        u64 sum = 0;
-        for (u32 l : W.seq_len) sum += packed ? ((u64)l + 1) / 2 : l;
-        if (sum >> 32) return fx_verdict_rc(ctx, FX_UNPROVEN, "a window of 2^32 bytes or more");      // (never: the window is below that)
+    // room for `sum` more bytes in the store, within the budget it shares with the block
+    int store_room(u64 sum) {
         // the store doubles while that leaves the block room to double as well; close to the cap it grows by an eighth
         const u64 need = store.keep_len + sum, room = cap > blk->keep_cap ? cap - blk->keep_cap : 0, soft = cap > 2 * blk->keep_cap ? cap - 2 * blk->keep_cap : 0;
         store.keep_max = need <= soft ? soft : std::min<u64>(room, need + need / 8);
@@ -190,6 +221,58 @@ struct FxWinDev {
             return LRGE_ERR_DEVICE;
         }
         blk->keep_max = cap > store.keep_cap ? cap - store.keep_cap : 0;
+        return LRGE_OK;
+    }
+    // A window of a run that does not keep all (FX_KEEP_NONE, FX_KEEP_SEL), behind k_fx_records: W.d_recs and the lengths of its
+    // n_rec records are on the device, `bases` is their sum.  The slice of the selection that falls into the window is found
+    // here; a window without a chosen record costs nothing more.  Else k_fx_pick gathers the chosen lengths, which come down and
+    // are scanned, and k_fx_keep copies identifiers and bases.  W leaves as a window of the chosen records only
+    int keep_window(Scratch &sc, lrge_hip_reads *W, const u32 *d_seq_len, const u32 *d_name_len, u64 n_rec, u64 n_use, u64 bases) {
+        W->sel = FxSelStats{n_rec, 0, bases, 0};
+        W->n = 0;
+        const u64 r0 = R->sel.seen, a = at, b = mode == FX_KEEP_SEL ? fx_sel_slice(sel, k, a, r0, n_rec) : a, m = b - a;
+        if (!m) return LRGE_OK;
+        const double t0 = fx_now_ms();
+        hipStream_t st = ctx->stream;
+        int rc;
+        ALLOC_OR_FAIL(d_pick_seq, sc, u32, m);
+        ALLOC_OR_FAIL(d_pick_name, sc, u32, m);
+        hipLaunchKernelGGL(k_fx_pick, dim3((u32)div_up(m, FX_THREADS)), dim3(FX_THREADS), 0, st, (const u32 *)(d_sel + a), (u32)r0, m, d_seq_len, d_name_len, d_pick_seq, d_pick_name);
+        KCHK(ctx);
+        std::vector<u32> name_len((size_t)m);
+        W->seq_len.resize((size_t)m);
+        HIPCHK(ctx, hipMemcpyAsync(W->seq_len.data(), d_pick_seq, (size_t)m * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipMemcpyAsync(name_len.data(), d_pick_name, (size_t)m * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipStreamSynchronize(st));
+        W->name_off.assign(1, 0);
+        u64 sum = 0, name_bytes = 0;
+        for (u64 j = 0; j < m; ++j) { sum += W->seq_len[j]; name_bytes += name_len[j]; W->name_off.push_back(name_bytes); }
+        if (sum > bases || sum >> 32 || name_bytes >> 32) return fx_verdict_rc(ctx, FX_UNPROVEN, "a window of 2^32 bytes or more");      // (never: the window is below that)
+        if ((rc = store_room(sum))) return rc;
+        ALLOC_OR_FAIL(d_dst, sc, u32, m);
+        ALLOC_OR_FAIL(d_name_dst, sc, u32, m);
+        ALLOC_OR_FAIL(d_names, sc, u8, std::max<u64>(1, name_bytes));
+        if ((rc = scan_exclusive_u32(ctx, sc, d_pick_seq, d_dst, m, nullptr)) || (rc = scan_exclusive_u32(ctx, sc, d_pick_name, d_name_dst, m, nullptr))) return rc;
+        hipLaunchKernelGGL(k_fx_keep, dim3((u32)std::min<u64>(m, (u64)ctx->n_cu * 32)), dim3(64), 0, st, (const u8 *)W->d_text, n_use, (const FxRec *)W->d_recs, (const u32 *)(d_sel + a), (u32)r0,
+                           m, (const u32 *)d_dst, (const u32 *)d_name_dst, store.keep + store.keep_len, d_names);
+        KCHK(ctx);
+        W->names.resize((size_t)name_bytes);
+        if (name_bytes) HIPCHK(ctx, hipMemcpyAsync(&W->names[0], d_names, (size_t)name_bytes, hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipStreamSynchronize(st));                     // (also: the scratch and the table go back to the pool, which other streams draw from)
+        store.keep_len += sum;
+        W->n = m; W->sel.kept = m; W->sel.bases_kept = sum;
+        W->ms[2] = (float)(fx_now_ms() - t0);
+        return LRGE_OK;
+    }
+    // the bases of the window's records (table W.d_recs, lengths d_seq_len) behind those of the earlier windows; BAM: the packed
+    // bytes, (seq_len + 1) / 2 a record
+    int store_window(Scratch &sc, const lrge_hip_reads &W, const u32 *d_seq_len, u64 n_use) {
+        const bool packed = W.fmt == FX_FMT_BAM;
+        u64 sum = 0;
+        for (u32 l : W.seq_len) sum += packed ? ((u64)l + 1) / 2 : l;
+        if (sum >> 32) return fx_verdict_rc(ctx, FX_UNPROVEN, "a window of 2^32 bytes or more");      // (never: the window is below that)
+        const int rrc = store_room(sum);
+        if (rrc) return rrc;
         if (W.n) {
             ALLOC_OR_FAIL(d_dst, sc, u32, W.n);
             const dim3 grid((u32)std::min<u64>(W.n, (u64)ctx->n_cu * 32));
@@ -263,6 +346,10 @@ struct FxWinRun {
         dev.blk = &last;
         int rc = win.step(true);
         if (rc) return rc;
+        if (dev.mode == FX_KEEP_SEL && dev.at < dev.k) {        // (the selection is ascending: the first ordinal left over names the fault)
+            LRGE_SET_ERR(ctx, "reads_open_selected: ordinal %u of %llu records", dev.sel[dev.at], (unsigned long long)R->sel.seen);
+            return LRGE_ERR_INVALID;
+        }
         if (!dev.store.keep && !dev.store.keep_reserve(0)) { LRGE_SET_ERR(ctx, "reads_open: device allocation failed"); return LRGE_ERR_DEVICE; }
         std::vector<FxRec> tab((size_t)R->n);
         const bool packed = win.fmt == FX_FMT_BAM;              // (the gather of BAM reads its records' spans as it reads the text)
@@ -370,13 +457,20 @@ static int fx_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R, FxWinScan *w) {
     if ((rc = fx_alloc_recs(ctx, R, n_rec))) return rc;
     ALLOC_OR_FAIL(d_seq_len, sc, u32, n_rec);
     ALLOC_OR_FAIL(d_name_len, sc, u32, n_rec);
-    ALLOC_OR_FAIL(d_flags, sc, u64, 2);                   // [0]: verdict bits (low word), [1]: identifier bytes
-    HIPCHK(ctx, hipMemsetAsync(d_flags, 0, 16, st));
+    ALLOC_OR_FAIL(d_flags, sc, u64, 3);                   // [0]: verdict bits (low word), [1]: identifier bytes, [2]: bases (a run that does not keep all)
+    HIPCHK(ctx, hipMemsetAsync(d_flags, 0, 24, st));
+    const FxKeepMode mode = w ? w->dev->mode : FX_KEEP_ALL;
     const u32 rec_blocks = (u32)div_up(n_rec, FX_THREADS);
     hipLaunchKernelGGL(k_fx_records, dim3(rec_blocks), dim3(FX_THREADS), 0, st, t, n_use, fmt, n_rec, (const u64 *)ls, n_lf, n_lines, l0, (const u64 *)hpos, (const u32 *)hrem,
                        n_rem, R->d_recs, d_seq_len, d_name_len, (u32 *)d_flags, (unsigned long long *)(d_flags + 1));
     KCHK(ctx);
-    u64 name_bytes = 0;
+    u64 name_bytes = 0, bases = 0;
+    if (mode != FX_KEEP_ALL) {                             // the census and the selected open: the window's bases come back with the verdict
+        hipLaunchKernelGGL(k_fx_bases, dim3(std::min<u32>(rec_blocks, (u32)ctx->n_cu * 8)), dim3(FX_THREADS), 0, st, (const u32 *)d_seq_len, n_rec, (unsigned long long *)(d_flags + 2));
+        KCHK(ctx);
+        if ((rc = fx_flags_back(ctx, d_flags, "a record outside the strict form", &name_bytes, &bases))) return rc;
+        return w->dev->keep_window(sc, R, d_seq_len, d_name_len, n_rec, n_use, bases);
+    }
     if ((rc = fx_flags_back(ctx, d_flags, "a record outside the strict form", &name_bytes))) return rc;
     if ((rc = fx_tables_to_host(ctx, R, sc, n_rec, d_seq_len, d_name_len, name_bytes)) || !w) return rc;
     return w->dev->store_window(sc, *R, d_seq_len, n_use);
@@ -400,9 +494,10 @@ struct FxSink {
     std::unique_ptr<FxWinRun> run;              // LRGE_GPU_INGEST_WINDOWED: text larger than a window passes through the block in windows (fx_window.h)
     DevKeep blk;
     const u8 *host_text = nullptr;              // the file's bytes, when they are the text
-    FxSink(lrge_hip_ctx *c, lrge_hip_reads *r, int f) : ctx(c), R(r), flags(f), cap(ingest_cap(c)),
-        window(std::max<u64>(1, c->opt_u64("INGEST_WINDOW_BYTES", std::min<u64>((u64)1 << 30, cap / 4)))), blk(c) {
-        if (flags & LRGE_GPU_INGEST_WINDOWED) run.reset(new FxWinRun(ctx, R, flags, cap, window));
+    FxKeepMode mode;                            // the census and the selected open: every text goes through the windows, whatever its size
+    FxSink(lrge_hip_ctx *c, lrge_hip_reads *r, int f, FxKeepMode m = FX_KEEP_ALL) : ctx(c), R(r), flags(f), cap(ingest_cap(c)),
+        window(std::max<u64>(1, c->opt_u64("INGEST_WINDOW_BYTES", std::min<u64>((u64)1 << 30, cap / 4)))), blk(c), mode(m) {
+        if ((flags & LRGE_GPU_INGEST_WINDOWED) || mode != FX_KEEP_ALL) run.reset(new FxWinRun(ctx, R, flags, cap, window));
         blk.keep_on = true; blk.keep_max = cap; blk.keep_slack = FX_PAD;
     }
     int over_cap() { LRGE_SET_ERR(ctx, "reads_open: text above INGEST_MAX_BYTES (%llu)", (unsigned long long)cap); return LRGE_ERR_UNPROVEN; }
@@ -410,6 +505,7 @@ struct FxSink {
     // only where it decides: BAM and SAM that stay resident take the resident route exactly as without the windowed flag
     template <class F> int windowed(u64 n, F kind_of, bool *yes) {
         *yes = false;
+        if (mode != FX_KEEP_ALL) { run->attach(&blk); *yes = true; return LRGE_OK; }       // (the first flush sniffs: FxWinDev::selected_format)
         if (!run || n <= window) return LRGE_OK;
         int kind = FX_FMT_EMPTY;
         if (flags & (LRGE_GPU_INGEST_BAM | LRGE_GPU_INGEST_SAM)) { const int rc = kind_of(&kind); if (rc) return rc; }
@@ -618,15 +714,21 @@ extern "C" void lrge_hip_reads_free(lrge_hip_reads *r) {
     delete r;
 }
 
-extern "C" int lrge_hip_reads_open_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, int flags, lrge_hip_reads **out) {
+// one call: lrge_hip_reads_open_mem (FX_KEEP_ALL), the census (FX_KEEP_NONE) or the selected open (FX_KEEP_SEL with sel[0, k))
+static int fx_open_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, int flags, FxKeepMode mode, const u32 *sel, u64 k, lrge_hip_reads **out) {
     if (!ctx || !out || (!file_bytes && len)) return LRGE_ERR_INVALID;
     *out = nullptr;
+    if (mode == FX_KEEP_SEL && ((k && !sel) || !fx_sel_ascending(sel, k))) { ctx->err = "reads_open_selected: the ordinals are not strictly ascending"; return LRGE_ERR_INVALID; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const double t0 = fx_now_ms();
     const u8 *d = (const u8 *)file_bytes;
     std::unique_ptr<lrge_hip_reads, void (*)(lrge_hip_reads *)> guard(new lrge_hip_reads(), lrge_hip_reads_free);
     guard->ctx = ctx;
     const auto b = [&](u64 i) -> u32 { return i < len ? d[i] : 0x100u; };
+    if (mode != FX_KEEP_ALL && b(0) == 'C' && b(1) == 'R' && b(2) == 'A' && b(3) == 'M') {     // (whatever the flags: FxWinDev::selected_format)
+        ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only";
+        return LRGE_ERR_UNPROVEN;
+    }
     // unaligned CRAM, for the caller who asked for it: a host walk and a device decode of the base blocks, no text and no record scan
     if ((flags & LRGE_GPU_INGEST_CRAM) && b(0) == 'C' && b(1) == 'R' && b(2) == 'A' && b(3) == 'M') {
         const int crc = fx_open_cram(ctx, guard.get(), d, len, t0);
@@ -634,12 +736,16 @@ extern "C" int lrge_hip_reads_open_mem(lrge_hip_ctx *ctx, const void *file_bytes
         *out = guard.release();
         return LRGE_OK;
     }
-    FxSink s(ctx, guard.get(), flags);
+    FxSink s(ctx, guard.get(), flags, mode);
     // the source, by the file's magic
     std::vector<BgzfBlock> t;
     uint64_t total = 0;
     int rc;
-    if (b(0) == 0x1f && b(1) == 0x8b) rc = bgzf_scan_blocks(d, len, &t, &total) ? fx_src_bgzf(s, d, t, total) : fx_src_gzip(s, d, len);
+    if (mode != FX_KEEP_ALL && (rc = s.run->dev.select(mode, sel, k))) return rc;
+    if (mode != FX_KEEP_ALL && b(0) == 0x28 && b(1) == 0xb5 && b(2) == 0x2f && b(3) == 0xfd && (flags & LRGE_GPU_INFLATE_ZSTD)) {
+        ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only, not Zstandard input";       // (its text is never windowed)
+        rc = LRGE_ERR_UNPROVEN;
+    } else if (b(0) == 0x1f && b(1) == 0x8b) rc = bgzf_scan_blocks(d, len, &t, &total) ? fx_src_bgzf(s, d, t, total) : fx_src_gzip(s, d, len);
     else if (b(0) == 0x42 && b(1) == 0x5a && (flags & LRGE_GPU_INFLATE_BZIP2)) rc = fx_src_bzip2(s, d, len);
     else if (b(0) == 0x28 && b(1) == 0xb5 && b(2) == 0x2f && b(3) == 0xfd && (flags & LRGE_GPU_INFLATE_ZSTD)) rc = fx_src_zstd(s, d, len);
     else if (b(0) == 0xfd && b(1) == 0x37 && b(2) == 0x7a && b(3) == 0x58 && b(4) == 0x5a && b(5) == 0x00 && (flags & LRGE_GPU_INFLATE_XZ)) rc = fx_src_xz(s, d, len);
@@ -649,8 +755,54 @@ extern "C" int lrge_hip_reads_open_mem(lrge_hip_ctx *ctx, const void *file_bytes
         rc = LRGE_ERR_UNPROVEN;
     } else rc = fx_src_raw(s, d, len);
     if (rc) return rc;
-    if ((rc = s.run && s.run->win.st.windows ? fx_finish_windowed(s, t0) : fx_finish_resident(s, t0))) return rc;
+    if ((rc = s.run && (s.run->win.st.windows || mode != FX_KEEP_ALL) ? fx_finish_windowed(s, t0) : fx_finish_resident(s, t0))) return rc;
     *out = guard.release();
+    return LRGE_OK;
+}
+
+extern "C" int lrge_hip_reads_open_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, int flags, lrge_hip_reads **out) {
+    return fx_open_mem(ctx, file_bytes, len, flags, FX_KEEP_ALL, nullptr, 0, out);
+}
+
+// ---- the selected ingest: a pass that keeps nothing, and one that keeps the chosen records ----
+extern "C" int lrge_hip_reads_census_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, int flags, uint64_t out[4]) {
+    if (!ctx || !out) return LRGE_ERR_INVALID;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    lrge_hip_reads *r = nullptr;
+    const int rc = fx_open_mem(ctx, file_bytes, len, flags, FX_KEEP_NONE, nullptr, 0, &r);
+    if (rc) return rc;
+    out[0] = r->sel.seen; out[1] = r->sel.bases_seen; out[2] = r->text_bytes; out[3] = r->win.windows;
+    lrge_hip_reads_free(r);
+    return LRGE_OK;
+}
+
+extern "C" int lrge_hip_reads_open_selected_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, int flags, const uint32_t *sel, uint32_t k, lrge_hip_reads **out) {
+    return fx_open_mem(ctx, file_bytes, len, flags, FX_KEEP_SEL, sel, k, out);
+}
+
+static int fx_slurp(lrge_hip_ctx *ctx, const char *path, std::string *raw) {
+    try { *raw = lrge::io::slurp(path); } catch (const std::exception &e) { ctx->err = e.what(); return LRGE_ERR_IO; }
+    return LRGE_OK;
+}
+
+extern "C" int lrge_hip_reads_census(lrge_hip_ctx *ctx, const char *path, int flags, uint64_t out[4]) {
+    if (!ctx || !path || !out) return LRGE_ERR_INVALID;
+    std::string raw;
+    const int rc = fx_slurp(ctx, path, &raw);
+    return rc ? rc : lrge_hip_reads_census_mem(ctx, raw.data(), raw.size(), flags, out);
+}
+
+extern "C" int lrge_hip_reads_open_selected(lrge_hip_ctx *ctx, const char *path, int flags, const uint32_t *sel, uint32_t k, lrge_hip_reads **out) {
+    if (!ctx || !path || !out) return LRGE_ERR_INVALID;
+    *out = nullptr;
+    std::string raw;
+    const int rc = fx_slurp(ctx, path, &raw);
+    return rc ? rc : lrge_hip_reads_open_selected_mem(ctx, raw.data(), raw.size(), flags, sel, k, out);
+}
+
+extern "C" int lrge_hip_reads_select_stats(const lrge_hip_reads *r, uint64_t out[4]) {
+    if (!r || !out) return LRGE_ERR_INVALID;
+    out[0] = r->sel.seen; out[1] = r->sel.kept; out[2] = r->sel.bases_seen; out[3] = r->sel.bases_kept;
     return LRGE_OK;
 }
 

@@ -12,6 +12,9 @@
 //   k_fx_names     identifiers compacted into one dense buffer
 //   k_fx_gather    one wavefront per selected read: its bases into one dense ASCII buffer, removed bytes dropped
 //   k_fx_store     windowed ingest: one wavefront per record of a window, its bases into the base store   (same copy)
+//   k_fx_bases     selected ingest: the sum of a window's sequence lengths           4 B read per record
+//   k_fx_pick      one lane per chosen record of a window: its two lengths into dense arrays
+//   k_fx_keep      one wavefront per chosen record: its identifier into the identifier buffer, its bases into the store   (same copy)
 // The text buffer is allocated with FX_PAD bytes behind its end, so whole 16-byte groups (and the word behind an unaligned
 // source word of the gather) may be loaded; every byte at or past `n` is masked out before use.
 #pragma once
@@ -234,4 +237,38 @@ __global__ __launch_bounds__(64) void k_fx_gather(const u8 *__restrict__ t, u64 
 __global__ __launch_bounds__(64) void k_fx_store(const u8 *__restrict__ t, u64 n, const FxRec *__restrict__ recs, const u32 *__restrict__ dst, u64 n_rec,
                                                  u8 *__restrict__ store) {
     for (u64 r = blockIdx.x; r < n_rec; r += gridDim.x) fx_copy_bases(t, n, recs[r], store + dst[r], threadIdx.x);
+}
+
+// Selected ingest (fx_window.h FX_KEEP_NONE / FX_KEEP_SEL).  The sum of a window's seq_len, added to *total: the
+// bases the pass has seen.  Grid stride, one atomic a wavefront; *total comes back with the verdict words of k_fx_records.
+__global__ __launch_bounds__(FX_THREADS) void k_fx_bases(const u32 *__restrict__ seq_len, u64 n_rec, unsigned long long *__restrict__ total) {
+    u64 s = 0;
+    for (u64 r = (u64)blockIdx.x * FX_THREADS + threadIdx.x; r < n_rec; r += (u64)gridDim.x * FX_THREADS) s += seq_len[r];
+    for (int d = 32; d > 0; d >>= 1) s += __shfl_down(s, d, 64);
+    if (lane_id() == 0 && s) atomicAdd(total, (unsigned long long)s);
+}
+
+// The chosen records of a window, one lane each: sel[0, n_sel) is the window's slice of the selection (fx_sel_slice: file
+// ordinals, ascending), r0 the ordinal of the window's first record.  Their lengths go to dense arrays of n_sel entries, the inputs
+// of the two scans that place them and of the copies to the host.
+__global__ __launch_bounds__(FX_THREADS) void k_fx_pick(const u32 *__restrict__ sel, u32 r0, u64 n_sel, const u32 *__restrict__ seq_len, const u32 *__restrict__ name_len,
+                                                        u32 *__restrict__ pick_seq, u32 *__restrict__ pick_name) {
+    const u64 j = (u64)blockIdx.x * FX_THREADS + threadIdx.x;
+    if (j >= n_sel) return;
+    const u32 r = sel[j] - r0;
+    pick_seq[j] = seq_len[r]; pick_name[j] = name_len[r];
+}
+
+// Chosen record j of the window, one wavefront each: its identifier to names[name_dst[j], ..), its bases to store[dst[j], ..) by the
+// copy body of k_fx_gather and k_fx_store.  dst / name_dst: the exclusive scans of k_fx_pick's arrays; `store` and `names` point
+// behind what the earlier windows kept.
+__global__ __launch_bounds__(64) void k_fx_keep(const u8 *__restrict__ t, u64 n, const FxRec *__restrict__ recs, const u32 *__restrict__ sel, u32 r0, u64 n_sel,
+                                                const u32 *__restrict__ dst, const u32 *__restrict__ name_dst, u8 *__restrict__ store, u8 *__restrict__ names) {
+    for (u64 j = blockIdx.x; j < n_sel; j += gridDim.x) {
+        const FxRec rec = recs[sel[j] - r0];
+        const u8 *s = t + rec.name_off;
+        u8 *d = names + name_dst[j];
+        for (u32 i = threadIdx.x; i < rec.name_len; i += 64) d[i] = s[i];
+        fx_copy_bases(t, n, rec, store + dst[j], threadIdx.x);
+    }
 }

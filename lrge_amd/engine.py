@@ -167,6 +167,29 @@ class Context:
         prove raises UnprovenInput: read the file with the host readers (readio.load) instead."""
         return DeviceReads(self, path_or_bytes, flags)
 
+    def census_reads(self, src, flags=_ffi.GPU_INFLATE_BGZF | _ffi.GPU_INFLATE_GZIP):
+        """The count pass of the sampled ingest (lrge_hip_reads_census*): the FASTA / FASTQ text of `src` (a path, or the bytes of
+        the whole file) passes through the windows and is proven, nothing is kept.  Returns (records, sequence bases, text bytes,
+        windows flushed); input the device does not prove raises UnprovenInput."""
+        L = self._lib
+        out = (C.c_uint64 * 4)()
+        if isinstance(src, (bytes, bytearray, memoryview, np.ndarray)):
+            buf = np.frombuffer(src, dtype=np.uint8) if not isinstance(src, np.ndarray) else np.ascontiguousarray(src, dtype=np.uint8)
+            rc = L.lrge_hip_reads_census_mem(self.h, buf.ctypes.data if buf.size else None, buf.size, int(flags), C.byref(out))
+        else:
+            import os
+            rc = L.lrge_hip_reads_census(self.h, os.fsencode(str(src)), int(flags), C.byref(out))
+        if rc == _ffi.ERR_UNPROVEN:
+            raise UnprovenInput(rc, L.lrge_hip_last_error(self.h).decode())
+        self._check(rc)
+        return tuple(int(x) for x in out)
+
+    def open_reads_selected(self, src, sel, flags=_ffi.GPU_INFLATE_BGZF | _ffi.GPU_INFLATE_GZIP):
+        """The second pass of the sampled ingest (lrge_hip_reads_open_selected*): only records `sel` (strictly ascending ordinals
+        in file order, 0-based) of the FASTA / FASTQ text of `src` are kept.  Returns a DeviceReads of len(sel) reads in file
+        order, read j being record sel[j]; DeviceReads.select_stats() tells what the pass saw."""
+        return DeviceReads(self, src, flags, sel)
+
     def _name_ranks(self, blob, name_off, n_names, idx_lists):
         """lrge_hip_name_ranks over a table of identifiers; idx_lists None: every identifier in order, as one list"""
         if idx_lists is None:
@@ -343,16 +366,25 @@ class DeviceReads:
     """The reads of one input file resident in HBM as text (lrge_hip_reads): `names` (list of bytes) and `lens` (uint32) are
     on the host, the bases never are.  seqset(idx, ranks) is an ordinary SeqSet of the chosen reads."""
 
-    def __init__(self, ctx, src, flags):
+    def __init__(self, ctx, src, flags, sel=None):
         self.ctx, self.h = ctx, None
         h = C.c_void_p()
         L = ctx._lib
+        if sel is not None:                                 # Context.open_reads_selected
+            sel = np.ascontiguousarray(sel, dtype=np.uint32).ravel()
+            sel_args = (sel.ctypes.data if sel.size else None, int(sel.size))
         if isinstance(src, (bytes, bytearray, memoryview, np.ndarray)):
             buf = np.frombuffer(src, dtype=np.uint8) if not isinstance(src, np.ndarray) else np.ascontiguousarray(src, dtype=np.uint8)
-            rc = L.lrge_hip_reads_open_mem(ctx.h, buf.ctypes.data if buf.size else None, buf.size, int(flags), C.byref(h))
+            if sel is not None:
+                rc = L.lrge_hip_reads_open_selected_mem(ctx.h, buf.ctypes.data if buf.size else None, buf.size, int(flags), *sel_args, C.byref(h))
+            else:
+                rc = L.lrge_hip_reads_open_mem(ctx.h, buf.ctypes.data if buf.size else None, buf.size, int(flags), C.byref(h))
         else:
             import os
-            rc = L.lrge_hip_reads_open(ctx.h, os.fsencode(str(src)), int(flags), C.byref(h))
+            if sel is not None:
+                rc = L.lrge_hip_reads_open_selected(ctx.h, os.fsencode(str(src)), int(flags), *sel_args, C.byref(h))
+            else:
+                rc = L.lrge_hip_reads_open(ctx.h, os.fsencode(str(src)), int(flags), C.byref(h))
         if rc == _ffi.ERR_UNPROVEN:
             raise UnprovenInput(rc, L.lrge_hip_last_error(ctx.h).decode())
         ctx._check(rc)
@@ -399,6 +431,13 @@ class DeviceReads:
         in bytes, bytes carried over cuts)"""
         a = (C.c_uint64 * 4)()
         self.ctx._check(self.ctx._lib.lrge_hip_reads_window_stats(self.h, C.byref(a)))
+        return tuple(int(x) for x in a)
+
+    def select_stats(self):
+        """(records seen, records kept, sequence bases seen, bases kept) of the pass behind Context.open_reads_selected; zeros for
+        a handle of Context.open_reads"""
+        a = (C.c_uint64 * 4)()
+        self.ctx._check(self.ctx._lib.lrge_hip_reads_select_stats(self.h, C.byref(a)))
         return tuple(int(x) for x in a)
 
     def name_ranks(self, *idx_lists):

@@ -6,7 +6,11 @@ unaligned SAM text (the "sam" kind: its record scan beside the FASTQ kind's, and
 the files of the kinds asked for are written.  Usage:
   python tools/ingest_bench.py [--gbases 1.08] [--dir /tmp] [--reps 5] [--kinds fq,bgzf.fq.gz,fq.gz,bam,sam]
                                [--bam-segments 262144,1048576,4194304] [--out profiles/ingest_bench.json]
-                               [--windowed [--window-mb 64[,1024]]]
+                               [--windowed [--window-mb 64[,1024]]] [--sampled K [--window-mb 64]]
+--sampled K: on each FASTQ file the two passes of the sampled ingest (lrge_hip_reads_census, then lrge_hip_reads_open_selected of K
+seeded ordinals and a read set of those K) beside the existing windowed open of the same file (and its read set of ALL reads),
+alternating in the same run; the result goes under the key "sampled" of --out.  With LRGE_HIP_LIB_AB naming a build from before
+the sampled ingest only the existing open is timed, under the key "sampled_parent": the number to put beside the two passes.
 --windowed: on each file the windowed device route (LRGE_GPU_INGEST_WINDOWED | LRGE_GPU_INGEST_WINDOWED_ALN with option
 INGEST_WINDOW_BYTES = --window-mb, one run per size of the list on the same files) beside the resident device route, alternating in the same run; the result of the FASTQ kinds
 goes under the key "windowed" of --out, that of the kinds bam and sam under "windowed_aln" / "<window-mb>"; the other entries are
@@ -87,6 +91,38 @@ extern "C" int route_device(lrge_hip_ctx *ctx, const char *path, int flags, doub
     *n_reads = n; *n_bases = b; *text_bytes = lrge_hip_reads_text_bytes(r);
     lrge_hip_seqset_free(s); lrge_hip_reads_free(r);
     ms[0] = t1 - t0; ms[1] = t2 - t1;
+    return rc;
+}
+"""
+
+# ms: census, selected open (stages: its timings), read set of the k kept reads + wait
+HELPER_SAMPLED = r"""
+#include <chrono>
+#include <cstdint>
+#include <vector>
+#include "lrge_hip.h"
+static double now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+extern "C" int route_sampled(lrge_hip_ctx *ctx, const char *path, int flags, const uint32_t *sel, uint32_t k, double ms[3], float stages[4], uint64_t census[4],
+                             uint64_t stats[4], uint64_t win[4]) {
+    const double t0 = now();
+    int rc = lrge_hip_reads_census(ctx, path, flags, census);
+    if (rc) return rc;
+    const double t1 = now();
+    lrge_hip_reads *r = nullptr;
+    rc = lrge_hip_reads_open_selected(ctx, path, flags, sel, k, &r);
+    if (rc) return rc;
+    const double t2 = now();
+    std::vector<uint32_t> idx(k);
+    for (uint32_t i = 0; i < k; ++i) idx[i] = i;
+    lrge_hip_seqset *s = nullptr;
+    rc = lrge_hip_seqset_from_reads(ctx, r, idx.data(), k, nullptr, &s);
+    if (!rc) rc = lrge_hip_seqset_wait(s);
+    const double t3 = now();
+    lrge_hip_reads_timings(r, stages);
+    lrge_hip_reads_select_stats(r, stats);
+    lrge_hip_reads_window_stats(r, win);
+    lrge_hip_seqset_free(s); lrge_hip_reads_free(r);
+    ms[0] = t1 - t0; ms[1] = t2 - t1; ms[2] = t3 - t2;
     return rc;
 }
 """
@@ -220,6 +256,51 @@ def windowed_runs(a, ctx, H, kinds, paths, text_bytes, aln):
     json.dump(result, open(a.out, "w"), indent=1)
 
 
+def sampled_runs(a, ctx, H, HS, kinds, paths, text_bytes):
+    """the existing windowed open and -- HS: the library has them -- the two passes of the sampled ingest on every file, alternating;
+    into the key "sampled" (HS None: "sampled_parent") of a.out"""
+    import numpy as np
+    out = {"window_bytes": a.window_mb << 20, "reps": a.reps, "k": a.sampled, "files": {}}
+    ctx.set_option("INGEST_WINDOW_BYTES", str(a.window_mb << 20))
+    for kind in kinds:
+        p = paths[kind]
+        with open(p, "rb") as fh:
+            while fh.read(64 << 20):
+                pass                                                  # page cache
+        runs = {"open": [], "sampled": []}
+        sel, seen = None, {}
+        for rep in range(a.reps + 1):
+            ms2, st, nr, nb, tb, bs, win = (C.c_double * 2)(), (C.c_float * 4)(), C.c_uint64(), C.c_uint64(), C.c_uint64(), (C.c_uint64 * 6)(), (C.c_uint64 * 4)()
+            rc = H.route_device(ctx.h, p.encode(), 15 | 32 | 64, C.byref(ms2), C.byref(st), C.byref(nr), C.byref(nb), C.byref(tb), C.byref(bs), C.byref(win))
+            assert rc == 0, (kind, rc, ctx._lib.lrge_hip_last_error(ctx.h))
+            seen["reads"], seen["bases"], seen["windows"] = nr.value, nb.value, win[0]
+            if rep:                                                    # (run 0 is the warm-up)
+                runs["open"].append(dict(open_ms=ms2[0], seqset_all_ms=ms2[1], text_ms=st[0], scan_ms=st[1], names_ms=st[2]))
+            if HS is None:
+                continue
+            if sel is None:
+                sel = np.sort(np.random.default_rng(1).choice(nr.value, min(a.sampled, nr.value), replace=False)).astype(np.uint32)
+            ms3, st, cen, sst, win = (C.c_double * 3)(), (C.c_float * 4)(), (C.c_uint64 * 4)(), (C.c_uint64 * 4)(), (C.c_uint64 * 4)()
+            rc = HS.route_sampled(ctx.h, p.encode(), 15, sel.ctypes.data, sel.size, C.byref(ms3), C.byref(st), C.byref(cen), C.byref(sst), C.byref(win))
+            assert rc == 0, (kind, rc, ctx._lib.lrge_hip_last_error(ctx.h))
+            assert (cen[0], cen[1], cen[2]) == (nr.value, nb.value, text_bytes[kind]) and (sst[0], sst[1], sst[2]) == (nr.value, sel.size, nb.value), (list(cen), list(sst))
+            seen["kept_bases"], seen["sampled_windows"] = sst[3], win[0]
+            if rep:
+                runs["sampled"].append(dict(census_ms=ms3[0], selected_open_ms=ms3[1], both_ms=ms3[0] + ms3[1], seqset_k_ms=ms3[2], text_ms=st[0], scan_ms=st[1], names_ms=st[2]))
+        f = dict(file_bytes=os.path.getsize(p), text_bytes=text_bytes[kind], **seen)
+        for route, rr in runs.items():
+            for key in (rr[0] if rr else {}):
+                f["%s_%s_median" % (route, key)] = statistics.median(x[key] for x in rr)
+                f["%s_%s_range" % (route, key)] = (min(x[key] for x in rr), max(x[key] for x in rr))
+        out["files"][kind] = f
+        print(kind, json.dumps(f), flush=True)
+    ctx.set_option("INGEST_WINDOW_BYTES", None)
+    result = json.load(open(a.out)) if os.path.exists(a.out) else {}
+    result["sampled" if HS is not None else "sampled_parent"] = out
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    json.dump(result, open(a.out, "w"), indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gbases", type=float, default=1.08)
@@ -230,14 +311,17 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ingest_bench.json"))
     ap.add_argument("--windowed", action="store_true")
     ap.add_argument("--window-mb", default="64")
+    ap.add_argument("--sampled", type=int, default=0)
     a = ap.parse_args()
     from lrge_amd import build as B, engine
     work = tempfile.mkdtemp(dir=a.dir, prefix="ingest_bench_")
     src = os.path.join(work, "helper.cpp")
     open(src, "w").write(HELPER)
     so = os.path.join(work, "libhelper.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-I" + os.path.join(ROOT, "include"), "-o", so, src,
-                           "-L" + B.LIB_DIR, "-llrge_hip", "-Wl,-rpath," + B.LIB_DIR])
+    lib_dir = os.path.dirname(os.environ.get("LRGE_HIP_LIB_AB") or "") or B.LIB_DIR          # (the helper calls the library the context comes from)
+    build = lambda out, cpp: subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-I" + os.path.join(ROOT, "include"), "-o", out, cpp,   # noqa: E731
+                                                    "-L" + lib_dir, "-llrge_hip", "-Wl,-rpath," + lib_dir])
+    build(so, src)
     parts = max(1, round(a.gbases * 1e9 * 2.02 / (256 << 20)))       # a record is 2 bytes per base and a header
     t0 = time.perf_counter()
     kinds = [k for k in KINDS if k in a.kinds.split(",")]
@@ -248,6 +332,21 @@ def main():
     H.route_host.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_double * 3), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     H.route_device.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_double * 2), C.POINTER(C.c_float * 4), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                C.POINTER(C.c_uint64), C.POINTER(C.c_uint64 * 6), C.POINTER(C.c_uint64 * 4)]
+    if a.sampled:
+        HS, extra = None, []
+        if hasattr(ctx._lib, "lrge_hip_reads_census"):
+            extra = [os.path.join(work, "sampled.cpp"), os.path.join(work, "libsampled.so")]
+            open(extra[0], "w").write(HELPER_SAMPLED)
+            build(extra[1], extra[0])
+            HS = C.CDLL(extra[1])
+            HS.route_sampled.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(C.c_double * 3), C.POINTER(C.c_float * 4)] + [C.POINTER(C.c_uint64 * 4)] * 3
+        a.window_mb = int(a.window_mb.split(",")[0])
+        sampled_runs(a, ctx, H, HS, [k for k in kinds if k not in ("bam", "sam")], paths, text_bytes)
+        ctx.close()
+        for p in list(paths.values()) + [src, so] + extra:
+            os.remove(p)
+        os.rmdir(work)
+        return
     if a.windowed:
         for mb in a.window_mb.split(","):
             a.window_mb = int(mb)
