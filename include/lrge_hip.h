@@ -631,6 +631,40 @@ int      lrge_hip_reads_open_selected_mem(lrge_hip_ctx *ctx, const void *file_by
                                           uint32_t k, lrge_hip_reads **out);
 int      lrge_hip_reads_select_stats(const lrge_hip_reads *reads, uint64_t out[4]);
 
+/* The sampled ingest with a seek map (k_fx_seek, k_fx_runs): the reference's count pass (io.rs count_records,
+   io.rs:140-145) reads the whole file, and so must the census, but its second reading (the two-pass reading of twoset.rs:122-201
+   and ava.rs, which write only the drawn reads) needs only the places where drawn reads lie.  Opt-in: every call above does what it
+   did.
+   lrge_hip_reads_census_map*: lrge_hip_reads_census* (the same out[4], the same refusals with the same texts) that also leaves a
+   map: the text is cut into cells of option INGEST_SEEK_STRIDE_BYTES (default 65536, at least 1), and every cell in which a record
+   starts (at the '>' or '@' of its header line) gets one point -- the first such record's ordinal, its text offset and, for BGZF,
+   the block that holds that offset.  Free the map with lrge_hip_read_map_free; it belongs to no context.
+   lrge_hip_read_map_stats: out[0] records, out[1] points, out[2] the stride, out[3] text bytes.  lrge_hip_read_map_points: the first
+   `cap` points copied out (any of the arrays may be NULL): ordinal, text offset, file offset of the BGZF block (0 for plain input).
+   lrge_hip_reads_open_mapped*: lrge_hip_reads_open_selected* of the input the map was made of.  For plain and BGZF input only the
+   runs that hold chosen records (from the last point at or below an ordinal to the first point above it; runs that touch are merged)
+   are brought: the path form reads only those file ranges, BGZF decodes only their blocks (CRC and ISIZE checked as always).  The
+   runs, concatenated, are scanned and proven like any text, and the handle is the one lrge_hip_reads_open_selected* gives -- the
+   same reads, text_bytes and select_stats (seen / bases_seen are the file's, taken from the map).  A map of gzip, bzip2 or xz input
+   runs the full selected pass.  LRGE_ERR_INVALID, before any device work: ordinals not strictly ascending; "the map is of another
+   input" (file length, text bytes, block count or container differ); an ordinal at or above the map's records; and, path form, a
+   file range that does not hold the blocks the map names.  LRGE_ERR_UNPROVEN "the map does not fit the input": the runs are not
+   proven or hold another number of records than the map says -- the caller may take lrge_hip_reads_open_selected*.
+   lrge_hip_reads_seek_stats: out[0] runs, out[1] text bytes brought, out[2] file bytes read, out[3] BGZF blocks decoded by
+   lrge_hip_reads_open_mapped*; zeros for a handle of every other open. */
+typedef struct lrge_hip_read_map lrge_hip_read_map;
+int      lrge_hip_reads_census_map(lrge_hip_ctx *ctx, const char *path, int flags, uint64_t out[4], lrge_hip_read_map **map);
+int      lrge_hip_reads_census_map_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, int flags, uint64_t out[4],
+                                       lrge_hip_read_map **map);
+void     lrge_hip_read_map_free(lrge_hip_read_map *map);
+int      lrge_hip_read_map_stats(const lrge_hip_read_map *map, uint64_t out[4]);
+int      lrge_hip_read_map_points(const lrge_hip_read_map *map, uint64_t *ord, uint64_t *text_off, uint64_t *c_off, uint64_t cap);
+int      lrge_hip_reads_open_mapped(lrge_hip_ctx *ctx, const char *path, int flags, const lrge_hip_read_map *map, const uint32_t *sel,
+                                    uint32_t k, lrge_hip_reads **out);
+int      lrge_hip_reads_open_mapped_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, int flags, const lrge_hip_read_map *map,
+                                        const uint32_t *sel, uint32_t k, lrge_hip_reads **out);
+int      lrge_hip_reads_seek_stats(const lrge_hip_reads *reads, uint64_t out[4]);
+
 /* Read sets built on the device from unaligned CRAM 3.0 / 3.1 (k_rans_decode): | LRGE_GPU_INGEST_CRAM (opt-in:
    no other flag implies it, and without it every call does what it did) sends input that starts with "CRAM" to a host walk of the
    containers -- the record loop of lrge_hip_read_records under a policy that reads no base, so identifiers, lengths and flags are

@@ -127,6 +127,30 @@ struct DeviceReads {
         return r;
     }
     uint64_t select_stats[4] = {0, 0, 0, 0};   // lrge_hip_reads_select_stats: records seen, kept, sequence bases seen, kept (open_selected)
+    // The same two passes with a seek map.  census_map: census that also leaves the map (lrge_hip_reads_census_map;
+    // free it with lrge_hip_read_map_free).  open_mapped: open_selected that brings only the runs of the map that hold records sel
+    // (lrge_hip_reads_open_mapped), seek_stats filled; nullptr as open(), *rc_out (may be null) the call's code
+    static bool census_map(const std::string &path, int flags, int device, uint64_t out[4], lrge_hip_read_map **map, std::shared_ptr<detail::Ctx> ctx = nullptr) {
+        if (!ctx) ctx = std::make_shared<detail::Ctx>(device);
+        const int rc = lrge_hip_reads_census_map(ctx->h, path.c_str(), flags, out, map);
+        if (rc == LRGE_ERR_UNPROVEN || rc == LRGE_ERR_IO) return false;
+        ctx->check(rc);
+        return true;
+    }
+    static std::unique_ptr<DeviceReads> open_mapped(const std::string &path, int flags, const lrge_hip_read_map *map, const std::vector<uint32_t> &sel, int device = 0,
+                                                    std::shared_ptr<detail::Ctx> ctx = nullptr, int *rc_out = nullptr) {
+        auto r = std::make_unique<DeviceReads>();
+        r->ctx = ctx ? ctx : std::make_shared<detail::Ctx>(device);
+        const int rc = lrge_hip_reads_open_mapped(r->ctx->h, path.c_str(), flags, map, sel.data(), (uint32_t)sel.size(), &r->h);
+        if (rc_out) *rc_out = rc;
+        if (rc == LRGE_ERR_UNPROVEN || rc == LRGE_ERR_IO) return nullptr;
+        r->ctx->check(rc);
+        r->ctx->check(lrge_hip_reads_select_stats(r->h, r->select_stats));
+        r->ctx->check(lrge_hip_reads_seek_stats(r->h, r->seek_stats));
+        r->tables();
+        return r;
+    }
+    uint64_t seek_stats[4] = {0, 0, 0, 0};     // lrge_hip_reads_seek_stats: runs, text bytes brought, file bytes read, BGZF blocks decoded (open_mapped)
 private:
     void tables() {
         ctx->check(lrge_hip_reads_window_stats(h, window_stats));
@@ -149,17 +173,27 @@ struct SampledSource {
     std::shared_ptr<detail::Ctx> ctx;           // made by census(); the strategy runs in it
     uint64_t counts[4] = {0, 0, 0, 0};          // the census: records, sequence bases, text bytes, windows
     bool counted = false;
+    bool seek = false;                          // the census keeps a seek map, and open() brings only the runs that hold drawn reads
+    std::shared_ptr<lrge_hip_read_map> map;     // the census's, when `seek`
     // the count pass, once; false: the device does not prove this input -- take DeviceReads::open, then the host readers
     bool census() {
         if (counted) return true;
         if (!ctx) ctx = std::make_shared<detail::Ctx>(device);
-        return counted = DeviceReads::census(path, flags, device, counts, ctx);
+        if (!seek) return counted = DeviceReads::census(path, flags, device, counts, ctx);
+        lrge_hip_read_map *m = nullptr;
+        counted = DeviceReads::census_map(path, flags, device, counts, &m, ctx);
+        map.reset(m, lrge_hip_read_map_free);
+        return counted;
     }
     // the drawn ordinals (any order) opened in file order; the pass must see the census's records
     std::shared_ptr<DeviceReads> open(const std::vector<uint32_t> &idx, std::vector<uint32_t> *ascending) {
         *ascending = idx;
         std::sort(ascending->begin(), ascending->end());
-        std::shared_ptr<DeviceReads> r = DeviceReads::open_selected(path, flags, *ascending, device, ctx);
+        std::shared_ptr<DeviceReads> r;
+        int rc = LRGE_ERR_UNPROVEN;
+        if (seek && map) r = DeviceReads::open_mapped(path, flags, map.get(), *ascending, device, ctx, &rc);
+        // (a map that does not fit the input: the pass of the whole file decides; any other refusal stands)
+        if (!r && rc == LRGE_ERR_UNPROVEN) r = DeviceReads::open_selected(path, flags, *ascending, device, ctx);
         if (!r) throw LrgeError(LRGE_ERR_UNPROVEN, std::string("sampled ingest: ") + lrge_hip_last_error(ctx->h));
         if (r->select_stats[0] != counts[0])
             throw LrgeError(LRGE_ERR_IO, "IO error: the input changed between the count and the selection (" + std::to_string(counts[0]) + " records, then " + std::to_string(r->select_stats[0]) + ")");

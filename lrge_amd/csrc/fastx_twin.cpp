@@ -153,8 +153,9 @@ int parse(const uint8_t *t, uint64_t n, uint64_t tile, Win *w) {
 // ---- the windowed ingest: win_twin.h over the passes above ----
 struct Scan {
     uint64_t tile;
+    bool sniff = true;                  // false: the sub-text of a mapped run, whole records of a proven text (a run may start with a read named HD..)
     int scan(const std::vector<uint8_t> &blk, bool first, bool end, uint64_t *cut, int *fmt) {
-        Win w = {first, end, 0};
+        Win w = {first && sniff, end, 0};
         const int rc = parse(blk.data(), blk.size(), tile, &w);
         *cut = end ? blk.size() : w.cut;
         *fmt = g.fmt;
@@ -164,6 +165,8 @@ struct Scan {
     void append(const std::vector<uint8_t> &blk, uint64_t cut, const FxRec &r, std::vector<uint8_t> &store) const { append_seq(blk.data(), cut, r, store); }
 };
 WinTwinOut gw;
+FxSeekMap gm;                           // the map of the last fastx_twin_census_map
+FxSeekPlan gp;                          // the plan of the last fastx_twin_seek_plan / fastx_twin_mapped
 }  // namespace
 
 extern "C" {
@@ -217,6 +220,89 @@ int fastx_twin_selected(const uint8_t *t, uint64_t n, uint64_t tile, uint64_t wi
     if (tile < 16 || tile % 16 || !piece) return -1;
     Scan sc = {tile};
     return win_twin_run(sc, t, n, window, piece, true, gw, FX_KEEP_SEL, sel, k);
+}
+
+// The seek map and the mapped second pass (fx_seek.h).  fastx_twin_census_map: fastx_twin_census that also keeps
+// the map of the text (plain input: the file is the text), its points through the point rule the device uses, from the record table
+// of every window; the points by fastx_twin_map_points (returns how many there are).
+int fastx_twin_census_map(const uint8_t *t, uint64_t n, uint64_t tile, uint64_t window, uint64_t piece, uint64_t stride, uint64_t out[4]) {
+    gw = WinTwinOut(); gm = FxSeekMap();
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (tile < 16 || tile % 16 || !piece || !stride) return -1;
+    Scan sc = {tile};
+    FxSeekMap m;
+    m.stride = stride;
+    const int rc = win_twin_run(sc, t, n, window, piece, true, gw, FX_KEEP_NONE, nullptr, 0, &m);
+    if (rc) return rc;
+    out[0] = gw.sel.seen; out[1] = gw.sel.bases_seen; out[2] = n; out[3] = gw.st.windows;
+    m.records = gw.sel.seen; m.bases = gw.sel.bases_seen; m.text_bytes = m.file_len = n; m.windows = gw.st.windows; m.fmt = gw.fmt;
+    gm = m;
+    return 0;
+}
+
+uint64_t fastx_twin_map_points(uint64_t *ord, uint64_t *off, uint64_t cap) {
+    for (uint64_t i = 0; i < gm.pts.size() && i < cap; ++i) { ord[i] = gm.pts[i].ord; off[i] = gm.pts[i].off; }
+    return gm.pts.size();
+}
+
+// the selection against the map: 0, or WIN_TWIN_INVALID for one that is not ascending or reaches the map's records
+static int sel_fits(const uint32_t *sel, uint64_t k) {
+    if ((k && !sel) || !fx_sel_ascending(sel, k)) return WIN_TWIN_INVALID;
+    for (uint64_t j = 0; j < k; ++j) if (sel[j] >= gm.records) return WIN_TWIN_INVALID;
+    return 0;
+}
+
+// The plan of selection sel[0, k) on the last map.  n_blk == 0: for the plain text.  Else for the same text in BGZF blocks of member
+// lengths c_len and text sizes isize (a file of file_len bytes): the block fields are attached as the device attaches them.
+// out = {runs, text bytes brought, file bytes read, blocks decoded}; the runs by fastx_twin_plan_runs (ord0, n_rec, t0, t1 each; returns
+// how many there are), the renumbered selection by fastx_twin_plan_sel
+int fastx_twin_seek_plan(const uint32_t *c_len, const uint32_t *isize, uint64_t n_blk, uint64_t file_len, const uint32_t *sel, uint64_t k, uint64_t out[4]) {
+    gp = FxSeekPlan();
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (sel_fits(sel, k)) return WIN_TWIN_INVALID;
+    FxSeekMap m = gm;
+    if (n_blk) {
+        std::vector<BgzfBlock> t(n_blk);
+        uint64_t c = 0, o = 0;
+        for (uint64_t i = 0; i < n_blk; ++i) { t[i] = BgzfBlock{c, o, 0, 0, c_len[i], isize[i], 0}; c += c_len[i]; o += isize[i]; }
+        if (o != m.text_bytes || c != file_len) return WIN_TWIN_INVALID;
+        m.kind = FX_SEEK_BGZF; m.n_blocks = n_blk; m.file_len = file_len;
+        fx_seek_attach(m, t.data(), n_blk);
+    }
+    fx_seek_plan(m, sel, k, &gp);
+    out[0] = gp.runs.size(); out[1] = gp.text_bytes; out[2] = gp.file_bytes; out[3] = gp.blocks;
+    return 0;
+}
+
+uint64_t fastx_twin_plan_runs(uint64_t *out, uint64_t cap) {
+    for (uint64_t i = 0; i < gp.runs.size() && i < cap; ++i) { out[4 * i] = gp.runs[i].ord0; out[4 * i + 1] = gp.runs[i].n_rec; out[4 * i + 2] = gp.runs[i].t0; out[4 * i + 3] = gp.runs[i].t1; }
+    return gp.runs.size();
+}
+void fastx_twin_plan_sel(uint32_t *out) { if (!gp.sel.empty()) memcpy(out, gp.sel.data(), gp.sel.size() * 4); }
+
+// The mapped second pass over text t, which must be the text of the last map (WIN_TWIN_INVALID: another size): the plan, the
+// sub-text built from its runs, and the selecting run of fastx_twin_selected over the sub-text with the renumbered selection.
+// FX_UNPROVEN also when the sub-text does not hold the plan's records.  The result reads as fastx_twin_selected's: name_off is
+// translated back into the whole text, the select stats' seen / bases_seen are the map's
+int fastx_twin_mapped(const uint8_t *t, uint64_t n, uint64_t tile, uint64_t window, uint64_t piece, const uint32_t *sel, uint64_t k) {
+    gw = WinTwinOut(); gp = FxSeekPlan();
+    if (tile < 16 || tile % 16 || !piece) return -1;
+    if (n != gm.text_bytes || gm.kind != FX_SEEK_PLAIN || sel_fits(sel, k)) return WIN_TWIN_INVALID;
+    fx_seek_plan(gm, sel, k, &gp);
+    std::vector<uint8_t> sub;
+    for (const FxSeekRun &r : gp.runs) sub.insert(sub.end(), t + r.t0, t + r.t1);
+    Scan sc = {tile, false};
+    int rc = win_twin_run(sc, sub.data(), sub.size(), window, piece, true, gw, FX_KEEP_SEL, gp.sel.data(), k);
+    if (rc == WIN_TWIN_INVALID || (!rc && gw.sel.seen != gp.records)) rc = (int)FX_UNPROVEN;        // the map does not fit the input
+    if (rc) { gw = WinTwinOut(); return rc; }
+    size_t ri = 0;
+    uint64_t before = 0;                // sub-text bytes in front of run ri
+    for (FxRec &r : gw.recs) {
+        while (r.name_off >= before + (gp.runs[ri].t1 - gp.runs[ri].t0)) { before += gp.runs[ri].t1 - gp.runs[ri].t0; ++ri; }
+        r.name_off = r.name_off - before + gp.runs[ri].t0;
+    }
+    gw.sel.seen = gm.records; gw.sel.bases_seen = gm.bases;
+    return 0;
 }
 
 void fastx_twin_select_stats(uint64_t out[4]) { gw.select_stats(out); }

@@ -1,0 +1,108 @@
+// fx_seek.h -- the seek map of a FASTA / FASTQ text and the plan of a pass that brings only the chosen runs,
+// shared by the device (host_fastx.inl; hipcc) and the host twin (fastx_twin.cpp; g++), as fx_window.h is.
+//
+// The census that proves the text (fx_window.h FX_KEEP_NONE) can leave a map behind.  The whole text is cut into cells of
+// `stride` bytes; a cell in which at least one record starts gets one point: the first record that starts in it.  A record starts
+// at the first byte of its header line, the '>' or '@' (FxRec::name_off - 1).  A point holds the record's ordinal (file order,
+// 0-based), its text offset and, for BGZF, the block that holds that offset.  Cells inside one long record have no point; the
+// points ascend strictly in ordinal and in offset, and the first point is record 0.
+//
+// The plan of a selection (strictly ascending ordinals): for each chosen ordinal the run from the last point at or below it to
+// the first point above it, or to the end of the text; runs that touch or overlap are merged.  The sub-text -- the runs'
+// bytes, concatenated -- is a text of whole records (a run starts at a header line and ends directly behind a line feed or at the
+// end of the text), and the selection renumbered into its ordinals names the same records.
+#pragma once
+#include <stdint.h>
+
+#include <vector>
+
+#include "bgzf_scan.h"
+#include "fx_window.h"
+
+enum { FX_SEEK_PLAIN = 0, FX_SEEK_BGZF = 1, FX_SEEK_OTHER = 2 };    // OTHER: a container that cannot be entered (gzip, bzip2, xz)
+#define FX_SEEK_NONE 0xFFFFFFFFu                                     // a cell's slot without a record start
+
+// blk: the index of the block that holds text offset `off` (o_off <= off < o_off + ISIZE), c_off / o_off / c_len its file offset,
+// text offset and member length; plain input: all 0
+struct FxSeekPoint { uint64_t ord, off, c_off, o_off; uint32_t c_len; uint32_t blk; };
+
+struct FxSeekMap {
+    uint64_t records = 0, bases = 0, text_bytes = 0, file_len = 0, n_blocks = 0, stride = 65536, windows = 0;
+    int kind = FX_SEEK_PLAIN, fmt = FX_FMT_EMPTY;
+    std::vector<FxSeekPoint> pts;
+    uint64_t last_cell = 0;                      // the cell of the last point (the builder's)
+};
+
+// the point rule: record `ord` starts at text offset `off`; records arrive in file order.  A window's first cell may be one an
+// earlier window gave a point to: the earlier point stands
+static inline void fx_seek_add(FxSeekMap &m, uint64_t ord, uint64_t off) {
+    const uint64_t cell = off / m.stride;
+    if (!m.pts.empty() && cell == m.last_cell) return;
+    m.pts.push_back(FxSeekPoint{ord, off, 0, 0, 0, 0});
+    m.last_cell = cell;
+}
+
+// the block fields of every point from the block table of the file the census read
+static inline void fx_seek_attach(FxSeekMap &m, const BgzfBlock *t, uint64_t n) {
+    uint64_t b = 0;
+    for (FxSeekPoint &p : m.pts) {
+        while (b < n && t[b].o_off + t[b].isize <= p.off) ++b;
+        if (b == n) return;                      // (never: a point lies inside the text)
+        p.c_off = t[b].c_off; p.o_off = t[b].o_off; p.c_len = t[b].c_len; p.blk = (uint32_t)b;
+    }
+}
+
+// one run: records [ord0, ord0 + n_rec), text [t0, t1).  BGZF: blocks [b0, b1), which are file bytes [f0, f1), the first of them
+// starting at text offset o0; plain: f0 = t0, f1 = t1, no blocks
+struct FxSeekRun { uint64_t ord0, n_rec, t0, t1, f0, f1, b0, b1, o0; };
+
+struct FxSeekPlan {
+    std::vector<FxSeekRun> runs;
+    std::vector<uint32_t> sel;                   // the selection in ordinals of the sub-text
+    uint64_t records = 0, text_bytes = 0, file_bytes = 0, blocks = 0;      // of the sub-text; a block or file byte shared by two runs counts once
+};
+
+// sel[0, k): strictly ascending, every ordinal below m.records (the caller has checked both)
+static inline void fx_seek_plan(const FxSeekMap &m, const uint32_t *sel, uint64_t k, FxSeekPlan *p) {
+    *p = FxSeekPlan();
+    p->sel.resize((size_t)k);
+    const uint64_t np = m.pts.size();
+    std::vector<uint64_t> first, behind;         // a run as points [first, behind); behind == np: to the end of the text
+    uint64_t i = 0;
+    for (uint64_t j = 0; j < k; ++j) {
+        while (i + 1 < np && m.pts[i + 1].ord <= sel[j]) ++i;       // the last point at or below the ordinal
+        if (!first.empty() && i <= behind.back()) { if (i == behind.back()) ++behind.back(); }      // touches or lies inside: merged
+        else { first.push_back(i); behind.push_back(i + 1); }
+    }
+    // the runs' fields, and the renumbering (the selection is ascending: one sweep)
+    uint64_t at = 0, prev_b1 = 0, prev_f1 = 0;
+    for (size_t r = 0; r < first.size(); ++r) {
+        const FxSeekPoint &a = m.pts[first[r]];
+        const bool to_end = behind[r] >= np;
+        FxSeekRun run;
+        run.ord0 = a.ord; run.t0 = a.off;
+        run.n_rec = (to_end ? m.records : m.pts[behind[r]].ord) - a.ord;
+        run.t1 = to_end ? m.text_bytes : m.pts[behind[r]].off;
+        if (m.kind == FX_SEEK_BGZF) {
+            run.b0 = a.blk; run.f0 = a.c_off; run.o0 = a.o_off;
+            if (to_end) { run.b1 = m.n_blocks; run.f1 = m.file_len; }
+            else {
+                const FxSeekPoint &z = m.pts[behind[r]];
+                const bool whole = z.off == z.o_off;                // the run ends where z's block starts: that block is not the run's
+                run.b1 = whole ? z.blk : (uint64_t)z.blk + 1;
+                run.f1 = whole ? z.c_off : z.c_off + z.c_len;
+            }
+            const uint64_t b_from = r && prev_b1 > run.b0 ? prev_b1 : run.b0, f_from = r && prev_f1 > run.f0 ? prev_f1 : run.f0;
+            p->blocks += run.b1 > b_from ? run.b1 - b_from : 0;
+            p->file_bytes += run.f1 > f_from ? run.f1 - f_from : 0;
+            prev_b1 = run.b1; prev_f1 = run.f1;
+        } else {
+            run.b0 = run.b1 = 0; run.f0 = run.t0; run.f1 = run.t1; run.o0 = 0;
+            p->file_bytes += run.t1 - run.t0;
+        }
+        p->runs.push_back(run);
+        p->text_bytes += run.t1 - run.t0;
+        for (; at < k && (uint64_t)sel[at] < run.ord0 + run.n_rec; ++at) p->sel[(size_t)at] = (uint32_t)(p->records + (sel[at] - run.ord0));
+        p->records += run.n_rec;
+    }
+}

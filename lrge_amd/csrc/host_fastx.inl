@@ -8,12 +8,19 @@
 // LRGE_GPU_INGEST_WINDOWED FASTA / FASTQ text larger than option INGEST_WINDOW_BYTES passes through HBM in windows and only the
 // bases stay (fx_window.h); with LRGE_GPU_INGEST_WINDOWED_ALN beside it so does unaligned BAM and SAM, BAM's
 // bases staying packed.  lrge_hip_reads_census* and lrge_hip_reads_open_selected* pass FASTA / FASTQ text through
-// the same windows and keep nothing, or only the records of a list of ordinals (FxKeepMode).  Included into lrge_hip.hip.
+// the same windows and keep nothing, or only the records of a list of ordinals (FxKeepMode); lrge_hip_reads_census_map*
+// leaves a seek map behind, with which lrge_hip_reads_open_mapped* brings only the runs of plain or BGZF input that hold chosen records
+// (fx_seek.h, fx_src_seek_raw, fx_src_seek_bgzf).  Included into lrge_hip.hip.
 // A call (lrge_hip_reads_open_mem) is one source (fx_src_raw, _bgzf, _gzip, _bzip2), which brings the text to the sink (FxSink) resident
 // or through the windows of the sink's FxWinRun, and one record scan (fx_parse_kind), chosen by the sniff (fx_kind).
 
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
 #include "dev_keep.h"
 #include "fx_window.h"
+#include "fx_seek.h"
 #include "cram_round.h"
 
 struct lrge_hip_reads {
@@ -31,7 +38,11 @@ struct lrge_hip_reads {
     bool is_cram = false;                       // opened from unaligned CRAM (host_cram.inl): d_text is a base store, as a windowed FASTA handle's
     CramStats cram;                             // lrge_hip_reads_cram_stats
     FxSelStats sel = {0, 0, 0, 0};              // lrge_hip_reads_select_stats: the pass of lrge_hip_reads_open_selected* (a window: what it adds)
+    u64 seek[4] = {0, 0, 0, 0};                 // lrge_hip_reads_seek_stats: runs, text bytes brought, file bytes read, BGZF blocks decoded (lrge_hip_reads_open_mapped*)
 };
+
+// the seek map of a census (fx_seek.h), as the caller holds it
+struct lrge_hip_read_map { FxSeekMap m; };
 
 static double fx_now_ms() { return DevPool::now_ms(); }
 
@@ -145,6 +156,9 @@ struct FxWinDev {
     const u32 *sel = nullptr;
     u32 *d_sel = nullptr;
     u64 k = 0, at = 0;
+    FxSeekMap *map = nullptr;                   // a census that was asked for a seek map (fx_seek.h): seek_window adds every window's points
+    bool mapped = false;                        // the text is the sub-text of a mapped open: whole records of a text the census proved, never sniffed
+    bool scan_refused = false;                  // a window was not proven by the record scan or the driver (not: the budget) -- what a mapped open reports as a map that does not fit
     FxWinDev(lrge_hip_ctx *c, lrge_hip_reads *r, int f, u64 cap_) : ctx(c), R(r), flags(f), cap(cap_), store(c) {
         store.keep_on = true; store.keep_slack = FX_PAD; store.keep_floor = 0;      // (block and store share one budget: neither takes more than it needs or doubles to)
         R->name_off.assign(1, 0);
@@ -160,9 +174,10 @@ struct FxWinDev {
         return LRGE_OK;
     }
     u64 len() const { return blk->keep_len; }
-    int unproven(const char *what) { LRGE_SET_ERR(ctx, "reads_open: not proven on the device (%s)", what); return LRGE_ERR_UNPROVEN; }
+    int unproven(const char *what) { scan_refused = true; LRGE_SET_ERR(ctx, "reads_open: not proven on the device (%s)", what); return LRGE_ERR_UNPROVEN; }
     // the census and the selected open take FASTA / FASTQ, whatever flags came with the call: the sniff of the text's first bytes
     int selected_format() {
+        if (mapped) return LRGE_OK;             // (a run may start with a read named HD.., SQ.. or RG..: fx_win_census)
         u8 head[4] = {0, 0, 0, 0};
         const u64 n = blk->keep_len;
         if (n) { HIPCHK(ctx, hipMemcpyAsync(head, blk->keep, (size_t)std::min<u64>(4, n), hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); }
@@ -186,11 +201,12 @@ struct FxWinDev {
     int flush(bool first, bool end, u64 *cut, int *fmt) {
         lrge_hip_reads W;                       // the window as a text of its own; the block stays the decoder's
         W.ctx = ctx; W.d_text = blk->keep; W.n_text = blk->keep_len;
-        FxWinScan w = {this, first, end, 0};
+        FxWinScan w = {this, first && !mapped, end, 0};
         const double t0 = fx_now_ms();
         const int prc = fx_parse_kind(ctx, &W, kind, &w);
         ctx->pool.release(W.d_recs);
         ms_names += W.ms[2]; ms_scan += fx_now_ms() - t0 - W.ms[2];
+        if (prc == LRGE_ERR_UNPROVEN && !store.keep_over) scan_refused = true;      // (the scan's verdict; the store's budget is the other refusal a window has)
         if (prc) return prc;
         *cut = end ? W.n_text : w.cut; *fmt = W.fmt;
         if (*cut) { u64 *sum = &R->bam.segments; const u64 *add = &W.bam.segments; for (int i = 0; i < 6; ++i) sum[i] += add[i]; }
@@ -221,6 +237,23 @@ struct FxWinDev {
             return LRGE_ERR_DEVICE;
         }
         blk->keep_max = cap > store.keep_cap ? cap - store.keep_cap : 0;
+        return LRGE_OK;
+    }
+    // A window of a census that leaves a seek map, behind k_fx_records: k_fx_seek finds the first record start of every cell of the
+    // window's prefix [0, n_use), the slots (record index and window offset, 8 bytes a cell) come down in one copy, and the point
+    // rule of fx_seek.h takes those that hold a record.  The window's records are R->sel.seen onwards, its bytes `through` onwards
+    int seek_window(Scratch &sc, const lrge_hip_reads *W, u64 n_rec, u64 n_use) {
+        if (!n_rec) return LRGE_OK;
+        const u64 S = map->stride, cell0 = through / S, n_cells = (through + n_use - 1) / S - cell0 + 1;
+        ALLOC_OR_FAIL(d_slot, sc, u32, 2 * n_cells);
+        HIPCHK(ctx, hipMemsetAsync(d_slot, 0xFF, (size_t)n_cells * 8, ctx->stream));
+        hipLaunchKernelGGL(k_fx_seek, dim3((u32)div_up(n_rec, FX_THREADS)), dim3(FX_THREADS), 0, ctx->stream, (const FxRec *)W->d_recs, n_rec, through, S, cell0, n_cells, d_slot);
+        KCHK(ctx);
+        std::vector<u32> slot((size_t)n_cells * 2);
+        HIPCHK(ctx, hipMemcpyAsync(slot.data(), d_slot, (size_t)n_cells * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        for (u64 c = 0; c < n_cells; ++c)
+            if (slot[c] != FX_SEEK_NONE) fx_seek_add(*map, R->sel.seen + slot[c], through + slot[n_cells + c]);
         return LRGE_OK;
     }
     // A window of a run that does not keep all (FX_KEEP_NONE, FX_KEEP_SEL), behind k_fx_records: W.d_recs and the lengths of its
@@ -469,6 +502,7 @@ static int fx_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R, FxWinScan *w) {
         hipLaunchKernelGGL(k_fx_bases, dim3(std::min<u32>(rec_blocks, (u32)ctx->n_cu * 8)), dim3(FX_THREADS), 0, st, (const u32 *)d_seq_len, n_rec, (unsigned long long *)(d_flags + 2));
         KCHK(ctx);
         if ((rc = fx_flags_back(ctx, d_flags, "a record outside the strict form", &name_bytes, &bases))) return rc;
+        if (w->dev->map && (rc = w->dev->seek_window(sc, R, n_rec, n_use))) return rc;
         return w->dev->keep_window(sc, R, d_seq_len, d_name_len, n_rec, n_use, bases);
     }
     if ((rc = fx_flags_back(ctx, d_flags, "a record outside the strict form", &name_bytes))) return rc;
@@ -715,7 +749,8 @@ extern "C" void lrge_hip_reads_free(lrge_hip_reads *r) {
 }
 
 // one call: lrge_hip_reads_open_mem (FX_KEEP_ALL), the census (FX_KEEP_NONE) or the selected open (FX_KEEP_SEL with sel[0, k))
-static int fx_open_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, int flags, FxKeepMode mode, const u32 *sel, u64 k, lrge_hip_reads **out) {
+// map: a census (FX_KEEP_NONE) that leaves the seek map of the text behind (fx_seek.h)
+static int fx_open_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, int flags, FxKeepMode mode, const u32 *sel, u64 k, lrge_hip_reads **out, FxSeekMap *map = nullptr) {
     if (!ctx || !out || (!file_bytes && len)) return LRGE_ERR_INVALID;
     *out = nullptr;
     if (mode == FX_KEEP_SEL && ((k && !sel) || !fx_sel_ascending(sel, k))) { ctx->err = "reads_open_selected: the ordinals are not strictly ascending"; return LRGE_ERR_INVALID; }
@@ -742,10 +777,20 @@ static int fx_open_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, 
     uint64_t total = 0;
     int rc;
     if (mode != FX_KEEP_ALL && (rc = s.run->dev.select(mode, sel, k))) return rc;
+    if (map) {
+        *map = FxSeekMap();
+        map->stride = std::max<u64>(1, ctx->opt_u64("INGEST_SEEK_STRIDE_BYTES", 65536));
+        map->kind = FX_SEEK_OTHER; map->file_len = len;
+        s.run->dev.map = map;
+    }
     if (mode != FX_KEEP_ALL && b(0) == 0x28 && b(1) == 0xb5 && b(2) == 0x2f && b(3) == 0xfd && (flags & LRGE_GPU_INFLATE_ZSTD)) {
         ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only, not Zstandard input";       // (its text is never windowed)
         rc = LRGE_ERR_UNPROVEN;
-    } else if (b(0) == 0x1f && b(1) == 0x8b) rc = bgzf_scan_blocks(d, len, &t, &total) ? fx_src_bgzf(s, d, t, total) : fx_src_gzip(s, d, len);
+    } else if (b(0) == 0x1f && b(1) == 0x8b) {
+        const bool bgzf = bgzf_scan_blocks(d, len, &t, &total);
+        if (map && bgzf) { map->kind = FX_SEEK_BGZF; map->n_blocks = t.size(); }
+        rc = bgzf ? fx_src_bgzf(s, d, t, total) : fx_src_gzip(s, d, len);
+    }
     else if (b(0) == 0x42 && b(1) == 0x5a && (flags & LRGE_GPU_INFLATE_BZIP2)) rc = fx_src_bzip2(s, d, len);
     else if (b(0) == 0x28 && b(1) == 0xb5 && b(2) == 0x2f && b(3) == 0xfd && (flags & LRGE_GPU_INFLATE_ZSTD)) rc = fx_src_zstd(s, d, len);
     else if (b(0) == 0xfd && b(1) == 0x37 && b(2) == 0x7a && b(3) == 0x58 && b(4) == 0x5a && b(5) == 0x00 && (flags & LRGE_GPU_INFLATE_XZ)) rc = fx_src_xz(s, d, len);
@@ -753,9 +798,14 @@ static int fx_open_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, 
              (b(0) == 0xfd && b(1) == 0x37 && b(2) == 0x7a && b(3) == 0x58 && b(4) == 0x5a)) {
         ctx->err = "reads_open: bzip2, zstd and xz input is decompressed on the host";
         rc = LRGE_ERR_UNPROVEN;
-    } else rc = fx_src_raw(s, d, len);
+    } else { if (map) map->kind = FX_SEEK_PLAIN; rc = fx_src_raw(s, d, len); }
     if (rc) return rc;
     if ((rc = s.run && (s.run->win.st.windows || mode != FX_KEEP_ALL) ? fx_finish_windowed(s, t0) : fx_finish_resident(s, t0))) return rc;
+    if (map) {
+        map->records = guard->sel.seen; map->bases = guard->sel.bases_seen; map->text_bytes = guard->text_bytes; map->windows = guard->win.windows;
+        map->fmt = guard->fmt;
+        if (map->kind == FX_SEEK_BGZF) fx_seek_attach(*map, t.data(), t.size());
+    }
     *out = guard.release();
     return LRGE_OK;
 }
@@ -804,6 +854,275 @@ extern "C" int lrge_hip_reads_select_stats(const lrge_hip_reads *r, uint64_t out
     if (!r || !out) return LRGE_ERR_INVALID;
     out[0] = r->sel.seen; out[1] = r->sel.kept; out[2] = r->sel.bases_seen; out[3] = r->sel.bases_kept;
     return LRGE_OK;
+}
+
+// ---- the seek map and the mapped second pass (fx_seek.h) ----
+extern "C" int lrge_hip_reads_census_map_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, int flags, uint64_t out[4], lrge_hip_read_map **map) {
+    if (!ctx || !out || !map) return LRGE_ERR_INVALID;
+    *map = nullptr;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    std::unique_ptr<lrge_hip_read_map> m(new lrge_hip_read_map());
+    lrge_hip_reads *r = nullptr;
+    const int rc = fx_open_mem(ctx, file_bytes, len, flags, FX_KEEP_NONE, nullptr, 0, &r, &m->m);
+    if (rc) return rc;
+    out[0] = r->sel.seen; out[1] = r->sel.bases_seen; out[2] = r->text_bytes; out[3] = r->win.windows;
+    lrge_hip_reads_free(r);
+    *map = m.release();
+    return LRGE_OK;
+}
+
+extern "C" int lrge_hip_reads_census_map(lrge_hip_ctx *ctx, const char *path, int flags, uint64_t out[4], lrge_hip_read_map **map) {
+    if (!ctx || !path || !out || !map) return LRGE_ERR_INVALID;
+    *map = nullptr;
+    std::string raw;
+    const int rc = fx_slurp(ctx, path, &raw);
+    return rc ? rc : lrge_hip_reads_census_map_mem(ctx, raw.data(), raw.size(), flags, out, map);
+}
+
+extern "C" void lrge_hip_read_map_free(lrge_hip_read_map *map) { delete map; }
+
+extern "C" int lrge_hip_read_map_stats(const lrge_hip_read_map *map, uint64_t out[4]) {
+    if (!map || !out) return LRGE_ERR_INVALID;
+    out[0] = map->m.records; out[1] = map->m.pts.size(); out[2] = map->m.stride; out[3] = map->m.text_bytes;
+    return LRGE_OK;
+}
+
+extern "C" int lrge_hip_read_map_points(const lrge_hip_read_map *map, uint64_t *ord, uint64_t *text_off, uint64_t *c_off, uint64_t cap) {
+    if (!map) return LRGE_ERR_INVALID;
+    for (u64 i = 0; i < map->m.pts.size() && i < cap; ++i) {
+        if (ord) ord[i] = map->m.pts[i].ord;
+        if (text_off) text_off[i] = map->m.pts[i].off;
+        if (c_off) c_off[i] = map->m.pts[i].c_off;
+    }
+    return LRGE_OK;
+}
+
+extern "C" int lrge_hip_reads_seek_stats(const lrge_hip_reads *r, uint64_t out[4]) {
+    if (!r || !out) return LRGE_ERR_INVALID;
+    memcpy(out, r->seek, sizeof r->seek);
+    return LRGE_OK;
+}
+
+// the file of a mapped open: the whole buffer, or a descriptor that is read by range
+struct FxInput {
+    const u8 *d = nullptr;
+    u64 len = 0;
+    int fd = -1;
+    const char *path = nullptr;
+    ~FxInput() { if (fd >= 0) close(fd); }
+    bool read(u64 off, u64 n, u8 *dst) const {
+        if (off > len || n > len - off) return false;
+        if (d) { if (n) memcpy(dst, d + off, (size_t)n); return true; }
+        for (u64 got = 0; got < n;) {
+            const ssize_t k = pread(fd, dst + got, (size_t)(n - got), (off_t)(off + got));
+            if (k <= 0) return false;
+            got += (u64)k;
+        }
+        return true;
+    }
+};
+struct FxPinned {
+    u8 *p = nullptr;
+    ~FxPinned() { if (p) (void)hipHostFree(p); }
+};
+static int fx_read_failed(lrge_hip_ctx *ctx) { ctx->err = "reads_open_mapped: the file could not be read"; return LRGE_ERR_IO; }
+static int fx_map_misfit(lrge_hip_ctx *ctx, const char *what) { LRGE_SET_ERR(ctx, "reads_open_mapped: the map does not fit the input (%s)", what); return LRGE_ERR_UNPROVEN; }
+static int fx_map_range(lrge_hip_ctx *ctx) { ctx->err = "reads_open_mapped: a file range does not hold the blocks of the map"; return LRGE_ERR_INVALID; }
+
+// plain input: the runs' bytes gathered into pinned staging, one copy per window's worth of sub-text
+static int fx_src_seek_raw(FxSink &s, const FxInput &in, const FxSeekPlan &plan) {
+    lrge_hip_ctx *ctx = s.ctx;
+    const u64 piece = std::min<u64>(s.window, plan.text_bytes);
+    int rc;
+    FxPinned stage;
+    if (piece) HIPCHK(ctx, hipHostMalloc((void **)&stage.p, (size_t)piece, hipHostMallocDefault));
+    u64 fill = 0;
+    const auto send = [&]() -> int {
+        if ((rc = s.room(fill))) return rc;
+        HIPCHK(ctx, hipMemcpyAsync(s.blk.keep + s.blk.keep_len, stage.p, (size_t)fill, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));            // (the staging is filled again)
+        s.blk.keep_len += fill; fill = 0;
+        return s.appended();
+    };
+    for (const FxSeekRun &r : plan.runs)
+        for (u64 at = r.t0; at < r.t1;) {
+            const u64 m = std::min<u64>(piece - fill, r.t1 - at);
+            if (!in.read(at, m, stage.p + fill)) return fx_read_failed(ctx);
+            fill += m; at += m;
+            if (fill == piece && (rc = send())) return rc;
+        }
+    if (fill && (rc = send())) return rc;
+    s.hand_over(s.blk);
+    return LRGE_OK;
+}
+
+// BGZF: only the blocks some run touches are decoded, each once, in batches of about a window into a staging block; k_fx_runs
+// copies the parts of the runs that lie in a batch to the tail of the sink's block.  The file ranges of the plan are read (or, from
+// a buffer, copied) back to back into `comp`, which the chunk pipeline takes as a file of its own -- a chunk's blocks must be
+// contiguous --, and scanned: every range must hold the blocks the map says
+static int fx_src_seek_bgzf(FxSink &s, const FxInput &in, const FxSeekPlan &plan) {
+    lrge_hip_ctx *ctx = s.ctx;
+    if (!(s.flags & LRGE_GPU_INFLATE_BGZF)) { ctx->err = "reads_open: BGZF input without LRGE_GPU_INFLATE_BGZF"; return LRGE_ERR_UNPROVEN; }
+    std::vector<BgzfBlock> fb;                  // the blocks of the runs, once each: c_off in `comp`, o_off in the whole text
+    std::vector<u8> comp;
+    u64 prev_b1 = 0, prev_f1 = 0;
+    for (const FxSeekRun &r : plan.runs) {
+        const bool joins = !fb.empty() && prev_b1 > r.b0;          // the run starts in a block the run before ended in
+        const u64 b_from = joins ? prev_b1 : r.b0;
+        if (b_from < r.b1) {
+            const u64 f_from = joins ? prev_f1 : r.f0, o_from = joins ? fb.back().o_off + fb.back().isize : r.o0, at = comp.size();
+            if (r.f1 <= f_from || r.f1 > in.len) return fx_map_range(ctx);
+            comp.resize((size_t)(at + (r.f1 - f_from)));
+            if (!in.read(f_from, r.f1 - f_from, comp.data() + at)) return fx_read_failed(ctx);
+            std::vector<BgzfBlock> part;
+            u64 total = 0;
+            if (!bgzf_scan_blocks(comp.data() + at, r.f1 - f_from, &part, &total) || part.size() != r.b1 - b_from) return fx_map_range(ctx);
+            for (BgzfBlock &b : part) { b.c_off += at; b.o_off += o_from; fb.push_back(b); }
+        }
+        if (fb.empty() || r.t0 < r.o0 || r.t1 > fb.back().o_off + fb.back().isize) return fx_map_range(ctx);
+        prev_b1 = r.b1; prev_f1 = r.f1;
+    }
+    const u8 *base = comp.data();
+    // batches of blocks of a window's size, as fx_src_bgzf makes them; the staging holds the largest
+    u64 stage_cap = 0;
+    for (size_t i = 0, j; i < fb.size(); i = j) {
+        u64 bytes = 0;
+        for (j = i; j < fb.size() && (j == i || bytes < s.window); ++j) bytes += fb[j].isize;
+        stage_cap = std::max(stage_cap, bytes);
+    }
+    Scratch sc(ctx);
+    ALLOC_OR_FAIL(d_stage, sc, u8, stage_cap + FX_PAD);
+    int rc;
+    size_t ri = 0;
+    u64 rpos = plan.runs.empty() ? 0 : plan.runs[0].t0;            // the next text byte of run ri to bring
+    for (size_t i = 0, j; i < fb.size(); i = j) {
+        std::vector<BgzfBlock> part;
+        u64 bytes = 0;
+        for (j = i; j < fb.size() && (j == i || bytes < s.window); ++j) {
+            part.push_back(fb[j]);
+            part.back().o_off = bytes;
+            bytes += fb[j].isize;
+        }
+        if ((rc = fx_bgzf_decode(ctx, base, part, d_stage))) return rc;
+        // what the runs take of these blocks, in order: the sub-text's next bytes
+        std::vector<FxRunCopy> copies;
+        u64 sum = 0;
+        for (size_t b = i; b < j && ri < plan.runs.size();) {
+            const FxSeekRun &r = plan.runs[ri];
+            const u64 bo = fb[b].o_off, be = bo + fb[b].isize;
+            if (rpos >= r.t1) { if (++ri < plan.runs.size()) rpos = plan.runs[ri].t0; continue; }
+            if (rpos >= be) { ++b; continue; }
+            if (rpos < bo) return fx_map_range(ctx);               // (never: the blocks cover the runs)
+            const u64 m = std::min<u64>(r.t1, be) - rpos, src = part[b - i].o_off + (rpos - bo);
+            if (src + m > bytes) return fx_map_range(ctx);         // (never)
+            if (!copies.empty() && copies.back().src + copies.back().len == src) copies.back().len += m;
+            else copies.push_back(FxRunCopy{src, sum, m});
+            sum += m; rpos += m;
+        }
+        if (!sum) continue;
+        if (sum >> 32) return s.run->dev.unproven("a window of 2^32 bytes or more");     // (the driver refuses such a block anyway; the grid below is a tile a wavefront)
+        if ((rc = s.room(sum))) return rc;
+        Scratch tables(ctx);                                       // (the batch's: released before the next)
+        std::vector<u64> first(copies.size() + 1, 0);
+        for (size_t c = 0; c < copies.size(); ++c) first[c + 1] = first[c] + div_up(copies[c].len, (u64)FX_RUN_TILE);
+        ALLOC_OR_FAIL(d_copies, tables, FxRunCopy, copies.size());
+        ALLOC_OR_FAIL(d_first, tables, u64, first.size());
+        HIPCHK(ctx, hipMemcpyAsync(d_copies, copies.data(), copies.size() * sizeof(FxRunCopy), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(d_first, first.data(), first.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(k_fx_runs, dim3((u32)first.back()), dim3(64), 0, ctx->stream, (const u8 *)d_stage, s.blk.keep + s.blk.keep_len,
+                           (const FxRunCopy *)d_copies, (const u64 *)d_first, (u32)copies.size());
+        KCHK(ctx);
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));            // (the tables are pageable, and the staging is decoded into again)
+        s.blk.keep_len += sum;
+        if ((rc = s.appended())) return rc;
+    }
+    while (ri < plan.runs.size() && rpos >= plan.runs[ri].t1) if (++ri < plan.runs.size()) rpos = plan.runs[ri].t0;
+    if (ri < plan.runs.size()) return fx_map_range(ctx);
+    s.hand_over(s.blk);
+    return LRGE_OK;
+}
+
+// One mapped open.  Everything that can be refused is refused before any device work: a selection that is not ascending, a map of
+// another input, an ordinal at or above the map's records
+static int fx_open_mapped(lrge_hip_ctx *ctx, FxInput &in, int flags, const lrge_hip_read_map *map, const u32 *sel, u64 k, lrge_hip_reads **out) {
+    *out = nullptr;
+    if ((k && !sel) || !fx_sel_ascending(sel, k)) { ctx->err = "reads_open_selected: the ordinals are not strictly ascending"; return LRGE_ERR_INVALID; }
+    const FxSeekMap &m = map->m;
+    u8 h[6] = {0, 0, 0, 0, 0, 0};
+    const u64 nh = std::min<u64>(6, in.len);
+    if (!in.read(0, nh, h)) return fx_read_failed(ctx);
+    const auto b = [&](u64 i) -> u32 { return i < nh ? h[i] : 0x100u; };
+    // what the census and the selected open refuse by name, whatever the map
+    if (b(0) == 'C' && b(1) == 'R' && b(2) == 'A' && b(3) == 'M') { ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only"; return LRGE_ERR_UNPROVEN; }
+    if (b(0) == 0x28 && b(1) == 0xb5 && b(2) == 0x2f && b(3) == 0xfd && (flags & LRGE_GPU_INFLATE_ZSTD)) {
+        ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only, not Zstandard input";
+        return LRGE_ERR_UNPROVEN;
+    }
+    const bool gz = b(0) == 0x1f && b(1) == 0x8b, packed = gz || (b(0) == 0x42 && b(1) == 0x5a) || (b(0) == 0x28 && b(1) == 0xb5 && b(2) == 0x2f && b(3) == 0xfd) ||
+                                                   (b(0) == 0xfd && b(1) == 0x37 && b(2) == 0x7a && b(3) == 0x58 && b(4) == 0x5a);
+    std::vector<BgzfBlock> t;
+    u64 total = 0;
+    bool fits = m.file_len == in.len && (m.kind == FX_SEEK_PLAIN ? !packed && m.text_bytes == in.len : m.kind == FX_SEEK_BGZF ? gz : packed);
+    if (fits && in.d && gz) {                   // the whole buffer is here: its block table says which kind it is
+        const bool bgzf = bgzf_scan_blocks(in.d, in.len, &t, &total);
+        fits = bgzf == (m.kind == FX_SEEK_BGZF) && (!bgzf || (t.size() == m.n_blocks && total == m.text_bytes));
+    }
+    if (!fits) { ctx->err = "reads_open_mapped: the map is of another input"; return LRGE_ERR_INVALID; }
+    for (u64 j = 0; j < k; ++j)
+        if (sel[j] >= m.records) { LRGE_SET_ERR(ctx, "reads_open_selected: ordinal %u of %llu records", sel[j], (unsigned long long)m.records); return LRGE_ERR_INVALID; }
+    if (m.kind == FX_SEEK_OTHER) {              // a container that cannot be entered: the full selected pass, the same handle
+        std::string raw;
+        int rc;
+        if (!in.d && (rc = fx_slurp(ctx, in.path, &raw))) return rc;
+        lrge_hip_reads *r = nullptr;
+        if ((rc = fx_open_mem(ctx, in.d ? (const void *)in.d : (const void *)raw.data(), in.d ? in.len : raw.size(), flags, FX_KEEP_SEL, sel, k, &r))) return rc;
+        if (r->sel.seen != m.records || r->text_bytes != m.text_bytes) { lrge_hip_reads_free(r); return fx_map_misfit(ctx, "another record count"); }
+        *out = r;
+        return LRGE_OK;
+    }
+    FxSeekPlan plan;
+    fx_seek_plan(m, sel, k, &plan);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const double t0 = fx_now_ms();
+    std::unique_ptr<lrge_hip_reads, void (*)(lrge_hip_reads *)> guard(new lrge_hip_reads(), lrge_hip_reads_free);
+    lrge_hip_reads *R = guard.get();
+    R->ctx = ctx;
+    FxSink s(ctx, R, flags, FX_KEEP_SEL);
+    s.run->dev.mapped = true;
+    int rc = s.run->dev.select(FX_KEEP_SEL, plan.sel.data(), k);
+    if (rc) return rc;
+    s.run->attach(&s.blk);
+    rc = m.kind == FX_SEEK_PLAIN ? fx_src_seek_raw(s, in, plan) : fx_src_seek_bgzf(s, in, plan);
+    if (!rc) rc = fx_finish_windowed(s, t0);
+    // the sub-text is proven again, and holds exactly the planner's records: else the input is not the one the map was made of
+    if (rc == LRGE_ERR_INVALID && s.run->dev.at < s.run->dev.k) return fx_map_misfit(ctx, "fewer records than the plan");
+    if (rc == LRGE_ERR_UNPROVEN && s.run->dev.scan_refused) { const std::string why = ctx->err; return fx_map_misfit(ctx, why.c_str()); }
+    if (rc) return rc;
+    if (R->sel.seen != plan.records) return fx_map_misfit(ctx, "another record count");
+    R->sel.seen = m.records; R->sel.bases_seen = m.bases; R->text_bytes = m.text_bytes;
+    if (R->fmt == FX_FMT_EMPTY) R->fmt = m.fmt;
+    R->seek[0] = plan.runs.size(); R->seek[1] = plan.text_bytes; R->seek[2] = plan.file_bytes; R->seek[3] = plan.blocks;
+    *out = guard.release();
+    return LRGE_OK;
+}
+
+extern "C" int lrge_hip_reads_open_mapped_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, int flags, const lrge_hip_read_map *map, const uint32_t *sel, uint32_t k,
+                                              lrge_hip_reads **out) {
+    if (!ctx || !out || !map || (!file_bytes && len)) return LRGE_ERR_INVALID;
+    static const u8 none = 0;
+    FxInput in;
+    in.d = file_bytes ? (const u8 *)file_bytes : &none; in.len = len;
+    return fx_open_mapped(ctx, in, flags, map, sel, k, out);
+}
+
+extern "C" int lrge_hip_reads_open_mapped(lrge_hip_ctx *ctx, const char *path, int flags, const lrge_hip_read_map *map, const uint32_t *sel, uint32_t k, lrge_hip_reads **out) {
+    if (!ctx || !path || !out || !map) return LRGE_ERR_INVALID;
+    *out = nullptr;
+    FxInput in;
+    struct stat st;
+    if ((in.fd = open(path, O_RDONLY | O_CLOEXEC)) < 0 || fstat(in.fd, &st) != 0 || !S_ISREG(st.st_mode)) { LRGE_SET_ERR(ctx, "IO error: %s: cannot be opened for reading by range", path); return LRGE_ERR_IO; }
+    in.len = (u64)st.st_size; in.path = path;
+    return fx_open_mapped(ctx, in, flags, map, sel, k, out);
 }
 
 extern "C" int lrge_hip_reads_open(lrge_hip_ctx *ctx, const char *path, int flags, lrge_hip_reads **out) {

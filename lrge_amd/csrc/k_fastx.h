@@ -15,6 +15,8 @@
 //   k_fx_bases     selected ingest: the sum of a window's sequence lengths           4 B read per record
 //   k_fx_pick      one lane per chosen record of a window: its two lengths into dense arrays
 //   k_fx_keep      one wavefront per chosen record: its identifier into the identifier buffer, its bases into the store   (same copy)
+//   k_fx_seek      seek map: one lane per record of a window, the first record start of every cell   32 B read per record
+//   k_fx_runs      mapped open: the trimmed runs from the decode staging to the tail of the block, a wavefront per 4 KiB tile
 // The text buffer is allocated with FX_PAD bytes behind its end, so whole 16-byte groups (and the word behind an unaligned
 // source word of the gather) may be loaded; every byte at or past `n` is masked out before use.
 #pragma once
@@ -182,25 +184,30 @@ __global__ __launch_bounds__(FX_THREADS) void k_fx_names(const u8 *__restrict__ 
     for (u32 i = 0; i < k; ++i) d[i] = s[i];
 }
 
+// s[0, len) to d[0, len) by one wavefront (`lane` of 64), for every alignment of either: aligned 4-byte words of the destination, each
+// assembled from the two source words it overlaps (the word behind the last source byte may be loaded: FX_PAD), bytes at both ends
+__device__ __forceinline__ void fx_copy_span(const u8 *__restrict__ s, u8 *__restrict__ d, u64 len, u32 lane) {
+    u64 head = (4 - ((uintptr_t)d & 3)) & 3;
+    if (head > len) head = len;
+    if (lane < head) d[lane] = s[lane];
+    const u64 nw = (len - head) >> 2;
+    for (u64 w = lane; w < nw; w += 64) {
+        const uintptr_t sa = (uintptr_t)(s + head + 4 * w);
+        const u32 sh = (u32)(sa & 3) * 8;
+        const u32 *q = reinterpret_cast<const u32 *>(sa & ~(uintptr_t)3);
+        const u32 lo = q[0];
+        reinterpret_cast<u32 *>(d + head)[w] = sh ? (u32)((((u64)q[1] << 32) | lo) >> sh) : lo;
+    }
+    for (u64 i = head + 4 * nw + lane; i < len; i += 64) d[i] = s[i];
+}
+
 // The bases of one record to d[0, seq_len), by one wavefront (`lane` of 64).  A single-line sequence (span == length) is copied
-// in aligned 4-byte words, each assembled from the two source words it overlaps; a multi-line one is compacted group by
+// by fx_copy_span; a multi-line one is compacted group by
 // group with a wave scan of the kept bytes.
 __device__ __forceinline__ void fx_copy_bases(const u8 *__restrict__ t, u64 n, const FxRec &rec, u8 *__restrict__ d, u32 lane) {
     const u64 a = rec.seq_off, len = rec.seq_len;
     if (rec.seq_span == len) {
-        const u8 *s = t + a;
-        u64 head = (4 - ((uintptr_t)d & 3)) & 3;
-        if (head > len) head = len;
-        if (lane < head) d[lane] = s[lane];
-        const u64 nw = (len - head) >> 2;
-        for (u64 w = lane; w < nw; w += 64) {
-            const uintptr_t sa = (uintptr_t)(s + head + 4 * w);
-            const u32 sh = (u32)(sa & 3) * 8;
-            const u32 *q = reinterpret_cast<const u32 *>(sa & ~(uintptr_t)3);
-            const u32 lo = q[0];
-            reinterpret_cast<u32 *>(d + head)[w] = sh ? (u32)((((u64)q[1] << 32) | lo) >> sh) : lo;
-        }
-        for (u64 i = head + 4 * nw + lane; i < len; i += 64) d[i] = s[i];
+        fx_copy_span(t + a, d, len, lane);
     } else {
         const u64 b = a + rec.seq_span;
         u64 done = 0;
@@ -271,4 +278,37 @@ __global__ __launch_bounds__(64) void k_fx_keep(const u8 *__restrict__ t, u64 n,
         for (u32 i = threadIdx.x; i < rec.name_len; i += 64) d[i] = s[i];
         fx_copy_bases(t, n, rec, store + dst[j], threadIdx.x);
     }
+}
+
+// The seek map of a census (fx_seek.h), behind k_fx_records: one lane per record of the window's proven prefix.
+// Record r starts at window offset recs[r].name_off - 1, the '>' or '@' of its header line, which is text offset `through` + that.
+// A record whose cell (text offset / stride) differs from its predecessor's is the first that starts in its cell: its index goes
+// to slot[cell - cell0] and its window offset to slot[n_cells + cell - cell0] (preset to FX_SEEK_NONE); record 0 always writes.
+// cell0: the cell of the window's first byte; every record lies in [cell0, cell0 + n_cells).
+__global__ __launch_bounds__(FX_THREADS) void k_fx_seek(const FxRec *__restrict__ recs, u64 n_rec, u64 through, u64 stride, u64 cell0, u64 n_cells,
+                                                        u32 *__restrict__ slot) {
+    const u64 r = (u64)blockIdx.x * FX_THREADS + threadIdx.x;
+    if (r >= n_rec) return;
+    const u64 at = recs[r].name_off - 1, cell = (through + at) / stride;
+    if (r && (through + recs[r - 1].name_off - 1) / stride == cell) return;
+    const u64 c = cell - cell0;
+    if (c >= n_cells) return;                               // (never: the prefix ends inside the last cell)
+    slot[c] = (u32)r; slot[n_cells + c] = (u32)at;
+}
+
+// The mapped open: copy j of the table is src[c.src, c.src + c.len) to dst[c.dst, ..), the trimmed part of a run
+// in the decode staging to its place behind the block's tail.  The copies are cut into tiles of FX_RUN_TILE bytes; first[j] is
+// the number of tiles in front of copy j (first[n_copy]: all of them), made by the host, and a wavefront takes a tile: it finds
+// its copy by bisection and moves the tile with fx_copy_span, whatever the alignment of either side.
+#define FX_RUN_TILE 4096u
+struct FxRunCopy { u64 src, dst, len; };
+__global__ __launch_bounds__(64) void k_fx_runs(const u8 *__restrict__ src, u8 *__restrict__ dst, const FxRunCopy *__restrict__ copies, const u64 *__restrict__ first,
+                                                u32 n_copy) {
+    const u64 tile = blockIdx.x;                            // (the grid is first[n_copy] wavefronts: a window is below 2^32 bytes, its tiles below 2^21)
+    if (tile >= first[n_copy]) return;
+    u32 lo = 0, hi = n_copy;                                // the last copy whose first tile is at or below `tile`
+    while (hi - lo > 1) { const u32 mid = lo + (hi - lo) / 2; if (first[mid] <= tile) lo = mid; else hi = mid; }
+    const FxRunCopy c = copies[lo];
+    const u64 off = (tile - first[lo]) * FX_RUN_TILE, m = c.len - off < FX_RUN_TILE ? c.len - off : FX_RUN_TILE;
+    fx_copy_span(src + c.src + off, dst + c.dst + off, m, threadIdx.x);
 }

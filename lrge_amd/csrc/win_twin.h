@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "fx_window.h"
+#include "fx_seek.h"
 
 // what a windowed run leaves, behind the <twin>_windowed_* accessors
 struct WinTwinOut {
@@ -42,6 +43,7 @@ template <class Scan> struct WinTwin {
     FxKeepMode mode = FX_KEEP_ALL;      // FX_KEEP_SEL: sel[0, k), strictly ascending; sel[0, at) lay in the windows flushed so far
     const uint32_t *sel = nullptr;
     uint64_t k = 0, at = 0;
+    FxSeekMap *map = nullptr;           // a census that leaves a seek map (fx_seek.h): every window's records go through the point rule
     WinTwin(Scan &s, WinTwinOut &o) : scan(s), out(o) {}
     void keep(const FxRec &r, uint64_t cut) {
         const uint64_t a = out.store.size();
@@ -64,6 +66,7 @@ template <class Scan> struct WinTwin {
         const uint64_t r0 = out.sel.seen, n_rec = recs.size();
         if ((r0 + n_rec) >> 32) return (int)FX_UNPROVEN;
         const uint64_t b = mode == FX_KEEP_SEL ? fx_sel_slice(sel, k, at, r0, n_rec) : at;
+        if (map) for (uint64_t i = 0; i < n_rec; ++i) fx_seek_add(*map, r0 + i, base + recs[i].name_off - 1);
         for (const FxRec &r : recs) out.sel.bases_seen += r.seq_len;
         for (; at < b; ++at) {
             const FxRec &r = recs[sel[at] - r0];
@@ -84,14 +87,14 @@ template <class Scan> struct WinTwin {
 // a text that ends before its first flush is scanned whole, as without windows (resident_bases: its bases count in the stats all
 // the same).  0 with `out` filled, or the verdict with `out` empty
 // mode, sel, k: what the run keeps (fx_window.h FxKeepMode); WIN_TWIN_INVALID: sel is not strictly ascending, or holds an ordinal
-// at or above the records the run saw
+// at or above the records the run saw.  map: a census (FX_KEEP_NONE) fills the points of a seek map (fx_seek.h; stride set by the caller)
 #define WIN_TWIN_INVALID (-2)
 template <class Scan> int win_twin_run(Scan &scan, const uint8_t *t, uint64_t n, uint64_t window, uint64_t piece, bool resident_bases, WinTwinOut &out,
-                                       FxKeepMode mode = FX_KEEP_ALL, const uint32_t *sel = nullptr, uint64_t k = 0) {
+                                       FxKeepMode mode = FX_KEEP_ALL, const uint32_t *sel = nullptr, uint64_t k = 0, FxSeekMap *map = nullptr) {
     out = WinTwinOut();
     if (mode == FX_KEEP_SEL && ((k && !sel) || !fx_sel_ascending(sel, k))) return WIN_TWIN_INVALID;
     WinTwin<Scan> b(scan, out);
-    b.mode = mode; b.sel = sel; b.k = k;
+    b.mode = mode; b.sel = sel; b.k = k; b.map = map;
     FxWindow<WinTwin<Scan>> win(b, window);
     int rc = 0;
     for (uint64_t p = 0; p < n && !rc; p += piece) {

@@ -190,6 +190,28 @@ class Context:
         order, read j being record sel[j]; DeviceReads.select_stats() tells what the pass saw."""
         return DeviceReads(self, src, flags, sel)
 
+    def census_map_reads(self, src, flags=_ffi.GPU_INFLATE_BGZF | _ffi.GPU_INFLATE_GZIP):
+        """census_reads that also leaves the seek map of the text (lrge_hip_reads_census_map*, option INGEST_SEEK_STRIDE_BYTES):
+        returns (counts, ReadMap).  open_reads_mapped(src, map, sel) then brings only the runs that hold chosen reads."""
+        L = self._lib
+        out, h = (C.c_uint64 * 4)(), C.c_void_p()
+        if isinstance(src, (bytes, bytearray, memoryview, np.ndarray)):
+            buf = np.frombuffer(src, dtype=np.uint8) if not isinstance(src, np.ndarray) else np.ascontiguousarray(src, dtype=np.uint8)
+            rc = L.lrge_hip_reads_census_map_mem(self.h, buf.ctypes.data if buf.size else None, buf.size, int(flags), C.byref(out), C.byref(h))
+        else:
+            import os
+            rc = L.lrge_hip_reads_census_map(self.h, os.fsencode(str(src)), int(flags), C.byref(out), C.byref(h))
+        if rc == _ffi.ERR_UNPROVEN:
+            raise UnprovenInput(rc, L.lrge_hip_last_error(self.h).decode())
+        self._check(rc)
+        return tuple(int(x) for x in out), ReadMap(self, h)
+
+    def open_reads_mapped(self, src, map, sel, flags=_ffi.GPU_INFLATE_BGZF | _ffi.GPU_INFLATE_GZIP):
+        """open_reads_selected of the input `map` was made of (lrge_hip_reads_open_mapped*): for plain and BGZF input only the runs
+        that hold records `sel` are read, decoded and scanned; the DeviceReads is the one open_reads_selected gives, and
+        DeviceReads.seek_stats() tells what was brought.  Input the map does not fit raises UnprovenInput."""
+        return DeviceReads(self, src, flags, sel, map)
+
     def _name_ranks(self, blob, name_off, n_names, idx_lists):
         """lrge_hip_name_ranks over a table of identifiers; idx_lists None: every identifier in order, as one list"""
         if idx_lists is None:
@@ -362,26 +384,72 @@ class SeqSet:
         return x[:n.value], y[:n.value]
 
 
+class ReadMap:
+    """The seek map a census left of one input (lrge_hip_read_map, Context.census_map_reads): one point per cell of the text in
+    which a record starts.  It belongs to no context and is freed with free() or with the object."""
+
+    def __init__(self, ctx, h):
+        self._lib, self.h = ctx._lib, h
+
+    def stats(self):
+        """(records, points, stride, text bytes)"""
+        a = (C.c_uint64 * 4)()
+        rc = self._lib.lrge_hip_read_map_stats(self.h, C.byref(a))
+        if rc:
+            raise _ffi.LrgeHipError(rc, "read_map_stats")
+        return tuple(int(x) for x in a)
+
+    def points(self):
+        """[(ordinal, text offset, file offset of the BGZF block -- 0 for plain input)] of every point"""
+        k = self.stats()[1]
+        a = [np.zeros(max(1, k), dtype=np.uint64) for _ in range(3)]
+        rc = self._lib.lrge_hip_read_map_points(self.h, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, k)
+        if rc:
+            raise _ffi.LrgeHipError(rc, "read_map_points")
+        return list(zip(*(x[:k].tolist() for x in a)))
+
+    def free(self):
+        if self.h is not None:
+            self._lib.lrge_hip_read_map_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class DeviceReads:
     """The reads of one input file resident in HBM as text (lrge_hip_reads): `names` (list of bytes) and `lens` (uint32) are
     on the host, the bases never are.  seqset(idx, ranks) is an ordinary SeqSet of the chosen reads."""
 
-    def __init__(self, ctx, src, flags, sel=None):
+    def __init__(self, ctx, src, flags, sel=None, map=None):
         self.ctx, self.h = ctx, None
         h = C.c_void_p()
         L = ctx._lib
         if sel is not None:                                 # Context.open_reads_selected
             sel = np.ascontiguousarray(sel, dtype=np.uint32).ravel()
             sel_args = (sel.ctypes.data if sel.size else None, int(sel.size))
+        if map is not None:                                 # Context.open_reads_mapped
+            if sel is None:
+                raise ValueError("a ReadMap needs a selection")
+            if map.h is None:
+                raise ValueError("the ReadMap was freed")
+            sel_args = (map.h,) + sel_args
         if isinstance(src, (bytes, bytearray, memoryview, np.ndarray)):
             buf = np.frombuffer(src, dtype=np.uint8) if not isinstance(src, np.ndarray) else np.ascontiguousarray(src, dtype=np.uint8)
-            if sel is not None:
+            if map is not None:
+                rc = L.lrge_hip_reads_open_mapped_mem(ctx.h, buf.ctypes.data if buf.size else None, buf.size, int(flags), *sel_args, C.byref(h))
+            elif sel is not None:
                 rc = L.lrge_hip_reads_open_selected_mem(ctx.h, buf.ctypes.data if buf.size else None, buf.size, int(flags), *sel_args, C.byref(h))
             else:
                 rc = L.lrge_hip_reads_open_mem(ctx.h, buf.ctypes.data if buf.size else None, buf.size, int(flags), C.byref(h))
         else:
             import os
-            if sel is not None:
+            if map is not None:
+                rc = L.lrge_hip_reads_open_mapped(ctx.h, os.fsencode(str(src)), int(flags), *sel_args, C.byref(h))
+            elif sel is not None:
                 rc = L.lrge_hip_reads_open_selected(ctx.h, os.fsencode(str(src)), int(flags), *sel_args, C.byref(h))
             else:
                 rc = L.lrge_hip_reads_open(ctx.h, os.fsencode(str(src)), int(flags), C.byref(h))
@@ -438,6 +506,13 @@ class DeviceReads:
         a handle of Context.open_reads"""
         a = (C.c_uint64 * 4)()
         self.ctx._check(self.ctx._lib.lrge_hip_reads_select_stats(self.h, C.byref(a)))
+        return tuple(int(x) for x in a)
+
+    def seek_stats(self):
+        """(runs, text bytes brought, file bytes read, BGZF blocks decoded) of the pass behind Context.open_reads_mapped; zeros for
+        a handle of every other open"""
+        a = (C.c_uint64 * 4)()
+        self.ctx._check(self.ctx._lib.lrge_hip_reads_seek_stats(self.h, C.byref(a)))
         return tuple(int(x) for x in a)
 
     def name_ranks(self, *idx_lists):

@@ -6,7 +6,11 @@ unaligned SAM text (the "sam" kind: its record scan beside the FASTQ kind's, and
 the files of the kinds asked for are written.  Usage:
   python tools/ingest_bench.py [--gbases 1.08] [--dir /tmp] [--reps 5] [--kinds fq,bgzf.fq.gz,fq.gz,bam,sam]
                                [--bam-segments 262144,1048576,4194304] [--out profiles/ingest_bench.json]
-                               [--windowed [--window-mb 64[,1024]]] [--sampled K [--window-mb 64]]
+                               [--windowed [--window-mb 64[,1024]]] [--sampled K [--window-mb 64]] [--sampled K1,K2,.. --seek]
+--sampled K1,K2,.. --seek: on the plain and the BGZF FASTQ file, for every K, the census without and with a seek map
+(lrge_hip_reads_census, lrge_hip_reads_census_map), the selected open and the mapped open of the same K seeded ordinals
+(lrge_hip_reads_open_selected, lrge_hip_reads_open_mapped) and the existing windowed open, all alternating in one run; with the
+bytes the mapped open brought and read, under the key "sampled_seek" / "<K>" of --out.
 --sampled K: on each FASTQ file the two passes of the sampled ingest (lrge_hip_reads_census, then lrge_hip_reads_open_selected of K
 seeded ordinals and a read set of those K) beside the existing windowed open of the same file (and its read set of ALL reads),
 alternating in the same run; the result goes under the key "sampled" of --out.  With LRGE_HIP_LIB_AB naming a build from before
@@ -123,6 +127,45 @@ extern "C" int route_sampled(lrge_hip_ctx *ctx, const char *path, int flags, con
     lrge_hip_reads_window_stats(r, win);
     lrge_hip_seqset_free(s); lrge_hip_reads_free(r);
     ms[0] = t1 - t0; ms[1] = t2 - t1; ms[2] = t3 - t2;
+    return rc;
+}
+"""
+
+# ms: census, census with a map, selected open, mapped open, read set of the k reads of the mapped handle + wait
+HELPER_SEEK = r"""
+#include <chrono>
+#include <cstdint>
+#include <vector>
+#include "lrge_hip.h"
+static double now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+extern "C" int route_seek(lrge_hip_ctx *ctx, const char *path, int flags, const uint32_t *sel, uint32_t k, double ms[5], uint64_t census[4], uint64_t map_stats[4],
+                          uint64_t sel_stats[4], uint64_t seek[4]) {
+    uint64_t c2[4], s2[4];
+    const double t0 = now();
+    int rc = lrge_hip_reads_census(ctx, path, flags, census);
+    if (rc) return rc;
+    const double t1 = now();
+    lrge_hip_read_map *m = nullptr;
+    if ((rc = lrge_hip_reads_census_map(ctx, path, flags, c2, &m))) return rc;
+    const double t2 = now();
+    lrge_hip_reads *a = nullptr, *b = nullptr;
+    if ((rc = lrge_hip_reads_open_selected(ctx, path, flags, sel, k, &a))) return rc;
+    const double t3 = now();
+    if ((rc = lrge_hip_reads_open_mapped(ctx, path, flags, m, sel, k, &b))) return rc;
+    const double t4 = now();
+    std::vector<uint32_t> idx(k);
+    for (uint32_t i = 0; i < k; ++i) idx[i] = i;
+    lrge_hip_seqset *s = nullptr;
+    rc = lrge_hip_seqset_from_reads(ctx, b, idx.data(), k, nullptr, &s);
+    if (!rc) rc = lrge_hip_seqset_wait(s);
+    const double t5 = now();
+    lrge_hip_read_map_stats(m, map_stats);
+    lrge_hip_reads_select_stats(a, s2);
+    lrge_hip_reads_select_stats(b, sel_stats);
+    lrge_hip_reads_seek_stats(b, seek);
+    for (int i = 0; i < 4; ++i) if (c2[i] != census[i] || s2[i] != sel_stats[i]) rc = rc ? rc : -100;      // the two routes must agree
+    lrge_hip_seqset_free(s); lrge_hip_reads_free(a); lrge_hip_reads_free(b); lrge_hip_read_map_free(m);
+    ms[0] = t1 - t0; ms[1] = t2 - t1; ms[2] = t3 - t2; ms[3] = t4 - t3; ms[4] = t5 - t4;
     return rc;
 }
 """
@@ -301,6 +344,46 @@ def sampled_runs(a, ctx, H, HS, kinds, paths, text_bytes):
     json.dump(result, open(a.out, "w"), indent=1)
 
 
+def seek_runs(a, ctx, H, HK, kinds, paths, text_bytes, ks):
+    """for every K: the windowed open, the census without and with a map, the selected and the mapped open on every file, all
+    alternating in every repeat; into the key "sampled_seek" / "<K>" of a.out"""
+    import numpy as np
+    ctx.set_option("INGEST_WINDOW_BYTES", str(a.window_mb << 20))
+    result = json.load(open(a.out)) if os.path.exists(a.out) else {}
+    for K in ks:
+        out = {"window_bytes": a.window_mb << 20, "reps": a.reps, "k": K, "files": {}}
+        for kind in kinds:
+            p = paths[kind]
+            with open(p, "rb") as fh:
+                while fh.read(64 << 20):
+                    pass                                              # page cache
+            runs, sel, seen = [], None, {}
+            for rep in range(a.reps + 1):
+                ms2, st, nr, nb, tb, bs, win = (C.c_double * 2)(), (C.c_float * 4)(), C.c_uint64(), C.c_uint64(), C.c_uint64(), (C.c_uint64 * 6)(), (C.c_uint64 * 4)()
+                rc = H.route_device(ctx.h, p.encode(), 15 | 32 | 64, C.byref(ms2), C.byref(st), C.byref(nr), C.byref(nb), C.byref(tb), C.byref(bs), C.byref(win))
+                assert rc == 0, (kind, rc, ctx._lib.lrge_hip_last_error(ctx.h))
+                if sel is None:
+                    sel = np.sort(np.random.default_rng(1).choice(nr.value, min(K, nr.value), replace=False)).astype(np.uint32)
+                ms5, cen, mst, sst, sk = (C.c_double * 5)(), (C.c_uint64 * 4)(), (C.c_uint64 * 4)(), (C.c_uint64 * 4)(), (C.c_uint64 * 4)()
+                rc = HK.route_seek(ctx.h, p.encode(), 15, sel.ctypes.data, sel.size, C.byref(ms5), C.byref(cen), C.byref(mst), C.byref(sst), C.byref(sk))
+                assert rc == 0, (kind, rc, ctx._lib.lrge_hip_last_error(ctx.h))
+                assert (cen[0], cen[1], cen[2]) == (nr.value, nb.value, text_bytes[kind]) and (sst[0], sst[1], sst[2]) == (nr.value, sel.size, nb.value), (list(cen), list(sst))
+                seen = dict(reads=nr.value, bases=nb.value, kept_bases=sst[3], points=mst[1], stride=mst[2], runs=sk[0], text_bytes_brought=sk[1], file_bytes_read=sk[2], blocks_decoded=sk[3])
+                if rep:                                                # (run 0 is the warm-up)
+                    runs.append(dict(open_ms=ms2[0], census_ms=ms5[0], census_map_ms=ms5[1], selected_open_ms=ms5[2], mapped_open_ms=ms5[3], seqset_k_ms=ms5[4],
+                                     map_cost_ms=ms5[1] - ms5[0], two_pass_ms=ms5[1] + ms5[3], two_pass_parent_ms=ms5[0] + ms5[2]))
+            f = dict(file_bytes=os.path.getsize(p), text_bytes=text_bytes[kind], every_run=runs, **seen)
+            for key in runs[0]:
+                f["%s_median" % key] = statistics.median(x[key] for x in runs)
+                f["%s_range" % key] = (min(x[key] for x in runs), max(x[key] for x in runs))
+            out["files"][kind] = f
+            print(K, kind, json.dumps({k: v for k, v in f.items() if k != "every_run"}), flush=True)
+        result.setdefault("sampled_seek", {})[str(K)] = out
+    ctx.set_option("INGEST_WINDOW_BYTES", None)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    json.dump(result, open(a.out, "w"), indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gbases", type=float, default=1.08)
@@ -311,8 +394,13 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ingest_bench.json"))
     ap.add_argument("--windowed", action="store_true")
     ap.add_argument("--window-mb", default="64")
-    ap.add_argument("--sampled", type=int, default=0)
+    ap.add_argument("--sampled", default="0")
+    ap.add_argument("--seek", action="store_true")
     a = ap.parse_args()
+    seek_ks = [int(k) for k in a.sampled.split(",") if int(k)] if a.seek else []
+    a.sampled = 0 if a.seek else int(a.sampled)
+    if a.seek and not seek_ks:
+        ap.error("--seek needs --sampled K[,K..]")
     from lrge_amd import build as B, engine
     work = tempfile.mkdtemp(dir=a.dir, prefix="ingest_bench_")
     src = os.path.join(work, "helper.cpp")
@@ -332,6 +420,19 @@ def main():
     H.route_host.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_double * 3), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     H.route_device.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_double * 2), C.POINTER(C.c_float * 4), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                C.POINTER(C.c_uint64), C.POINTER(C.c_uint64 * 6), C.POINTER(C.c_uint64 * 4)]
+    if seek_ks:
+        extra = [os.path.join(work, "seek.cpp"), os.path.join(work, "libseek.so")]
+        open(extra[0], "w").write(HELPER_SEEK)
+        build(extra[1], extra[0])
+        HK = C.CDLL(extra[1])
+        HK.route_seek.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(C.c_double * 5)] + [C.POINTER(C.c_uint64 * 4)] * 4
+        a.window_mb = int(a.window_mb.split(",")[0])
+        seek_runs(a, ctx, H, HK, [k for k in kinds if k in ("fq", "bgzf.fq.gz")], paths, text_bytes, seek_ks)
+        ctx.close()
+        for p in list(paths.values()) + [src, so] + extra:
+            os.remove(p)
+        os.rmdir(work)
+        return
     if a.sampled:
         HS, extra = None, []
         if hasattr(ctx._lib, "lrge_hip_reads_census"):

@@ -5,12 +5,15 @@
 // Every *.bam file goes through bam_twin_windowed at segments 64, 257 and 4096, every *.sam file through sam_twin_windowed, every
 // other file through fastx_twin_windowed at tiles 64 and 4096, at windows 64, 257, 3001 and 20000 and pieces 1, 61, the window and
 // the whole text; a window above the text must give the resident twin's record count.  Every FASTA / FASTQ run is followed by the
-// two passes of the selected ingest (fastx_twin_census, fastx_twin_selected) on the same text, window and piece.  Prints the verdict counts; the exit
+// two passes of the selected ingest (fastx_twin_census, fastx_twin_selected) on the same text, window and piece, and by the seek map
+// (fastx_twin_census_map at strides 1, 64, 3000 and above the text, fastx_twin_seek_plan for the plain text and for BGZF blocks of 3000 text
+// bytes, fastx_twin_mapped).  Prints the verdict counts; the exit
 // status is 1 when the verdicts of one file disagree.
 // TEST INFRASTRUCTURE, not part of the product library.
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -60,6 +63,54 @@ static uint64_t fastx_selected(const char *path, const std::vector<uint8_t> &t, 
     return bad;
 }
 
+// The seek map over a text whose windowed run gave verdict `rc` and table `all` (name_off in the whole text): the census with a map
+// has the same verdict and counts; its points are strictly ascending records of `all` at their header bytes, the first record 0; the
+// plan of every third record and the last brings whole runs, for the plain text and for made-up BGZF blocks of 3000 text bytes;
+// the mapped run gives the records of the selected run.  Returns the disagreements
+static uint64_t fastx_seek(const char *path, const std::vector<uint8_t> &t, uint64_t tile, uint64_t window, uint64_t piece, int rc, const std::vector<FxRec> &all) {
+    uint64_t bad = 0;
+    const auto fail = [&](const char *what, uint64_t stride) { ++bad; fprintf(stderr, "%s: tile %llu window %llu piece %llu stride %llu: %s\n", path, (unsigned long long)tile, (unsigned long long)window, (unsigned long long)piece, (unsigned long long)stride, what); };
+    const uint64_t strides[] = {1, 64, 3000, (uint64_t)t.size() + 1};
+    for (uint64_t stride : strides) {
+        uint64_t cs[4], ps[4];
+        const int crc = fastx_twin::fastx_twin_census_map(t.data(), t.size(), tile, window, piece, stride, cs);
+        if (crc != rc || (!rc && cs[0] != all.size())) { fail("the census with a map disagrees with the windowed run", stride); continue; }
+        if (rc) continue;
+        const uint64_t np = fastx_twin::fastx_twin_map_points(nullptr, nullptr, 0);
+        std::vector<uint64_t> ord(np + 1), off(np + 1);
+        fastx_twin::fastx_twin_map_points(ord.data(), off.data(), np);
+        bool good = all.empty() ? np == 0 : np > 0 && ord[0] == 0;
+        for (uint64_t i = 0; i < np && good; ++i) good = ord[i] < all.size() && off[i] == all[ord[i]].name_off - 1 && (!i || (ord[i] > ord[i - 1] && off[i] / stride > off[i - 1] / stride));
+        if (!good) { fail("the points are not first record starts of their cells", stride); continue; }
+        std::vector<uint32_t> sel;
+        for (uint64_t i = 0; i < all.size(); ++i) if (i % 3 == 0 || i + 1 == all.size()) sel.push_back((uint32_t)i);
+        // the plan on the plain text, and on blocks of 3000 text bytes whose members are 100 bytes longer than half their text
+        if (fastx_twin::fastx_twin_seek_plan(nullptr, nullptr, 0, 0, sel.data(), sel.size(), ps) || ps[1] > t.size() || ps[1] != ps[2] || ps[3]) fail("the plan of the plain text", stride);
+        std::vector<uint32_t> c_len, isize;
+        uint64_t file_len = 0;
+        for (uint64_t o = 0; o < t.size(); o += 3000) { isize.push_back((uint32_t)std::min<uint64_t>(3000, t.size() - o)); c_len.push_back(isize.back() / 2 + 100); file_len += c_len.back(); }
+        isize.push_back(0); c_len.push_back(28); file_len += 28;    // (the empty block at the end of a BGZF file)
+        uint64_t bs[4];
+        if (fastx_twin::fastx_twin_seek_plan(c_len.data(), isize.data(), c_len.size(), file_len, sel.data(), sel.size(), bs) || bs[0] != ps[0] || bs[1] != ps[1] || bs[2] > file_len ||
+            bs[3] > c_len.size() || (!sel.empty() && (!bs[3] || bs[2] < 28)))
+            fail("the plan of the BGZF blocks", stride);
+        const int mrc = fastx_twin::fastx_twin_mapped(t.data(), t.size(), tile, window, piece, sel.data(), sel.size());
+        if (mrc) { fail("the mapped run is not proven", stride); continue; }
+        const uint64_t k = fastx_twin::fastx_twin_windowed_count();
+        std::vector<FxRec> tab(k);
+        fastx_twin::fastx_twin_windowed_table(tab.data());
+        bool same = k == sel.size();
+        for (uint64_t j = 0; j < k && same; ++j) {
+            std::vector<uint8_t> out(tab[j].seq_len + 1);
+            same = tab[j].name_off == all[sel[j]].name_off && tab[j].seq_len == all[sel[j]].seq_len && fastx_twin::fastx_twin_windowed_seq(j, out.data()) == tab[j].seq_len;
+        }
+        if (!same) fail("the mapped run kept other records", stride);
+        sel.push_back((uint32_t)all.size());
+        if (fastx_twin::fastx_twin_mapped(t.data(), t.size(), tile, window, piece, sel.data(), sel.size()) != WIN_TWIN_INVALID) fail("an ordinal past the records is not invalid", stride);
+    }
+    return bad;
+}
+
 int main(int argc, char **argv) {
     const uint64_t windows[] = {64, 257, 3001, 20000}, segs[] = {64, 257, 4096}, tiles[] = {64, 4096};
     uint64_t runs = 0, proven = 0, bad = 0;
@@ -89,6 +140,7 @@ int main(int argc, char **argv) {
                         else (is_sam ? sam_twin::sam_twin_windowed_seq : fastx_twin::fastx_twin_windowed_seq)(i, out.data());
                     }
                     if (!is_bam && !is_sam) bad += fastx_selected(argv[a], t, S, window, piece, rc, tab);
+                    if (!is_bam && !is_sam) bad += fastx_seek(argv[a], t, S, window, piece, rc, tab);
                     ++runs; proven += rc == 0;
                     if (first == -100) { first = rc; first_count = count; }
                     else if (rc != first || count != first_count) { ++bad; fprintf(stderr, "%s: S %llu window %llu piece %llu: verdict %d, %llu records; first %d, %llu\n", argv[a], (unsigned long long)S, (unsigned long long)window, (unsigned long long)piece, rc, (unsigned long long)count, first, (unsigned long long)first_count); }
