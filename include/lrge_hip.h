@@ -620,7 +620,8 @@ void     lrge_hip_reads_free(lrge_hip_reads *reads);
    empty handle, and the pass still proves the file.  LRGE_ERR_INVALID, before any handle is handed out: ordinals that are not
    strictly ascending; an ordinal at or above the number of records the pass saw (the message names the ordinal and the count).
    LRGE_ERR_UNPROVEN for both, whatever the flags: text whose first bytes say BAM, SAM or CRAM ("selected ingest takes FASTA /
-   FASTQ only"), Zstandard input (its text is never windowed); everything else as lrge_hip_reads_open*.
+   FASTQ only"; BAM is taken with LRGE_GPU_INGEST_SELECT_ALN beside LRGE_GPU_INGEST_BAM, below), Zstandard input (its text is never
+   windowed); everything else as lrge_hip_reads_open*.
    lrge_hip_reads_select_stats: out[0] records seen, out[1] records kept, out[2] sequence bases seen, out[3] bases kept by the
    pass that made the handle; zeros for a handle of lrge_hip_reads_open*. */
 int      lrge_hip_reads_census(lrge_hip_ctx *ctx, const char *path, int flags, uint64_t out[4]);
@@ -664,6 +665,22 @@ int      lrge_hip_reads_open_mapped(lrge_hip_ctx *ctx, const char *path, int fla
 int      lrge_hip_reads_open_mapped_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, int flags, const lrge_hip_read_map *map,
                                         const uint32_t *sel, uint32_t k, lrge_hip_reads **out);
 int      lrge_hip_reads_seek_stats(const lrge_hip_reads *reads, uint64_t out[4]);
+
+/* The sampled ingest of unaligned BAM (k_bam_keep beside k_fx_bases, k_fx_pick, k_bam_spans, k_fx_seek): uBAM is
+   what PacBio HiFi and dorado write, and two thirds of its text are qualities and tags the tool never reads (io.rs:93, 154-184).
+   | LRGE_GPU_INGEST_SELECT_ALN (opt-in; it has effect only beside LRGE_GPU_INGEST_BAM and only in lrge_hip_reads_census*,
+   _open_selected*, _census_map* and _open_mapped*; without it every call does what it did, the refusal text included): text whose
+   first bytes are "BAM\1" is a BAM run in those six calls.  It passes through the windows of DESIGN section 18 whatever
+   LRGE_GPU_INGEST_WINDOWED / _WINDOWED_ALN say, from the sources of the FASTA / FASTQ sampled calls (plain, BGZF, gzip, bzip2, xz);
+   SAM, CRAM and Zstandard stay refused with the same texts.  The count and the records sel[j] are those of lrge_hip_read_records on
+   the same bytes, or the call is LRGE_ERR_UNPROVEN (a mapped record, a damaged record, 1-3 trailing bytes, in whichever window) and
+   hands out no handle.  A header that ends the text is an empty census and an empty handle.  The handle is the windowed BAM handle
+   restricted to the chosen reads: (l_seq + 1) / 2 packed bytes a chosen record, dense, in file order, the pad nibble as it is;
+   lrge_hip_seqset_from_reads, _name_ranks, _table, _window_stats and _bam_stats (summed over the windows the pass flushed; a mapped
+   open: those of the sub-text) work unchanged.  select_stats out[2] / out[3] count bases; window_stats out[1] and INGEST_MAX_BYTES
+   count store bytes.  A point of the seek map is a record's block_size field, the first point record 0 behind the header; a mapped
+   open of a BAM map without both flags is refused as the census is. */
+#define LRGE_GPU_INGEST_SELECT_ALN 1024
 
 /* Read sets built on the device from unaligned CRAM 3.0 / 3.1 (k_rans_decode): | LRGE_GPU_INGEST_CRAM (opt-in:
    no other flag implies it, and without it every call does what it did) sends input that starts with "CRAM" to a host walk of the

@@ -20,6 +20,7 @@ GPU_INFLATE_XZ = 256
 GPU_INGEST_CRAM = 512
 GPU_INGEST_WINDOWED = 32
 GPU_INGEST_WINDOWED_ALN = 64
+GPU_INGEST_SELECT_ALN = 1024
 PRESET_AVA_ONT, PRESET_AVA_PB = 0, 1
 
 T_NAMES = ["pack", "sketch", "index_sort", "index_table", "qfilter", "lookup", "expand", "anchor_sort", "group",

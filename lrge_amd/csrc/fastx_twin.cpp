@@ -245,39 +245,14 @@ uint64_t fastx_twin_map_points(uint64_t *ord, uint64_t *off, uint64_t cap) {
     return gm.pts.size();
 }
 
-// the selection against the map: 0, or WIN_TWIN_INVALID for one that is not ascending or reaches the map's records
-static int sel_fits(const uint32_t *sel, uint64_t k) {
-    if ((k && !sel) || !fx_sel_ascending(sel, k)) return WIN_TWIN_INVALID;
-    for (uint64_t j = 0; j < k; ++j) if (sel[j] >= gm.records) return WIN_TWIN_INVALID;
-    return 0;
-}
-
-// The plan of selection sel[0, k) on the last map.  n_blk == 0: for the plain text.  Else for the same text in BGZF blocks of member
-// lengths c_len and text sizes isize (a file of file_len bytes): the block fields are attached as the device attaches them.
+// The plan of selection sel[0, k) on the last map (win_twin_seek_plan).
 // out = {runs, text bytes brought, file bytes read, blocks decoded}; the runs by fastx_twin_plan_runs (ord0, n_rec, t0, t1 each; returns
 // how many there are), the renumbered selection by fastx_twin_plan_sel
 int fastx_twin_seek_plan(const uint32_t *c_len, const uint32_t *isize, uint64_t n_blk, uint64_t file_len, const uint32_t *sel, uint64_t k, uint64_t out[4]) {
-    gp = FxSeekPlan();
-    out[0] = out[1] = out[2] = out[3] = 0;
-    if (sel_fits(sel, k)) return WIN_TWIN_INVALID;
-    FxSeekMap m = gm;
-    if (n_blk) {
-        std::vector<BgzfBlock> t(n_blk);
-        uint64_t c = 0, o = 0;
-        for (uint64_t i = 0; i < n_blk; ++i) { t[i] = BgzfBlock{c, o, 0, 0, c_len[i], isize[i], 0}; c += c_len[i]; o += isize[i]; }
-        if (o != m.text_bytes || c != file_len) return WIN_TWIN_INVALID;
-        m.kind = FX_SEEK_BGZF; m.n_blocks = n_blk; m.file_len = file_len;
-        fx_seek_attach(m, t.data(), n_blk);
-    }
-    fx_seek_plan(m, sel, k, &gp);
-    out[0] = gp.runs.size(); out[1] = gp.text_bytes; out[2] = gp.file_bytes; out[3] = gp.blocks;
-    return 0;
+    return win_twin_seek_plan(gm, c_len, isize, n_blk, file_len, sel, k, &gp, out);
 }
 
-uint64_t fastx_twin_plan_runs(uint64_t *out, uint64_t cap) {
-    for (uint64_t i = 0; i < gp.runs.size() && i < cap; ++i) { out[4 * i] = gp.runs[i].ord0; out[4 * i + 1] = gp.runs[i].n_rec; out[4 * i + 2] = gp.runs[i].t0; out[4 * i + 3] = gp.runs[i].t1; }
-    return gp.runs.size();
-}
+uint64_t fastx_twin_plan_runs(uint64_t *out, uint64_t cap) { return win_twin_plan_runs(gp, out, cap); }
 void fastx_twin_plan_sel(uint32_t *out) { if (!gp.sel.empty()) memcpy(out, gp.sel.data(), gp.sel.size() * 4); }
 
 // The mapped second pass over text t, which must be the text of the last map (WIN_TWIN_INVALID: another size): the plan, the
@@ -287,21 +262,14 @@ void fastx_twin_plan_sel(uint32_t *out) { if (!gp.sel.empty()) memcpy(out, gp.se
 int fastx_twin_mapped(const uint8_t *t, uint64_t n, uint64_t tile, uint64_t window, uint64_t piece, const uint32_t *sel, uint64_t k) {
     gw = WinTwinOut(); gp = FxSeekPlan();
     if (tile < 16 || tile % 16 || !piece) return -1;
-    if (n != gm.text_bytes || gm.kind != FX_SEEK_PLAIN || sel_fits(sel, k)) return WIN_TWIN_INVALID;
+    if (n != gm.text_bytes || gm.kind != FX_SEEK_PLAIN || win_twin_sel_fits(gm, sel, k)) return WIN_TWIN_INVALID;
     fx_seek_plan(gm, sel, k, &gp);
-    std::vector<uint8_t> sub;
-    for (const FxSeekRun &r : gp.runs) sub.insert(sub.end(), t + r.t0, t + r.t1);
+    const std::vector<uint8_t> sub = win_twin_sub_text(gp, t);
     Scan sc = {tile, false};
     int rc = win_twin_run(sc, sub.data(), sub.size(), window, piece, true, gw, FX_KEEP_SEL, gp.sel.data(), k);
     if (rc == WIN_TWIN_INVALID || (!rc && gw.sel.seen != gp.records)) rc = (int)FX_UNPROVEN;        // the map does not fit the input
     if (rc) { gw = WinTwinOut(); return rc; }
-    size_t ri = 0;
-    uint64_t before = 0;                // sub-text bytes in front of run ri
-    for (FxRec &r : gw.recs) {
-        while (r.name_off >= before + (gp.runs[ri].t1 - gp.runs[ri].t0)) { before += gp.runs[ri].t1 - gp.runs[ri].t0; ++ri; }
-        r.name_off = r.name_off - before + gp.runs[ri].t0;
-    }
-    gw.sel.seen = gm.records; gw.sel.bases_seen = gm.bases;
+    win_twin_mapped_back(gw, gp, gm);
     return 0;
 }
 

@@ -1,16 +1,20 @@
-// fx_seek.h -- the seek map of a FASTA / FASTQ text and the plan of a pass that brings only the chosen runs,
-// shared by the device (host_fastx.inl; hipcc) and the host twin (fastx_twin.cpp; g++), as fx_window.h is.
+// fx_seek.h -- the seek map of a FASTA / FASTQ text or of unaligned BAM and the plan of a pass that brings only the chosen runs
+// (DESIGN sections 24 and 25), shared by the device (host_fastx.inl; hipcc) and the host twins (fastx_twin.cpp, bam_twin.cpp; g++), as
+// fx_window.h is.
 //
 // The census that proves the text (fx_window.h FX_KEEP_NONE) can leave a map behind.  The whole text is cut into cells of
-// `stride` bytes; a cell in which at least one record starts gets one point: the first record that starts in it.  A record starts
-// at the first byte of its header line, the '>' or '@' (FxRec::name_off - 1).  A point holds the record's ordinal (file order,
+// `stride` bytes; a cell in which at least one record starts gets one point: the first record that starts in it.  Where a record
+// starts is fx_rec_start: FASTA / FASTQ at the first byte of its header line, the '>' or '@' (FxRec::name_off - FX_LEAD_TEXT); BAM at
+// its block_size field (FxRec::name_off - FX_LEAD_BAM, bam_record), so the BAM header lies in front of record 0's point at hdr_end as
+// leading blank lines do.  A point holds the record's ordinal (file order,
 // 0-based), its text offset and, for BGZF, the block that holds that offset.  Cells inside one long record have no point; the
 // points ascend strictly in ordinal and in offset, and the first point is record 0.
 //
 // The plan of a selection (strictly ascending ordinals): for each chosen ordinal the run from the last point at or below it to
 // the first point above it, or to the end of the text; runs that touch or overlap are merged.  The sub-text -- the runs'
 // bytes, concatenated -- is a text of whole records (a run starts at a header line and ends directly behind a line feed or at the
-// end of the text), and the selection renumbered into its ordinals names the same records.
+// end of the text; a BAM run starts at a block_size field and ends in front of the next, so the sub-text is a record stream without
+// a header), and the selection renumbered into its ordinals names the same records.
 #pragma once
 #include <stdint.h>
 
@@ -21,6 +25,11 @@
 
 enum { FX_SEEK_PLAIN = 0, FX_SEEK_BGZF = 1, FX_SEEK_OTHER = 2 };    // OTHER: a container that cannot be entered (gzip, bzip2, xz)
 #define FX_SEEK_NONE 0xFFFFFFFFu                                     // a cell's slot without a record start
+
+// the record-start rule: a record starts `lead` bytes in front of its identifier
+#define FX_LEAD_TEXT 1u                                              // the '>' or '@'
+#define FX_LEAD_BAM 36u                                              // block_size and the 32 bytes of fixed fields (bam_record)
+FX_HD uint64_t fx_rec_start(uint64_t name_off, uint32_t lead) { return name_off - lead; }
 
 // blk: the index of the block that holds text offset `off` (o_off <= off < o_off + ISIZE), c_off / o_off / c_len its file offset,
 // text offset and member length; plain input: all 0

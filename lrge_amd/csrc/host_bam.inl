@@ -20,6 +20,8 @@ struct BamDev {
     u64 *d_cand = nullptr, *d_from = nullptr;                           // (d_from: later the table bases, one more than segments)
     BamSeg *d_seg = nullptr;
     u32 *d_list = nullptr, *d_seq_len = nullptr, *d_name_len = nullptr;
+    bool count_bases = false;                                           // a run that does not keep all: `bases` is the sum of the lengths
+    u64 bases = 0;
 
     int header(u64 *he, u32 *verdict) {
         ALLOC_OR_FAIL(d_hdr, sc, BamHeader, 1);
@@ -57,28 +59,37 @@ struct BamDev {
         const int rc = fx_alloc_recs(ctx, R, std::max<u64>(1, n_rec));
         if (rc) return rc;
         if (!(d_seq_len = sc.get<u32>(std::max<u64>(1, n_rec))) || !(d_name_len = sc.get<u32>(std::max<u64>(1, n_rec)))) return LRGE_ERR_DEVICE;
-        ALLOC_OR_FAIL(d_flags, sc, u64, 2);                   // [0]: verdict bits (low word), [1]: identifier bytes
-        HIPCHK(ctx, hipMemsetAsync(d_flags, 0, 16, st));
+        ALLOC_OR_FAIL(d_flags, sc, u64, 3);                   // [0]: verdict bits (low word), [1]: identifier bytes, [2]: bases (count_bases)
+        HIPCHK(ctx, hipMemsetAsync(d_flags, 0, 24, st));
         HIPCHK(ctx, hipMemcpyAsync(d_cand, start, (size_t)n_seg * 8, hipMemcpyHostToDevice, st));
         HIPCHK(ctx, hipMemcpyAsync(d_from, base, ((size_t)n_seg + 1) * 8, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_bam_records, bam_walker_grid(ctx, n_seg), dim3(64), 0, st, t, n, hdr_end, S, (const u64 *)d_cand, (const u64 *)d_from, n_seg, cut, R->d_recs, d_seq_len,
                            d_name_len, (u32 *)d_flags, (unsigned long long *)(d_flags + 1));
         KCHK(ctx);
-        u64 f[2] = {0, 0};
-        HIPCHK(ctx, hipMemcpyAsync(f, d_flags, sizeof f, hipMemcpyDeviceToHost, st));
+        if (count_bases && n_rec) {                            // the sum comes back in the copy below: no synchronisation of its own
+            hipLaunchKernelGGL(k_fx_bases, dim3(std::min<u32>((u32)div_up(n_rec, FX_THREADS), (u32)ctx->n_cu * 8)), dim3(FX_THREADS), 0, st, (const u32 *)d_seq_len, n_rec,
+                               (unsigned long long *)(d_flags + 2));
+            KCHK(ctx);
+        }
+        u64 f[3] = {0, 0, 0};
+        HIPCHK(ctx, hipMemcpyAsync(f, d_flags, count_bases ? 24 : 16, hipMemcpyDeviceToHost, st));
         HIPCHK(ctx, hipStreamSynchronize(st));                 // (start and base are pageable: their copies are done)
-        *flags = (u32)f[0]; *name_bytes = f[1];
+        *flags = (u32)f[0]; *name_bytes = f[1]; bases = f[2];
         return LRGE_OK;
     }
 };
 }  // namespace
 
 // w: the text is a window (fx_window.h) -- only the first has a header, one that is not the last is scanned
-// up to its cut (w->cut; 0: there is none yet), and the packed bases of its records go to the store
+// up to its cut (w->cut; 0: there is none yet), and the packed bases of its records go to the store.  A run that does not keep all
+// (the census and the selected open) brings neither the tables to the host nor the window to the store: the bases
+// are counted behind k_bam_records, the seek map takes its points, and FxWinDev::keep_window keeps the chosen records
 static int bam_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R, FxWinScan *w) {
     Scratch sc(ctx);
     R->name_off.assign(1, 0);
     BamDev dev{ctx, R, sc, R->d_text, R->n_text, ctx->stream};
+    const FxKeepMode mode = w ? w->dev->mode : FX_KEEP_ALL;
+    dev.count_bases = mode != FX_KEEP_ALL;
     const u64 S = std::max<u64>(64, ctx->opt_u64("BAM_SEGMENT_BYTES", (u64)256 << 10));
     u64 n_rec = 0, name_bytes = 0;
     const char *refused = nullptr;
@@ -88,6 +99,12 @@ static int bam_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R, FxWinScan *w) 
     R->fmt = FX_FMT_BAM;                                                // (a refused file leaves no read set, so no format either)
     if (!n_rec) return LRGE_OK;                                         // the header ends the text, or the window has no whole record yet
     if (name_bytes >> 32) return fx_verdict_rc(ctx, FX_UNPROVEN, "4 GiB of identifiers or more");
+    if (mode != FX_KEEP_ALL) {
+        const u64 n_use = w->end ? R->n_text : w->cut;
+        int src;
+        if (w->dev->map && (src = w->dev->seek_window(sc, R, n_rec, n_use))) return src;
+        return w->dev->keep_window(sc, R, dev.d_seq_len, dev.d_name_len, n_rec, n_use, dev.bases);
+    }
     const int rc = fx_tables_to_host(ctx, R, sc, n_rec, dev.d_seq_len, dev.d_name_len, name_bytes);
     if (rc || !w) return rc;
     return w->dev->store_window(sc, *R, dev.d_seq_len, R->n_text);

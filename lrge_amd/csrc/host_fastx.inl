@@ -175,12 +175,16 @@ struct FxWinDev {
     }
     u64 len() const { return blk->keep_len; }
     int unproven(const char *what) { scan_refused = true; LRGE_SET_ERR(ctx, "reads_open: not proven on the device (%s)", what); return LRGE_ERR_UNPROVEN; }
-    // the census and the selected open take FASTA / FASTQ, whatever flags came with the call: the sniff of the text's first bytes
+    // the census and the selected open take FASTA / FASTQ, whatever flags came with the call: the sniff of the text's first bytes.
+    // With LRGE_GPU_INGEST_SELECT_ALN beside LRGE_GPU_INGEST_BAM the magic of BAM makes the run a BAM run, through
+    // the windows whatever LRGE_GPU_INGEST_WINDOWED / _WINDOWED_ALN say, as FASTA / FASTQ text is
+    bool select_aln() const { return (flags & LRGE_GPU_INGEST_BAM) && (flags & LRGE_GPU_INGEST_SELECT_ALN); }
     int selected_format() {
-        if (mapped) return LRGE_OK;             // (a run may start with a read named HD.., SQ.. or RG..: fx_win_census)
+        if (mapped) return LRGE_OK;             // (a run may start with a read named HD.., SQ.. or RG..: fx_win_census; the kind is the map's)
         u8 head[4] = {0, 0, 0, 0};
         const u64 n = blk->keep_len;
         if (n) { HIPCHK(ctx, hipMemcpyAsync(head, blk->keep, (size_t)std::min<u64>(4, n), hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); }
+        if (select_aln() && fx_sniff(LRGE_GPU_INGEST_BAM, head, n) == FX_FMT_BAM) { kind = FX_FMT_BAM; return LRGE_OK; }
         if (fx_sniff(LRGE_GPU_INGEST_BAM | LRGE_GPU_INGEST_SAM, head, n) == FX_FMT_EMPTY && !(n >= 4 && !memcmp(head, "CRAM", 4))) return LRGE_OK;
         ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only";
         return LRGE_ERR_UNPROVEN;
@@ -239,7 +243,7 @@ struct FxWinDev {
         blk->keep_max = cap > store.keep_cap ? cap - store.keep_cap : 0;
         return LRGE_OK;
     }
-    // A window of a census that leaves a seek map, behind k_fx_records: k_fx_seek finds the first record start of every cell of the
+    // A window of a census that leaves a seek map, behind k_fx_records or k_bam_records: k_fx_seek finds the first record start of every cell of the
     // window's prefix [0, n_use), the slots (record index and window offset, 8 bytes a cell) come down in one copy, and the point
     // rule of fx_seek.h takes those that hold a record.  The window's records are R->sel.seen onwards, its bytes `through` onwards
     int seek_window(Scratch &sc, const lrge_hip_reads *W, u64 n_rec, u64 n_use) {
@@ -247,7 +251,8 @@ struct FxWinDev {
         const u64 S = map->stride, cell0 = through / S, n_cells = (through + n_use - 1) / S - cell0 + 1;
         ALLOC_OR_FAIL(d_slot, sc, u32, 2 * n_cells);
         HIPCHK(ctx, hipMemsetAsync(d_slot, 0xFF, (size_t)n_cells * 8, ctx->stream));
-        hipLaunchKernelGGL(k_fx_seek, dim3((u32)div_up(n_rec, FX_THREADS)), dim3(FX_THREADS), 0, ctx->stream, (const FxRec *)W->d_recs, n_rec, through, S, cell0, n_cells, d_slot);
+        hipLaunchKernelGGL(k_fx_seek, dim3((u32)div_up(n_rec, FX_THREADS)), dim3(FX_THREADS), 0, ctx->stream, (const FxRec *)W->d_recs, n_rec, through, S, cell0, n_cells,
+                           kind == FX_FMT_BAM ? FX_LEAD_BAM : FX_LEAD_TEXT, d_slot);
         KCHK(ctx);
         std::vector<u32> slot((size_t)n_cells * 2);
         HIPCHK(ctx, hipMemcpyAsync(slot.data(), d_slot, (size_t)n_cells * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -259,7 +264,9 @@ struct FxWinDev {
     // A window of a run that does not keep all (FX_KEEP_NONE, FX_KEEP_SEL), behind k_fx_records: W.d_recs and the lengths of its
     // n_rec records are on the device, `bases` is their sum.  The slice of the selection that falls into the window is found
     // here; a window without a chosen record costs nothing more.  Else k_fx_pick gathers the chosen lengths, which come down and
-    // are scanned, and k_fx_keep copies identifiers and bases.  W leaves as a window of the chosen records only
+    // are scanned, and k_fx_keep copies identifiers and bases.  W leaves as a window of the chosen records only.  A BAM run
+    // (behind k_bam_records): the store takes the packed bytes, so k_bam_spans turns the picked lengths into the spans that are
+    // scanned, and k_bam_keep copies; bases_kept still counts bases
     int keep_window(Scratch &sc, lrge_hip_reads *W, const u32 *d_seq_len, const u32 *d_name_len, u64 n_rec, u64 n_use, u64 bases) {
         W->sel = FxSelStats{n_rec, 0, bases, 0};
         W->n = 0;
@@ -278,22 +285,37 @@ struct FxWinDev {
         HIPCHK(ctx, hipMemcpyAsync(name_len.data(), d_pick_name, (size_t)m * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(ctx, hipStreamSynchronize(st));
         W->name_off.assign(1, 0);
-        u64 sum = 0, name_bytes = 0;
-        for (u64 j = 0; j < m; ++j) { sum += W->seq_len[j]; name_bytes += name_len[j]; W->name_off.push_back(name_bytes); }
-        if (sum > bases || sum >> 32 || name_bytes >> 32) return fx_verdict_rc(ctx, FX_UNPROVEN, "a window of 2^32 bytes or more");      // (never: the window is below that)
+        const bool packed = kind == FX_FMT_BAM;
+        u64 sum = 0, kept = 0, name_bytes = 0;                     // sum: the bytes the store takes
+        for (u64 j = 0; j < m; ++j) {
+            const u64 l = W->seq_len[j];
+            kept += l; sum += packed ? (l + 1) / 2 : l; name_bytes += name_len[j]; W->name_off.push_back(name_bytes);
+        }
+        if (kept > bases || sum >> 32 || name_bytes >> 32) return fx_verdict_rc(ctx, FX_UNPROVEN, "a window of 2^32 bytes or more");      // (never: the window is below that)
         if ((rc = store_room(sum))) return rc;
         ALLOC_OR_FAIL(d_dst, sc, u32, m);
         ALLOC_OR_FAIL(d_name_dst, sc, u32, m);
         ALLOC_OR_FAIL(d_names, sc, u8, std::max<u64>(1, name_bytes));
-        if ((rc = scan_exclusive_u32(ctx, sc, d_pick_seq, d_dst, m, nullptr)) || (rc = scan_exclusive_u32(ctx, sc, d_pick_name, d_name_dst, m, nullptr))) return rc;
-        hipLaunchKernelGGL(k_fx_keep, dim3((u32)std::min<u64>(m, (u64)ctx->n_cu * 32)), dim3(64), 0, st, (const u8 *)W->d_text, n_use, (const FxRec *)W->d_recs, (const u32 *)(d_sel + a), (u32)r0,
-                           m, (const u32 *)d_dst, (const u32 *)d_name_dst, store.keep + store.keep_len, d_names);
+        const u32 *d_span = d_pick_seq;
+        if (packed) {
+            hipLaunchKernelGGL(k_bam_spans, dim3((u32)div_up(m, 256)), dim3(256), 0, st, (const u32 *)d_pick_seq, m, d_dst);
+            KCHK(ctx);
+            d_span = d_dst;                                        // (the scan runs in place, as store_window's does)
+        }
+        if ((rc = scan_exclusive_u32(ctx, sc, d_span, d_dst, m, nullptr)) || (rc = scan_exclusive_u32(ctx, sc, d_pick_name, d_name_dst, m, nullptr))) return rc;
+        const dim3 grid((u32)std::min<u64>(m, (u64)ctx->n_cu * 32));
+        if (packed)
+            hipLaunchKernelGGL(k_bam_keep, grid, dim3(64), 0, st, (const u8 *)W->d_text, (const FxRec *)W->d_recs, (const u32 *)(d_sel + a), (u32)r0, m, (const u32 *)d_dst,
+                               (const u32 *)d_name_dst, store.keep + store.keep_len, d_names);
+        else
+            hipLaunchKernelGGL(k_fx_keep, grid, dim3(64), 0, st, (const u8 *)W->d_text, n_use, (const FxRec *)W->d_recs, (const u32 *)(d_sel + a), (u32)r0,
+                               m, (const u32 *)d_dst, (const u32 *)d_name_dst, store.keep + store.keep_len, d_names);
         KCHK(ctx);
         W->names.resize((size_t)name_bytes);
         if (name_bytes) HIPCHK(ctx, hipMemcpyAsync(&W->names[0], d_names, (size_t)name_bytes, hipMemcpyDeviceToHost, st));
         HIPCHK(ctx, hipStreamSynchronize(st));                     // (also: the scratch and the table go back to the pool, which other streams draw from)
         store.keep_len += sum;
-        W->n = m; W->sel.kept = m; W->sel.bases_kept = sum;
+        W->n = m; W->sel.kept = m; W->sel.bases_kept = kept;
         W->ms[2] = (float)(fx_now_ms() - t0);
         return LRGE_OK;
     }
@@ -1058,6 +1080,8 @@ static int fx_open_mapped(lrge_hip_ctx *ctx, FxInput &in, int flags, const lrge_
         ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only, not Zstandard input";
         return LRGE_ERR_UNPROVEN;
     }
+    const bool aln = (flags & LRGE_GPU_INGEST_BAM) && (flags & LRGE_GPU_INGEST_SELECT_ALN);
+    if (m.fmt == FX_FMT_BAM && !aln) { ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only"; return LRGE_ERR_UNPROVEN; }      // (a BAM map: DESIGN section 25)
     const bool gz = b(0) == 0x1f && b(1) == 0x8b, packed = gz || (b(0) == 0x42 && b(1) == 0x5a) || (b(0) == 0x28 && b(1) == 0xb5 && b(2) == 0x2f && b(3) == 0xfd) ||
                                                    (b(0) == 0xfd && b(1) == 0x37 && b(2) == 0x7a && b(3) == 0x58 && b(4) == 0x5a);
     std::vector<BgzfBlock> t;
@@ -1089,6 +1113,7 @@ static int fx_open_mapped(lrge_hip_ctx *ctx, FxInput &in, int flags, const lrge_
     R->ctx = ctx;
     FxSink s(ctx, R, flags, FX_KEEP_SEL);
     s.run->dev.mapped = true;
+    if (m.fmt == FX_FMT_BAM) s.run->dev.kind = FX_FMT_BAM;       // (the sub-text is never sniffed: it is a record stream without a header)
     int rc = s.run->dev.select(FX_KEEP_SEL, plan.sel.data(), k);
     if (rc) return rc;
     s.run->attach(&s.blk);

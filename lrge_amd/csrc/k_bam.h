@@ -12,6 +12,7 @@
 //                  FxRec, seq_len, name_len; verdict bits and identifier bytes as k_fx_records leaves them (k_fx_names follows)
 //   k_bam_gather   one wavefront per selected read: packed 4-bit codes -> ASCII in aligned words, 8 bases per lane and step
 //   k_bam_spans, k_bam_store   windowed ingest: the packed bytes of a window's records into the base store
+//   k_bam_keep     sampled ingest: identifier and packed bytes of a window's chosen records, by k_bam_store's body
 // A walker takes the 24 bytes of a record's fixed fields and nothing else of it; lanes of one wavefront walk different segments,
 // and a short list is spread over the workgroups (walker i is lane i / gridDim.x of workgroup i % gridDim.x), so that few
 // segments still use many CUs.  The text buffer has FX_PAD bytes behind its end (k_fastx.h): the gather's word behind an
@@ -113,41 +114,59 @@ __global__ __launch_bounds__(256) void k_bam_spans(const u32 *__restrict__ seq_l
     if (r < n_rec) span[r] = (u32)(((u64)seq_len[r] + 1) >> 1);
 }
 
-// Record r's seq_span packed bytes to store[dst[r], dst[r] + seq_span), one wavefront per record, grid-strided; every record
-// starts on a byte and the pad nibble of an odd length is copied as it is, so k_bam_gather reads the store as it reads the
-// text.  A plain byte copy between two buffers whose alignments differ: single bytes up to the first 16-byte boundary of the
+// The copy body of k_bam_store and k_bam_keep, one wavefront: `len` bytes from s to d.
+// A plain byte copy between two buffers whose alignments differ: single bytes up to the first 16-byte boundary of the
 // destination, then 16 bytes per lane and step -- five aligned source words funnel-shifted into four (four when source and
 // destination agree modulo 4, which is uniform over the record) and one 16-byte store, so a wavefront moves 1 KiB a step and a
 // HiFi record of 5-10 KB is a handful of steps -- then single bytes behind the last whole group.  The word behind an
 // unaligned source word may lie up to 3 bytes behind the record: inside the block, or in the FX_PAD bytes behind it.
+__device__ __forceinline__ void bam_copy_packed(const u8 *__restrict__ s, u8 *__restrict__ d, u64 len, u32 lane) {
+    u64 head = (16 - ((uintptr_t)d & 15)) & 15;
+    if (head > len) head = len;
+    if (lane < head) d[lane] = s[lane];
+    const u64 ng = (len - head) >> 4;
+    const u32 mis = (u32)((uintptr_t)(s + head) & 3), sh = mis * 8;
+    const u32 *q0 = reinterpret_cast<const u32 *>(s + head - mis);        // (pointer arithmetic: the loads stay global)
+    uint4 *dq = reinterpret_cast<uint4 *>(d + head);
+    if (sh == 0) {
+        for (u64 g = lane; g < ng; g += 64) {
+            const u32 *q = q0 + 4 * g;
+            dq[g] = make_uint4(q[0], q[1], q[2], q[3]);
+        }
+    } else {
+        for (u64 g = lane; g < ng; g += 64) {
+            const u32 *q = q0 + 4 * g;
+            const u32 a = q[0], b = q[1], c = q[2], e = q[3], f = q[4];
+            dq[g] = make_uint4((a >> sh) | (b << (32 - sh)), (b >> sh) | (c << (32 - sh)), (c >> sh) | (e << (32 - sh)), (e >> sh) | (f << (32 - sh)));
+        }
+    }
+    const u64 i = head + 16 * ng + lane;
+    if (i < len) d[i] = s[i];
+}
+
+// Record r's seq_span packed bytes to store[dst[r], dst[r] + seq_span), one wavefront per record, grid-strided; every record
+// starts on a byte and the pad nibble of an odd length is copied as it is, so k_bam_gather reads the store as it reads the
+// text.  The copy is bam_copy_packed.
 // No LDS, no scratch; the launch is k_fx_store's (a wavefront per workgroup, 32 workgroups a CU: 8 a SIMD, full occupancy
 // for a copy whose only cost is the latency of its loads).
 __global__ __launch_bounds__(64) void k_bam_store(const u8 *__restrict__ t, const FxRec *__restrict__ recs, const u32 *__restrict__ dst, u64 n_rec, u8 *__restrict__ store) {
     const u32 lane = threadIdx.x;
-    for (u64 r = blockIdx.x; r < n_rec; r += gridDim.x) {
-        const u8 *s = t + recs[r].seq_off;
-        u8 *d = store + dst[r];
-        const u64 len = recs[r].seq_span;
-        u64 head = (16 - ((uintptr_t)d & 15)) & 15;
-        if (head > len) head = len;
-        if (lane < head) d[lane] = s[lane];
-        const u64 ng = (len - head) >> 4;
-        const u32 mis = (u32)((uintptr_t)(s + head) & 3), sh = mis * 8;
-        const u32 *q0 = reinterpret_cast<const u32 *>(s + head - mis);        // (pointer arithmetic: the loads stay global)
-        uint4 *dq = reinterpret_cast<uint4 *>(d + head);
-        if (sh == 0) {
-            for (u64 g = lane; g < ng; g += 64) {
-                const u32 *q = q0 + 4 * g;
-                dq[g] = make_uint4(q[0], q[1], q[2], q[3]);
-            }
-        } else {
-            for (u64 g = lane; g < ng; g += 64) {
-                const u32 *q = q0 + 4 * g;
-                const u32 a = q[0], b = q[1], c = q[2], e = q[3], f = q[4];
-                dq[g] = make_uint4((a >> sh) | (b << (32 - sh)), (b >> sh) | (c << (32 - sh)), (c >> sh) | (e << (32 - sh)), (e >> sh) | (f << (32 - sh)));
-            }
-        }
-        const u64 i = head + 16 * ng + lane;
-        if (i < len) d[i] = s[i];
+    for (u64 r = blockIdx.x; r < n_rec; r += gridDim.x) bam_copy_packed(t + recs[r].seq_off, store + dst[r], recs[r].seq_span, lane);
+}
+
+// ---- sampled ingest (fx_window.h FX_KEEP_SEL) ----
+// Chosen record j of the window (sel[j] - r0 in its table), one wavefront each, grid-strided: its identifier's name_len bytes as they
+// are (NULs kept; `*` has length 0 already) to names[name_dst[j], ..), its seq_span packed bytes to store[dst[j], ..) by
+// bam_copy_packed.  dst: the exclusive scan of the chosen spans (k_fx_pick, k_bam_spans), name_dst: that of the chosen identifier
+// lengths; `store` and `names` point behind what the earlier windows kept.  No LDS, no scratch; the launch is k_fx_keep's.
+__global__ __launch_bounds__(64) void k_bam_keep(const u8 *__restrict__ t, const FxRec *__restrict__ recs, const u32 *__restrict__ sel, u32 r0, u64 n_sel,
+                                                 const u32 *__restrict__ dst, const u32 *__restrict__ name_dst, u8 *__restrict__ store, u8 *__restrict__ names) {
+    const u32 lane = threadIdx.x;
+    for (u64 j = blockIdx.x; j < n_sel; j += gridDim.x) {
+        const FxRec rec = recs[sel[j] - r0];
+        const u8 *s = t + rec.name_off;
+        u8 *d = names + name_dst[j];
+        for (u32 i = lane; i < rec.name_len; i += 64) d[i] = s[i];
+        bam_copy_packed(t + rec.seq_off, store + dst[j], rec.seq_span, lane);
     }
 }

@@ -23,6 +23,7 @@
 #include "internal.h"
 #include "k_prims.h"
 #include "fastx_core.h"
+#include "fx_seek.h"
 
 #define FX_THREADS 256
 #define FX_PAD 64u
@@ -280,17 +281,18 @@ __global__ __launch_bounds__(64) void k_fx_keep(const u8 *__restrict__ t, u64 n,
     }
 }
 
-// The seek map of a census (fx_seek.h), behind k_fx_records: one lane per record of the window's proven prefix.
-// Record r starts at window offset recs[r].name_off - 1, the '>' or '@' of its header line, which is text offset `through` + that.
+// The seek map of a census (fx_seek.h), behind k_fx_records or k_bam_records: one lane per record of the window's
+// proven prefix.  Record r starts at window offset fx_rec_start(recs[r].name_off, lead) -- the '>' or '@' of its header line (lead 1),
+// the block_size field of a BAM record (lead 36) --, which is text offset `through` + that.
 // A record whose cell (text offset / stride) differs from its predecessor's is the first that starts in its cell: its index goes
 // to slot[cell - cell0] and its window offset to slot[n_cells + cell - cell0] (preset to FX_SEEK_NONE); record 0 always writes.
 // cell0: the cell of the window's first byte; every record lies in [cell0, cell0 + n_cells).
-__global__ __launch_bounds__(FX_THREADS) void k_fx_seek(const FxRec *__restrict__ recs, u64 n_rec, u64 through, u64 stride, u64 cell0, u64 n_cells,
+__global__ __launch_bounds__(FX_THREADS) void k_fx_seek(const FxRec *__restrict__ recs, u64 n_rec, u64 through, u64 stride, u64 cell0, u64 n_cells, u32 lead,
                                                         u32 *__restrict__ slot) {
     const u64 r = (u64)blockIdx.x * FX_THREADS + threadIdx.x;
     if (r >= n_rec) return;
-    const u64 at = recs[r].name_off - 1, cell = (through + at) / stride;
-    if (r && (through + recs[r - 1].name_off - 1) / stride == cell) return;
+    const u64 at = fx_rec_start(recs[r].name_off, lead), cell = (through + at) / stride;
+    if (r && (through + fx_rec_start(recs[r - 1].name_off, lead)) / stride == cell) return;
     const u64 c = cell - cell0;
     if (c >= n_cells) return;                               // (never: the prefix ends inside the last cell)
     slot[c] = (u32)r; slot[n_cells + c] = (u32)at;

@@ -44,6 +44,7 @@ template <class Scan> struct WinTwin {
     const uint32_t *sel = nullptr;
     uint64_t k = 0, at = 0;
     FxSeekMap *map = nullptr;           // a census that leaves a seek map (fx_seek.h): every window's records go through the point rule
+    uint32_t lead = FX_LEAD_TEXT;       // where a record starts in front of its identifier (fx_rec_start): FX_LEAD_BAM for a BAM twin
     WinTwin(Scan &s, WinTwinOut &o) : scan(s), out(o) {}
     void keep(const FxRec &r, uint64_t cut) {
         const uint64_t a = out.store.size();
@@ -66,7 +67,7 @@ template <class Scan> struct WinTwin {
         const uint64_t r0 = out.sel.seen, n_rec = recs.size();
         if ((r0 + n_rec) >> 32) return (int)FX_UNPROVEN;
         const uint64_t b = mode == FX_KEEP_SEL ? fx_sel_slice(sel, k, at, r0, n_rec) : at;
-        if (map) for (uint64_t i = 0; i < n_rec; ++i) fx_seek_add(*map, r0 + i, base + recs[i].name_off - 1);
+        if (map) for (uint64_t i = 0; i < n_rec; ++i) fx_seek_add(*map, r0 + i, base + fx_rec_start(recs[i].name_off, lead));
         for (const FxRec &r : recs) out.sel.bases_seen += r.seq_len;
         for (; at < b; ++at) {
             const FxRec &r = recs[sel[at] - r0];
@@ -87,14 +88,15 @@ template <class Scan> struct WinTwin {
 // a text that ends before its first flush is scanned whole, as without windows (resident_bases: its bases count in the stats all
 // the same).  0 with `out` filled, or the verdict with `out` empty
 // mode, sel, k: what the run keeps (fx_window.h FxKeepMode); WIN_TWIN_INVALID: sel is not strictly ascending, or holds an ordinal
-// at or above the records the run saw.  map: a census (FX_KEEP_NONE) fills the points of a seek map (fx_seek.h; stride set by the caller)
+// at or above the records the run saw.  map: a census (FX_KEEP_NONE) fills the points of a seek map (fx_seek.h; stride set by the caller),
+// a record starting `lead` bytes in front of its identifier
 #define WIN_TWIN_INVALID (-2)
 template <class Scan> int win_twin_run(Scan &scan, const uint8_t *t, uint64_t n, uint64_t window, uint64_t piece, bool resident_bases, WinTwinOut &out,
-                                       FxKeepMode mode = FX_KEEP_ALL, const uint32_t *sel = nullptr, uint64_t k = 0, FxSeekMap *map = nullptr) {
+                                       FxKeepMode mode = FX_KEEP_ALL, const uint32_t *sel = nullptr, uint64_t k = 0, FxSeekMap *map = nullptr, uint32_t lead = FX_LEAD_TEXT) {
     out = WinTwinOut();
     if (mode == FX_KEEP_SEL && ((k && !sel) || !fx_sel_ascending(sel, k))) return WIN_TWIN_INVALID;
     WinTwin<Scan> b(scan, out);
-    b.mode = mode; b.sel = sel; b.k = k; b.map = map;
+    b.mode = mode; b.sel = sel; b.k = k; b.map = map; b.lead = lead;
     FxWindow<WinTwin<Scan>> win(b, window);
     int rc = 0;
     for (uint64_t p = 0; p < n && !rc; p += piece) {
@@ -102,10 +104,63 @@ template <class Scan> int win_twin_run(Scan &scan, const uint8_t *t, uint64_t n,
         rc = win.step(false);
     }
     uint64_t all = 0;
-    if (!rc) rc = win.st.windows ? win.step(true) : b.flush(true, true, &all, &win.fmt);         // (or the resident scan)
+    // (or the resident scan; `first` is the driver's word: the scan of a mapped sub-text clears it itself, as in every window)
+    if (!rc) rc = win.st.windows ? win.step(true) : b.flush(true, true, &all, &win.fmt);
     if (!rc && mode == FX_KEEP_SEL && b.at < k) rc = WIN_TWIN_INVALID;
     if (rc) { out = WinTwinOut(); return rc; }
     out.st = win.st; out.st.bases = win.st.windows || resident_bases ? out.store.size() : 0;
     out.fmt = win.fmt;
     return 0;
+}
+
+// ---- the seek map of a twin (fx_seek.h), once for the twins that have one (fastx_twin.cpp, bam_twin.cpp) ----
+// the selection against map m: 0, or WIN_TWIN_INVALID for one that is not ascending or reaches the map's records
+static inline int win_twin_sel_fits(const FxSeekMap &m, const uint32_t *sel, uint64_t k) {
+    if ((k && !sel) || !fx_sel_ascending(sel, k)) return WIN_TWIN_INVALID;
+    for (uint64_t j = 0; j < k; ++j) if (sel[j] >= m.records) return WIN_TWIN_INVALID;
+    return 0;
+}
+
+// The plan of selection sel[0, k) on map gm.  n_blk == 0: for the plain text.  Else for the same text in BGZF blocks of member
+// lengths c_len and text sizes isize (a file of file_len bytes): the block fields are attached as the device attaches them.
+// out = {runs, text bytes brought, file bytes read, blocks decoded}
+static inline int win_twin_seek_plan(const FxSeekMap &gm, const uint32_t *c_len, const uint32_t *isize, uint64_t n_blk, uint64_t file_len, const uint32_t *sel, uint64_t k,
+                                     FxSeekPlan *gp, uint64_t out[4]) {
+    *gp = FxSeekPlan();
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (win_twin_sel_fits(gm, sel, k)) return WIN_TWIN_INVALID;
+    FxSeekMap m = gm;
+    if (n_blk) {
+        std::vector<BgzfBlock> t(n_blk);
+        uint64_t c = 0, o = 0;
+        for (uint64_t i = 0; i < n_blk; ++i) { t[i] = BgzfBlock{c, o, 0, 0, c_len[i], isize[i], 0}; c += c_len[i]; o += isize[i]; }
+        if (o != m.text_bytes || c != file_len) return WIN_TWIN_INVALID;
+        m.kind = FX_SEEK_BGZF; m.n_blocks = n_blk; m.file_len = file_len;
+        fx_seek_attach(m, t.data(), n_blk);
+    }
+    fx_seek_plan(m, sel, k, gp);
+    out[0] = gp->runs.size(); out[1] = gp->text_bytes; out[2] = gp->file_bytes; out[3] = gp->blocks;
+    return 0;
+}
+
+static inline uint64_t win_twin_plan_runs(const FxSeekPlan &gp, uint64_t *out, uint64_t cap) {
+    for (uint64_t i = 0; i < gp.runs.size() && i < cap; ++i) { out[4 * i] = gp.runs[i].ord0; out[4 * i + 1] = gp.runs[i].n_rec; out[4 * i + 2] = gp.runs[i].t0; out[4 * i + 3] = gp.runs[i].t1; }
+    return gp.runs.size();
+}
+
+// the sub-text of plan gp over text t, and -- behind the selecting run over it -- the records' name_off translated back into the
+// whole text, the select stats' seen / bases_seen the map's
+static inline std::vector<uint8_t> win_twin_sub_text(const FxSeekPlan &gp, const uint8_t *t) {
+    std::vector<uint8_t> sub;
+    for (const FxSeekRun &r : gp.runs) sub.insert(sub.end(), t + r.t0, t + r.t1);
+    return sub;
+}
+static inline void win_twin_mapped_back(WinTwinOut &gw, const FxSeekPlan &gp, const FxSeekMap &gm) {
+    size_t ri = 0;
+    uint64_t before = 0;                // sub-text bytes in front of run ri
+    for (FxRec &r : gw.recs) {
+        while (r.name_off >= before + (gp.runs[ri].t1 - gp.runs[ri].t0)) { before += gp.runs[ri].t1 - gp.runs[ri].t0; ++ri; }
+        r.name_off = r.name_off - before + gp.runs[ri].t0;
+    }
+    gw.sel.seen = gm.records; gw.sel.bases_seen = gm.bases;
 }

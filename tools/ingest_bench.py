@@ -7,7 +7,7 @@ the files of the kinds asked for are written.  Usage:
   python tools/ingest_bench.py [--gbases 1.08] [--dir /tmp] [--reps 5] [--kinds fq,bgzf.fq.gz,fq.gz,bam,sam]
                                [--bam-segments 262144,1048576,4194304] [--out profiles/ingest_bench.json]
                                [--windowed [--window-mb 64[,1024]]] [--sampled K [--window-mb 64]] [--sampled K1,K2,.. --seek]
---sampled K1,K2,.. --seek: on the plain and the BGZF FASTQ file, for every K, the census without and with a seek map
+--sampled K1,K2,.. --seek: on the plain and the BGZF FASTQ file and on the uBAM (kind bam: LRGE_GPU_INGEST_SELECT_ALN), for every K, the census without and with a seek map
 (lrge_hip_reads_census, lrge_hip_reads_census_map), the selected open and the mapped open of the same K seeded ordinals
 (lrge_hip_reads_open_selected, lrge_hip_reads_open_mapped) and the existing windowed open, all alternating in one run; with the
 bytes the mapped open brought and read, under the key "sampled_seek" / "<K>" of --out.
@@ -365,7 +365,7 @@ def seek_runs(a, ctx, H, HK, kinds, paths, text_bytes, ks):
                 if sel is None:
                     sel = np.sort(np.random.default_rng(1).choice(nr.value, min(K, nr.value), replace=False)).astype(np.uint32)
                 ms5, cen, mst, sst, sk = (C.c_double * 5)(), (C.c_uint64 * 4)(), (C.c_uint64 * 4)(), (C.c_uint64 * 4)(), (C.c_uint64 * 4)()
-                rc = HK.route_seek(ctx.h, p.encode(), 15, sel.ctypes.data, sel.size, C.byref(ms5), C.byref(cen), C.byref(mst), C.byref(sst), C.byref(sk))
+                rc = HK.route_seek(ctx.h, p.encode(), 15 | (1024 if kind == "bam" else 0), sel.ctypes.data, sel.size, C.byref(ms5), C.byref(cen), C.byref(mst), C.byref(sst), C.byref(sk))
                 assert rc == 0, (kind, rc, ctx._lib.lrge_hip_last_error(ctx.h))
                 assert (cen[0], cen[1], cen[2]) == (nr.value, nb.value, text_bytes[kind]) and (sst[0], sst[1], sst[2]) == (nr.value, sel.size, nb.value), (list(cen), list(sst))
                 seen = dict(reads=nr.value, bases=nb.value, kept_bases=sst[3], points=mst[1], stride=mst[2], runs=sk[0], text_bytes_brought=sk[1], file_bytes_read=sk[2], blocks_decoded=sk[3])
@@ -427,7 +427,7 @@ def main():
         HK = C.CDLL(extra[1])
         HK.route_seek.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(C.c_double * 5)] + [C.POINTER(C.c_uint64 * 4)] * 4
         a.window_mb = int(a.window_mb.split(",")[0])
-        seek_runs(a, ctx, H, HK, [k for k in kinds if k in ("fq", "bgzf.fq.gz")], paths, text_bytes, seek_ks)
+        seek_runs(a, ctx, H, HK, [k for k in kinds if k in ("fq", "bgzf.fq.gz", "bam")], paths, text_bytes, seek_ks)
         ctx.close()
         for p in list(paths.values()) + [src, so] + extra:
             os.remove(p)
