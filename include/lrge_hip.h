@@ -553,7 +553,7 @@ int  lrge_hip_xz_inflate(lrge_hip_ctx *ctx, const void *comp, uint64_t comp_len,
    records are those of the resident scan and of lrge_hip_read_records, or the call is LRGE_ERR_UNPROVEN (a window the scan does
    not prove, a window of another format than the first, a window of 2^32 bytes or more, 2^32 records or 4 GiB of identifiers in
    all); for text that is not well formed (empty
-   lines between records) the verdict may depend on the window.  Text within one window, BAM and SAM stay resident as without the flag; so does Zstandard text of any size (a known limit: its matches need the earlier text).
+   lines between records) the verdict may depend on the window.  Text within one window, BAM and SAM stay resident as without the flag; so does Zstandard text of any size without LRGE_GPU_INGEST_WINDOWED_ZSTD (below).
    | LRGE_GPU_INGEST_WINDOWED_ALN (k_bam_spans, k_bam_store; effective only beside LRGE_GPU_INGEST_WINDOWED and the
    format's own flag): unaligned BAM and SAM above INGEST_WINDOW_BYTES pass through in windows too.  A BAM window is cut at the
    first record start of the chain proven from its front that the block does not hold whole, a SAM window directly behind its
@@ -621,7 +621,7 @@ void     lrge_hip_reads_free(lrge_hip_reads *reads);
    strictly ascending; an ordinal at or above the number of records the pass saw (the message names the ordinal and the count).
    LRGE_ERR_UNPROVEN for both, whatever the flags: text whose first bytes say BAM, SAM or CRAM ("selected ingest takes FASTA /
    FASTQ only"; BAM is taken with LRGE_GPU_INGEST_SELECT_ALN beside LRGE_GPU_INGEST_BAM, below), Zstandard input (its text is never
-   windowed); everything else as lrge_hip_reads_open*.
+   windowed without LRGE_GPU_INGEST_WINDOWED_ZSTD, below); everything else as lrge_hip_reads_open*.
    lrge_hip_reads_select_stats: out[0] records seen, out[1] records kept, out[2] sequence bases seen, out[3] bases kept by the
    pass that made the handle; zeros for a handle of lrge_hip_reads_open*. */
 int      lrge_hip_reads_census(lrge_hip_ctx *ctx, const char *path, int flags, uint64_t out[4]);
@@ -681,6 +681,22 @@ int      lrge_hip_reads_seek_stats(const lrge_hip_reads *reads, uint64_t out[4])
    count store bytes.  A point of the seek map is a record's block_size field, the first point record 0 behind the header; a mapped
    open of a BAM map without both flags is refused as the census is. */
 #define LRGE_GPU_INGEST_SELECT_ALN 1024
+
+/* The windowed and the sampled ingest of Zstandard (k_zs_xxh64_part, k_zs_slide): a match reaches back at most
+   Window_Size bytes, so the decoder needs no more of the earlier text than the last min(frame bytes so far, window) bytes of the
+   frame that is open when a round starts.
+   | LRGE_GPU_INGEST_WINDOWED_ZSTD (opt-in; it has effect only beside LRGE_GPU_INFLATE_ZSTD; without it every call does what it did,
+   the refusal texts included): lrge_hip_reads_open* | LRGE_GPU_INGEST_WINDOWED passes Zstandard text above INGEST_WINDOW_BYTES
+   through the windows as gzip, bzip2 and xz text, and lrge_hip_reads_census*, _open_selected*, _census_map* and _open_mapped* take
+   Zstandard input (a map of it runs the full selected pass, as one of gzip, bzip2 or xz).  The rounds are decoded in a work block of
+   history plus one round (option ZSTD_ROUND_BLOCKS; its default then keeps a round's text within INGEST_WINDOW_BYTES), sized once
+   from the block headers; INGEST_MAX_BYTES bounds the store, the window block and that work block together ("text above
+   INGEST_MAX_BYTES" when the work block alone does not fit).  Frames, skippable frames, checksums (a frame that spans rounds is
+   hashed in parts) and refusals are those of the resident route.  Text of 4 GiB or more is not verified.
+   lrge_hip_reads_zstd_stats: out[0] rounds, out[1] the largest history carried into a round, out[2] the largest work text (history
+   plus round), out[3] bytes of history moved; zeros for a handle whose call did not slide. */
+#define LRGE_GPU_INGEST_WINDOWED_ZSTD 2048
+int      lrge_hip_reads_zstd_stats(const lrge_hip_reads *reads, uint64_t out[4]);
 
 /* Read sets built on the device from unaligned CRAM 3.0 / 3.1 (k_rans_decode): | LRGE_GPU_INGEST_CRAM (opt-in:
    no other flag implies it, and without it every call does what it did) sends input that starts with "CRAM" to a host walk of the

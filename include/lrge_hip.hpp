@@ -78,7 +78,8 @@ struct Ctx {
 // The records of one FASTA / FASTQ file (or, with | LRGE_GPU_INGEST_BAM / LRGE_GPU_INGEST_SAM, one unaligned BAM / SAM) parsed on the device;
 // | LRGE_GPU_INGEST_WINDOWED: FASTA / FASTQ text above option INGEST_WINDOW_BYTES passes through in windows and only the bases stay;
 // | LRGE_GPU_INGEST_WINDOWED_ALN beside it and the format's flag: unaligned BAM (its bases kept packed) and SAM as well;
-// | LRGE_GPU_INFLATE_BZIP2, | LRGE_GPU_INFLATE_ZSTD, | LRGE_GPU_INFLATE_XZ: bzip2, Zstandard and xz input decompressed on the device too (Zstandard text is never windowed)
+// | LRGE_GPU_INFLATE_BZIP2, | LRGE_GPU_INFLATE_ZSTD, | LRGE_GPU_INFLATE_XZ: bzip2, Zstandard and xz input decompressed on the device too (Zstandard text is never windowed without the next flag)
+// | LRGE_GPU_INGEST_WINDOWED_ZSTD (opt-in) beside LRGE_GPU_INFLATE_ZSTD: Zstandard text passes through the windows too, and census / open_selected / census_map / open_mapped take it;
 // | LRGE_GPU_INGEST_SELECT_ALN (opt-in) beside LRGE_GPU_INGEST_BAM: census / open_selected / census_map / open_mapped take unaligned BAM too;
 // | LRGE_GPU_INGEST_CRAM (opt-in, implied by nothing): unaligned CRAM, walked on the host, its base blocks decoded on the device (the flags pass through as given)
 // (lrge_hip_reads_open, io.rs:154-184): identifiers and lengths on
@@ -151,10 +152,12 @@ struct DeviceReads {
         r->tables();
         return r;
     }
+    uint64_t zstd_stats[4] = {0, 0, 0, 0};     // lrge_hip_reads_zstd_stats: rounds, largest history, largest work text, bytes of history moved (zeros: the call did not slide)
     uint64_t seek_stats[4] = {0, 0, 0, 0};     // lrge_hip_reads_seek_stats: runs, text bytes brought, file bytes read, BGZF blocks decoded (open_mapped)
 private:
     void tables() {
         ctx->check(lrge_hip_reads_window_stats(h, window_stats));
+        ctx->check(lrge_hip_reads_zstd_stats(h, zstd_stats));
         const uint64_t n = lrge_hip_reads_count(h);
         std::vector<uint64_t> off(n + 1);
         std::string blob(lrge_hip_reads_name_bytes(h), '\0');

@@ -65,6 +65,7 @@ pub const LRGE_GPU_INGEST_SELECT_ALN: c_int = 1024; // beside LRGE_GPU_INGEST_BA
 pub const LRGE_GPU_INGEST_CRAM: c_int = 512; // lrge_hip_reads_open*: unaligned CRAM, its base blocks decoded on the device (io.rs:93, 154-184); opt-in
 pub const LRGE_GPU_INFLATE_XZ: c_int = 256; // lrge_hip_reads_open* / lrge_hip_read_records_gpu_ex: xz decompressed on the device (io.rs:36-63)
 pub const LRGE_GPU_INFLATE_ZSTD: c_int = 128; // lrge_hip_reads_open* / lrge_hip_read_records_gpu_ex: Zstandard decompressed on the device (io.rs:36-63)
+pub const LRGE_GPU_INGEST_WINDOWED_ZSTD: c_int = 2048; // beside LRGE_GPU_INFLATE_ZSTD: Zstandard text through the windows, and in lrge_hip_reads_census* / _open_selected* / _census_map* / _open_mapped* (io.rs:36-63, 140-145); opt-in
 pub const LRGE_GPU_INFLATE_BZIP2: c_int = 16; // lrge_hip_reads_open* / lrge_hip_read_records_gpu_ex: bzip2 decompressed on the device (io.rs:36-63)
 
 extern "C" {
@@ -74,6 +75,8 @@ extern "C" {
     fn lrge_hip_reads_cram_stats(reads: *const c_void, out: *mut c_void) -> c_int;
     fn lrge_hip_rans_decode(ctx: *mut lrge_hip_ctx, comp: *const c_void, comp_len: u64, streams: *mut c_void, n: u32, out: *mut c_void,
                             out_cap: u64, stats: *mut c_void) -> c_int;
+    // the sliding Zstandard rounds of an opened handle (LRGE_GPU_INGEST_WINDOWED_ZSTD): rounds, largest history, largest work text, bytes moved
+    fn lrge_hip_reads_zstd_stats(reads: *const c_void, out: *mut u64) -> c_int;
     fn lrge_hip_ctx_destroy(ctx: *mut lrge_hip_ctx);
     fn lrge_hip_last_error(ctx: *const lrge_hip_ctx) -> *const c_char;
     fn lrge_hip_seqset_upload(ctx: *mut lrge_hip_ctx, bases: *const c_char, offsets: *const u64, n: u32,

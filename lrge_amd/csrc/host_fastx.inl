@@ -1,7 +1,7 @@
 // host_fastx.inl -- read sets built on the device from FASTA / FASTQ text (k_fastx.h), from unaligned BAM
 // (k_bam.h, host_bam.inl), from unaligned SAM (k_sam.h, host_sam.inl) and, without any text, from
 // unaligned CRAM (k_cram.h, host_cram.inl): the text reaches HBM
-// decompressed (BGZF chunks decoded into one block by the pipeline of host_inflate.inl, the gzip, bzip2 and Zstandard rounds appended device-to-device, plain input copied once), the
+// decompressed (BGZF chunks decoded into one block by the pipeline of host_inflate.inl, the gzip, bzip2, xz and (sliding: DESIGN section 26) Zstandard rounds appended device-to-device, plain input copied once), the
 // record scan runs there, only identifiers and lengths come back, and lrge_hip_seqset_from_reads gathers the selected reads
 // into dense ASCII for the device-source pack of host_seqset.inl.  Whatever the scan cannot prove is LRGE_ERR_UNPROVEN: the
 // caller takes lrge_hip_read_records*, which parses the file or reports it with the reference's messages.  With
@@ -37,6 +37,7 @@ struct lrge_hip_reads {
     FxWinStats win = {0, 0, 0, 0};              // lrge_hip_reads_window_stats
     bool is_cram = false;                       // opened from unaligned CRAM (host_cram.inl): d_text is a base store, as a windowed FASTA handle's
     CramStats cram;                             // lrge_hip_reads_cram_stats
+    uint64_t zs_slide[4] = {0, 0, 0, 0};        // lrge_hip_reads_zstd_stats: the sliding Zstandard rounds of the call (zeros: it did not slide)
     FxSelStats sel = {0, 0, 0, 0};              // lrge_hip_reads_select_stats: the pass of lrge_hip_reads_open_selected* (a window: what it adds)
     u64 seek[4] = {0, 0, 0, 0};                 // lrge_hip_reads_seek_stats: runs, text bytes brought, file bytes read, BGZF blocks decoded (lrge_hip_reads_open_mapped*)
 };
@@ -143,6 +144,7 @@ struct FxWinDev {
     lrge_hip_reads *R;                          // collects the identifiers and lengths of every window
     int flags;
     u64 cap;                                    // INGEST_MAX_BYTES: the block and the store together
+    u64 aside = 0;                              // ... and what a decoder holds beside them under the same cap (the sliding Zstandard work block)
     DevKeep *blk = nullptr;                     // the block the text is appended to (a decoder's own, or one of the call)
     DevKeep store;                              // the bases of the records flushed so far, dense, in file order (BAM: packed, a record starts on a byte)
     int kind = FX_FMT_EMPTY;                    // FX_FMT_BAM / FX_FMT_SAM: the run is that format's, by the sniff of its first bytes; else FASTA / FASTQ
@@ -199,7 +201,7 @@ struct FxWinDev {
         if (mode != FX_KEEP_ALL) return selected_format();
         const int rc = fx_kind(ctx, flags, nullptr, blk->keep, blk->keep_len, &kind);
         if (rc) return rc;
-        if ((*yes = !fx_kind_windowed(flags, kind))) { blk->keep_hint = was_hint; blk->keep_floor = was_floor; blk->keep_grow = was_grow; blk->keep_max = cap; }
+        if ((*yes = !fx_kind_windowed(flags, kind))) { blk->keep_hint = was_hint; blk->keep_floor = was_floor; blk->keep_grow = was_grow; blk->keep_max = cap - aside; }
         return LRGE_OK;
     }
     int flush(bool first, bool end, u64 *cut, int *fmt) {
@@ -233,14 +235,15 @@ struct FxWinDev {
     // room for `sum` more bytes in the store, within the budget it shares with the block
     int store_room(u64 sum) {
         // the store doubles while that leaves the block room to double as well; close to the cap it grows by an eighth
-        const u64 need = store.keep_len + sum, room = cap > blk->keep_cap ? cap - blk->keep_cap : 0, soft = cap > 2 * blk->keep_cap ? cap - 2 * blk->keep_cap : 0;
+        const u64 lim = cap - aside;
+        const u64 need = store.keep_len + sum, room = lim > blk->keep_cap ? lim - blk->keep_cap : 0, soft = lim > 2 * blk->keep_cap ? lim - 2 * blk->keep_cap : 0;
         store.keep_max = need <= soft ? soft : std::min<u64>(room, need + need / 8);
         if (!store.keep_reserve(sum)) {
             if (store.keep_over) { LRGE_SET_ERR(ctx, "reads_open: bases and window above INGEST_MAX_BYTES (%llu)", (unsigned long long)cap); return LRGE_ERR_UNPROVEN; }
             LRGE_SET_ERR(ctx, "reads_open: base store: %s", hipGetErrorString(store.e));
             return LRGE_ERR_DEVICE;
         }
-        blk->keep_max = cap > store.keep_cap ? cap - store.keep_cap : 0;
+        blk->keep_max = lim > store.keep_cap ? lim - store.keep_cap : 0;
         return LRGE_OK;
     }
     // A window of a census that leaves a seek map, behind k_fx_records or k_bam_records: k_fx_seek finds the first record start of every cell of the
@@ -708,16 +711,30 @@ static int fx_src_bzip2(FxSink &s, const u8 *d, u64 len) {
                                 "bzip2", "reads_open: bzip2 data not accepted by the device (%s near file offset %llu)", bz_status_name);
 }
 
-// Zstandard: a match reaches back through the frame's earlier text, so the text is never windowed: with LRGE_GPU_INGEST_WINDOWED too
-// it is taken resident, within INGEST_MAX_BYTES
+// Zstandard: a match reaches back through the frame's earlier text, so the text is never windowed without
+// LRGE_GPU_INGEST_WINDOWED_ZSTD: with LRGE_GPU_INGEST_WINDOWED alone it is taken resident, within INGEST_MAX_BYTES.  With the flag
+// the decoder slides (host_zstd.inl): it keeps the history a round needs in a work block of its own, which comes
+// out of INGEST_MAX_BYTES beside the window block and the store, and every finished round passes through the windows as a gzip
+// round does
+static bool fx_zstd_slides(int flags) { return (flags & LRGE_GPU_INFLATE_ZSTD) && (flags & LRGE_GPU_INGEST_WINDOWED_ZSTD); }
 static int fx_src_zstd(FxSink &s, const u8 *d, u64 len) {
     ZsStats st;
+    ZsSlide sl = {0, 0, 0, 0};
     ZsDev dev(s.ctx);
     dev.to_host = false;
-    s.run.reset();
+    if (!fx_zstd_slides(s.flags)) s.run.reset();
+    if (s.run) {
+        dev.sliding = true; dev.slide_window = s.window;
+        dev.work_budget = [&](u64 bytes) {
+            if (bytes > s.cap) return false;
+            s.run->dev.aside = bytes; dev.keep_max = s.cap - bytes;
+            return true;
+        };
+    }
     const int rc = fx_inflate_to_device(s, dev, [&](u64 *bad) {
-        return zs_run(dev, d, len, s.ctx->opt_u64("ZSTD_ROUND_BLOCKS", 0), zs_checksum_on(s.ctx), [](const uint8_t *, uint64_t) { return true; }, st, bad);
+        return zs_run(dev, d, len, s.ctx->opt_u64("ZSTD_ROUND_BLOCKS", 0), zs_checksum_on(s.ctx), [](const uint8_t *, uint64_t) { return true; }, st, bad, &sl);
     }, "zstd", "reads_open: zstd data not accepted by the device (%s near file offset %llu)", zs_status_name);
+    s.R->zs_slide[0] = sl.rounds; s.R->zs_slide[1] = sl.max_history; s.R->zs_slide[2] = sl.max_work; s.R->zs_slide[3] = sl.moved;
     if (s.ctx->opt("VERBOSE")) fprintf(stderr, "[lrge_hip] reads_open: zstd content checksums %.2f ms of the text-to-HBM share\n", dev.ms[5]);
     return rc;
 }
@@ -805,8 +822,8 @@ static int fx_open_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, 
         map->kind = FX_SEEK_OTHER; map->file_len = len;
         s.run->dev.map = map;
     }
-    if (mode != FX_KEEP_ALL && b(0) == 0x28 && b(1) == 0xb5 && b(2) == 0x2f && b(3) == 0xfd && (flags & LRGE_GPU_INFLATE_ZSTD)) {
-        ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only, not Zstandard input";       // (its text is never windowed)
+    if (mode != FX_KEEP_ALL && b(0) == 0x28 && b(1) == 0xb5 && b(2) == 0x2f && b(3) == 0xfd && (flags & LRGE_GPU_INFLATE_ZSTD) && !fx_zstd_slides(flags)) {
+        ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only, not Zstandard input";       // (its text is never windowed without LRGE_GPU_INGEST_WINDOWED_ZSTD)
         rc = LRGE_ERR_UNPROVEN;
     } else if (b(0) == 0x1f && b(1) == 0x8b) {
         const bool bgzf = bgzf_scan_blocks(d, len, &t, &total);
@@ -1076,7 +1093,7 @@ static int fx_open_mapped(lrge_hip_ctx *ctx, FxInput &in, int flags, const lrge_
     const auto b = [&](u64 i) -> u32 { return i < nh ? h[i] : 0x100u; };
     // what the census and the selected open refuse by name, whatever the map
     if (b(0) == 'C' && b(1) == 'R' && b(2) == 'A' && b(3) == 'M') { ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only"; return LRGE_ERR_UNPROVEN; }
-    if (b(0) == 0x28 && b(1) == 0xb5 && b(2) == 0x2f && b(3) == 0xfd && (flags & LRGE_GPU_INFLATE_ZSTD)) {
+    if (b(0) == 0x28 && b(1) == 0xb5 && b(2) == 0x2f && b(3) == 0xfd && (flags & LRGE_GPU_INFLATE_ZSTD) && !fx_zstd_slides(flags)) {
         ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only, not Zstandard input";
         return LRGE_ERR_UNPROVEN;
     }
@@ -1179,6 +1196,12 @@ extern "C" int lrge_hip_reads_timings(const lrge_hip_reads *r, float ms[4]) {
 extern "C" int lrge_hip_reads_window_stats(const lrge_hip_reads *r, uint64_t out[4]) {
     if (!r || !out) return LRGE_ERR_INVALID;
     out[0] = r->win.windows; out[1] = r->win.bases; out[2] = r->win.max_window; out[3] = r->win.carried;
+    return LRGE_OK;
+}
+
+extern "C" int lrge_hip_reads_zstd_stats(const lrge_hip_reads *r, uint64_t out[4]) {
+    if (!r || !out) return LRGE_ERR_INVALID;
+    memcpy(out, r->zs_slide, sizeof r->zs_slide);
     return LRGE_OK;
 }
 

@@ -7,6 +7,11 @@
 // hold at zs_block_bytes plus the text per block, at most ZS_ROUND_MAX.  Option ZSTD_CHECKSUM (default 1): 0 skips XXH64.  Option
 // ZSTD_TIMING: the stages are separated by synchronisations and their times are printed to stderr when the call ends
 // (tools/zstd_bench.py); the checksum's time is always measured, its launch is followed by the read of its word anyway.
+//
+// The sliding mode (the windowed and the sampled ingest under LRGE_GPU_INGEST_WINDOWED_ZSTD): the rounds are
+// decoded in a work block [history | round] of their own, sized once from the block headers.  A finished round is appended
+// device-to-device to the DevKeep block and flushed through the ingest's windows, as a gzip round is; the history the next round
+// needs moves to the front of the work block.  Everything is ordered on the context's main stream.
 
 static const char *zs_status_name(int s) {
     switch (s) {
@@ -36,12 +41,17 @@ static const char *zs_status_name(int s) {
 
 namespace {
 struct ZsDev : DevKeep {
-    GzBuf in, blocks, hbuf, lit, seq, res, status, org, groups, hash;
+    GzBuf in, blocks, hbuf, lit, seq, res, status, org, groups, hash, work, xstate;
     u64 n = 0;
+    // the sliding mode: work holds work_len bytes, the round behind `hist` bytes of history; retire() left keep_hist bytes to carry
+    bool sliding = false;
+    u64 slide_window = 0;                                        // the ingest's window: a round's text stays below it (default_round)
+    u64 work_text = 0, work_len = 0, hist = 0, keep_hist = 0;
+    std::function<bool(u64)> work_budget;                        // the work block's bytes, taken from the budget the caller shares out (false: above it)
     bool timing = false, to_host = true;
     double ms[6] = {0, 0, 0, 0, 0, 0};                           // heads, literals, sequences, execute, resolve, checksum
     explicit ZsDev(lrge_hip_ctx *c) : DevKeep(c) {
-        for (GzBuf *b : {&in, &blocks, &hbuf, &lit, &seq, &res, &status, &org, &groups, &hash}) b->ctx = c;
+        for (GzBuf *b : {&in, &blocks, &hbuf, &lit, &seq, &res, &status, &org, &groups, &hash, &work, &xstate}) b->ctx = c;
         timing = c->opt("ZSTD_TIMING") != nullptr;
         keep_on = true;
     }
@@ -62,7 +72,46 @@ struct ZsDev : DevKeep {
     uint32_t default_round() {
         size_t mfree = 0, mtot = 0;
         if (hipMemGetInfo(&mfree, &mtot) != hipSuccess) { (void)hipGetLastError(); mfree = 0; }
-        return (uint32_t)std::min<u64>(ZS_ROUND_MAX, std::max<u64>(1, ((u64)mfree + ctx->pool.idle()) / 2 / (zs_block_bytes() + ZS_BLOCK_MAX)));
+        const u64 k = std::min<u64>(ZS_ROUND_MAX, std::max<u64>(1, ((u64)mfree + ctx->pool.idle()) / 2 / (zs_block_bytes() + ZS_BLOCK_MAX)));
+        return (uint32_t)(sliding ? std::min<u64>(k, std::max<u64>(1, slide_window / ZS_BLOCK_MAX)) : k);
+    }
+    bool slides() const { return sliding; }
+    bool plan(uint64_t work_bytes) {
+        const u64 bytes = work_bytes + ZS_PAD;
+        if (work_budget && !work_budget(bytes)) { keep_over = true; return false; }
+        work_text = work_bytes;
+        return work.need((size_t)bytes, &e) && xstate.need(2 * sizeof(ZsXxh), &e);
+    }
+    // the history to the front: one copy when source and destination are apart, else the forward copy of k_zs_slide
+    bool slide(uint64_t history, uint64_t bytes) {
+        if (history != keep_hist || history > work_len || history + bytes > work_text) return false;      // (never: zs_run's own plan)
+        const u64 from = work_len - history;
+        if (history && from >= history) { if (!ok(hipMemcpyAsync(work.p, work.as<u8>() + from, (size_t)history, hipMemcpyDeviceToDevice, ctx->stream))) return false; }
+        else if (history && from) {
+            hipLaunchKernelGGL(k_zs_slide, dim3(1), dim3(ZS_SLIDE_THREADS), 0, ctx->stream, work.as<u8>(), from, history);
+            if (!ok(hipGetLastError())) return false;
+        }
+        hist = history; work_len = history + bytes;
+        return true;
+    }
+    // the checked round behind the text kept so far, through the caller's windows; the next round's history is noted
+    bool retire(uint64_t keep_bytes) {
+        const u64 bytes = work_len - hist;
+        if (keep_bytes > work_len || !keep_reserve(bytes)) return false;
+        if (bytes && !ok(hipMemcpyAsync(keep + keep_len, work.as<const u8>() + hist, (size_t)bytes, hipMemcpyDeviceToDevice, ctx->stream))) return false;
+        keep_len += bytes; keep_hist = keep_bytes;
+        return !keep_flush || keep_flush();
+    }
+    bool xxh64_part(const ZsXxhJob *job, uint32_t m, uint64_t *h) {
+        Lap lap(*this, 5, true);
+        for (uint32_t i = 0; i < m; ++i) if (job[i].at + job[i].len > work_len) return false;                 // (never)
+        if (!hash.need((size_t)m * (sizeof(ZsXxhJob) + 8), &e)) return false;
+        u64 *out = (u64 *)(hash.as<ZsXxhJob>() + m);
+        if (!ok(hipMemcpyAsync(hash.p, job, (size_t)m * sizeof(ZsXxhJob), hipMemcpyHostToDevice, ctx->stream))) return false;
+        hipLaunchKernelGGL(k_zs_xxh64_part, dim3(m), dim3(64), 0, ctx->stream, work.as<const u8>(), hash.as<const ZsXxhJob>(), xstate.as<ZsXxh>(), out);
+        if (!ok(hipGetLastError())) return false;
+        if (!ok(hipMemcpyAsync(h, out, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream)) || !sync()) return false;
+        return lap.end();
     }
     bool put_blocks(const ZsBlock *b, uint32_t k) {
         return blocks.need((size_t)k * sizeof(ZsBlock), &e) && ok(hipMemcpyAsync(blocks.p, b, (size_t)k * sizeof(ZsBlock), hipMemcpyHostToDevice, ctx->stream));
@@ -101,19 +150,20 @@ struct ZsDev : DevKeep {
         hipStream_t st = ctx->stream;
         if (!put_blocks(b, k) || !org.need((size_t)(bytes + 1) * 4, &e) || !groups.need((size_t)(n_groups + 1) * 4, &e) || !status.need((size_t)k * 4, &e)) return false;
         if (!ok(hipMemcpyAsync(groups.p, group, (size_t)(n_groups + 1) * 4, hipMemcpyHostToDevice, st)) || !ok(hipMemsetAsync(status.p, 0, (size_t)k * 4, st))) return false;
-        const u64 base = keep_len;
+        u8 *const text = sliding ? work.as<u8>() : keep;
+        const u64 base = sliding ? hist : keep_len;
         {
             Lap lap(*this, 3);
-            hipLaunchKernelGGL(k_zs_execute, dim3(k), dim3(64), 0, st, in.as<const u8>(), blocks.as<const ZsBlock>(), k, lit.as<const u8>(), seq.as<const ZsSeq>(), keep, org.as<u32>(),
+            hipLaunchKernelGGL(k_zs_execute, dim3(k), dim3(64), 0, st, in.as<const u8>(), blocks.as<const ZsBlock>(), k, lit.as<const u8>(), seq.as<const ZsSeq>(), text, org.as<u32>(),
                                base, status.as<u32>());
             if (!ok(hipGetLastError())) return false;
             if (!ok(hipMemcpyAsync(st_h, status.p, (size_t)k * 4, hipMemcpyDeviceToHost, st)) || !sync() || !lap.end()) return false;
         }
         for (uint32_t j = 0; j < k; ++j) if (st_h[j]) return true;         // (no block's origins are resolved when one of them is damaged)
         Lap lap(*this, 4);
-        hipLaunchKernelGGL(k_zs_resolve, dim3(n_groups), dim3(ZS_RESOLVE_THREADS), 0, st, blocks.as<const ZsBlock>(), groups.as<const u32>(), keep, org.as<const u32>(), base);
+        hipLaunchKernelGGL(k_zs_resolve, dim3(n_groups), dim3(ZS_RESOLVE_THREADS), 0, st, blocks.as<const ZsBlock>(), groups.as<const u32>(), text, org.as<const u32>(), base);
         if (!ok(hipGetLastError()) || !lap.end()) return false;
-        keep_len += bytes;
+        if (!sliding) keep_len += bytes;                             // (sliding: retire() appends the round)
         return true;
     }
     bool xxh64(const uint64_t *at, const uint64_t *len, uint32_t m, uint64_t *h) {
@@ -122,7 +172,7 @@ struct ZsDev : DevKeep {
         for (uint32_t i = 0; i < m; ++i) { span[2 * i] = at[i]; span[2 * i + 1] = len[i]; }
         if (!hash.need((size_t)m * 24, &e)) return false;
         if (!ok(hipMemcpyAsync(hash.p, span.data(), (size_t)m * 16, hipMemcpyHostToDevice, ctx->stream))) return false;
-        hipLaunchKernelGGL(k_zs_xxh64, dim3(m), dim3(64), 0, ctx->stream, (const u8 *)keep, hash.as<const u64>(), hash.as<u64>() + 2 * (size_t)m);
+        hipLaunchKernelGGL(k_zs_xxh64, dim3(m), dim3(64), 0, ctx->stream, sliding ? work.as<const u8>() : (const u8 *)keep, hash.as<const u64>(), hash.as<u64>() + 2 * (size_t)m);
         if (!ok(hipGetLastError())) return false;
         if (!ok(hipMemcpyAsync(h, hash.as<u64>() + 2 * (size_t)m, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream)) || !sync()) return false;
         return lap.end();
@@ -131,7 +181,7 @@ struct ZsDev : DevKeep {
         if (!to_host) return keep ? keep : (const uint8_t *)this;      // (the text stays: the sink does not read it)
         u8 *h = ctx_pin(1, std::max<u64>(1, len));
         if (!h) return nullptr;
-        if (!ok(hipMemcpyAsync(h, keep + at, (size_t)len, hipMemcpyDeviceToHost, ctx->stream)) || !sync()) return nullptr;
+        if (!ok(hipMemcpyAsync(h, (sliding ? work.as<const u8>() : keep) + at, (size_t)len, hipMemcpyDeviceToHost, ctx->stream)) || !sync()) return nullptr;
         return h;
     }
 };

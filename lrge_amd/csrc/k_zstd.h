@@ -8,6 +8,9 @@
 //                    in front of the block is not read, the byte's origin is recorded instead
 //   k_zs_resolve     one workgroup per frame of the round: its blocks in order, a barrier between them; deferred bytes read final ones
 //   k_zs_xxh64       one wavefront per frame: four lanes hold the four accumulators
+//   k_zs_xxh64_part  the same for a frame that spans rounds of the sliding driver: one wavefront per part, the accumulators from
+//                    and to a state in device memory
+//   k_zs_slide       the history to the front of the work text, source and destination overlapping: one workgroup, chunk by chunk
 // No workgroup waits for another: every dependency is a kernel boundary or a barrier inside one workgroup.
 #pragma once
 #include "zs_core.h"
@@ -84,4 +87,29 @@ __global__ __launch_bounds__(64) void k_zs_xxh64(const u8 *__restrict__ text, co
     ZsDevEnv e{&T, threadIdx.x, {0}, {0}};
     const u64 h = zs_xxh64(e, text + span[2 * blockIdx.x], span[2 * blockIdx.x + 1]);
     if (threadIdx.x == 0) out[blockIdx.x] = h;
+}
+
+// part f of the launch: text[job[f].at, + job[f].len) into state[job[f].slot & 1] (zs_xxh64_part); two parts of one launch are of
+// two frames and name two states
+__global__ __launch_bounds__(64) void k_zs_xxh64_part(const u8 *__restrict__ text, const ZsXxhJob *__restrict__ job, ZsXxh *state, u64 *__restrict__ out) {
+    __shared__ ZsTabs T;
+    ZsDevEnv e{&T, threadIdx.x, {0}, {0}};
+    const ZsXxhJob J = job[blockIdx.x];
+    const u64 h = zs_xxh64_part(e, state[J.slot & 1], text + J.at, J.len, (J.flags & 1) != 0, (J.flags & 2) != 0);
+    if (threadIdx.x == 0) out[blockIdx.x] = h;
+}
+
+// text[from, from + n) to text[0, n), from > 0, the two overlapping when from < n.  One workgroup walks the bytes upwards in chunks
+// of ZS_SLIDE_THREADS * ZS_SLIDE_PER: every thread reads its bytes of a chunk, the barrier, then writes them.  A chunk's writes end
+// below the next chunk's reads (from > 0), and a thread has read a chunk before it passes that chunk's barrier, so no byte is
+// overwritten before it is read
+#define ZS_SLIDE_THREADS 1024
+#define ZS_SLIDE_PER 16
+__global__ __launch_bounds__(ZS_SLIDE_THREADS) void k_zs_slide(u8 *text, u64 from, u64 n) {
+    for (u64 c = 0; c < n; c += (u64)ZS_SLIDE_THREADS * ZS_SLIDE_PER) {
+        u8 v[ZS_SLIDE_PER];
+        for (u32 k = 0; k < ZS_SLIDE_PER; ++k) { const u64 i = c + (u64)k * ZS_SLIDE_THREADS + threadIdx.x; v[k] = i < n ? text[from + i] : (u8)0; }
+        __syncthreads();
+        for (u32 k = 0; k < ZS_SLIDE_PER; ++k) { const u64 i = c + (u64)k * ZS_SLIDE_THREADS + threadIdx.x; if (i < n) text[i] = v[k]; }
+    }
 }

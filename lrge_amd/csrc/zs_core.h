@@ -553,6 +553,14 @@ ZS_FN void zs_resolve_block(uint8_t *text, const uint32_t *org, uint64_t out, ui
 ZS_FN uint64_t zs_rotl(uint64_t x, uint32_t r) { return x << r | x >> (64 - r); }
 ZS_FN uint64_t zs_xxh_round(uint64_t acc, uint64_t w) { return zs_rotl(acc + w * ZS_P2, 31) * ZS_P1; }
 ZS_FN uint64_t zs_xxh_merge(uint64_t h, uint64_t v) { return (h ^ zs_xxh_round(0, v)) * ZS_P1 + ZS_P4; }
+// the end of a hash: h already holds the merged accumulators (or ZS_P5) plus the length; p[i, n) are the bytes behind the last stripe
+ZS_FN uint64_t zs_xxh_finish(uint64_t h, const uint8_t *p, uint64_t i, uint64_t n) {
+    for (; i + 8 <= n; i += 8) h = zs_rotl(h ^ zs_xxh_round(0, zs_le64(p + i)), 27) * ZS_P1 + ZS_P4;
+    if (i + 4 <= n) { h = zs_rotl(h ^ (uint64_t)zs_le32(p + i) * ZS_P1, 23) * ZS_P2 + ZS_P3; i += 4; }
+    for (; i < n; ++i) h = zs_rotl(h ^ p[i] * ZS_P5, 11) * ZS_P1;
+    h ^= h >> 33; h *= ZS_P2; h ^= h >> 29; h *= ZS_P3; h ^= h >> 32;
+    return h;
+}
 // lanes 0..3 hold the four accumulators over the 32-byte stripes; every lane returns the hash
 template <class E> ZS_FN uint64_t zs_xxh64(E &e, const uint8_t *p, uint64_t n) {
     ZsTabs &t = *e.t;
@@ -575,11 +583,42 @@ template <class E> ZS_FN uint64_t zs_xxh64(E &e, const uint8_t *p, uint64_t n) {
         h = zs_rotl(t.acc[0], 1) + zs_rotl(t.acc[1], 7) + zs_rotl(t.acc[2], 12) + zs_rotl(t.acc[3], 18);
         for (uint32_t i = 0; i < 4; ++i) h = zs_xxh_merge(h, t.acc[i]);
     } else h = ZS_P5;
-    h += n;
-    uint64_t i = 32 * stripes;
-    for (; i + 8 <= n; i += 8) h = zs_rotl(h ^ zs_xxh_round(0, zs_le64(p + i)), 27) * ZS_P1 + ZS_P4;
-    if (i + 4 <= n) { h = zs_rotl(h ^ (uint64_t)zs_le32(p + i) * ZS_P1, 23) * ZS_P2 + ZS_P3; i += 4; }
-    for (; i < n; ++i) h = zs_rotl(h ^ p[i] * ZS_P5, 11) * ZS_P1;
-    h ^= h >> 33; h *= ZS_P2; h ^= h >> 29; h *= ZS_P3; h ^= h >> 32;
-    return h;
+    return zs_xxh_finish(h + n, p, 32 * stripes, n);
+}
+
+// XXH64 of a frame whose text arrives in parts (a frame that spans rounds of the sliding driver, zs_round.h): the four
+// accumulators and the count of bytes they have taken.  `hashed` stays a multiple of 32 until the frame ends: a part takes whole
+// stripes only, and the next part starts again at the frame byte `hashed`
+struct ZsXxh { uint64_t acc[4]; uint64_t hashed; };
+// one part: p[0, n) are the frame's bytes from `hashed` on (0 when `first`: S is not read).  Not `last`: the whole stripes of
+// the part go into S, and 0 is returned.  `last`: p[0, n) is all that is left of the frame, and every lane returns the hash of
+// its hashed + n bytes -- as zs_xxh64 does, the form below 32 bytes that uses no accumulator included.  Lanes 0..3 as there
+template <class E> ZS_FN uint64_t zs_xxh64_part(E &e, ZsXxh &S, const uint8_t *p, uint64_t n, bool first, bool last) {
+    ZsTabs &t = *e.t;
+    const uint64_t h0 = first ? 0 : S.hashed, stripes = n / 32;
+    e.sync();
+    for (uint32_t l = e.lane0(); l < e.lane1() && l < 4; ++l) {
+        uint64_t a = first ? (l == 0 ? ZS_P1 + ZS_P2 : l == 1 ? ZS_P2 : l == 2 ? 0 : 0 - ZS_P1) : S.acc[l];
+        uint64_t s = 0;
+        for (; s + 8 <= stripes; s += 8) {
+            uint64_t w[8];
+            for (uint32_t i = 0; i < 8; ++i) __builtin_memcpy(&w[i], p + 32 * (s + i) + 8 * l, 8);
+            for (uint32_t i = 0; i < 8; ++i) a = zs_xxh_round(a, w[i]);
+        }
+        for (; s < stripes; ++s) a = zs_xxh_round(a, zs_le64(p + 32 * s + 8 * l));
+        t.acc[l] = a;
+    }
+    e.sync();                                           // (every lane has read S.hashed; the accumulators are in t)
+    if (!last) {
+        for (uint32_t l = e.lane0(); l < e.lane1() && l < 4; ++l) S.acc[l] = t.acc[l];
+        if (e.lane0() == 0) S.hashed = h0 + 32 * stripes;
+        return 0;
+    }
+    const uint64_t total = h0 + n;
+    uint64_t h;
+    if (total >= 32) {
+        h = zs_rotl(t.acc[0], 1) + zs_rotl(t.acc[1], 7) + zs_rotl(t.acc[2], 12) + zs_rotl(t.acc[3], 18);
+        for (uint32_t i = 0; i < 4; ++i) h = zs_xxh_merge(h, t.acc[i]);
+    } else h = ZS_P5;
+    return zs_xxh_finish(h + total, p, 32 * stripes, n);
 }

@@ -163,7 +163,7 @@ class Context:
 
     def open_reads(self, path_or_bytes, flags=_ffi.GPU_INFLATE_BGZF | _ffi.GPU_INFLATE_GZIP):
         """A FASTA / FASTQ file (a path, or the bytes of the whole file) parsed on the device: plain, BGZF or any other gzip
-        (| _ffi.GPU_INFLATE_BZIP2: bzip2 as well; | _ffi.GPU_INFLATE_ZSTD: Zstandard as well, always resident; | _ffi.GPU_INFLATE_XZ: xz as well), by `flags` (lrge_hip_reads_open*); | _ffi.GPU_INGEST_BAM takes unaligned BAM as well, | _ffi.GPU_INGEST_SAM unaligned SAM, | _ffi.GPU_INGEST_CRAM (opt-in, implied by nothing) unaligned CRAM with its base blocks decoded on the device (DeviceReads.cram_stats); | _ffi.GPU_INGEST_WINDOWED lets FASTA / FASTQ text above option INGEST_WINDOW_BYTES pass through in windows with only the bases kept (DeviceReads.window_stats), and | _ffi.GPU_INGEST_WINDOWED_ALN beside it and the format's own flag does the same for unaligned BAM (its bases kept packed, 4 bits each) and SAM.  Returns a DeviceReads with names, lens and seqset().  Input the device does not
+        (| _ffi.GPU_INFLATE_BZIP2: bzip2 as well; | _ffi.GPU_INFLATE_ZSTD: Zstandard as well, resident unless | _ffi.GPU_INGEST_WINDOWED_ZSTD stands beside it and the windowed flag: then it passes through the windows too, DeviceReads.zstd_stats(); | _ffi.GPU_INFLATE_XZ: xz as well), by `flags` (lrge_hip_reads_open*); | _ffi.GPU_INGEST_BAM takes unaligned BAM as well, | _ffi.GPU_INGEST_SAM unaligned SAM, | _ffi.GPU_INGEST_CRAM (opt-in, implied by nothing) unaligned CRAM with its base blocks decoded on the device (DeviceReads.cram_stats); | _ffi.GPU_INGEST_WINDOWED lets FASTA / FASTQ text above option INGEST_WINDOW_BYTES pass through in windows with only the bases kept (DeviceReads.window_stats), and | _ffi.GPU_INGEST_WINDOWED_ALN beside it and the format's own flag does the same for unaligned BAM (its bases kept packed, 4 bits each) and SAM.  Returns a DeviceReads with names, lens and seqset().  Input the device does not
         prove raises UnprovenInput: read the file with the host readers (readio.load) instead."""
         return DeviceReads(self, path_or_bytes, flags)
 
@@ -513,6 +513,13 @@ class DeviceReads:
         a handle of every other open"""
         a = (C.c_uint64 * 4)()
         self.ctx._check(self.ctx._lib.lrge_hip_reads_seek_stats(self.h, C.byref(a)))
+        return tuple(int(x) for x in a)
+
+    def zstd_stats(self):
+        """(rounds, largest history carried into a round, largest work text -- history plus round --, bytes of history moved) of the
+        sliding Zstandard decode behind an open with GPU_INGEST_WINDOWED_ZSTD; zeros for a handle whose call did not slide"""
+        a = (C.c_uint64 * 4)()
+        self.ctx._check(self.ctx._lib.lrge_hip_reads_zstd_stats(self.h, C.byref(a)))
         return tuple(int(x) for x in a)
 
     def name_ranks(self, *idx_lists):

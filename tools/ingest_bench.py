@@ -7,6 +7,13 @@ the files of the kinds asked for are written.  Usage:
   python tools/ingest_bench.py [--gbases 1.08] [--dir /tmp] [--reps 5] [--kinds fq,bgzf.fq.gz,fq.gz,bam,sam]
                                [--bam-segments 262144,1048576,4194304] [--out profiles/ingest_bench.json]
                                [--windowed [--window-mb 64[,1024]]] [--sampled K [--window-mb 64]] [--sampled K1,K2,.. --seek]
+                               [--kinds fq.zst --zstd-windowed K [--window-mb 64] [--out profiles/ingest_zstd_windowed_bench.json]]
+--zstd-windowed K (kind fq.zst: the FASTQ text compressed by libzstd at level 3 with content checksums, once as one frame and once
+as 64 frames): in every repeat the resident open (LRGE_GPU_INFLATE_ZSTD), the windowed open (| LRGE_GPU_INGEST_WINDOWED |
+LRGE_GPU_INGEST_WINDOWED_ZSTD), the census, the selected open of K seeded ordinals and the host way (libzstd on
+one thread, then the open of the plain text) run one after the other, so all five alternate in one process; under the key
+"zstd_windowed" of --out.  With LRGE_HIP_LIB_AB naming a build from before the flag only the resident open is timed, under the
+key "zstd_windowed_parent".
 --sampled K1,K2,.. --seek: on the plain and the BGZF FASTQ file and on the uBAM (kind bam: LRGE_GPU_INGEST_SELECT_ALN), for every K, the census without and with a seek map
 (lrge_hip_reads_census, lrge_hip_reads_census_map), the selected open and the mapped open of the same K seeded ordinals
 (lrge_hip_reads_open_selected, lrge_hip_reads_open_mapped) and the existing windowed open, all alternating in one run; with the
@@ -344,6 +351,80 @@ def sampled_runs(a, ctx, H, HS, kinds, paths, text_bytes):
     json.dump(result, open(a.out, "w"), indent=1)
 
 
+def zstd_files(d, parts):
+    """the FASTQ text of the other kinds as ingest.fq.zst (one frame) and ingest.fq64.zst (64 frames): libzstd level 3, content checksums"""
+    import gzip_bench as GB
+    import zstd_corpus as Z
+    with mp.get_context("spawn").Pool(16) as pool:
+        text = b"".join(pool.map(GB._fastq, range(parts)))
+    paths = {"fq.zst": os.path.join(d, "ingest.fq.zst"), "fq64.zst": os.path.join(d, "ingest.fq64.zst")}
+    open(paths["fq.zst"], "wb").write(Z.compress(text, 3))
+    cut = -(-len(text) // 64)
+    with mp.get_context("spawn").Pool(16) as pool:
+        open(paths["fq64.zst"], "wb").write(b"".join(pool.map(Z.compress, [text[i:i + cut] for i in range(0, len(text), cut)])))
+    return paths, len(text)
+
+
+def zstd_runs(a, ctx, H, HS, paths, n_text):
+    """the five routes of --zstd-windowed on both files, alternating in every repeat (HS None: the library is from before the flag,
+    only the resident open); into the key "zstd_windowed" (HS None: "zstd_windowed_parent") of a.out"""
+    import numpy as np
+    from lrge_amd import readio
+    ZSTD, SLIDE = 128, 32 | 2048
+    out = {"window_bytes": a.window_mb << 20, "reps": a.reps, "k": a.zstd_windowed, "text_bytes": n_text, "files": {}}
+    ctx.set_option("INGEST_WINDOW_BYTES", str(a.window_mb << 20))
+    for kind, p in paths.items():
+        raw = open(p, "rb").read()                                    # (page cache; the host way starts from these bytes' file too)
+        runs, sel, seen = [], None, {}
+        for rep in range(a.reps + 1):
+            r = {}
+            for route, flags in (("resident", 15 | ZSTD), ("windowed", 15 | ZSTD | SLIDE)):
+                if route == "windowed" and HS is None:
+                    continue
+                ms2, st, nr, nb, tb, bs, win = (C.c_double * 2)(), (C.c_float * 4)(), C.c_uint64(), C.c_uint64(), C.c_uint64(), (C.c_uint64 * 6)(), (C.c_uint64 * 4)()
+                rc = H.route_device(ctx.h, p.encode(), flags, C.byref(ms2), C.byref(st), C.byref(nr), C.byref(nb), C.byref(tb), C.byref(bs), C.byref(win))
+                assert rc == 0, (kind, route, rc, ctx._lib.lrge_hip_last_error(ctx.h))
+                assert tb.value == n_text and seen.setdefault("reads", (nr.value, nb.value)) == (nr.value, nb.value) and (win[0] > 1) == (route == "windowed"), (kind, route, list(win))
+                r.update({route + "_open_ms": ms2[0], route + "_text_ms": st[0], route + "_scan_ms": st[1], route + "_seqset_ms": ms2[1]})
+                if route == "windowed":
+                    seen.update(windows=win[0], store_bytes=win[1], largest_window_bytes=win[2])
+            if HS is not None:
+                if sel is None:
+                    sel = np.sort(np.random.default_rng(1).choice(seen["reads"][0], min(a.zstd_windowed, seen["reads"][0]), replace=False)).astype(np.uint32)
+                ms3, st, cen, sst, win = (C.c_double * 3)(), (C.c_float * 4)(), (C.c_uint64 * 4)(), (C.c_uint64 * 4)(), (C.c_uint64 * 4)()
+                rc = HS.route_sampled(ctx.h, p.encode(), 15 | ZSTD | 2048, sel.ctypes.data, sel.size, C.byref(ms3), C.byref(st), C.byref(cen), C.byref(sst), C.byref(win))
+                assert rc == 0, (kind, rc, ctx._lib.lrge_hip_last_error(ctx.h))
+                assert (cen[0], cen[1], cen[2]) == (seen["reads"][0], seen["reads"][1], n_text) and (sst[0], sst[1]) == (seen["reads"][0], sel.size), (list(cen), list(sst))
+                seen["kept_bases"] = sst[3]
+                r.update(census_ms=ms3[0], selected_open_ms=ms3[1], two_pass_ms=ms3[0] + ms3[1], seqset_k_ms=ms3[2])
+                t0 = time.perf_counter()
+                text = readio.zstd_decompress(open(p, "rb").read())
+                t1 = time.perf_counter()
+                dr = ctx.open_reads(text, 3)
+                t2 = time.perf_counter()
+                assert dr.n == seen["reads"][0] and len(text) == n_text
+                dr.free()
+                del text
+                r.update(libzstd_ms=(t1 - t0) * 1e3, host_way_ms=(t2 - t0) * 1e3)
+            if rep:                                                    # (run 0 is the warm-up)
+                runs.append(r)
+        f = dict(file_bytes=len(raw), reads=seen["reads"][0], bases=seen["reads"][1], every_run=runs, **{k: v for k, v in seen.items() if k != "reads"})
+        if HS is not None:
+            dr = ctx.open_reads(raw, 15 | ZSTD | SLIDE)
+            f["zstd_stats"] = dict(zip(("rounds", "largest_history", "largest_work_text", "history_bytes_moved"), dr.zstd_stats()))
+            dr.free()
+        for key in runs[0]:
+            f["%s_median" % key] = statistics.median(x[key] for x in runs)
+            f["%s_range" % key] = (min(x[key] for x in runs), max(x[key] for x in runs))
+        out["files"][kind] = f
+        print(kind, json.dumps({k: v for k, v in f.items() if k != "every_run"}), flush=True)
+    ctx.set_option("INGEST_WINDOW_BYTES", None)
+    result = json.load(open(a.out)) if os.path.exists(a.out) else {}
+    result["zstd_windowed" if HS is not None else "zstd_windowed_parent"] = out
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    json.dump(result, open(a.out, "w"), indent=1)
+
+
 def seek_runs(a, ctx, H, HK, kinds, paths, text_bytes, ks):
     """for every K: the windowed open, the census without and with a map, the selected and the mapped open on every file, all
     alternating in every repeat; into the key "sampled_seek" / "<K>" of a.out"""
@@ -396,6 +477,7 @@ def main():
     ap.add_argument("--window-mb", default="64")
     ap.add_argument("--sampled", default="0")
     ap.add_argument("--seek", action="store_true")
+    ap.add_argument("--zstd-windowed", type=int, default=0)
     a = ap.parse_args()
     seek_ks = [int(k) for k in a.sampled.split(",") if int(k)] if a.seek else []
     a.sampled = 0 if a.seek else int(a.sampled)
@@ -412,6 +494,27 @@ def main():
     build(so, src)
     parts = max(1, round(a.gbases * 1e9 * 2.02 / (256 << 20)))       # a record is 2 bytes per base and a header
     t0 = time.perf_counter()
+    if a.zstd_windowed:
+        paths, n_text = zstd_files(work, parts)
+        print("files written in %.0f s: %d text bytes" % (time.perf_counter() - t0, n_text), flush=True)
+        ctx = engine.Context(0)
+        H = C.CDLL(so)
+        H.route_device.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_double * 2), C.POINTER(C.c_float * 4), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                   C.POINTER(C.c_uint64), C.POINTER(C.c_uint64 * 6), C.POINTER(C.c_uint64 * 4)]
+        HS, extra = None, []
+        if hasattr(ctx._lib, "lrge_hip_reads_zstd_stats"):
+            extra = [os.path.join(work, "sampled.cpp"), os.path.join(work, "libsampled.so")]
+            open(extra[0], "w").write(HELPER_SAMPLED)
+            build(extra[1], extra[0])
+            HS = C.CDLL(extra[1])
+            HS.route_sampled.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(C.c_double * 3), C.POINTER(C.c_float * 4)] + [C.POINTER(C.c_uint64 * 4)] * 3
+        a.window_mb = int(a.window_mb.split(",")[0])
+        zstd_runs(a, ctx, H, HS, paths, n_text)
+        ctx.close()
+        for p in list(paths.values()) + [src, so] + extra:
+            os.remove(p)
+        os.rmdir(work)
+        return
     kinds = [k for k in KINDS if k in a.kinds.split(",")]
     paths, text_bytes = write_files(work, parts, kinds)
     print("files written in %.0f s: %s text bytes" % (time.perf_counter() - t0, text_bytes), flush=True)

@@ -89,7 +89,7 @@ int main(int argc, char **argv) {
         else if (a == "--gpu-gzip") gpu_gzip = true;             // every gzip input (plain, multi-member, BGZF) decompressed on --device
         else if (a == "--gpu-xz") gpu_xz = true;                 // xz input decompressed on --device (with --gpu-ingest: kept in HBM); not implied by --gpu-ingest
         else if (a == "--gpu-cram") gpu_cram = true;             // beside --gpu-ingest: unaligned CRAM walked on the host, its base blocks decoded on --device; not implied by --gpu-ingest
-        else if (a == "--gpu-zstd") gpu_zstd = true;             // Zstandard input decompressed on --device (with --gpu-ingest: kept in HBM); not implied by --gpu-ingest
+        else if (a == "--gpu-zstd") gpu_zstd = true;             // Zstandard input decompressed on --device (with --gpu-ingest: kept in HBM, through the windows and -- with --gpu-sample -- the sampled route: LRGE_GPU_INGEST_WINDOWED_ZSTD); not implied by --gpu-ingest
         else if (a == "--gpu-bzip2") gpu_bzip2 = true;           // bzip2 input decompressed on --device (with --gpu-ingest: kept in HBM)
         else if (a == "--gpu-ingest") { gpu_ingest = true; gpu_gzip = true; }   // FASTA / FASTQ / unaligned BAM / unaligned SAM parsed on --device too: the bases never reach host memory (implies --gpu-gzip)
         else if (a == "--gpu-sample") gpu_sample = true;         // beside --gpu-ingest: a count pass, then only the drawn reads are kept (lrge_hip_reads_census, lrge_hip_reads_open_selected); not implied by --gpu-ingest
@@ -121,7 +121,7 @@ int main(int argc, char **argv) {
         // do not prove takes the route of --gpu-ingest alone
         std::unique_ptr<lrge::SampledSource> sampled;
         if (gpu_ingest) {
-            const int fl = LRGE_GPU_INFLATE_BGZF | LRGE_GPU_INFLATE_GZIP | LRGE_GPU_INGEST_BAM | LRGE_GPU_INGEST_SAM | LRGE_GPU_INGEST_WINDOWED | LRGE_GPU_INGEST_WINDOWED_ALN | (gpu_bzip2 ? LRGE_GPU_INFLATE_BZIP2 : 0) | (gpu_zstd ? LRGE_GPU_INFLATE_ZSTD : 0) | (gpu_xz ? LRGE_GPU_INFLATE_XZ : 0) | (gpu_cram ? LRGE_GPU_INGEST_CRAM : 0);
+            const int fl = LRGE_GPU_INFLATE_BGZF | LRGE_GPU_INFLATE_GZIP | LRGE_GPU_INGEST_BAM | LRGE_GPU_INGEST_SAM | LRGE_GPU_INGEST_WINDOWED | LRGE_GPU_INGEST_WINDOWED_ALN | (gpu_bzip2 ? LRGE_GPU_INFLATE_BZIP2 : 0) | (gpu_zstd ? LRGE_GPU_INFLATE_ZSTD | LRGE_GPU_INGEST_WINDOWED_ZSTD : 0) | (gpu_xz ? LRGE_GPU_INFLATE_XZ : 0) | (gpu_cram ? LRGE_GPU_INGEST_CRAM : 0);
             if (gpu_sample) {
                 sampled.reset(new lrge::SampledSource{input, fl | LRGE_GPU_INGEST_SELECT_ALN, device});       // (unaligned BAM takes the sampled route too: DESIGN section 25)
                 sampled->seek = gpu_seek;
