@@ -295,6 +295,20 @@ inline bool bgzf_inflate_with(Ctx &ctx, const std::string &raw, std::string &out
     ctx.check(rc);
     return true;
 }
+// a round decoder's C entry (lrge_hip_gzip_inflate, _bzip2_, _zstd_, _xz_) into `out`: false, with `out` empty, for the return
+// codes in `host` (the host path decompresses, with its messages); any other failure throws
+template <class Stats>
+inline bool stream_inflate_with(Ctx &ctx, int (*entry)(lrge_hip_ctx *, const void *, uint64_t, int (*)(void *, const void *, uint64_t), void *, Stats *),
+                                std::initializer_list<int> host, const std::string &raw, std::string &out) {
+    out.clear();
+    const int rc = entry(ctx.h, raw.data(), raw.size(), [](void *u, const void *b, uint64_t n) {
+        static_cast<std::string *>(u)->append(static_cast<const char *>(b), (size_t)n);
+        return 0;
+    }, &out, nullptr);
+    if (std::find(host.begin(), host.end(), rc) != host.end()) { out.clear(); return false; }
+    ctx.check(rc);
+    return true;
+}
 }  // namespace detail
 
 inline std::function<bool(const std::string &, std::string &)> bgzf_inflater(int device) {
@@ -310,14 +324,7 @@ inline std::function<bool(const std::string &, std::string &)> gzip_inflater(int
     return [ctx](const std::string &raw, std::string &out) -> bool {
         if (detail::is_bzip2(raw) || detail::is_zstd(raw) || detail::is_xz(raw)) return false;
         if (lrge_hip_bgzf_scan(raw.data(), raw.size(), nullptr, nullptr) == LRGE_OK) return detail::bgzf_inflate_with(*ctx, raw, out);
-        out.clear();
-        const int rc = lrge_hip_gzip_inflate(ctx->h, raw.data(), raw.size(), [](void *u, const void *b, uint64_t n) {
-            static_cast<std::string *>(u)->append(static_cast<const char *>(b), (size_t)n);
-            return 0;
-        }, &out, nullptr);
-        if (rc == LRGE_ERR_PARSE || rc == LRGE_ERR_TOO_MANY) { out.clear(); return false; }
-        ctx->check(rc);
-        return true;
+        return detail::stream_inflate_with(*ctx, lrge_hip_gzip_inflate, {LRGE_ERR_PARSE, LRGE_ERR_TOO_MANY}, raw, out);
     };
 }
 
@@ -328,14 +335,7 @@ inline std::function<bool(const std::string &, std::string &)> bzip2_inflater(in
     auto ctx = std::make_shared<detail::Ctx>(device);
     return [ctx, gzip](const std::string &raw, std::string &out) -> bool {
         if (!detail::is_bzip2(raw)) return gzip ? gzip(raw, out) : false;
-        out.clear();
-        const int rc = lrge_hip_bzip2_inflate(ctx->h, raw.data(), raw.size(), [](void *u, const void *b, uint64_t n) {
-            static_cast<std::string *>(u)->append(static_cast<const char *>(b), (size_t)n);
-            return 0;
-        }, &out, nullptr);
-        if (rc == LRGE_ERR_PARSE) { out.clear(); return false; }
-        ctx->check(rc);
-        return true;
+        return detail::stream_inflate_with(*ctx, lrge_hip_bzip2_inflate, {LRGE_ERR_PARSE}, raw, out);
     };
 }
 
@@ -346,14 +346,7 @@ inline std::function<bool(const std::string &, std::string &)> zstd_inflater(int
     auto ctx = std::make_shared<detail::Ctx>(device);
     return [ctx, other](const std::string &raw, std::string &out) -> bool {
         if (!detail::is_zstd(raw)) return other ? other(raw, out) : false;
-        out.clear();
-        const int rc = lrge_hip_zstd_inflate(ctx->h, raw.data(), raw.size(), [](void *u, const void *b, uint64_t n) {
-            static_cast<std::string *>(u)->append(static_cast<const char *>(b), (size_t)n);
-            return 0;
-        }, &out, nullptr);
-        if (rc == LRGE_ERR_PARSE || rc == LRGE_ERR_TOO_MANY) { out.clear(); return false; }
-        ctx->check(rc);
-        return true;
+        return detail::stream_inflate_with(*ctx, lrge_hip_zstd_inflate, {LRGE_ERR_PARSE, LRGE_ERR_TOO_MANY}, raw, out);
     };
 }
 
@@ -364,14 +357,7 @@ inline std::function<bool(const std::string &, std::string &)> xz_inflater(int d
     auto ctx = std::make_shared<detail::Ctx>(device);
     return [ctx, other](const std::string &raw, std::string &out) -> bool {
         if (!detail::is_xz(raw)) return other ? other(raw, out) : false;
-        out.clear();
-        const int rc = lrge_hip_xz_inflate(ctx->h, raw.data(), raw.size(), [](void *u, const void *b, uint64_t n) {
-            static_cast<std::string *>(u)->append(static_cast<const char *>(b), (size_t)n);
-            return 0;
-        }, &out, nullptr);
-        if (rc == LRGE_ERR_PARSE || rc == LRGE_ERR_TOO_MANY) { out.clear(); return false; }
-        ctx->check(rc);
-        return true;
+        return detail::stream_inflate_with(*ctx, lrge_hip_xz_inflate, {LRGE_ERR_PARSE, LRGE_ERR_TOO_MANY}, raw, out);
     };
 }
 

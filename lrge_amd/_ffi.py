@@ -31,6 +31,7 @@ C_NAMES = ["query_bases", "query_minimizers", "anchors", "groups", "groups_chain
            "rs_scatter_launches", "rs_scatter_items", "rs_scatter_bytes", "lpg_split", "lookup_launches", "table_disp_sum", "anchors_kept", "index_parts", "sketch_launches", "sketch_wave_launches",
            "shared_name_pairs", "shared_name_distinct"]
 
+GZIP_STAT_NAMES = ["members", "chunks", "speculative_starts", "rejected_starts", "redecoded_chunks", "overflow_retries", "bytes_out"]   # lrge_hip_gzip_stats
 BZIP2_STAT_NAMES = ["blocks", "candidates", "rejected_candidates", "rounds", "bytes_out"]   # lrge_hip_bzip2_stats
 ZSTD_STAT_NAMES = ["frames", "skippable_frames", "blocks", "raw_blocks", "rle_blocks", "sequences", "checksums_checked", "rounds", "bytes_out",
                    "checksum_us"]   # lrge_hip_zstd_stats

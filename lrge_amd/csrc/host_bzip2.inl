@@ -41,12 +41,6 @@ struct BzDev : DevKeep {
         timing = c->opt("BZIP2_TIMING") != nullptr;
     }
     ~BzDev() { (void)hipStreamSynchronize(ctx->stream); }
-    // a stage's time, when asked for: the stream is drained at its end
-    struct Lap {
-        BzDev &d; int slot; double t0;
-        Lap(BzDev &dev, int s) : d(dev), slot(s), t0(dev.timing ? DevPool::now_ms() : 0) {}
-        bool end() { if (!d.timing) return true; const bool r = d.sync(); d.ms[slot] += DevPool::now_ms() - t0; return r; }
-    };
     bool load(const uint8_t *d, uint64_t len) {
         n = len;
         const u64 body = len & ~(u64)15, size = ((len + 15) & ~(u64)15) + BZ_PAD;
@@ -56,7 +50,7 @@ struct BzDev : DevKeep {
         return sync();
     }
     bool find(std::vector<uint64_t> &c) {
-        Lap lap(*this, 0);
+        Lap lap(*this, ms[0], timing);
         // about one candidate per block is expected: a list that proves too short is sized by the count, and the scan runs once more
         u64 cap = n / 64 + 16;
         for (int pass = 0;; ++pass) {
@@ -79,14 +73,10 @@ struct BzDev : DevKeep {
             return lap.end();
         }
     }
-    uint32_t default_round(uint32_t block) {
-        size_t mfree = 0, mtot = 0;
-        if (hipMemGetInfo(&mfree, &mtot) != hipSuccess) { (void)hipGetLastError(); mfree = 0; }
-        // (the text of a block is about its size again)
-        return (uint32_t)std::min<u64>(BZ_ROUND_MAX, std::max<u64>(1, ((u64)mfree + ctx->pool.idle()) / 2 / (bz_candidate_bytes(block) + block)));
-    }
+    // (the text of a block is about its size again)
+    uint32_t default_round(uint32_t block) { return (uint32_t)std::min<u64>(BZ_ROUND_MAX, std::max<u64>(1, dev_budget(ctx) / (bz_candidate_bytes(block) + block))); }
     bool decode(const uint64_t *p, uint32_t k, uint32_t block, BzRes *r) {
-        Lap lap(*this, 1);
+        Lap lap(*this, ms[1], timing);
         bs = block;
         if (!pos.need((size_t)k * 8, &e) || !res.need((size_t)k * sizeof(BzRes), &e) || !L.need((size_t)k * bs, &e) || !cnt.need((size_t)k * 1024, &e)) return false;
         if (!ok(hipMemcpyAsync(pos.p, p, (size_t)k * 8, hipMemcpyHostToDevice, ctx->stream))) return false;
@@ -105,16 +95,16 @@ struct BzDev : DevKeep {
         if (!ok(hipMemcpyAsync(links.p, l, (size_t)m * sizeof(BzLink), hipMemcpyHostToDevice, st)) || !ok(hipMemsetAsync(bad.p, 0, 4, st))) return false;
         const u32 lane_blocks = (u32)div_up(m, 64);
         {
-            Lap lap(*this, 2);
+            Lap lap(*this, ms[2], timing);
             hipLaunchKernelGGL(k_bz_scatter, dim3(m), dim3(64), 0, st, links.as<const BzLink>(), m, bs, L.as<const u8>(), cnt.as<const u32>(), tt.as<u32>());
             if (!ok(hipGetLastError()) || !lap.end()) return false;
         }
         {
-            Lap lap(*this, 3);
+            Lap lap(*this, ms[3], timing);
             hipLaunchKernelGGL(k_bz_walk, dim3(lane_blocks), dim3(64), 0, st, links.as<const BzLink>(), m, bs, tt.as<const u32>(), L.as<u8>(), bad.as<u32>());
             if (!ok(hipGetLastError()) || !lap.end()) return false;
         }
-        Lap lap(*this, 4);
+        Lap lap(*this, ms[4], timing);
         hipLaunchKernelGGL(k_bz_rle_count, dim3(lane_blocks), dim3(64), 0, st, links.as<const BzLink>(), m, bs, L.as<const u8>(), lens.as<u64>());
         if (!ok(hipGetLastError())) return false;
         std::vector<u64> len_h(m);
@@ -124,24 +114,19 @@ struct BzDev : DevKeep {
         if (bad_h) { e = hipErrorUnknown; return false; }          // (a link left its block: the counts were not L's)
         u64 total = 0;
         for (uint32_t a = 0; a < m; ++a) { l[a].out_off = total; l[a].run_open = (len_h[a] & BZ_RUN_OPEN) != 0; total += len_h[a] & ~BZ_RUN_OPEN; }
-        // the text: behind the earlier rounds' in the block that stays (keep_on), or in a buffer of the round
+        // the text: in a buffer of the round on its way to the host, or behind the earlier rounds' in the block that stays
         u8 *dst;
-        if (keep_on) { if (!keep_reserve(total)) return false; dst = keep + keep_len; }
-        else { if (!out.need((size_t)total + 4, &e)) return false; dst = out.as<u8>(); }
+        if (to_host) { if (!out.need((size_t)total + 4, &e)) return false; dst = out.as<u8>(); }
+        else { if (!keep_reserve(total)) return false; dst = keep + keep_len; }
         if (!ok(hipMemcpyAsync(links.p, l, (size_t)m * sizeof(BzLink), hipMemcpyHostToDevice, st))) return false;
         hipLaunchKernelGGL(k_bz_rle_write, dim3(lane_blocks), dim3(64), 0, st, links.as<const BzLink>(), m, bs, L.as<const u8>(), dst, crc.as<u32>());
         if (!ok(hipGetLastError())) return false;
         if (!ok(hipMemcpyAsync(crc_h, crc.p, (size_t)m * 4, hipMemcpyDeviceToHost, st))) return false;
         if (!lap.end()) return false;
-        u8 *h_out = nullptr;
-        if (keep_on) { keep_len += total; if (keep_flush && !keep_flush()) return false; }
-        else {
-            if (!(h_out = ctx_pin(1, std::max<u64>(1, total)))) return false;
-            if (!ok(hipMemcpyAsync(h_out, dst, (size_t)total, hipMemcpyDeviceToHost, st))) return false;
-        }
-        if (!sync()) return false;
+        if (!to_host) keep_len += total;
+        // (to the host, deliver has drained the stream; the block that stays is flushed before the CRCs are waited for)
+        if (!(*bytes = deliver(dst, total)) || (!to_host && !sync())) return false;
         *out_bytes = total;
-        *bytes = keep_on ? keep : h_out;
         return true;
     }
 };
@@ -151,29 +136,13 @@ struct BzDev : DevKeep {
 static int bzip2_inflate_impl(lrge_hip_ctx *ctx, const uint8_t *comp, uint64_t comp_len, int (*sink)(void *, const void *, uint64_t), void *user,
                               lrge_hip_bzip2_stats *stats) {
     (void)hipSetDevice(ctx->device);
+    static const CodecText text = {"bzip2", bz_status_name, 0, nullptr};
     BzStats st;
-    u64 bad = 0;
-    bool sink_stop = false;
-    int rc;
-    {
-        BzDev dev(ctx);
-        rc = bz_run(dev, comp, comp_len, ctx->opt_u64("BZIP2_ROUND_BLOCKS", 0), [&](const uint8_t *b, uint64_t k) {
-            if (sink(user, b, k) != 0) { sink_stop = true; return false; }
-            return true;
-        }, st, &bad);
-        if (rc == BZ_RUN_DEVICE && !sink_stop) {
-            LRGE_SET_ERR(ctx, "bzip2 inflate: %s", hipGetErrorString(dev.e != hipSuccess ? dev.e : hipErrorUnknown));
-            (void)hipGetLastError();
-        }
-        (void)hipStreamSynchronize(ctx->stream);
+    BzDev dev(ctx);
+    return codec_inflate(dev, text, sink, user, [&](auto &to_sink, u64 *bad) { return bz_run(dev, comp, comp_len, ctx->opt_u64("BZIP2_ROUND_BLOCKS", 0), to_sink, st, bad); }, [&] {
         if (dev.timing) fprintf(stderr, "[lrge_hip] bzip2 stages ms: find %.3f entropy %.3f scatter %.3f walk %.3f rle_crc %.3f\n", dev.ms[0], dev.ms[1], dev.ms[2], dev.ms[3], dev.ms[4]);
-    }
-    if (stats) { stats->blocks = st.blocks; stats->candidates = st.candidates; stats->rejected_candidates = st.rejected; stats->rounds = st.rounds; stats->bytes_out = st.bytes_out; }
-    if (rc == BZ_RUN_OK) return LRGE_OK;
-    if (sink_stop) { ctx->err = "bzip2 inflate: the sink stopped the call"; return LRGE_ERR_IO; }
-    if (rc == BZ_RUN_DEVICE) return LRGE_ERR_DEVICE;
-    LRGE_SET_ERR(ctx, "bzip2 data at file offset %llu: %s", (unsigned long long)bad, bz_status_name(rc));
-    return LRGE_ERR_PARSE;
+        if (stats) { stats->blocks = st.blocks; stats->candidates = st.candidates; stats->rejected_candidates = st.rejected; stats->rounds = st.rounds; stats->bytes_out = st.bytes_out; }
+    });
 }
 
 extern "C" int lrge_hip_bzip2_inflate(lrge_hip_ctx *ctx, const void *comp, uint64_t comp_len, int (*sink)(void *user, const void *bytes, uint64_t n),

@@ -47,11 +47,7 @@ struct lrge_hip_read_map { FxSeekMap m; };
 
 static double fx_now_ms() { return DevPool::now_ms(); }
 
-static u64 ingest_cap(lrge_hip_ctx *ctx) {
-    size_t mfree = 0, mtot = 0;
-    if (hipMemGetInfo(&mfree, &mtot) != hipSuccess) { (void)hipGetLastError(); mfree = 0; }
-    return ctx->opt_u64("INGEST_MAX_BYTES", ((u64)mfree + ctx->pool.idle()) / 2);       // (the batch planner's accounting: idle arena bytes are reusable)
-}
+static u64 ingest_cap(lrge_hip_ctx *ctx) { return ctx->opt_u64("INGEST_MAX_BYTES", dev_budget(ctx)); }
 
 static int fx_verdict_rc(lrge_hip_ctx *ctx, u32 verdict, const char *what) {
     if (verdict & FX_UNPROVEN) { LRGE_SET_ERR(ctx, "reads_open: not proven on the device (%s)", what); return LRGE_ERR_UNPROVEN; }
@@ -116,6 +112,15 @@ static int fx_sniff(int flags, const u8 *head, u64 n) {
     return (flags & LRGE_GPU_INGEST_SAM) && n >= 3 && sam_sniff(head, n) ? FX_FMT_SAM : FX_FMT_EMPTY;
 }
 
+// the container of a file by its first min(6, n) bytes.  FX_BOX_XZ: the five bytes that name xz to a caller who did not ask for it;
+// the device decoder is given the file only where the sixth is the magic's 0 as well (xz_whole)
+enum FxBox { FX_BOX_OTHER, FX_BOX_CRAM, FX_BOX_GZIP, FX_BOX_BZIP2, FX_BOX_ZSTD, FX_BOX_XZ };
+static FxBox fx_container(const u8 *d, u64 n, bool *xz_whole = nullptr) {
+    const auto is = [&](const char *magic, u64 k) { return n >= k && !memcmp(d, magic, (size_t)k); };
+    if (xz_whole) *xz_whole = is("\xfd" "7zXZ\0", 6);
+    return is("CRAM", 4) ? FX_BOX_CRAM : is("\x1f\x8b", 2) ? FX_BOX_GZIP : is("BZ", 2) ? FX_BOX_BZIP2 : is("\x28\xb5\x2f\xfd", 4) ? FX_BOX_ZSTD : is("\xfd" "7zXZ", 5) ? FX_BOX_XZ : FX_BOX_OTHER;
+}
+
 // the kind of a text of n bytes, after obtaining those bytes: the file's own when they are the text (host), else four bytes
 // copied from the block d_text.  Nothing is copied for a caller who asked for neither BAM nor SAM, or for a text below either magic
 static int fx_kind(lrge_hip_ctx *ctx, int flags, const u8 *host, const u8 *d_text, u64 n, int *kind) {
@@ -162,7 +167,7 @@ struct FxWinDev {
     bool mapped = false;                        // the text is the sub-text of a mapped open: whole records of a text the census proved, never sniffed
     bool scan_refused = false;                  // a window was not proven by the record scan or the driver (not: the budget) -- what a mapped open reports as a map that does not fit
     FxWinDev(lrge_hip_ctx *c, lrge_hip_reads *r, int f, u64 cap_) : ctx(c), R(r), flags(f), cap(cap_), store(c) {
-        store.keep_on = true; store.keep_slack = FX_PAD; store.keep_floor = 0;      // (block and store share one budget: neither takes more than it needs or doubles to)
+        store.keep_slack = FX_PAD; store.keep_floor = 0;     // (block and store share one budget: neither takes more than it needs or doubles to)
         R->name_off.assign(1, 0);
     }
     ~FxWinDev() { ctx->pool.release(d_sel); }
@@ -557,7 +562,7 @@ struct FxSink {
     FxSink(lrge_hip_ctx *c, lrge_hip_reads *r, int f, FxKeepMode m = FX_KEEP_ALL) : ctx(c), R(r), flags(f), cap(ingest_cap(c)),
         window(std::max<u64>(1, c->opt_u64("INGEST_WINDOW_BYTES", std::min<u64>((u64)1 << 30, cap / 4)))), blk(c), mode(m) {
         if ((flags & LRGE_GPU_INGEST_WINDOWED) || mode != FX_KEEP_ALL) run.reset(new FxWinRun(ctx, R, flags, cap, window));
-        blk.keep_on = true; blk.keep_max = cap; blk.keep_slack = FX_PAD;
+        blk.keep_max = cap; blk.keep_slack = FX_PAD;
     }
     int over_cap() { LRGE_SET_ERR(ctx, "reads_open: text above INGEST_MAX_BYTES (%llu)", (unsigned long long)cap); return LRGE_ERR_UNPROVEN; }
     // does a text of n bytes go through windows in `blk`?  kind_of(int *kind): the sniff of its first bytes (fx_kind), asked for
@@ -664,14 +669,13 @@ static int fx_src_bgzf(FxSink &s, const u8 *d, const std::vector<BgzfBlock> &t, 
 // gzip, bzip2, Zstandard and xz: the rounds of the decoder's driver (run(&bad): gz_run, bz_run, zs_run, xz_run) with the decoder `dev` keeping
 // every round's text in its own block (dev_keep.h), which becomes the handle's.  A windowed call flushes that block through the
 // sink's run whenever a round has been appended (DevKeep::keep_flush); whether its windows stay on is the first flush's sniff.
-// refused: the message for a stream the decoder does not take, with status(rc) and the file offset
-static_assert((int)GZ_RUN_OK == (int)BZ_RUN_OK && (int)GZ_RUN_DEVICE == (int)BZ_RUN_DEVICE && (int)GZ_RUN_OK == (int)ZS_RUN_OK && (int)GZ_RUN_DEVICE == (int)ZS_RUN_DEVICE &&
-              (int)GZ_RUN_OK == (int)XZ_RUN_OK && (int)GZ_RUN_DEVICE == (int)XZ_RUN_DEVICE, "one set of driver codes");
+// refused: the message for a stream the decoder does not take, with status(rc) and the file offset.  (One set of driver codes: the
+// static_assert beside codec_inflate, host_gzip.inl.)
 template <class Dev, class Run, class Status>
 static int fx_inflate_to_device(FxSink &s, Dev &dev, Run run, const char *codec, const char *refused, Status status) {
     lrge_hip_ctx *ctx = s.ctx;
     u64 bad = 0;
-    dev.keep_on = true; dev.keep_max = s.cap; dev.keep_slack = FX_PAD;
+    dev.to_host = false; dev.keep_max = s.cap; dev.keep_slack = FX_PAD;
     if (s.run) s.run->attach(&dev);
     const int rc = dev.e == hipSuccess ? run(&bad) : (int)GZ_RUN_DEVICE;
     (void)hipStreamSynchronize(ctx->stream);
@@ -721,7 +725,6 @@ static int fx_src_zstd(FxSink &s, const u8 *d, u64 len) {
     ZsStats st;
     ZsSlide sl = {0, 0, 0, 0};
     ZsDev dev(s.ctx);
-    dev.to_host = false;
     if (!fx_zstd_slides(s.flags)) s.run.reset();
     if (s.run) {
         dev.sliding = true; dev.slide_window = s.window;
@@ -743,7 +746,6 @@ static int fx_src_zstd(FxSink &s, const u8 *d, u64 len) {
 static int fx_src_xz(FxSink &s, const u8 *d, u64 len) {
     XzStats st;
     XzDev dev(s.ctx);
-    dev.to_host = false;
     const int rc = fx_inflate_to_device(s, dev, [&](u64 *bad) { return xz_run(dev, d, len, xz_cfg(s.ctx), [](const uint8_t *, uint64_t) { return true; }, st, bad); },
                                         "xz", "reads_open: xz data not accepted by the device (%s near file offset %llu)", xz_status_name);
     if (s.ctx->opt("VERBOSE")) fprintf(stderr, "[lrge_hip] reads_open: xz decode %.2f ms, block checks %.2f ms of the text-to-HBM share\n", dev.ms[1], dev.ms[2]);
@@ -798,13 +800,14 @@ static int fx_open_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, 
     const u8 *d = (const u8 *)file_bytes;
     std::unique_ptr<lrge_hip_reads, void (*)(lrge_hip_reads *)> guard(new lrge_hip_reads(), lrge_hip_reads_free);
     guard->ctx = ctx;
-    const auto b = [&](u64 i) -> u32 { return i < len ? d[i] : 0x100u; };
-    if (mode != FX_KEEP_ALL && b(0) == 'C' && b(1) == 'R' && b(2) == 'A' && b(3) == 'M') {     // (whatever the flags: FxWinDev::selected_format)
+    bool xz_whole;
+    const FxBox box = fx_container(d, len, &xz_whole);
+    if (mode != FX_KEEP_ALL && box == FX_BOX_CRAM) {     // (whatever the flags: FxWinDev::selected_format)
         ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only";
         return LRGE_ERR_UNPROVEN;
     }
     // unaligned CRAM, for the caller who asked for it: a host walk and a device decode of the base blocks, no text and no record scan
-    if ((flags & LRGE_GPU_INGEST_CRAM) && b(0) == 'C' && b(1) == 'R' && b(2) == 'A' && b(3) == 'M') {
+    if ((flags & LRGE_GPU_INGEST_CRAM) && box == FX_BOX_CRAM) {
         const int crc = fx_open_cram(ctx, guard.get(), d, len, t0);
         if (crc) return crc;
         *out = guard.release();
@@ -822,19 +825,18 @@ static int fx_open_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, 
         map->kind = FX_SEEK_OTHER; map->file_len = len;
         s.run->dev.map = map;
     }
-    if (mode != FX_KEEP_ALL && b(0) == 0x28 && b(1) == 0xb5 && b(2) == 0x2f && b(3) == 0xfd && (flags & LRGE_GPU_INFLATE_ZSTD) && !fx_zstd_slides(flags)) {
+    if (mode != FX_KEEP_ALL && box == FX_BOX_ZSTD && (flags & LRGE_GPU_INFLATE_ZSTD) && !fx_zstd_slides(flags)) {
         ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only, not Zstandard input";       // (its text is never windowed without LRGE_GPU_INGEST_WINDOWED_ZSTD)
         rc = LRGE_ERR_UNPROVEN;
-    } else if (b(0) == 0x1f && b(1) == 0x8b) {
+    } else if (box == FX_BOX_GZIP) {
         const bool bgzf = bgzf_scan_blocks(d, len, &t, &total);
         if (map && bgzf) { map->kind = FX_SEEK_BGZF; map->n_blocks = t.size(); }
         rc = bgzf ? fx_src_bgzf(s, d, t, total) : fx_src_gzip(s, d, len);
     }
-    else if (b(0) == 0x42 && b(1) == 0x5a && (flags & LRGE_GPU_INFLATE_BZIP2)) rc = fx_src_bzip2(s, d, len);
-    else if (b(0) == 0x28 && b(1) == 0xb5 && b(2) == 0x2f && b(3) == 0xfd && (flags & LRGE_GPU_INFLATE_ZSTD)) rc = fx_src_zstd(s, d, len);
-    else if (b(0) == 0xfd && b(1) == 0x37 && b(2) == 0x7a && b(3) == 0x58 && b(4) == 0x5a && b(5) == 0x00 && (flags & LRGE_GPU_INFLATE_XZ)) rc = fx_src_xz(s, d, len);
-    else if ((b(0) == 0x42 && b(1) == 0x5a) || (b(0) == 0x28 && b(1) == 0xb5 && b(2) == 0x2f && b(3) == 0xfd) ||
-             (b(0) == 0xfd && b(1) == 0x37 && b(2) == 0x7a && b(3) == 0x58 && b(4) == 0x5a)) {
+    else if (box == FX_BOX_BZIP2 && (flags & LRGE_GPU_INFLATE_BZIP2)) rc = fx_src_bzip2(s, d, len);
+    else if (box == FX_BOX_ZSTD && (flags & LRGE_GPU_INFLATE_ZSTD)) rc = fx_src_zstd(s, d, len);
+    else if (box == FX_BOX_XZ && xz_whole && (flags & LRGE_GPU_INFLATE_XZ)) rc = fx_src_xz(s, d, len);
+    else if (box == FX_BOX_BZIP2 || box == FX_BOX_ZSTD || box == FX_BOX_XZ) {
         ctx->err = "reads_open: bzip2, zstd and xz input is decompressed on the host";
         rc = LRGE_ERR_UNPROVEN;
     } else { if (map) map->kind = FX_SEEK_PLAIN; rc = fx_src_raw(s, d, len); }
@@ -1090,17 +1092,16 @@ static int fx_open_mapped(lrge_hip_ctx *ctx, FxInput &in, int flags, const lrge_
     u8 h[6] = {0, 0, 0, 0, 0, 0};
     const u64 nh = std::min<u64>(6, in.len);
     if (!in.read(0, nh, h)) return fx_read_failed(ctx);
-    const auto b = [&](u64 i) -> u32 { return i < nh ? h[i] : 0x100u; };
+    const FxBox box = fx_container(h, nh);
     // what the census and the selected open refuse by name, whatever the map
-    if (b(0) == 'C' && b(1) == 'R' && b(2) == 'A' && b(3) == 'M') { ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only"; return LRGE_ERR_UNPROVEN; }
-    if (b(0) == 0x28 && b(1) == 0xb5 && b(2) == 0x2f && b(3) == 0xfd && (flags & LRGE_GPU_INFLATE_ZSTD) && !fx_zstd_slides(flags)) {
+    if (box == FX_BOX_CRAM) { ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only"; return LRGE_ERR_UNPROVEN; }
+    if (box == FX_BOX_ZSTD && (flags & LRGE_GPU_INFLATE_ZSTD) && !fx_zstd_slides(flags)) {
         ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only, not Zstandard input";
         return LRGE_ERR_UNPROVEN;
     }
     const bool aln = (flags & LRGE_GPU_INGEST_BAM) && (flags & LRGE_GPU_INGEST_SELECT_ALN);
     if (m.fmt == FX_FMT_BAM && !aln) { ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only"; return LRGE_ERR_UNPROVEN; }      // (a BAM map: DESIGN section 25)
-    const bool gz = b(0) == 0x1f && b(1) == 0x8b, packed = gz || (b(0) == 0x42 && b(1) == 0x5a) || (b(0) == 0x28 && b(1) == 0xb5 && b(2) == 0x2f && b(3) == 0xfd) ||
-                                                   (b(0) == 0xfd && b(1) == 0x37 && b(2) == 0x7a && b(3) == 0x58 && b(4) == 0x5a);
+    const bool gz = box == FX_BOX_GZIP, packed = gz || box == FX_BOX_BZIP2 || box == FX_BOX_ZSTD || box == FX_BOX_XZ;
     std::vector<BgzfBlock> t;
     u64 total = 0;
     bool fits = m.file_len == in.len && (m.kind == FX_SEEK_PLAIN ? !packed && m.text_bytes == in.len : m.kind == FX_SEEK_BGZF ? gz : packed);

@@ -136,8 +136,8 @@ struct GzDev : DevKeep {
             !seg_crc.need(std::max<size_t>(1, ns) * 4, &e) || !err.need(4, &e) || !out.need(std::max<u64>(1, out_bytes), &e) ||
             !bigtab.need(std::max<size_t>(1, big_ptr.size()) * sizeof(void *), &e))
             return false;
-        u8 *h_out = keep_on ? nullptr : ctx_pin(1, std::max<u64>(1, out_bytes));
-        if (!h_out && !keep_on) return false;
+        u8 *h_out = to_host ? ctx_pin(1, std::max<u64>(1, out_bytes)) : nullptr;
+        if (!h_out && to_host) return false;
         hipStream_t st = ctx->stream;
         if (!ok(hipMemcpyAsync(links.p, l, (size_t)nl * sizeof(GzLink), hipMemcpyHostToDevice, st))) return false;
         if (!tl.empty() && !ok(hipMemcpyAsync(tiles.p, tl.data(), tl.size() * sizeof(GzTile), hipMemcpyHostToDevice, st))) return false;
@@ -155,7 +155,7 @@ struct GzDev : DevKeep {
         }
         if (ns && !ok(hipMemcpyAsync(seg_crc_h, seg_crc.p, (size_t)ns * 4, hipMemcpyDeviceToHost, st))) return false;
         if (!ok(hipMemcpyAsync(marker_err, err.p, 4, hipMemcpyDeviceToHost, st))) return false;
-        if (keep_on) {                                           // the round's bytes stay in HBM, behind what the earlier rounds left
+        if (!to_host) {                                          // the round's bytes stay in HBM, behind what the earlier rounds left
             if (!keep_reserve(out_bytes)) return false;
             if (out_bytes && !ok(hipMemcpyAsync(keep + keep_len, out.p, out_bytes, hipMemcpyDeviceToDevice, st))) return false;
             keep_len += out_bytes;
@@ -163,12 +163,12 @@ struct GzDev : DevKeep {
         }
         // the bytes travel on the side stream while the next round is staged and decoded (bytes_ready waits for them)
         if (!ok(hipEventRecord(ev_out, st)) || !ok(hipStreamWaitEvent(ctx->stream2, ev_out, 0))) return false;
-        if (!keep_on && out_bytes && !ok(hipMemcpyAsync(h_out, out.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream2))) return false;
+        if (to_host && out_bytes && !ok(hipMemcpyAsync(h_out, out.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream2))) return false;
         if (!ok(hipEventRecord(ev_out, ctx->stream2))) return false;
         if (!sync()) return false;
         if (*marker_err == 0xFFFFFFFFu) *marker_err = 0;
         drop_big();
-        *bytes = keep_on ? keep : h_out;
+        *bytes = to_host ? h_out : keep;
         return true;
     }
 };
@@ -178,37 +178,52 @@ static GzCfg gz_cfg(lrge_hip_ctx *ctx) {
     return GzCfg{ctx->opt_u64("GZIP_CHUNK_BYTES", (u64)512 << 10), ctx->opt_u64("GZIP_ROUND_BYTES", (u64)256 << 20), ctx->opt_u64("GZIP_SLOT_RATIO", 8)};
 }
 
+// ---- the common entry of the four round decoders (gzip, bzip2, Zstandard, xz) ----
+// What differs between them behind the driver: the name in the messages, the text of a driver status, and the status that means
+// "too big" (LRGE_ERR_TOO_MANY, with its message; 0: the codec has none)
+struct CodecText { const char *name; const char *(*status_name)(int); int too_big; const char *too_big_msg; };
+static_assert((int)GZ_RUN_OK == (int)BZ_RUN_OK && (int)GZ_RUN_DEVICE == (int)BZ_RUN_DEVICE && (int)GZ_RUN_OK == (int)ZS_RUN_OK && (int)GZ_RUN_DEVICE == (int)ZS_RUN_DEVICE &&
+              (int)GZ_RUN_OK == (int)XZ_RUN_OK && (int)GZ_RUN_DEVICE == (int)XZ_RUN_DEVICE, "one set of driver codes");
+// run(to_sink, &bad) drives the backend `dev` (gz_run, bz_run, zs_run, xz_run) with the C sink behind to_sink; done() copies the
+// stats out and prints the stage line while the backend still holds its times.  OK, a sink that stopped, a device failure, too
+// big and any other status become LRGE_OK, LRGE_ERR_IO, LRGE_ERR_DEVICE, LRGE_ERR_TOO_MANY and LRGE_ERR_PARSE
+template <class Dev, class Run, class Done>
+static int codec_inflate(Dev &dev, const CodecText &c, int (*sink)(void *, const void *, uint64_t), void *user, Run run, Done done) {
+    lrge_hip_ctx *ctx = dev.ctx;
+    u64 bad = 0;
+    bool sink_stop = false;
+    auto to_sink = [&](const uint8_t *b, uint64_t k) {
+        if (sink(user, b, k) != 0) { sink_stop = true; return false; }
+        return true;
+    };
+    const int rc = dev.e == hipSuccess ? run(to_sink, &bad) : (int)GZ_RUN_DEVICE;
+    if (rc == GZ_RUN_DEVICE && !sink_stop) {
+        LRGE_SET_ERR(ctx, "%s inflate: %s", c.name, hipGetErrorString(dev.e != hipSuccess ? dev.e : hipErrorUnknown));
+        (void)hipGetLastError();
+    }
+    (void)hipStreamSynchronize(ctx->stream);
+    done();
+    if (rc == GZ_RUN_OK) return LRGE_OK;
+    if (sink_stop) { LRGE_SET_ERR(ctx, "%s inflate: the sink stopped the call", c.name); return LRGE_ERR_IO; }
+    if (rc == GZ_RUN_DEVICE) return LRGE_ERR_DEVICE;
+    if (c.too_big && rc == c.too_big) { LRGE_SET_ERR(ctx, "%s inflate: %s", c.name, c.too_big_msg); return LRGE_ERR_TOO_MANY; }
+    LRGE_SET_ERR(ctx, "%s data at file offset %llu: %s", c.name, (unsigned long long)bad, c.status_name(rc));
+    return LRGE_ERR_PARSE;
+}
+
 // the whole gzip buffer through `sink`; LRGE_ERR_PARSE / TOO_MANY / DEVICE as lrge_hip_gzip_inflate
 static int gzip_inflate_impl(lrge_hip_ctx *ctx, const uint8_t *comp, uint64_t comp_len, int (*sink)(void *, const void *, uint64_t), void *user,
                              lrge_hip_gzip_stats *stats) {
     (void)hipSetDevice(ctx->device);
+    static const CodecText text = {"gzip", [](int s) { return gz_status_name((u32)s); }, GZ_RUN_TOO_MANY, "a chunk decodes to more symbols than its slot holds"};
     const GzCfg cfg = gz_cfg(ctx);
     GzStats st;
-    u64 bad = 0;
-    bool sink_stop = false;
-    int rc;
-    {
-        GzDev dev(ctx, cfg);
-        rc = dev.e == hipSuccess ? gz_run(dev, comp, comp_len, cfg, [&](const uint8_t *b, uint64_t k) {
-            if (sink(user, b, k) != 0) { sink_stop = true; return false; }
-            return true;
-        }, st, &bad) : (int)GZ_RUN_DEVICE;
-        if (rc == GZ_RUN_DEVICE && !sink_stop) {
-            LRGE_SET_ERR(ctx, "gzip inflate: %s", hipGetErrorString(dev.e != hipSuccess ? dev.e : hipErrorUnknown));
-            (void)hipGetLastError();
-        }
-        (void)hipStreamSynchronize(ctx->stream);
-    }
-    if (stats) {
+    GzDev dev(ctx, cfg);
+    return codec_inflate(dev, text, sink, user, [&](auto &to_sink, u64 *bad) { return gz_run(dev, comp, comp_len, cfg, to_sink, st, bad); }, [&] {
+        if (!stats) return;
         stats->members = st.members; stats->chunks = st.chunks; stats->speculative_starts = st.speculative; stats->rejected_starts = st.rejected;
         stats->redecoded_chunks = st.redecoded; stats->overflow_retries = st.overflow_retries; stats->bytes_out = st.bytes_out;
-    }
-    if (rc == GZ_RUN_OK) return LRGE_OK;
-    if (sink_stop) { ctx->err = "gzip inflate: the sink stopped the call"; return LRGE_ERR_IO; }
-    if (rc == GZ_RUN_DEVICE) return LRGE_ERR_DEVICE;
-    if (rc == GZ_RUN_TOO_MANY) { ctx->err = "gzip inflate: a chunk decodes to more symbols than its slot holds"; return LRGE_ERR_TOO_MANY; }
-    LRGE_SET_ERR(ctx, "gzip data at file offset %llu: %s", (unsigned long long)bad, gz_status_name((u32)rc));
-    return LRGE_ERR_PARSE;
+    });
 }
 
 extern "C" int lrge_hip_gzip_inflate(lrge_hip_ctx *ctx, const void *comp, uint64_t comp_len, int (*sink)(void *user, const void *bytes, uint64_t n),
@@ -234,45 +249,27 @@ extern "C" int lrge_hip_read_records_gpu_ex(lrge_hip_ctx *ctx, const char *path,
     if (used_device) *used_device = 0;
     struct DeviceFail { int rc; };
     int used = 0;
+    // a round decoder behind the hook, when the caller's flags name it: false for input the device does not accept or cannot prove
+    // (the host path, with its messages)
+    const auto through = [&](int flag, auto impl, const std::string &raw, std::string &data) -> bool {
+        if (!(flags & flag)) return false;
+        data.clear();
+        const int rc = impl(ctx, (const uint8_t *)raw.data(), raw.size(), [](void *u, const void *b, uint64_t k) {
+            ((std::string *)u)->append((const char *)b, (size_t)k);
+            return 0;
+        }, &data, nullptr);
+        if (rc == LRGE_ERR_DEVICE) throw DeviceFail{rc};
+        if (rc != LRGE_OK) { data.clear(); return false; }
+        used = 1;
+        return true;
+    };
     try {
         lrge::io::iter_records(path, [&](const std::string &n, const std::string &s) { cb(user, n.data(), (uint64_t)n.size(), s.data(), (uint64_t)s.size()); },
                                [&](const std::string &raw, std::string &data) -> bool {
-            if (lrge::io::detect_compression_format(raw) == lrge::io::CompressionFormat::Bzip2) {
-                if (!(flags & LRGE_GPU_INFLATE_BZIP2)) return false;
-                data.clear();
-                const int rc = bzip2_inflate_impl(ctx, (const uint8_t *)raw.data(), raw.size(), [](void *u, const void *b, uint64_t k) {
-                    ((std::string *)u)->append((const char *)b, (size_t)k);
-                    return 0;
-                }, &data, nullptr);
-                if (rc == LRGE_ERR_DEVICE) throw DeviceFail{rc};
-                if (rc != LRGE_OK) { data.clear(); return false; }     // not accepted by the device: the host path, with its messages
-                used = 1;
-                return true;
-            }
-            if (lrge::io::detect_compression_format(raw) == lrge::io::CompressionFormat::Zstd) {
-                if (!(flags & LRGE_GPU_INFLATE_ZSTD)) return false;
-                data.clear();
-                const int rc = zstd_inflate_impl(ctx, (const uint8_t *)raw.data(), raw.size(), [](void *u, const void *b, uint64_t k) {
-                    ((std::string *)u)->append((const char *)b, (size_t)k);
-                    return 0;
-                }, &data, nullptr);
-                if (rc == LRGE_ERR_DEVICE) throw DeviceFail{rc};
-                if (rc != LRGE_OK) { data.clear(); return false; }     // not accepted by the device: the host path, with its messages
-                used = 1;
-                return true;
-            }
-            if (lrge::io::detect_compression_format(raw) == lrge::io::CompressionFormat::Xz) {
-                if (!(flags & LRGE_GPU_INFLATE_XZ)) return false;
-                data.clear();
-                const int rc = xz_inflate_impl(ctx, (const uint8_t *)raw.data(), raw.size(), [](void *u, const void *b, uint64_t k) {
-                    ((std::string *)u)->append((const char *)b, (size_t)k);
-                    return 0;
-                }, &data, nullptr);
-                if (rc == LRGE_ERR_DEVICE) throw DeviceFail{rc};
-                if (rc != LRGE_OK) { data.clear(); return false; }     // not accepted by the device: the host path, with its messages
-                used = 1;
-                return true;
-            }
+            const lrge::io::CompressionFormat fmt = lrge::io::detect_compression_format(raw);
+            if (fmt == lrge::io::CompressionFormat::Bzip2) return through(LRGE_GPU_INFLATE_BZIP2, bzip2_inflate_impl, raw, data);
+            if (fmt == lrge::io::CompressionFormat::Zstd) return through(LRGE_GPU_INFLATE_ZSTD, zstd_inflate_impl, raw, data);
+            if (fmt == lrge::io::CompressionFormat::Xz) return through(LRGE_GPU_INFLATE_XZ, xz_inflate_impl, raw, data);
             std::vector<BgzfBlock> t;
             uint64_t total = 0;
             if (bgzf_scan_blocks((const uint8_t *)raw.data(), raw.size(), &t, &total)) {
@@ -284,16 +281,7 @@ extern "C" int lrge_hip_read_records_gpu_ex(lrge_hip_ctx *ctx, const char *path,
                 used = 1;
                 return true;
             }
-            if (!(flags & LRGE_GPU_INFLATE_GZIP)) return false;
-            data.clear();
-            const int rc = gzip_inflate_impl(ctx, (const uint8_t *)raw.data(), raw.size(), [](void *u, const void *b, uint64_t k) {
-                ((std::string *)u)->append((const char *)b, (size_t)k);
-                return 0;
-            }, &data, nullptr);
-            if (rc == LRGE_ERR_DEVICE) throw DeviceFail{rc};
-            if (rc != LRGE_OK) { data.clear(); return false; }     // not provable on the device: the host path, with its messages
-            used = 1;
-            return true;
+            return through(LRGE_GPU_INFLATE_GZIP, gzip_inflate_impl, raw, data);
         });
     } catch (const DeviceFail &) {
         return LRGE_ERR_DEVICE;

@@ -40,36 +40,29 @@ static const char *xz_status_name(int s) {
 namespace {
 struct XzDev : DevKeep {
     GzBuf in, table, tasks, slots, status, spans, crc;
-    bool timing = false, to_host = true;
+    bool timing = false;
     double ms[3] = {0, 0, 0};                                      // upload, decode, check
     explicit XzDev(lrge_hip_ctx *c) : DevKeep(c) {
         for (GzBuf *b : {&in, &table, &tasks, &slots, &status, &spans, &crc}) b->ctx = c;
         timing = c->opt("XZ_TIMING") != nullptr;
-        keep_on = true;
     }
     ~XzDev() { (void)hipStreamSynchronize(ctx->stream); }
     bool over() const { return keep_over; }
     bool load(const uint8_t *d, uint64_t len, const XzChunk *c, uint64_t n_chunks) {
-        const double t0 = DevPool::now_ms();
+        Lap lap(*this, ms[0], true);                               // (always: the stream is drained here whether the time is wanted or not)
         if (!in.need((size_t)len + 16, &e) || !table.need((size_t)(n_chunks + 1) * sizeof(XzChunk), &e)) return false;
         if (len && !ok(hipMemcpyAsync(in.p, d, (size_t)len, hipMemcpyHostToDevice, ctx->stream))) return false;
         if (n_chunks && !ok(hipMemcpyAsync(table.p, c, (size_t)n_chunks * sizeof(XzChunk), hipMemcpyHostToDevice, ctx->stream))) return false;
-        const bool r = sync();
-        ms[0] += DevPool::now_ms() - t0;
-        return r;
+        return lap.end();
     }
-    uint32_t default_round(uint64_t block_bytes) {
-        size_t mfree = 0, mtot = 0;
-        if (hipMemGetInfo(&mfree, &mtot) != hipSuccess) { (void)hipGetLastError(); mfree = 0; }
-        return (uint32_t)std::min<u64>(XZ_ROUND_MAX, std::max<u64>(1, ((u64)mfree + ctx->pool.idle()) / 2 / (block_bytes + XZ_SLOT_BYTES)));
-    }
+    uint32_t default_round(uint64_t block_bytes) { return (uint32_t)std::min<u64>(XZ_ROUND_MAX, std::max<u64>(1, dev_budget(ctx) / (block_bytes + XZ_SLOT_BYTES))); }
     bool reserve(uint64_t bytes, uint32_t k) {
         if (!keep_reserve(bytes)) return false;
         if (!slots.need((size_t)k * XZ_SLOT_BYTES, &e)) return false;
         return ok(hipMemsetAsync(slots.p, 0, (size_t)k * XZ_SLOT_BYTES, ctx->stream));
     }
     bool decode(const XzTask *t, uint32_t m, uint32_t *st_h, uint32_t *bad_h) {
-        const double t0 = DevPool::now_ms();
+        Lap lap(*this, ms[1], true);
         hipStream_t st = ctx->stream;
         if (!tasks.need((size_t)m * sizeof(XzTask), &e) || !status.need((size_t)m * 8, &e)) return false;
         if (!ok(hipMemcpyAsync(tasks.p, t, (size_t)m * sizeof(XzTask), hipMemcpyHostToDevice, st)) || !ok(hipMemsetAsync(status.p, 0, (size_t)m * 8, st))) return false;
@@ -77,31 +70,23 @@ struct XzDev : DevKeep {
                            status.as<u32>(), status.as<u32>() + m);
         if (!ok(hipGetLastError())) return false;
         if (!ok(hipMemcpyAsync(st_h, status.p, (size_t)m * 4, hipMemcpyDeviceToHost, st)) ||
-            !ok(hipMemcpyAsync(bad_h, status.as<u32>() + m, (size_t)m * 4, hipMemcpyDeviceToHost, st)) || !sync())
+            !ok(hipMemcpyAsync(bad_h, status.as<u32>() + m, (size_t)m * 4, hipMemcpyDeviceToHost, st)))
             return false;
-        ms[1] += DevPool::now_ms() - t0;
-        return true;
+        return lap.end();
     }
     bool check(const XzSpan *s, uint32_t m, uint64_t *c) {
-        const double t0 = DevPool::now_ms();
+        Lap lap(*this, ms[2], true);
         if (!spans.need((size_t)m * sizeof(XzSpan), &e) || !crc.need((size_t)m * 8, &e)) return false;
         if (!ok(hipMemcpyAsync(spans.p, s, (size_t)m * sizeof(XzSpan), hipMemcpyHostToDevice, ctx->stream))) return false;
         hipLaunchKernelGGL(k_xz_check, dim3(m), dim3(64), 0, ctx->stream, (const u8 *)(keep + keep_len), spans.as<const XzSpan>(), m, crc.as<u64>());
         if (!ok(hipGetLastError())) return false;
-        if (!ok(hipMemcpyAsync(c, crc.p, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream)) || !sync()) return false;
-        ms[2] += DevPool::now_ms() - t0;
-        return true;
+        if (!ok(hipMemcpyAsync(c, crc.p, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream))) return false;
+        return lap.end();
     }
     const uint8_t *commit(uint64_t bytes) {
-        if (!to_host) {                                            // the text stays: the sink does not read it
-            keep_len += bytes;
-            if (keep_flush && !keep_flush()) return nullptr;
-            return keep ? keep : (const uint8_t *)this;
-        }
-        u8 *h = ctx_pin(1, std::max<u64>(1, bytes));
-        if (!h) return nullptr;
-        if (bytes && (!ok(hipMemcpyAsync(h, keep + keep_len, (size_t)bytes, hipMemcpyDeviceToHost, ctx->stream)) || !sync())) return nullptr;
-        return h;                                                  // (keep_len stays: the next round takes the same room)
+        const u8 *round = keep + keep_len;
+        if (!to_host) keep_len += bytes;                           // (to the host keep_len stays: the next round takes the same room)
+        return deliver(round, bytes);
     }
 };
 
@@ -120,33 +105,14 @@ static void xz_stats_out(const XzStats &st, const XzDev &dev, lrge_hip_xz_stats 
 static int xz_inflate_impl(lrge_hip_ctx *ctx, const uint8_t *comp, uint64_t comp_len, int (*sink)(void *, const void *, uint64_t), void *user,
                            lrge_hip_xz_stats *stats) {
     (void)hipSetDevice(ctx->device);
+    static const CodecText text = {"xz", xz_status_name, XZ_E_TOO_BIG, "the text does not fit the device budget"};
     XzStats st;
-    u64 bad = 0;
-    bool sink_stop = false;
-    int rc;
-    {
-        XzDev dev(ctx);
-        size_t mfree = 0, mtot = 0;
-        if (hipMemGetInfo(&mfree, &mtot) != hipSuccess) { (void)hipGetLastError(); mfree = 0; }
-        dev.keep_max = ((u64)mfree + ctx->pool.idle()) / 2;              // (a round's text; the ingest cap's default: host_fastx.inl)
-        rc = xz_run(dev, comp, comp_len, xz_cfg(ctx), [&](const uint8_t *b, uint64_t k) {
-            if (sink(user, b, k) != 0) { sink_stop = true; return false; }
-            return true;
-        }, st, &bad);
-        if (rc == XZ_RUN_DEVICE && !sink_stop) {
-            LRGE_SET_ERR(ctx, "xz inflate: %s", hipGetErrorString(dev.e != hipSuccess ? dev.e : hipErrorUnknown));
-            (void)hipGetLastError();
-        }
-        (void)hipStreamSynchronize(ctx->stream);
+    XzDev dev(ctx);
+    dev.keep_max = dev_budget(ctx);                                     // (a round's text; the ingest cap's default: host_fastx.inl)
+    return codec_inflate(dev, text, sink, user, [&](auto &to_sink, u64 *bad) { return xz_run(dev, comp, comp_len, xz_cfg(ctx), to_sink, st, bad); }, [&] {
         if (dev.timing) fprintf(stderr, "[lrge_hip] xz stages ms: walk %.3f upload %.3f decode %.3f check %.3f\n", st.walk_us / 1000.0, dev.ms[0], dev.ms[1], dev.ms[2]);
         xz_stats_out(st, dev, stats);
-    }
-    if (rc == XZ_RUN_OK) return LRGE_OK;
-    if (sink_stop) { ctx->err = "xz inflate: the sink stopped the call"; return LRGE_ERR_IO; }
-    if (rc == XZ_RUN_DEVICE) return LRGE_ERR_DEVICE;
-    if (rc == XZ_E_TOO_BIG) { ctx->err = "xz inflate: the text does not fit the device budget"; return LRGE_ERR_TOO_MANY; }
-    LRGE_SET_ERR(ctx, "xz data at file offset %llu: %s", (unsigned long long)bad, xz_status_name(rc));
-    return LRGE_ERR_PARSE;
+    });
 }
 
 extern "C" int lrge_hip_xz_inflate(lrge_hip_ctx *ctx, const void *comp, uint64_t comp_len, int (*sink)(void *user, const void *bytes, uint64_t n),

@@ -48,19 +48,13 @@ struct ZsDev : DevKeep {
     u64 slide_window = 0;                                        // the ingest's window: a round's text stays below it (default_round)
     u64 work_text = 0, work_len = 0, hist = 0, keep_hist = 0;
     std::function<bool(u64)> work_budget;                        // the work block's bytes, taken from the budget the caller shares out (false: above it)
-    bool timing = false, to_host = true;
+    bool timing = false;
     double ms[6] = {0, 0, 0, 0, 0, 0};                           // heads, literals, sequences, execute, resolve, checksum
     explicit ZsDev(lrge_hip_ctx *c) : DevKeep(c) {
         for (GzBuf *b : {&in, &blocks, &hbuf, &lit, &seq, &res, &status, &org, &groups, &hash, &work, &xstate}) b->ctx = c;
         timing = c->opt("ZSTD_TIMING") != nullptr;
-        keep_on = true;
     }
     ~ZsDev() { (void)hipStreamSynchronize(ctx->stream); }
-    struct Lap {
-        ZsDev &d; int slot; bool on; double t0;
-        Lap(ZsDev &dev, int s, bool always = false) : d(dev), slot(s), on(dev.timing || always), t0(on ? DevPool::now_ms() : 0) {}
-        bool end() { if (!on) return true; const bool r = d.sync(); d.ms[slot] += DevPool::now_ms() - t0; return r; }
-    };
     bool over() const { return keep_over; }
     bool load(const uint8_t *d, uint64_t len) {
         n = len;
@@ -70,9 +64,7 @@ struct ZsDev : DevKeep {
         return sync();
     }
     uint32_t default_round() {
-        size_t mfree = 0, mtot = 0;
-        if (hipMemGetInfo(&mfree, &mtot) != hipSuccess) { (void)hipGetLastError(); mfree = 0; }
-        const u64 k = std::min<u64>(ZS_ROUND_MAX, std::max<u64>(1, ((u64)mfree + ctx->pool.idle()) / 2 / (zs_block_bytes() + ZS_BLOCK_MAX)));
+        const u64 k = std::min<u64>(ZS_ROUND_MAX, std::max<u64>(1, dev_budget(ctx) / (zs_block_bytes() + ZS_BLOCK_MAX)));
         return (uint32_t)(sliding ? std::min<u64>(k, std::max<u64>(1, slide_window / ZS_BLOCK_MAX)) : k);
     }
     bool slides() const { return sliding; }
@@ -103,7 +95,7 @@ struct ZsDev : DevKeep {
         return !keep_flush || keep_flush();
     }
     bool xxh64_part(const ZsXxhJob *job, uint32_t m, uint64_t *h) {
-        Lap lap(*this, 5, true);
+        Lap lap(*this, ms[5], true);
         for (uint32_t i = 0; i < m; ++i) if (job[i].at + job[i].len > work_len) return false;                 // (never)
         if (!hash.need((size_t)m * (sizeof(ZsXxhJob) + 8), &e)) return false;
         u64 *out = (u64 *)(hash.as<ZsXxhJob>() + m);
@@ -117,7 +109,7 @@ struct ZsDev : DevKeep {
         return blocks.need((size_t)k * sizeof(ZsBlock), &e) && ok(hipMemcpyAsync(blocks.p, b, (size_t)k * sizeof(ZsBlock), hipMemcpyHostToDevice, ctx->stream));
     }
     bool heads(ZsBlock *b, uint32_t k) {
-        Lap lap(*this, 0);
+        Lap lap(*this, ms[0], timing);
         if (!put_blocks(b, k) || !hbuf.need((size_t)k * sizeof(ZsHead), &e)) return false;
         hipLaunchKernelGGL(k_zs_heads, dim3((u32)div_up(k, 64)), dim3(64), 0, ctx->stream, in.as<const u8>(), blocks.as<const ZsBlock>(), k, hbuf.as<ZsHead>());
         if (!ok(hipGetLastError())) return false;
@@ -133,11 +125,11 @@ struct ZsDev : DevKeep {
             return false;
         if (!ok(hipMemsetAsync(status.p, 0, (size_t)k * 4, st)) || !ok(hipMemsetAsync(res.p, 0, (size_t)k * sizeof(ZsSeqRes), st))) return false;
         {
-            Lap lap(*this, 1);
+            Lap lap(*this, ms[1], timing);
             hipLaunchKernelGGL(k_zs_literals, dim3(k), dim3(64), 0, st, in.as<const u8>(), n, blocks.as<const ZsBlock>(), k, lit.as<u8>(), status.as<u32>());
             if (!ok(hipGetLastError()) || !lap.end()) return false;
         }
-        Lap lap(*this, 2);
+        Lap lap(*this, ms[2], timing);
         hipLaunchKernelGGL(k_zs_sequences, dim3(k), dim3(64), 0, st, in.as<const u8>(), n, blocks.as<const ZsBlock>(), k, seq.as<ZsSeq>(), res.as<ZsSeqRes>());
         if (!ok(hipGetLastError())) return false;
         if (!ok(hipMemcpyAsync(lit_status, status.p, (size_t)k * 4, hipMemcpyDeviceToHost, st)) || !ok(hipMemcpyAsync(r, res.p, (size_t)k * sizeof(ZsSeqRes), hipMemcpyDeviceToHost, st)) ||
@@ -153,21 +145,21 @@ struct ZsDev : DevKeep {
         u8 *const text = sliding ? work.as<u8>() : keep;
         const u64 base = sliding ? hist : keep_len;
         {
-            Lap lap(*this, 3);
+            Lap lap(*this, ms[3], timing);
             hipLaunchKernelGGL(k_zs_execute, dim3(k), dim3(64), 0, st, in.as<const u8>(), blocks.as<const ZsBlock>(), k, lit.as<const u8>(), seq.as<const ZsSeq>(), text, org.as<u32>(),
                                base, status.as<u32>());
             if (!ok(hipGetLastError())) return false;
             if (!ok(hipMemcpyAsync(st_h, status.p, (size_t)k * 4, hipMemcpyDeviceToHost, st)) || !sync() || !lap.end()) return false;
         }
         for (uint32_t j = 0; j < k; ++j) if (st_h[j]) return true;         // (no block's origins are resolved when one of them is damaged)
-        Lap lap(*this, 4);
+        Lap lap(*this, ms[4], timing);
         hipLaunchKernelGGL(k_zs_resolve, dim3(n_groups), dim3(ZS_RESOLVE_THREADS), 0, st, blocks.as<const ZsBlock>(), groups.as<const u32>(), text, org.as<const u32>(), base);
         if (!ok(hipGetLastError()) || !lap.end()) return false;
         if (!sliding) keep_len += bytes;                             // (sliding: retire() appends the round)
         return true;
     }
     bool xxh64(const uint64_t *at, const uint64_t *len, uint32_t m, uint64_t *h) {
-        Lap lap(*this, 5, true);
+        Lap lap(*this, ms[5], true);
         std::vector<u64> span(2 * (size_t)m);
         for (uint32_t i = 0; i < m; ++i) { span[2 * i] = at[i]; span[2 * i + 1] = len[i]; }
         if (!hash.need((size_t)m * 24, &e)) return false;
@@ -177,13 +169,8 @@ struct ZsDev : DevKeep {
         if (!ok(hipMemcpyAsync(h, hash.as<u64>() + 2 * (size_t)m, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream)) || !sync()) return false;
         return lap.end();
     }
-    const uint8_t *bytes(uint64_t at, uint64_t len) {
-        if (!to_host) return keep ? keep : (const uint8_t *)this;      // (the text stays: the sink does not read it)
-        u8 *h = ctx_pin(1, std::max<u64>(1, len));
-        if (!h) return nullptr;
-        if (!ok(hipMemcpyAsync(h, (sliding ? work.as<const u8>() : keep) + at, (size_t)len, hipMemcpyDeviceToHost, ctx->stream)) || !sync()) return nullptr;
-        return h;
-    }
+    // (the text that stays has been flushed by retire(), where it slides; else nothing flushes it)
+    const uint8_t *bytes(uint64_t at, uint64_t len) { return deliver((sliding ? work.as<const u8>() : keep) + at, len, false); }
 };
 
 static bool zs_checksum_on(lrge_hip_ctx *ctx) { return ctx->opt_u64("ZSTD_CHECKSUM", 1) != 0; }
@@ -199,34 +186,17 @@ static void zs_stats_out(const ZsStats &st, const ZsDev &dev, lrge_hip_zstd_stat
 static int zstd_inflate_impl(lrge_hip_ctx *ctx, const uint8_t *comp, uint64_t comp_len, int (*sink)(void *, const void *, uint64_t), void *user,
                              lrge_hip_zstd_stats *stats) {
     (void)hipSetDevice(ctx->device);
+    static const CodecText text = {"zstd", zs_status_name, ZS_E_TOO_BIG, "the text does not fit the device budget"};
     ZsStats st;
-    u64 bad = 0;
-    bool sink_stop = false;
-    int rc;
-    {
-        ZsDev dev(ctx);
-        size_t mfree = 0, mtot = 0;
-        if (hipMemGetInfo(&mfree, &mtot) != hipSuccess) { (void)hipGetLastError(); mfree = 0; }
-        dev.keep_max = ((u64)mfree + ctx->pool.idle()) / 2;            // (the ingest cap's default: host_fastx.inl)
-        rc = zs_run(dev, comp, comp_len, ctx->opt_u64("ZSTD_ROUND_BLOCKS", 0), zs_checksum_on(ctx), [&](const uint8_t *b, uint64_t k) {
-            if (sink(user, b, k) != 0) { sink_stop = true; return false; }
-            return true;
-        }, st, &bad);
-        if (rc == ZS_RUN_DEVICE && !sink_stop) {
-            LRGE_SET_ERR(ctx, "zstd inflate: %s", hipGetErrorString(dev.e != hipSuccess ? dev.e : hipErrorUnknown));
-            (void)hipGetLastError();
-        }
-        (void)hipStreamSynchronize(ctx->stream);
+    ZsDev dev(ctx);
+    dev.keep_max = dev_budget(ctx);                                   // (the ingest cap's default: host_fastx.inl)
+    return codec_inflate(dev, text, sink, user, [&](auto &to_sink, u64 *bad) {
+        return zs_run(dev, comp, comp_len, ctx->opt_u64("ZSTD_ROUND_BLOCKS", 0), zs_checksum_on(ctx), to_sink, st, bad);
+    }, [&] {
         if (dev.timing) fprintf(stderr, "[lrge_hip] zstd stages ms: heads %.3f literals %.3f sequences %.3f execute %.3f resolve %.3f checksum %.3f\n", dev.ms[0], dev.ms[1],
                                 dev.ms[2], dev.ms[3], dev.ms[4], dev.ms[5]);
         zs_stats_out(st, dev, stats);
-    }
-    if (rc == ZS_RUN_OK) return LRGE_OK;
-    if (sink_stop) { ctx->err = "zstd inflate: the sink stopped the call"; return LRGE_ERR_IO; }
-    if (rc == ZS_RUN_DEVICE) return LRGE_ERR_DEVICE;
-    if (rc == ZS_E_TOO_BIG) { ctx->err = "zstd inflate: the text does not fit the device budget"; return LRGE_ERR_TOO_MANY; }
-    LRGE_SET_ERR(ctx, "zstd data at file offset %llu: %s", (unsigned long long)bad, zs_status_name(rc));
-    return LRGE_ERR_PARSE;
+    });
 }
 
 extern "C" int lrge_hip_zstd_inflate(lrge_hip_ctx *ctx, const void *comp, uint64_t comp_len, int (*sink)(void *user, const void *bytes, uint64_t n),

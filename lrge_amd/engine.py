@@ -75,10 +75,8 @@ class Context:
         self._check(self._lib.lrge_hip_bgzf_inflate(self.h, data, len(data), out, total.value))
         return out.raw[:total.value]
 
-    def gzip_inflate(self, data, stats=False):
-        """Any gzip buffer (plain, multi-member or BGZF) decompressed on the device (lrge_hip_gzip_inflate); bytes in, bytes
-        out.  Damaged or trailing data raises LrgeHipError with code ERR_PARSE, a chunk beyond its slot ERR_TOO_MANY.
-        stats=True returns (bytes, dict of lrge_hip_gzip_stats)."""
+    def _stream_inflate(self, fn, data, stat_names):
+        """One round decoder's C entry `fn` over `data`, its rounds collected by a sink: (bytes, dict of its stats)."""
         data = bytes(data)
         parts = []
 
@@ -86,59 +84,35 @@ class Context:
             parts.append(C.string_at(p, n))
             return 0
         cb = _ffi.GZIP_SINK(sink)
-        st = (C.c_uint64 * 7)()
-        self._check(self._lib.lrge_hip_gzip_inflate(self.h, data, len(data), cb, None, C.cast(st, C.c_void_p)))
-        out = b"".join(parts)
-        if not stats:
-            return out
-        keys = ("members", "chunks", "speculative_starts", "rejected_starts", "redecoded_chunks", "overflow_retries", "bytes_out")
-        return out, dict(zip(keys, list(st)))
+        st = (C.c_uint64 * len(stat_names))()
+        self._check(fn(self.h, data, len(data), cb, None, C.cast(st, C.c_void_p)))
+        return b"".join(parts), dict(zip(stat_names, list(st)))
+
+    def gzip_inflate(self, data, stats=False):
+        """Any gzip buffer (plain, multi-member or BGZF) decompressed on the device (lrge_hip_gzip_inflate); bytes in, bytes
+        out.  Damaged or trailing data raises LrgeHipError with code ERR_PARSE, a chunk beyond its slot ERR_TOO_MANY.
+        stats=True returns (bytes, dict of lrge_hip_gzip_stats)."""
+        out, st = self._stream_inflate(self._lib.lrge_hip_gzip_inflate, data, _ffi.GZIP_STAT_NAMES)
+        return (out, st) if stats else out
 
     def bzip2_inflate(self, data):
         """A bzip2 buffer (one stream) decompressed on the device (lrge_hip_bzip2_inflate): bytes in, (bytes, dict of
         lrge_hip_bzip2_stats) out.  Input the device does not accept (damage, a second stream, trailing bytes, a randomised
         block) raises LrgeHipError with code ERR_PARSE."""
-        data = bytes(data)
-        parts = []
-
-        def sink(_user, p, n):
-            parts.append(C.string_at(p, n))
-            return 0
-        cb = _ffi.GZIP_SINK(sink)
-        st = (C.c_uint64 * len(_ffi.BZIP2_STAT_NAMES))()
-        self._check(self._lib.lrge_hip_bzip2_inflate(self.h, data, len(data), cb, None, C.cast(st, C.c_void_p)))
-        return b"".join(parts), dict(zip(_ffi.BZIP2_STAT_NAMES, list(st)))
+        return self._stream_inflate(self._lib.lrge_hip_bzip2_inflate, data, _ffi.BZIP2_STAT_NAMES)
 
     def zstd_inflate(self, data):
         """A Zstandard buffer (frames and skippable frames back to back) decompressed on the device (lrge_hip_zstd_inflate):
         bytes in, (bytes, dict of lrge_hip_zstd_stats) out.  Input the device does not accept (damage, a dictionary, a window
         above 2^27 bytes, trailing bytes) raises LrgeHipError with code ERR_PARSE; text above the device budget ERR_TOO_MANY."""
-        data = bytes(data)
-        parts = []
-
-        def sink(_user, p, n):
-            parts.append(C.string_at(p, n))
-            return 0
-        cb = _ffi.GZIP_SINK(sink)
-        st = (C.c_uint64 * len(_ffi.ZSTD_STAT_NAMES))()
-        self._check(self._lib.lrge_hip_zstd_inflate(self.h, data, len(data), cb, None, C.cast(st, C.c_void_p)))
-        return b"".join(parts), dict(zip(_ffi.ZSTD_STAT_NAMES, list(st)))
+        return self._stream_inflate(self._lib.lrge_hip_zstd_inflate, data, _ffi.ZSTD_STAT_NAMES)
 
     def xz_inflate(self, data):
         """An .xz buffer (streams and stream padding back to back) decompressed on the device (lrge_hip_xz_inflate): bytes in,
         (bytes, dict of lrge_hip_xz_stats) out.  Input the device does not accept (damage, a filter other than LZMA2, a SHA-256
         check, trailing bytes, fewer blocks than option XZ_MIN_BLOCKS) raises LrgeHipError with code ERR_PARSE; a round's text
         above the device budget ERR_TOO_MANY."""
-        data = bytes(data)
-        parts = []
-
-        def sink(_user, p, n):
-            parts.append(C.string_at(p, n))
-            return 0
-        cb = _ffi.GZIP_SINK(sink)
-        st = (C.c_uint64 * len(_ffi.XZ_STAT_NAMES))()
-        self._check(self._lib.lrge_hip_xz_inflate(self.h, data, len(data), cb, None, C.cast(st, C.c_void_p)))
-        return b"".join(parts), dict(zip(_ffi.XZ_STAT_NAMES, list(st)))
+        return self._stream_inflate(self._lib.lrge_hip_xz_inflate, data, _ffi.XZ_STAT_NAMES)
 
     def rans_decode(self, streams, comp=None):
         """A batch of independent rANS streams decoded on the device (lrge_hip_rans_decode, the unit of the CRAM ingest).  streams:
