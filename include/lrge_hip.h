@@ -620,7 +620,8 @@ void     lrge_hip_reads_free(lrge_hip_reads *reads);
    empty handle, and the pass still proves the file.  LRGE_ERR_INVALID, before any handle is handed out: ordinals that are not
    strictly ascending; an ordinal at or above the number of records the pass saw (the message names the ordinal and the count).
    LRGE_ERR_UNPROVEN for both, whatever the flags: text whose first bytes say BAM, SAM or CRAM ("selected ingest takes FASTA /
-   FASTQ only"; BAM is taken with LRGE_GPU_INGEST_SELECT_ALN beside LRGE_GPU_INGEST_BAM, below), Zstandard input (its text is never
+   FASTQ only"; BAM is taken with LRGE_GPU_INGEST_SELECT_ALN beside LRGE_GPU_INGEST_BAM, SAM with LRGE_GPU_INGEST_SELECT_SAM beside
+   LRGE_GPU_INGEST_SAM, CRAM with LRGE_GPU_INGEST_SELECT_CRAM beside LRGE_GPU_INGEST_CRAM, below), Zstandard input (its text is never
    windowed without LRGE_GPU_INGEST_WINDOWED_ZSTD, below); everything else as lrge_hip_reads_open*.
    lrge_hip_reads_select_stats: out[0] records seen, out[1] records kept, out[2] sequence bases seen, out[3] bases kept by the
    pass that made the handle; zeros for a handle of lrge_hip_reads_open*. */
@@ -672,7 +673,7 @@ int      lrge_hip_reads_seek_stats(const lrge_hip_reads *reads, uint64_t out[4])
    _open_selected*, _census_map* and _open_mapped*; without it every call does what it did, the refusal text included): text whose
    first bytes are "BAM\1" is a BAM run in those six calls.  It passes through the windows of DESIGN section 18 whatever
    LRGE_GPU_INGEST_WINDOWED / _WINDOWED_ALN say, from the sources of the FASTA / FASTQ sampled calls (plain, BGZF, gzip, bzip2, xz);
-   SAM, CRAM and Zstandard stay refused with the same texts.  The count and the records sel[j] are those of lrge_hip_read_records on
+   SAM (without LRGE_GPU_INGEST_SELECT_SAM, below), CRAM (without LRGE_GPU_INGEST_SELECT_CRAM, below) and Zstandard stay refused with the same texts.  The count and the records sel[j] are those of lrge_hip_read_records on
    the same bytes, or the call is LRGE_ERR_UNPROVEN (a mapped record, a damaged record, 1-3 trailing bytes, in whichever window) and
    hands out no handle.  A header that ends the text is an empty census and an empty handle.  The handle is the windowed BAM handle
    restricted to the chosen reads: (l_seq + 1) / 2 packed bytes a chosen record, dense, in file order, the pad nibble as it is;
@@ -681,6 +682,47 @@ int      lrge_hip_reads_seek_stats(const lrge_hip_reads *reads, uint64_t out[4])
    count store bytes.  A point of the seek map is a record's block_size field, the first point record 0 behind the header; a mapped
    open of a BAM map without both flags is refused as the census is. */
 #define LRGE_GPU_INGEST_SELECT_ALN 1024
+
+/* The sampled ingest of unaligned SAM (the windows of section 18 in the keep modes, k_fx_bases behind k_sam_records,
+   k_fx_pick, k_fx_keep, k_fx_seek; no kernel of its own): what samtools and dorado write as text (io.rs:92-96, 154-184).
+   | LRGE_GPU_INGEST_SELECT_SAM (opt-in; it has effect only beside LRGE_GPU_INGEST_SAM and only in lrge_hip_reads_census*,
+   _open_selected*, _census_map* and _open_mapped*; without it every call does what it did, the refusal text included): text that
+   starts with "@HD", "@SQ" or "@RG" is a SAM run in those calls.  It passes through the windows of DESIGN section 18 whatever
+   LRGE_GPU_INGEST_WINDOWED / _WINDOWED_ALN say, from the sources of the FASTA / FASTQ sampled calls (plain, BGZF, gzip, bzip2, xz,
+   sliding Zstandard).  The count and the records sel[j] are those of lrge_hip_read_records on the same bytes, or the call is
+   LRGE_ERR_UNPROVEN (a record line with fewer than ten tabs, a bad flag, a mapped record, in whichever window) and hands out no
+   handle.  A header that ends the text is an empty census and an empty handle.  The handle is the windowed SAM handle restricted to
+   the chosen reads: their bases as ASCII, dense, in file order ("*" is length 0); lrge_hip_seqset_from_reads, _name_ranks, _table,
+   _window_stats, _select_stats and _seek_stats work unchanged.  A point of the seek map is the first byte of a record's line, so
+   header, @CO and empty lines lie in front of whichever point follows them; a run is whole lines, and the runs of a mapped open are
+   scanned as a SAM text without a header.  Plain and BGZF input is entered; a map of gzip, bzip2, xz or Zstandard input runs the full
+   selected pass.  A mapped open of a SAM map without both flags is refused as the census is. */
+#define LRGE_GPU_INGEST_SELECT_SAM 4096
+
+/* The sampled ingest of unaligned CRAM (k_rans_decode into a scratch of a round's size, k_fx_runs for the chosen
+   reads; no kernel of its own).  CRAM does not pass through the windows: every BA block is independent and its place is known from
+   the walk, so the four calls are the pipeline of LRGE_GPU_INGEST_CRAM (below) with another sink.
+   | LRGE_GPU_INGEST_SELECT_CRAM (opt-in; it has effect only beside LRGE_GPU_INGEST_CRAM and only in lrge_hip_reads_census*,
+   _open_selected*, _census_map* and _open_mapped*; without it every call does what it did, the refusal text included): input that
+   starts with "CRAM" is walked on the host as in lrge_hip_reads_open*, the walk keeping only the chosen ordinals' identifiers
+   (none for a census).  lrge_hip_reads_census*: every BA block is decoded and nothing kept, so a damaged body in any slice is
+   LRGE_ERR_UNPROVEN as in the full open; out[0] records, out[1] the sum of the lengths, out[2] what lrge_hip_reads_text_bytes of the
+   full open reports (the bases), out[3] 0.  lrge_hip_reads_open_selected*: the same over every block, the chosen reads' ranges
+   copied to a store of exactly the chosen bases; k = 0 is legal.  lrge_hip_reads_census_map*: the census and a map whose points are
+   the slices in which a record starts (lrge_hip_read_map_points: that record's ordinal, the slice's base offset, the file offset of
+   its BA block; lrge_hip_read_map_stats: out[2], the stride, is 0).  lrge_hip_reads_open_mapped*: "the map is of another input"
+   (LRGE_ERR_INVALID) on another file length, record count, base count or slice count; the walk again (identifiers, lengths and the
+   mapped-record refusal are the host's; slices that are not the map's: "the map does not fit the input"); then only the BA blocks of
+   slices that hold a chosen read with bases are decoded, and a refused head is found only there.  lrge_hip_reads_seek_stats: out[0]
+   stretches of consecutive slices decoded, out[1] raw bytes decoded, out[2] compressed BA bytes uploaded, out[3] BA blocks decoded.
+   The path forms read the whole file.  Everything the walk and the stream heads refuse is refused with the texts of the full open,
+   and CRAM_MIN_BLOCKS is tested against the file's BA blocks in all four calls.  INGEST_MAX_BYTES bounds the chosen bases plus the
+   largest round's compressed and raw bytes (the transform scratch is not counted): the rounds are those of option CRAM_ROUND_BYTES,
+   halved until they fit; "chosen bases and one round of CRAM blocks above INGEST_MAX_BYTES" (LRGE_ERR_UNPROVEN) when a single block
+   does not.  The handle is the CRAM handle restricted to the k chosen reads in file order: lrge_hip_reads_text_bytes is the file's,
+   select_stats = (records, k, bases of the file, bases kept); in lrge_hip_reads_cram_stats containers, slices and records are the
+   file's, the block and byte counts those of the blocks the pass decoded; window_stats out[0] is 0 and out[1] the bytes of the store. */
+#define LRGE_GPU_INGEST_SELECT_CRAM 8192
 
 /* The windowed and the sampled ingest of Zstandard (k_zs_xxh64_part, k_zs_slide): a match reaches back at most
    Window_Size bytes, so the decoder needs no more of the earlier text than the last min(frame bytes so far, window) bytes of the

@@ -61,6 +61,8 @@ pub const LRGE_PRESET_AVA_PB: c_int = 1; //  Preset::AvaPb  (preset.rs:24)
 pub const LRGE_GPU_INGEST_SAM: c_int = 8; // lrge_hip_reads_open*: unaligned SAM scanned on the device (io.rs:92-96)
 pub const LRGE_GPU_INGEST_WINDOWED_ALN: c_int = 64; // beside LRGE_GPU_INGEST_WINDOWED and the format's flag: unaligned BAM / SAM in windows too (io.rs:154-184)
 pub const LRGE_GPU_INGEST_WINDOWED: c_int = 32; // lrge_hip_reads_open*: FASTA / FASTQ above the text cap in windows, only the bases kept (io.rs:154-184)
+pub const LRGE_GPU_INGEST_SELECT_CRAM: c_int = 8192; // beside LRGE_GPU_INGEST_CRAM: unaligned CRAM in lrge_hip_reads_census* / _open_selected* / _census_map* / _open_mapped* (io.rs:93, 140-145); opt-in
+pub const LRGE_GPU_INGEST_SELECT_SAM: c_int = 4096; // beside LRGE_GPU_INGEST_SAM: unaligned SAM in lrge_hip_reads_census* / _open_selected* / _census_map* / _open_mapped* (io.rs:92-96, 140-145); opt-in
 pub const LRGE_GPU_INGEST_SELECT_ALN: c_int = 1024; // beside LRGE_GPU_INGEST_BAM: unaligned BAM in lrge_hip_reads_census* / _open_selected* / _census_map* / _open_mapped* (io.rs:93, 140-145); opt-in
 pub const LRGE_GPU_INGEST_CRAM: c_int = 512; // lrge_hip_reads_open*: unaligned CRAM, its base blocks decoded on the device (io.rs:93, 154-184); opt-in
 pub const LRGE_GPU_INFLATE_XZ: c_int = 256; // lrge_hip_reads_open* / lrge_hip_read_records_gpu_ex: xz decompressed on the device (io.rs:36-63)

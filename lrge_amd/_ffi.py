@@ -22,6 +22,8 @@ GPU_INGEST_WINDOWED = 32
 GPU_INGEST_WINDOWED_ALN = 64
 GPU_INGEST_SELECT_ALN = 1024
 GPU_INGEST_WINDOWED_ZSTD = 2048
+GPU_INGEST_SELECT_SAM = 4096
+GPU_INGEST_SELECT_CRAM = 8192
 PRESET_AVA_ONT, PRESET_AVA_PB = 0, 1
 
 T_NAMES = ["pack", "sketch", "index_sort", "index_table", "qfilter", "lookup", "expand", "anchor_sort", "group",

@@ -8,10 +8,13 @@
 //                 an Err naming it.
 //   cram_run      the rounds: the blocks whose compressed bytes fit `round_bytes` go up together with their descriptors and are
 //                 decoded by one launch of the backend `Dev`, which leaves each block's bytes at its offset in the dense store.
+//   cram_sampled  the sampled ingest: census, selected open, census with a map and mapped open over the same walk,
+//                 heads and rounds, with a backend that decodes into a scratch and keeps the chosen reads only (at the end of this file).
 #pragma once
 #include <stdint.h>
 #include <string.h>
 
+#include <algorithm>
 #include <chrono>
 #include <memory>
 #include <string>
@@ -19,6 +22,7 @@
 
 #include "../../include/lrge_io.hpp"
 #include "rans_core.h"
+#include "fx_seek.h"
 
 struct CramStats {
     uint64_t containers = 0, slices = 0, records = 0;
@@ -59,13 +63,22 @@ struct CramWalk {
     std::vector<uint64_t> ba_out;           // [slices + 1]: where a slice's bases start in the dense store
 };
 
-// false: `why` says what the device path does not prove (or what the host reader reports)
-static inline bool cram_walk(const uint8_t *d, uint64_t n, CramWalk &cw, std::string &why) {
+// which identifiers a walk keeps (the sampled ingest): those of the ordinals sel[0, k), strictly ascending --
+// none for k = 0, the census -- so the host memory for names scales with the sample.  names / name_off then hold the kept ones only
+struct CramNames { const uint32_t *sel; uint64_t k; };
+
+// false: `why` says what the device path does not prove (or what the host reader reports).  keep == nullptr: every identifier
+static inline bool cram_walk(const uint8_t *d, uint64_t n, CramWalk &cw, std::string &why, const CramNames *keep = nullptr) {
     using namespace lrge::io;
     if (detect_compression_format(std::string((const char *)d, (size_t)(n < 8 ? n : 8))) != CompressionFormat::None) { why = "CRAM behind a compression format"; return false; }
     cw.name_off.assign(1, 0);
+    uint64_t ord = 0, at = 0;
     try {
-        cram::parse_with(d, (size_t)n, [&](const std::string &name, const std::string &) { cw.names += name; cw.name_off.push_back(cw.names.size()); }, MAPPED_MSG, cw.w);
+        cram::parse_with(d, (size_t)n, [&](const std::string &name, const std::string &) {
+            const uint64_t i = ord++;
+            if (keep) { if (at >= keep->k || keep->sel[at] != i) return; ++at; }
+            cw.names += name; cw.name_off.push_back(cw.names.size());
+        }, MAPPED_MSG, cw.w);
     } catch (const std::exception &e) { why = e.what(); return false; }
     cw.ba_out.assign(1, 0);
     for (const auto &b : cw.w.ba) cw.ba_out.push_back(cw.ba_out.back() + (uint64_t)b.raw_size);
@@ -365,4 +378,150 @@ static inline std::vector<RansStream> cram_streams(const CramWalk &cw) {
         if (b.data || b.raw_size) s.push_back(RansStream{b.data, b.size, b.method, b.raw_size, cw.ba_out[k]});
     }
     return s;
+}
+
+// ---- the sampled ingest: the same walk, heads and rounds with another sink ----
+// A second backend decodes a round into a scratch block of the round's raw size and copies the chosen reads' ranges from there to
+// a dense store of exactly the chosen bases.  What is shared by the device (host_cram.inl) and the twin (cram_twin.cpp) is here: the
+// plan of a selection, the descriptors rebased to the scratch, the copy table of a round, the round size that fits the budget, the
+// seek map of kind FX_SEEK_CRAM and the four calls' common course (cram_sampled).
+struct CramCopy { uint64_t src, dst, len; };        // (the layout of FxRunCopy, k_fastx.h: k_fx_runs takes the table as it is)
+
+// sel[0, k): strictly ascending, every ordinal below the walk's records (the caller has checked both)
+struct CramKeepPlan {
+    std::vector<uint64_t> dst;            // [k + 1]: where chosen read j lies in the dense store; dst[k]: the chosen bases
+    std::vector<uint64_t> first;          // [slices + 1]: the chosen reads of slice s are j in [first[s], first[s + 1])
+    std::vector<RansStream> streams;      // the BA blocks the pass decodes, in file order
+    std::vector<uint32_t> slice_of;       // ... and the slice of each
+    uint64_t runs = 0;                    // stretches of consecutive slices among them, as the planner of fx_seek.h merges runs
+};
+
+// touched_only: the mapped open -- only the BA blocks of slices that hold a chosen read with bases; else every BA block of the file
+static inline void cram_keep_plan(const CramWalk &cw, const uint32_t *sel, uint64_t k, bool touched_only, CramKeepPlan &p) {
+    const size_t n_slices = cw.w.ba.size();
+    p = CramKeepPlan();
+    p.dst.assign(1, 0);
+    p.first.assign(n_slices + 1, 0);
+    std::vector<uint8_t> touched(n_slices, 0);
+    for (uint64_t j = 0; j < k; ++j) {
+        const auto &r = cw.w.recs[sel[j]];
+        p.dst.push_back(p.dst.back() + r.len);
+        ++p.first[r.slice + 1];
+        if (r.len) touched[r.slice] = 1;
+    }
+    for (size_t s = 0; s < n_slices; ++s) p.first[s + 1] += p.first[s];
+    uint32_t prev = 0;
+    for (size_t s = 0; s < n_slices; ++s) {
+        const auto &b = cw.w.ba[s];
+        if (!(b.data || b.raw_size) || (touched_only && !touched[s])) continue;
+        if (p.streams.empty() || prev + 1 != (uint32_t)s) ++p.runs;
+        p.streams.push_back(RansStream{b.data, b.size, b.method, b.raw_size, cw.ba_out[s]});
+        p.slice_of.push_back((uint32_t)s);
+        prev = (uint32_t)s;
+    }
+}
+
+// the m blocks of a round (copies of the descriptors) placed back to back in a scratch of the returned size: scr[a] is where block a starts
+static inline uint64_t cram_rebase(RansBlk *b, uint32_t m, uint64_t *scr) {
+    uint64_t o = 0;
+    for (uint32_t a = 0; a < m; ++a) { scr[a] = o; b[a].out_off = o; o += b[a].out_len; }
+    return o;
+}
+
+// the copies of a round whose blocks are streams [at, at + m) of the plan: every chosen read with bases, scratch to store; neighbours
+// on both sides are one copy
+static inline void cram_round_copies(const CramWalk &cw, const CramKeepPlan &p, const uint32_t *sel, size_t at, uint32_t m, const uint64_t *scr, std::vector<CramCopy> &out) {
+    out.clear();
+    for (uint32_t a = 0; a < m; ++a) {
+        const uint32_t s = p.slice_of[at + a];
+        for (uint64_t j = p.first[s]; j < p.first[s + 1]; ++j) {
+            const auto &r = cw.w.recs[sel[j]];
+            if (!r.len) continue;
+            const CramCopy c = {scr[a] + r.off, p.dst[j], r.len};
+            if (!out.empty() && out.back().src + out.back().len == c.src && out.back().dst + out.back().len == c.dst) out.back().len += c.len;
+            else out.push_back(c);
+        }
+    }
+}
+
+// the largest round cram_run forms over s at `round_bytes`: its compressed bytes as they go up (padded to words) plus its raw bytes
+static inline uint64_t cram_largest_round(const std::vector<RansStream> &s, uint64_t round_bytes, uint64_t *raw_max = nullptr) {
+    uint64_t best = 0, best_raw = 0;
+    for (size_t i = 0, j; i < s.size(); i = j) {
+        uint64_t in = 0, raw = 0;
+        for (j = i; j < s.size() && (j == i || in + s[j].n <= round_bytes); ++j) { in = (in + s[j].n + 3) & ~(uint64_t)3; raw += (uint64_t)s[j].raw_size; }
+        best = std::max(best, in + raw); best_raw = std::max(best_raw, raw);
+    }
+    if (raw_max) *raw_max = best_raw;
+    return best;
+}
+
+// The round size of a pass that has `room` bytes beside its store: option CRAM_ROUND_BYTES where its largest round fits, else halved
+// until it does -- at 1 every block is a round of its own.  0: a single block does not fit
+static inline uint64_t cram_fit_round(const std::vector<RansStream> &s, uint64_t round_bytes, uint64_t room) {
+    for (uint64_t r = round_bytes;; r = r / 2) {
+        if (cram_largest_round(s, r) <= room) return r;
+        if (r <= 1) return 0;
+    }
+}
+
+// the seek map of a CRAM (fx_seek.h, kind FX_SEEK_CRAM): one point per slice in which a record starts -- that record's ordinal, the
+// slice's base offset, the file offset of its BA block (0: it has none); n_blocks: the slices, text_bytes: the bases
+static inline void cram_seek_map(const CramWalk &cw, const uint8_t *d, uint64_t len, FxSeekMap &m) {
+    m = FxSeekMap();
+    m.kind = FX_SEEK_CRAM; m.fmt = cw.w.recs.empty() ? FX_FMT_EMPTY : FX_FMT_FASTA; m.stride = 0;
+    m.file_len = len; m.records = cw.w.recs.size(); m.bases = m.text_bytes = cw.ba_out.back(); m.n_blocks = cw.w.ba.size();
+    for (size_t i = 0; i < cw.w.recs.size(); ++i) {
+        const uint32_t s = cw.w.recs[i].slice;
+        if (i && cw.w.recs[i - 1].slice == s) continue;
+        m.pts.push_back(FxSeekPoint{i, cw.ba_out[s], cw.w.ba[s].data ? (uint64_t)(cw.w.ba[s].data - d) : 0, 0, 0, s});
+    }
+}
+
+static inline bool cram_same_points(const FxSeekMap &a, const FxSeekMap &b) {
+    if (a.pts.size() != b.pts.size()) return false;
+    for (size_t i = 0; i < a.pts.size(); ++i)
+        if (a.pts[i].ord != b.pts[i].ord || a.pts[i].off != b.pts[i].off || a.pts[i].c_off != b.pts[i].c_off || a.pts[i].blk != b.pts[i].blk) return false;
+    return true;
+}
+
+// One of the four sampled calls over file d[0, len).  sel[0, k): strictly ascending (checked by the caller); mapped: `map` is the
+// map of an earlier census, and only the touched blocks are decoded; else `map` (optional) is filled.
+// Sink: bool begin(const CramWalk &, const CramKeepPlan &, const uint32_t *sel, uint64_t k) -- the store of plan.dst[k] bytes; false: its own error
+//       and the Dev of cram_run, whose rounds it decodes into its scratch and copies from (cram_rebase, cram_round_copies).
+enum { CRAM_S_OK = 0, CRAM_S_UNPROVEN, CRAM_S_ORDINAL, CRAM_S_OTHER_INPUT, CRAM_S_MISFIT, CRAM_S_OVER_CAP, CRAM_S_BACKEND };
+struct CramSampled {
+    CramWalk cw;
+    CramKeepPlan plan;
+    CramStats st;
+    uint64_t round_bytes = 0, seek[4] = {0, 0, 0, 0};
+    uint32_t bad_ordinal = 0;
+};
+template <class Sink>
+static inline int cram_sampled(Sink &sink, const uint8_t *d, uint64_t len, const uint32_t *sel, uint64_t k, bool mapped, FxSeekMap *map, uint64_t min_blocks, uint64_t round_bytes,
+                               uint64_t cap, CramSampled &o, std::string &why) {
+    if (mapped && (map->kind != FX_SEEK_CRAM || map->file_len != len)) return CRAM_S_OTHER_INPUT;
+    const CramNames keep = {sel, k};
+    const uint64_t w0 = cram_now_us();
+    if (!cram_walk(d, len, o.cw, why, &keep)) return CRAM_S_UNPROVEN;
+    o.st.walk_us = cram_now_us() - w0;
+    o.st.containers = o.cw.w.containers; o.st.slices = o.cw.w.ba.size(); o.st.records = o.cw.w.recs.size();
+    const uint64_t n = o.cw.w.recs.size();
+    if (n >> 32) { why = "2^32 CRAM records or more"; return CRAM_S_UNPROVEN; }
+    if (o.cw.names.size() >> 32) { why = "4 GiB of identifiers or more"; return CRAM_S_UNPROVEN; }
+    if (cram_streams(o.cw).size() < min_blocks) { why = "fewer BA blocks than CRAM_MIN_BLOCKS"; return CRAM_S_UNPROVEN; }
+    FxSeekMap now;
+    if (mapped || map) cram_seek_map(o.cw, d, len, now);
+    if (mapped && (map->records != now.records || map->bases != now.bases || map->n_blocks != now.n_blocks)) return CRAM_S_OTHER_INPUT;
+    for (uint64_t j = 0; j < k; ++j) if (sel[j] >= n) { o.bad_ordinal = sel[j]; return CRAM_S_ORDINAL; }
+    if (mapped && !cram_same_points(*map, now)) { why = "other slices than the map's"; return CRAM_S_MISFIT; }
+    cram_keep_plan(o.cw, sel, k, mapped, o.plan);
+    if (o.plan.dst.back() > cap || !(o.round_bytes = cram_fit_round(o.plan.streams, round_bytes, cap - o.plan.dst.back()))) return CRAM_S_OVER_CAP;
+    if (!sink.begin(o.cw, o.plan, sel, k)) return CRAM_S_BACKEND;
+    const int64_t bad = cram_run(sink, o.plan.streams, o.round_bytes, true, o.st, nullptr, why);
+    if (bad < 0) return CRAM_S_BACKEND;
+    if (bad) return CRAM_S_UNPROVEN;
+    if (mapped) { o.seek[0] = o.plan.runs; o.seek[1] = o.st.raw_bytes; o.seek[2] = o.st.comp_bytes; o.seek[3] = o.plan.streams.size(); }
+    else if (map) *map = now;
+    return CRAM_S_OK;
 }

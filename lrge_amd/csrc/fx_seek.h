@@ -1,12 +1,13 @@
-// fx_seek.h -- the seek map of a FASTA / FASTQ text or of unaligned BAM and the plan of a pass that brings only the chosen runs
-// (DESIGN sections 24 and 25), shared by the device (host_fastx.inl; hipcc) and the host twins (fastx_twin.cpp, bam_twin.cpp; g++), as
-// fx_window.h is.
+// fx_seek.h -- the seek map of a FASTA / FASTQ text, of unaligned BAM or of unaligned SAM and the plan of a pass that brings only the
+// chosen runs (DESIGN sections 24, 25 and 27), shared by the device (host_fastx.inl; hipcc) and the host twins (fastx_twin.cpp,
+// bam_twin.cpp, sam_twin.cpp; g++), as fx_window.h is.
 //
 // The census that proves the text (fx_window.h FX_KEEP_NONE) can leave a map behind.  The whole text is cut into cells of
 // `stride` bytes; a cell in which at least one record starts gets one point: the first record that starts in it.  Where a record
 // starts is fx_rec_start: FASTA / FASTQ at the first byte of its header line, the '>' or '@' (FxRec::name_off - FX_LEAD_TEXT); BAM at
 // its block_size field (FxRec::name_off - FX_LEAD_BAM, bam_record), so the BAM header lies in front of record 0's point at hdr_end as
-// leading blank lines do.  A point holds the record's ordinal (file order,
+// leading blank lines do; SAM at the first byte of its line (FxRec::name_off itself, sam_record: FX_LEAD_SAM is 0), so header, @CO
+// and empty lines lie in front of whichever point follows them.  A point holds the record's ordinal (file order,
 // 0-based), its text offset and, for BGZF, the block that holds that offset.  Cells inside one long record have no point; the
 // points ascend strictly in ordinal and in offset, and the first point is record 0.
 //
@@ -14,7 +15,7 @@
 // the first point above it, or to the end of the text; runs that touch or overlap are merged.  The sub-text -- the runs'
 // bytes, concatenated -- is a text of whole records (a run starts at a header line and ends directly behind a line feed or at the
 // end of the text; a BAM run starts at a block_size field and ends in front of the next, so the sub-text is a record stream without
-// a header), and the selection renumbered into its ordinals names the same records.
+// a header; a SAM run is whole lines, the sub-text a SAM text without a header), and the selection renumbered into its ordinals names the same records.
 #pragma once
 #include <stdint.h>
 
@@ -23,12 +24,15 @@
 #include "bgzf_scan.h"
 #include "fx_window.h"
 
-enum { FX_SEEK_PLAIN = 0, FX_SEEK_BGZF = 1, FX_SEEK_OTHER = 2 };    // OTHER: a container that cannot be entered (gzip, bzip2, xz)
+// OTHER: a container that cannot be entered (gzip, bzip2, xz); CRAM: no text at all -- a point is a slice (cram_round.h cram_seek_map:
+// ord the first record that starts in it, off its base offset, c_off the file offset of its BA block, blk the slice), n_blocks the slices
+enum { FX_SEEK_PLAIN = 0, FX_SEEK_BGZF = 1, FX_SEEK_OTHER = 2, FX_SEEK_CRAM = 3 };
 #define FX_SEEK_NONE 0xFFFFFFFFu                                     // a cell's slot without a record start
 
 // the record-start rule: a record starts `lead` bytes in front of its identifier
 #define FX_LEAD_TEXT 1u                                              // the '>' or '@'
 #define FX_LEAD_BAM 36u                                              // block_size and the 32 bytes of fixed fields (bam_record)
+#define FX_LEAD_SAM 0u                                               // the identifier is the first field of the line (sam_record)
 FX_HD uint64_t fx_rec_start(uint64_t name_off, uint32_t lead) { return name_off - lead; }
 
 // blk: the index of the block that holds text offset `off` (o_off <= off < o_off + ISIZE), c_off / o_off / c_len its file offset,

@@ -8,6 +8,8 @@
 // precomputed offset in the handle's dense store, the form a windowed FASTA handle has, so the gather, the identifier ranks and
 // every other consumer work unchanged.  Option CRAM_MIN_BLOCKS (default CRAM_MIN_BLOCKS_DEFAULT = 32, the measured break-even rounded up to a power of two: DESIGN section 22): a file with
 // fewer BA blocks stays with the host.
+// The sampled ingest (fx_cram_sampled below): the same walk and rounds with a second backend, CramKeepDev, which
+// decodes a round into a scratch of the round's size and keeps the chosen reads only.
 
 #define CRAM_MIN_BLOCKS_DEFAULT 32
 
@@ -109,6 +111,106 @@ static int fx_open_cram(lrge_hip_ctx *ctx, lrge_hip_reads *R, const u8 *d, u64 l
     if (ctx->opt("VERBOSE")) fprintf(stderr, "[lrge_hip] reads_open: CRAM, %llu records in %llu slices, %llu bases from %llu compressed bytes in %llu rounds; walk %.2f ms, decode %.2f ms\n",
                                     (unsigned long long)n, (unsigned long long)st.slices, (unsigned long long)total, (unsigned long long)st.comp_bytes, (unsigned long long)st.rounds,
                                     st.walk_us / 1000.0, st.decode_us / 1000.0);
+    return LRGE_OK;
+}
+
+// ---- the sampled ingest of CRAM: census, selected open, census with a map, mapped open ----
+namespace {
+static_assert(sizeof(CramCopy) == sizeof(FxRunCopy), "k_fx_runs takes the copy table of cram_round_copies as it is");
+
+// The second backend of cram_run: a round is decoded by CramDev into a scratch block of the round's raw size -- the descriptors
+// rebased on a copy, cram_run and k_rans_decode as they are -- and k_fx_runs copies the chosen reads' ranges from there to the dense
+// store, which is allocated once at the chosen bases.  A census has no store and no copy
+struct CramKeepDev {
+    lrge_hip_ctx *ctx;
+    CramDev dev;
+    GzBuf scratch, copies, first;
+    const CramWalk *cw = nullptr;
+    const CramKeepPlan *plan = nullptr;
+    const u32 *sel = nullptr;
+    u8 *store = nullptr;
+    u64 at = 0;
+    explicit CramKeepDev(lrge_hip_ctx *c) : ctx(c), dev(c) { for (GzBuf *b : {&scratch, &copies, &first}) b->ctx = c; }
+    ~CramKeepDev() { ctx->pool.release(store); }
+    bool begin(const CramWalk &w, const CramKeepPlan &p, const uint32_t *s, uint64_t) {
+        cw = &w; plan = &p; sel = s; at = 0;
+        return (store = (u8 *)ctx->pool.alloc((size_t)p.dst.back() + FX_PAD, &dev.e)) != nullptr;
+    }
+    bool round(const uint8_t *h_in, size_t in_bytes, const RansBlk *blk, uint32_t m, const RansTables &t, uint64_t tmp_bytes, uint32_t *st_h) {
+        std::vector<RansBlk> b(blk, blk + m);
+        std::vector<uint64_t> scr(m);
+        const u64 raw = cram_rebase(b.data(), m, scr.data());
+        if (!scratch.need((size_t)raw + FX_PAD, &dev.e)) return false;          // (FX_PAD: fx_copy_span may load the word behind a range's last byte)
+        dev.out = scratch.as<u8>();
+        if (!dev.round(h_in, in_bytes, b.data(), m, t, tmp_bytes, st_h)) return false;
+        bool good = true;
+        for (uint32_t a = 0; a < m; ++a) good = good && st_h[a] == RANS_OK;
+        std::vector<CramCopy> c;
+        if (good) cram_round_copies(*cw, *plan, sel, (size_t)at, m, scr.data(), c);
+        at += m;
+        if (c.empty()) return true;
+        std::vector<u64> f(c.size() + 1, 0);
+        for (size_t i = 0; i < c.size(); ++i) {
+            if (c[i].src + c[i].len > raw || c[i].dst + c[i].len > plan->dst.back()) return dev.ok(hipErrorInvalidValue);      // (never: the walk proved the lengths)
+            f[i + 1] = f[i] + div_up(c[i].len, (u64)FX_RUN_TILE);
+        }
+        if (f.back() >> 31 || c.size() >> 32) return dev.ok(hipErrorInvalidValue);                                             // (never: a round is below 2^31 tiles)
+        hipStream_t st = ctx->stream;
+        if (!dev.up(copies, c.data(), c.size() * sizeof(CramCopy)) || !dev.up(first, f.data(), f.size() * 8)) return false;
+        hipLaunchKernelGGL(k_fx_runs, dim3((u32)f.back()), dim3(64), 0, st, scratch.as<const u8>(), store, copies.as<const FxRunCopy>(), first.as<const u64>(), (u32)c.size());
+        return dev.ok(hipGetLastError()) && dev.ok(hipStreamSynchronize(st));      // (the tables are pageable, and the scratch is decoded into again)
+    }
+};
+}  // namespace
+
+static bool cram_select_flags(int flags) { return (flags & LRGE_GPU_INGEST_CRAM) && (flags & LRGE_GPU_INGEST_SELECT_CRAM); }
+
+// One sampled call on input that starts with "CRAM", under LRGE_GPU_INGEST_SELECT_CRAM beside LRGE_GPU_INGEST_CRAM.  mode
+// FX_KEEP_NONE: the census (map: filled when given); FX_KEEP_SEL: the selected open, or -- mapped -- the mapped open on `map`
+static int fx_cram_sampled(lrge_hip_ctx *ctx, lrge_hip_reads *R, const u8 *d, u64 len, FxKeepMode mode, const u32 *sel, u64 k, bool mapped, FxSeekMap *map, double t0) {
+    const auto unproven = [&](const std::string &why) { LRGE_SET_ERR(ctx, "reads_open: not proven on the device (%s)", why.c_str()); return (int)LRGE_ERR_UNPROVEN; };
+    if (mode != FX_KEEP_SEL) k = 0;
+    const u64 cap = ingest_cap(ctx);
+    CramSampled o;
+    CramKeepDev sink(ctx);
+    std::string why;
+    const int rc = cram_sampled(sink, d, len, sel, k, mapped, map, ctx->opt_u64("CRAM_MIN_BLOCKS", CRAM_MIN_BLOCKS_DEFAULT), std::max<u64>(1, ctx->opt_u64("CRAM_ROUND_BYTES", (u64)256 << 20)),
+                                cap, o, why);
+    switch (rc) {
+    case CRAM_S_OK: break;
+    case CRAM_S_UNPROVEN: return unproven(why);
+    case CRAM_S_ORDINAL: LRGE_SET_ERR(ctx, "reads_open_selected: ordinal %u of %llu records", o.bad_ordinal, (unsigned long long)o.cw.w.recs.size()); return LRGE_ERR_INVALID;
+    case CRAM_S_OTHER_INPUT: ctx->err = "reads_open_mapped: the map is of another input"; return LRGE_ERR_INVALID;
+    case CRAM_S_MISFIT: LRGE_SET_ERR(ctx, "reads_open_mapped: the map does not fit the input (%s)", why.c_str()); return LRGE_ERR_UNPROVEN;
+    case CRAM_S_OVER_CAP: LRGE_SET_ERR(ctx, "reads_open_selected: chosen bases and one round of CRAM blocks above INGEST_MAX_BYTES (%llu)", (unsigned long long)cap); return LRGE_ERR_UNPROVEN;
+    default: return cram_device_error(ctx, sink.dev, "reads_open_selected: CRAM base blocks");
+    }
+    const double t1 = fx_now_ms();
+    const u64 n = o.cw.w.recs.size(), total = o.cw.ba_out.back(), kept = o.plan.dst.back();
+    std::vector<FxRec> tab((size_t)k);
+    R->seq_len.resize((size_t)k);
+    for (u64 j = 0; j < k; ++j) {
+        const u32 l = o.cw.w.recs[sel[j]].len;
+        R->seq_len[(size_t)j] = l;
+        tab[(size_t)j] = FxRec{0, o.plan.dst[(size_t)j], l, (u32)(o.cw.name_off[(size_t)j + 1] - o.cw.name_off[(size_t)j]), l};
+    }
+    int arc;
+    if ((arc = fx_alloc_recs(ctx, R, std::max<u64>(1, k)))) return arc;
+    if (k) HIPCHK(ctx, hipMemcpyAsync(R->d_recs, tab.data(), tab.size() * sizeof(FxRec), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    R->d_text = sink.store; sink.store = nullptr; R->n_text = kept;
+    R->n = k; R->names.swap(o.cw.names); R->name_off.swap(o.cw.name_off);
+    R->fmt = k ? FX_FMT_FASTA : FX_FMT_EMPTY;
+    R->text_bytes = total; R->is_cram = true;
+    R->cram = o.st;
+    R->sel = FxSelStats{n, k, total, kept};
+    R->win.bases = kept;                                              // (window_stats out[1]: the bytes of the dense store; no window was flushed)
+    memcpy(R->seek, o.seek, sizeof R->seek);
+    const double t2 = fx_now_ms();
+    R->ms[0] = (float)(t1 - t0); R->ms[1] = 0; R->ms[2] = (float)(t2 - t1); R->ms[3] = (float)(t2 - t0);
+    if (ctx->opt("VERBOSE")) fprintf(stderr, "[lrge_hip] reads_open_selected: CRAM, %llu of %llu records, %llu of %llu bases kept; %llu of %llu slices decoded in %llu rounds of at most %llu compressed bytes; walk %.2f ms, decode %.2f ms\n",
+                                    (unsigned long long)k, (unsigned long long)n, (unsigned long long)kept, (unsigned long long)total, (unsigned long long)o.plan.streams.size(),
+                                    (unsigned long long)o.st.slices, (unsigned long long)o.st.rounds, (unsigned long long)o.round_bytes, o.st.walk_us / 1000.0, o.st.decode_us / 1000.0);
     return LRGE_OK;
 }
 

@@ -10,7 +10,9 @@
 // bases staying packed.  lrge_hip_reads_census* and lrge_hip_reads_open_selected* pass FASTA / FASTQ text through
 // the same windows and keep nothing, or only the records of a list of ordinals (FxKeepMode); lrge_hip_reads_census_map*
 // leaves a seek map behind, with which lrge_hip_reads_open_mapped* brings only the runs of plain or BGZF input that hold chosen records
-// (fx_seek.h, fx_src_seek_raw, fx_src_seek_bgzf).  Included into lrge_hip.hip.
+// (fx_seek.h, fx_src_seek_raw, fx_src_seek_bgzf); with the formats' own opt-in flags the four sampled calls take unaligned
+// BAM, Zstandard (section 26), unaligned SAM through its windows and unaligned CRAM through fx_cram_sampled (section 27).
+// Included into lrge_hip.hip.
 // A call (lrge_hip_reads_open_mem) is one source (fx_src_raw, _bgzf, _gzip, _bzip2), which brings the text to the sink (FxSink) resident
 // or through the windows of the sink's FxWinRun, and one record scan (fx_parse_kind), chosen by the sniff (fx_kind).
 
@@ -186,12 +188,16 @@ struct FxWinDev {
     // With LRGE_GPU_INGEST_SELECT_ALN beside LRGE_GPU_INGEST_BAM the magic of BAM makes the run a BAM run, through
     // the windows whatever LRGE_GPU_INGEST_WINDOWED / _WINDOWED_ALN say, as FASTA / FASTQ text is
     bool select_aln() const { return (flags & LRGE_GPU_INGEST_BAM) && (flags & LRGE_GPU_INGEST_SELECT_ALN); }
+    // ... and with LRGE_GPU_INGEST_SELECT_SAM beside LRGE_GPU_INGEST_SAM text that sam_sniff takes makes it a SAM run
+    bool select_sam() const { return (flags & LRGE_GPU_INGEST_SAM) && (flags & LRGE_GPU_INGEST_SELECT_SAM); }
+    u32 lead() const { return kind == FX_FMT_BAM ? FX_LEAD_BAM : kind == FX_FMT_SAM ? FX_LEAD_SAM : FX_LEAD_TEXT; }      // where a record starts (fx_rec_start)
     int selected_format() {
         if (mapped) return LRGE_OK;             // (a run may start with a read named HD.., SQ.. or RG..: fx_win_census; the kind is the map's)
         u8 head[4] = {0, 0, 0, 0};
         const u64 n = blk->keep_len;
         if (n) { HIPCHK(ctx, hipMemcpyAsync(head, blk->keep, (size_t)std::min<u64>(4, n), hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); }
         if (select_aln() && fx_sniff(LRGE_GPU_INGEST_BAM, head, n) == FX_FMT_BAM) { kind = FX_FMT_BAM; return LRGE_OK; }
+        if (select_sam() && fx_sniff(LRGE_GPU_INGEST_SAM, head, n) == FX_FMT_SAM) { kind = FX_FMT_SAM; return LRGE_OK; }
         if (fx_sniff(LRGE_GPU_INGEST_BAM | LRGE_GPU_INGEST_SAM, head, n) == FX_FMT_EMPTY && !(n >= 4 && !memcmp(head, "CRAM", 4))) return LRGE_OK;
         ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only";
         return LRGE_ERR_UNPROVEN;
@@ -251,7 +257,7 @@ struct FxWinDev {
         blk->keep_max = lim > store.keep_cap ? lim - store.keep_cap : 0;
         return LRGE_OK;
     }
-    // A window of a census that leaves a seek map, behind k_fx_records or k_bam_records: k_fx_seek finds the first record start of every cell of the
+    // A window of a census that leaves a seek map, behind k_fx_records, k_bam_records or k_sam_records: k_fx_seek finds the first record start of every cell of the
     // window's prefix [0, n_use), the slots (record index and window offset, 8 bytes a cell) come down in one copy, and the point
     // rule of fx_seek.h takes those that hold a record.  The window's records are R->sel.seen onwards, its bytes `through` onwards
     int seek_window(Scratch &sc, const lrge_hip_reads *W, u64 n_rec, u64 n_use) {
@@ -260,7 +266,7 @@ struct FxWinDev {
         ALLOC_OR_FAIL(d_slot, sc, u32, 2 * n_cells);
         HIPCHK(ctx, hipMemsetAsync(d_slot, 0xFF, (size_t)n_cells * 8, ctx->stream));
         hipLaunchKernelGGL(k_fx_seek, dim3((u32)div_up(n_rec, FX_THREADS)), dim3(FX_THREADS), 0, ctx->stream, (const FxRec *)W->d_recs, n_rec, through, S, cell0, n_cells,
-                           kind == FX_FMT_BAM ? FX_LEAD_BAM : FX_LEAD_TEXT, d_slot);
+                           lead(), d_slot);
         KCHK(ctx);
         std::vector<u32> slot((size_t)n_cells * 2);
         HIPCHK(ctx, hipMemcpyAsync(slot.data(), d_slot, (size_t)n_cells * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -802,9 +808,13 @@ static int fx_open_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, 
     guard->ctx = ctx;
     bool xz_whole;
     const FxBox box = fx_container(d, len, &xz_whole);
-    if (mode != FX_KEEP_ALL && box == FX_BOX_CRAM) {     // (whatever the flags: FxWinDev::selected_format)
-        ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only";
-        return LRGE_ERR_UNPROVEN;
+    if (mode != FX_KEEP_ALL && box == FX_BOX_CRAM) {     // (without both flags, whatever the others: FxWinDev::selected_format)
+        if (!cram_select_flags(flags)) { ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only"; return LRGE_ERR_UNPROVEN; }
+        // the sampled ingest of CRAM: no text and no windows -- the walk, then the rounds into a scratch
+        const int crc = fx_cram_sampled(ctx, guard.get(), d, len, mode, sel, k, false, map, t0);
+        if (crc) return crc;
+        *out = guard.release();
+        return LRGE_OK;
     }
     // unaligned CRAM, for the caller who asked for it: a host walk and a device decode of the base blocks, no text and no record scan
     if ((flags & LRGE_GPU_INGEST_CRAM) && box == FX_BOX_CRAM) {
@@ -922,6 +932,8 @@ extern "C" int lrge_hip_reads_census_map(lrge_hip_ctx *ctx, const char *path, in
 
 extern "C" void lrge_hip_read_map_free(lrge_hip_read_map *map) { delete map; }
 
+// (a CRAM map, kind FX_SEEK_CRAM: out[1] counts its points, one a slice in which a record starts; out[2], the stride, is 0; out[3] the bases.
+// lrge_hip_read_map_points: text_off is the slice's base offset, c_off the file offset of its BA block)
 extern "C" int lrge_hip_read_map_stats(const lrge_hip_read_map *map, uint64_t out[4]) {
     if (!map || !out) return LRGE_ERR_INVALID;
     out[0] = map->m.records; out[1] = map->m.pts.size(); out[2] = map->m.stride; out[3] = map->m.text_bytes;
@@ -1094,13 +1106,28 @@ static int fx_open_mapped(lrge_hip_ctx *ctx, FxInput &in, int flags, const lrge_
     if (!in.read(0, nh, h)) return fx_read_failed(ctx);
     const FxBox box = fx_container(h, nh);
     // what the census and the selected open refuse by name, whatever the map
-    if (box == FX_BOX_CRAM) { ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only"; return LRGE_ERR_UNPROVEN; }
+    if (box == FX_BOX_CRAM && !cram_select_flags(flags)) { ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only"; return LRGE_ERR_UNPROVEN; }
+    if (box == FX_BOX_CRAM || m.kind == FX_SEEK_CRAM) {      // the mapped open of a CRAM: the walk again, then only the touched slices' blocks
+        if (box != FX_BOX_CRAM) { ctx->err = "reads_open_mapped: the map is of another input"; return LRGE_ERR_INVALID; }
+        std::string raw;
+        int rc;
+        if (!in.d && (rc = fx_slurp(ctx, in.path, &raw))) return rc;
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        std::unique_ptr<lrge_hip_reads, void (*)(lrge_hip_reads *)> guard(new lrge_hip_reads(), lrge_hip_reads_free);
+        guard->ctx = ctx;
+        FxSeekMap of = m;
+        if ((rc = fx_cram_sampled(ctx, guard.get(), in.d ? in.d : (const u8 *)raw.data(), in.d ? in.len : raw.size(), FX_KEEP_SEL, sel, k, true, &of, fx_now_ms()))) return rc;
+        *out = guard.release();
+        return LRGE_OK;
+    }
     if (box == FX_BOX_ZSTD && (flags & LRGE_GPU_INFLATE_ZSTD) && !fx_zstd_slides(flags)) {
         ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only, not Zstandard input";
         return LRGE_ERR_UNPROVEN;
     }
     const bool aln = (flags & LRGE_GPU_INGEST_BAM) && (flags & LRGE_GPU_INGEST_SELECT_ALN);
     if (m.fmt == FX_FMT_BAM && !aln) { ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only"; return LRGE_ERR_UNPROVEN; }      // (a BAM map: DESIGN section 25)
+    const bool sam = (flags & LRGE_GPU_INGEST_SAM) && (flags & LRGE_GPU_INGEST_SELECT_SAM);
+    if (m.fmt == FX_FMT_SAM && !sam) { ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only"; return LRGE_ERR_UNPROVEN; }      // (a SAM map: DESIGN section 27)
     const bool gz = box == FX_BOX_GZIP, packed = gz || box == FX_BOX_BZIP2 || box == FX_BOX_ZSTD || box == FX_BOX_XZ;
     std::vector<BgzfBlock> t;
     u64 total = 0;
@@ -1131,7 +1158,7 @@ static int fx_open_mapped(lrge_hip_ctx *ctx, FxInput &in, int flags, const lrge_
     R->ctx = ctx;
     FxSink s(ctx, R, flags, FX_KEEP_SEL);
     s.run->dev.mapped = true;
-    if (m.fmt == FX_FMT_BAM) s.run->dev.kind = FX_FMT_BAM;       // (the sub-text is never sniffed: it is a record stream without a header)
+    if (m.fmt == FX_FMT_BAM || m.fmt == FX_FMT_SAM) s.run->dev.kind = m.fmt;      // (the sub-text is never sniffed: it is a record stream, or whole SAM lines, without a header)
     int rc = s.run->dev.select(FX_KEEP_SEL, plan.sel.data(), k);
     if (rc) return rc;
     s.run->attach(&s.blk);

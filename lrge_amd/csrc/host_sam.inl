@@ -5,7 +5,10 @@
 // the caller has seen the SAM magic at the start of R->d_text, or of the first window.
 // w: the text is a window (fx_window.h).  One that is not the last is cut directly behind its last line feed
 // (w->cut; 0: it has none yet) and the prefix is scanned as a complete text of that size with the window's own line table: all
-// its line feeds lie in the prefix, whose last line is the empty one behind the cut.  The bases go to the store.
+// its line feeds lie in the prefix, whose last line is the empty one behind the cut.  The bases go to the store.  A run that does
+// not keep all (the census and the selected open) brings neither the tables to the host nor the window to the
+// store: the bases are counted behind k_sam_records, the seek map takes its points (a record starts at the first byte of its line),
+// and FxWinDev::keep_window keeps the chosen records by its unpacked branch -- a SAM sequence is one line, seq_span == seq_len
 static int sam_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R, FxWinScan *w) {
     u64 n = R->n_text;
     const u8 *t = R->d_text;
@@ -39,7 +42,7 @@ static int sam_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R, FxWinScan *w) 
     // which lines carry a record, and the rank of each
     ALLOC_OR_FAIL(d_mark, sc, u32, n_lines);
     ALLOC_OR_FAIL(d_rank, sc, u32, n_lines);
-    ALLOC_OR_FAIL(d_flags, sc, u64, 3);                   // [0]: verdict bits (low word), [1]: identifier bytes, [2]: records (low word)
+    ALLOC_OR_FAIL(d_flags, sc, u64, 3);                   // [0]: verdict bits (low word), [1]: identifier bytes, [2]: records (low word), later the bases
     HIPCHK(ctx, hipMemsetAsync(d_flags, 0, 24, st));
     hipLaunchKernelGGL(k_sam_mark, dim3((u32)div_up(n_lines, SAM_THREADS)), dim3(SAM_THREADS), 0, st, t, n, (const u64 *)ls, c.n_lf, n_lines, d_mark);
     KCHK(ctx);
@@ -49,12 +52,24 @@ static int sam_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R, FxWinScan *w) 
     HIPCHK(ctx, ctx->d2h_sync(st));
     if (!n_rec) { R->fmt = FX_FMT_SAM; return LRGE_OK; }    // header lines only: the host returns no record
     if ((rc = fx_alloc_recs(ctx, R, n_rec))) return rc;
+    const FxKeepMode mode = w ? w->dev->mode : FX_KEEP_ALL;
+    if (mode != FX_KEEP_ALL) HIPCHK(ctx, hipMemsetAsync(d_flags + 2, 0, 8, st));      // (the record count is on the host: the word now sums the bases)
     ALLOC_OR_FAIL(d_seq_len, sc, u32, n_rec);
     ALLOC_OR_FAIL(d_name_len, sc, u32, n_rec);
     const u32 grid = (u32)std::min<u64>(div_up(n_lines, SAM_WAVES), (u64)ctx->n_cu * 8);
     hipLaunchKernelGGL(k_sam_records, dim3(grid), dim3(SAM_THREADS), 0, st, t, n, (const u64 *)ls, c.n_lf, n_lines, (const u32 *)d_mark, (const u32 *)d_rank, R->d_recs,
                        d_seq_len, d_name_len, (u32 *)d_flags, (unsigned long long *)(d_flags + 1));
     KCHK(ctx);
+    if (mode != FX_KEEP_ALL) {                              // the window's bases come back with the verdict words: no synchronisation of their own
+        u64 bases = 0;
+        hipLaunchKernelGGL(k_fx_bases, dim3((u32)std::min<u64>(div_up(n_rec, FX_THREADS), (u64)ctx->n_cu * 8)), dim3(FX_THREADS), 0, st, (const u32 *)d_seq_len, n_rec,
+                           (unsigned long long *)(d_flags + 2));
+        KCHK(ctx);
+        if ((rc = fx_flags_back(ctx, d_flags, "a SAM record line outside the strict form", &name_bytes, &bases))) return rc;
+        R->fmt = FX_FMT_SAM;
+        if (w->dev->map && (rc = w->dev->seek_window(sc, R, n_rec, n))) return rc;
+        return w->dev->keep_window(sc, R, d_seq_len, d_name_len, n_rec, n, bases);
+    }
     if ((rc = fx_flags_back(ctx, d_flags, "a SAM record line outside the strict form", &name_bytes))) return rc;
     R->fmt = FX_FMT_SAM;                                    // (a refused file leaves no read set, so no format either)
     if ((rc = fx_tables_to_host(ctx, R, sc, n_rec, d_seq_len, d_name_len, name_bytes)) || !w) return rc;

@@ -3,7 +3,8 @@
 // record line in steps of SAM_STEP bytes, 64 "lanes" of one 16-byte group each, the tabs ranked by an inclusive scan of the
 // lanes' popcounts -- so the CPU suite checks the stepping against the host parser (tests/test_sam_twin.py); and the windowed
 // ingest of fx_window.h over the same passes, with the window and the appended piece as parameters
-// (tests/test_sam_window_twin.py).
+// (tests/test_sam_window_twin.py); and the sampled ingest of DESIGN section 27 over the same windows -- the census, the selection,
+// the seek map and the mapped pass (tests/test_sam_select_twin.py, tests/test_sam_seek_twin.py).
 // TEST INFRASTRUCTURE, not part of the product library.
 #include <stdint.h>
 #include <string.h>
@@ -109,8 +110,9 @@ int parse(const uint8_t *t, uint64_t n, uint64_t *cut) {
 
 // ---- the windowed ingest: win_twin.h over the passes above ----
 struct Scan {
+    bool header = true;                 // false: the sub-text of a mapped run, whole lines of a proven text -- it starts with a record line and is never sniffed
     int scan(const std::vector<uint8_t> &blk, bool first, bool end, uint64_t *cut, int *fmt) {
-        if (first && !sam_sniff(blk.data(), blk.size())) return (int)FX_UNPROVEN;     // (later windows are SAM by the run, not by their first bytes)
+        if (first && header && !sam_sniff(blk.data(), blk.size())) return (int)FX_UNPROVEN;     // (later windows are SAM by the run, not by their first bytes)
         uint64_t c = 0;
         const int rc = parse(blk.data(), blk.size(), end ? nullptr : &c);
         *cut = end ? blk.size() : c;
@@ -123,6 +125,17 @@ struct Scan {
     }
 };
 WinTwinOut gw;
+FxSeekMap gm;                           // the map of the last sam_twin_census_map
+FxSeekPlan gp;                          // the plan of the last sam_twin_seek_plan / sam_twin_mapped
+
+// one run through the windows in a keep mode
+int windowed_run(const uint8_t *t, uint64_t n, uint64_t window, uint64_t piece, bool header, FxKeepMode mode, const uint32_t *sel, uint64_t k, FxSeekMap *map) {
+    gw = WinTwinOut();
+    if (!piece) return -1;
+    Scan sc;
+    sc.header = header;
+    return win_twin_run(sc, t, n, window, piece, false, gw, mode, sel, k, map, FX_LEAD_SAM);
+}
 }  // namespace
 
 extern "C" {
@@ -138,11 +151,73 @@ int sam_twin_parse(const uint8_t *t, uint64_t n) {
 // FX_UNPROVEN, FX_TOO_MANY; the records by sam_twin_windowed_count / _table / _seq, the counts by _stats (windows flushed first: 0
 // means the text ended before its first flush and was scanned whole, as without windows, and no store was kept)
 int sam_twin_windowed(const uint8_t *t, uint64_t n, uint64_t window, uint64_t piece) {
-    gw = WinTwinOut();
-    if (!piece) return -1;
-    Scan sc;
-    return win_twin_run(sc, t, n, window, piece, false, gw);
+    return windowed_run(t, n, window, piece, true, FX_KEEP_ALL, nullptr, 0, nullptr);
 }
+
+// The same text in the two passes of the sampled ingest, as bam_twin_census / _selected.  sam_twin_census keeps
+// nothing: out = {records, sequence bases, text bytes, windows flushed}.  sam_twin_selected keeps records sel[0, k) (strictly
+// ascending ordinals): the accessors below read its result as they read sam_twin_windowed's (the store holds the chosen records'
+// bases), sam_twin_windowed_select_stats what the run saw and kept.  0, FX_UNPROVEN, FX_TOO_MANY, or WIN_TWIN_INVALID for a
+// selection that is not ascending or reaches past the records
+int sam_twin_census(const uint8_t *t, uint64_t n, uint64_t window, uint64_t piece, uint64_t out[4]) {
+    out[0] = out[1] = out[2] = out[3] = 0;
+    const int rc = windowed_run(t, n, window, piece, true, FX_KEEP_NONE, nullptr, 0, nullptr);
+    if (!rc) { out[0] = gw.sel.seen; out[1] = gw.sel.bases_seen; out[2] = n; out[3] = gw.st.windows; }
+    return rc;
+}
+
+int sam_twin_selected(const uint8_t *t, uint64_t n, uint64_t window, uint64_t piece, const uint32_t *sel, uint64_t k) {
+    return windowed_run(t, n, window, piece, true, FX_KEEP_SEL, sel, k, nullptr);
+}
+
+// The seek map and the mapped second pass (fx_seek.h), as bam_twin_census_map / _seek_plan / _mapped: a record starts at the first
+// byte of its line (fx_rec_start with FX_LEAD_SAM), so header, @CO and empty lines lie in front of whichever point follows them;
+// the planner is fx_seek_plan
+int sam_twin_census_map(const uint8_t *t, uint64_t n, uint64_t window, uint64_t piece, uint64_t stride, uint64_t out[4]) {
+    gm = FxSeekMap();
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (!stride) return -1;
+    FxSeekMap m;
+    m.stride = stride;
+    const int rc = windowed_run(t, n, window, piece, true, FX_KEEP_NONE, nullptr, 0, &m);
+    if (rc) return rc;
+    out[0] = gw.sel.seen; out[1] = gw.sel.bases_seen; out[2] = n; out[3] = gw.st.windows;
+    m.records = gw.sel.seen; m.bases = gw.sel.bases_seen; m.text_bytes = m.file_len = n; m.windows = gw.st.windows; m.fmt = gw.fmt;
+    gm = m;
+    return 0;
+}
+
+uint64_t sam_twin_map_points(uint64_t *ord, uint64_t *off, uint64_t cap) {
+    for (uint64_t i = 0; i < gm.pts.size() && i < cap; ++i) { ord[i] = gm.pts[i].ord; off[i] = gm.pts[i].off; }
+    return gm.pts.size();
+}
+
+int sam_twin_seek_plan(const uint32_t *c_len, const uint32_t *isize, uint64_t n_blk, uint64_t file_len, const uint32_t *sel, uint64_t k, uint64_t out[4]) {
+    return win_twin_seek_plan(gm, c_len, isize, n_blk, file_len, sel, k, &gp, out);
+}
+uint64_t sam_twin_plan_runs(uint64_t *out, uint64_t cap) { return win_twin_plan_runs(gp, out, cap); }
+void sam_twin_plan_sel(uint32_t *out) { if (!gp.sel.empty()) memcpy(out, gp.sel.data(), gp.sel.size() * 4); }
+
+// The mapped second pass over text t, which must be the text of the last map (WIN_TWIN_INVALID: another size): the runs of the
+// plan, concatenated, are whole lines -- a SAM text without a header, scanned from its first window on without the sniff.
+// FX_UNPROVEN also when the sub-text does not hold the plan's records
+int sam_twin_mapped(const uint8_t *t, uint64_t n, uint64_t window, uint64_t piece, const uint32_t *sel, uint64_t k) {
+    gw = WinTwinOut(); gp = FxSeekPlan();
+    if (!piece) return -1;
+    if (n != gm.text_bytes || gm.kind != FX_SEEK_PLAIN || win_twin_sel_fits(gm, sel, k)) return WIN_TWIN_INVALID;
+    fx_seek_plan(gm, sel, k, &gp);
+    const std::vector<uint8_t> sub = win_twin_sub_text(gp, t);
+    int rc = windowed_run(sub.data(), sub.size(), window, piece, false, FX_KEEP_SEL, gp.sel.data(), k, nullptr);
+    if (rc == WIN_TWIN_INVALID || (!rc && gw.sel.seen != gp.records)) rc = (int)FX_UNPROVEN;        // the map does not fit the input
+    if (rc) { gw = WinTwinOut(); return rc; }
+    win_twin_mapped_back(gw, gp, gm);
+    if (gw.fmt == FX_FMT_EMPTY) gw.fmt = gm.fmt;
+    return 0;
+}
+
+void sam_twin_windowed_select_stats(uint64_t out[4]) { gw.select_stats(out); }
+// the records of every window of the last run, in order (at most `cap` are written); returns how many windows took records or a cut
+uint64_t sam_twin_windowed_cuts(uint64_t *out, uint64_t cap) { return gw.cuts(out, cap); }
 
 uint64_t sam_twin_windowed_count(void) { return gw.recs.size(); }
 void sam_twin_windowed_table(FxRec *out) { gw.table(out); }

@@ -44,7 +44,7 @@ template <class Scan> struct WinTwin {
     const uint32_t *sel = nullptr;
     uint64_t k = 0, at = 0;
     FxSeekMap *map = nullptr;           // a census that leaves a seek map (fx_seek.h): every window's records go through the point rule
-    uint32_t lead = FX_LEAD_TEXT;       // where a record starts in front of its identifier (fx_rec_start): FX_LEAD_BAM for a BAM twin
+    uint32_t lead = FX_LEAD_TEXT;       // where a record starts in front of its identifier (fx_rec_start): FX_LEAD_BAM for a BAM twin, FX_LEAD_SAM for a SAM twin
     WinTwin(Scan &s, WinTwinOut &o) : scan(s), out(o) {}
     void keep(const FxRec &r, uint64_t cut) {
         const uint64_t a = out.store.size();
@@ -113,7 +113,7 @@ template <class Scan> int win_twin_run(Scan &scan, const uint8_t *t, uint64_t n,
     return 0;
 }
 
-// ---- the seek map of a twin (fx_seek.h), once for the twins that have one (fastx_twin.cpp, bam_twin.cpp) ----
+// ---- the seek map of a twin (fx_seek.h), once for the twins that have one (fastx_twin.cpp, bam_twin.cpp, sam_twin.cpp) ----
 // the selection against map m: 0, or WIN_TWIN_INVALID for one that is not ascending or reaches the map's records
 static inline int win_twin_sel_fits(const FxSeekMap &m, const uint32_t *sel, uint64_t k) {
     if ((k && !sel) || !fx_sel_ascending(sel, k)) return WIN_TWIN_INVALID;

@@ -5,7 +5,10 @@
 // (tests/test_cram_twin.py dumps them).  Every stream goes through the twin's batch decode alone and must give its plain bytes;
 // every file goes through the walk and the rounds, whole and one block a round, and must either be refused or give the bases the host
 // reader gives (both run here: lrge::io::cram::parse).  Every buffer the block decode touches is a heap block of its exact size
-// (cram_twin.cpp), so a step outside one ends the run.  Exit code 0: all held.
+// (cram_twin.cpp), so a step outside one ends the run.  Every file that opens also goes through the four calls of the sampled ingest
+// (cram_twin_sampled) -- the census, every third read and the last selected, the census with a map and the mapped
+// open of the same reads -- whose round scratch is a heap block of exactly the round's raw size and whose store one of exactly the
+// chosen bases: the kept reads must be the host reader's.  Exit code 0: all held.
 #include <dirent.h>
 
 #include <cstdio>
@@ -24,7 +27,7 @@ int main(int argc, char **argv) {
         while (dirent *e = readdir(d)) names.push_back(e->d_name);
         closedir(d);
     }
-    int streams = 0, files = 0, refused = 0, bad = 0;
+    int streams = 0, files = 0, refused = 0, bad = 0, sampled = 0;
     for (const std::string &n : names) {
         if (n.size() > 5 && n.compare(0, 2, "s_") == 0 && n.compare(n.size() - 3, 3, ".in") == 0) {
             const std::string comp = slurp(dir + "/" + n), plain = slurp(dir + "/" + n.substr(0, n.size() - 3) + ".out");
@@ -56,10 +59,33 @@ int main(int argc, char **argv) {
                 for (uint64_t i = 0; same && i < k; ++i)
                     same = host[i].first == nm.substr(noff[i], noff[i + 1] - noff[i]) && host[i].second == std::string((const char *)bases.data() + boff[i], len[i]);
                 if (!same) { printf("FILE %s: the twin's records are not the host reader's\n", n.c_str()); ++bad; }
+                // the sampled ingest of the same file at the same round size
+                std::vector<uint32_t> sel;
+                for (uint64_t i = 0; i < k; ++i) if (i % 3 == 0 || i + 1 == k) sel.push_back((uint32_t)i);
+                uint64_t cs[4];
+                const uint8_t *fd = (const uint8_t *)file.data();
+                if (!same || cram_twin_sampled(0, fd, file.size(), nullptr, 0, round_bytes, 0, 0, cs) || cs[0] != k || cs[1] != cram_twin_base_bytes() ||
+                    cram_twin_sampled(2, fd, file.size(), nullptr, 0, round_bytes, 0, 0, cs) || cs[0] != k) { printf("FILE %s: the census disagrees with the open\n", n.c_str()); ++bad; continue; }
+                for (int what : {1, 3}) {
+                    bool kept_same = cram_twin_sampled(what, fd, file.size(), sel.data(), sel.size(), round_bytes, 0, 0, cs) == 0 && cram_twin_kept() == sel.size();
+                    if (kept_same) {
+                        std::vector<uint32_t> sl(sel.size() + 1);
+                        std::vector<uint64_t> so(sel.size() + 1), sb(sel.size() + 1);
+                        std::string sn(cram_twin_kept_name_bytes() + 1, '\0');
+                        uint64_t stats[CRAM_STAT_WORDS], seek[4], mem[4];
+                        cram_twin_sampled_stats(stats, seek, mem);
+                        std::vector<uint8_t> store(mem[0] + 1);
+                        cram_twin_kept_table(sel.data(), sl.data(), so.data(), &sn[0], sb.data(), store.data());
+                        for (uint64_t j = 0; kept_same && j < sel.size(); ++j)
+                            kept_same = host[sel[j]].first == sn.substr(so[j], so[j + 1] - so[j]) && host[sel[j]].second == std::string((const char *)store.data() + sb[j], sl[j]);
+                    }
+                    if (!kept_same) { printf("FILE %s: the %s open's reads are not the host reader's\n", n.c_str(), what == 1 ? "selected" : "mapped"); ++bad; }
+                    else ++sampled;
+                }
             }
             ++files;
         }
     }
-    printf("%d streams ok, %d files walked (%d opens refused), %d bad\n", streams, files, refused, bad);
+    printf("%d streams ok, %d files walked (%d opens refused), %d sampled opens ok, %d bad\n", streams, files, refused, sampled, bad);
     return bad ? 1 : (streams && files ? 0 : 3);
 }

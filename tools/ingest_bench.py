@@ -15,6 +15,9 @@ one thread, then the open of the plain text) run one after the other, so all fiv
 "zstd_windowed" of --out.  With LRGE_HIP_LIB_AB naming a build from before the flag only the resident open is timed, under the
 key "zstd_windowed_parent".
 --sampled K1,K2,.. --seek: on the plain and the BGZF FASTQ file and on the uBAM (kind bam: LRGE_GPU_INGEST_SELECT_ALN), for every K, the census without and with a seek map
+(--kinds sam,sam.gz,cram --sampled K1,K2 --seek: the same on unaligned SAM text, plain and bgzipped, under LRGE_GPU_INGEST_SELECT_SAM, and on an
+unaligned CRAM of --cram-slices slices under LRGE_GPU_INGEST_SELECT_CRAM; the single open beside them is the parent
+commit's route for the same command -- the full windowed SAM open, the full CRAM open.  The kinds sam.gz and cram are written only when named)
 (lrge_hip_reads_census, lrge_hip_reads_census_map), the selected open and the mapped open of the same K seeded ordinals
 (lrge_hip_reads_open_selected, lrge_hip_reads_open_mapped) and the existing windowed open, all alternating in one run; with the
 bytes the mapped open brought and read, under the key "sampled_seek" / "<K>" of --out.
@@ -145,6 +148,19 @@ HELPER_SEEK = r"""
 #include <vector>
 #include "lrge_hip.h"
 static double now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+static uint64_t g_kept[2];      // identifier bytes on the host and bytes in the store of the last mapped handle
+extern "C" void kept_bytes(uint64_t out[2]) { out[0] = g_kept[0]; out[1] = g_kept[1]; }
+// identifier bytes on the host and bytes in the store of the single full open
+extern "C" int full_bytes(lrge_hip_ctx *ctx, const char *path, int flags, uint64_t out[2]) {
+    lrge_hip_reads *r = nullptr;
+    const int rc = lrge_hip_reads_open(ctx, path, flags, &r);
+    if (rc) return rc;
+    uint64_t w[4] = {0, 0, 0, 0};
+    lrge_hip_reads_window_stats(r, w);
+    out[0] = lrge_hip_reads_name_bytes(r); out[1] = w[0] ? w[1] : lrge_hip_reads_text_bytes(r);      // (a resident text stays whole)
+    lrge_hip_reads_free(r);
+    return 0;
+}
 extern "C" int route_seek(lrge_hip_ctx *ctx, const char *path, int flags, const uint32_t *sel, uint32_t k, double ms[5], uint64_t census[4], uint64_t map_stats[4],
                           uint64_t sel_stats[4], uint64_t seek[4]) {
     uint64_t c2[4], s2[4];
@@ -167,6 +183,8 @@ extern "C" int route_seek(lrge_hip_ctx *ctx, const char *path, int flags, const 
     if (!rc) rc = lrge_hip_seqset_wait(s);
     const double t5 = now();
     lrge_hip_read_map_stats(m, map_stats);
+    g_kept[0] = lrge_hip_reads_name_bytes(b);
+    { uint64_t w[4] = {0, 0, 0, 0}; lrge_hip_reads_window_stats(b, w); g_kept[1] = w[1]; }
     lrge_hip_reads_select_stats(a, s2);
     lrge_hip_reads_select_stats(b, sel_stats);
     lrge_hip_reads_seek_stats(b, seek);
@@ -221,6 +239,30 @@ def _bgzf(data, block=65280, level=1):
 
 
 KINDS = ("fq", "bgzf.fq.gz", "fq.gz", "bam", "sam")
+EXTRA_KINDS = ("sam.gz", "cram")      # written only when --kinds names them: bgzipped SAM, and an unaligned CRAM (cram_file)
+# the flags of the single open and of the sampled calls, by kind (fq, bgzf.fq.gz, bam: as before)
+OPEN_FLAGS = {"cram": 3 | 512}
+SEEK_FLAGS = {"bam": 15 | 1024, "sam": 15 | 4096, "sam.gz": 15 | 4096, "cram": 3 | 512 | 8192}
+
+
+def cram_file(path, slices, slice_kb):
+    """an unaligned CRAM 3.0 of `slices` slices of slice_kb of bases each (BA in rANS 4x8 order 1, what CRAM 3.0 writers use for
+    bases), made as tools/cram_bench.py makes its files: one container of four distinct slices is encoded once by tests/cram_writer.py
+    and repeated -- containers are independent, so the file is a legal CRAM whose reads repeat.  Returns the bases"""
+    import numpy as np
+    import cram_writer as CW
+    rng = np.random.Generator(np.random.PCG64(7))
+    read_len, per_slice = 8192, max(1, slice_kb * 1024 // 8192)
+    acgt = np.frombuffer(b"ACGT", np.uint8)
+    reads = [(b"bench/%d" % i, bytes(rng.choice(acgt, read_len))) for i in range(4 * per_slice)]
+    hdr = b"@HD\tVN:1.6\tSO:unsorted\n"
+    head = 26 + len(CW.container(0, 0, 0, 0, 0, 0, [CW.block("raw", 0, 0, struct.pack("<i", len(hdr)) + hdr)], [0]))
+    eof = CW.container(-1, 4542278, 0, 0, 0, 0, [CW.block("raw", 1, 0, b"\x01\x00\x01\x00\x01\x00")], [])
+    one = CW.write_cram(reads, method="gzip", slices_per_container=4, records_per_slice=per_slice, with_quality=False, with_tags=False, method_for={"BA": "rans1"})
+    k = max(1, slices // 4)
+    with open(path, "wb") as fh:
+        fh.write(one[:head] + one[head:len(one) - len(eof)] * k + eof)
+    return len(reads) * read_len * k
 
 
 def _part(args):
@@ -243,6 +285,9 @@ def _part(args):
     if "sam" in kinds:
         sam = (SAM_HEADER if idx == 0 else b"") + _usam(d)
         out["sam"] = (len(sam), sam)
+    if "sam.gz" in kinds:
+        sam = (SAM_HEADER if idx == 0 else b"") + _usam(d)
+        out["sam.gz"] = (len(sam), _bgzf(sam))
     return out
 
 
@@ -257,7 +302,7 @@ def write_files(d, parts, kinds):
                 files[k].write(data)
                 size[k] += n
     for k, fh in files.items():
-        if k in ("bgzf.fq.gz", "bam"):
+        if k in ("bgzf.fq.gz", "bam", "sam.gz"):
             fh.write(W.EOF_BLOCK)
         fh.close()
     return paths, size
@@ -441,15 +486,21 @@ def seek_runs(a, ctx, H, HK, kinds, paths, text_bytes, ks):
             runs, sel, seen = [], None, {}
             for rep in range(a.reps + 1):
                 ms2, st, nr, nb, tb, bs, win = (C.c_double * 2)(), (C.c_float * 4)(), C.c_uint64(), C.c_uint64(), C.c_uint64(), (C.c_uint64 * 6)(), (C.c_uint64 * 4)()
-                rc = H.route_device(ctx.h, p.encode(), 15 | 32 | 64, C.byref(ms2), C.byref(st), C.byref(nr), C.byref(nb), C.byref(tb), C.byref(bs), C.byref(win))
+                rc = H.route_device(ctx.h, p.encode(), OPEN_FLAGS.get(kind, 15 | 32 | 64), C.byref(ms2), C.byref(st), C.byref(nr), C.byref(nb), C.byref(tb), C.byref(bs), C.byref(win))
                 assert rc == 0, (kind, rc, ctx._lib.lrge_hip_last_error(ctx.h))
+                if sel is None:
+                    full = (C.c_uint64 * 2)()
+                    assert HK.full_bytes(ctx.h, p.encode(), OPEN_FLAGS.get(kind, 15 | 32 | 64), C.byref(full)) == 0
                 if sel is None:
                     sel = np.sort(np.random.default_rng(1).choice(nr.value, min(K, nr.value), replace=False)).astype(np.uint32)
                 ms5, cen, mst, sst, sk = (C.c_double * 5)(), (C.c_uint64 * 4)(), (C.c_uint64 * 4)(), (C.c_uint64 * 4)(), (C.c_uint64 * 4)()
-                rc = HK.route_seek(ctx.h, p.encode(), 15 | (1024 if kind == "bam" else 0), sel.ctypes.data, sel.size, C.byref(ms5), C.byref(cen), C.byref(mst), C.byref(sst), C.byref(sk))
+                rc = HK.route_seek(ctx.h, p.encode(), SEEK_FLAGS.get(kind, 15), sel.ctypes.data, sel.size, C.byref(ms5), C.byref(cen), C.byref(mst), C.byref(sst), C.byref(sk))
                 assert rc == 0, (kind, rc, ctx._lib.lrge_hip_last_error(ctx.h))
                 assert (cen[0], cen[1], cen[2]) == (nr.value, nb.value, text_bytes[kind]) and (sst[0], sst[1], sst[2]) == (nr.value, sel.size, nb.value), (list(cen), list(sst))
-                seen = dict(reads=nr.value, bases=nb.value, kept_bases=sst[3], points=mst[1], stride=mst[2], runs=sk[0], text_bytes_brought=sk[1], file_bytes_read=sk[2], blocks_decoded=sk[3])
+                kb = (C.c_uint64 * 2)()
+                HK.kept_bytes(C.byref(kb))
+                seen = dict(reads=nr.value, bases=nb.value, kept_bases=sst[3], points=mst[1], stride=mst[2], runs=sk[0], text_bytes_brought=sk[1], file_bytes_read=sk[2], blocks_decoded=sk[3],
+                            open_store_bytes=full[1], open_name_bytes=full[0], mapped_store_bytes=kb[1], mapped_name_bytes=kb[0])
                 if rep:                                                # (run 0 is the warm-up)
                     runs.append(dict(open_ms=ms2[0], census_ms=ms5[0], census_map_ms=ms5[1], selected_open_ms=ms5[2], mapped_open_ms=ms5[3], seqset_k_ms=ms5[4],
                                      map_cost_ms=ms5[1] - ms5[0], two_pass_ms=ms5[1] + ms5[3], two_pass_parent_ms=ms5[0] + ms5[2]))
@@ -459,7 +510,10 @@ def seek_runs(a, ctx, H, HK, kinds, paths, text_bytes, ks):
                 f["%s_range" % key] = (min(x[key] for x in runs), max(x[key] for x in runs))
             out["files"][kind] = f
             print(K, kind, json.dumps({k: v for k, v in f.items() if k != "every_run"}), flush=True)
-        result.setdefault("sampled_seek", {})[str(K)] = out
+        prev = result.setdefault("sampled_seek", {}).get(str(K))
+        if prev and (prev.get("window_bytes"), prev.get("reps")) == (out["window_bytes"], out["reps"]):      # (a second run with other kinds into the same --out adds its files)
+            out["files"] = {**prev["files"], **out["files"]}
+        result["sampled_seek"][str(K)] = out
     ctx.set_option("INGEST_WINDOW_BYTES", None)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     json.dump(result, open(a.out, "w"), indent=1)
@@ -478,6 +532,8 @@ def main():
     ap.add_argument("--sampled", default="0")
     ap.add_argument("--seek", action="store_true")
     ap.add_argument("--zstd-windowed", type=int, default=0)
+    ap.add_argument("--cram-slices", type=int, default=512)
+    ap.add_argument("--cram-slice-kb", type=int, default=256)
     a = ap.parse_args()
     seek_ks = [int(k) for k in a.sampled.split(",") if int(k)] if a.seek else []
     a.sampled = 0 if a.seek else int(a.sampled)
@@ -515,8 +571,11 @@ def main():
             os.remove(p)
         os.rmdir(work)
         return
-    kinds = [k for k in KINDS if k in a.kinds.split(",")]
-    paths, text_bytes = write_files(work, parts, kinds)
+    kinds = [k for k in KINDS + EXTRA_KINDS if k in a.kinds.split(",")]
+    paths, text_bytes = write_files(work, parts, [k for k in kinds if k != "cram"])
+    if "cram" in kinds:
+        paths["cram"] = os.path.join(work, "ingest.cram")
+        text_bytes["cram"] = cram_file(paths["cram"], a.cram_slices, a.cram_slice_kb)      # (what lrge_hip_reads_text_bytes reports: the bases)
     print("files written in %.0f s: %s text bytes" % (time.perf_counter() - t0, text_bytes), flush=True)
     ctx = engine.Context(0)
     H = C.CDLL(so)
@@ -529,8 +588,10 @@ def main():
         build(extra[1], extra[0])
         HK = C.CDLL(extra[1])
         HK.route_seek.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(C.c_double * 5)] + [C.POINTER(C.c_uint64 * 4)] * 4
+        HK.full_bytes.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_uint64 * 2)]
+        HK.kept_bytes.argtypes = [C.POINTER(C.c_uint64 * 2)]
         a.window_mb = int(a.window_mb.split(",")[0])
-        seek_runs(a, ctx, H, HK, [k for k in kinds if k in ("fq", "bgzf.fq.gz", "bam")], paths, text_bytes, seek_ks)
+        seek_runs(a, ctx, H, HK, [k for k in kinds if k in ("fq", "bgzf.fq.gz", "bam", "sam", "sam.gz", "cram")], paths, text_bytes, seek_ks)
         ctx.close()
         for p in list(paths.values()) + [src, so] + extra:
             os.remove(p)

@@ -123,7 +123,7 @@ int main(int argc, char **argv) {
         if (gpu_ingest) {
             const int fl = LRGE_GPU_INFLATE_BGZF | LRGE_GPU_INFLATE_GZIP | LRGE_GPU_INGEST_BAM | LRGE_GPU_INGEST_SAM | LRGE_GPU_INGEST_WINDOWED | LRGE_GPU_INGEST_WINDOWED_ALN | (gpu_bzip2 ? LRGE_GPU_INFLATE_BZIP2 : 0) | (gpu_zstd ? LRGE_GPU_INFLATE_ZSTD | LRGE_GPU_INGEST_WINDOWED_ZSTD : 0) | (gpu_xz ? LRGE_GPU_INFLATE_XZ : 0) | (gpu_cram ? LRGE_GPU_INGEST_CRAM : 0);
             if (gpu_sample) {
-                sampled.reset(new lrge::SampledSource{input, fl | LRGE_GPU_INGEST_SELECT_ALN, device});       // (unaligned BAM takes the sampled route too: DESIGN section 25)
+                sampled.reset(new lrge::SampledSource{input, fl | LRGE_GPU_INGEST_SELECT_ALN | LRGE_GPU_INGEST_SELECT_SAM | (gpu_cram ? LRGE_GPU_INGEST_SELECT_CRAM : 0), device});       // (unaligned BAM, SAM and -- with --gpu-cram -- CRAM take the sampled route too: DESIGN sections 25 and 27)
                 sampled->seek = gpu_seek;
                 if (!sampled->census()) sampled.reset();
                 else if (!sampled->counts[0]) throw lrge::LrgeError(LRGE_ERR_IO, "IO error: Is the file empty?");

@@ -8,7 +8,8 @@
 // two passes of the selected ingest (fastx_twin_census, fastx_twin_selected) on the same text, window and piece, and by the seek map
 // (fastx_twin_census_map at strides 1, 64, 3000 and above the text, fastx_twin_seek_plan for the plain text and for BGZF blocks of 3000 text
 // bytes, fastx_twin_mapped).  Every BAM run is followed by the same passes of its own twin (bam_twin_census, bam_twin_selected,
-// bam_twin_census_map at strides 1, 36, 3000 and above the text, bam_twin_seek_plan, bam_twin_mapped).  Prints the
+// bam_twin_census_map at strides 1, 36, 3000 and above the text, bam_twin_seek_plan, bam_twin_mapped), every SAM run by those of sam_twin.cpp (sam_twin_census, sam_twin_selected,
+// sam_twin_census_map at strides 1, 64, 3000 and above the text, sam_twin_seek_plan, sam_twin_mapped).  Prints the
 // verdict counts; the exit status is 1 when the verdicts of one file disagree.
 // TEST INFRASTRUCTURE, not part of the product library.
 #include <stdio.h>
@@ -179,6 +180,72 @@ static uint64_t bam_sampled(const char *path, const std::vector<uint8_t> &t, uin
     return bad;
 }
 
+// The sampled ingest of a SAM text whose windowed run gave verdict `rc` and table `all` (name_off in the whole text), as bam_sampled:
+// census and selection (the store holds the chosen bases), then the map -- its points are first bytes of record lines, the first
+// record 0 --, the plan on the plain text and on made-up BGZF blocks, and the mapped run, which gives the selected run's records and
+// store.  Returns the disagreements
+static uint64_t sam_sampled(const char *path, const std::vector<uint8_t> &t, uint64_t window, uint64_t piece, int rc, const std::vector<FxRec> &all) {
+    using namespace sam_twin;
+    uint64_t bad = 0, bases = 0, cs[4], ss[4];
+    for (const FxRec &r : all) bases += r.seq_len;
+    const auto fail = [&](const char *what, uint64_t stride) { ++bad; fprintf(stderr, "%s: window %llu piece %llu stride %llu: %s\n", path, (unsigned long long)window, (unsigned long long)piece, (unsigned long long)stride, what); };
+    const int crc = sam_twin_census(t.data(), t.size(), window, piece, cs);
+    if (crc != rc || (!rc && (cs[0] != all.size() || cs[1] != bases || cs[2] != t.size()))) fail("the census disagrees with the windowed run", 0);
+    std::vector<uint32_t> sel;
+    for (uint64_t i = 0; i < all.size(); ++i) if (i % 3 == 0 || i + 1 == all.size()) sel.push_back((uint32_t)i);
+    std::vector<uint8_t> store;
+    const auto kept_right = [&](bool compare) {
+        const uint64_t k = sam_twin_windowed_count();
+        std::vector<FxRec> tab(k);
+        sam_twin_windowed_table(tab.data());
+        sam_twin_windowed_select_stats(ss);
+        uint64_t kept = 0;
+        bool same = k == sel.size();
+        for (uint64_t j = 0; j < k && same; ++j) {
+            std::vector<uint8_t> out(tab[j].seq_len + 1);
+            same = tab[j].name_off == all[sel[j]].name_off && tab[j].seq_len == all[sel[j]].seq_len && tab[j].seq_off == kept && tab[j].seq_span == tab[j].seq_len &&
+                   sam_twin_windowed_seq(j, out.data()) == tab[j].seq_len;
+            kept += tab[j].seq_len;
+        }
+        std::vector<uint8_t> st(sam_twin_windowed_store(nullptr) + 1);
+        st.resize(sam_twin_windowed_store(st.data()));
+        if (compare) same = same && st == store; else store = st;
+        return same && st.size() == kept && ss[0] == all.size() && ss[1] == k && ss[2] == bases && ss[3] == kept;
+    };
+    const int src = sam_twin_selected(t.data(), t.size(), window, piece, sel.data(), sel.size());
+    if (src != rc) fail("the selected run has another verdict", 0);
+    if (src || rc) return bad;
+    if (!kept_right(false)) fail("the selected run kept other records", 0);
+    sel.push_back((uint32_t)all.size());
+    if (sam_twin_selected(t.data(), t.size(), window, piece, sel.data(), sel.size()) != WIN_TWIN_INVALID) fail("an ordinal past the records is not invalid", 0);
+    sel.pop_back();
+    const uint64_t strides[] = {1, 64, 3000, (uint64_t)t.size() + 1};
+    for (uint64_t stride : strides) {
+        uint64_t ps[4], bs[4];
+        if (sam_twin_census_map(t.data(), t.size(), window, piece, stride, cs) || cs[0] != all.size() || cs[1] != bases) { fail("the census with a map disagrees with the windowed run", stride); continue; }
+        const uint64_t np = sam_twin_map_points(nullptr, nullptr, 0);
+        std::vector<uint64_t> ord(np + 1), off(np + 1);
+        sam_twin_map_points(ord.data(), off.data(), np);
+        bool good = all.empty() ? np == 0 : np > 0 && ord[0] == 0;
+        for (uint64_t i = 0; i < np && good; ++i) good = ord[i] < all.size() && off[i] == all[ord[i]].name_off && (!i || (ord[i] > ord[i - 1] && off[i] / stride > off[i - 1] / stride));
+        if (!good) { fail("the points are not first record starts of their cells", stride); continue; }
+        if (sam_twin_seek_plan(nullptr, nullptr, 0, 0, sel.data(), sel.size(), ps) || ps[1] > t.size() || ps[1] != ps[2] || ps[3]) fail("the plan of the plain text", stride);
+        std::vector<uint32_t> c_len, isize;
+        uint64_t file_len = 0;
+        for (uint64_t o = 0; o < t.size(); o += 3000) { isize.push_back((uint32_t)std::min<uint64_t>(3000, t.size() - o)); c_len.push_back(isize.back() / 2 + 100); file_len += c_len.back(); }
+        isize.push_back(0); c_len.push_back(28); file_len += 28;    // (the empty block at the end of a BGZF file)
+        if (sam_twin_seek_plan(c_len.data(), isize.data(), c_len.size(), file_len, sel.data(), sel.size(), bs) || bs[0] != ps[0] || bs[1] != ps[1] || bs[2] > file_len ||
+            bs[3] > c_len.size() || (!sel.empty() && (!bs[3] || bs[2] < 28)))
+            fail("the plan of the BGZF blocks", stride);
+        if (sam_twin_mapped(t.data(), t.size(), window, piece, sel.data(), sel.size())) { fail("the mapped run is not proven", stride); continue; }
+        if (!kept_right(true)) fail("the mapped run kept other records", stride);
+        sel.push_back((uint32_t)all.size());
+        if (sam_twin_mapped(t.data(), t.size(), window, piece, sel.data(), sel.size()) != WIN_TWIN_INVALID) fail("an ordinal past the records is not invalid", stride);
+        sel.pop_back();
+    }
+    return bad;
+}
+
 int main(int argc, char **argv) {
     const uint64_t windows[] = {64, 257, 3001, 20000}, segs[] = {64, 257, 4096}, tiles[] = {64, 4096};
     uint64_t runs = 0, proven = 0, bad = 0;
@@ -210,6 +277,7 @@ int main(int argc, char **argv) {
                     if (!is_bam && !is_sam) bad += fastx_selected(argv[a], t, S, window, piece, rc, tab);
                     if (!is_bam && !is_sam) bad += fastx_seek(argv[a], t, S, window, piece, rc, tab);
                     if (is_bam) bad += bam_sampled(argv[a], t, S, window, piece, rc, tab);
+                    if (is_sam) bad += sam_sampled(argv[a], t, window, piece, rc, tab);
                     ++runs; proven += rc == 0;
                     if (first == -100) { first = rc; first_count = count; }
                     else if (rc != first || count != first_count) { ++bad; fprintf(stderr, "%s: S %llu window %llu piece %llu: verdict %d, %llu records; first %d, %llu\n", argv[a], (unsigned long long)S, (unsigned long long)window, (unsigned long long)piece, rc, (unsigned long long)count, first, (unsigned long long)first_count); }
