@@ -56,7 +56,7 @@ EXPORTS = [
     "lrge_hip_reads_table", "lrge_hip_reads_timings", "lrge_hip_reads_bam_stats", "lrge_hip_reads_window_stats", "lrge_hip_reads_cram_stats", "lrge_hip_rans_decode", "lrge_hip_seqset_from_reads", "lrge_hip_reads_free",
     "lrge_hip_name_ranks", "lrge_hip_reads_name_ranks",
     "lrge_hip_reads_census", "lrge_hip_reads_census_mem", "lrge_hip_reads_open_selected", "lrge_hip_reads_open_selected_mem", "lrge_hip_reads_select_stats",
-    "lrge_hip_reads_census_map", "lrge_hip_reads_census_map_mem", "lrge_hip_read_map_free", "lrge_hip_read_map_stats", "lrge_hip_read_map_points",
+    "lrge_hip_reads_census_map", "lrge_hip_reads_census_map_mem", "lrge_hip_read_map_free", "lrge_hip_read_map_stats", "lrge_hip_read_map_points", "lrge_hip_read_map_entries",
     "lrge_hip_reads_open_mapped", "lrge_hip_reads_open_mapped_mem", "lrge_hip_reads_seek_stats", "lrge_hip_reads_zstd_stats",
     "lrge_hip_index_build", "lrge_hip_index_build_for", "lrge_hip_index_build_sharded", "lrge_hip_index_build_tsharded", "lrge_hip_last_shard_stats", "lrge_hip_index_free",
     "lrge_hip_comm_alltoallv", "lrge_hip_comm_rccl_ranks", "lrge_hip_comm_rccl_ops", "lrge_hip_comm_local_group_serialize", "lrge_hip_comm_local_turn",
@@ -160,6 +160,7 @@ def lib():
         L.lrge_hip_read_map_free.restype = None
         L.lrge_hip_read_map_stats.argtypes = [vp, C.POINTER(C.c_uint64 * 4)]
         L.lrge_hip_read_map_points.argtypes = [vp, vp, vp, vp, C.c_uint64]
+        L.lrge_hip_read_map_entries.argtypes = [vp, C.POINTER(C.c_uint64 * 4)]
         L.lrge_hip_reads_open_mapped.argtypes = [vp, C.c_char_p, C.c_int, vp, vp, C.c_uint32, C.POINTER(vp)]
         L.lrge_hip_reads_open_mapped_mem.argtypes = [vp, vp, C.c_uint64, C.c_int, vp, vp, C.c_uint32, C.POINTER(vp)]
         L.lrge_hip_reads_seek_stats.argtypes = [vp, C.POINTER(C.c_uint64 * 4)]

@@ -6,10 +6,12 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "fastx_core.h"
 #include "win_twin.h"
+#include "gz_twin.h"
 
 namespace fastx_twin {           // (a name of its own: tools/window_twin_check.cpp holds the three twins in one translation unit)
 namespace {
@@ -167,6 +169,7 @@ struct Scan {
 WinTwinOut gw;
 FxSeekMap gm;                           // the map of the last fastx_twin_census_map
 FxSeekPlan gp;                          // the plan of the last fastx_twin_seek_plan / fastx_twin_mapped
+std::vector<uint8_t> gz_text;           // the text of the last fastx_twin_gz_census_map
 }  // namespace
 
 extern "C" {
@@ -272,6 +275,104 @@ int fastx_twin_mapped(const uint8_t *t, uint64_t n, uint64_t tile, uint64_t wind
     win_twin_mapped_back(gw, gp, gm);
     return 0;
 }
+
+// ---- the seek map of plain and multi-member gzip (fx_seek.h FX_SEEK_GZIP) ----
+// The census with a map on gzip bytes: gz_run over the twin's backend with the recorder the device uses (chunk, round, ratio as
+// gzip_twin_inflate; entries every `spacing` text bytes), the text through the windows with the point rule, the entries attached
+// to the points.  A stream gz_run does not accept is FX_UNPROVEN, as on the device.  The text by fastx_twin_gz_text
+int fastx_twin_gz_census_map(const uint8_t *d, uint64_t n, uint64_t chunk, uint64_t round, uint64_t ratio, uint64_t spacing, uint64_t tile, uint64_t window, uint64_t piece,
+                             uint64_t stride, uint64_t out[4]) {
+    gw = WinTwinOut(); gm = FxSeekMap(); gz_text.clear();
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (tile < 16 || tile % 16 || !piece || !stride || !spacing) return -1;
+    FxSeekMap m;
+    m.stride = stride; m.gz_spacing = spacing; m.kind = FX_SEEK_GZIP; m.file_len = n;
+    GzTwin t;
+    t.keep_wins = true;
+    GzStats st;
+    GzSeekRec<GzTwin> rec = {&m, spacing};
+    if (gz_run(t, d, n, GzCfg{chunk, round, ratio}, [&](const uint8_t *b, uint64_t k) { gz_text.insert(gz_text.end(), b, b + k); return true; }, st, nullptr, &rec))
+        return (int)FX_UNPROVEN;
+    Scan sc = {tile};
+    const int rc = win_twin_run(sc, gz_text.data(), gz_text.size(), window, piece, true, gw, FX_KEEP_NONE, nullptr, 0, &m);
+    if (rc) { m.pts.clear(); m.n_blocks = m.ent.size(); gm = m; return rc; }      // (the entries and the text stay readable: they are the gzip side's alone)
+    out[0] = gw.sel.seen; out[1] = gw.sel.bases_seen; out[2] = gz_text.size(); out[3] = gw.st.windows;
+    m.records = gw.sel.seen; m.bases = gw.sel.bases_seen; m.text_bytes = gz_text.size(); m.windows = gw.st.windows; m.fmt = gw.fmt;
+    fx_seek_attach_gzip(m);
+    gm = m;
+    return 0;
+}
+
+uint64_t fastx_twin_gz_text(uint8_t *dst) { if (dst && !gz_text.empty()) memcpy(dst, gz_text.data(), gz_text.size()); return gz_text.size(); }
+uint32_t fastx_twin_gz_ring(void) { return GZ_RING; }
+// would the device enter the last map (fx_gz_enterable)?  The twin's own passes enter every map: they test the decode
+int fastx_twin_gz_enterable(void) { return fx_gz_enterable(gm) ? 1 : 0; }
+
+// the entries of the last map, six words each: bit, text offset, text length, CRC-32, valid, in_member; returns how many there are
+uint64_t fastx_twin_gz_entries(uint64_t *out, uint64_t cap) {
+    for (uint64_t i = 0; i < gm.ent.size() && i < cap; ++i) {
+        const FxGzEntry &e = gm.ent[i];
+        uint64_t *o = out + 6 * i;
+        o[0] = e.bit; o[1] = e.off; o[2] = e.len; o[3] = e.crc; o[4] = e.valid; o[5] = e.in_member;
+    }
+    return gm.ent.size();
+}
+// the window of entry i; and one byte of it overwritten (a damaged map)
+void fastx_twin_gz_window(uint64_t i, uint8_t *dst) { memcpy(dst, gm.ent_win.data() + i * FX_GZ_WIN, FX_GZ_WIN); }
+void fastx_twin_gz_poke_window(uint64_t i, uint32_t j, uint8_t v) { gm.ent_win[i * FX_GZ_WIN + j] = v; }
+// the points' entry fields (lrge_hip_read_map_points' c_off, and the entry index)
+uint64_t fastx_twin_gz_point_entries(uint64_t *c_off, uint64_t *blk, uint64_t cap) {
+    for (uint64_t i = 0; i < gm.pts.size() && i < cap; ++i) { c_off[i] = gm.pts[i].c_off; blk[i] = gm.pts[i].blk; }
+    return gm.pts.size();
+}
+
+// Entry i decoded alone from its seed out of file d[0, n) -- which may be a damaged copy of the census's -- as the device's
+// wavefront decodes it, the text at byte `skew` of a 4-byte aligned block.  Returns the status word of gz_entry_run (0: out[0, len)
+// is the entry's text), or -1 when a byte outside [skew, skew + len) of the block was written
+int fastx_twin_gz_entry(const uint8_t *d, uint64_t n, uint64_t i, uint32_t skew, uint8_t *out) {
+    if (i >= gm.ent.size()) return -1;
+    const uint64_t len = gm.ent[i].len;
+    std::vector<uint32_t> blk((size_t)((skew + len + 64) / 4 + 1), 0xA5A5A5A5u);
+    uint8_t *b = (uint8_t *)blk.data();
+    const uint32_t rc = gz_twin_entry(gm, i, d, n, i ? gm.ent_win.data() + i * FX_GZ_WIN : nullptr, b, skew);
+    for (uint64_t j = 0; j < blk.size() * 4; ++j) if ((j < skew || j >= skew + len) && b[j] != 0xA5) return -1;
+    if (!rc && len) memcpy(out, b + skew, (size_t)len);
+    return (int)rc;
+}
+
+// The mapped second pass over gzip file d, which must have the length of the last map's (WIN_TWIN_INVALID): the plan, every entry the
+// runs touch decoded once from its seed, the sub-text built from what the runs take of them, and the selecting run over it, as
+// fastx_twin_mapped.  An entry that fails its checks is FX_UNPROVEN: the map does not fit the input
+int fastx_twin_gz_mapped(const uint8_t *d, uint64_t n, uint64_t tile, uint64_t window, uint64_t piece, const uint32_t *sel, uint64_t k) {
+    gw = WinTwinOut(); gp = FxSeekPlan();
+    if (tile < 16 || tile % 16 || !piece) return -1;
+    if (n != gm.file_len || gm.kind != FX_SEEK_GZIP || win_twin_sel_fits(gm, sel, k)) return WIN_TWIN_INVALID;
+    fx_seek_plan(gm, sel, k, &gp);
+    std::vector<uint8_t> sub;
+    std::vector<uint8_t> txt;
+    uint64_t have = ~(uint64_t)0, decoded = 0;           // the entry in txt
+    for (const FxSeekRun &r : gp.runs)
+        for (uint64_t b = r.b0; b < r.b1; ++b) {
+            const FxGzEntry &e = gm.ent[b];
+            if (have != b) {
+                txt.assign((size_t)e.len + 8, 0);
+                std::vector<uint32_t> al((size_t)(e.len / 4 + 4));
+                if (gz_twin_entry(gm, b, d, n, b ? gm.ent_win.data() + b * FX_GZ_WIN : nullptr, (uint8_t *)al.data(), (uint32_t)(sub.size() & 3))) return (int)FX_UNPROVEN;
+                memcpy(txt.data(), (uint8_t *)al.data() + (sub.size() & 3), (size_t)e.len);
+                have = b; ++decoded;
+            }
+            const uint64_t a = std::max(r.t0, e.off), z = std::min(r.t1, e.off + e.len);
+            if (a < z) sub.insert(sub.end(), txt.begin() + (long)(a - e.off), txt.begin() + (long)(z - e.off));
+        }
+    if (decoded != gp.blocks || sub.size() != gp.text_bytes) return (int)FX_UNPROVEN;       // (never: the planner counts what is decoded)
+    Scan sc = {tile, false};
+    int rc = win_twin_run(sc, sub.data(), sub.size(), window, piece, true, gw, FX_KEEP_SEL, gp.sel.data(), k);
+    if (rc == WIN_TWIN_INVALID || (!rc && gw.sel.seen != gp.records)) rc = (int)FX_UNPROVEN;
+    if (rc) { gw = WinTwinOut(); return rc; }
+    win_twin_mapped_back(gw, gp, gm);
+    return 0;
+}
+void fastx_twin_plan_stats(uint64_t out[4]) { out[0] = gp.runs.size(); out[1] = gp.text_bytes; out[2] = gp.file_bytes; out[3] = gp.blocks; }
 
 void fastx_twin_select_stats(uint64_t out[4]) { gw.select_stats(out); }
 // the dense store of the kept bases, bytes [0, fastx_twin_windowed_stats()[1])

@@ -24,9 +24,10 @@
 #include "bgzf_scan.h"
 #include "fx_window.h"
 
-// OTHER: a container that cannot be entered (gzip, bzip2, xz); CRAM: no text at all -- a point is a slice (cram_round.h cram_seek_map:
-// ord the first record that starts in it, off its base offset, c_off the file offset of its BA block, blk the slice), n_blocks the slices
-enum { FX_SEEK_PLAIN = 0, FX_SEEK_BGZF = 1, FX_SEEK_OTHER = 2, FX_SEEK_CRAM = 3 };
+// OTHER: a container that cannot be entered (bzip2, xz); CRAM: no text at all -- a point is a slice (cram_round.h cram_seek_map:
+// ord the first record that starts in it, off its base offset, c_off the file offset of its BA block, blk the slice), n_blocks the slices;
+// GZIP: plain or multi-member gzip, entered at the entries below, n_blocks the entries
+enum { FX_SEEK_PLAIN = 0, FX_SEEK_BGZF = 1, FX_SEEK_OTHER = 2, FX_SEEK_CRAM = 3, FX_SEEK_GZIP = 4 };
 #define FX_SEEK_NONE 0xFFFFFFFFu                                     // a cell's slot without a record start
 
 // the record-start rule: a record starts `lead` bytes in front of its identifier
@@ -39,12 +40,39 @@ FX_HD uint64_t fx_rec_start(uint64_t name_off, uint32_t lead) { return name_off 
 // text offset and member length; plain input: all 0
 struct FxSeekPoint { uint64_t ord, off, c_off, o_off; uint32_t c_len; uint32_t blk; };
 
+// One entry of a gzip file (gzip_round.h GzSeekRec): a true boundary of the stream at absolute bit offset `bit`, where text offset
+// `off` starts; the stream is inside a member there (in_member) of which `valid` bytes of the 32 KiB window in front belong to it; the text
+// from here to the next entry (the last: to the end) has `len` bytes and CRC-32 `crc`.  Entry i's window is ent_win[i * FX_GZ_WIN ..]:
+// the text [off - 32768, off), zeros in front of the text.  The windows are host memory outside INGEST_MAX_BYTES: 32 KiB an
+// entry, 1.6 % of the text at the default spacing and chunk (an entry every 2 MiB of text or so).
+// An entry is decoded from file bytes [bit >> 3, fx_gz_cover_end): FX_GZ_SLACK bytes past the next entry's byte, so that the stop rule
+// (gzip_core.h gz_canon, gz_is_header) sees the boundary it ends at as the census saw it
+#define FX_GZ_WIN 32768u
+#define FX_GZ_SLACK 16u
+struct FxGzEntry { uint64_t bit, off, len; uint32_t crc, valid, in_member, pad; };
+
 struct FxSeekMap {
     uint64_t records = 0, bases = 0, text_bytes = 0, file_len = 0, n_blocks = 0, stride = 65536, windows = 0;
     int kind = FX_SEEK_PLAIN, fmt = FX_FMT_EMPTY;
     std::vector<FxSeekPoint> pts;
     uint64_t last_cell = 0;                      // the cell of the last point (the builder's)
+    std::vector<FxGzEntry> ent;                  // FX_SEEK_GZIP: the entries, ascending in bit and in text offset; entry 0 is bit 0
+    std::vector<uint8_t> ent_win;                // ... and their windows
+    uint64_t gz_spacing = 0;                     // ... and the spacing they were taken at (option INGEST_SEEK_GZIP_BYTES)
+    uint64_t gz_links = 0;                       // ... and the accepted chunks of the census they were taken from
 };
+
+// Is a gzip map worth entering?  Not when the spacing left entry 0 alone although the census walked several chunks: the mapped open
+// could skip nothing and would decode by one wavefront what the selected pass decodes by one a chunk.  Such a map gets the kind
+// "other" (the full selected pass, 0 runs).  A file of one chunk is one entry either way and is entered
+static inline bool fx_gz_enterable(const FxSeekMap &m) { return m.ent.size() > 1 || m.gz_links <= 1; }
+
+// the file bytes of entry i end here
+static inline uint64_t fx_gz_cover_end(const FxSeekMap &m, uint64_t i) {
+    if (i + 1 >= m.ent.size()) return m.file_len;
+    const uint64_t e = (m.ent[i + 1].bit >> 3) + FX_GZ_SLACK;
+    return e < m.file_len ? e : m.file_len;
+}
 
 // the point rule: record `ord` starts at text offset `off`; records arrive in file order.  A window's first cell may be one an
 // earlier window gave a point to: the earlier point stands
@@ -65,8 +93,20 @@ static inline void fx_seek_attach(FxSeekMap &m, const BgzfBlock *t, uint64_t n) 
     }
 }
 
+// ... and from the entry table of a gzip map: the entry that holds the point's offset, c_off its byte, c_len the bytes that cover it
+static inline void fx_seek_attach_gzip(FxSeekMap &m) {
+    const uint64_t n = m.ent.size();
+    m.n_blocks = n;
+    uint64_t b = 0;
+    for (FxSeekPoint &p : m.pts) {
+        while (b < n && m.ent[b].off + m.ent[b].len <= p.off) ++b;
+        if (b == n) return;                      // (never: a point lies inside the text)
+        p.c_off = m.ent[b].bit >> 3; p.o_off = m.ent[b].off; p.c_len = (uint32_t)(fx_gz_cover_end(m, b) - p.c_off); p.blk = (uint32_t)b;
+    }
+}
+
 // one run: records [ord0, ord0 + n_rec), text [t0, t1).  BGZF: blocks [b0, b1), which are file bytes [f0, f1), the first of them
-// starting at text offset o0; plain: f0 = t0, f1 = t1, no blocks
+// starting at text offset o0; gzip: entries [b0, b1), file bytes [f0, f1) with the slack of the last; plain: f0 = t0, f1 = t1, no blocks
 struct FxSeekRun { uint64_t ord0, n_rec, t0, t1, f0, f1, b0, b1, o0; };
 
 struct FxSeekPlan {
@@ -96,7 +136,7 @@ static inline void fx_seek_plan(const FxSeekMap &m, const uint32_t *sel, uint64_
         run.ord0 = a.ord; run.t0 = a.off;
         run.n_rec = (to_end ? m.records : m.pts[behind[r]].ord) - a.ord;
         run.t1 = to_end ? m.text_bytes : m.pts[behind[r]].off;
-        if (m.kind == FX_SEEK_BGZF) {
+        if (m.kind == FX_SEEK_BGZF || m.kind == FX_SEEK_GZIP) {
             run.b0 = a.blk; run.f0 = a.c_off; run.o0 = a.o_off;
             if (to_end) { run.b1 = m.n_blocks; run.f1 = m.file_len; }
             else {
@@ -105,6 +145,7 @@ static inline void fx_seek_plan(const FxSeekMap &m, const uint32_t *sel, uint64_
                 run.b1 = whole ? z.blk : (uint64_t)z.blk + 1;
                 run.f1 = whole ? z.c_off : z.c_off + z.c_len;
             }
+            if (m.kind == FX_SEEK_GZIP) run.f1 = fx_gz_cover_end(m, run.b1 - 1);     // (an entry's bytes reach past the next entry's first)
             const uint64_t b_from = r && prev_b1 > run.b0 ? prev_b1 : run.b0, f_from = r && prev_f1 > run.f0 ? prev_f1 : run.f0;
             p->blocks += run.b1 > b_from ? run.b1 - b_from : 0;
             p->file_bytes += run.f1 > f_from ? run.f1 - f_from : 0;

@@ -13,6 +13,12 @@
 #pragma once
 #include "inflate_core.h"
 
+#ifdef __HIPCC__
+#define INF_FN_M __host__ __device__ inline      // a member of an environment both compilers see
+#else
+#define INF_FN_M inline
+#endif
+
 enum {
     GZ_E_HEADER = 10,       // not a gzip member header (magic, method, reserved flags, FHCRC), or trailing bytes
     GZ_E_CRC = 11,          // a member's CRC32 or ISIZE differs from its trailer (checked by the host)
@@ -226,3 +232,94 @@ INF_FN uint32_t gz_crc_shift_tab(const uint32_t *pw, uint32_t crc, uint32_t n) {
 }
 // CRC-32 register update over n bytes (no init / final xor): crc = ~standard crc while running
 INF_FN uint32_t gz_crc_run(const uint32_t *t, uint32_t c, uint8_t byte) { return t[(c ^ byte) & 0xFF] ^ (c >> 8); }
+
+// ---- the seeded decode of one entry of a seek map (fx_seek.h FX_SEEK_GZIP) ----
+// An entry is a true boundary whose member state and 32 KiB window are known, so gz_decode from it is an ordinary inflate whose
+// history is preloaded: bytes, no markers.  The history is a byte ring of GZ_RING bytes (kernel: LDS) that holds the window in front of
+// the entry's first byte; the text leaves it by halves: whenever a half is complete it is folded into the entry's CRC-32 (64 lane
+// stripes, shifted and XOR-combined) and written to the entry's place in the staging block in aligned 4-byte words.  The ring is
+// indexed by the output address (text position + `skew`, the staging offset's low two bits), so a half's words are aligned in the ring
+// and in memory alike; only the entry's first and last word are written as bytes -- the neighbouring entries own their other bytes.
+#define GZ_RING 65536u
+#define GZ_HALF (GZ_RING / 2)
+#define GZ_E_ENTRY 15u       // a seeded decode that ended elsewhere, or with another length or CRC-32, than the map says
+
+// one seeded decode: file bytes comp[c_off, c_off + n) from bit `start` (0..7) to bit `stop` (GZ_NONE with eof: the end of the file, which
+// is comp[c_off + n]); the text, `len` bytes of CRC-32 `crc`, to stage[out_off, out_off + len); window `win` of the uploaded windows
+// (GZ_NONE: none -- entry 0), of which `valid` bytes belong to the member the entry starts inside (in_member)
+struct GzEntryTask { uint64_t c_off, out_off; uint32_t n, start, stop, len, crc, valid, win, eof; };
+
+// T: the tables (InfDevTabs / TwinTabs).  M: the memory side --
+//   M::ld(p), M::st(p, v)      a ring byte this wavefront stored moments before (kernel: ld_wave / st_wave)
+//   M::word(p, w)              an aligned 4-byte store to the staging block
+//   M::wave_xor(c)             the XOR over the wavefront's lanes (twin: its one lane has walked all 64 stripes)
+template <class T, class M> struct GzSeedEnv : T {
+    static constexpr int full = GZ_E_OVERFLOW;
+    uint8_t *ring;
+    const uint32_t *crc_tab, *pw;   // the CRC-32 table and gz_crc_powers(32)
+    uint8_t *dst;                   // where text byte 0 goes
+    uint32_t skew;                  // the low two bits of that address
+    uint32_t pos, cap, valid, done; // done: text bytes that have left the ring
+    uint32_t crc;                   // ... and their CRC-32
+    bool own;
+    uint32_t mstart;
+    template <class... A> INF_FN_M GzSeedEnv(uint8_t *ring_, const uint32_t *crc_tab_, const uint32_t *pw_, uint8_t *dst_, uint32_t skew_, uint32_t cap_, uint32_t valid_, A &&...a)
+        : T(a...), ring(ring_), crc_tab(crc_tab_), pw(pw_), dst(dst_), skew(skew_), pos(0), cap(cap_), valid(valid_), done(0), crc(0), own(false), mstart(0) {}
+    INF_FN_M uint8_t *at(uint32_t i) const { return ring + ((i + skew) & (GZ_RING - 1)); }      // text byte i (or, below 0, window byte GZ_WIN + i)
+    // the entry's window in front of text byte 0
+    INF_FN_M void preload(const uint8_t *win) { for (uint32_t j = this->lane; j < GZ_WIN; j += this->nl) M::st(at(j - GZ_WIN), win[j]); }
+    // a member that started in the entry: back to its first byte; else the bytes of the window that belong to the member
+    INF_FN_M uint32_t reach() const { return own ? pos - mstart : pos >= GZ_WIN ? GZ_WIN : pos + valid; }
+    // text [done, z) leaves the ring (z - done <= GZ_HALF): its CRC by 64 stripes, its bytes in words
+    INF_FN_M void leave(uint32_t z) {
+        const uint32_t a = done, n = z - a;
+        if (!n) return;
+        const uint32_t s = (n + 63) / 64;
+        uint32_t c = 0;
+        for (uint32_t l = this->lane; l < 64; l += this->nl) {
+            const uint32_t x = l * s < n ? l * s : n, y = x + s < n ? x + s : n;
+            uint32_t r = 0xFFFFFFFFu;
+            for (uint32_t i = x; i < y; ++i) r = gz_crc_run(crc_tab, r, M::ld(at(a + i)));
+            if (y > x) c ^= gz_crc_shift_tab(pw, ~r, n - y);
+        }
+        crc = gz_crc_shift_tab(pw, crc, n) ^ M::wave_xor(c);
+        uint32_t head = (4u - ((a + skew) & 3u)) & 3u;            // bytes up to the first aligned address
+        if (head > n) head = n;
+        for (uint32_t j = this->lane; j < head; j += this->nl) dst[a + j] = M::ld(at(a + j));
+        const uint32_t nw = (n - head) >> 2;
+        for (uint32_t w = this->lane; w < nw; w += this->nl) {
+            const uint32_t i = a + head + 4 * w;
+            M::word(dst + i, (uint32_t)M::ld(at(i)) | (uint32_t)M::ld(at(i + 1)) << 8 | (uint32_t)M::ld(at(i + 2)) << 16 | (uint32_t)M::ld(at(i + 3)) << 24);
+        }
+        for (uint32_t j = head + 4 * nw + this->lane; j < n; j += this->nl) dst[a + j] = M::ld(at(a + j));
+        done = z;
+    }
+    // behind every advance of pos by at most a half: the half that is complete leaves
+    INF_FN_M void drain() { if ((pos + skew) / GZ_HALF != (done + skew) / GZ_HALF) leave(((pos + skew) & ~(GZ_HALF - 1)) - skew); }
+    INF_FN_M void finish() { leave(pos); }
+    INF_FN_M void lit(uint8_t b) { if (this->lane == 0) M::st(at(pos), b); ++pos; drain(); }
+    INF_FN_M void copy(uint32_t dist, uint32_t len) {
+        for (uint32_t c = 0; c < len; c += 64) {                  // len <= 258; j >= dist repeats the first dist bytes (see k_inflate.h)
+            for (uint32_t j = c + this->lane; j < len && j < c + 64; j += this->nl) M::st(at(pos + j), M::ld(at(pos - dist + (j < dist ? j : j % dist))));
+        }
+        pos += len; drain();
+    }
+    INF_FN_M void stored(const uint8_t *src, uint32_t n) {        // up to 65535 bytes: by pieces that end at a half
+        while (n) {
+            const uint32_t room = GZ_HALF - ((pos + skew) & (GZ_HALF - 1)), k = n < room ? n : room;
+            for (uint32_t j = this->lane; j < k; j += this->nl) M::st(at(pos + j), src[j]);
+            pos += k; src += k; n -= k; drain();
+        }
+    }
+    INF_FN_M void seg(uint32_t, const GzSeg &) {}                // (the census checked every member; the entry's CRC covers the bytes)
+};
+
+// the entry's decode with its checks: the status word (INF_OK: stage holds the entry's text)
+template <class E> INF_FN uint32_t gz_entry_run(E &e, const uint8_t *p, const GzEntryTask &t) {
+    GzRes r;
+    gz_decode(e, p, t.n, t.eof != 0, t.start, t.stop, GZ_NONE, r);
+    if (r.status) return r.status;
+    e.finish();
+    const bool ended = t.stop == GZ_NONE ? r.eof != 0 : (r.end_bit == t.stop && !r.eof);
+    return ended && r.n_sym == t.len && e.crc == t.crc ? (uint32_t)INF_OK : GZ_E_ENTRY;
+}

@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "fx_seek.h"
 #include "gzip_core.h"
 
 struct GzStats { uint64_t members, chunks, speculative, rejected, redecoded, overflow_retries, bytes_out; };
@@ -41,6 +42,46 @@ enum { GZ_RUN_OK = 0, GZ_RUN_TOO_MANY = -1, GZ_RUN_DEVICE = -2 };
 static inline uint64_t gz_slot_symbols(const GzCfg &c) { return std::max<uint64_t>(c.ratio * c.chunk, 65536); }
 static inline uint32_t gz_slot_segs(const GzCfg &c) { return (uint32_t)std::min<uint64_t>(c.chunk / 8 + 4, GZ_MAX_SEGS_PER_CHUNK); }
 
+// What a recorder sees of a round, after `finish`: the accepted links, their segments and the segments' CRCs, the byte of the file the
+// round's bit offsets count from, the text offset of the round's first byte and whether the stream is inside a member at the first link
+struct GzRound { uint64_t R0, text_base; const GzLink *links; uint32_t nl; const GzSeg *segs; const uint32_t *seg_crc; bool in_member; };
+
+// The recorder of a census that leaves a seek map (fx_seek.h FX_SEEK_GZIP): it keeps the entry table.  Entry 0 is the
+// first link of the file (bit 0, an empty window); after that an accepted link becomes an entry when its text offset is at least `spacing`
+// behind the previous entry's.  A link's text CRC is the fold of its segments' CRCs, an entry's the fold of its links'.  The windows of
+// the round's new entries come from the backend in one call: bool windows_out(const uint32_t *link, uint32_t k, uint8_t *dst) -- window
+// of link[i] (as `finish` left it) to dst + i * GZ_WIN
+template <class D> struct GzSeekRec {
+    FxSeekMap *m;
+    uint64_t spacing;
+    bool round(D &dev, const GzRound &r) {
+        std::vector<uint32_t> pick;
+        bool in = r.in_member;
+        for (uint32_t k = 0; k < r.nl; ++k) {
+            const GzLink &l = r.links[k];
+            const uint64_t off = r.text_base + l.out_off;
+            ++m->gz_links;
+            if (m->ent.empty() || off >= m->ent.back().off + spacing) {
+                m->ent.push_back(FxGzEntry{r.R0 * 8 + l.start, off, 0, 0, in ? l.valid : 0, in ? 1u : 0u, 0});
+                pick.push_back(k);
+            }
+            FxGzEntry &e = m->ent.back();
+            for (uint32_t s = l.seg0; s < l.seg0 + l.nseg; ++s) {
+                const GzSeg &g = r.segs[s];
+                e.crc = inf_crc_shift(e.crc, g.o1 - g.o0) ^ r.seg_crc[s];
+                e.len += g.o1 - g.o0;
+                if (g.flags & GZ_SEG_HEAD) in = true;
+                if (g.flags & GZ_SEG_TRAIL) in = false;
+            }
+        }
+        if (pick.empty()) return true;
+        const size_t at = m->ent_win.size();
+        m->ent_win.resize(at + pick.size() * (size_t)GZ_WIN);
+        return dev.windows_out(pick.data(), (uint32_t)pick.size(), &m->ent_win[at]);
+    }
+};
+struct GzNoRec { template <class D> bool round(D &, const GzRound &) { return true; } };
+
 // D (the decode backend):
 //   bool load(const uint8_t *d, uint64_t off, uint32_t n)         the round's bytes d[off, off + n)
 //   void prefetch(const uint8_t *d, uint64_t off, uint32_t n)     a hint: the next round will likely lie inside d[off, off + n)
@@ -58,9 +99,10 @@ static inline uint32_t gz_slot_segs(const GzCfg &c) { return (uint32_t)std::min<
 //                                                                  still be in flight:
 //   bool bytes_ready()                                             waits for it
 // sink(bytes, n) -> bool (false: stop with GZ_RUN_DEVICE)
+// rec: a recorder (rec->round(dev, GzRound) after every round's member checks; false: stop with GZ_RUN_DEVICE), or null: nothing more is asked of the backend
 // Returns GZ_RUN_OK, GZ_RUN_TOO_MANY, GZ_RUN_DEVICE, or an INF_E_* / GZ_E_* status (*bad_off: file offset of the chunk).
-template <class D, class Sink>
-static int gz_run(D &dev, const uint8_t *d, uint64_t n, GzCfg cfg, Sink &&sink, GzStats &st, uint64_t *bad_off) {
+template <class D, class Sink, class Rec = GzNoRec>
+static int gz_run(D &dev, const uint8_t *d, uint64_t n, GzCfg cfg, Sink &&sink, GzStats &st, uint64_t *bad_off, Rec *rec = nullptr) {
     memset(&st, 0, sizeof st);
     cfg.chunk = std::min<uint64_t>(std::max<uint64_t>(cfg.chunk, 64), (uint64_t)64 << 20);
     cfg.ratio = std::min<uint64_t>(std::max<uint64_t>(cfg.ratio, 1), 64);
@@ -74,6 +116,7 @@ static int gz_run(D &dev, const uint8_t *d, uint64_t n, GzCfg cfg, Sink &&sink, 
     bool in_member = false;                  // the stream is inside a member there
     uint32_t valid = 0;                      // bytes of the carried window that belong to that member
     uint32_t mcrc = 0; uint64_t msize = 0;   // that member's CRC and size so far
+    uint64_t text_base = 0;                  // text bytes of the rounds before this one
     const uint8_t *pend = nullptr; uint64_t pend_n = 0;      // the previous round's bytes, delivered while this round decodes
     auto flush = [&]() -> bool {
         if (!pend_n) return true;
@@ -201,6 +244,7 @@ static int gz_run(D &dev, const uint8_t *d, uint64_t n, GzCfg cfg, Sink &&sink, 
         if (!dev.finish(links.data(), (uint32_t)links.size(), segs.data(), (uint32_t)segs.size(), out_bytes, seg_crc.data(), &marker_err, &bytes))
             return GZ_RUN_DEVICE;
         if (marker_err) { if (bad_off) *bad_off = R0 + (links[marker_err - 1].start >> 3); return GZ_E_MARKER; }
+        const bool in0 = in_member;
         // member checks: every segment's CRC folded into its member's
         for (uint32_t s = 0; s < segs.size(); ++s) {
             const GzSeg &g = segs[s];
@@ -217,6 +261,8 @@ static int gz_run(D &dev, const uint8_t *d, uint64_t n, GzCfg cfg, Sink &&sink, 
                 in_member = false; ++st.members;
             }
         }
+        if (rec && !rec->round(dev, GzRound{R0, text_base, links.data(), (uint32_t)links.size(), segs.data(), seg_crc.data(), in0})) return GZ_RUN_DEVICE;
+        text_base += out_bytes;
         pend = bytes; pend_n = out_bytes;
         if (done) return !flush() ? (int)GZ_RUN_DEVICE : in_member ? (int)INF_E_INPUT : (int)GZ_RUN_OK;
         const uint64_t next = R0 * 8 + expect;

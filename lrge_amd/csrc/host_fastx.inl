@@ -41,7 +41,7 @@ struct lrge_hip_reads {
     CramStats cram;                             // lrge_hip_reads_cram_stats
     uint64_t zs_slide[4] = {0, 0, 0, 0};        // lrge_hip_reads_zstd_stats: the sliding Zstandard rounds of the call (zeros: it did not slide)
     FxSelStats sel = {0, 0, 0, 0};              // lrge_hip_reads_select_stats: the pass of lrge_hip_reads_open_selected* (a window: what it adds)
-    u64 seek[4] = {0, 0, 0, 0};                 // lrge_hip_reads_seek_stats: runs, text bytes brought, file bytes read, BGZF blocks decoded (lrge_hip_reads_open_mapped*)
+    u64 seek[4] = {0, 0, 0, 0};                 // lrge_hip_reads_seek_stats: runs, text bytes brought, file bytes read, BGZF blocks or gzip entries decoded (lrge_hip_reads_open_mapped*)
 };
 
 // the seek map of a census (fx_seek.h), as the caller holds it
@@ -701,8 +701,8 @@ static int fx_inflate_to_device(FxSink &s, Dev &dev, Run run, const char *codec,
     return LRGE_ERR_UNPROVEN;
 }
 
-// any other gzip input
-static int fx_src_gzip(FxSink &s, const u8 *d, u64 len) {
+// any other gzip input.  map: the census leaves the entry table of a seek map behind (gzip_round.h GzSeekRec)
+static int fx_src_gzip(FxSink &s, const u8 *d, u64 len, FxSeekMap *map = nullptr) {
     lrge_hip_ctx *ctx = s.ctx;
     if (!(s.flags & LRGE_GPU_INFLATE_GZIP)) { ctx->err = "reads_open: gzip input without LRGE_GPU_INFLATE_GZIP"; return LRGE_ERR_UNPROVEN; }
     const GzCfg cfg = gz_cfg(ctx);
@@ -710,8 +710,10 @@ static int fx_src_gzip(FxSink &s, const u8 *d, u64 len) {
     GzDev dev(ctx, cfg);
     // a first size: the last member's ISIZE (the whole text of a single-member file below 4 GiB); later rounds grow the block
     if (len >= 18) dev.keep_hint = std::min<u64>(s.cap, bgzf_u32(d + len - 4));
-    return fx_inflate_to_device(s, dev, [&](u64 *bad) { return gz_run(dev, d, len, cfg, [](const uint8_t *, uint64_t) { return true; }, st, bad); }, "gzip",
-                                "reads_open: gzip data not proven on the device (status %d near file offset %llu)", [](int rc) { return rc; });
+    GzSeekRec<GzDev> rec = {map, map ? map->gz_spacing : 0};
+    return fx_inflate_to_device(s, dev, [&](u64 *bad) {
+        return map ? gz_run(dev, d, len, cfg, [](const uint8_t *, uint64_t) { return true; }, st, bad, &rec) : gz_run(dev, d, len, cfg, [](const uint8_t *, uint64_t) { return true; }, st, bad);
+    }, "gzip", "reads_open: gzip data not proven on the device (status %d near file offset %llu)", [](int rc) { return rc; });
 }
 
 static int fx_src_bzip2(FxSink &s, const u8 *d, u64 len) {
@@ -841,7 +843,8 @@ static int fx_open_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, 
     } else if (box == FX_BOX_GZIP) {
         const bool bgzf = bgzf_scan_blocks(d, len, &t, &total);
         if (map && bgzf) { map->kind = FX_SEEK_BGZF; map->n_blocks = t.size(); }
-        rc = bgzf ? fx_src_bgzf(s, d, t, total) : fx_src_gzip(s, d, len);
+        if (map && !bgzf) { map->kind = FX_SEEK_GZIP; map->gz_spacing = std::max<u64>(1, ctx->opt_u64("INGEST_SEEK_GZIP_BYTES", (u64)1 << 20)); }
+        rc = bgzf ? fx_src_bgzf(s, d, t, total) : fx_src_gzip(s, d, len, map);
     }
     else if (box == FX_BOX_BZIP2 && (flags & LRGE_GPU_INFLATE_BZIP2)) rc = fx_src_bzip2(s, d, len);
     else if (box == FX_BOX_ZSTD && (flags & LRGE_GPU_INFLATE_ZSTD)) rc = fx_src_zstd(s, d, len);
@@ -856,6 +859,10 @@ static int fx_open_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, 
         map->records = guard->sel.seen; map->bases = guard->sel.bases_seen; map->text_bytes = guard->text_bytes; map->windows = guard->win.windows;
         map->fmt = guard->fmt;
         if (map->kind == FX_SEEK_BGZF) fx_seek_attach(*map, t.data(), t.size());
+        // (BAM and SAM inside plain gzip keep the full selected pass: DESIGN section 28 -- the entry table is dropped)
+        // ... and so does a map that is not worth entering (fx_gz_enterable)
+        if (map->kind == FX_SEEK_GZIP && (map->fmt == FX_FMT_BAM || map->fmt == FX_FMT_SAM || !fx_gz_enterable(*map))) { map->kind = FX_SEEK_OTHER; map->ent = {}; map->ent_win = {}; map->gz_spacing = 0; }
+        if (map->kind == FX_SEEK_GZIP) fx_seek_attach_gzip(*map);
     }
     *out = guard.release();
     return LRGE_OK;
@@ -950,6 +957,12 @@ extern "C" int lrge_hip_read_map_points(const lrge_hip_read_map *map, uint64_t *
     return LRGE_OK;
 }
 
+extern "C" int lrge_hip_read_map_entries(const lrge_hip_read_map *map, uint64_t out[4]) {
+    if (!map || !out) return LRGE_ERR_INVALID;
+    out[0] = map->m.ent.size(); out[1] = map->m.ent_win.size(); out[2] = (uint64_t)map->m.kind; out[3] = map->m.gz_spacing;
+    return LRGE_OK;
+}
+
 extern "C" int lrge_hip_reads_seek_stats(const lrge_hip_reads *r, uint64_t out[4]) {
     if (!r || !out) return LRGE_ERR_INVALID;
     memcpy(out, r->seek, sizeof r->seek);
@@ -1009,6 +1022,47 @@ static int fx_src_seek_raw(FxSink &s, const FxInput &in, const FxSeekPlan &plan)
     return LRGE_OK;
 }
 
+// A batch of decoded pieces lies in a staging block: text [o_off, o_off + len) at d_stage + src, the pieces ascending in o_off (BGZF
+// blocks, gzip entries).  What the runs take of them, in order, is the sub-text's next bytes: k_fx_runs copies it to the tail of the
+// sink's block, and the windows take their turn.  ri / rpos: the run that is being brought and its next text byte
+struct FxPiece { u64 o_off, len, src; };
+static int fx_runs_take(FxSink &s, const FxSeekPlan &plan, size_t *ri_, u64 *rpos_, const std::vector<FxPiece> &pc, const u8 *d_stage, u64 bytes) {
+    lrge_hip_ctx *ctx = s.ctx;
+    size_t &ri = *ri_;
+    u64 &rpos = *rpos_;
+    int rc;
+    std::vector<FxRunCopy> copies;
+    u64 sum = 0;
+    for (size_t b = 0; b < pc.size() && ri < plan.runs.size();) {
+        const FxSeekRun &r = plan.runs[ri];
+        const u64 bo = pc[b].o_off, be = bo + pc[b].len;
+        if (rpos >= r.t1) { if (++ri < plan.runs.size()) rpos = plan.runs[ri].t0; continue; }
+        if (rpos >= be) { ++b; continue; }
+        if (rpos < bo) return fx_map_range(ctx);               // (never: the pieces cover the runs)
+        const u64 m = std::min<u64>(r.t1, be) - rpos, src = pc[b].src + (rpos - bo);
+        if (src + m > bytes) return fx_map_range(ctx);         // (never)
+        if (!copies.empty() && copies.back().src + copies.back().len == src) copies.back().len += m;
+        else copies.push_back(FxRunCopy{src, sum, m});
+        sum += m; rpos += m;
+    }
+    if (!sum) return LRGE_OK;
+    if (sum >> 32) return s.run->dev.unproven("a window of 2^32 bytes or more");     // (the driver refuses such a block anyway; the grid below is a tile a wavefront)
+    if ((rc = s.room(sum))) return rc;
+    Scratch tables(ctx);                                       // (the batch's: released before the next)
+    std::vector<u64> first(copies.size() + 1, 0);
+    for (size_t c = 0; c < copies.size(); ++c) first[c + 1] = first[c] + div_up(copies[c].len, (u64)FX_RUN_TILE);
+    ALLOC_OR_FAIL(d_copies, tables, FxRunCopy, copies.size());
+    ALLOC_OR_FAIL(d_first, tables, u64, first.size());
+    HIPCHK(ctx, hipMemcpyAsync(d_copies, copies.data(), copies.size() * sizeof(FxRunCopy), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_first, first.data(), first.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_fx_runs, dim3((u32)first.back()), dim3(64), 0, ctx->stream, d_stage, s.blk.keep + s.blk.keep_len,
+                       (const FxRunCopy *)d_copies, (const u64 *)d_first, (u32)copies.size());
+    KCHK(ctx);
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));            // (the tables are pageable, and the staging is decoded into again)
+    s.blk.keep_len += sum;
+    return s.appended();
+}
+
 // BGZF: only the blocks some run touches are decoded, each once, in batches of about a window into a staging block; k_fx_runs
 // copies the parts of the runs that lie in a batch to the tail of the sink's block.  The file ranges of the plan are read (or, from
 // a buffer, copied) back to back into `comp`, which the chunk pipeline takes as a file of its own -- a chunk's blocks must be
@@ -1057,37 +1111,93 @@ static int fx_src_seek_bgzf(FxSink &s, const FxInput &in, const FxSeekPlan &plan
             bytes += fb[j].isize;
         }
         if ((rc = fx_bgzf_decode(ctx, base, part, d_stage))) return rc;
-        // what the runs take of these blocks, in order: the sub-text's next bytes
-        std::vector<FxRunCopy> copies;
-        u64 sum = 0;
-        for (size_t b = i; b < j && ri < plan.runs.size();) {
-            const FxSeekRun &r = plan.runs[ri];
-            const u64 bo = fb[b].o_off, be = bo + fb[b].isize;
-            if (rpos >= r.t1) { if (++ri < plan.runs.size()) rpos = plan.runs[ri].t0; continue; }
-            if (rpos >= be) { ++b; continue; }
-            if (rpos < bo) return fx_map_range(ctx);               // (never: the blocks cover the runs)
-            const u64 m = std::min<u64>(r.t1, be) - rpos, src = part[b - i].o_off + (rpos - bo);
-            if (src + m > bytes) return fx_map_range(ctx);         // (never)
-            if (!copies.empty() && copies.back().src + copies.back().len == src) copies.back().len += m;
-            else copies.push_back(FxRunCopy{src, sum, m});
-            sum += m; rpos += m;
+        std::vector<FxPiece> pc;
+        for (size_t b = i; b < j; ++b) pc.push_back(FxPiece{fb[b].o_off, fb[b].isize, part[b - i].o_off});
+        if ((rc = fx_runs_take(s, plan, &ri, &rpos, pc, d_stage, bytes))) return rc;
+    }
+    while (ri < plan.runs.size() && rpos >= plan.runs[ri].t1) if (++ri < plan.runs.size()) rpos = plan.runs[ri].t0;
+    if (ri < plan.runs.size()) return fx_map_range(ctx);
+    s.hand_over(s.blk);
+    return LRGE_OK;
+}
+
+// Plain and multi-member gzip: only the entries some run touches are decoded, each once and each from its seed by
+// one wavefront (k_gz_entry), in batches of about a window of text.  The file ranges of the plan go back to back through pinned
+// staging to the device in one copy, the entries' windows in another.  An entry's text length is the map's, so a batch's entries lie
+// back to back in the staging block by a prefix: no slot ratio, no retry.  An entry that does not end where the map says, or whose
+// length or CRC-32 differs, is a map that does not fit the input
+static int fx_src_seek_gzip(FxSink &s, const FxInput &in, const FxSeekMap &m, const FxSeekPlan &plan) {
+    lrge_hip_ctx *ctx = s.ctx;
+    if (!(s.flags & LRGE_GPU_INFLATE_GZIP)) { ctx->err = "reads_open: gzip input without LRGE_GPU_INFLATE_GZIP"; return LRGE_ERR_UNPROVEN; }
+    // the entries of the runs, once each, and where their file bytes lie in the staging (ranges that touch or overlap are one)
+    struct Need { u64 ent, c_at; };
+    std::vector<Need> need;
+    u64 comp_len = 0, range_f0 = 0, range_f1 = 0, range_at = 0, prev_b1 = 0;
+    std::vector<std::pair<u64, u64>> ranges;    // file [first, second)
+    for (const FxSeekRun &r : plan.runs)
+        for (u64 b = need.empty() ? r.b0 : std::max<u64>(r.b0, prev_b1); b < r.b1; prev_b1 = ++b) {
+            if (b >= m.ent.size()) return fx_map_range(ctx);
+            const u64 f0 = m.ent[b].bit >> 3, f1 = fx_gz_cover_end(m, b);
+            if (f1 < f0 || f1 > in.len || f1 - f0 >= ((u64)1 << 29)) return f1 > in.len || f1 < f0 ? fx_map_range(ctx) : s.over_cap();      // (bit offsets of a decode are 32 bits wide)
+            if (ranges.empty() || f0 > range_f1) { range_at = comp_len; range_f0 = f0; range_f1 = f1; ranges.push_back({f0, f1}); comp_len += f1 - f0; }
+            else if (f1 > range_f1) { comp_len += f1 - range_f1; range_f1 = f1; ranges.back().second = f1; }
+            need.push_back(Need{b, range_at + (f0 - range_f0)});
         }
-        if (!sum) continue;
-        if (sum >> 32) return s.run->dev.unproven("a window of 2^32 bytes or more");     // (the driver refuses such a block anyway; the grid below is a tile a wavefront)
-        if ((rc = s.room(sum))) return rc;
-        Scratch tables(ctx);                                       // (the batch's: released before the next)
-        std::vector<u64> first(copies.size() + 1, 0);
-        for (size_t c = 0; c < copies.size(); ++c) first[c + 1] = first[c] + div_up(copies[c].len, (u64)FX_RUN_TILE);
-        ALLOC_OR_FAIL(d_copies, tables, FxRunCopy, copies.size());
-        ALLOC_OR_FAIL(d_first, tables, u64, first.size());
-        HIPCHK(ctx, hipMemcpyAsync(d_copies, copies.data(), copies.size() * sizeof(FxRunCopy), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(d_first, first.data(), first.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_fx_runs, dim3((u32)first.back()), dim3(64), 0, ctx->stream, (const u8 *)d_stage, s.blk.keep + s.blk.keep_len,
-                           (const FxRunCopy *)d_copies, (const u64 *)d_first, (u32)copies.size());
+    if (need.size() != plan.blocks || comp_len != plan.file_bytes) return fx_map_range(ctx);        // (never: the planner counts the same entries and bytes)
+    // batches of about a window of text, as fx_src_seek_bgzf makes them; the staging holds the largest
+    u64 stage_cap = 0;
+    for (size_t i = 0, j; i < need.size(); i = j) {
+        u64 bytes = 0;
+        for (j = i; j < need.size() && (j == i || bytes < s.window); ++j) bytes += m.ent[need[j].ent].len;
+        stage_cap = std::max(stage_cap, bytes);
+    }
+    if (stage_cap > s.cap || stage_cap >> 32) return s.over_cap();     // (one entry's text above the budget: its length is a 32-bit count on the device)
+    FxPinned pin;
+    const u64 win_bytes = (u64)need.size() * GZ_WIN;
+    if (comp_len + win_bytes) HIPCHK(ctx, hipHostMalloc((void **)&pin.p, (size_t)(comp_len + win_bytes), hipHostMallocDefault));
+    {
+        u64 at = 0;
+        for (const auto &r : ranges) { if (!in.read(r.first, r.second - r.first, pin.p + at)) return fx_read_failed(ctx); at += r.second - r.first; }
+        for (size_t i = 0; i < need.size(); ++i) memcpy(pin.p + comp_len + i * (size_t)GZ_WIN, m.ent_win.data() + need[i].ent * (size_t)GZ_WIN, GZ_WIN);
+    }
+    Scratch sc(ctx);
+    ALLOC_OR_FAIL(d_comp, sc, u8, comp_len + win_bytes + 16);
+    ALLOC_OR_FAIL(d_stage, sc, u8, stage_cap + FX_PAD);
+    const u8 *d_wins = d_comp + comp_len;       // (read by bytes: no alignment asked)
+    if (comp_len + win_bytes) HIPCHK(ctx, hipMemcpyAsync(d_comp, pin.p, (size_t)(comp_len + win_bytes), hipMemcpyHostToDevice, ctx->stream));
+    int rc;
+    size_t ri = 0;
+    u64 rpos = plan.runs.empty() ? 0 : plan.runs[0].t0;
+    for (size_t i = 0, j; i < need.size(); i = j) {
+        std::vector<GzEntryTask> task;
+        std::vector<FxPiece> pc;
+        u64 bytes = 0;
+        for (j = i; j < need.size() && (j == i || bytes < s.window); ++j) {
+            const u64 b = need[j].ent;
+            const FxGzEntry &e = m.ent[b];
+            const bool last = b + 1 == m.ent.size();
+            const u64 f0 = e.bit >> 3;
+            task.push_back(GzEntryTask{need[j].c_at, bytes, (u32)(fx_gz_cover_end(m, b) - f0), (u32)(e.bit & 7), last ? GZ_NONE : (u32)(m.ent[b + 1].bit - 8 * f0), (u32)e.len,
+                                       e.crc, e.valid, b ? (u32)j : GZ_NONE, last ? 1u : 0u});
+            pc.push_back(FxPiece{e.off, e.len, bytes});
+            bytes += e.len;
+        }
+        Scratch tables(ctx);
+        std::vector<u32> status(task.size());
+        ALLOC_OR_FAIL(d_task, tables, GzEntryTask, task.size());
+        ALLOC_OR_FAIL(d_status, tables, u32, task.size());
+        HIPCHK(ctx, hipMemcpyAsync(d_task, task.data(), task.size() * sizeof(GzEntryTask), hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(k_gz_entry, dim3((u32)task.size()), dim3(64), 0, ctx->stream, (const u8 *)d_comp, (const GzEntryTask *)d_task, (u32)task.size(), d_wins, d_stage, d_status);
         KCHK(ctx);
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));            // (the tables are pageable, and the staging is decoded into again)
-        s.blk.keep_len += sum;
-        if ((rc = s.appended())) return rc;
+        HIPCHK(ctx, hipMemcpyAsync(status.data(), d_status, task.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        for (size_t k = 0; k < status.size(); ++k)
+            if (status[k]) {
+                char why[96];
+                snprintf(why, sizeof why, "gzip entry %llu: status %u", (unsigned long long)need[i + k].ent, status[k]);
+                return fx_map_misfit(ctx, why);
+            }
+        if ((rc = fx_runs_take(s, plan, &ri, &rpos, pc, d_stage, bytes))) return rc;
     }
     while (ri < plan.runs.size() && rpos >= plan.runs[ri].t1) if (++ri < plan.runs.size()) rpos = plan.runs[ri].t0;
     if (ri < plan.runs.size()) return fx_map_range(ctx);
@@ -1131,7 +1241,11 @@ static int fx_open_mapped(lrge_hip_ctx *ctx, FxInput &in, int flags, const lrge_
     const bool gz = box == FX_BOX_GZIP, packed = gz || box == FX_BOX_BZIP2 || box == FX_BOX_ZSTD || box == FX_BOX_XZ;
     std::vector<BgzfBlock> t;
     u64 total = 0;
-    bool fits = m.file_len == in.len && (m.kind == FX_SEEK_PLAIN ? !packed && m.text_bytes == in.len : m.kind == FX_SEEK_BGZF ? gz : packed);
+    bool fits = m.file_len == in.len && (m.kind == FX_SEEK_PLAIN ? !packed && m.text_bytes == in.len : m.kind == FX_SEEK_BGZF || m.kind == FX_SEEK_GZIP ? gz : packed);
+    if (fits && m.kind == FX_SEEK_GZIP) {       // the entry table is whole: as many entries as the points name, a window each but the first, all of the text
+        fits = !m.ent.empty() && m.ent.size() == m.n_blocks && m.ent_win.size() == m.ent.size() * (size_t)FX_GZ_WIN && m.ent[0].bit == 0 &&
+               m.ent.back().off + m.ent.back().len == m.text_bytes;
+    }
     if (fits && in.d && gz) {                   // the whole buffer is here: its block table says which kind it is
         const bool bgzf = bgzf_scan_blocks(in.d, in.len, &t, &total);
         fits = bgzf == (m.kind == FX_SEEK_BGZF) && (!bgzf || (t.size() == m.n_blocks && total == m.text_bytes));
@@ -1162,7 +1276,7 @@ static int fx_open_mapped(lrge_hip_ctx *ctx, FxInput &in, int flags, const lrge_
     int rc = s.run->dev.select(FX_KEEP_SEL, plan.sel.data(), k);
     if (rc) return rc;
     s.run->attach(&s.blk);
-    rc = m.kind == FX_SEEK_PLAIN ? fx_src_seek_raw(s, in, plan) : fx_src_seek_bgzf(s, in, plan);
+    rc = m.kind == FX_SEEK_PLAIN ? fx_src_seek_raw(s, in, plan) : m.kind == FX_SEEK_GZIP ? fx_src_seek_gzip(s, in, m, plan) : fx_src_seek_bgzf(s, in, plan);
     if (!rc) rc = fx_finish_windowed(s, t0);
     // the sub-text is proven again, and holds exactly the planner's records: else the input is not the one the map was made of
     if (rc == LRGE_ERR_INVALID && s.run->dev.at < s.run->dev.k) return fx_map_misfit(ctx, "fewer records than the plan");

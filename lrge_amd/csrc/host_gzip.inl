@@ -171,6 +171,17 @@ struct GzDev : DevKeep {
         *bytes = to_host ? h_out : keep;
         return true;
     }
+    // the recorder of a seek map (gzip_round.h GzSeekRec) takes the windows of the links it keeps as entries: `windows` still holds the
+    // round's; one gather, one copy down
+    GzBuf pick_idx, pick;
+    bool windows_out(const uint32_t *link, uint32_t k, uint8_t *dst) {
+        pick_idx.ctx = ctx; pick.ctx = ctx;
+        if (!pick_idx.need((size_t)k * 4, &e) || !pick.need((size_t)k * GZ_WIN, &e)) return false;
+        if (!ok(hipMemcpyAsync(pick_idx.p, link, (size_t)k * 4, hipMemcpyHostToDevice, ctx->stream))) return false;
+        hipLaunchKernelGGL(k_gz_win_pick, dim3(k), dim3(256), 0, ctx->stream, windows.as<const u8>(), pick_idx.as<const u32>(), pick.as<u8>());
+        if (!ok(hipGetLastError())) return false;
+        return ok(hipMemcpyAsync(dst, pick.p, (size_t)k * GZ_WIN, hipMemcpyDeviceToHost, ctx->stream)) && sync();
+    }
 };
 }  // namespace
 

@@ -158,3 +158,45 @@ __global__ __launch_bounds__(GZ_RESOLVE_THREADS) void k_gz_resolve(const GzLink 
     if (g < L.nseg && z > ps) atomicXor(seg_crc + L.seg0 + g, gz_crc_shift_tab(pw, ~c, sg[g].o1 - z));
     if (bad) atomicMin(err, T.link + 1);                     // (0xFFFFFFFF: none)
 }
+
+// ---- the seek map ----
+// k_gz_win_pick: the windows of the links a census keeps as entries, gathered out of `windows` into one block that comes down in one copy
+// (a workgroup a window, 16 bytes a lane and step)
+__global__ __launch_bounds__(256) void k_gz_win_pick(const u8 *__restrict__ windows, const u32 *__restrict__ link, u8 *__restrict__ out) {
+    const uint4 *src = reinterpret_cast<const uint4 *>(windows + (u64)link[blockIdx.x] * GZ_WIN);
+    uint4 *dst = reinterpret_cast<uint4 *>(out + (u64)blockIdx.x * GZ_WIN);
+    for (u32 j = threadIdx.x; j < GZ_WIN / 16; j += 256) dst[j] = src[j];
+}
+
+// k_gz_entry: one wavefront an entry, gz_decode from the entry's bit to the next entry's with the window preloaded into a byte ring in
+// LDS (gzip_core.h GzSeedEnv): no markers, no window chain, no resolve.  74 KiB of LDS a workgroup, two on a CU, as k_gz_decode.
+struct alignas(16) GzEntryLds {
+    u8 ring[GZ_RING];
+    InfLdsTabs tabs;
+    u32 crc_tab[256];
+    u32 pw[32];
+};
+
+struct GzSeedDevMem {
+    __device__ static u8 ld(const u8 *p) { return ld_wave(p); }
+    __device__ static void st(u8 *p, u8 v) { st_wave(p, v); }
+    __device__ static void word(u8 *p, u32 w) { *reinterpret_cast<u32 *>(p) = w; }
+    __device__ static u32 wave_xor(u32 c) { for (int m = 32; m; m >>= 1) c ^= (u32)__shfl_xor((int)c, m); return c; }
+};
+typedef GzSeedEnv<InfDevTabs, GzSeedDevMem> GzSeedDevEnv;
+
+__global__ __launch_bounds__(64) void k_gz_entry(const u8 *__restrict__ comp, const GzEntryTask *__restrict__ tasks, u32 nt, const u8 *__restrict__ wins,
+                                                 u8 *__restrict__ stage, u32 *__restrict__ status) {
+    __shared__ GzEntryLds S;
+    const u32 k = blockIdx.x, lane = threadIdx.x;
+    if (k >= nt) return;
+    inf_crc_table(S.crc_tab, lane, 64);
+    if (lane == 0) gz_crc_powers(S.pw, 32);
+    const GzEntryTask T = tasks[k];
+    u8 *dst = stage + T.out_off;
+    GzSeedDevEnv e(S.ring, S.crc_tab, S.pw, dst, (u32)((uintptr_t)dst & 3u), T.len, T.valid, S.tabs, lane);
+    if (T.win != GZ_NONE) e.preload(wins + (u64)T.win * GZ_WIN);
+    __syncthreads();
+    const u32 rc = gz_entry_run(e, comp + T.c_off, T);
+    if (lane == 0) status[k] = rc;
+}

@@ -382,6 +382,14 @@ class ReadMap:
             raise _ffi.LrgeHipError(rc, "read_map_points")
         return list(zip(*(x[:k].tolist() for x in a)))
 
+    def entries(self):
+        """(entries, window bytes held, kind, spacing in force) of a gzip map; (0, 0, kind, 0) of any other"""
+        a = (C.c_uint64 * 4)()
+        rc = self._lib.lrge_hip_read_map_entries(self.h, C.byref(a))
+        if rc:
+            raise _ffi.LrgeHipError(rc, "read_map_entries")
+        return tuple(int(x) for x in a)
+
     def free(self):
         if self.h is not None:
             self._lib.lrge_hip_read_map_free(self.h)

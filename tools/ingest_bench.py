@@ -15,6 +15,8 @@ one thread, then the open of the plain text) run one after the other, so all fiv
 "zstd_windowed" of --out.  With LRGE_HIP_LIB_AB naming a build from before the flag only the resident open is timed, under the
 key "zstd_windowed_parent".
 --sampled K1,K2,.. --seek: on the plain and the BGZF FASTQ file and on the uBAM (kind bam: LRGE_GPU_INGEST_SELECT_ALN), for every K, the census without and with a seek map
+(--kinds fq.gz --sampled K1,K2 --seek [--gzip-chunk-kb N]: the same on the plain gzip FASTQ, entered at the entries of its map; the selected open
+beside it is the route the parent commit took for the mapped open, "blocks_decoded" counts entries, and with --gzip-chunk-kb the result goes under "<K>@chunk<N>k")
 (--kinds sam,sam.gz,cram --sampled K1,K2 --seek: the same on unaligned SAM text, plain and bgzipped, under LRGE_GPU_INGEST_SELECT_SAM, and on an
 unaligned CRAM of --cram-slices slices under LRGE_GPU_INGEST_SELECT_CRAM; the single open beside them is the parent
 commit's route for the same command -- the full windowed SAM open, the full CRAM open.  The kinds sam.gz and cram are written only when named)
@@ -475,9 +477,11 @@ def seek_runs(a, ctx, H, HK, kinds, paths, text_bytes, ks):
     alternating in every repeat; into the key "sampled_seek" / "<K>" of a.out"""
     import numpy as np
     ctx.set_option("INGEST_WINDOW_BYTES", str(a.window_mb << 20))
+    if a.gzip_chunk_kb:                                                # (kind fq.gz, DESIGN section 28: a smaller chunk gives more entries)
+        ctx.set_option("GZIP_CHUNK_BYTES", str(a.gzip_chunk_kb << 10))
     result = json.load(open(a.out)) if os.path.exists(a.out) else {}
     for K in ks:
-        out = {"window_bytes": a.window_mb << 20, "reps": a.reps, "k": K, "files": {}}
+        out = {"window_bytes": a.window_mb << 20, "reps": a.reps, "k": K, "gzip_chunk_bytes": a.gzip_chunk_kb << 10, "files": {}}
         for kind in kinds:
             p = paths[kind]
             with open(p, "rb") as fh:
@@ -510,11 +514,13 @@ def seek_runs(a, ctx, H, HK, kinds, paths, text_bytes, ks):
                 f["%s_range" % key] = (min(x[key] for x in runs), max(x[key] for x in runs))
             out["files"][kind] = f
             print(K, kind, json.dumps({k: v for k, v in f.items() if k != "every_run"}), flush=True)
-        prev = result.setdefault("sampled_seek", {}).get(str(K))
+        key = str(K) + ("@chunk%dk" % a.gzip_chunk_kb if a.gzip_chunk_kb else "")
+        prev = result.setdefault("sampled_seek", {}).get(key)
         if prev and (prev.get("window_bytes"), prev.get("reps")) == (out["window_bytes"], out["reps"]):      # (a second run with other kinds into the same --out adds its files)
             out["files"] = {**prev["files"], **out["files"]}
-        result["sampled_seek"][str(K)] = out
+        result["sampled_seek"][key] = out
     ctx.set_option("INGEST_WINDOW_BYTES", None)
+    ctx.set_option("GZIP_CHUNK_BYTES", None)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     json.dump(result, open(a.out, "w"), indent=1)
 
@@ -531,6 +537,7 @@ def main():
     ap.add_argument("--window-mb", default="64")
     ap.add_argument("--sampled", default="0")
     ap.add_argument("--seek", action="store_true")
+    ap.add_argument("--gzip-chunk-kb", type=int, default=0)
     ap.add_argument("--zstd-windowed", type=int, default=0)
     ap.add_argument("--cram-slices", type=int, default=512)
     ap.add_argument("--cram-slice-kb", type=int, default=256)
@@ -591,7 +598,7 @@ def main():
         HK.full_bytes.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_uint64 * 2)]
         HK.kept_bytes.argtypes = [C.POINTER(C.c_uint64 * 2)]
         a.window_mb = int(a.window_mb.split(",")[0])
-        seek_runs(a, ctx, H, HK, [k for k in kinds if k in ("fq", "bgzf.fq.gz", "bam", "sam", "sam.gz", "cram")], paths, text_bytes, seek_ks)
+        seek_runs(a, ctx, H, HK, [k for k in kinds if k in ("fq", "bgzf.fq.gz", "fq.gz", "bam", "sam", "sam.gz", "cram")], paths, text_bytes, seek_ks)
         ctx.close()
         for p in list(paths.values()) + [src, so] + extra:
             os.remove(p)

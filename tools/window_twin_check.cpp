@@ -10,6 +10,9 @@
 // bytes, fastx_twin_mapped).  Every BAM run is followed by the same passes of its own twin (bam_twin_census, bam_twin_selected,
 // bam_twin_census_map at strides 1, 36, 3000 and above the text, bam_twin_seek_plan, bam_twin_mapped), every SAM run by those of sam_twin.cpp (sam_twin_census, sam_twin_selected,
 // sam_twin_census_map at strides 1, 64, 3000 and above the text, sam_twin_seek_plan, sam_twin_mapped).  Prints the
+// Every *.gz file (plain or multi-member gzip of FASTA / FASTQ) goes through the seek map of gzip: fastx_twin_gz_census_map
+// at chunks 64 and 1024 and spacings 1, 4096 and above the text, every entry decoded alone from its seed at the four staging skews against its
+// slice of the text, the plan, and fastx_twin_gz_mapped against fastx_twin_selected on the text.  Prints the
 // verdict counts; the exit status is 1 when the verdicts of one file disagree.
 // TEST INFRASTRUCTURE, not part of the product library.
 #include <stdio.h>
@@ -246,6 +249,55 @@ static uint64_t sam_sampled(const char *path, const std::vector<uint8_t> &t, uin
     return bad;
 }
 
+// The seek map of a gzip file: returns the disagreements
+static uint64_t gzip_seek(const char *path, const std::vector<uint8_t> &d) {
+    uint64_t bad = 0;
+    const auto fail = [&](const char *what, uint64_t chunk, uint64_t spacing) { ++bad; fprintf(stderr, "%s: gzip seek, chunk %llu spacing %llu: %s\n", path, (unsigned long long)chunk, (unsigned long long)spacing, what); };
+    for (uint64_t chunk : {(uint64_t)64, (uint64_t)1024})
+        for (uint64_t sp = 0; sp < 3; ++sp) {
+            uint64_t cs[4];
+            uint64_t spacing = sp == 0 ? 1 : 4096;
+            int rc = fastx_twin::fastx_twin_gz_census_map(d.data(), d.size(), chunk, (uint64_t)256 << 20, 64, spacing, 64, 3001, 4096, 512, cs);
+            if (sp == 2) { spacing = fastx_twin::fastx_twin_gz_text(nullptr) + 1; rc = fastx_twin::fastx_twin_gz_census_map(d.data(), d.size(), chunk, (uint64_t)256 << 20, 64, spacing, 64, 3001, 4096, 512, cs); }
+            std::vector<uint8_t> text((size_t)fastx_twin::fastx_twin_gz_text(nullptr) + 1);
+            const uint64_t n = fastx_twin::fastx_twin_gz_text(text.data());
+            const uint64_t ne = fastx_twin::fastx_twin_gz_entries(nullptr, 0);
+            std::vector<uint64_t> ent(6 * ne + 6);
+            fastx_twin::fastx_twin_gz_entries(ent.data(), ne);
+            if (!ne || ent[0] || ent[1]) { fail("entry 0 is not the start of the file", chunk, spacing); continue; }
+            for (uint64_t i = 0; i < ne; ++i) {
+                const uint64_t off = ent[6 * i + 1], len = ent[6 * i + 2];
+                if (off + len > n || (i + 1 < ne && ent[6 * i + 7] != off + len) || (i + 1 == ne && off + len != n)) { fail("the entries do not tile the text", chunk, spacing); break; }
+                std::vector<uint8_t> out((size_t)len + 1);
+                for (uint32_t skew = 0; skew < 4; ++skew)
+                    if (fastx_twin::fastx_twin_gz_entry(d.data(), d.size(), i, skew, out.data()) || memcmp(out.data(), text.data() + off, (size_t)len)) { fail("an entry decoded from its seed is not its text", chunk, spacing); break; }
+            }
+            if (rc) continue;                      // (a text that is no FASTA / FASTQ: the entries are the gzip side's alone)
+            std::vector<uint32_t> sel;
+            for (uint64_t i = 0; i < cs[0]; i += 3) sel.push_back((uint32_t)i);
+            if (cs[0] && sel.back() != cs[0] - 1) sel.push_back((uint32_t)(cs[0] - 1));
+            uint64_t ps[4], ms[4];
+            if (fastx_twin::fastx_twin_seek_plan(nullptr, nullptr, 0, 0, sel.data(), sel.size(), ps) || ps[1] > n || ps[2] > d.size() || ps[3] > ne) fail("the plan", chunk, spacing);
+            if (fastx_twin::fastx_twin_gz_mapped(d.data(), d.size(), 64, 3001, 4096, sel.data(), sel.size())) { fail("the mapped pass is not proven", chunk, spacing); continue; }
+            fastx_twin::fastx_twin_plan_stats(ms);
+            if (memcmp(ps, ms, sizeof ps)) fail("the mapped pass brought something else than the plan", chunk, spacing);
+            const uint64_t k = fastx_twin::fastx_twin_windowed_count();
+            std::vector<FxRec> tab(k);
+            fastx_twin::fastx_twin_windowed_table(tab.data());
+            std::vector<std::vector<uint8_t>> seqs(k);
+            for (uint64_t j = 0; j < k; ++j) { seqs[j].resize(tab[j].seq_len + 1); fastx_twin::fastx_twin_windowed_seq(j, seqs[j].data()); }
+            if (fastx_twin::fastx_twin_selected(text.data(), n, 64, 3001, 4096, sel.data(), sel.size()) || fastx_twin::fastx_twin_windowed_count() != k) { fail("the selected pass differs", chunk, spacing); continue; }
+            std::vector<FxRec> want(k);
+            fastx_twin::fastx_twin_windowed_table(want.data());
+            for (uint64_t j = 0; j < k; ++j) {
+                std::vector<uint8_t> out(want[j].seq_len + 1);
+                fastx_twin::fastx_twin_windowed_seq(j, out.data());
+                if (want[j].name_off != tab[j].name_off || want[j].seq_len != tab[j].seq_len || memcmp(out.data(), seqs[j].data(), want[j].seq_len)) { fail("a record of the mapped pass differs", chunk, spacing); break; }
+            }
+        }
+    return bad;
+}
+
 int main(int argc, char **argv) {
     const uint64_t windows[] = {64, 257, 3001, 20000}, segs[] = {64, 257, 4096}, tiles[] = {64, 4096};
     uint64_t runs = 0, proven = 0, bad = 0;
@@ -254,6 +306,7 @@ int main(int argc, char **argv) {
         const auto ends = [&](const char *x) { return path.size() > 4 && path.compare(path.size() - 4, 4, x) == 0; };
         const bool is_bam = ends(".bam"), is_sam = ends(".sam");
         const std::vector<uint8_t> t = slurp(argv[a]);
+        if (path.size() > 3 && path.compare(path.size() - 3, 3, ".gz") == 0) { bad += gzip_seek(argv[a], t); ++runs; continue; }
         const uint64_t n = t.size();
         int first = -100;
         uint64_t first_count = 0;
