@@ -132,6 +132,21 @@ def build_cram_twin(force=False):
     return _build_twin(CRAM_TWIN_PATH, "cram_twin.cpp", force, libs=("-lz", "-ldl"))
 
 
+PRIMS_CHECK_PATH = os.path.join(LIB_DIR, "libprims_check.so")
+
+
+def build_prims_check(force=False):
+    """The test harness over csrc/k_prims.h (tools/prims_check.hip, hipcc for gfx950): one exported call per primitive, for
+    tests/test_gpu_prims.py.  Stale when the header, internal.h or the harness is newer."""
+    os.makedirs(LIB_DIR, exist_ok=True)
+    src = os.path.join(os.path.dirname(_HERE), "tools", "prims_check.hip")
+    deps = [src, os.path.join(CSRC, "k_prims.h"), os.path.join(CSRC, "internal.h"), os.path.join(os.path.dirname(_HERE), "include", "lrge_hip.h")]
+    if not force and os.path.exists(PRIMS_CHECK_PATH) and os.path.getmtime(PRIMS_CHECK_PATH) >= _newest(deps):
+        return PRIMS_CHECK_PATH
+    subprocess.check_call(["hipcc"] + HIPCC_FLAGS + ["-o", PRIMS_CHECK_PATH, src])
+    return PRIMS_CHECK_PATH
+
+
 CLI_PATH = os.path.join(LIB_DIR, "lrge-hip")
 
 

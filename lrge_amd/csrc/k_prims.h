@@ -997,6 +997,9 @@ static int compact_heads(lrge_hip_ctx *ctx, Scratch &sc, const u64 *keys, u64 n,
 // instead of once per pass plus a histogram read per pass.  Same stable LSD passes, same ranking (ballot digit
 // matching + per-wave counters) as k_rs_scatter, so the resulting order is identical to the tiled global sort.
 // Segments above the variant's capacity stay on the global segmented sort.
+// (nbits == 0 is the one place where the two forms differ by construction: the single pass here ranks by bit 0, the global one's digit
+// mask is empty and it ranks by nothing.  The one caller passes nbits = KeyLayout::sh_q() = bits_rpos + 1 + bits_rid >= 3
+// (host_overlap_seeds.inl), never 0, and tests/test_gpu_prims.py leaves that width out.)
 // ------------------------------------------------------------------------------------------
 struct SegDesc { u32 start, len, seg, src; };     // src: offset of the segment in the INPUT array (the output goes to start)
 // DB = digit bits of a pass.  9-bit digits (the 512- and 1024-thread variants: one digit per thread in the scan step) sort the

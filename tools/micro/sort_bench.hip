@@ -1,7 +1,10 @@
 // sort_bench.hip -- the index sort of csrc/k_prims.h alone, in its three forms: the LSD passes (radix_sort_keys), the hybrid form
 // (index_sort_hybrid: two most-significant-digit passes, the rest inside LDS) and the hybrid form with tiny LDS classes (every
 // sub-bucket takes the segmented global passes).  Exact against std::stable_sort on the small inputs, order + permutation
-// checks and timing at index scale.  Development harness, not part of the product or the tests.
+// checks and timing at index scale.  Development harness, not part of the product or the tests: a record of the measurements in
+// sort_forms.h (the k_seg_sort_keys it launches is that file's retired keys-only sibling of k_seg_sort_local, not a product kernel).  It
+// still compiles against the current header.  What the product launches is held to host models by tests/test_gpu_prims.py through
+// tools/prims_check.hip, which shares this file's bare-context setup and none of the retired forms.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -o tools/micro/_bin/sort_bench tools/micro/sort_bench.hip && tools/micro/_bin/sort_bench [n]
 #include "sort_forms.h"      // (includes ../../lrge_amd/csrc/k_prims.h and the retired forms it was split from in round 4)
 
