@@ -147,6 +147,22 @@ def build_prims_check(force=False):
     return PRIMS_CHECK_PATH
 
 
+SEED_CHECK_PATH = os.path.join(LIB_DIR, "libseed_check.so")
+
+
+def build_seed_check(force=False):
+    """The test harness over csrc/k_index.h and csrc/k_seed.h (tools/seed_check.hip, hipcc for gfx950): the table build, the lookup,
+    the seed counts and both expansions, one exported call each, for tests/test_gpu_seed.py.  Stale when one of the headers it
+    includes or the harness is newer."""
+    os.makedirs(LIB_DIR, exist_ok=True)
+    src = os.path.join(os.path.dirname(_HERE), "tools", "seed_check.hip")
+    deps = [src] + [os.path.join(CSRC, h) for h in ("k_seed.h", "k_index.h", "k_prims.h", "internal.h")] + [os.path.join(os.path.dirname(_HERE), "include", "lrge_hip.h")]
+    if not force and os.path.exists(SEED_CHECK_PATH) and os.path.getmtime(SEED_CHECK_PATH) >= _newest(deps):
+        return SEED_CHECK_PATH
+    subprocess.check_call(["hipcc"] + HIPCC_FLAGS + ["-o", SEED_CHECK_PATH, src])
+    return SEED_CHECK_PATH
+
+
 CLI_PATH = os.path.join(LIB_DIR, "lrge-hip")
 
 

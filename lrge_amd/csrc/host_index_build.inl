@@ -410,19 +410,10 @@ static int index_build_one(lrge_hip_ctx *ctx, const lrge_hip_seqset *targets, in
                 const u32 n_tiles = (u32)div_up(n_runs, PLACE_TILE);
                 u32 *bmax = sc.get<u32>((size_t)n_tiles + 1);
                 if (!bmax) return LRGE_ERR_DEVICE;
-                hipLaunchKernelGGL(k_place_reduce, dim3(n_tiles), dim3(PLACE_THREADS), 0, ctx->stream, skey, d_runstart, n_runs, cap, bmax, kshift_t, ht_fix, SegStarts{d_seg_start, seg_e, 2 * (u32)P.k});
-                KCHK(ctx);
-                hipLaunchKernelGGL(k_place_scan, dim3(1), dim3(1024), 0, ctx->stream, bmax, n_tiles);
-                KCHK(ctx);
-                hipLaunchKernelGGL(k_place_apply, dim3(std::min<u32>(n_tiles, (u32)ctx->n_cu * 8)), dim3(PLACE_THREADS), 0, ctx->stream,
-                                   skey, d_runstart, n_runs, M, cap, n_slots, bmax, ht, d_occ, max_bin, d_occ + max_bin + 1, kshift_t, ht_fix,
-                                   fused_fill ? bmax + n_tiles : (u32 *)nullptr, pk_t ? (const u64 *)nullptr : (const u64 *)spos, pk_t ? pk_pos1 : 0u,
-                                   ctx->opt("NO_INLINE_SINGLETONS") ? 0u : 1u, SegStarts{d_seg_start, seg_e, 2 * (u32)P.k});
-                KCHK(ctx);
-                if (fused_fill) {
-                    hipLaunchKernelGGL(k_fill_tail, dim3((u32)std::min<u64>(div_up(n_slots - cap / 2, 256), (u64)ctx->n_cu * 8)), dim3(256), 0, ctx->stream, ht, n_slots, bmax + n_tiles);
-                    KCHK(ctx);
-                }
+                rc = place_table_launch(ctx, skey, d_runstart, n_runs, M, cap, n_slots, kshift_t, ht_fix, fused_fill,
+                                        pk_t ? (const u64 *)nullptr : (const u64 *)spos, pk_t ? pk_pos1 : 0u, ctx->opt("NO_INLINE_SINGLETONS") ? 0u : 1u,
+                                        SegStarts{d_seg_start, seg_e, 2 * (u32)P.k}, bmax, ht, d_occ, max_bin, (u32)ctx->n_cu * 8);
+                if (rc) return rc;
                 sc.drop(bmax);
             }
             // the k-th smallest occurrence count almost always sits in the first few bins: fetch 16 KB of

@@ -228,19 +228,10 @@ int OverlapRun::batch(u32 q0, u32 q1, u64 A) {
             u32 *d_kept = bsc.get<u32>((size_t)nqb + 1), *d_qlist = bsc.get<u32>((size_t)nqb + 1);
             if (!akey || !d_kept || !d_qlist) return LRGE_ERR_DEVICE;
             // the queries by the size of their slot: one launch per class (k_seed.h), largest first so that the long workgroups start early
-            h_qlist.resize(nqb);
-            u32 n_cls[3] = {0, 0, 0};
             const u32 smax = (u32)ctx->opt_u64("DEBUG_EXPQ_SMALL_MAX", EXPQ_SMALL_MAX), mmax = (u32)ctx->opt_u64("DEBUG_EXPQ_MID_MAX", EXPQ_MID_MAX);   // (tests: every class on small sets)
-            auto cls_of = [&](u32 c) { return c <= smax ? 0 : c <= mmax ? 1 : 2; };
-            for (u32 q = q0; q < q1; ++q) ++n_cls[cls_of(h_qtot[q])];
-            u32 at[3] = {n_cls[2] + n_cls[1], n_cls[2], 0};
-            for (u32 q = q0; q < q1; ++q) h_qlist[at[cls_of(h_qtot[q])]++] = q - q0;
-            HIPCHK(ctx, hipMemcpyAsync(d_qlist, h_qlist.data(), (size_t)nqb * 4, hipMemcpyHostToDevice, ctx->stream));
-            const u32 npl = std::min<u32>(min_n, EXPQ_PLANES);
-            if (n_cls[2]) hipLaunchKernelGGL((k_expand_q<1024, 17>), dim3(n_cls[2]), dim3(1024), 0, ctx->stream, so.x, so.y, mb, sp, hs, hn, aoff, so.mz_off, q0, d_qlist, kl, akey, bits_qy, npl, d_kept);
-            if (n_cls[1]) hipLaunchKernelGGL((k_expand_q<512, 16>), dim3(n_cls[1]), dim3(512), 0, ctx->stream, so.x, so.y, mb, sp, hs, hn, aoff, so.mz_off, q0, d_qlist + n_cls[2], kl, akey, bits_qy, npl, d_kept);
-            if (n_cls[0]) hipLaunchKernelGGL((k_expand_q<256, 14>), dim3(n_cls[0]), dim3(256), 0, ctx->stream, so.x, so.y, mb, sp, hs, hn, aoff, so.mz_off, q0, d_qlist + n_cls[2] + n_cls[1], kl, akey, bits_qy, npl, d_kept);
-            KCHK(ctx);
+            rc = expand_q_launch(ctx, h_qtot.data() + q0, nqb, smax, mmax, std::min<u32>(min_n, EXPQ_PLANES), h_qlist, d_qlist,
+                                 so.x, so.y, mb, sp, hs, hn, aoff, so.mz_off, q0, kl, akey, bits_qy, d_kept);
+            if (rc) return rc;
             t.stop();
             h_qkept.resize((size_t)(q1 - q0));
             HIPCHK(ctx, ctx->d2h(h_qkept.data(), d_kept, (size_t)(q1 - q0) * 4, ctx->stream));

@@ -278,6 +278,29 @@ __global__ __launch_bounds__(256) void k_fill_tail(u64 *__restrict__ ht, u64 n_s
         *(ulonglong2 *)(ht + 2 * q) = empty;
 }
 
+// The launches of one table build, on ctx->stream: reduce, scan, apply and -- fused_fill: the table has not been cleared -- the
+// tail.  bmax: n_tiles + 1 words of scratch (the tile maxima, then the last slot); d_occ: max_bin + 5 zeroed words (the histogram,
+// [max_bin + 1] the overflow flag, then 8-byte aligned the sum of displacements); grid_cap: most blocks k_place_apply and
+// k_fill_tail get (n_cu * 8).  The index build and tools/seed_check.hip both come through here.
+static inline int place_table_launch(lrge_hip_ctx *ctx, const u64 *skey, const u32 *run_start, u32 n_runs, u64 M, u64 cap, u64 n_slots,
+                                     u32 kshift, u32 fix, bool fused_fill, const u64 *ypos, u32 pk_pos1, u32 inline_single, SegStarts seg,
+                                     u32 *bmax, u64 *ht, u32 *d_occ, u32 max_bin, u32 grid_cap) {
+    const u32 n_tiles = (u32)div_up(n_runs, PLACE_TILE);
+    hipLaunchKernelGGL(k_place_reduce, dim3(n_tiles), dim3(PLACE_THREADS), 0, ctx->stream, skey, run_start, n_runs, cap, bmax, kshift, fix, seg);
+    KCHK(ctx);
+    hipLaunchKernelGGL(k_place_scan, dim3(1), dim3(1024), 0, ctx->stream, bmax, n_tiles);
+    KCHK(ctx);
+    hipLaunchKernelGGL(k_place_apply, dim3(std::min<u32>(n_tiles, grid_cap)), dim3(PLACE_THREADS), 0, ctx->stream,
+                       skey, run_start, n_runs, M, cap, n_slots, bmax, ht, d_occ, max_bin, d_occ + max_bin + 1, kshift, fix,
+                       fused_fill ? bmax + n_tiles : (u32 *)nullptr, ypos, pk_pos1, inline_single, seg);
+    KCHK(ctx);
+    if (fused_fill) {
+        hipLaunchKernelGGL(k_fill_tail, dim3((u32)std::min<u64>(div_up(n_slots - cap / 2, 256), (u64)grid_cap)), dim3(256), 0, ctx->stream, ht, n_slots, bmax + n_tiles);
+        KCHK(ctx);
+    }
+    return LRGE_OK;
+}
+
 // The table is ORDERED: keys were placed in ascending byte-reversed order, each at its home slot or right behind its
 // predecessor, so a probe can stop at the first entry that is not smaller in that order -- an absent key (most query
 // minimizers of noisy reads) costs no more than a present one instead of a walk to the next empty slot.  An empty slot

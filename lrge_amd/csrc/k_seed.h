@@ -328,6 +328,26 @@ __global__ __launch_bounds__(THREADS) void k_expand_q(const u64 *__restrict__ qx
     if (threadIdx.x == 0) kept[ql] = base;
 }
 
+// The launches of k_expand_q for the queries [q0, q0 + nqb), on ctx->stream: the queries by the size of their slot (qtot[0 .. nqb):
+// the anchor totals of q0 ..), one launch per class, largest first so that the long workgroups start early.  h_qlist must live until
+// the copy has run (the caller synchronises); d_qlist: nqb words.  OverlapRun::batch and tools/seed_check.hip both come through here.
+static inline int expand_q_launch(lrge_hip_ctx *ctx, const u32 *qtot, u32 nqb, u32 smax, u32 mmax, u32 n_planes, std::vector<u32> &h_qlist, u32 *d_qlist,
+                                  const u64 *qx, const u64 *qy, u64 mz_begin, const SeedParams &sp, const u64 *hs, const u32 *hn, const u32 *aoff,
+                                  const u32 *qmz_off, u32 q0, KeyLayout kl, u64 *akey, u32 bits_qy, u32 *d_kept) {
+    h_qlist.resize(nqb);
+    u32 n_cls[3] = {0, 0, 0};
+    auto cls_of = [&](u32 c) { return c <= smax ? 0 : c <= mmax ? 1 : 2; };
+    for (u32 q = 0; q < nqb; ++q) ++n_cls[cls_of(qtot[q])];
+    u32 at[3] = {n_cls[2] + n_cls[1], n_cls[2], 0};
+    for (u32 q = 0; q < nqb; ++q) h_qlist[at[cls_of(qtot[q])]++] = q;
+    HIPCHK(ctx, hipMemcpyAsync(d_qlist, h_qlist.data(), (size_t)nqb * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (n_cls[2]) hipLaunchKernelGGL((k_expand_q<1024, 17>), dim3(n_cls[2]), dim3(1024), 0, ctx->stream, qx, qy, mz_begin, sp, hs, hn, aoff, qmz_off, q0, d_qlist, kl, akey, bits_qy, n_planes, d_kept);
+    if (n_cls[1]) hipLaunchKernelGGL((k_expand_q<512, 16>), dim3(n_cls[1]), dim3(512), 0, ctx->stream, qx, qy, mz_begin, sp, hs, hn, aoff, qmz_off, q0, d_qlist + n_cls[2], kl, akey, bits_qy, n_planes, d_kept);
+    if (n_cls[0]) hipLaunchKernelGGL((k_expand_q<256, 14>), dim3(n_cls[0]), dim3(256), 0, ctx->stream, qx, qy, mz_begin, sp, hs, hn, aoff, qmz_off, q0, d_qlist + n_cls[2] + n_cls[1], kl, akey, bits_qy, n_planes, d_kept);
+    KCHK(ctx);
+    return LRGE_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // K4a: query occurrence filter (mm2:seed.c mm_seed_mz_flt), run on the minimizers that are present in
 // the index.  (x, query|index) pairs are sorted by x and then stably by query; a run of identical
