@@ -1,5 +1,5 @@
 // host_index_build.inl -- part of lrge_hip.hip (one translation unit; included there, in this order): index_build_one: sketch -> (restriction + global statistics) -> radix sort -> run heads -> ordered table -> mid_occ, for one index (a whole set, one part of a partitioned index, one rank's restricted index).
-// How many more hash bits than the low byte the SEGMENT of a segment-packed entry implies (index_sort_segpacked): `over`, what the word
+// How many more hash bits than the low byte the SEGMENT of a segment-packed entry implies (index_sort_seg): `over`, what the word
 // is too narrow by (full-size C5 in 3 parts has read ids of 20 bits: 2 too many); beyond that, e is chosen so that what is LEFT of the
 // hash, nr = 2k - 8 - e bits, takes as few 8-bit LSD passes as possible (round 5: k = 19 -> e = 6, nr = 24: passes A + A2 + 3 instead of
 // A + A2 + 4; k = 15 -> e = 0, 22 bits in 3 passes either way).  DEBUG_SEG_EXTRA forces an e on small sets; SEG_PACK_EXTRA_MAX caps it
@@ -119,8 +119,8 @@ static int index_build_one(lrge_hip_ctx *ctx, const lrge_hip_seqset *targets, in
         // (k_prims.h: radix_sort_keys_first_pass_from_slots; option NO_SLOT_SORT: compact first, rounds 1-3)
         const bool keep_slots = pk && !ro && !ctx->opt("NO_SLOT_SORT");
         // SEGW entries (round 5): a build that will take the segment-packed sort below -- pairs too wide for one word, a plain build, a set
-        // large enough -- has its sketch write [word, 16-bit digit pair] instead of (hash, y): 12 bytes per entry instead of 16 through
-        // the slots, the compaction and the sort's first two passes (k_sketch.h PK == 2; k_prims.h index_sort_segw).  Decided before
+        // large enough -- has its sketch write [word, digit pair (a u32)] instead of (hash, y): 12 bytes per entry instead of 16 through
+        // the slots, the compaction and the sort's first two passes (k_sketch.h PK == 2; k_prims.h index_sort_seg).  Decided before
         // the count is known: from the bases, at the density the part planner assumes.  option NO_SEGW: pairs, as rounds 3-4.
         {
             const u32 yb_p = pk_rid + pk_pos1;
@@ -300,7 +300,7 @@ static int index_build_one(lrge_hip_ctx *ctx, const lrge_hip_seqset *targets, in
             // (v1, the second buffer of the pair layout, is taken by the branches that sort pairs only: on the SEGW path -- the default
             // at H. sapiens scale -- it would be 27 GB of transient peak beside the 24 B per entry that path needs)
             u64 *v1 = nullptr;
-            // the pair layout, segment-packed (k_prims.h: index_sort_segpacked): behind the first digit the low hash byte is implied
+            // the pair layout, segment-packed (k_prims.h: index_sort_seg): behind the first digit the low hash byte is implied
             // and the rest of the entry fits one word -- fewer bytes through the remaining passes, 8 bytes per entry resident
             const u32 yb_p = pk_rid + pk_pos1;
             // `over` more hash bits must be implied by the segment for the word to fit (full-size C5 in 3 parts has read ids of 20 bits:
@@ -313,30 +313,23 @@ static int index_build_one(lrge_hip_ctx *ctx, const lrge_hip_seqset *targets, in
             if (so.segw && M == 0) {
                 // (nothing to sort: an empty pair stream is an empty SEGW stream; the wave-dense sketch left no dense arrays at all)
                 if (so.wave_x) { sc.drop(so.wave_x); sc.drop(so.wave_d); sc.drop(so.wave_cnt); sc.drop(so.wave_offs); skey = spos = k1; }
-            } else if (so.segw) {
-                // (the sketch already wrote what pass A wants: decided above, whatever M turned out to be)
-                const bool wave = so.wave_x != nullptr;          // (the wave-dense sketch: 16-bit DIG members, pass A reads the wavefronts' slots)
-                u32 *d1 = wave ? (u32 *)sc.get<wdig_t>(M + 2) : sc.get<u32>(M + 1);
-                if (!d1) return LRGE_ERR_DEVICE;
-                u64 *rk = nullptr, *spare_ = nullptr;
-                WaveSrc ws{so.wave_x, so.wave_d, so.wave_cnt, so.wave_offs, so.n_waves, so.wave_cap};
-                rc = index_sort_segw(ctx, sc, so.x, (u32 *)so.y, k1, d1, M, 2 * P.k, yb_p, pk_pos1, extra, &rk, &d_seg_start, wave ? &ws : nullptr, &spare_);
-                if (rc) return rc;
-                h_seg_start.assign((256u << extra) + 1, 0u);
-                HIPCHK(ctx, ctx->d2h(h_seg_start.data(), d_seg_start, h_seg_start.size() * 4, ctx->stream));
-                seg_packed = true; kshift_t = yb_p; seg_e = extra;
-                skey = rk; spos = rk;
-                sc.drop(spare_); if (so.y) sc.drop((u32 *)so.y); sc.drop(d1);
-            } else if (pass_from == 0 && extra_ok && 2 * P.k > 16 && !ctx->opt("NO_SEG_PACK") && M >= ctx->opt_u64("SEG_PACK_MIN", 1ULL << 22)) {
-                v1 = sc.get<u64>(M + 1); if (!v1) return LRGE_ERR_DEVICE;
+            } else if (so.segw || (pass_from == 0 && extra_ok && 2 * P.k > 16 && !ctx->opt("NO_SEG_PACK") && M >= ctx->opt_u64("SEG_PACK_MIN", 1ULL << 22))) {
+                // (SEGW: the sketch already wrote what pass A wants: decided above, whatever M turned out to be)
+                const bool wave = so.wave_x != nullptr;          // (the wave-dense sketch: pass A reads the wavefronts' slots)
+                u64 *m1 = so.segw ? (u64 *)sc.get<u32>(M + (wave ? 2 : 1)) : sc.get<u64>(M + 1);      // the second member's buffer
+                if (!m1) return LRGE_ERR_DEVICE;
+                const WaveSrc ws{so.wave_x, so.wave_d, so.wave_cnt, so.wave_offs, so.n_waves, so.wave_cap};
+                IndexSortIn in;
+                if (wave) in.ws = &ws;
+                else if (so.segw) { in.x = so.x; in.dig = (u32 *)so.y; }
+                else { in.x = so.x; in.y = so.y; }
                 u64 *rk = nullptr;
-                rc = index_sort_segpacked(ctx, sc, so.x, so.y, k1, v1, M, 2 * P.k, yb_p, pk_pos1, extra, &rk, &d_seg_start);
+                rc = index_sort_seg(ctx, sc, in, k1, m1, M, 2 * P.k, yb_p, pk_pos1, extra, &rk, &d_seg_start);      // (releases every buffer but rk's)
                 if (rc) return rc;
                 h_seg_start.assign((256u << extra) + 1, 0u);              // (the dump wants them: they arrive with the table build's first round trip)
                 HIPCHK(ctx, ctx->d2h(h_seg_start.data(), d_seg_start, h_seg_start.size() * 4, ctx->stream));
                 seg_packed = true; kshift_t = yb_p; seg_e = extra;
                 skey = rk; spos = rk;
-                sc.drop(rk == so.x ? so.y : so.x); sc.drop(k1); sc.drop(v1);
             } else {
             v1 = sc.get<u64>(M + 1); if (!v1) return LRGE_ERR_DEVICE;
             u64 *rk, *rv;

@@ -11,8 +11,8 @@ struct SketchOut {
     u64 *slots = nullptr; u32 *offs = nullptr; u32 n_chunks = 0;
     bool segw = false;                // y holds a u32 ARRAY: SEGW entries (k_sketch.h, sketch_write_chunk PK == 2): x = word, y[i] = the two sort digits
     // wave-dense form (k_sketch.h: k_sketch_wave; SEGW entries only): x / y stay null -- wavefront v's entries sit, densely and in emission order,
-    // at wave_x / wave_d [v * wave_cap ...), wave_cnt[v] of them; the index sort's first pass reads them there (k_prims.h: index_sort_segw, WaveSrc)
-    u64 *wave_x = nullptr; wdig_t *wave_d = nullptr; u32 *wave_cnt = nullptr, *wave_offs = nullptr; u32 n_waves = 0, wave_cap = 0;      // wave_offs: exclusive scan of wave_cnt
+    // at wave_x / wave_d [v * wave_cap ...), wave_cnt[v] of them; the index sort's first pass reads them there (k_prims.h: index_sort_seg, WaveSrc)
+    u64 *wave_x = nullptr; u32 *wave_d = nullptr; u32 *wave_cnt = nullptr, *wave_offs = nullptr; u32 n_waves = 0, wave_cap = 0;      // wave_offs: exclusive scan of wave_cnt
 };
 
 // What the sketch is asked for.  An entry is one of four things (k_sketch.h): the (hash << 8 | span, y) pair of a query, the (hash, y) pair
@@ -163,7 +163,7 @@ struct SketchRun {
         u32 capw = (u32)ctx->opt_u64("WAVE_CAP", HPC ? 2560 : 3328);
         capw = std::max<u32>(64, capw / 64 * 64);
         u64 *wx = sc.get<u64>((size_t)n_waves * capw + 8);
-        wdig_t *wd = (wx && segw) ? sc.get<wdig_t>((size_t)n_waves * capw + 8) : nullptr;      // (packed 8-byte entries have no digit member)
+        u32 *wd = (wx && segw) ? sc.get<u32>((size_t)n_waves * capw + 8) : nullptr;      // (packed 8-byte entries have no digit member)
         u32 *wcnt = (wx && (wd || !segw)) ? sc.get<u32>((size_t)n_waves + 1) : nullptr, *woffs = wcnt ? sc.get<u32>((size_t)n_waves + 1) : nullptr;
         if (!(wx && (wd || !segw) && wcnt && woffs)) {
             if (wx) sc.drop(wx); if (wd) sc.drop(wd); if (wcnt) sc.drop(wcnt); if (woffs) sc.drop(woffs);
@@ -178,7 +178,7 @@ struct SketchRun {
             if (segw) hipLaunchKernelGGL((k_sketch_wave<K, W, HPC, 2>), dim3((u32)div_up(c1 - c0, SK_THREADS)), dim3(SK_THREADS), 0, ctx->stream, s->d_pack, s->d_nmask, s->d_woff,
                                          s->d_len, cm, c1, wcnt, d_total + 1, wx, wd, rq.pk_pos1, rq.pk_ybits, capw, c0);
             else hipLaunchKernelGGL((k_sketch_wave<K, W, HPC, 1>), dim3((u32)div_up(c1 - c0, SK_THREADS)), dim3(SK_THREADS), 0, ctx->stream, s->d_pack, s->d_nmask, s->d_woff,
-                                    s->d_len, cm, c1, wcnt, d_total + 1, wx, (wdig_t *)nullptr, rq.pk_pos1, rq.pk_ybits, capw, c0);
+                                    s->d_len, cm, c1, wcnt, d_total + 1, wx, (u32 *)nullptr, rq.pk_pos1, rq.pk_ybits, capw, c0);
         };
         u32 c_done = 0;
         int rc = gw.walk(64, &c_done, launch_wave); if (rc) return rc;

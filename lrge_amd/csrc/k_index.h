@@ -78,7 +78,7 @@ __device__ __forceinline__ u64 ht_home(u64 key, u64 cap, u32 fix) {
 #define PLACE_TILE (PLACE_THREADS * PLACE_ROWS)
 #define PLACE_COMP 384      // slots a wavefront composes in LDS (64 runs at load 1/2 span ~128)
 
-// The hash of entry `st` of the sorted stream.  seg.start != null: a segment-packed index (k_prims.h: index_sort_segpacked).
+// The hash of entry `st` of the sorted stream.  seg.start != null: a segment-packed index (k_prims.h: index_sort_seg).
 // The stream is ordered by the byte-reversed hash; written as ONE number, that order is the hash's SIGNIFICANCE STRING
 //     S = b0 . b1 . b2 ... b(m-1)          (b0 = low byte, most significant; the top byte b(m-1) holds tb = nbits - 8 (m - 1) bits)
 // (hash_to_sig: a byte swap with the partial top byte squeezed).  A segment-packed entry keeps the low nr = nbits - 8 - e bits R of

@@ -2,6 +2,7 @@
 // written for gfx950: 64-lane wavefronts, ballot-based digit matching, LDS counters.
 #pragma once
 #include "internal.h"
+#include <functional>
 #include <type_traits>
 
 // ------------------------------------------------------------------------------------------
@@ -261,7 +262,7 @@ struct SegTile { u32 start, len, hbase, hstride, seg, delta, src, pad; };
 // (key = segment << sh_q | sort bits, value = self << 43 | span << 32 | qpos) -- see k_seed.h for the layouts.
 // The SIGNIFICANCE STRING of an nbits-bit hash: the index stream is ordered by the byte-reversed hash (k_index.h), i.e. by
 //     S = b0 . b1 . b2 ... b(m-1)          (b0 = low byte, most significant; the top byte b(m-1) holds tb = nbits - 8 (m - 1) bits)
-// read as one number -- a byte swap with the partial top byte squeezed.  Segment-packed index entries (index_sort_segpacked) keep the
+// read as one number -- a byte swap with the partial top byte squeezed.  Segment-packed index entries (index_sort_seg) keep the
 // low bits of S; its top bits are the number of their segment.
 __host__ __device__ __forceinline__ u64 hash_to_sig(u64 h, u32 nbits) {
     const u32 m = (nbits + 7) >> 3, tb = nbits - 8 * (m - 1);
@@ -274,12 +275,11 @@ __host__ __device__ __forceinline__ u64 sig_to_hash(u64 S, u32 nbits) {
     return __builtin_bswap64(X << (64 - 8 * m));
 }
 struct UnpackParams {
-    u32 sb, bits_qy, sh_q, dmask, nbits;
+    u32 sb = 0, bits_qy = 0, sh_q = 0, dmask = 255, nbits = 0;
     // nd_out != null (round 6): the scatter also leaves, beside every key it writes, the key's digit of the NEXT pass -- (key >> nd_shift) &
     // nd_mask, one byte -- so that the next pass's histogram reads 1 byte per entry instead of the 8-byte key (k_rs_hist, key32 == 2).
     // The bytes of a (tile, digit) run are consecutive like its keys, and neighbouring tiles meet in one L2 (xcd_tile): whole lines go out.
-    u8 *nd_out; u32 nd_shift, nd_mask;
-    u32 dig16;      // the DIG member of SEGW entries (RS_MODE_DW*: keys_in, and RS_MODE_DW's keys_out) is a u16 array instead of a u32 one (the wave-dense sketch's, round 6)
+    u8 *nd_out = nullptr; u32 nd_shift = 0, nd_mask = 0;
 };   // dmask: digit mask of the pass (the last digit may be narrower than 8 bits); nbits: hash bits (PACK / PACKQ)
 #define RS_MODE_PAIRS 0
 #define RS_MODE_KEYS 1
@@ -288,7 +288,7 @@ struct UnpackParams {
                             // hash's significance string (k_index.h: hash_to_sig; the low hash byte is the segment); `shift` addresses the packed value
 #define RS_MODE_PACKQ 4     // the same, and the pass's digit -- the top e = up.sh_q bits of the second hash byte, `shift` = 16 - e addresses the HASH -- is
                             // left out of the word as well: R = the low up.nbits - 8 - e bits (the pass makes the digit part of the segment:
-                            // index_sort_segpacked with e > 0; e <= 7)
+                            // index_sort_seg with e > 0; e <= 7)
 
 // SEGW entries (round 5; k_sketch.h, sketch_write_chunk PK == 2): the sketch hands the sort a WORD per entry -- [the low nbits - 16 bits of the
 // hash's significance string | rid | pos << 1 | strand] -- and, in a u32 array, the string's top 16 bits DIG = b0 << 8 | b1: 12 bytes instead
@@ -314,16 +314,9 @@ __device__ __forceinline__ u32 xcd_tile(u32 b, u32 nb) {
 // A sort whose FIRST pass reads the sketch's per-chunk slots in place of a dense array (k_sketch.h: k_sketch_direct writes chunk c's
 // entries to slots[c * cap ...), offs[] = exclusive scan of the per-chunk counts): dense index i lives in chunk c = the last one
 // with offs[c] <= i, at slots[c * cap + i - offs[c]].  What that saves is k_sketch_compact: one read and one write of every entry.
-// the DIG member of a wave-dense SEGW entry (k_sketch.h: k_sketch_wave): 16 bits suffice, but 2-byte loads and stores ... see DESIGN section 9
-#ifndef WAVE_DIG_BITS
-#define WAVE_DIG_BITS 32
-#endif
-#if WAVE_DIG_BITS == 16
-typedef u16 wdig_t;
-#else
-typedef u32 wdig_t;
-#endif
-struct SlotSrc { const u64 *slots; const u32 *offs; const u32 *tile_chunk; u32 n_chunks, cap, total; const wdig_t *dig; const u32 *tile_desc; };      // dig: the 16-bit DIG members beside the words (the wave-dense sketch's slots: RS_MODE_DW); tile_desc: see k_tile_desc
+// (The DIG member of a wave-dense SEGW entry -- k_sketch.h: k_sketch_wave -- is a u32 like the dense form's: 16 bits would do, but 2-byte loads
+// and stores are slow on this chip)
+struct SlotSrc { const u64 *slots; const u32 *offs; const u32 *tile_chunk; u32 n_chunks, cap, total; const u32 *dig; const u32 *tile_desc; };      // dig: the DIG members beside the words (the wave-dense sketch's slots: RS_MODE_DW); tile_desc: see k_tile_desc
 #define SLOT_LDS 384        // chunk offsets a tile keeps in LDS (4096 entries span ~95 chunks of ~43; more: read from memory)
 
 // tile_chunk[t] = the chunk that holds dense index t * RS_TILE (the last c with offs[c] <= it)
@@ -434,11 +427,11 @@ __device__ __forceinline__ void rs_load_from_slots(const SlotSrc &S, u32 bid, u6
 // DB: digit bits.  The library launches 8 only; the 10-bit instantiation lives with the measurements that ruled it out
 // (tools/micro/sort_forms.h: one 10-bit pass 0.58 + 0.15 + 1.33 ms against 0.43 + 0.05 + 0.88, the whole sort 5.8 against 5.0 ms)
 // sig_nbits != 0: the keys are raw hashes of that many bits and the digit is cut from their significance string (k_index.h:
-// hash_to_sig) -- the first LSD pass of index_sort_segpacked without an A2 pass reads the pairs' hashes
+// hash_to_sig) -- the first LSD pass of index_sort_seg over pairs without an A2 pass reads their hashes
 template <bool SEG, int DB = 8, bool SLOTS = false>
 __global__ __launch_bounds__(RS_THREADS) void k_rs_hist(const u64 *__restrict__ keys, u64 n, int shift, u32 nb,
                                                         u32 *__restrict__ hist, const SegTile *__restrict__ tiles, u32 dmask = 255, SlotSrc src = SlotSrc(),
-                                                        u32 use_src = 0, u32 sig_nbits = 0, u32 key32 = 0) {       // key32 = 1: `keys` is a u32 array (the DIG member of SEGW entries); 3: a u16 array (the same, wave-dense form); 2: a u8 array of ready-made digits
+                                                        u32 use_src = 0, u32 sig_nbits = 0, u32 key32 = 0) {       // key32 = 1: `keys` is a u32 array (the DIG member of SEGW entries); 2: a u8 array of ready-made digits
     constexpr u32 ND = 1u << DB;
     static_assert(!SLOTS || !SEG, "slots feed whole (unsegmented) sorts only");
     __shared__ u32 h[ND];
@@ -483,7 +476,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_hist(const u64 *__restrict__ 
     else {
 #pragma unroll
         for (int r = 0; r < RS_ITEMS; ++r)
-            kk[r] = l0 + (u32)r * 64 < n_tile ? (key32 == 3 ? (u64)((const u16 *)keys)[tile0 + l0 + (u32)r * 64] : key32 ? (u64)((const u32 *)keys)[tile0 + l0 + (u32)r * 64] : keys[tile0 + l0 + (u32)r * 64]) : 0;
+            kk[r] = l0 + (u32)r * 64 < n_tile ? (key32 ? (u64)((const u32 *)keys)[tile0 + l0 + (u32)r * 64] : keys[tile0 + l0 + (u32)r * 64]) : 0;
     }
 #pragma unroll
     for (int r = 0; r < RS_ITEMS; ++r)
@@ -528,7 +521,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(const u64 *__restrict
     u64 k[RS_ITEMS], v[RS_ITEMS];
     u32 rank[RS_ITEMS];
     // all loads of the tile are issued up front: the values arrive while the keys are being ranked
-    if (SLOTS && MODE == RS_MODE_DW) {       // the wave-dense sketch's slots: 16-bit DIG members and the words, the same index in both arrays
+    if (SLOTS && MODE == RS_MODE_DW) {       // the wave-dense sketch's slots: DIG members and the words, the same index in both arrays
 #pragma unroll
         for (int r = 0; r < RS_ITEMS; ++r) { k[r] = ~0ULL; v[r] = 0; }
         rs_for_slot_items(src, bid, tile0, n_tile, s_offs, [&](int r, u64 si) { k[r] = (u64)src.dig[si]; v[r] = src.slots[si]; });
@@ -536,14 +529,14 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(const u64 *__restrict
     else {
 #pragma unroll
         for (int r = 0; r < RS_ITEMS; ++r)
-            k[r] = l0 + (u32)r * 64 < n_tile ? (DWIN ? (up.dig16 ? (u64)((const u16 *)keys_in)[base + (u64)r * 64] : (u64)((const u32 *)keys_in)[base + (u64)r * 64]) : keys_in[base + (u64)r * 64]) : ~0ULL;
+            k[r] = l0 + (u32)r * 64 < n_tile ? (DWIN ? (u64)((const u32 *)keys_in)[base + (u64)r * 64] : keys_in[base + (u64)r * 64]) : ~0ULL;
     }
     if ((MODE == RS_MODE_PAIRS || MODE == RS_MODE_PACK || MODE == RS_MODE_PACKQ || DWIN) && !(SLOTS && MODE == RS_MODE_DW)) {
 #pragma unroll
         for (int r = 0; r < RS_ITEMS; ++r) v[r] = l0 + (u32)r * 64 < n_tile ? vals_in[base + (u64)r * 64] : 0;
     }
     if (MODE == RS_MODE_PACK) {
-        // the low hash byte is implied by the segment the tile lies in (index_sort_segpacked): what is left of the hash and
+        // the low hash byte is implied by the segment the tile lies in (index_sort_seg): what is left of the hash and
         // the position fit one word, and every later pass moves 8 bytes per entry instead of 16
         const u64 pmask = (1ULL << up.bits_qy) - 1, rmask = (1ULL << (up.nbits - 8)) - 1;
 #pragma unroll
@@ -655,7 +648,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(const u64 *__restrict
             ko[r] = stage[p];
             u32 d = (u32)(ko[r] >> shift) & dmask;
             if (MODE == RS_MODE_PACKQ || MODE == RS_MODE_DWQ) d = sdig[p];
-            if (MODE == RS_MODE_DW) { if (up.dig16) ((u16 *)keys_out)[gbase[d] + p] = (u16)ko[r]; else ((u32 *)keys_out)[gbase[d] + p] = (u32)ko[r]; }
+            if (MODE == RS_MODE_DW) ((u32 *)keys_out)[gbase[d] + p] = (u32)ko[r];
             else keys_out[gbase[d] + p] = ko[r];
             if (MODE != RS_MODE_DW && MODE != RS_MODE_PAIRS && up.nd_out) up.nd_out[gbase[d] + p] = (u8)((u32)(ko[r] >> up.nd_shift) & up.nd_mask);
         }
@@ -673,6 +666,51 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(const u64 *__restrict
         if (p < n_tile) vals_out[gbase[(u32)(ko[r] >> shift) & dmask] + p] = stage[p];
     }
 }
+
+// ONE PASS of a sort, as every driver below queues it: the histogram of the pass's digit over the nb tiles, its exclusive scan, the timed
+// scatter, the counters (`items` entries of `bytes_per` bytes through the scatter).  The histogram reads `hs`; the scatter's arguments are
+// the kernel's own.  after_scan (may be empty) is queued between the scan and the scatter.
+struct HistSrc { const u64 *keys; int shift; u32 key32 = 0, sig_nbits = 0; };      // see k_rs_hist
+template <bool SEG, int MODE, bool SLOTS = false>
+static int rs_pass(lrge_hip_ctx *ctx, Scratch &sc, u32 *hist, u32 nb, const SegTile *tiles, const HistSrc &hs, const u64 *ki, const u64 *vi, u64 *ko, u64 *vo,
+                   u64 n, int shift, const UnpackParams &up, u64 items, u32 bytes_per, const SlotSrc &src = SlotSrc(), u32 use_src = 0,
+                   const std::function<int()> &after_scan = nullptr) {
+    hipLaunchKernelGGL((k_rs_hist<SEG, 8, SLOTS>), dim3(nb), dim3(RS_THREADS), 0, ctx->stream, hs.keys, n, hs.shift, nb, hist, tiles, up.dmask, src, use_src, hs.sig_nbits, hs.key32);
+    KCHK(ctx);
+    int rc = scan_exclusive_u32(ctx, sc, hist, hist, (u64)256 * nb, nullptr);
+    if (!rc && after_scan) rc = after_scan();
+    if (rc) return rc;
+    StageTimer ts(ctx, LRGE_T_RS_SCATTER);
+    hipLaunchKernelGGL((k_rs_scatter<SEG, MODE, 8, SLOTS>), dim3(nb), dim3(RS_THREADS), 0, ctx->stream, ki, vi, ko, vo, n, shift, nb, hist, tiles, up, src, use_src);
+    KCHK(ctx);
+    ts.stop();
+    ctx->counters[LRGE_C_RS_SCATTER_LAUNCHES] += 1;
+    ctx->counters[LRGE_C_RS_SCATTER_ITEMS] += items;
+    ctx->counters[LRGE_C_RS_SCATTER_BYTES] += bytes_per * items;
+    return LRGE_OK;
+}
+
+// Next-pass digit bytes (UnpackParams::nd_out): a scatter that writes keys also leaves the byte the NEXT pass ranks by, and that pass's
+// histogram reads 1 byte per entry instead of 8.  Option NO_DIGIT_BYTES, or a sort of fewer than two passes: every histogram reads the keys.
+struct DigitBytes {
+    u8 *nd = nullptr;
+    bool valid = false;                                // nd holds the digits of the pass about to run
+    DigitBytes(lrge_hip_ctx *ctx, Scratch &sc, u64 n, int passes) {
+        if (ctx->opt("NO_DIGIT_BYTES") || passes < 2) return;
+        nd = sc.get<u8>(n + 64);
+        if (!nd) { (void)hipGetLastError(); ctx->err.clear(); }       // (no memory for them: the sort runs without)
+    }
+    // what the scatter of the pass about to run adds to its parameters when the pass behind it (`more`: there is one) ranks by (key >> shift) & mask
+    void next(UnpackParams &up, bool more, u32 shift, u32 mask) const {
+        up.nd_out = nullptr;
+        if (nd && more) { up.nd_out = nd; up.nd_shift = shift; up.nd_mask = mask; }
+    }
+    // what the histogram of the pass about to run reads: the bytes the scatter before left, or the keys
+    HistSrc hist(const u64 *keys, int shift) const { return valid ? HistSrc{(const u64 *)nd, 0, 2u} : HistSrc{keys, shift}; }
+    void ran(const UnpackParams &up) { valid = up.nd_out != nullptr; }
+    void drop(Scratch &sc) { if (nd) sc.drop(nd); }
+};
+static inline u32 digit_mask(int bits_left) { return bits_left >= 8 ? 255u : bits_left > 0 ? (1u << bits_left) - 1u : 0u; }      // of a pass with that many key bits at and above its shift
 
 // Sorts (keys, vals) by bits [begin_bit, begin_bit + nbits) of the key (rounded up to whole bytes).  Ping-pongs between (k0,v0) and (k1,v1);
 // *res_k / *res_v point at the buffers holding the result.
@@ -693,21 +731,9 @@ static int radix_sort_pairs(lrge_hip_ctx *ctx, Scratch &sc, u64 *k0, u64 *v0, u6
     u64 *ki = k0, *vi = v0, *ko = k1, *vo = v1;
     for (int p = pass_begin; p < (pass_end < 0 ? passes : std::min(pass_end, passes)); ++p) {
         int shift = begin_bit + (reverse_digits ? passes - 1 - p : p) * 8;
-        if (d_tiles) hipLaunchKernelGGL(k_rs_hist<true>, dim3(nb), dim3(RS_THREADS), 0, ctx->stream, ki, n, shift, nb, hist, d_tiles);
-        else hipLaunchKernelGGL(k_rs_hist<false>, dim3(nb), dim3(RS_THREADS), 0, ctx->stream, ki, n, shift, nb, hist, d_tiles);
-        KCHK(ctx);
-        int rc = scan_exclusive_u32(ctx, sc, hist, hist, (u64)256 * nb, nullptr);
+        int rc = d_tiles ? rs_pass<true, RS_MODE_PAIRS>(ctx, sc, hist, nb, d_tiles, HistSrc{ki, shift}, ki, vi, ko, vo, n, shift, UnpackParams(), n, 32)
+                         : rs_pass<false, RS_MODE_PAIRS>(ctx, sc, hist, nb, d_tiles, HistSrc{ki, shift}, ki, vi, ko, vo, n, shift, UnpackParams(), n, 32);
         if (rc) return rc;
-        {
-            StageTimer ts(ctx, LRGE_T_RS_SCATTER);
-            if (d_tiles) hipLaunchKernelGGL((k_rs_scatter<true, RS_MODE_PAIRS>), dim3(nb), dim3(RS_THREADS), 0, ctx->stream, ki, vi, ko, vo, n, shift, nb, hist, d_tiles, UnpackParams{0, 0, 0, 255});
-            else hipLaunchKernelGGL((k_rs_scatter<false, RS_MODE_PAIRS>), dim3(nb), dim3(RS_THREADS), 0, ctx->stream, ki, vi, ko, vo, n, shift, nb, hist, d_tiles, UnpackParams{0, 0, 0, 255});
-            KCHK(ctx);
-            ts.stop();
-            ctx->counters[LRGE_C_RS_SCATTER_LAUNCHES] += 1;
-            ctx->counters[LRGE_C_RS_SCATTER_ITEMS] += n;
-            ctx->counters[LRGE_C_RS_SCATTER_BYTES] += 32 * n;
-        }
         u64 *t = ki; ki = ko; ko = t;
         t = vi; vi = vo; vo = t;
     }
@@ -728,37 +754,20 @@ static int radix_sort_packed_seg(lrge_hip_ctx *ctx, Scratch &sc, u64 *pk0, u64 *
     ALLOC_OR_FAIL(hist, sc, u32, (u64)256 * nb);
     const int passes = nbits > 0 ? (nbits + 7) / 8 : 1;
     u64 *ki = pk0, *ko = pk1;
-    // next-pass digit bytes (UnpackParams::nd_out; option NO_DIGIT_BYTES: every histogram reads the packed anchors)
-    u8 *nd = (ctx->opt("NO_DIGIT_BYTES") || passes < 2) ? nullptr : sc.get<u8>(n + 64);
-    if (!nd) { (void)hipGetLastError(); ctx->err.clear(); }
-    bool nd_valid = false;
+    DigitBytes db(ctx, sc, n, passes);
     for (int p = 0; p < passes; ++p) {
         const int shift = p * 8;
-        up.dmask = nbits - shift >= 8 ? 255u : (1u << (nbits - shift)) - 1u;   // bits above nbits are payload, not key
-        up.nd_out = nullptr;
-        if (nd && p + 2 < passes + 1 && p + 1 < passes) { up.nd_out = nd; up.nd_shift = (u32)shift + 8u; up.nd_mask = nbits - (shift + 8) >= 8 ? 255u : (1u << (nbits - (shift + 8))) - 1u; }
+        const bool last = p + 1 == passes;
+        up.dmask = digit_mask(nbits - shift);          // bits above nbits are payload, not key
+        db.next(up, !last, (u32)shift + 8u, digit_mask(nbits - (shift + 8)));
         const u32 us = (src_first && p == 0) ? 1u : 0u;
-        if (nd_valid) hipLaunchKernelGGL(k_rs_hist<true>, dim3(nb), dim3(RS_THREADS), 0, ctx->stream, (const u64 *)nd, n, 0, nb, hist, d_tiles, up.dmask, SlotSrc(), 0u, 0u, 2u);
-        else hipLaunchKernelGGL(k_rs_hist<true>, dim3(nb), dim3(RS_THREADS), 0, ctx->stream, ki, n, shift, nb, hist, d_tiles, up.dmask, SlotSrc(), us);
-        KCHK(ctx);
-        int rc = scan_exclusive_u32(ctx, sc, hist, hist, (u64)256 * nb, nullptr);
+        const int rc = last ? rs_pass<true, RS_MODE_UNPACK>(ctx, sc, hist, nb, d_tiles, db.hist(ki, shift), ki, nullptr, out_k, out_v, n, shift, up, n_items, 24, SlotSrc(), us)
+                            : rs_pass<true, RS_MODE_KEYS>(ctx, sc, hist, nb, d_tiles, db.hist(ki, shift), ki, nullptr, ko, nullptr, n, shift, up, n_items, 16, SlotSrc(), us);
         if (rc) return rc;
-        {
-            StageTimer ts(ctx, LRGE_T_RS_SCATTER);
-            if (p + 1 < passes)
-                hipLaunchKernelGGL((k_rs_scatter<true, RS_MODE_KEYS>), dim3(nb), dim3(RS_THREADS), 0, ctx->stream, ki, (const u64 *)nullptr, ko, (u64 *)nullptr, n, shift, nb, hist, d_tiles, up, SlotSrc(), us);
-            else
-                hipLaunchKernelGGL((k_rs_scatter<true, RS_MODE_UNPACK>), dim3(nb), dim3(RS_THREADS), 0, ctx->stream, ki, (const u64 *)nullptr, out_k, out_v, n, shift, nb, hist, d_tiles, up, SlotSrc(), us);
-            KCHK(ctx);
-            ts.stop();
-            ctx->counters[LRGE_C_RS_SCATTER_LAUNCHES] += 1;
-            ctx->counters[LRGE_C_RS_SCATTER_ITEMS] += n_items;
-            ctx->counters[LRGE_C_RS_SCATTER_BYTES] += (p + 1 < passes ? 16 : 24) * n_items;
-        }
-        nd_valid = up.nd_out != nullptr;
+        db.ran(up);
         u64 *t = ki; ki = ko; ko = t;
     }
-    if (nd) sc.drop(nd);
+    db.drop(sc);
     sc.drop(hist);
     return LRGE_OK;
 }
@@ -771,7 +780,7 @@ static int radix_sort_keys_first_pass_from_slots(lrge_hip_ctx *ctx, Scratch &sc,
     if (n >= (1ULL << 32)) { LRGE_SET_ERR(ctx, "radix sort limited to < 2^32 items (got %llu)", (unsigned long long)n); return LRGE_ERR_INVALID; }
     const u32 nb = (u32)div_up(n, RS_TILE);
     const int passes = (nbits + 7) / 8, d = reverse_digits ? passes - 1 : 0, shift = begin_bit + d * 8;
-    UnpackParams up{0, 0, 0, nbits - d * 8 >= 8 ? 255u : (1u << (nbits - d * 8)) - 1u};
+    UnpackParams up; up.dmask = digit_mask(nbits - d * 8);
     ALLOC_OR_FAIL(hist, sc, u32, (u64)256 * nb);
     ALLOC_OR_FAIL(tile_chunk, sc, u32, (size_t)nb + 1);
     hipLaunchKernelGGL(k_tile_chunks, dim3((u32)div_up(nb, 256)), dim3(256), 0, ctx->stream, offs, n_chunks, nb, tile_chunk);
@@ -785,20 +794,8 @@ static int radix_sort_keys_first_pass_from_slots(lrge_hip_ctx *ctx, Scratch &sc,
         KCHK(ctx);
     }
     SlotSrc src{slots, offs, tile_chunk, n_chunks, cap, (u32)n, nullptr, tile_desc};
-    hipLaunchKernelGGL((k_rs_hist<false, 8, true>), dim3(nb), dim3(RS_THREADS), 0, ctx->stream, (const u64 *)nullptr, n, shift, nb, hist, (const SegTile *)nullptr, up.dmask, src);
-    KCHK(ctx);
-    int rc = scan_exclusive_u32(ctx, sc, hist, hist, (u64)256 * nb, nullptr);
+    int rc = rs_pass<false, RS_MODE_KEYS, true>(ctx, sc, hist, nb, nullptr, HistSrc{nullptr, shift}, nullptr, nullptr, out, nullptr, n, shift, up, n, 16, src);
     if (rc) return rc;
-    {
-        StageTimer ts(ctx, LRGE_T_RS_SCATTER);
-        hipLaunchKernelGGL((k_rs_scatter<false, RS_MODE_KEYS, 8, true>), dim3(nb), dim3(RS_THREADS), 0, ctx->stream, (const u64 *)nullptr, (const u64 *)nullptr, out, (u64 *)nullptr, n,
-                           shift, nb, hist, (const SegTile *)nullptr, up, src);
-        KCHK(ctx);
-        ts.stop();
-        ctx->counters[LRGE_C_RS_SCATTER_LAUNCHES] += 1;
-        ctx->counters[LRGE_C_RS_SCATTER_ITEMS] += n;
-        ctx->counters[LRGE_C_RS_SCATTER_BYTES] += 16 * n;
-    }
     sc.drop(hist); sc.drop(tile_chunk); if (tile_desc) sc.drop(tile_desc);
     return LRGE_OK;
 }
@@ -816,37 +813,18 @@ static int radix_sort_keys(lrge_hip_ctx *ctx, Scratch &sc, u64 *k0, u64 *k1, u64
     const int passes = (nbits + 7) / 8;
     u64 *ki = k0, *ko = k1;
     const int p_end = pass_end < 0 ? passes : std::min(pass_end, passes);
-    // next-pass digit bytes (UnpackParams::nd_out; option NO_DIGIT_BYTES: every histogram reads the keys)
-    u8 *nd = (ctx->opt("NO_DIGIT_BYTES") || p_end - pass_begin < 2) ? nullptr : sc.get<u8>(n + 64);
-    if (!nd) { (void)hipGetLastError(); ctx->err.clear(); }
-    bool nd_valid = false;
+    DigitBytes db(ctx, sc, n, p_end - pass_begin);
     for (int p = pass_begin; p < p_end; ++p) {
-        const int d = reverse_digits ? passes - 1 - p : p;
+        const int d = reverse_digits ? passes - 1 - p : p, d2 = reverse_digits ? d - 1 : d + 1;      // this pass's digit and the next one's
         const int shift = begin_bit + d * 8;
-        UnpackParams up{0, 0, 0, nbits - d * 8 >= 8 ? 255u : (1u << (nbits - d * 8)) - 1u, 0, nullptr, 0, 0};
-        if (nd && p + 1 < p_end) {
-            const int d2 = reverse_digits ? passes - 2 - p : p + 1;
-            up.nd_out = nd; up.nd_shift = (u32)(begin_bit + d2 * 8); up.nd_mask = nbits - d2 * 8 >= 8 ? 255u : (1u << (nbits - d2 * 8)) - 1u;
-        }
-        if (nd_valid) hipLaunchKernelGGL((k_rs_hist<false, 8>), dim3(nb), dim3(RS_THREADS), 0, ctx->stream, (const u64 *)nd, n, 0, nb, hist, (const SegTile *)nullptr, up.dmask, SlotSrc(), 0u, 0u, 2u);
-        else hipLaunchKernelGGL((k_rs_hist<false, 8>), dim3(nb), dim3(RS_THREADS), 0, ctx->stream, ki, n, shift, nb, hist, (const SegTile *)nullptr, up.dmask);
-        KCHK(ctx);
-        int rc = scan_exclusive_u32(ctx, sc, hist, hist, (u64)256 * nb, nullptr);
+        UnpackParams up; up.dmask = digit_mask(nbits - d * 8);
+        db.next(up, p + 1 < p_end, (u32)(begin_bit + d2 * 8), digit_mask(nbits - d2 * 8));
+        int rc = rs_pass<false, RS_MODE_KEYS>(ctx, sc, hist, nb, nullptr, db.hist(ki, shift), ki, nullptr, ko, nullptr, n, shift, up, n, 16);
         if (rc) return rc;
-        {
-            StageTimer ts(ctx, LRGE_T_RS_SCATTER);
-            hipLaunchKernelGGL((k_rs_scatter<false, RS_MODE_KEYS, 8>), dim3(nb), dim3(RS_THREADS), 0, ctx->stream, ki, (const u64 *)nullptr, ko, (u64 *)nullptr, n, shift, nb,
-                               hist, (const SegTile *)nullptr, up);
-            KCHK(ctx);
-            ts.stop();
-            ctx->counters[LRGE_C_RS_SCATTER_LAUNCHES] += 1;
-            ctx->counters[LRGE_C_RS_SCATTER_ITEMS] += n;
-            ctx->counters[LRGE_C_RS_SCATTER_BYTES] += 16 * n;
-        }
-        nd_valid = up.nd_out != nullptr;
+        db.ran(up);
         u64 *t = ki; ki = ko; ko = t;
     }
-    if (nd) sc.drop(nd);
+    db.drop(sc);
     sc.drop(hist);
     *res = ki;
     return LRGE_OK;
@@ -863,7 +841,7 @@ static int radix_sort_keys(lrge_hip_ctx *ctx, Scratch &sc, u64 *k0, u64 *k1, u64
 #define HC_TILE (HC_THREADS * HC_ITEMS)
 
 // seg_start (may be null; n_seg + 1 ascending entries): positions that start a run whatever the keys say -- the entries of a
-// segment-packed index (index_sort_segpacked) carry their hash without its low byte, so two neighbours on either side of a
+// segment-packed index (index_sort_seg) carry their hash without its low byte, so two neighbours on either side of a
 // segment boundary may look alike
 __device__ __forceinline__ u32 hc_boundary_flags(const u32 *__restrict__ seg_start, u32 n_seg, u64 n, u64 base) {
     u32 lo = 0, hi = n_seg + 1;                      // first boundary >= base
@@ -906,23 +884,15 @@ __device__ __forceinline__ u32 hc_load_flags(const u64 *__restrict__ keys, u64 n
     return f;
 }
 
-// flags: the 16 head bits of every thread's line, kept for k_heads_fill (instead of re-reading 128 bytes of keys); stored as a dword per
-// thread since round 6 (HFLAG_BITS=16: the u16 array of rounds 2-5 -- 2-byte stores and loads are slow on this chip)
-#ifndef HFLAG_BITS
-#define HFLAG_BITS 32
-#endif
-#if HFLAG_BITS == 16
-typedef u16 hflag_t;
-#else
-typedef u32 hflag_t;
-#endif
+// flags: the 16 head bits of every thread's line, kept for k_heads_fill (instead of re-reading 128 bytes of keys); a dword per thread
+// (a u16 array in rounds 2-5: 2-byte stores and loads are slow on this chip)
 __global__ __launch_bounds__(HC_THREADS) void k_heads_count(const u64 *__restrict__ keys, u64 n, u32 shift, u32 *__restrict__ bcount,
-                                                            hflag_t *__restrict__ flags, const u32 *__restrict__ seg_start = nullptr, u32 n_seg = 0) {
+                                                            u32 *__restrict__ flags, const u32 *__restrict__ seg_start = nullptr, u32 n_seg = 0) {
     __shared__ u32 ws[HC_THREADS / 64];
     const u64 base = (u64)blockIdx.x * HC_TILE + (u64)threadIdx.x * HC_ITEMS;
     u32 f = hc_load_flags(keys, n, shift, base);
     if (seg_start && base < n) f |= hc_boundary_flags(seg_start, n_seg, n, base);
-    flags[(u64)blockIdx.x * HC_THREADS + threadIdx.x] = (hflag_t)f;
+    flags[(u64)blockIdx.x * HC_THREADS + threadIdx.x] = f;
     u32 c = (u32)__popc(f);
     for (int d = 32; d > 0; d >>= 1) c += __shfl_down(c, d, 64);
     if (lane_id() == 0) ws[threadIdx.x >> 6] = c;
@@ -930,7 +900,7 @@ __global__ __launch_bounds__(HC_THREADS) void k_heads_count(const u64 *__restric
     if (threadIdx.x == 0) { u32 t = 0; for (int w = 0; w < HC_THREADS / 64; ++w) t += ws[w]; bcount[blockIdx.x] = t; }
 }
 
-__global__ __launch_bounds__(HC_THREADS) void k_heads_fill(const hflag_t *__restrict__ flags, const u32 *__restrict__ boff,
+__global__ __launch_bounds__(HC_THREADS) void k_heads_fill(const u32 *__restrict__ flags, const u32 *__restrict__ boff,
                                                            u32 *__restrict__ starts) {
     __shared__ u32 ws[HC_THREADS / 64];
     __shared__ u32 tile[HC_TILE];            // the block's heads, in order: they leave as one coalesced run
@@ -956,7 +926,7 @@ static int compact_heads_async(lrge_hip_ctx *ctx, Scratch &sc, const u64 *keys, 
     if (n == 0) { HIPCHK(ctx, hipMemsetAsync(d_count, 0, 4, ctx->stream)); return LRGE_OK; }
     const u32 nb = (u32)div_up(n, HC_TILE);
     ALLOC_OR_FAIL(bc, sc, u32, (size_t)nb + 1);
-    ALLOC_OR_FAIL(fl, sc, hflag_t, (size_t)nb * HC_THREADS);
+    ALLOC_OR_FAIL(fl, sc, u32, (size_t)nb * HC_THREADS);
     hipLaunchKernelGGL(k_heads_count, dim3(nb), dim3(HC_THREADS), 0, ctx->stream, keys, n, shift, bc, fl);
     KCHK(ctx);
     int rc = scan_exclusive_u32(ctx, sc, bc, bc, nb, d_count);
@@ -975,7 +945,7 @@ static int compact_heads(lrge_hip_ctx *ctx, Scratch &sc, const u64 *keys, u64 n,
     const u32 nb = (u32)div_up(n, HC_TILE);
     ALLOC_OR_FAIL(bc, sc, u32, (size_t)nb + 1);
     ALLOC_OR_FAIL(d_tot, sc, u32, 1);
-    ALLOC_OR_FAIL(fl, sc, hflag_t, (size_t)nb * HC_THREADS);
+    ALLOC_OR_FAIL(fl, sc, u32, (size_t)nb * HC_THREADS);
     hipLaunchKernelGGL(k_heads_count, dim3(nb), dim3(HC_THREADS), 0, ctx->stream, keys, n, shift, bc, fl, seg_start, n_seg);
     KCHK(ctx);
     int rc = scan_exclusive_u32(ctx, sc, bc, bc, nb, d_tot);
@@ -1157,235 +1127,125 @@ __global__ __launch_bounds__(256) void k_seg_fine_starts(const u32 *__restrict__
 }
 __global__ void k_store_u32(u32 *p, u32 v) { *p = v; }
 
-static int index_sort_segpacked(lrge_hip_ctx *ctx, Scratch &sc, u64 *kx, u64 *ky, u64 *k1, u64 *v1, u64 n, int nbits, u32 ybits, u32 pos1, u32 e,
-                                u64 **res, u32 **d_seg_start) {
+// SEGW entries (RS_MODE_DW* above) in place of the pairs: the sketch's words and its u32 DIG array.  Pass A moves 12 bytes per entry instead of 16
+// (and its histogram reads 4 instead of 8), pass A2 / the first LSD pass reads 12 instead of 16; from there on the entries are the packed words
+// of the pair form, bit for bit.
+// WaveSrc (round 6): pass A reads the wave-dense sketch's slots (k_sketch.h: k_sketch_wave) in place of dense arrays -- through the slot-source
+// form of its two kernels (SlotSrc) -- words and u32 DIG members at the same index of two arrays.  The slots are released as soon as pass A has read
+// them and the second word buffer is taken in their place.
+struct WaveSrc { u64 *wx; u32 *wd; u32 *cnt, *offs; u32 n_waves, cap; };      // offs: exclusive scan of cnt
+// Where pass A reads its n entries -- exactly one of: (hash, y) pairs (x, y); dense SEGW entries (x = the words, dig); the wave-dense slots (ws).
+struct IndexSortIn {
+    u64 *x = nullptr, *y = nullptr; u32 *dig = nullptr; const WaveSrc *ws = nullptr;
+    bool segw() const { return dig || ws; }
+};
+// tiles[t], t < grid, of the passes over the n_seg segments that begin at starts[] (tb: n_seg + 1 words of scratch)
+static int seg_tiles_build(lrge_hip_ctx *ctx, const u32 *starts, u32 n_seg, u32 *tb, u32 grid, SegTile *tiles) {
+    hipLaunchKernelGGL(k_seg_tile_scan, dim3(1), dim3(1024), 0, ctx->stream, starts, n_seg, tb);
+    hipLaunchKernelGGL(k_seg_tile_fill, dim3(div_up(grid, 256)), dim3(256), 0, ctx->stream, starts, (const u32 *)tb, n_seg, grid, tiles);
+    KCHK(ctx);
+    return LRGE_OK;
+}
+// k1: n + 1 u64; m1: the second member's buffer, n + 1 u64 (pairs) or n + 1 u32 (SEGW), passed as the kernels take it.  *res = the sorted words,
+// in a block of `sc` (an input buffer, k1, or the buffer taken for the slots); every other input buffer and k1 / m1 are released.
+static int index_sort_seg(lrge_hip_ctx *ctx, Scratch &sc, const IndexSortIn &in, u64 *k1, u64 *m1, u64 n, int nbits, u32 ybits, u32 pos1, u32 e,
+                          u64 **res, u32 **d_seg_start) {
     // e > 0: e more hash bits are implied by the segment -- the NEXT bits of the byte-reversed order, the top e bits q of the second
     // byte -- because the word would be too narrow without (large parts: read ids of 19-20 bits) or because what is left of the hash then
-    // takes a pass less.  Pass A2 is a most-significant-digit pass on q inside each of A's 256 segments (pairs in, packed words out:
-    // RS_MODE_PACKQ), leaving 256 << e segments numbered b0 << e | q.  The entry keeps R, the low nr = nbits - 8 - e bits of the hash's
-    // significance string (hash_to_sig): R compares like the order itself, so the keys-only LSD passes behind cut it into 8-bit
+    // takes a pass less.  Pass A2 is a most-significant-digit pass on q inside each of A's 256 segments (entries in, packed words out:
+    // RS_MODE_PACKQ / RS_MODE_DWQ), leaving 256 << e segments numbered b0 << e | q.  The entry keeps R, the low nr = nbits - 8 - e bits of the
+    // hash's significance string (hash_to_sig): R compares like the order itself, so the keys-only LSD passes behind cut it into 8-bit
     // digits from the bottom, the last one taking what is left.  k = 19, e = 6: 32 + 24 + 3 x 16 = 104 bytes per entry through the
     // scatters and five histograms (round 4, e = 2 with byte-aligned digits: 120 and six; the plain pair sort: 160).
+    const bool segw = in.segw();
     const int nr = nbits - 8 - (int)e, passes = (nr + 7) / 8;      // LSD passes over R
     const u32 nb = (u32)div_up(n, RS_TILE), n_seg = 256u << e;
     const u32 max_tiles = nb + n_seg;                  // every segment ends in at most one partial tile
     ALLOC_OR_FAIL(hist, sc, u32, (u64)256 * (max_tiles + 1) + 256);
-    // next-pass digit bytes (UnpackParams::nd_out): every scatter that writes packed words also leaves the byte the NEXT pass ranks by, and
-    // that pass's histogram reads 1 byte per entry instead of 8 (option NO_DIGIT_BYTES: the histograms read the words, rounds 3-5)
-    u8 *nd = ctx->opt("NO_DIGIT_BYTES") ? nullptr : sc.get<u8>(n + 64);
-    if (!nd) { (void)hipGetLastError(); ctx->err.clear(); }
-    bool nd_valid = false;                             // nd holds the digits of the pass about to run
-    auto nd_of = [&](int j_next) -> UnpackParams {      // what the scatter in front of LSD pass j_next adds to its parameters
-        UnpackParams q{0, 0, 0, 0, 0, nullptr, 0, 0};
-        if (nd && j_next < passes) { const int w_ = nr - 8 * j_next >= 8 ? 8 : nr - 8 * j_next; q.nd_out = nd; q.nd_shift = ybits + 8u * (u32)j_next; q.nd_mask = (1u << w_) - 1u; }
-        return q;
+    DigitBytes db(ctx, sc, n, passes + (e ? 1 : 0));   // every scatter that writes packed words leaves the next LSD pass's digit
+    // the parameters of a scatter that writes packed words in front of LSD pass j_next; packs: it makes them out of entries (sh_q: pass A2's e)
+    auto params = [&](u32 dmask, int j_next, bool packs, u32 sh_q = 0) {
+        UnpackParams up; up.dmask = dmask;
+        if (packs) { up.sb = ybits; up.bits_qy = pos1; up.sh_q = sh_q; up.nbits = (u32)nbits; }
+        db.next(up, j_next < passes, ybits + 8u * (u32)j_next, digit_mask(nr - 8 * j_next));
+        return up;
     };
-    // ---- pass A: pairs by the low hash byte ----
-    {
-        hipLaunchKernelGGL(k_rs_hist<false>, dim3(nb), dim3(RS_THREADS), 0, ctx->stream, kx, n, 0, nb, hist, (const SegTile *)nullptr, 255u);
+    int rc;
+    // ---- pass A: by the low hash byte b0, both members move ----
+    if (in.ws) {
+        // dense tiles of RS_TILE entries over the VIRTUAL dense array: entry i lives in the wavefront slot v = the last one with offs[v] <= i,
+        // at index v * cap + i - offs[v] (SlotSrc / rs_for_slot_items; a tile spans two or three slots of ~2 000-2 800 entries).
+        // (One tile per slot -- half-full tiles, twice as many, digit runs of 8 entries -- took 34 ms per part instead of 16.)
+        const WaveSrc &ws = *in.ws;
+        ALLOC_OR_FAIL(tile_chunk, sc, u32, (size_t)nb + 1);
+        hipLaunchKernelGGL(k_tile_chunks, dim3((u32)div_up(nb, 256)), dim3(256), 0, ctx->stream, (const u32 *)ws.offs, ws.n_waves, nb, tile_chunk);
         KCHK(ctx);
-        int rc = scan_exclusive_u32(ctx, sc, hist, hist, (u64)256 * nb, nullptr); if (rc) return rc;
-        StageTimer ts(ctx, LRGE_T_RS_SCATTER);
-        hipLaunchKernelGGL((k_rs_scatter<false, RS_MODE_PAIRS>), dim3(nb), dim3(RS_THREADS), 0, ctx->stream, kx, ky, k1, v1, n, 0, nb, hist, (const SegTile *)nullptr,
-                           UnpackParams{0, 0, 0, 255});
+        ALLOC_OR_FAIL(tile_desc, sc, u32, (size_t)nb * 8 + 8);
+        hipLaunchKernelGGL(k_tile_desc, dim3((u32)div_up(nb, 256)), dim3(256), 0, ctx->stream, (const u32 *)ws.offs, ws.n_waves, (u32)n, nb, tile_desc);
         KCHK(ctx);
-        ts.stop();
-        ctx->counters[LRGE_C_RS_SCATTER_LAUNCHES] += 1; ctx->counters[LRGE_C_RS_SCATTER_ITEMS] += n; ctx->counters[LRGE_C_RS_SCATTER_BYTES] += 32 * n;
-    }
+        const SlotSrc src{ws.wx, ws.offs, tile_chunk, ws.n_waves, ws.cap, (u32)n, ws.wd, tile_desc};
+        rc = rs_pass<false, RS_MODE_DW, true>(ctx, sc, hist, nb, nullptr, HistSrc{nullptr, 8, 1u}, nullptr, nullptr, m1, k1, n, 8, UnpackParams(), n, 24, src);
+        if (rc) return rc;
+        sc.drop(tile_chunk); sc.drop(tile_desc);
+    } else if (segw) rc = rs_pass<false, RS_MODE_DW>(ctx, sc, hist, nb, nullptr, HistSrc{(const u64 *)in.dig, 8, 1u}, (const u64 *)in.dig, in.x, m1, k1, n, 8, UnpackParams(), n, 24);
+    else rc = rs_pass<false, RS_MODE_PAIRS>(ctx, sc, hist, nb, nullptr, HistSrc{in.x, 0}, in.x, in.y, k1, m1, n, 0, UnpackParams(), n, 32);
+    if (rc) return rc;
     u32 *d_b = sc.get<u32>(n_seg + 1), *d_c = e ? sc.get<u32>(257) : nullptr, *d_tb = sc.get<u32>(n_seg + 1);
     if (!d_b || !d_tb || (e && !d_c)) return LRGE_ERR_DEVICE;
     u32 *coarse = e ? d_c : d_b;                       // the 256 segments of pass A
     hipLaunchKernelGGL(k_gather_strided_u32, dim3(1), dim3(256), 0, ctx->stream, hist, (u64)nb, 256u, coarse);
     hipLaunchKernelGGL(k_store_u32, dim3(1), dim3(1), 0, ctx->stream, coarse + 256, (u32)n);
     KCHK(ctx);
-    ALLOC_OR_FAIL(d_tiles, sc, u32, (size_t)max_tiles * (sizeof(SegTile) / 4) + 8);
-    u32 cur_tiles = nb + 256;                          // the grid of the passes over `cur_seg` segments
-    hipLaunchKernelGGL(k_seg_tile_scan, dim3(1), dim3(1024), 0, ctx->stream, (const u32 *)coarse, 256u, d_tb);
-    hipLaunchKernelGGL(k_seg_tile_fill, dim3(div_up(cur_tiles, 256)), dim3(256), 0, ctx->stream, (const u32 *)coarse, (const u32 *)d_tb, 256u, cur_tiles, (SegTile *)d_tiles);
-    KCHK(ctx);
-    u64 *pi = kx, *po = ky;          // (the sketch's pair buffers are free once pass A has read them: they carry the packed words)
-    if (e) {
-        // ---- pass A2: inside every segment by q, packing ----
-        const u32 qm = (1u << e) - 1;
-        hipLaunchKernelGGL(k_rs_hist<true>, dim3(cur_tiles), dim3(RS_THREADS), 0, ctx->stream, k1, n, 16 - (int)e, cur_tiles, hist, (const SegTile *)d_tiles, qm);
-        KCHK(ctx);
-        int rc = scan_exclusive_u32(ctx, sc, hist, hist, (u64)256 * cur_tiles, nullptr); if (rc) return rc;
-        hipLaunchKernelGGL(k_seg_fine_starts, dim3(div_up(n_seg + 1, 256)), dim3(256), 0, ctx->stream, (const u32 *)hist, (const u32 *)coarse, (const u32 *)d_tb, e, (u32)n, d_b);
-        KCHK(ctx);
-        {
-            StageTimer ts(ctx, LRGE_T_RS_SCATTER);
-            const UnpackParams nq = nd_of(0);
-            hipLaunchKernelGGL((k_rs_scatter<true, RS_MODE_PACKQ>), dim3(cur_tiles), dim3(RS_THREADS), 0, ctx->stream, k1, v1, pi, (u64 *)nullptr, n, 16 - (int)e, cur_tiles, hist,
-                               (const SegTile *)d_tiles, UnpackParams{ybits, pos1, e, qm, (u32)nbits, nq.nd_out, nq.nd_shift, nq.nd_mask});
-            nd_valid = nq.nd_out != nullptr;
-            KCHK(ctx);
-            ts.stop();
-        }
-        ctx->counters[LRGE_C_RS_SCATTER_LAUNCHES] += 1; ctx->counters[LRGE_C_RS_SCATTER_ITEMS] += n; ctx->counters[LRGE_C_RS_SCATTER_BYTES] += 24 * n;
-        cur_tiles = max_tiles;
-        hipLaunchKernelGGL(k_seg_tile_scan, dim3(1), dim3(1024), 0, ctx->stream, (const u32 *)d_b, n_seg, d_tb);
-        hipLaunchKernelGGL(k_seg_tile_fill, dim3(div_up(cur_tiles, 256)), dim3(256), 0, ctx->stream, (const u32 *)d_b, (const u32 *)d_tb, n_seg, cur_tiles, (SegTile *)d_tiles);
-        KCHK(ctx);
+    ALLOC_OR_FAIL(d_tiles, sc, SegTile, (size_t)max_tiles + 1);
+    u32 cur_tiles = nb + 256;                          // the grid of the passes over the current segments
+    rc = seg_tiles_build(ctx, coarse, 256u, d_tb, cur_tiles, d_tiles); if (rc) return rc;
+    // the packing pass (A2, or the first LSD pass) reads (pk, pv) and writes the words to pi; the LSD passes behind it go between pi and po
+    const u64 *pk = segw ? m1 : k1, *pv = segw ? k1 : m1;      // pairs: (hash, y); SEGW: (DIG, word)
+    const u32 pack_bytes = segw ? 20 : 24;
+    u64 *pi = in.x, *po = segw ? k1 : in.y;           // (the sketch's buffers are free once pass A has read them; k1 once the packing pass has)
+    if (in.ws) {        // the slots have been read: they go, the second word buffer comes (in stream order: the arena recycles on ctx->stream)
+        sc.drop(in.ws->wx); sc.drop(in.ws->wd); sc.drop(in.ws->cnt); sc.drop(in.ws->offs);
+        pi = sc.get<u64>(n + 1);
+        if (!pi) return LRGE_ERR_DEVICE;
     }
-    // ---- the digits of R, least significant first (e == 0: the first of them reads the pairs and packs) ----
+    if (e) {
+        // ---- pass A2: inside every segment by q, the top e bits of b1, packing ----
+        const int qshift = (segw ? 8 : 16) - (int)e;          // (of the DIG member; of the hash)
+        const UnpackParams up = params((1u << e) - 1, 0, true, e);
+        auto fine_starts = [&]() -> int {
+            hipLaunchKernelGGL(k_seg_fine_starts, dim3(div_up(n_seg + 1, 256)), dim3(256), 0, ctx->stream, (const u32 *)hist, (const u32 *)coarse, (const u32 *)d_tb, e, (u32)n, d_b);
+            KCHK(ctx);
+            return LRGE_OK;
+        };
+        rc = segw ? rs_pass<true, RS_MODE_DWQ>(ctx, sc, hist, cur_tiles, d_tiles, HistSrc{pk, qshift, 1u}, pk, pv, pi, nullptr, n, qshift, up, n, pack_bytes, SlotSrc(), 0, fine_starts)
+                  : rs_pass<true, RS_MODE_PACKQ>(ctx, sc, hist, cur_tiles, d_tiles, HistSrc{pk, qshift}, pk, pv, pi, nullptr, n, qshift, up, n, pack_bytes, SlotSrc(), 0, fine_starts);
+        if (rc) return rc;
+        db.ran(up);
+        cur_tiles = max_tiles;
+        rc = seg_tiles_build(ctx, d_b, n_seg, d_tb, cur_tiles, d_tiles); if (rc) return rc;
+    }
+    // ---- the digits of R, least significant first (e == 0: the first of them reads the entries and packs) ----
     for (int j = 0; j < passes; ++j) {
         const bool first = !e && j == 0;
-        const int w = nr - 8 * j >= 8 ? 8 : nr - 8 * j;
-        const u32 dm = (1u << w) - 1u;
         const int pshift = (int)ybits + 8 * j;                           // where digit j sits in the packed word
-        if (first) hipLaunchKernelGGL(k_rs_hist<true>, dim3(cur_tiles), dim3(RS_THREADS), 0, ctx->stream, k1, n, 0, cur_tiles, hist, (const SegTile *)d_tiles, dm, SlotSrc(), 0u, (u32)nbits);
-        else if (nd_valid) hipLaunchKernelGGL(k_rs_hist<true>, dim3(cur_tiles), dim3(RS_THREADS), 0, ctx->stream, (const u64 *)nd, n, 0, cur_tiles, hist, (const SegTile *)d_tiles, dm, SlotSrc(), 0u, 0u, 2u);
-        else hipLaunchKernelGGL(k_rs_hist<true>, dim3(cur_tiles), dim3(RS_THREADS), 0, ctx->stream, pi, n, pshift, cur_tiles, hist, (const SegTile *)d_tiles, dm);
-        KCHK(ctx);
-        int rc = scan_exclusive_u32(ctx, sc, hist, hist, (u64)256 * cur_tiles, nullptr); if (rc) return rc;
-        StageTimer ts(ctx, LRGE_T_RS_SCATTER);
-        const UnpackParams nq = nd_of(j + 1);
-        if (first) hipLaunchKernelGGL((k_rs_scatter<true, RS_MODE_PACK>), dim3(cur_tiles), dim3(RS_THREADS), 0, ctx->stream, k1, v1, pi, (u64 *)nullptr, n, pshift, cur_tiles, hist,
-                                      (const SegTile *)d_tiles, UnpackParams{ybits, pos1, 0, dm, (u32)nbits, nq.nd_out, nq.nd_shift, nq.nd_mask});
-        else hipLaunchKernelGGL((k_rs_scatter<true, RS_MODE_KEYS>), dim3(cur_tiles), dim3(RS_THREADS), 0, ctx->stream, pi, (const u64 *)nullptr, po, (u64 *)nullptr, n, pshift, cur_tiles,
-                                hist, (const SegTile *)d_tiles, UnpackParams{0, 0, 0, dm, 0, nq.nd_out, nq.nd_shift, nq.nd_mask});
-        KCHK(ctx);
-        ts.stop();
-        nd_valid = nq.nd_out != nullptr;
-        ctx->counters[LRGE_C_RS_SCATTER_LAUNCHES] += 1; ctx->counters[LRGE_C_RS_SCATTER_ITEMS] += n; ctx->counters[LRGE_C_RS_SCATTER_BYTES] += (first ? 24 : 16) * n;
+        const UnpackParams up = params(digit_mask(nr - 8 * j), j + 1, first);
+        // (first, pairs: the digit is cut from the hashes' significance strings.  SEGW: digit 0 of R lies in the word's own hash field -- nbits - 16 >= 8
+        // is the caller's condition -- so the histogram reads the words)
+        if (first && segw) rc = rs_pass<true, RS_MODE_DWP>(ctx, sc, hist, cur_tiles, d_tiles, HistSrc{pv, pshift}, pk, pv, pi, nullptr, n, pshift, up, n, pack_bytes);
+        else if (first) rc = rs_pass<true, RS_MODE_PACK>(ctx, sc, hist, cur_tiles, d_tiles, HistSrc{pk, 0, 0u, (u32)nbits}, pk, pv, pi, nullptr, n, pshift, up, n, pack_bytes);
+        else rc = rs_pass<true, RS_MODE_KEYS>(ctx, sc, hist, cur_tiles, d_tiles, db.hist(pi, pshift), pi, nullptr, po, nullptr, n, pshift, up, n, 16);
+        if (rc) return rc;
+        db.ran(up);
         if (!first) { u64 *t = pi; pi = po; po = t; }
     }
     if (d_c) sc.drop(d_c);
     sc.drop(d_tb);
-    if (nd) sc.drop(nd);
-    sc.drop(hist); sc.drop((u32 *)d_tiles);
+    db.drop(sc);
+    sc.drop(hist); sc.drop(d_tiles);
     *res = pi; *d_seg_start = d_b;
-    return LRGE_OK;
-}
-
-// The same sort over SEGW entries (RS_MODE_DW* above): wx = the words, dy = the u32 DIG array, both as the sketch left them; k1 / d1 =
-// buffers of n + 1 u64 / u32.  Pass A moves 12 bytes per entry instead of 16 (and its histogram reads 4 instead of 8), pass A2 / the
-// first LSD pass reads 12 instead of 16; from there on the entries are the packed words of index_sort_segpacked, bit for bit.
-// WaveSrc (round 6): pass A reads the wave-dense sketch's slots (k_sketch.h: k_sketch_wave) in place of the dense (wx, dy) arrays -- through
-// the slot-source form of its two kernels (SlotSrc) --, DIG members of 16 bits (d1 is then a u16 array too).  The slots are
-// released as soon as pass A has read them and the second word buffer is taken in their place; *spare = the word buffer that does not
-// hold the result.
-struct WaveSrc { u64 *wx; wdig_t *wd; u32 *cnt, *offs; u32 n_waves, cap; };      // offs: exclusive scan of cnt
-static int index_sort_segw(lrge_hip_ctx *ctx, Scratch &sc, u64 *wx, u32 *dy, u64 *k1, u32 *d1, u64 n, int nbits, u32 ybits, u32 pos1, u32 e,
-                           u64 **res, u32 **d_seg_start, const WaveSrc *ws = nullptr, u64 **spare = nullptr) {
-    (void)pos1;
-    const u32 dig16 = (ws && sizeof(wdig_t) == 2) ? 1u : 0u, dkey = dig16 ? 3u : 1u;      // width of the DIG arrays (UnpackParams::dig16; k_rs_hist's key32)
-    const int nr = nbits - 8 - (int)e, passes = (nr + 7) / 8;      // LSD passes over R
-    const u32 nb = (u32)div_up(n, RS_TILE), n_seg = 256u << e;
-    const u32 max_tiles = nb + n_seg;
-    ALLOC_OR_FAIL(hist, sc, u32, (u64)256 * (max_tiles + 1) + 256);
-    // next-pass digit bytes (UnpackParams::nd_out): every scatter that writes packed words also leaves the byte the NEXT pass ranks by, and
-    // that pass's histogram reads 1 byte per entry instead of 8 (option NO_DIGIT_BYTES: the histograms read the words, rounds 3-5)
-    u8 *nd = ctx->opt("NO_DIGIT_BYTES") ? nullptr : sc.get<u8>(n + 64);
-    if (!nd) { (void)hipGetLastError(); ctx->err.clear(); }
-    bool nd_valid = false;                             // nd holds the digits of the pass about to run
-    auto nd_of = [&](int j_next) -> UnpackParams {      // what the scatter in front of LSD pass j_next adds to its parameters
-        UnpackParams q{0, 0, 0, 0, 0, nullptr, 0, 0};
-        if (nd && j_next < passes) { const int w_ = nr - 8 * j_next >= 8 ? 8 : nr - 8 * j_next; q.nd_out = nd; q.nd_shift = ybits + 8u * (u32)j_next; q.nd_mask = (1u << w_) - 1u; }
-        return q;
-    };
-    // ---- pass A: (DIG, word) by b0 ----
-    const u32 nbA = nb;
-    if (ws) {
-        // dense tiles of RS_TILE entries over the VIRTUAL dense array: entry i lives in the wavefront slot v = the last one with offs[v] <= i,
-        // at index v * cap + i - offs[v] (k_prims.h: SlotSrc / rs_for_slot_items; a tile spans two or three slots of ~2 000-2 800 entries).
-        // (One tile per slot -- half-full tiles, twice as many, digit runs of 8 entries -- took 34 ms per part instead of 16.)
-        ALLOC_OR_FAIL(tile_chunk, sc, u32, (size_t)nb + 1);
-        hipLaunchKernelGGL(k_tile_chunks, dim3((u32)div_up(nb, 256)), dim3(256), 0, ctx->stream, (const u32 *)ws->offs, ws->n_waves, nb, tile_chunk);
-        KCHK(ctx);
-        ALLOC_OR_FAIL(tile_desc, sc, u32, (size_t)nb * 8 + 8);
-        hipLaunchKernelGGL(k_tile_desc, dim3((u32)div_up(nb, 256)), dim3(256), 0, ctx->stream, (const u32 *)ws->offs, ws->n_waves, (u32)n, nb, tile_desc);
-        KCHK(ctx);
-        SlotSrc src{ws->wx, ws->offs, tile_chunk, ws->n_waves, ws->cap, (u32)n, ws->wd, tile_desc};
-        hipLaunchKernelGGL((k_rs_hist<false, 8, true>), dim3(nb), dim3(RS_THREADS), 0, ctx->stream, (const u64 *)nullptr, n, 8, nb, hist, (const SegTile *)nullptr, 255u, src, 0u, 0u, dkey);
-        KCHK(ctx);
-        int rc = scan_exclusive_u32(ctx, sc, hist, hist, (u64)256 * nb, nullptr); if (rc) return rc;
-        StageTimer ts(ctx, LRGE_T_RS_SCATTER);
-        hipLaunchKernelGGL((k_rs_scatter<false, RS_MODE_DW, 8, true>), dim3(nb), dim3(RS_THREADS), 0, ctx->stream, (const u64 *)nullptr, (const u64 *)nullptr, (u64 *)d1, k1, n, 8, nb, hist,
-                           (const SegTile *)nullptr, UnpackParams{0, 0, 0, 255, 0, nullptr, 0, 0, dig16}, src);
-        KCHK(ctx);
-        ts.stop();
-        ctx->counters[LRGE_C_RS_SCATTER_LAUNCHES] += 1; ctx->counters[LRGE_C_RS_SCATTER_ITEMS] += n; ctx->counters[LRGE_C_RS_SCATTER_BYTES] += (dig16 ? 20 : 24) * n;
-        sc.drop(tile_chunk); sc.drop(tile_desc);
-    } else {
-        hipLaunchKernelGGL(k_rs_hist<false>, dim3(nb), dim3(RS_THREADS), 0, ctx->stream, (const u64 *)dy, n, 8, nb, hist, (const SegTile *)nullptr, 255u, SlotSrc(), 0u, 0u, 1u);
-        KCHK(ctx);
-        int rc = scan_exclusive_u32(ctx, sc, hist, hist, (u64)256 * nb, nullptr); if (rc) return rc;
-        StageTimer ts(ctx, LRGE_T_RS_SCATTER);
-        hipLaunchKernelGGL((k_rs_scatter<false, RS_MODE_DW>), dim3(nb), dim3(RS_THREADS), 0, ctx->stream, (const u64 *)dy, (const u64 *)wx, (u64 *)d1, k1, n, 8, nb, hist,
-                           (const SegTile *)nullptr, UnpackParams{0, 0, 0, 255, 0});
-        KCHK(ctx);
-        ts.stop();
-        ctx->counters[LRGE_C_RS_SCATTER_LAUNCHES] += 1; ctx->counters[LRGE_C_RS_SCATTER_ITEMS] += n; ctx->counters[LRGE_C_RS_SCATTER_BYTES] += 24 * n;
-    }
-    u32 *d_b = sc.get<u32>(n_seg + 1), *d_c = e ? sc.get<u32>(257) : nullptr, *d_tb = sc.get<u32>(n_seg + 1);
-    if (!d_b || !d_tb || (e && !d_c)) return LRGE_ERR_DEVICE;
-    u32 *coarse = e ? d_c : d_b;                       // the 256 segments of pass A
-    hipLaunchKernelGGL(k_gather_strided_u32, dim3(1), dim3(256), 0, ctx->stream, hist, (u64)nbA, 256u, coarse);
-    hipLaunchKernelGGL(k_store_u32, dim3(1), dim3(1), 0, ctx->stream, coarse + 256, (u32)n);
-    KCHK(ctx);
-    ALLOC_OR_FAIL(d_tiles, sc, u32, (size_t)max_tiles * (sizeof(SegTile) / 4) + 8);
-    u32 cur_tiles = nb + 256;
-    hipLaunchKernelGGL(k_seg_tile_scan, dim3(1), dim3(1024), 0, ctx->stream, (const u32 *)coarse, 256u, d_tb);
-    hipLaunchKernelGGL(k_seg_tile_fill, dim3(div_up(cur_tiles, 256)), dim3(256), 0, ctx->stream, (const u32 *)coarse, (const u32 *)d_tb, 256u, cur_tiles, (SegTile *)d_tiles);
-    KCHK(ctx);
-    if (ws) {        // the slots have been read: they go, the second word buffer comes (in stream order: the arena recycles on ctx->stream)
-        sc.drop(ws->wx); sc.drop(ws->wd); sc.drop(ws->cnt); sc.drop(ws->offs);
-        wx = sc.get<u64>(n + 1);
-        if (!wx) return LRGE_ERR_DEVICE;
-    }
-    u64 *pi = wx, *po = k1;          // (the sketch's word buffer is free once pass A has read it; k1 once the packing pass has)
-    if (e) {
-        // ---- pass A2: inside every segment by the top e bits of b1, packing ----
-        const u32 qm = (1u << e) - 1;
-        hipLaunchKernelGGL(k_rs_hist<true>, dim3(cur_tiles), dim3(RS_THREADS), 0, ctx->stream, (const u64 *)d1, n, 8 - (int)e, cur_tiles, hist, (const SegTile *)d_tiles, qm, SlotSrc(), 0u, 0u, dkey);
-        KCHK(ctx);
-        int rc = scan_exclusive_u32(ctx, sc, hist, hist, (u64)256 * cur_tiles, nullptr); if (rc) return rc;
-        hipLaunchKernelGGL(k_seg_fine_starts, dim3(div_up(n_seg + 1, 256)), dim3(256), 0, ctx->stream, (const u32 *)hist, (const u32 *)coarse, (const u32 *)d_tb, e, (u32)n, d_b);
-        KCHK(ctx);
-        {
-            StageTimer ts(ctx, LRGE_T_RS_SCATTER);
-            const UnpackParams nq = nd_of(0);
-            hipLaunchKernelGGL((k_rs_scatter<true, RS_MODE_DWQ>), dim3(cur_tiles), dim3(RS_THREADS), 0, ctx->stream, (const u64 *)d1, (const u64 *)k1, pi, (u64 *)nullptr, n, 8 - (int)e, cur_tiles, hist,
-                               (const SegTile *)d_tiles, UnpackParams{ybits, pos1, e, qm, (u32)nbits, nq.nd_out, nq.nd_shift, nq.nd_mask, dig16});
-            nd_valid = nq.nd_out != nullptr;
-            KCHK(ctx);
-            ts.stop();
-        }
-        ctx->counters[LRGE_C_RS_SCATTER_LAUNCHES] += 1; ctx->counters[LRGE_C_RS_SCATTER_ITEMS] += n; ctx->counters[LRGE_C_RS_SCATTER_BYTES] += 20 * n;
-        cur_tiles = max_tiles;
-        hipLaunchKernelGGL(k_seg_tile_scan, dim3(1), dim3(1024), 0, ctx->stream, (const u32 *)d_b, n_seg, d_tb);
-        hipLaunchKernelGGL(k_seg_tile_fill, dim3(div_up(cur_tiles, 256)), dim3(256), 0, ctx->stream, (const u32 *)d_b, (const u32 *)d_tb, n_seg, cur_tiles, (SegTile *)d_tiles);
-        KCHK(ctx);
-    }
-    // ---- the digits of R, least significant first (e == 0: the first of them reads (DIG, word) and packs) ----
-    for (int j = 0; j < passes; ++j) {
-        const bool first = !e && j == 0;
-        const int w = nr - 8 * j >= 8 ? 8 : nr - 8 * j;
-        const u32 dm = (1u << w) - 1u;
-        const int pshift = (int)ybits + 8 * j;                           // where digit j sits in the packed word
-        // (first: digit 0 of R lies in the word's own hash field -- nbits - 16 >= 8 is the caller's condition -- so the histogram reads the words)
-        if (!first && nd_valid) hipLaunchKernelGGL(k_rs_hist<true>, dim3(cur_tiles), dim3(RS_THREADS), 0, ctx->stream, (const u64 *)nd, n, 0, cur_tiles, hist, (const SegTile *)d_tiles, dm, SlotSrc(), 0u, 0u, 2u);
-        else hipLaunchKernelGGL(k_rs_hist<true>, dim3(cur_tiles), dim3(RS_THREADS), 0, ctx->stream, first ? k1 : pi, n, pshift, cur_tiles, hist, (const SegTile *)d_tiles, dm);
-        KCHK(ctx);
-        int rc = scan_exclusive_u32(ctx, sc, hist, hist, (u64)256 * cur_tiles, nullptr); if (rc) return rc;
-        StageTimer ts(ctx, LRGE_T_RS_SCATTER);
-        const UnpackParams nq = nd_of(j + 1);
-        if (first) hipLaunchKernelGGL((k_rs_scatter<true, RS_MODE_DWP>), dim3(cur_tiles), dim3(RS_THREADS), 0, ctx->stream, (const u64 *)d1, (const u64 *)k1, pi, (u64 *)nullptr, n, pshift, cur_tiles, hist,
-                                      (const SegTile *)d_tiles, UnpackParams{ybits, pos1, 0, dm, (u32)nbits, nq.nd_out, nq.nd_shift, nq.nd_mask, dig16});
-        else hipLaunchKernelGGL((k_rs_scatter<true, RS_MODE_KEYS>), dim3(cur_tiles), dim3(RS_THREADS), 0, ctx->stream, pi, (const u64 *)nullptr, po, (u64 *)nullptr, n, pshift, cur_tiles,
-                                hist, (const SegTile *)d_tiles, UnpackParams{0, 0, 0, dm, 0, nq.nd_out, nq.nd_shift, nq.nd_mask});
-        KCHK(ctx);
-        ts.stop();
-        nd_valid = nq.nd_out != nullptr;
-        ctx->counters[LRGE_C_RS_SCATTER_LAUNCHES] += 1; ctx->counters[LRGE_C_RS_SCATTER_ITEMS] += n; ctx->counters[LRGE_C_RS_SCATTER_BYTES] += (first ? 20 : 16) * n;
-        if (!first) { u64 *t = pi; pi = po; po = t; }
-    }
-    if (d_c) sc.drop(d_c);
-    sc.drop(d_tb);
-    if (nd) sc.drop(nd);
-    sc.drop(hist); sc.drop((u32 *)d_tiles);
-    *res = pi; *d_seg_start = d_b;
-    if (spare) *spare = po;
+    // what does not hold the result goes: the other word buffer, the input's second member or (pairs) k1, and m1
+    sc.drop(po);
+    if (segw) { if (in.dig) sc.drop(in.dig); } else sc.drop(k1);
+    sc.drop(m1);
     return LRGE_OK;
 }

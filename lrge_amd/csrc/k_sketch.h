@@ -495,7 +495,7 @@ __global__ __launch_bounds__(SK_THREADS) void k_sketch_count(const u64 *__restri
 // one, every 32-byte sector reaches HBM as four partial writes (measured 4x the bytes).  The last <= 4 are
 // kept in registers and leave as one sector-aligned 32-byte run per array whenever the output index
 // reaches a multiple of 4; only the head and the tail of the lane's range are written singly.
-// PK == 2 (index only, "SEGW": round 5): the entry as the segment-packed index sort wants it (k_prims.h, index_sort_segw) -- out_x gets
+// PK == 2 (index only, "SEGW": round 5): the entry as the segment-packed index sort wants it (k_prims.h, index_sort_seg) -- out_x gets
 // one word, [the low 2k - 16 bits of the hash's significance string | rid | pos << 1 | strand] (pk_ybits = the width of the y field),
 // and out_y, read as a u32 ARRAY, the top 16 bits of that string: the two digits the sort's first two passes order by.  12 bytes per
 // entry instead of the pair's 16 through the slots, the compaction and those two passes.
@@ -590,7 +590,7 @@ __global__ __launch_bounds__(SK_THREADS) void k_sketch_direct(const u64 *__restr
 // WAVEFRONT owns a slot -- room for `cap` entries behind its 64 chunks -- and fills it densely: whenever some of its lanes reach an
 // emission site of the state machine together, one ballot ranks them, the wavefront's counter (LDS, wavefront-scope atomics: lanes that sit at other
 // program points must see every update) moves on by their number, and they write consecutive entries -- 8-byte words (and, PK == 2, the
-// 16-bit digit pair) in runs that the L2 combines into whole lines.  No gaps inside a slot, `wave_cnt[wave]` entries in it: the index
+// digit pair, a u32) in runs that the L2 combines into whole lines.  No gaps inside a slot, `wave_cnt[wave]` entries in it: the index
 // sort's first pass reads the slots through its slot-source form (k_prims.h: SlotSrc, rs_for_slot_items) and no compaction runs.
 // The entries of a slot come in the order the lanes EMIT them, not in read order -- inside 8 192 bases.  The index does not care: the
 // sort is by hash, a key's position list is only ever expanded into anchors that are sorted by position again (k_seed.h), and
@@ -601,7 +601,7 @@ template <int K, int W, bool HPC, int PK>
 __global__ __launch_bounds__(SK_THREADS) void k_sketch_wave(const u64 *__restrict__ pack, const u32 *__restrict__ nmask,
                                                            const u64 *__restrict__ woff, const u32 *__restrict__ lens,
                                                            ChunkMap cm, u32 n_chunks, u32 *__restrict__ wave_cnt, u32 *__restrict__ overflow,
-                                                           u64 *__restrict__ out_x, wdig_t *__restrict__ out_d, u32 pk_pos1, u32 pk_ybits,
+                                                           u64 *__restrict__ out_x, u32 *__restrict__ out_d, u32 pk_pos1, u32 pk_ybits,
                                                            u32 cap, u32 c_base /* a multiple of 64 */) {
     static_assert(PK == 1 || PK == 2, "index entries only: packed words, or SEGW words + digit pairs");
     __shared__ u32 s_cnt[SK_THREADS / 64];
@@ -627,7 +627,7 @@ __global__ __launch_bounds__(SK_THREADS) void k_sketch_wave(const u64 *__restric
                 else {
                     const u64 S = hash_to_sig(x >> 8, 2 * K);
                     out_x[sbase + idx] = (S & ((1ULL << (2 * K - 16)) - 1)) << pk_ybits | (y >> 32) << pk_pos1 | (u64)(u32)y;
-                    out_d[sbase + idx] = (wdig_t)(S >> (2 * K - 16));
+                    out_d[sbase + idx] = (u32)(S >> (2 * K - 16));
                 }
             }
         });

@@ -1,6 +1,6 @@
 """Plain numpy models of the primitives in lrge_amd/csrc/k_prims.h -- the exclusive scan, the stable LSD radix sorts, the unpack of
-packed anchors, the slot gather, the run heads, hash_to_sig / sig_to_hash -- and the case families that tests/test_gpu_prims.py runs on
-the device.  The models know nothing of tiles, wavefronts or LDS.  Every model takes the name of a NEAR MISS (a plausible wrong
+packed anchors, the slot gather, the segment-packed index sort, the run heads, hash_to_sig / sig_to_hash -- and the case families that
+tests/test_gpu_prims.py runs on the device.  The models know nothing of tiles, wavefronts or LDS.  Every model takes the name of a NEAR MISS (a plausible wrong
 kernel); tests/test_prims_ref.py proves on the CPU that each family holds a case on which the near miss and the truth differ, so that
 the device comparison could tell them apart.  No wrong kernel ever runs on a GPU."""
 import numpy as np
@@ -217,6 +217,60 @@ def sig_to_hash(s, nbits):
         h |= (s & 0xff) << (8 * j)
         s >>= 8
     return h
+
+
+# ------------------------------------------------------------------------------------------
+# the segment-packed index sort: entries (hash h, y = rid << 32 | pos << 1 | strand) in, one packed word per entry out
+# ------------------------------------------------------------------------------------------
+def sig_of(h, nbits):
+    """hash_to_sig over an array"""
+    h = u64(h)
+    m = (nbits + 7) // 8
+    tb = nbits - 8 * (m - 1)
+    s = np.zeros(h.size, dtype=np.uint64)
+    for j in range(m - 1):
+        s = shl(s, 8) | (shr(h, 8 * j) & U64(0xff))
+    return shl(s, tb) | (shr(h, 8 * (m - 1)) & U64(0xff))
+
+
+def y_fields(y, pos1):
+    y = u64(y)
+    return shr(y, 32), y & U64(mask(pos1))
+
+
+def segw_entries(h, y, nbits, ybits, pos1):
+    """(word, DIG) of the SEGW form: the string's top 16 bits apart, the rest on top of the squeezed position"""
+    S = sig_of(h, nbits)
+    rid, low = y_fields(y, pos1)
+    return u64(shl(S & U64(mask(nbits - 16)), ybits) | shl(rid, pos1) | low), shr(S, nbits - 16).astype(np.uint32)
+
+
+INDEX_SORT_MISSES = ("unstable", "raw_hash_R", "e_plus_1", "e_minus_1", "rid_at_32", "no_last_start", "a2_low_bits")
+
+
+def index_sort(h, y, nbits, ybits, pos1, e, miss=None):
+    """(words, seg_start): the words R << ybits | rid << pos1 | low in stable order of the significance string S, R its low
+    nbits - 8 - e bits; seg_start[s] = entries whose segment S >> (nbits - 8 - e) is smaller, seg_start[256 << e] = n"""
+    h, y = u64(h), u64(y)
+    if miss == "e_plus_1":
+        e += 1
+    if miss == "e_minus_1":
+        e = max(0, e - 1)
+    nr = nbits - 8 - e
+    S = sig_of(h, nbits)
+    seg = shr(S, nr)
+    R = (h if miss == "raw_hash_R" else S) & U64(mask(nr))
+    rid, low = y_fields(y, pos1)
+    word = shl(R, ybits) | (shl(rid, 32) if miss == "rid_at_32" else shl(rid, pos1)) | low
+    key = S
+    if miss == "a2_low_bits":           # pass A2 ranks by the low e bits of the second byte b1 = bits [nbits - 16, nbits - 8) of S
+        seg = shl(shr(S, nbits - 8), e) | (shr(S, nbits - 16) & U64(mask(e)))
+        key = shl(seg, nr) | R
+    order = stable_order(key, miss == "unstable")
+    starts = np.searchsorted(seg[order], np.arange((256 << e) + 1, dtype=np.uint64), side="left").astype(np.uint32)
+    if miss == "no_last_start":
+        starts[-1] = 0
+    return u64(word[order]), starts
 
 
 # ==========================================================================================
@@ -450,6 +504,90 @@ def head_boundaries(keys, shift, n_seg, seed=11):
     b[0] = 0
     b[-1] = n
     return b.astype(np.uint32)
+
+
+INDEX_N = (1, 255, 4095, 4096, 4097, 3 * 4096 + 5, 17 * 4096 - 5)
+INDEX_NBITS = (24, 30, 38)
+INDEX_E = (0, 1, 6, 7)
+HASH_KINDS = ("uniform", "one_b0", "one_per_segment", "all_equal", "a2_bits_only", "below_a2_only")
+
+
+def index_layout(nbits, e, tight):
+    """(ybits, pos1): the tight word has no bit to spare, nbits - 8 - e + ybits == 64; the loose one leaves the top unused.  The read
+    number takes ybits - pos1 <= 32 bits, and pos1 < 32, so that a read number left at bit 32 shows."""
+    ybits = 64 - (nbits - 8 - e) if tight else 30
+    return ybits, max(12, ybits - 32)
+
+
+def index_entries(kind, n, nbits, ybits, pos1, e, seed=13):
+    """(h, y): n hashes of the given kind and positions that hold the input index (stability shows) under random bits up to the top of
+    the read number"""
+    rng = np.random.Generator(np.random.PCG64(seed * 7919 + n * 31 + nbits * 5 + e))
+    i = np.arange(n, dtype=np.uint64)
+    u = rng.integers(0, 1 << 62, n, dtype=np.uint64)
+    base = U64(0x2A5A5A5A5A5A5A5A)
+    if kind == "uniform":
+        h = u
+    elif kind == "one_b0":                  # one of pass A's segments spans every tile, 255 are empty
+        h = (u & ~U64(0xff)) | U64(0x5A)
+    elif kind == "one_per_segment":         # n < 256 distinct low bytes in shuffled order: empty segments between
+        assert n < 256
+        b0 = rng.permutation(256)[:n].astype(np.uint64)
+        h = (u & ~U64(0xff)) | b0
+    elif kind == "all_equal":
+        h = np.full(n, base, dtype=np.uint64)
+    elif kind == "a2_bits_only":            # equal but for the top e bits of the second byte: what pass A2 ranks by
+        m = U64(mask(e) << (16 - e))
+        h = (base & ~m) | (u & m)
+    elif kind == "below_a2_only":           # equal but for the bits of the second byte below those: the top of R
+        m = U64(mask(8 - e) << 8)
+        h = (base & ~m) | (u & m)
+    else:
+        raise ValueError(kind)
+    h &= U64(mask(nbits))
+    rbits = ybits - pos1
+    low = i & U64(mask(pos1))
+    rid = (shr(i, pos1) | shl(rng.integers(0, 1 << 32, n, dtype=np.uint64), 5)) & U64(mask(rbits))       # (n < 2^17, pos1 >= 12: five bits hold the rest of i)
+    return u64(h), u64(shl(rid, 32) | low)
+
+
+INDEX_GROUPS = ("layouts", "sizes") + HASH_KINDS
+
+
+def index_cases(group):
+    """(kind, n, nbits, e, tight) of one group: every nbits x e x layout at a few tiles; every size (with and without pass A2, the narrowest
+    and the widest R); every hash kind at every e"""
+    if group == "layouts":
+        return [("uniform", 3 * 4096 + 5, nbits, e, tight) for nbits in INDEX_NBITS for e in INDEX_E for tight in (False, True)]
+    if group == "sizes":
+        return [c for n in INDEX_N for c in (("uniform", n, 30, 0, False), ("uniform", n, 38, 6, True), ("all_equal", n, 24, 7, False))]
+    n = 255 if group == "one_per_segment" else 2 * 4096 + 5
+    return [c for e in INDEX_E for c in ((group, n, 38, e, False), (group, n, 24, e, True))]
+
+
+def index_forms(h, y, nbits, ybits, pos1, cap, counts):
+    """the same entries as the sort's three sources: the pairs, the dense SEGW arrays, the wave-dense slots (words, DIG members, counts)"""
+    w, d = segw_entries(h, y, nbits, ybits, pos1)
+    return (h, y), (w, d), (slots_fill(cap, counts, w), slots_fill(cap, counts, d.astype(np.uint64)).astype(np.uint32), np.asarray(counts, dtype=np.uint32))
+
+
+def wave_table_for(n, cap=2816, seed=21):
+    """per-wavefront counts of a wave-dense sketch that holds n entries: slots of `cap` (a multiple of 64), 2 000 to cap entries in
+    each, an empty wavefront now and then, the last one taking what is left"""
+    rng = np.random.Generator(np.random.PCG64(seed + n))
+    counts, left = [0], n
+    while left:
+        c = min(left, int(rng.integers(2000, cap + 1)))
+        counts.append(c)
+        left -= c
+        if rng.integers(0, 4) == 0:
+            counts.append(0)
+    return cap, np.array(counts + [0], dtype=np.uint32)
+
+
+def index_slot_tables():
+    """the chunk tables a wave-dense sketch could have left: cap a multiple of 64 and at most RS_TILE"""
+    return [t for t in slot_tables() if t[1] % 64 == 0 and t[1] <= RS_TILE]
 
 
 SIG_NBITS = (30, 38, 8, 9, 16, 17, 63)

@@ -1,12 +1,13 @@
 """The primitives of lrge_amd/csrc/k_prims.h against the plain models of tests/prims_ref.py, bit for bit, on the device: the exclusive scan
 (both levels, the vector and the scalar branches, k_scan_small's carry loop), radix_sort_pairs / radix_sort_keys (sizes around the tile and
 the XCD map, partial top digits, both digit orders, pass ranges, with and without next-pass digit bytes), the first pass from slots (descriptor,
-LDS-cached offsets, per-entry search), the packed segmented sort beside all three k_seg_sort_local variants, and the run heads with forced
-boundaries.  tools/prims_check.hip (lrge_amd/_lib/libprims_check.so) includes the product's header and launches exactly what the product
+LDS-cached offsets, per-entry search), the packed segmented sort beside all three k_seg_sort_local variants, the segment-packed index sort (index_sort_seg: pairs, dense SEGW
+entries and wave-dense slots give the same words and segment starts), and the run heads with forced boundaries.  tools/prims_check.hip (lrge_amd/_lib/libprims_check.so) includes the product's header and launches exactly what the product
 launches; values are input positions, so stability shows; every call also returns the primitive's code and whether the guard bands around
 its device buffers still hold their pattern.  tests/test_prims_ref.py proves on the CPU that these cases can tell near misses apart.
 
-Measured on one MI355X: the module's 53 tests take 2.6 s, the slowest of them 0.26 s (test_whole_sorts[sizes]; the two 134 MB scans 0.17 s each)."""
+Measured on one MI355X: the module's 71 tests take 3.1 s, the slowest of them 0.26 s (test_whole_sorts[sizes]; the two 134 MB scans 0.17 s each;
+the 18 index sort tests 0.5 s together, the slowest of those 0.14 s, test_index_sort[layouts])."""
 import ctypes as C
 import functools
 
@@ -40,6 +41,7 @@ class Prims:
         L.pc_sort_keys_from_slots.argtypes = [V, V, U3, U3, U6, I, I, I, I, S, V, V]
         L.pc_anchor_sort.argtypes = [V, U6, U6, I, U3, U3, U3, V, V, V, U3, U6, I, S, V, V, V]
         L.pc_heads.argtypes = [V, U6, U3, V, U3, I, V, V, V]
+        L.pc_index_sort.argtypes = [I, V, V, V, V, V, U3, U3, U6, I, U3, U3, U3, S, V, V, V]
         m = C.c_int(0)
         assert L.pc_init(C.byref(m)) == LRGE_OK, "no device"
         self.lsort_mask = m.value
@@ -93,6 +95,20 @@ class Prims:
                                    int(src_first), opts, _p(ok), _p(ov), C.byref(g))
         self._done(rc, g)
         return ok[:n_out], ov[:n_out]
+
+    def index_sort(self, form, n, nbits, ybits, pos1, e, x, y=None, dig=None, counts=None, cap=0, opts=None):
+        x = R.u64(x)
+        y = None if y is None else R.u64(y)
+        dig = None if dig is None else np.ascontiguousarray(dig, dtype=np.uint32)
+        offs = None
+        if counts is not None:
+            counts = np.ascontiguousarray(counts, dtype=np.uint32)
+            offs = np.concatenate([[0], np.cumsum(counts.astype(np.uint64))[:-1]]).astype(np.uint32)
+        words, starts, g = np.zeros(n, dtype=np.uint64), np.zeros((256 << e) + 1, dtype=np.uint32), C.c_int(0)
+        rc = self.L.pc_index_sort(form, _p(x), _p(y), _p(dig), _p(counts), _p(offs), 0 if counts is None else counts.size, cap, n, nbits, ybits, pos1, e, opts,
+                                  _p(words), _p(starts), C.byref(g))
+        self._done(rc, g)
+        return words, starts
 
     def heads(self, keys, shift, forced=None, use_async=False):
         keys = R.u64(keys)
@@ -253,6 +269,40 @@ def test_anchor_sorts_agree(pc, nbits):
         local, tiles, n_local = R.plan_anchor_sort(segs, lambda c: 0 if c <= 2048 else 1 if c <= 8192 and c % 2 else None)
         k, val = pc.anchor_sort(pk, n_out, nbits, local, tiles, n_local, src_first=True)
         same(k, want_k, (kind, "sparse keys")); same(val, want_v, (kind, "sparse values"))
+
+
+# ------------------------------------------------------------------------------------------
+# the segment-packed index sort: pairs, dense SEGW entries and wave-dense slots, with and without next-pass digit bytes
+# ------------------------------------------------------------------------------------------
+def _check_index_sort(pc, h, y, nbits, ybits, pos1, e, cap, counts, what):
+    n = h.size
+    want_w, want_s = R.index_sort(h, y, nbits, ybits, pos1, e)
+    (_, _), (w, d), (sw, sd, cnt) = R.index_forms(h, y, nbits, ybits, pos1, cap, counts)
+    for opts in (None, b"NO_DIGIT_BYTES"):
+        for form, got in (("pairs", pc.index_sort(0, n, nbits, ybits, pos1, e, h, y=y, opts=opts)),
+                          ("segw", pc.index_sort(1, n, nbits, ybits, pos1, e, w, dig=d, opts=opts)),
+                          ("wave", pc.index_sort(2, n, nbits, ybits, pos1, e, sw, dig=sd, counts=cnt, cap=cap, opts=opts))):
+            same(got[0], want_w, what + (form, opts, "words"))
+            same(got[1], want_s, what + (form, opts, "segment starts"))
+
+
+@pytest.mark.parametrize("group", R.INDEX_GROUPS)
+def test_index_sort(pc, group):
+    for case in R.index_cases(group):
+        kind, n, nbits, e, tight = case
+        ybits, pos1 = R.index_layout(nbits, e, tight)
+        h, y = R.index_entries(kind, n, nbits, ybits, pos1, e)
+        _check_index_sort(pc, h, y, nbits, ybits, pos1, e, *R.wave_table_for(n), case)
+
+
+@pytest.mark.parametrize("table", R.index_slot_tables(), ids=lambda t: t[0])
+def test_index_sort_from_the_slot_tables(pc, table):
+    name, cap, counts = table
+    n = int(counts.sum())
+    for nbits, e, tight in ((30, 0, False), (38, 6, True)):
+        ybits, pos1 = R.index_layout(nbits, e, tight)
+        h, y = R.index_entries("uniform", n, nbits, ybits, pos1, e)
+        _check_index_sort(pc, h, y, nbits, ybits, pos1, e, cap, counts, (name, nbits, e))
 
 
 # ------------------------------------------------------------------------------------------

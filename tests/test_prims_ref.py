@@ -2,7 +2,8 @@
 tests/test_gpu_prims.py runs against lrge_amd/csrc/k_prims.h, the model's answer is computed together with the answers of named near-miss
 models -- an unstable sort, the other digit mask, a lost carry, a forgotten head ... -- and at least one case of the family must separate
 each near miss from the truth.  Also: the per-pass sort model over all passes is the composed-key model, the paths of the slot reader
-are all reached by the chunk tables, and hash_to_sig / sig_to_hash are inverse."""
+are all reached by the chunk tables, the index sort model is the plain sort of the significance strings, and hash_to_sig / sig_to_hash
+are inverse."""
 import numpy as np
 import pytest
 
@@ -158,6 +159,87 @@ def test_anchor_words_use_the_whole_payload_and_the_plan_has_every_shape():
     # the lengths fill each variant exactly, one short and one over
     for cap in R.LSORT_CAP:
         assert {cap - 1, cap} <= set(R.SEG_LENS) and (cap + 1 in R.SEG_LENS or cap == 16384)
+
+
+# ---- the segment-packed index sort ----
+def _index_sort(case, miss=None):
+    kind, n, nbits, e, tight = case
+    ybits, pos1 = R.index_layout(nbits, e, tight)
+    h, y = R.index_entries(kind, n, nbits, ybits, pos1, e)
+    return R.index_sort(h, y, nbits, ybits, pos1, e, miss)
+
+
+ALL_INDEX_CASES = [c for g in R.INDEX_GROUPS for c in R.index_cases(g)]
+
+
+@pytest.mark.parametrize("miss", R.INDEX_SORT_MISSES)
+def test_index_sort_cases_separate(miss):
+    # the groups that must tell the near miss from the truth on their own (each is one GPU test): the rest of them hold no case that could
+    groups = {"unstable": ("all_equal", "a2_bits_only", "below_a2_only", "sizes"), "a2_low_bits": ("layouts", "uniform", "a2_bits_only", "below_a2_only"),
+              "e_minus_1": ("layouts", "sizes", "uniform", "a2_bits_only")}.get(miss, R.INDEX_GROUPS)
+    for g in groups:
+        assert separated(R.index_cases(g), _index_sort, lambda c: _index_sort(c, miss)) > 0, g
+
+
+def test_index_sort_cases_are_what_they_say():
+    for g in R.INDEX_GROUPS:
+        for kind, n, nbits, e, tight in R.index_cases(g):
+            nr = nbits - 8 - e
+            ybits, pos1 = R.index_layout(nbits, e, tight)
+            assert nr >= 1 and nbits - 16 >= 8 and nr + ybits <= 64 and (nr + ybits == 64) == tight and pos1 < 32 and ybits - pos1 <= 32
+            h, y = R.index_entries(kind, n, nbits, ybits, pos1, e)
+            assert h.size == n and int(h.max()) <= R.mask(nbits)
+            S = R.sig_of(h, nbits)
+            segs = np.unique(R.shr(S, nr)).size
+            if kind == "one_b0":
+                assert np.unique(h & R.U64(0xff)).size == 1 and np.unique(h).size > n // 2
+            if kind == "one_per_segment":
+                assert n < 256 and np.unique(h & R.U64(0xff)).size == n
+            if kind == "all_equal":
+                assert segs == 1 and np.unique(h).size == 1
+            if kind == "a2_bits_only":
+                assert segs == min(n, 1 << e) and np.unique(S & R.U64(R.mask(nr))).size == 1
+            if kind == "below_a2_only":
+                assert segs == 1 and np.unique(h).size == 1 << (8 - e)
+            # the positions hold the input index, and the read numbers reach their top bit
+            rid, low = R.y_fields(y, pos1)
+            assert np.array_equal((rid & R.U64(31)) << R.U64(pos1) | low, np.arange(n, dtype=np.uint64))
+            assert n < 64 or int(rid.max()) >> (ybits - pos1 - 1) == 1
+    assert {c[1] for c in ALL_INDEX_CASES} >= set(R.INDEX_N) and {c[2] for c in ALL_INDEX_CASES} == set(R.INDEX_NBITS) and {c[3] for c in ALL_INDEX_CASES} == set(R.INDEX_E)
+
+
+def test_index_sort_model_is_the_plain_sort_of_the_strings():
+    for case in R.index_cases("layouts") + R.index_cases("all_equal"):
+        kind, n, nbits, e, tight = case
+        ybits, pos1 = R.index_layout(nbits, e, tight)
+        h, y = R.index_entries(kind, n, nbits, ybits, pos1, e)
+        assert np.array_equal(R.sig_of(h[:200], nbits), np.array([R.hash_to_sig(int(v), nbits) for v in h[:200]], dtype=np.uint64))
+        words, starts = R.index_sort(h, y, nbits, ybits, pos1, e)
+        ent = sorted((R.hash_to_sig(int(a), nbits), i, int(b)) for i, (a, b) in enumerate(zip(h[:600], y[:600])))      # ties: input order
+        w600, s600 = R.index_sort(h[:600], y[:600], nbits, ybits, pos1, e)
+        nr = nbits - 8 - e
+        assert [int(v) for v in w600] == [(S & R.mask(nr)) << ybits | (b >> 32) << pos1 | (b & R.mask(pos1)) for S, _, b in ent]
+        if e <= 1:                                      # (a quadratic count: the small tables only)
+            assert [int(v) for v in s600] == [sum(1 for S, _, _ in ent if S >> nr < s) for s in range(256 << e)] + [600]
+        assert starts.size == (256 << e) + 1 and starts[-1] == n and (np.diff(starts.astype(np.int64)) >= 0).all()
+        # the SEGW form of an entry holds the same string, DIG on top of the word's hash field, over the same squeezed position
+        w, d = R.segw_entries(h, y, nbits, ybits, pos1)
+        rid, low = R.y_fields(y, pos1)
+        assert np.array_equal(R.shl(d.astype(np.uint64), nbits - 16) | R.shr(w, ybits), R.sig_of(h, nbits))
+        assert np.array_equal(w & R.U64(R.mask(ybits)), R.shl(rid, pos1) | low)
+
+
+def test_wave_tables_hold_the_entries_in_slots_a_sketch_could_leave():
+    for n in R.INDEX_N:
+        cap, counts = R.wave_table_for(n)
+        assert cap % 64 == 0 and cap <= R.RS_TILE and int(counts.sum()) == n and counts.max() <= cap and counts[0] == 0 and counts[-1] == 0
+    assert len(R.index_slot_tables()) == 10 and all(cap % 64 == 0 and cap <= R.RS_TILE for _, cap, _ in R.index_slot_tables())
+    spans = [s for _, cap, counts in R.index_slot_tables() for s in R.slot_tile_spans(cap, counts)]
+    assert min(spans) <= 3 and 7 in spans and max(spans) > 90                # the one-load descriptor, and the offsets through LDS behind it
+    h, y = R.index_entries("uniform", 4097, 30, 30, 12, 0)
+    cap, counts = R.wave_table_for(4097)
+    (_, _), (w, d), (sw, sd, _) = R.index_forms(h, y, 30, 30, 12, cap, counts)
+    assert np.array_equal(R.slots_dense(sw, counts, cap), w) and np.array_equal(R.slots_dense(sd.astype(np.uint64), counts, cap), d.astype(np.uint64))
 
 
 # ---- run heads ----

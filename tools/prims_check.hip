@@ -1,6 +1,6 @@
 // prims_check.hip -- the primitives of lrge_amd/csrc/k_prims.h, one call each, for tests/test_gpu_prims.py: the device-wide exclusive scan,
-// the stable LSD radix sorts, the segment-local LDS sort and the run-head compaction.  The header is included as the product includes it:
-// this file holds no kernel, every launch below is the product's own code.  Each pc_ function takes host arrays, copies them into device
+// the stable LSD radix sorts, the segment-local LDS sort, the segment-packed index sort and the run-head compaction.  The header is included
+// as the product includes it: this file holds no kernel, every launch below is the product's own code.  Each pc_ function takes host arrays, copies them into device
 // buffers that carry a guard band in front and behind (a byte pattern), calls ONE primitive on one stream, copies the result back and
 // returns the primitive's return code; *guard_ok says whether every band still holds its pattern.  Word offsets shift a buffer off its
 // 16-byte alignment (the scan's scalar branches).  Not part of the ABI: include/lrge_hip.h does not declare these.
@@ -216,7 +216,7 @@ int pc_anchor_sort(const u64 *h_pk, u64 n_in, u64 n_out, int nbits, u32 sb, u32 
     PC_NEED(segs.alloc(0, (size_t)n_seg_all * sizeof(SegDesc))); PC_NEED(tiles.alloc(0, (size_t)n_tiles * sizeof(SegTile)));
     PC_NEED(pk0.put(h_pk, n_in * 8));
     PC_NEED(segs.put(h_segs, (size_t)n_seg_all * sizeof(SegDesc))); PC_NEED(tiles.put(h_tiles, (size_t)n_tiles * sizeof(SegTile)));
-    UnpackParams up; up.sb = sb; up.bits_qy = bits_qy; up.sh_q = sh_q; up.dmask = 255; up.nbits = 0; up.nd_out = nullptr; up.nd_shift = 0; up.nd_mask = 0; up.dig16 = 0;
+    UnpackParams up; up.sb = sb; up.bits_qy = bits_qy; up.sh_q = sh_q;
     const SegDesc *d0 = segs.p<SegDesc>(), *d1 = d0 + n_segs[0], *d2 = d1 + n_segs[1];
     int rc = LRGE_OK;
     {
@@ -230,6 +230,39 @@ int pc_anchor_sort(const u64 *h_pk, u64 n_in, u64 n_out, int nbits, u32 sb, u32 
     }
     PC_NEED(ok.get(h_ok, n_out * 8)); PC_NEED(ov.get(h_ov, n_out * 8));
     *guard_ok = pk0.intact() && pk1.intact() && ok.intact() && ov.intact() && segs.intact() && tiles.intact();
+    return rc;
+}
+
+// The segment-packed index sort over n entries in one of its three source forms.  form 0: (hash, y) pairs (h_x, h_y); 1: dense SEGW entries, the
+// words h_x and the DIG members h_dig; 2: the wave-dense sketch's slots -- n_waves slots of `cap` words h_x and DIG members h_dig, h_cnt entries in
+// each, h_offs their exclusive scan.  h_words receives the n packed words, h_seg_start the (256 << e) + 1 segment starts.  The sort releases its
+// inputs to the pool; the guarded buffers here are none of the pool's, so that is a no-op.  The result may lie in a pool block of the sort's own.
+int pc_index_sort(int form, const u64 *h_x, const u64 *h_y, const u32 *h_dig, const u32 *h_cnt, const u32 *h_offs, u32 n_waves, u32 cap, u64 n, int nbits,
+                  u32 ybits, u32 pos1, u32 e, const char *opts, u64 *h_words, u32 *h_seg_start, int *guard_ok) {
+    set_opts(opts);
+    *guard_ok = 0;
+    const size_t n_in = form == 2 ? (size_t)n_waves * cap : n, mb = form == 0 ? 8 : 4;      // input entries; bytes of the second member
+    GBuf x, m, cnt, offs, k1, m1;
+    PC_NEED(x.alloc(0, n_in * 8)); PC_NEED(m.alloc(0, n_in * mb)); PC_NEED(k1.alloc(0, n * 8)); PC_NEED(m1.alloc(0, n * mb));
+    PC_NEED(x.put(h_x, n_in * 8)); PC_NEED(m.put(form == 0 ? (const void *)h_y : (const void *)h_dig, n_in * mb));
+    if (form == 2) {
+        PC_NEED(cnt.alloc(0, (size_t)n_waves * 4)); PC_NEED(offs.alloc(0, (size_t)n_waves * 4));
+        PC_NEED(cnt.put(h_cnt, (size_t)n_waves * 4)); PC_NEED(offs.put(h_offs, (size_t)n_waves * 4));
+    }
+    u64 *res = nullptr; u32 *d_seg = nullptr;
+    Scratch sc(g_ctx);
+    const WaveSrc ws{x.p<u64>(), m.p<u32>(), cnt.p<u32>(), offs.p<u32>(), n_waves, cap};
+    IndexSortIn in;
+    if (form == 0) { in.x = x.p<u64>(); in.y = m.p<u64>(); }
+    else if (form == 1) { in.x = x.p<u64>(); in.dig = m.p<u32>(); }
+    else in.ws = &ws;
+    const int rc = finish(index_sort_seg(g_ctx, sc, in, k1.p<u64>(), m1.p<u64>(), n, nbits, ybits, pos1, e, &res, &d_seg));
+    if (!rc) {
+        PC_NEED(res && d_seg);
+        PC_NEED(hipMemcpy(h_words, res, n * 8, hipMemcpyDeviceToHost) == hipSuccess);
+        PC_NEED(hipMemcpy(h_seg_start, d_seg, (((size_t)256 << e) + 1) * 4, hipMemcpyDeviceToHost) == hipSuccess);
+    }
+    *guard_ok = x.intact() && m.intact() && k1.intact() && m1.intact() && (form != 2 || (cnt.intact() && offs.intact()));
     return rc;
 }
 
