@@ -28,6 +28,11 @@
 struct BamSeg { uint64_t start, count, landing; };
 
 struct BamStats { uint64_t segments, empty_segments, speculative_starts, rejected_starts, repair_rounds, rewalked_segments; };
+// the counts of a run of windows: every field sums (a new field is added here as well)
+inline void bam_stats_add(BamStats &sum, const BamStats &w) {
+    sum.segments += w.segments; sum.empty_segments += w.empty_segments; sum.speculative_starts += w.speculative_starts;
+    sum.rejected_starts += w.rejected_starts; sum.repair_rounds += w.repair_rounds; sum.rewalked_segments += w.rewalked_segments;
+}
 
 // multi-byte fields lie at any byte offset: assembled from bytes
 FX_HD uint32_t bam_u16(const uint8_t *t, uint64_t o) { return (uint32_t)t[o] | (uint32_t)t[o + 1] << 8; }

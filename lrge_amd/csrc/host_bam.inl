@@ -1,7 +1,7 @@
 // host_bam.inl -- the record scan of unaligned BAM text in HBM (k_bam.h): the device backend of bam_run
 // (bam_round.h), which drives the header, a candidate start per segment, the walks, the repair rounds and then the table, here
 // and in the host twin alike.  Between the rounds only the segment summaries travel (24 B a segment).  Included into
-// host_fastx.inl, whose tail (fx_tables_to_host) brings the identifiers and the lengths down.
+// host_fastx.inl, whose tail (fx_scan_tail) takes the table from there.
 
 #include "bam_round.h"
 
@@ -20,8 +20,8 @@ struct BamDev {
     u64 *d_cand = nullptr, *d_from = nullptr;                           // (d_from: later the table bases, one more than segments)
     BamSeg *d_seg = nullptr;
     u32 *d_list = nullptr, *d_seq_len = nullptr, *d_name_len = nullptr;
-    bool count_bases = false;                                           // a run that does not keep all: `bases` is the sum of the lengths
-    u64 bases = 0;
+    bool count_bases = false;                                           // a run that does not keep all: f[2] is the sum of the lengths
+    u64 f[3] = {0, 0, 0};                                               // the flag words records() brought back (fx_flags_back)
 
     int header(u64 *he, u32 *verdict) {
         ALLOC_OR_FAIL(d_hdr, sc, BamHeader, 1);
@@ -66,16 +66,9 @@ struct BamDev {
         hipLaunchKernelGGL(k_bam_records, bam_walker_grid(ctx, n_seg), dim3(64), 0, st, t, n, hdr_end, S, (const u64 *)d_cand, (const u64 *)d_from, n_seg, cut, R->d_recs, d_seq_len,
                            d_name_len, (u32 *)d_flags, (unsigned long long *)(d_flags + 1));
         KCHK(ctx);
-        if (count_bases && n_rec) {                            // the sum comes back in the copy below: no synchronisation of its own
-            hipLaunchKernelGGL(k_fx_bases, dim3(std::min<u32>((u32)div_up(n_rec, FX_THREADS), (u32)ctx->n_cu * 8)), dim3(FX_THREADS), 0, st, (const u32 *)d_seq_len, n_rec,
-                               (unsigned long long *)(d_flags + 2));
-            KCHK(ctx);
-        }
-        u64 f[3] = {0, 0, 0};
-        HIPCHK(ctx, hipMemcpyAsync(f, d_flags, count_bases ? 24 : 16, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));                 // (start and base are pageable: their copies are done)
-        *flags = (u32)f[0]; *name_bytes = f[1]; bases = f[2];
-        return LRGE_OK;
+        const int frc = fx_flags_back(ctx, count_bases, d_flags, d_seq_len, n_rec, f);      // (the stream is synchronised: start and base are pageable, their copies are done)
+        *flags = (u32)f[0]; *name_bytes = f[1];
+        return frc;
     }
 };
 }  // namespace
@@ -88,8 +81,7 @@ static int bam_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R, FxWinScan *w) 
     Scratch sc(ctx);
     R->name_off.assign(1, 0);
     BamDev dev{ctx, R, sc, R->d_text, R->n_text, ctx->stream};
-    const FxKeepMode mode = w ? w->dev->mode : FX_KEEP_ALL;
-    dev.count_bases = mode != FX_KEEP_ALL;
+    dev.count_bases = fx_scan_selects(w);
     const u64 S = std::max<u64>(64, ctx->opt_u64("BAM_SEGMENT_BYTES", (u64)256 << 10));
     u64 n_rec = 0, name_bytes = 0;
     const char *refused = nullptr;
@@ -98,16 +90,8 @@ static int bam_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R, FxWinScan *w) 
     if (v) return fx_verdict_rc(ctx, (u32)v, refused);
     R->fmt = FX_FMT_BAM;                                                // (a refused file leaves no read set, so no format either)
     if (!n_rec) return LRGE_OK;                                         // the header ends the text, or the window has no whole record yet
-    if (name_bytes >> 32) return fx_verdict_rc(ctx, FX_UNPROVEN, "4 GiB of identifiers or more");
-    if (mode != FX_KEEP_ALL) {
-        const u64 n_use = w->end ? R->n_text : w->cut;
-        int src;
-        if (w->dev->map && (src = w->dev->seek_window(sc, R, n_rec, n_use))) return src;
-        return w->dev->keep_window(sc, R, dev.d_seq_len, dev.d_name_len, n_rec, n_use, dev.bases);
-    }
-    const int rc = fx_tables_to_host(ctx, R, sc, n_rec, dev.d_seq_len, dev.d_name_len, name_bytes);
-    if (rc || !w) return rc;
-    return w->dev->store_window(sc, *R, dev.d_seq_len, R->n_text);
+    // (bam_run has judged the verdict word, with its own message; the prefix's end is for the seek map: the packed copies take whole records)
+    return fx_scan_tail(ctx, R, sc, w, dev.f, nullptr, dev.d_seq_len, dev.d_name_len, n_rec, w && !w->end ? w->cut : R->n_text);
 }
 
 extern "C" int lrge_hip_reads_bam_stats(const lrge_hip_reads *r, lrge_hip_bam_stats *out) {

@@ -57,19 +57,18 @@ static int cram_device_error(lrge_hip_ctx *ctx, const CramDev &dev, const char *
 
 // input that starts with "CRAM", under LRGE_GPU_INGEST_CRAM: the whole call
 static int fx_open_cram(lrge_hip_ctx *ctx, lrge_hip_reads *R, const u8 *d, u64 len, double t0) {
-    const auto unproven = [&](const std::string &why) { LRGE_SET_ERR(ctx, "reads_open: not proven on the device (%s)", why.c_str()); return (int)LRGE_ERR_UNPROVEN; };
     CramWalk cw;
     std::string why;
     const uint64_t w0 = cram_now_us();
-    if (!cram_walk(d, len, cw, why)) return unproven(why);
+    if (!cram_walk(d, len, cw, why)) return fx_unproven(ctx, why.c_str());
     CramStats &st = R->cram;
     st.walk_us = cram_now_us() - w0;
     st.containers = cw.w.containers; st.slices = cw.w.ba.size(); st.records = cw.w.recs.size();
     const u64 n = cw.w.recs.size(), total = cw.ba_out.back();
-    if (n >> 32) { LRGE_SET_ERR(ctx, "reads_open: 2^32 records or a sequence of 2^32 bases (%s)", "CRAM records"); return LRGE_ERR_TOO_MANY; }
-    if (cw.names.size() >> 32) return unproven("4 GiB of identifiers or more");
+    if (n >> 32) return fx_verdict_rc(ctx, FX_TOO_MANY, "CRAM records");
+    if (cw.names.size() >> 32) return fx_unproven(ctx, "4 GiB of identifiers or more");
     const std::vector<RansStream> s = cram_streams(cw);
-    if (s.size() < ctx->opt_u64("CRAM_MIN_BLOCKS", CRAM_MIN_BLOCKS_DEFAULT)) return unproven("fewer BA blocks than CRAM_MIN_BLOCKS");
+    if (s.size() < ctx->opt_u64("CRAM_MIN_BLOCKS", CRAM_MIN_BLOCKS_DEFAULT)) return fx_unproven(ctx, "fewer BA blocks than CRAM_MIN_BLOCKS");
     const u64 round_bytes = std::max<u64>(1, ctx->opt_u64("CRAM_ROUND_BYTES", (u64)256 << 20)), cap = ingest_cap(ctx);
     u64 comp = 0, largest = 0;
     for (const RansStream &k : s) { comp += k.n; largest = std::max<u64>(largest, k.n); }
@@ -77,18 +76,14 @@ static int fx_open_cram(lrge_hip_ctx *ctx, lrge_hip_reads *R, const u8 *d, u64 l
         LRGE_SET_ERR(ctx, "reads_open: bases and one round above INGEST_MAX_BYTES (%llu)", (unsigned long long)cap);
         return LRGE_ERR_UNPROVEN;
     }
-    hipError_t e = hipSuccess;
-    if (!(R->d_text = (u8 *)ctx->pool.alloc((size_t)total + FX_PAD, &e))) {
-        LRGE_SET_ERR(ctx, "reads_open: device allocation of %llu bytes failed: %s", (unsigned long long)total, hipGetErrorString(e));
-        return LRGE_ERR_DEVICE;
-    }
-    R->n_text = total;
+    int rc = fx_alloc_text(ctx, R, total);
+    if (rc) return rc;
     {
         CramDev dev(ctx);
         dev.out = R->d_text;
         const int64_t bad = cram_run(dev, s, round_bytes, true, st, nullptr, why);
         if (bad < 0) return cram_device_error(ctx, dev, "reads_open: CRAM base blocks");
-        if (bad) return unproven(why);
+        if (bad) return fx_unproven(ctx, why.c_str());
     }
     const double t1 = fx_now_ms();
     // the record table of a base store: a record's bases are where the walk found them
@@ -99,10 +94,7 @@ static int fx_open_cram(lrge_hip_ctx *ctx, lrge_hip_reads *R, const u8 *d, u64 l
         R->seq_len[(size_t)i] = r.len;
         tab[(size_t)i] = FxRec{0, cw.ba_out[r.slice] + r.off, r.len, (u32)(cw.name_off[(size_t)i + 1] - cw.name_off[(size_t)i]), r.len};
     }
-    int rc;
-    if ((rc = fx_alloc_recs(ctx, R, std::max<u64>(1, n)))) return rc;
-    if (n) HIPCHK(ctx, hipMemcpyAsync(R->d_recs, tab.data(), tab.size() * sizeof(FxRec), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = fx_upload_recs(ctx, R, tab))) return rc;
     R->n = n; R->names.swap(cw.names); R->name_off.swap(cw.name_off);
     R->fmt = n ? FX_FMT_FASTA : FX_FMT_EMPTY;
     R->text_bytes = total; R->is_cram = true;
@@ -168,7 +160,6 @@ static bool cram_select_flags(int flags) { return (flags & LRGE_GPU_INGEST_CRAM)
 // One sampled call on input that starts with "CRAM", under LRGE_GPU_INGEST_SELECT_CRAM beside LRGE_GPU_INGEST_CRAM.  mode
 // FX_KEEP_NONE: the census (map: filled when given); FX_KEEP_SEL: the selected open, or -- mapped -- the mapped open on `map`
 static int fx_cram_sampled(lrge_hip_ctx *ctx, lrge_hip_reads *R, const u8 *d, u64 len, FxKeepMode mode, const u32 *sel, u64 k, bool mapped, FxSeekMap *map, double t0) {
-    const auto unproven = [&](const std::string &why) { LRGE_SET_ERR(ctx, "reads_open: not proven on the device (%s)", why.c_str()); return (int)LRGE_ERR_UNPROVEN; };
     if (mode != FX_KEEP_SEL) k = 0;
     const u64 cap = ingest_cap(ctx);
     CramSampled o;
@@ -178,10 +169,10 @@ static int fx_cram_sampled(lrge_hip_ctx *ctx, lrge_hip_reads *R, const u8 *d, u6
                                 cap, o, why);
     switch (rc) {
     case CRAM_S_OK: break;
-    case CRAM_S_UNPROVEN: return unproven(why);
-    case CRAM_S_ORDINAL: LRGE_SET_ERR(ctx, "reads_open_selected: ordinal %u of %llu records", o.bad_ordinal, (unsigned long long)o.cw.w.recs.size()); return LRGE_ERR_INVALID;
-    case CRAM_S_OTHER_INPUT: ctx->err = "reads_open_mapped: the map is of another input"; return LRGE_ERR_INVALID;
-    case CRAM_S_MISFIT: LRGE_SET_ERR(ctx, "reads_open_mapped: the map does not fit the input (%s)", why.c_str()); return LRGE_ERR_UNPROVEN;
+    case CRAM_S_UNPROVEN: return fx_unproven(ctx, why.c_str());
+    case CRAM_S_ORDINAL: return fx_ordinal_rc(ctx, o.bad_ordinal, o.cw.w.recs.size());
+    case CRAM_S_OTHER_INPUT: return fx_map_other(ctx);
+    case CRAM_S_MISFIT: return fx_map_misfit(ctx, why.c_str());
     case CRAM_S_OVER_CAP: LRGE_SET_ERR(ctx, "reads_open_selected: chosen bases and one round of CRAM blocks above INGEST_MAX_BYTES (%llu)", (unsigned long long)cap); return LRGE_ERR_UNPROVEN;
     default: return cram_device_error(ctx, sink.dev, "reads_open_selected: CRAM base blocks");
     }
@@ -195,9 +186,7 @@ static int fx_cram_sampled(lrge_hip_ctx *ctx, lrge_hip_reads *R, const u8 *d, u6
         tab[(size_t)j] = FxRec{0, o.plan.dst[(size_t)j], l, (u32)(o.cw.name_off[(size_t)j + 1] - o.cw.name_off[(size_t)j]), l};
     }
     int arc;
-    if ((arc = fx_alloc_recs(ctx, R, std::max<u64>(1, k)))) return arc;
-    if (k) HIPCHK(ctx, hipMemcpyAsync(R->d_recs, tab.data(), tab.size() * sizeof(FxRec), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if ((arc = fx_upload_recs(ctx, R, tab))) return arc;
     R->d_text = sink.store; sink.store = nullptr; R->n_text = kept;
     R->n = k; R->names.swap(o.cw.names); R->name_off.swap(o.cw.name_off);
     R->fmt = k ? FX_FMT_FASTA : FX_FMT_EMPTY;

@@ -51,11 +51,25 @@ static double fx_now_ms() { return DevPool::now_ms(); }
 
 static u64 ingest_cap(lrge_hip_ctx *ctx) { return ctx->opt_u64("INGEST_MAX_BYTES", dev_budget(ctx)); }
 
+// ---- what a call is refused with: every text has its one site here ----
+static int fx_unproven(lrge_hip_ctx *ctx, const char *what) { LRGE_SET_ERR(ctx, "reads_open: not proven on the device (%s)", what); return LRGE_ERR_UNPROVEN; }
 static int fx_verdict_rc(lrge_hip_ctx *ctx, u32 verdict, const char *what) {
-    if (verdict & FX_UNPROVEN) { LRGE_SET_ERR(ctx, "reads_open: not proven on the device (%s)", what); return LRGE_ERR_UNPROVEN; }
+    if (verdict & FX_UNPROVEN) return fx_unproven(ctx, what);
     LRGE_SET_ERR(ctx, "reads_open: 2^32 records or a sequence of 2^32 bases (%s)", what);
     return LRGE_ERR_TOO_MANY;
 }
+// the sampled calls: a container or a format they were not asked for by its flags (also: ", not Zstandard input")
+static int fx_fastx_only(lrge_hip_ctx *ctx, const char *also = "") { ctx->err = std::string("reads_open_selected: selected ingest takes FASTA / FASTQ only") + also; return LRGE_ERR_UNPROVEN; }
+static int fx_sel_checked(lrge_hip_ctx *ctx, const u32 *sel, u64 k) {
+    if ((!k || sel) && fx_sel_ascending(sel, k)) return LRGE_OK;
+    ctx->err = "reads_open_selected: the ordinals are not strictly ascending";
+    return LRGE_ERR_INVALID;
+}
+static int fx_ordinal_rc(lrge_hip_ctx *ctx, u32 ordinal, u64 records) { LRGE_SET_ERR(ctx, "reads_open_selected: ordinal %u of %llu records", ordinal, (unsigned long long)records); return LRGE_ERR_INVALID; }
+static int fx_read_failed(lrge_hip_ctx *ctx) { ctx->err = "reads_open_mapped: the file could not be read"; return LRGE_ERR_IO; }
+static int fx_map_other(lrge_hip_ctx *ctx) { ctx->err = "reads_open_mapped: the map is of another input"; return LRGE_ERR_INVALID; }
+static int fx_map_misfit(lrge_hip_ctx *ctx, const char *what) { LRGE_SET_ERR(ctx, "reads_open_mapped: the map does not fit the input (%s)", what); return LRGE_ERR_UNPROVEN; }
+static int fx_map_range(lrge_hip_ctx *ctx) { ctx->err = "reads_open_mapped: a file range does not hold the blocks of the map"; return LRGE_ERR_INVALID; }
 
 // the record table of n records in R->d_recs
 static int fx_alloc_recs(lrge_hip_ctx *ctx, lrge_hip_reads *R, u64 n) {
@@ -64,17 +78,37 @@ static int fx_alloc_recs(lrge_hip_ctx *ctx, lrge_hip_reads *R, u64 n) {
     LRGE_SET_ERR(ctx, "reads_open: record table: %s", hipGetErrorString(e));
     return LRGE_ERR_DEVICE;
 }
+// ... the text block of `bytes` bytes in R->d_text, FX_PAD bytes of slack behind it
+static int fx_alloc_text(lrge_hip_ctx *ctx, lrge_hip_reads *R, u64 bytes) {
+    hipError_t e = hipSuccess;
+    R->n_text = bytes;
+    if ((R->d_text = (u8 *)ctx->pool.alloc((size_t)bytes + FX_PAD, &e))) return LRGE_OK;
+    LRGE_SET_ERR(ctx, "reads_open: device allocation of %llu bytes failed: %s", (unsigned long long)bytes, hipGetErrorString(e));
+    return LRGE_ERR_DEVICE;
+}
+// ... and a table made on the host -- the records of a base store -- copied into it (one record is allocated at least)
+static int fx_upload_recs(lrge_hip_ctx *ctx, lrge_hip_reads *R, const std::vector<FxRec> &tab) {
+    const int rc = fx_alloc_recs(ctx, R, std::max<u64>(1, tab.size()));
+    if (rc) return rc;
+    if (!tab.empty()) HIPCHK(ctx, hipMemcpyAsync(R->d_recs, tab.data(), tab.size() * sizeof(FxRec), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return LRGE_OK;
+}
 
-// behind the kernel that fills the record table: its verdict bits ([0], low word) and the identifier bytes ([1]) come back
-// (bases: d_flags has a third word, the sum of the sequence lengths by k_fx_bases, which comes back in the same copy)
-static int fx_flags_back(lrge_hip_ctx *ctx, const u64 *d_flags, const char *outside, u64 *name_bytes, u64 *bases = nullptr) {
-    u64 flags[3] = {0, 0, 0};
-    HIPCHK(ctx, ctx->d2h(flags, d_flags, bases ? 24 : 16, ctx->stream));
+// the bytes a record of `len` bases takes in a base store: BAM's stay packed, two to a byte, and a record starts on a byte
+static u64 fx_store_span(u64 len, bool packed) { return packed ? (len + 1) / 2 : len; }
+
+// behind the kernel that fills the record table: the flag words come back in one copy -- f[0] the verdict bits (low word), f[1] the identifier
+// bytes and, for a run that does not keep all (bases), f[2] the sum of d_seq_len, which k_fx_bases adds up first: no synchronisation of its own
+static int fx_flags_back(lrge_hip_ctx *ctx, bool bases, u64 *d_flags, const u32 *d_seq_len, u64 n_rec, u64 f[3]) {
+    f[0] = f[1] = f[2] = 0;
+    if (bases && n_rec) {
+        hipLaunchKernelGGL(k_fx_bases, dim3(std::min<u32>((u32)div_up(n_rec, FX_THREADS), (u32)ctx->n_cu * 8)), dim3(FX_THREADS), 0, ctx->stream, d_seq_len, n_rec,
+                           (unsigned long long *)(d_flags + 2));
+        KCHK(ctx);
+    }
+    HIPCHK(ctx, ctx->d2h(f, d_flags, bases ? 24 : 16, ctx->stream));
     HIPCHK(ctx, ctx->d2h_sync(ctx->stream));
-    if ((u32)flags[0]) return fx_verdict_rc(ctx, (u32)flags[0], outside);
-    if (flags[1] >> 32) return fx_verdict_rc(ctx, FX_UNPROVEN, "4 GiB of identifiers or more");
-    *name_bytes = flags[1];
-    if (bases) *bases = flags[2];
     return LRGE_OK;
 }
 
@@ -139,6 +173,13 @@ static int fx_kind(lrge_hip_ctx *ctx, int flags, const u8 *host, const u8 *d_tex
 // BAM and SAM stay resident unless the caller asked for their windows as well
 static bool fx_kind_windowed(int flags, int kind) { return kind == FX_FMT_EMPTY || (flags & LRGE_GPU_INGEST_WINDOWED_ALN); }
 
+// the census and the selected open take FASTA / FASTQ, whatever flags came with the call: the sniff of the text's first bytes.
+// With LRGE_GPU_INGEST_SELECT_ALN beside LRGE_GPU_INGEST_BAM the magic of BAM makes the run a BAM run, through
+// the windows whatever LRGE_GPU_INGEST_WINDOWED / _WINDOWED_ALN say, as FASTA / FASTQ text is
+static bool fx_select_aln(int flags) { return (flags & LRGE_GPU_INGEST_BAM) && (flags & LRGE_GPU_INGEST_SELECT_ALN); }
+// ... and with LRGE_GPU_INGEST_SELECT_SAM beside LRGE_GPU_INGEST_SAM text that sam_sniff takes makes it a SAM run
+static bool fx_select_sam(int flags) { return (flags & LRGE_GPU_INGEST_SAM) && (flags & LRGE_GPU_INGEST_SELECT_SAM); }
+
 // ---- windowed ingest: the device backend of fx_window.h ----
 struct FxWinDev;
 // the scan of one window (fx_parse_kind): up to its cut (left in `cut`; 0: there is none yet) unless `end`
@@ -183,24 +224,17 @@ struct FxWinDev {
         return LRGE_OK;
     }
     u64 len() const { return blk->keep_len; }
-    int unproven(const char *what) { scan_refused = true; LRGE_SET_ERR(ctx, "reads_open: not proven on the device (%s)", what); return LRGE_ERR_UNPROVEN; }
-    // the census and the selected open take FASTA / FASTQ, whatever flags came with the call: the sniff of the text's first bytes.
-    // With LRGE_GPU_INGEST_SELECT_ALN beside LRGE_GPU_INGEST_BAM the magic of BAM makes the run a BAM run, through
-    // the windows whatever LRGE_GPU_INGEST_WINDOWED / _WINDOWED_ALN say, as FASTA / FASTQ text is
-    bool select_aln() const { return (flags & LRGE_GPU_INGEST_BAM) && (flags & LRGE_GPU_INGEST_SELECT_ALN); }
-    // ... and with LRGE_GPU_INGEST_SELECT_SAM beside LRGE_GPU_INGEST_SAM text that sam_sniff takes makes it a SAM run
-    bool select_sam() const { return (flags & LRGE_GPU_INGEST_SAM) && (flags & LRGE_GPU_INGEST_SELECT_SAM); }
+    int unproven(const char *what) { scan_refused = true; return fx_unproven(ctx, what); }
     u32 lead() const { return kind == FX_FMT_BAM ? FX_LEAD_BAM : kind == FX_FMT_SAM ? FX_LEAD_SAM : FX_LEAD_TEXT; }      // where a record starts (fx_rec_start)
     int selected_format() {
         if (mapped) return LRGE_OK;             // (a run may start with a read named HD.., SQ.. or RG..: fx_win_census; the kind is the map's)
         u8 head[4] = {0, 0, 0, 0};
         const u64 n = blk->keep_len;
         if (n) { HIPCHK(ctx, hipMemcpyAsync(head, blk->keep, (size_t)std::min<u64>(4, n), hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); }
-        if (select_aln() && fx_sniff(LRGE_GPU_INGEST_BAM, head, n) == FX_FMT_BAM) { kind = FX_FMT_BAM; return LRGE_OK; }
-        if (select_sam() && fx_sniff(LRGE_GPU_INGEST_SAM, head, n) == FX_FMT_SAM) { kind = FX_FMT_SAM; return LRGE_OK; }
+        if (fx_select_aln(flags) && fx_sniff(LRGE_GPU_INGEST_BAM, head, n) == FX_FMT_BAM) { kind = FX_FMT_BAM; return LRGE_OK; }
+        if (fx_select_sam(flags) && fx_sniff(LRGE_GPU_INGEST_SAM, head, n) == FX_FMT_SAM) { kind = FX_FMT_SAM; return LRGE_OK; }
         if (fx_sniff(LRGE_GPU_INGEST_BAM | LRGE_GPU_INGEST_SAM, head, n) == FX_FMT_EMPTY && !(n >= 4 && !memcmp(head, "CRAM", 4))) return LRGE_OK;
-        ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only";
-        return LRGE_ERR_UNPROVEN;
+        return fx_fastx_only(ctx);
     }
     // the sniff of the first window makes the run a BAM or SAM run: a later window is never sniffed.  BAM and SAM that stay
     // resident turn the windows off: the block takes back the growth rule a resident text has without the flag (attach() had made it
@@ -226,7 +260,7 @@ struct FxWinDev {
         if (prc == LRGE_ERR_UNPROVEN && !store.keep_over) scan_refused = true;      // (the scan's verdict; the store's budget is the other refusal a window has)
         if (prc) return prc;
         *cut = end ? W.n_text : w.cut; *fmt = W.fmt;
-        if (*cut) { u64 *sum = &R->bam.segments; const u64 *add = &W.bam.segments; for (int i = 0; i < 6; ++i) sum[i] += add[i]; }
+        if (*cut) bam_stats_add(R->bam, W.bam);
         if (*cut && mode != FX_KEEP_ALL) {        // (W.n, W.names and W.seq_len: the chosen records of the window, W.sel: all of them)
             if ((R->sel.seen + W.sel.seen) >> 32) return fx_verdict_rc(ctx, FX_UNPROVEN, "2^32 records or more");
             R->sel.seen += W.sel.seen; R->sel.bases_seen += W.sel.bases_seen;
@@ -236,10 +270,10 @@ struct FxWinDev {
         if (!*cut || !W.n) return LRGE_OK;
         if ((R->n + W.n) >> 32) return fx_verdict_rc(ctx, FX_UNPROVEN, "2^32 records or more");
         if ((R->names.size() + W.names.size()) >> 32) return fx_verdict_rc(ctx, FX_UNPROVEN, "4 GiB of identifiers or more");
-        const u64 at = R->names.size();
+        const u64 names_at = R->names.size();
         R->names += W.names;
         R->seq_len.insert(R->seq_len.end(), W.seq_len.begin(), W.seq_len.end());
-        for (u64 i = 1; i <= W.n; ++i) R->name_off.push_back(at + W.name_off[i]);
+        for (u64 i = 1; i <= W.n; ++i) R->name_off.push_back(names_at + W.name_off[i]);
         R->n += W.n;
         return LRGE_OK;
     }
@@ -275,6 +309,15 @@ struct FxWinDev {
             if (slot[c] != FX_SEEK_NONE) fx_seek_add(*map, R->sel.seen + slot[c], through + slot[n_cells + c]);
         return LRGE_OK;
     }
+    // d_dst: where m records of d_len bases start behind the store's end -- the scan of their spans (fx_store_span; packed: k_bam_spans', in place)
+    int store_offsets(Scratch &sc, bool packed, const u32 *d_len, u64 m, u32 *d_dst) {
+        if (packed) {
+            hipLaunchKernelGGL(k_bam_spans, dim3((u32)div_up(m, 256)), dim3(256), 0, ctx->stream, d_len, m, d_dst);
+            KCHK(ctx);
+            d_len = d_dst;
+        }
+        return scan_exclusive_u32(ctx, sc, d_len, d_dst, m, nullptr);
+    }
     // A window of a run that does not keep all (FX_KEEP_NONE, FX_KEEP_SEL), behind k_fx_records: W.d_recs and the lengths of its
     // n_rec records are on the device, `bases` is their sum.  The slice of the selection that falls into the window is found
     // here; a window without a chosen record costs nothing more.  Else k_fx_pick gathers the chosen lengths, which come down and
@@ -303,20 +346,14 @@ struct FxWinDev {
         u64 sum = 0, kept = 0, name_bytes = 0;                     // sum: the bytes the store takes
         for (u64 j = 0; j < m; ++j) {
             const u64 l = W->seq_len[j];
-            kept += l; sum += packed ? (l + 1) / 2 : l; name_bytes += name_len[j]; W->name_off.push_back(name_bytes);
+            kept += l; sum += fx_store_span(l, packed); name_bytes += name_len[j]; W->name_off.push_back(name_bytes);
         }
         if (kept > bases || sum >> 32 || name_bytes >> 32) return fx_verdict_rc(ctx, FX_UNPROVEN, "a window of 2^32 bytes or more");      // (never: the window is below that)
         if ((rc = store_room(sum))) return rc;
         ALLOC_OR_FAIL(d_dst, sc, u32, m);
         ALLOC_OR_FAIL(d_name_dst, sc, u32, m);
         ALLOC_OR_FAIL(d_names, sc, u8, std::max<u64>(1, name_bytes));
-        const u32 *d_span = d_pick_seq;
-        if (packed) {
-            hipLaunchKernelGGL(k_bam_spans, dim3((u32)div_up(m, 256)), dim3(256), 0, st, (const u32 *)d_pick_seq, m, d_dst);
-            KCHK(ctx);
-            d_span = d_dst;                                        // (the scan runs in place, as store_window's does)
-        }
-        if ((rc = scan_exclusive_u32(ctx, sc, d_span, d_dst, m, nullptr)) || (rc = scan_exclusive_u32(ctx, sc, d_pick_name, d_name_dst, m, nullptr))) return rc;
+        if ((rc = store_offsets(sc, packed, d_pick_seq, m, d_dst)) || (rc = scan_exclusive_u32(ctx, sc, d_pick_name, d_name_dst, m, nullptr))) return rc;
         const dim3 grid((u32)std::min<u64>(m, (u64)ctx->n_cu * 32));
         if (packed)
             hipLaunchKernelGGL(k_bam_keep, grid, dim3(64), 0, st, (const u8 *)W->d_text, (const FxRec *)W->d_recs, (const u32 *)(d_sel + a), (u32)r0, m, (const u32 *)d_dst,
@@ -338,19 +375,14 @@ struct FxWinDev {
     int store_window(Scratch &sc, const lrge_hip_reads &W, const u32 *d_seq_len, u64 n_use) {
         const bool packed = W.fmt == FX_FMT_BAM;
         u64 sum = 0;
-        for (u32 l : W.seq_len) sum += packed ? ((u64)l + 1) / 2 : l;
+        for (u32 l : W.seq_len) sum += fx_store_span(l, packed);
         if (sum >> 32) return fx_verdict_rc(ctx, FX_UNPROVEN, "a window of 2^32 bytes or more");      // (never: the window is below that)
         const int rrc = store_room(sum);
         if (rrc) return rrc;
         if (W.n) {
             ALLOC_OR_FAIL(d_dst, sc, u32, W.n);
             const dim3 grid((u32)std::min<u64>(W.n, (u64)ctx->n_cu * 32));
-            if (packed) {
-                hipLaunchKernelGGL(k_bam_spans, dim3((u32)div_up(W.n, 256)), dim3(256), 0, ctx->stream, d_seq_len, W.n, d_dst);
-                KCHK(ctx);
-                d_seq_len = d_dst;                               // (the scan runs in place, as the record scans' do)
-            }
-            const int src = scan_exclusive_u32(ctx, sc, d_seq_len, d_dst, W.n, nullptr);
+            const int src = store_offsets(sc, packed, d_seq_len, W.n, d_dst);
             if (src) return src;
             if (packed)
                 hipLaunchKernelGGL(k_bam_store, grid, dim3(64), 0, ctx->stream, (const u8 *)W.d_text, (const FxRec *)W.d_recs, (const u32 *)d_dst, W.n, store.keep + store.keep_len);
@@ -415,22 +447,17 @@ struct FxWinRun {
         dev.blk = &last;
         int rc = win.step(true);
         if (rc) return rc;
-        if (dev.mode == FX_KEEP_SEL && dev.at < dev.k) {        // (the selection is ascending: the first ordinal left over names the fault)
-            LRGE_SET_ERR(ctx, "reads_open_selected: ordinal %u of %llu records", dev.sel[dev.at], (unsigned long long)R->sel.seen);
-            return LRGE_ERR_INVALID;
-        }
+        if (dev.mode == FX_KEEP_SEL && dev.at < dev.k) return fx_ordinal_rc(ctx, dev.sel[dev.at], R->sel.seen);      // (the selection is ascending: the first ordinal left over names the fault)
         if (!dev.store.keep && !dev.store.keep_reserve(0)) { LRGE_SET_ERR(ctx, "reads_open: device allocation failed"); return LRGE_ERR_DEVICE; }
         std::vector<FxRec> tab((size_t)R->n);
         const bool packed = win.fmt == FX_FMT_BAM;              // (the gather of BAM reads its records' spans as it reads the text)
         u64 o = 0;
         for (u64 i = 0; i < R->n; ++i) {
-            const u64 span = packed ? ((u64)R->seq_len[i] + 1) / 2 : R->seq_len[i];
+            const u64 span = fx_store_span(R->seq_len[i], packed);
             tab[i] = FxRec{0, o, span, (u32)(R->name_off[i + 1] - R->name_off[i]), R->seq_len[i]};
             o += span;
         }
-        if ((rc = fx_alloc_recs(ctx, R, std::max<u64>(1, R->n)))) return rc;
-        if (!tab.empty()) HIPCHK(ctx, hipMemcpyAsync(R->d_recs, tab.data(), tab.size() * sizeof(FxRec), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        if ((rc = fx_upload_recs(ctx, R, tab))) return rc;
         R->d_text = dev.store.keep; R->n_text = dev.store.keep_len; dev.store.keep = nullptr;
         R->fmt = win.fmt;
         R->text_bytes = dev.through + n_text;
@@ -439,6 +466,24 @@ struct FxWinRun {
         return LRGE_OK;
     }
 };
+
+// does the scan serve a run that does not keep all (the census and the selected open)?  Its windows' bases are counted
+static bool fx_scan_selects(const FxWinScan *w) { return w && w->dev->mode != FX_KEEP_ALL; }
+// The tail of the three record scans, which left the table of the prefix [0, n_use) in R->d_recs, the lengths of its n_rec records in d_seq_len /
+// d_name_len and the flag words in f (fx_flags_back; outside: what a record outside the strict form is refused with).  A run that does not keep
+// all: the seek map takes the window's points, keep_window the chosen records.  Else the tables go to the host, a window's (w) bases to the store
+static int fx_scan_tail(lrge_hip_ctx *ctx, lrge_hip_reads *R, Scratch &sc, FxWinScan *w, const u64 f[3], const char *outside, const u32 *d_seq_len, const u32 *d_name_len, u64 n_rec,
+                        u64 n_use) {
+    if ((u32)f[0]) return fx_verdict_rc(ctx, (u32)f[0], outside);
+    if (f[1] >> 32) return fx_verdict_rc(ctx, FX_UNPROVEN, "4 GiB of identifiers or more");
+    int rc;
+    if (fx_scan_selects(w)) {
+        if (w->dev->map && (rc = w->dev->seek_window(sc, R, n_rec, n_use))) return rc;
+        return w->dev->keep_window(sc, R, d_seq_len, d_name_len, n_rec, n_use, f[2]);
+    }
+    if ((rc = fx_tables_to_host(ctx, R, sc, n_rec, d_seq_len, d_name_len, f[1])) || !w) return rc;
+    return w->dev->store_window(sc, *R, d_seq_len, n_use);
+}
 
 // the prologue of the scans that work on lines (FASTA / FASTQ, SAM): the census of every tile of t[0, n) and its summary
 struct FxTiles { u64 n_tiles; u32 *c_lf, *c_rem, *c_hdr; FxSummary hs; };
@@ -528,22 +573,12 @@ static int fx_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R, FxWinScan *w) {
     ALLOC_OR_FAIL(d_name_len, sc, u32, n_rec);
     ALLOC_OR_FAIL(d_flags, sc, u64, 3);                   // [0]: verdict bits (low word), [1]: identifier bytes, [2]: bases (a run that does not keep all)
     HIPCHK(ctx, hipMemsetAsync(d_flags, 0, 24, st));
-    const FxKeepMode mode = w ? w->dev->mode : FX_KEEP_ALL;
-    const u32 rec_blocks = (u32)div_up(n_rec, FX_THREADS);
-    hipLaunchKernelGGL(k_fx_records, dim3(rec_blocks), dim3(FX_THREADS), 0, st, t, n_use, fmt, n_rec, (const u64 *)ls, n_lf, n_lines, l0, (const u64 *)hpos, (const u32 *)hrem,
-                       n_rem, R->d_recs, d_seq_len, d_name_len, (u32 *)d_flags, (unsigned long long *)(d_flags + 1));
+    hipLaunchKernelGGL(k_fx_records, dim3((u32)div_up(n_rec, FX_THREADS)), dim3(FX_THREADS), 0, st, t, n_use, fmt, n_rec, (const u64 *)ls, n_lf, n_lines, l0, (const u64 *)hpos,
+                       (const u32 *)hrem, n_rem, R->d_recs, d_seq_len, d_name_len, (u32 *)d_flags, (unsigned long long *)(d_flags + 1));
     KCHK(ctx);
-    u64 name_bytes = 0, bases = 0;
-    if (mode != FX_KEEP_ALL) {                             // the census and the selected open: the window's bases come back with the verdict
-        hipLaunchKernelGGL(k_fx_bases, dim3(std::min<u32>(rec_blocks, (u32)ctx->n_cu * 8)), dim3(FX_THREADS), 0, st, (const u32 *)d_seq_len, n_rec, (unsigned long long *)(d_flags + 2));
-        KCHK(ctx);
-        if ((rc = fx_flags_back(ctx, d_flags, "a record outside the strict form", &name_bytes, &bases))) return rc;
-        if (w->dev->map && (rc = w->dev->seek_window(sc, R, n_rec, n_use))) return rc;
-        return w->dev->keep_window(sc, R, d_seq_len, d_name_len, n_rec, n_use, bases);
-    }
-    if ((rc = fx_flags_back(ctx, d_flags, "a record outside the strict form", &name_bytes))) return rc;
-    if ((rc = fx_tables_to_host(ctx, R, sc, n_rec, d_seq_len, d_name_len, name_bytes)) || !w) return rc;
-    return w->dev->store_window(sc, *R, d_seq_len, n_use);
+    u64 f[3];
+    if ((rc = fx_flags_back(ctx, fx_scan_selects(w), d_flags, d_seq_len, n_rec, f))) return rc;
+    return fx_scan_tail(ctx, R, sc, w, f, "a record outside the strict form", d_seq_len, d_name_len, n_rec, n_use);
 }
 
 #include "host_bam.inl"      // bam_parse_device: the same for unaligned BAM (needs the struct and the tail above)
@@ -593,14 +628,7 @@ struct FxSink {
     // behind every append to blk: the windows' turn; not 0: the code they stopped the call with
     int appended() { return run->appended() ? (int)LRGE_OK : run->stopped(); }
     // a resident text of `bytes` bytes: its block, the handle's from the start
-    int resident(u64 bytes) {
-        if (bytes > cap) return over_cap();
-        hipError_t e = hipSuccess;
-        R->n_text = bytes;
-        if ((R->d_text = (u8 *)ctx->pool.alloc((size_t)bytes + FX_PAD, &e))) return LRGE_OK;
-        LRGE_SET_ERR(ctx, "reads_open: device allocation of %llu bytes failed: %s", (unsigned long long)bytes, hipGetErrorString(e));
-        return LRGE_ERR_DEVICE;
-    }
+    int resident(u64 bytes) { return bytes > cap ? over_cap() : fx_alloc_text(ctx, R, bytes); }
     // the text is complete in block b: it becomes the handle's
     void hand_over(DevKeep &b) { R->d_text = b.keep; R->n_text = b.keep_len; b.keep = nullptr; }
 };
@@ -639,6 +667,27 @@ static int fx_bgzf_decode(lrge_hip_ctx *ctx, const u8 *d, const std::vector<Bgzf
     return LRGE_OK;
 }
 
+// A batch of the pieces a decoding source works through (BGZF blocks, gzip entries): items [i, the end it returns) of n_items -- items
+// until they hold a window of text, at least one.  size(j): the text bytes of item j; *bytes: those of the batch
+template <class F> static size_t fx_batch_end(size_t i, size_t n_items, u64 window, F size, u64 *bytes) {
+    size_t j = i;
+    for (*bytes = 0; j < n_items && (j == i || *bytes < window); ++j) *bytes += size(j);
+    return j;
+}
+// ... and the text bytes of the largest batch: what a staging block for every batch holds
+template <class F> static u64 fx_batch_largest(size_t n_items, u64 window, F size) {
+    u64 largest = 0, bytes;
+    for (size_t i = 0; i < n_items; largest = std::max(largest, bytes)) i = fx_batch_end(i, n_items, window, size, &bytes);
+    return largest;
+}
+
+// blocks [i, j) of table t as a run of their own for the chunk pipeline: their text lies back to back from offset `at`
+static std::vector<BgzfBlock> fx_bgzf_part(const std::vector<BgzfBlock> &t, size_t i, size_t j, u64 at) {
+    std::vector<BgzfBlock> part(t.begin() + i, t.begin() + j);
+    for (BgzfBlock &b : part) { b.o_off = at; at += b.isize; }
+    return part;
+}
+
 // BGZF (block table t, `total` text bytes): all blocks in one run of the pipeline, or runs of a window's size
 static int fx_src_bgzf(FxSink &s, const u8 *d, const std::vector<BgzfBlock> &t, u64 total) {
     lrge_hip_ctx *ctx = s.ctx;
@@ -656,15 +705,11 @@ static int fx_src_bgzf(FxSink &s, const u8 *d, const std::vector<BgzfBlock> &t, 
     if (rc) return rc;
     if (!windowed) return (rc = s.resident(total)) ? rc : fx_bgzf_decode(ctx, d, t, s.R->d_text);
     // runs of blocks of a window's size, each decoded behind the tail the window before it left
+    const auto isize = [&](size_t b) { return (u64)t[b].isize; };
     for (size_t i = 0, j; i < t.size(); i = j) {
-        std::vector<BgzfBlock> part;
-        u64 bytes = 0;
-        for (j = i; j < t.size() && (j == i || bytes < s.window); ++j) {
-            part.push_back(t[j]);
-            part.back().o_off = s.blk.keep_len + bytes;
-            bytes += t[j].isize;
-        }
-        if ((rc = s.room(bytes)) || (rc = fx_bgzf_decode(ctx, d, part, s.blk.keep))) return rc;
+        u64 bytes;
+        j = fx_batch_end(i, t.size(), s.window, isize, &bytes);
+        if ((rc = s.room(bytes)) || (rc = fx_bgzf_decode(ctx, d, fx_bgzf_part(t, i, j, s.blk.keep_len), s.blk.keep))) return rc;
         s.blk.keep_len += bytes;
         if ((rc = s.appended())) return rc;
     }
@@ -760,7 +805,15 @@ static int fx_src_xz(FxSink &s, const u8 *d, u64 len) {
     return rc;
 }
 
-#include "host_cram.inl"     // fx_open_cram: unaligned CRAM under LRGE_GPU_INGEST_CRAM (needs the struct, ingest_cap and fx_alloc_recs above)
+#include "host_cram.inl"     // fx_open_cram: unaligned CRAM under LRGE_GPU_INGEST_CRAM (needs the struct, ingest_cap and fx_upload_recs above)
+
+// What the sampled calls refuse by the container's magic and the flags alone, before any device work: CRAM without both of its flags, whatever
+// the others (FxWinDev::selected_format), and Zstandard that does not slide -- its text is never windowed without LRGE_GPU_INGEST_WINDOWED_ZSTD
+static int fx_sampled_refusal(lrge_hip_ctx *ctx, FxBox box, int flags) {
+    if (box == FX_BOX_CRAM && !cram_select_flags(flags)) return fx_fastx_only(ctx);
+    if (box == FX_BOX_ZSTD && (flags & LRGE_GPU_INFLATE_ZSTD) && !fx_zstd_slides(flags)) return fx_fastx_only(ctx, ", not Zstandard input");
+    return LRGE_OK;
+}
 
 // ---- the two ends of a call ----  windows were flushed: the rest of the block is the last, the store the handle's text
 static int fx_finish_windowed(FxSink &s, double t0) {
@@ -796,32 +849,32 @@ extern "C" void lrge_hip_reads_free(lrge_hip_reads *r) {
     if (ctx_alive) { r->ctx->pool.release(r->d_text); r->ctx->pool.release(r->d_recs); }     // (a destroyed context has already freed its pool)
     delete r;
 }
+// the handle a call fills: freed unless the call releases it to the caller
+using FxReadsGuard = std::unique_ptr<lrge_hip_reads, void (*)(lrge_hip_reads *)>;
+static FxReadsGuard fx_new_reads(lrge_hip_ctx *ctx) {
+    FxReadsGuard guard(new lrge_hip_reads(), lrge_hip_reads_free);
+    guard->ctx = ctx;
+    return guard;
+}
 
 // one call: lrge_hip_reads_open_mem (FX_KEEP_ALL), the census (FX_KEEP_NONE) or the selected open (FX_KEEP_SEL with sel[0, k))
 // map: a census (FX_KEEP_NONE) that leaves the seek map of the text behind (fx_seek.h)
 static int fx_open_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, int flags, FxKeepMode mode, const u32 *sel, u64 k, lrge_hip_reads **out, FxSeekMap *map = nullptr) {
     if (!ctx || !out || (!file_bytes && len)) return LRGE_ERR_INVALID;
     *out = nullptr;
-    if (mode == FX_KEEP_SEL && ((k && !sel) || !fx_sel_ascending(sel, k))) { ctx->err = "reads_open_selected: the ordinals are not strictly ascending"; return LRGE_ERR_INVALID; }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const double t0 = fx_now_ms();
+    int rc;
+    if (mode == FX_KEEP_SEL && (rc = fx_sel_checked(ctx, sel, k))) return rc;
     const u8 *d = (const u8 *)file_bytes;
-    std::unique_ptr<lrge_hip_reads, void (*)(lrge_hip_reads *)> guard(new lrge_hip_reads(), lrge_hip_reads_free);
-    guard->ctx = ctx;
     bool xz_whole;
     const FxBox box = fx_container(d, len, &xz_whole);
-    if (mode != FX_KEEP_ALL && box == FX_BOX_CRAM) {     // (without both flags, whatever the others: FxWinDev::selected_format)
-        if (!cram_select_flags(flags)) { ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only"; return LRGE_ERR_UNPROVEN; }
-        // the sampled ingest of CRAM: no text and no windows -- the walk, then the rounds into a scratch
-        const int crc = fx_cram_sampled(ctx, guard.get(), d, len, mode, sel, k, false, map, t0);
-        if (crc) return crc;
-        *out = guard.release();
-        return LRGE_OK;
-    }
-    // unaligned CRAM, for the caller who asked for it: a host walk and a device decode of the base blocks, no text and no record scan
-    if ((flags & LRGE_GPU_INGEST_CRAM) && box == FX_BOX_CRAM) {
-        const int crc = fx_open_cram(ctx, guard.get(), d, len, t0);
-        if (crc) return crc;
+    if (mode != FX_KEEP_ALL && (rc = fx_sampled_refusal(ctx, box, flags))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const double t0 = fx_now_ms();
+    FxReadsGuard guard = fx_new_reads(ctx);
+    // unaligned CRAM, for the caller who asked for it: a host walk and a device decode of the base blocks, no text and no record scan;
+    // its sampled ingest: no text and no windows either -- the walk, then the rounds into a scratch
+    if (box == FX_BOX_CRAM && (mode != FX_KEEP_ALL || (flags & LRGE_GPU_INGEST_CRAM))) {
+        if ((rc = mode != FX_KEEP_ALL ? fx_cram_sampled(ctx, guard.get(), d, len, mode, sel, k, false, map, t0) : fx_open_cram(ctx, guard.get(), d, len, t0))) return rc;
         *out = guard.release();
         return LRGE_OK;
     }
@@ -829,7 +882,6 @@ static int fx_open_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, 
     // the source, by the file's magic
     std::vector<BgzfBlock> t;
     uint64_t total = 0;
-    int rc;
     if (mode != FX_KEEP_ALL && (rc = s.run->dev.select(mode, sel, k))) return rc;
     if (map) {
         *map = FxSeekMap();
@@ -837,10 +889,7 @@ static int fx_open_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, 
         map->kind = FX_SEEK_OTHER; map->file_len = len;
         s.run->dev.map = map;
     }
-    if (mode != FX_KEEP_ALL && box == FX_BOX_ZSTD && (flags & LRGE_GPU_INFLATE_ZSTD) && !fx_zstd_slides(flags)) {
-        ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only, not Zstandard input";       // (its text is never windowed without LRGE_GPU_INGEST_WINDOWED_ZSTD)
-        rc = LRGE_ERR_UNPROVEN;
-    } else if (box == FX_BOX_GZIP) {
+    if (box == FX_BOX_GZIP) {
         const bool bgzf = bgzf_scan_blocks(d, len, &t, &total);
         if (map && bgzf) { map->kind = FX_SEEK_BGZF; map->n_blocks = t.size(); }
         if (map && !bgzf) { map->kind = FX_SEEK_GZIP; map->gz_spacing = std::max<u64>(1, ctx->opt_u64("INGEST_SEEK_GZIP_BYTES", (u64)1 << 20)); }
@@ -873,39 +922,47 @@ extern "C" int lrge_hip_reads_open_mem(lrge_hip_ctx *ctx, const void *file_bytes
 }
 
 // ---- the selected ingest: a pass that keeps nothing, and one that keeps the chosen records ----
-extern "C" int lrge_hip_reads_census_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, int flags, uint64_t out[4]) {
-    if (!ctx || !out) return LRGE_ERR_INVALID;
-    out[0] = out[1] = out[2] = out[3] = 0;
+// the census, with the seek map it leaves behind when one is asked for; out is zeroed by the caller
+static int fx_census(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, int flags, uint64_t out[4], FxSeekMap *map) {
     lrge_hip_reads *r = nullptr;
-    const int rc = fx_open_mem(ctx, file_bytes, len, flags, FX_KEEP_NONE, nullptr, 0, &r);
+    const int rc = fx_open_mem(ctx, file_bytes, len, flags, FX_KEEP_NONE, nullptr, 0, &r, map);
     if (rc) return rc;
     out[0] = r->sel.seen; out[1] = r->sel.bases_seen; out[2] = r->text_bytes; out[3] = r->win.windows;
     lrge_hip_reads_free(r);
     return LRGE_OK;
 }
 
+extern "C" int lrge_hip_reads_census_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, int flags, uint64_t out[4]) {
+    if (!ctx || !out) return LRGE_ERR_INVALID;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    return fx_census(ctx, file_bytes, len, flags, out, nullptr);
+}
+
 extern "C" int lrge_hip_reads_open_selected_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, int flags, const uint32_t *sel, uint32_t k, lrge_hip_reads **out) {
     return fx_open_mem(ctx, file_bytes, len, flags, FX_KEEP_SEL, sel, k, out);
 }
 
+// the file at `path` as one buffer (raw holds it)
 static int fx_slurp(lrge_hip_ctx *ctx, const char *path, std::string *raw) {
     try { *raw = lrge::io::slurp(path); } catch (const std::exception &e) { ctx->err = e.what(); return LRGE_ERR_IO; }
     return LRGE_OK;
 }
+// ... for the call that takes a path: mem(bytes, len) is its form that takes a buffer
+template <class F> static int fx_with_file(lrge_hip_ctx *ctx, const char *path, F mem) {
+    std::string raw;
+    const int rc = fx_slurp(ctx, path, &raw);
+    return rc ? rc : mem(raw.data(), (uint64_t)raw.size());
+}
 
 extern "C" int lrge_hip_reads_census(lrge_hip_ctx *ctx, const char *path, int flags, uint64_t out[4]) {
     if (!ctx || !path || !out) return LRGE_ERR_INVALID;
-    std::string raw;
-    const int rc = fx_slurp(ctx, path, &raw);
-    return rc ? rc : lrge_hip_reads_census_mem(ctx, raw.data(), raw.size(), flags, out);
+    return fx_with_file(ctx, path, [&](const void *d, uint64_t n) { return lrge_hip_reads_census_mem(ctx, d, n, flags, out); });
 }
 
 extern "C" int lrge_hip_reads_open_selected(lrge_hip_ctx *ctx, const char *path, int flags, const uint32_t *sel, uint32_t k, lrge_hip_reads **out) {
     if (!ctx || !path || !out) return LRGE_ERR_INVALID;
     *out = nullptr;
-    std::string raw;
-    const int rc = fx_slurp(ctx, path, &raw);
-    return rc ? rc : lrge_hip_reads_open_selected_mem(ctx, raw.data(), raw.size(), flags, sel, k, out);
+    return fx_with_file(ctx, path, [&](const void *d, uint64_t n) { return lrge_hip_reads_open_selected_mem(ctx, d, n, flags, sel, k, out); });
 }
 
 extern "C" int lrge_hip_reads_select_stats(const lrge_hip_reads *r, uint64_t out[4]) {
@@ -920,21 +977,15 @@ extern "C" int lrge_hip_reads_census_map_mem(lrge_hip_ctx *ctx, const void *file
     *map = nullptr;
     out[0] = out[1] = out[2] = out[3] = 0;
     std::unique_ptr<lrge_hip_read_map> m(new lrge_hip_read_map());
-    lrge_hip_reads *r = nullptr;
-    const int rc = fx_open_mem(ctx, file_bytes, len, flags, FX_KEEP_NONE, nullptr, 0, &r, &m->m);
-    if (rc) return rc;
-    out[0] = r->sel.seen; out[1] = r->sel.bases_seen; out[2] = r->text_bytes; out[3] = r->win.windows;
-    lrge_hip_reads_free(r);
-    *map = m.release();
-    return LRGE_OK;
+    const int rc = fx_census(ctx, file_bytes, len, flags, out, &m->m);
+    if (!rc) *map = m.release();
+    return rc;
 }
 
 extern "C" int lrge_hip_reads_census_map(lrge_hip_ctx *ctx, const char *path, int flags, uint64_t out[4], lrge_hip_read_map **map) {
     if (!ctx || !path || !out || !map) return LRGE_ERR_INVALID;
     *map = nullptr;
-    std::string raw;
-    const int rc = fx_slurp(ctx, path, &raw);
-    return rc ? rc : lrge_hip_reads_census_map_mem(ctx, raw.data(), raw.size(), flags, out, map);
+    return fx_with_file(ctx, path, [&](const void *d, uint64_t n) { return lrge_hip_reads_census_map_mem(ctx, d, n, flags, out, map); });
 }
 
 extern "C" void lrge_hip_read_map_free(lrge_hip_read_map *map) { delete map; }
@@ -987,13 +1038,17 @@ struct FxInput {
         return true;
     }
 };
+// the whole file in memory, for what takes a buffer: the input is read by its path into raw, unless it is a buffer already
+static int fx_input_whole(lrge_hip_ctx *ctx, FxInput &in, std::string *raw) {
+    if (in.d) return LRGE_OK;
+    const int rc = fx_slurp(ctx, in.path, raw);
+    if (!rc) { in.d = (const u8 *)raw->data(); in.len = raw->size(); }
+    return rc;
+}
 struct FxPinned {
     u8 *p = nullptr;
     ~FxPinned() { if (p) (void)hipHostFree(p); }
 };
-static int fx_read_failed(lrge_hip_ctx *ctx) { ctx->err = "reads_open_mapped: the file could not be read"; return LRGE_ERR_IO; }
-static int fx_map_misfit(lrge_hip_ctx *ctx, const char *what) { LRGE_SET_ERR(ctx, "reads_open_mapped: the map does not fit the input (%s)", what); return LRGE_ERR_UNPROVEN; }
-static int fx_map_range(lrge_hip_ctx *ctx) { ctx->err = "reads_open_mapped: a file range does not hold the blocks of the map"; return LRGE_ERR_INVALID; }
 
 // plain input: the runs' bytes gathered into pinned staging, one copy per window's worth of sub-text
 static int fx_src_seek_raw(FxSink &s, const FxInput &in, const FxSeekPlan &plan) {
@@ -1024,44 +1079,54 @@ static int fx_src_seek_raw(FxSink &s, const FxInput &in, const FxSeekPlan &plan)
 
 // A batch of decoded pieces lies in a staging block: text [o_off, o_off + len) at d_stage + src, the pieces ascending in o_off (BGZF
 // blocks, gzip entries).  What the runs take of them, in order, is the sub-text's next bytes: k_fx_runs copies it to the tail of the
-// sink's block, and the windows take their turn.  ri / rpos: the run that is being brought and its next text byte
+// sink's block, and the windows take their turn (take).  ri / rpos: the run that is being brought and its next text byte.  Behind the
+// last batch every run has been brought, and the block becomes the handle's (finish)
 struct FxPiece { u64 o_off, len, src; };
-static int fx_runs_take(FxSink &s, const FxSeekPlan &plan, size_t *ri_, u64 *rpos_, const std::vector<FxPiece> &pc, const u8 *d_stage, u64 bytes) {
-    lrge_hip_ctx *ctx = s.ctx;
-    size_t &ri = *ri_;
-    u64 &rpos = *rpos_;
-    int rc;
-    std::vector<FxRunCopy> copies;
-    u64 sum = 0;
-    for (size_t b = 0; b < pc.size() && ri < plan.runs.size();) {
-        const FxSeekRun &r = plan.runs[ri];
-        const u64 bo = pc[b].o_off, be = bo + pc[b].len;
-        if (rpos >= r.t1) { if (++ri < plan.runs.size()) rpos = plan.runs[ri].t0; continue; }
-        if (rpos >= be) { ++b; continue; }
-        if (rpos < bo) return fx_map_range(ctx);               // (never: the pieces cover the runs)
-        const u64 m = std::min<u64>(r.t1, be) - rpos, src = pc[b].src + (rpos - bo);
-        if (src + m > bytes) return fx_map_range(ctx);         // (never)
-        if (!copies.empty() && copies.back().src + copies.back().len == src) copies.back().len += m;
-        else copies.push_back(FxRunCopy{src, sum, m});
-        sum += m; rpos += m;
+struct FxRunsTaker {
+    FxSink &s; const FxSeekPlan &plan;
+    size_t ri = 0; u64 rpos;
+    FxRunsTaker(FxSink &s_, const FxSeekPlan &p) : s(s_), plan(p), rpos(p.runs.empty() ? 0 : p.runs[0].t0) {}
+    int take(const std::vector<FxPiece> &pc, const u8 *d_stage, u64 bytes) {
+        lrge_hip_ctx *ctx = s.ctx;
+        int rc;
+        std::vector<FxRunCopy> copies;
+        u64 sum = 0;
+        for (size_t b = 0; b < pc.size() && ri < plan.runs.size();) {
+            const FxSeekRun &r = plan.runs[ri];
+            const u64 bo = pc[b].o_off, be = bo + pc[b].len;
+            if (rpos >= r.t1) { if (++ri < plan.runs.size()) rpos = plan.runs[ri].t0; continue; }
+            if (rpos >= be) { ++b; continue; }
+            if (rpos < bo) return fx_map_range(ctx);               // (never: the pieces cover the runs)
+            const u64 m = std::min<u64>(r.t1, be) - rpos, src = pc[b].src + (rpos - bo);
+            if (src + m > bytes) return fx_map_range(ctx);         // (never)
+            if (!copies.empty() && copies.back().src + copies.back().len == src) copies.back().len += m;
+            else copies.push_back(FxRunCopy{src, sum, m});
+            sum += m; rpos += m;
+        }
+        if (!sum) return LRGE_OK;
+        if (sum >> 32) return s.run->dev.unproven("a window of 2^32 bytes or more");     // (the driver refuses such a block anyway; the grid below is a tile a wavefront)
+        if ((rc = s.room(sum))) return rc;
+        Scratch tables(ctx);                                       // (the batch's: released before the next)
+        std::vector<u64> first(copies.size() + 1, 0);
+        for (size_t c = 0; c < copies.size(); ++c) first[c + 1] = first[c] + div_up(copies[c].len, (u64)FX_RUN_TILE);
+        ALLOC_OR_FAIL(d_copies, tables, FxRunCopy, copies.size());
+        ALLOC_OR_FAIL(d_first, tables, u64, first.size());
+        HIPCHK(ctx, hipMemcpyAsync(d_copies, copies.data(), copies.size() * sizeof(FxRunCopy), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(d_first, first.data(), first.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(k_fx_runs, dim3((u32)first.back()), dim3(64), 0, ctx->stream, d_stage, s.blk.keep + s.blk.keep_len,
+                           (const FxRunCopy *)d_copies, (const u64 *)d_first, (u32)copies.size());
+        KCHK(ctx);
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));            // (the tables are pageable, and the staging is decoded into again)
+        s.blk.keep_len += sum;
+        return s.appended();
     }
-    if (!sum) return LRGE_OK;
-    if (sum >> 32) return s.run->dev.unproven("a window of 2^32 bytes or more");     // (the driver refuses such a block anyway; the grid below is a tile a wavefront)
-    if ((rc = s.room(sum))) return rc;
-    Scratch tables(ctx);                                       // (the batch's: released before the next)
-    std::vector<u64> first(copies.size() + 1, 0);
-    for (size_t c = 0; c < copies.size(); ++c) first[c + 1] = first[c] + div_up(copies[c].len, (u64)FX_RUN_TILE);
-    ALLOC_OR_FAIL(d_copies, tables, FxRunCopy, copies.size());
-    ALLOC_OR_FAIL(d_first, tables, u64, first.size());
-    HIPCHK(ctx, hipMemcpyAsync(d_copies, copies.data(), copies.size() * sizeof(FxRunCopy), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(d_first, first.data(), first.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_fx_runs, dim3((u32)first.back()), dim3(64), 0, ctx->stream, d_stage, s.blk.keep + s.blk.keep_len,
-                       (const FxRunCopy *)d_copies, (const u64 *)d_first, (u32)copies.size());
-    KCHK(ctx);
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));            // (the tables are pageable, and the staging is decoded into again)
-    s.blk.keep_len += sum;
-    return s.appended();
-}
+    int finish() {
+        while (ri < plan.runs.size() && rpos >= plan.runs[ri].t1) if (++ri < plan.runs.size()) rpos = plan.runs[ri].t0;
+        if (ri < plan.runs.size()) return fx_map_range(s.ctx);
+        s.hand_over(s.blk);
+        return LRGE_OK;
+    }
+};
 
 // BGZF: only the blocks some run touches are decoded, each once, in batches of about a window into a staging block; k_fx_runs
 // copies the parts of the runs that lie in a batch to the tail of the sink's block.  The file ranges of the plan are read (or, from
@@ -1091,34 +1156,21 @@ static int fx_src_seek_bgzf(FxSink &s, const FxInput &in, const FxSeekPlan &plan
     }
     const u8 *base = comp.data();
     // batches of blocks of a window's size, as fx_src_bgzf makes them; the staging holds the largest
-    u64 stage_cap = 0;
-    for (size_t i = 0, j; i < fb.size(); i = j) {
-        u64 bytes = 0;
-        for (j = i; j < fb.size() && (j == i || bytes < s.window); ++j) bytes += fb[j].isize;
-        stage_cap = std::max(stage_cap, bytes);
-    }
+    const auto isize = [&](size_t b) { return (u64)fb[b].isize; };
     Scratch sc(ctx);
-    ALLOC_OR_FAIL(d_stage, sc, u8, stage_cap + FX_PAD);
+    ALLOC_OR_FAIL(d_stage, sc, u8, fx_batch_largest(fb.size(), s.window, isize) + FX_PAD);
     int rc;
-    size_t ri = 0;
-    u64 rpos = plan.runs.empty() ? 0 : plan.runs[0].t0;            // the next text byte of run ri to bring
+    FxRunsTaker runs(s, plan);
     for (size_t i = 0, j; i < fb.size(); i = j) {
-        std::vector<BgzfBlock> part;
-        u64 bytes = 0;
-        for (j = i; j < fb.size() && (j == i || bytes < s.window); ++j) {
-            part.push_back(fb[j]);
-            part.back().o_off = bytes;
-            bytes += fb[j].isize;
-        }
+        u64 bytes;
+        j = fx_batch_end(i, fb.size(), s.window, isize, &bytes);
+        const std::vector<BgzfBlock> part = fx_bgzf_part(fb, i, j, 0);
         if ((rc = fx_bgzf_decode(ctx, base, part, d_stage))) return rc;
         std::vector<FxPiece> pc;
         for (size_t b = i; b < j; ++b) pc.push_back(FxPiece{fb[b].o_off, fb[b].isize, part[b - i].o_off});
-        if ((rc = fx_runs_take(s, plan, &ri, &rpos, pc, d_stage, bytes))) return rc;
+        if ((rc = runs.take(pc, d_stage, bytes))) return rc;
     }
-    while (ri < plan.runs.size() && rpos >= plan.runs[ri].t1) if (++ri < plan.runs.size()) rpos = plan.runs[ri].t0;
-    if (ri < plan.runs.size()) return fx_map_range(ctx);
-    s.hand_over(s.blk);
-    return LRGE_OK;
+    return runs.finish();
 }
 
 // Plain and multi-member gzip: only the entries some run touches are decoded, each once and each from its seed by
@@ -1145,12 +1197,8 @@ static int fx_src_seek_gzip(FxSink &s, const FxInput &in, const FxSeekMap &m, co
         }
     if (need.size() != plan.blocks || comp_len != plan.file_bytes) return fx_map_range(ctx);        // (never: the planner counts the same entries and bytes)
     // batches of about a window of text, as fx_src_seek_bgzf makes them; the staging holds the largest
-    u64 stage_cap = 0;
-    for (size_t i = 0, j; i < need.size(); i = j) {
-        u64 bytes = 0;
-        for (j = i; j < need.size() && (j == i || bytes < s.window); ++j) bytes += m.ent[need[j].ent].len;
-        stage_cap = std::max(stage_cap, bytes);
-    }
+    const auto ent_len = [&](size_t a) { return (u64)m.ent[need[a].ent].len; };
+    const u64 stage_cap = fx_batch_largest(need.size(), s.window, ent_len);
     if (stage_cap > s.cap || stage_cap >> 32) return s.over_cap();     // (one entry's text above the budget: its length is a 32-bit count on the device)
     FxPinned pin;
     const u64 win_bytes = (u64)need.size() * GZ_WIN;
@@ -1166,21 +1214,21 @@ static int fx_src_seek_gzip(FxSink &s, const FxInput &in, const FxSeekMap &m, co
     const u8 *d_wins = d_comp + comp_len;       // (read by bytes: no alignment asked)
     if (comp_len + win_bytes) HIPCHK(ctx, hipMemcpyAsync(d_comp, pin.p, (size_t)(comp_len + win_bytes), hipMemcpyHostToDevice, ctx->stream));
     int rc;
-    size_t ri = 0;
-    u64 rpos = plan.runs.empty() ? 0 : plan.runs[0].t0;
-    for (size_t i = 0, j; i < need.size(); i = j) {
+    FxRunsTaker runs(s, plan);
+    for (size_t i = 0, end; i < need.size(); i = end) {
         std::vector<GzEntryTask> task;
         std::vector<FxPiece> pc;
-        u64 bytes = 0;
-        for (j = i; j < need.size() && (j == i || bytes < s.window); ++j) {
+        u64 bytes, at = 0;                      // at: where the entry's text lies in the staging block
+        end = fx_batch_end(i, need.size(), s.window, ent_len, &bytes);
+        for (size_t j = i; j < end; ++j) {
             const u64 b = need[j].ent;
             const FxGzEntry &e = m.ent[b];
             const bool last = b + 1 == m.ent.size();
             const u64 f0 = e.bit >> 3;
-            task.push_back(GzEntryTask{need[j].c_at, bytes, (u32)(fx_gz_cover_end(m, b) - f0), (u32)(e.bit & 7), last ? GZ_NONE : (u32)(m.ent[b + 1].bit - 8 * f0), (u32)e.len,
+            task.push_back(GzEntryTask{need[j].c_at, at, (u32)(fx_gz_cover_end(m, b) - f0), (u32)(e.bit & 7), last ? GZ_NONE : (u32)(m.ent[b + 1].bit - 8 * f0), (u32)e.len,
                                        e.crc, e.valid, b ? (u32)j : GZ_NONE, last ? 1u : 0u});
-            pc.push_back(FxPiece{e.off, e.len, bytes});
-            bytes += e.len;
+            pc.push_back(FxPiece{e.off, e.len, at});
+            at += e.len;
         }
         Scratch tables(ctx);
         std::vector<u32> status(task.size());
@@ -1197,47 +1245,37 @@ static int fx_src_seek_gzip(FxSink &s, const FxInput &in, const FxSeekMap &m, co
                 snprintf(why, sizeof why, "gzip entry %llu: status %u", (unsigned long long)need[i + k].ent, status[k]);
                 return fx_map_misfit(ctx, why);
             }
-        if ((rc = fx_runs_take(s, plan, &ri, &rpos, pc, d_stage, bytes))) return rc;
+        if ((rc = runs.take(pc, d_stage, bytes))) return rc;
     }
-    while (ri < plan.runs.size() && rpos >= plan.runs[ri].t1) if (++ri < plan.runs.size()) rpos = plan.runs[ri].t0;
-    if (ri < plan.runs.size()) return fx_map_range(ctx);
-    s.hand_over(s.blk);
-    return LRGE_OK;
+    return runs.finish();
 }
 
 // One mapped open.  Everything that can be refused is refused before any device work: a selection that is not ascending, a map of
 // another input, an ordinal at or above the map's records
 static int fx_open_mapped(lrge_hip_ctx *ctx, FxInput &in, int flags, const lrge_hip_read_map *map, const u32 *sel, u64 k, lrge_hip_reads **out) {
     *out = nullptr;
-    if ((k && !sel) || !fx_sel_ascending(sel, k)) { ctx->err = "reads_open_selected: the ordinals are not strictly ascending"; return LRGE_ERR_INVALID; }
+    int rc = fx_sel_checked(ctx, sel, k);
+    if (rc) return rc;
     const FxSeekMap &m = map->m;
     u8 h[6] = {0, 0, 0, 0, 0, 0};
     const u64 nh = std::min<u64>(6, in.len);
     if (!in.read(0, nh, h)) return fx_read_failed(ctx);
     const FxBox box = fx_container(h, nh);
+    if (m.kind == FX_SEEK_CRAM && box != FX_BOX_CRAM) return fx_map_other(ctx);
     // what the census and the selected open refuse by name, whatever the map
-    if (box == FX_BOX_CRAM && !cram_select_flags(flags)) { ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only"; return LRGE_ERR_UNPROVEN; }
-    if (box == FX_BOX_CRAM || m.kind == FX_SEEK_CRAM) {      // the mapped open of a CRAM: the walk again, then only the touched slices' blocks
-        if (box != FX_BOX_CRAM) { ctx->err = "reads_open_mapped: the map is of another input"; return LRGE_ERR_INVALID; }
-        std::string raw;
-        int rc;
-        if (!in.d && (rc = fx_slurp(ctx, in.path, &raw))) return rc;
+    if ((rc = fx_sampled_refusal(ctx, box, flags))) return rc;
+    std::string raw;                            // the whole file, where it is not read by range
+    if (box == FX_BOX_CRAM) {                   // the mapped open of a CRAM: the walk again, then only the touched slices' blocks
+        if ((rc = fx_input_whole(ctx, in, &raw))) return rc;
         HIPCHK(ctx, hipSetDevice(ctx->device));
-        std::unique_ptr<lrge_hip_reads, void (*)(lrge_hip_reads *)> guard(new lrge_hip_reads(), lrge_hip_reads_free);
-        guard->ctx = ctx;
+        FxReadsGuard guard = fx_new_reads(ctx);
         FxSeekMap of = m;
-        if ((rc = fx_cram_sampled(ctx, guard.get(), in.d ? in.d : (const u8 *)raw.data(), in.d ? in.len : raw.size(), FX_KEEP_SEL, sel, k, true, &of, fx_now_ms()))) return rc;
+        if ((rc = fx_cram_sampled(ctx, guard.get(), in.d, in.len, FX_KEEP_SEL, sel, k, true, &of, fx_now_ms()))) return rc;
         *out = guard.release();
         return LRGE_OK;
     }
-    if (box == FX_BOX_ZSTD && (flags & LRGE_GPU_INFLATE_ZSTD) && !fx_zstd_slides(flags)) {
-        ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only, not Zstandard input";
-        return LRGE_ERR_UNPROVEN;
-    }
-    const bool aln = (flags & LRGE_GPU_INGEST_BAM) && (flags & LRGE_GPU_INGEST_SELECT_ALN);
-    if (m.fmt == FX_FMT_BAM && !aln) { ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only"; return LRGE_ERR_UNPROVEN; }      // (a BAM map: DESIGN section 25)
-    const bool sam = (flags & LRGE_GPU_INGEST_SAM) && (flags & LRGE_GPU_INGEST_SELECT_SAM);
-    if (m.fmt == FX_FMT_SAM && !sam) { ctx->err = "reads_open_selected: selected ingest takes FASTA / FASTQ only"; return LRGE_ERR_UNPROVEN; }      // (a SAM map: DESIGN section 27)
+    // (a BAM map: DESIGN section 25; a SAM map: section 27)
+    if ((m.fmt == FX_FMT_BAM && !fx_select_aln(flags)) || (m.fmt == FX_FMT_SAM && !fx_select_sam(flags))) return fx_fastx_only(ctx);
     const bool gz = box == FX_BOX_GZIP, packed = gz || box == FX_BOX_BZIP2 || box == FX_BOX_ZSTD || box == FX_BOX_XZ;
     std::vector<BgzfBlock> t;
     u64 total = 0;
@@ -1250,15 +1288,12 @@ static int fx_open_mapped(lrge_hip_ctx *ctx, FxInput &in, int flags, const lrge_
         const bool bgzf = bgzf_scan_blocks(in.d, in.len, &t, &total);
         fits = bgzf == (m.kind == FX_SEEK_BGZF) && (!bgzf || (t.size() == m.n_blocks && total == m.text_bytes));
     }
-    if (!fits) { ctx->err = "reads_open_mapped: the map is of another input"; return LRGE_ERR_INVALID; }
+    if (!fits) return fx_map_other(ctx);
     for (u64 j = 0; j < k; ++j)
-        if (sel[j] >= m.records) { LRGE_SET_ERR(ctx, "reads_open_selected: ordinal %u of %llu records", sel[j], (unsigned long long)m.records); return LRGE_ERR_INVALID; }
+        if (sel[j] >= m.records) return fx_ordinal_rc(ctx, sel[j], m.records);
     if (m.kind == FX_SEEK_OTHER) {              // a container that cannot be entered: the full selected pass, the same handle
-        std::string raw;
-        int rc;
-        if (!in.d && (rc = fx_slurp(ctx, in.path, &raw))) return rc;
         lrge_hip_reads *r = nullptr;
-        if ((rc = fx_open_mem(ctx, in.d ? (const void *)in.d : (const void *)raw.data(), in.d ? in.len : raw.size(), flags, FX_KEEP_SEL, sel, k, &r))) return rc;
+        if ((rc = fx_input_whole(ctx, in, &raw)) || (rc = fx_open_mem(ctx, in.d, in.len, flags, FX_KEEP_SEL, sel, k, &r))) return rc;
         if (r->sel.seen != m.records || r->text_bytes != m.text_bytes) { lrge_hip_reads_free(r); return fx_map_misfit(ctx, "another record count"); }
         *out = r;
         return LRGE_OK;
@@ -1267,14 +1302,12 @@ static int fx_open_mapped(lrge_hip_ctx *ctx, FxInput &in, int flags, const lrge_
     fx_seek_plan(m, sel, k, &plan);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const double t0 = fx_now_ms();
-    std::unique_ptr<lrge_hip_reads, void (*)(lrge_hip_reads *)> guard(new lrge_hip_reads(), lrge_hip_reads_free);
+    FxReadsGuard guard = fx_new_reads(ctx);
     lrge_hip_reads *R = guard.get();
-    R->ctx = ctx;
     FxSink s(ctx, R, flags, FX_KEEP_SEL);
     s.run->dev.mapped = true;
     if (m.fmt == FX_FMT_BAM || m.fmt == FX_FMT_SAM) s.run->dev.kind = m.fmt;      // (the sub-text is never sniffed: it is a record stream, or whole SAM lines, without a header)
-    int rc = s.run->dev.select(FX_KEEP_SEL, plan.sel.data(), k);
-    if (rc) return rc;
+    if ((rc = s.run->dev.select(FX_KEEP_SEL, plan.sel.data(), k))) return rc;
     s.run->attach(&s.blk);
     rc = m.kind == FX_SEEK_PLAIN ? fx_src_seek_raw(s, in, plan) : m.kind == FX_SEEK_GZIP ? fx_src_seek_gzip(s, in, m, plan) : fx_src_seek_bgzf(s, in, plan);
     if (!rc) rc = fx_finish_windowed(s, t0);
@@ -1312,9 +1345,7 @@ extern "C" int lrge_hip_reads_open_mapped(lrge_hip_ctx *ctx, const char *path, i
 extern "C" int lrge_hip_reads_open(lrge_hip_ctx *ctx, const char *path, int flags, lrge_hip_reads **out) {
     if (!ctx || !path || !out) return LRGE_ERR_INVALID;
     *out = nullptr;
-    std::string raw;
-    try { raw = lrge::io::slurp(path); } catch (const std::exception &e) { ctx->err = e.what(); return LRGE_ERR_IO; }
-    return lrge_hip_reads_open_mem(ctx, raw.data(), raw.size(), flags, out);
+    return fx_with_file(ctx, path, [&](const void *d, uint64_t n) { return lrge_hip_reads_open_mem(ctx, d, n, flags, out); });
 }
 
 extern "C" uint64_t lrge_hip_reads_count(const lrge_hip_reads *r) { return r ? r->n : 0; }

@@ -1,6 +1,6 @@
 // host_sam.inl -- the record scan of unaligned SAM text in HBM (k_sam.h): the line table by the census and
 // scatter passes of the FASTQ scan, a mark and a rank per line, then a wavefront per record line.  Included into host_fastx.inl,
-// whose tail (fx_tables_to_host) brings the identifiers and the lengths down.
+// whose tail (fx_scan_tail) takes the table from there.
 
 // the caller has seen the SAM magic at the start of R->d_text, or of the first window.
 // w: the text is a window (fx_window.h).  One that is not the last is cut directly behind its last line feed
@@ -47,31 +47,20 @@ static int sam_parse_device(lrge_hip_ctx *ctx, lrge_hip_reads *R, FxWinScan *w) 
     hipLaunchKernelGGL(k_sam_mark, dim3((u32)div_up(n_lines, SAM_THREADS)), dim3(SAM_THREADS), 0, st, t, n, (const u64 *)ls, c.n_lf, n_lines, d_mark);
     KCHK(ctx);
     if ((rc = scan_exclusive_u32(ctx, sc, d_mark, d_rank, n_lines, (u32 *)(d_flags + 2)))) return rc;
-    u64 n_rec = 0, name_bytes = 0;
+    u64 n_rec = 0;
     HIPCHK(ctx, ctx->d2h(&n_rec, d_flags + 2, 8, st));
     HIPCHK(ctx, ctx->d2h_sync(st));
     if (!n_rec) { R->fmt = FX_FMT_SAM; return LRGE_OK; }    // header lines only: the host returns no record
     if ((rc = fx_alloc_recs(ctx, R, n_rec))) return rc;
-    const FxKeepMode mode = w ? w->dev->mode : FX_KEEP_ALL;
-    if (mode != FX_KEEP_ALL) HIPCHK(ctx, hipMemsetAsync(d_flags + 2, 0, 8, st));      // (the record count is on the host: the word now sums the bases)
+    if (fx_scan_selects(w)) HIPCHK(ctx, hipMemsetAsync(d_flags + 2, 0, 8, st));      // (the record count is on the host: the word now sums the bases)
     ALLOC_OR_FAIL(d_seq_len, sc, u32, n_rec);
     ALLOC_OR_FAIL(d_name_len, sc, u32, n_rec);
     const u32 grid = (u32)std::min<u64>(div_up(n_lines, SAM_WAVES), (u64)ctx->n_cu * 8);
     hipLaunchKernelGGL(k_sam_records, dim3(grid), dim3(SAM_THREADS), 0, st, t, n, (const u64 *)ls, c.n_lf, n_lines, (const u32 *)d_mark, (const u32 *)d_rank, R->d_recs,
                        d_seq_len, d_name_len, (u32 *)d_flags, (unsigned long long *)(d_flags + 1));
     KCHK(ctx);
-    if (mode != FX_KEEP_ALL) {                              // the window's bases come back with the verdict words: no synchronisation of their own
-        u64 bases = 0;
-        hipLaunchKernelGGL(k_fx_bases, dim3((u32)std::min<u64>(div_up(n_rec, FX_THREADS), (u64)ctx->n_cu * 8)), dim3(FX_THREADS), 0, st, (const u32 *)d_seq_len, n_rec,
-                           (unsigned long long *)(d_flags + 2));
-        KCHK(ctx);
-        if ((rc = fx_flags_back(ctx, d_flags, "a SAM record line outside the strict form", &name_bytes, &bases))) return rc;
-        R->fmt = FX_FMT_SAM;
-        if (w->dev->map && (rc = w->dev->seek_window(sc, R, n_rec, n))) return rc;
-        return w->dev->keep_window(sc, R, d_seq_len, d_name_len, n_rec, n, bases);
-    }
-    if ((rc = fx_flags_back(ctx, d_flags, "a SAM record line outside the strict form", &name_bytes))) return rc;
-    R->fmt = FX_FMT_SAM;                                    // (a refused file leaves no read set, so no format either)
-    if ((rc = fx_tables_to_host(ctx, R, sc, n_rec, d_seq_len, d_name_len, name_bytes)) || !w) return rc;
-    return w->dev->store_window(sc, *R, d_seq_len, n);
+    u64 f[3];
+    if ((rc = fx_flags_back(ctx, fx_scan_selects(w), d_flags, d_seq_len, n_rec, f))) return rc;
+    R->fmt = FX_FMT_SAM;                                    // (a refused file leaves no read set: whoever called drops the handle with its format)
+    return fx_scan_tail(ctx, R, sc, w, f, "a SAM record line outside the strict form", d_seq_len, d_name_len, n_rec, n);
 }

@@ -197,9 +197,10 @@ def test_refusals(ctx, knobs, twin):
     assert ei.value.code == _ffi.ERR_INVALID and "the map is of another input" in str(ei.value)
     fq = b"@r\nACGT\n+\nIIII\n"
     _, mfq = ctx.census_map_reads(fq, flags())
-    for src, mp in ((data, mfq), (fq, m)):
+    # (the last: Zstandard that the sampled calls refuse by name under its flag -- a CRAM map on it is of another input first)
+    for src, mp, fl in ((data, mfq, flags()), (fq, m, flags()), (b"\x28\xb5\x2f\xfd" + fq, m, flags() | _ffi.GPU_INFLATE_ZSTD)):
         with pytest.raises(_ffi.LrgeHipError) as ei:
-            ctx.open_reads_mapped(src, mp, [0], flags())
+            ctx.open_reads_mapped(src, mp, [0], fl)
         assert ei.value.code == _ffi.ERR_INVALID and "the map is of another input" in str(ei.value)
     mfq.free(); m2.free()
     # bad selections keep their wording
