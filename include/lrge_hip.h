@@ -647,7 +647,7 @@ int      lrge_hip_reads_select_stats(const lrge_hip_reads *reads, uint64_t out[4
    runs that hold chosen records (from the last point at or below an ordinal to the first point above it; runs that touch are merged)
    are brought: the path form reads only those file ranges, BGZF decodes only their blocks (CRC and ISIZE checked as always).  The
    runs, concatenated, are scanned and proven like any text, and the handle is the one lrge_hip_reads_open_selected* gives -- the
-   same reads, text_bytes and select_stats (seen / bases_seen are the file's, taken from the map).  A map of bzip2 or xz input
+   same reads, text_bytes and select_stats (seen / bases_seen are the file's, taken from the map).  A map of xz input
    runs the full selected pass.  Plain and multi-member gzip is entered (k_gz_entry, k_gz_win_pick): the census
    keeps an entry table -- entry 0 the start of the file, then every accepted chunk of the speculative decode whose text offset is at
    least option INGEST_SEEK_GZIP_BYTES (default 1 MiB, at least 1) behind the previous entry's: its bit offset, text offset, member
@@ -658,12 +658,21 @@ int      lrge_hip_reads_select_stats(const lrge_hip_reads *reads, uint64_t out[4
    INGEST_MAX_BYTES is the selected open's "text above INGEST_MAX_BYTES".
    A gzip map whose only entry is the file's start although the census walked several chunks (a text below the spacing) is not
    entered: its kind is 2 and the mapped open runs the full selected pass.
-   lrge_hip_read_map_entries: out[0] entries, out[1] window bytes held, out[2] the map's kind (0 plain, 1 BGZF, 2 a container that is
-   not entered, 3 CRAM, 4 gzip), out[3] the spacing in force (0: no gzip map).  LRGE_ERR_INVALID, before any device work: ordinals not strictly ascending; "the map is of another
+   bzip2 under LRGE_GPU_INFLATE_BZIP2 is entered too (k_bz_walk_rec, k_bz_rle_write_rec, k_bz_marks_text), FASTA / FASTQ
+   text only.  The census keeps every accepted block -- its bit offset and end bit, the bytes in front of the run-length layer, origPtr,
+   the stored CRC, its text offset and length -- and 64 marks of 16 bytes a block, which let a second decode enter the block's inverse
+   BWT and run-length layer at 64 places (1 KiB a block of host memory outside INGEST_MAX_BYTES).  Entries are groups of whole
+   consecutive blocks: a new one opens at the first block whose text offset is at least option INGEST_SEEK_BZIP2_BYTES (default 512 KiB,
+   at least 1) behind the previous entry's.  A point's c_off is the first byte of the entry that holds its offset; the mapped open reads
+   only the file ranges of the entries the runs touch, and a block whose entropy decode gives another length, origPtr, CRC or end than
+   the map's, or that does not arrive where its marks say, is "the map does not fit the input".  A map whose only entry spans several
+   blocks is not entered (kind 2); a file of one block is.
+   lrge_hip_read_map_entries: out[0] entries, out[1] window bytes (bzip2: mark bytes) held, out[2] the map's kind (0 plain, 1 BGZF, 2 a container that is
+   not entered, 3 CRAM, 4 gzip, 5 bzip2), out[3] the spacing in force (0: neither a gzip nor a bzip2 map).  LRGE_ERR_INVALID, before any device work: ordinals not strictly ascending; "the map is of another
    input" (file length, text bytes, block count or container differ); an ordinal at or above the map's records; and, path form, a
    file range that does not hold the blocks the map names.  LRGE_ERR_UNPROVEN "the map does not fit the input": the runs are not
    proven or hold another number of records than the map says -- the caller may take lrge_hip_reads_open_selected*.
-   lrge_hip_reads_seek_stats: out[0] runs, out[1] text bytes brought, out[2] file bytes read, out[3] BGZF blocks or gzip entries decoded by
+   lrge_hip_reads_seek_stats: out[0] runs, out[1] text bytes brought, out[2] file bytes read, out[3] BGZF blocks or gzip / bzip2 entries decoded by
    lrge_hip_reads_open_mapped*; zeros for a handle of every other open. */
 typedef struct lrge_hip_read_map lrge_hip_read_map;
 int      lrge_hip_reads_census_map(lrge_hip_ctx *ctx, const char *path, int flags, uint64_t out[4], lrge_hip_read_map **map);

@@ -1,8 +1,9 @@
 // bz_core.h -- the bit-level rules of one bzip2 stream: the MSB-first bit reader, the two 48-bit magics, the entropy decode of
 // one block (symbol map, selectors, delta-coded code lengths, canonical tables, Huffman + move-to-front + RUNA/RUNB into the BWT
 // column L), the inverse BWT (counting scatter into packed links, the walk), the run-length layer in front of the BWT ("RLE1":
-// four equal bytes, then a count byte) and bzip2's CRC (MSB first, polynomial 0x04c11db7).  Compiled by hipcc (k_bzip2.h) and g++
-// (bz_twin.cpp) alike; written from the format's description.
+// four equal bytes, then a count byte), bzip2's CRC (MSB first, polynomial 0x04c11db7), and the marks at which a block's walk and
+// run-length layer can be entered again with the seeded decode of one segment.  Compiled by hipcc (k_bzip2.h) and g++
+// (bz_twin.h) alike; written from the format's description.
 //
 // The block decode is written for one wavefront with wavefront-uniform control: every lane walks the same bits and takes the
 // same branches; `lane` / `nl` spread the loops that have independent iterations (table build, move-to-front shift, run fill)
@@ -15,8 +16,10 @@
 
 #ifdef __HIPCC__
 #define BZ_FN __host__ __device__ static inline
+#define BZ_MEM __host__ __device__
 #else
 #define BZ_FN static inline
+#define BZ_MEM
 #endif
 #ifdef __clang__
 #define BZ_UNROLL _Pragma("unroll")
@@ -46,6 +49,7 @@ enum {
     BZ_E_TRAILING = 13,     // bytes behind the stream (a second stream included)
     BZ_E_CHAIN = 14,        // a block ends where neither a block nor the end of the stream starts
     BZ_E_RUN = 15,          // a block stops behind four equal bytes, where their count byte belongs (libbz2 gives an error)
+    BZ_E_ENTRY = 16,        // a block entered at its marks (bz_segment) does not arrive where the seek map says
 };
 
 #define BZ_BLOCK_MAGIC 0x314159265359ull
@@ -273,12 +277,37 @@ BZ_FN void bz_out_put(BzOut &o, uint32_t c) {
     if (((uintptr_t)o.p & 3) == 0) bz_out_flush(o);
 }
 
+// ---- marks: where a block can be entered ----
+// A block of n bytes in front of the run-length layer is cut into BZ_MARKS segments of bz_seg(n) steps of the walk.  Mark j stands in
+// front of step p_j = j * seg, for p_j < n, and holds what a decode needs to start there: the walk pointer `at`, the state of the
+// run-length layer before pre[p_j] is consumed (prev | run << 16; run == 4: pre[p_j] is a count byte), the text bytes pre[0, p_j)
+// gave and the running CRC register there.  A census that leaves a seek map records them on its one walk (the sinks below)
+#define BZ_MARKS 64u
+struct BzMark { uint32_t at, state, off, crc; };
+BZ_FN uint32_t bz_seg(uint32_t n) { const uint32_t s = 4 * ((n + 255) / 256); return s < 4 ? 4u : s; }
+BZ_FN uint32_t bz_mark_count(uint32_t n) { const uint32_t s = bz_seg(n); return (n + s - 1) / s; }      // the marks a block has (the other slots stay zero)
+// the sink a decode without a map passes: nothing is kept, nothing is compiled in
+struct BzNoMarks {
+    BZ_FN void walk(uint32_t, uint32_t) {}
+    BZ_FN void rle(uint32_t, uint32_t, uint32_t, uint32_t, uint32_t) {}
+};
+// the recording sink: m[0, BZ_MARKS) of one block, step `next` is mark j's
+struct BzMarkRec {
+    BzMark *m; uint32_t seg, j, next;
+    BZ_MEM BzMarkRec(BzMark *m_, uint32_t n) : m(m_), seg(bz_seg(n)), j(0), next(0) {}
+    BZ_MEM void walk(uint32_t i, uint32_t at) { if (i == next) { m[j++].at = at; next += seg; } }
+    BZ_MEM void rle(uint32_t i, uint32_t prev, uint32_t run, uint32_t off, uint32_t crc) {
+        if (i == next) { BzMark &k = m[j++]; k.state = prev | run << 16; k.off = off; k.crc = crc; next += seg; }
+    }
+};
+
 // n steps from orig: the block's bytes in front of the run-length layer.  False: a link leaves the block (tt is not a scatter's)
-BZ_FN bool bz_walk(const uint32_t *tt, uint32_t n, uint32_t orig, uint8_t *pre) {
+template <class M> BZ_FN bool bz_walk(const uint32_t *tt, uint32_t n, uint32_t orig, uint8_t *pre, M &&mk) {
     BzOut o{pre, 0, 0};
     uint32_t at = orig;
     for (uint32_t i = 0; i < n; ++i) {
         if (at >= n) return false;
+        mk.walk(i, at);
         const uint32_t e = tt[at];
         bz_out_put(o, e & 255);
         at = e >> 8;
@@ -286,6 +315,7 @@ BZ_FN bool bz_walk(const uint32_t *tt, uint32_t n, uint32_t orig, uint8_t *pre) 
     bz_out_flush(o);
     return true;
 }
+BZ_FN bool bz_walk(const uint32_t *tt, uint32_t n, uint32_t orig, uint8_t *pre) { return bz_walk(tt, n, orig, pre, BzNoMarks()); }
 
 // ---- the run-length layer: four equal bytes, then a count byte of 0..255 more of them ----
 struct BzRle { uint32_t prev, run; };                               // the last byte (256: none) and how often it stands
@@ -303,12 +333,13 @@ BZ_FN uint64_t bz_rle_len(const uint8_t *pre, uint32_t n) {
     return s.run == 4 ? k | BZ_RUN_OPEN : k;
 }
 // the text to out; returns its CRC
-BZ_FN uint32_t bz_rle_write(const uint8_t *pre, uint32_t n, const uint32_t *crc_tab, uint8_t *out) {
+template <class M> BZ_FN uint32_t bz_rle_write(const uint8_t *pre, uint32_t n, const uint32_t *crc_tab, uint8_t *out, M &&mk) {
     BzRle s{256, 0};
     BzOut o{out, 0, 0};
     uint32_t crc = 0xFFFFFFFFu;
     for (uint32_t i = 0; i < n; ++i) {
         const uint32_t c = pre[i];
+        mk.rle(i, s.prev, s.run, (uint32_t)(o.p - out), crc);
         if (s.run == 4) {
             for (uint32_t j = 0; j < c; ++j) { bz_out_put(o, s.prev); crc = crc << 8 ^ crc_tab[crc >> 24 ^ s.prev]; }
             s.run = 0; s.prev = 256;
@@ -320,4 +351,52 @@ BZ_FN uint32_t bz_rle_write(const uint8_t *pre, uint32_t n, const uint32_t *crc_
     }
     bz_out_flush(o);
     return ~crc;
+}
+BZ_FN uint32_t bz_rle_write(const uint8_t *pre, uint32_t n, const uint32_t *crc_tab, uint8_t *out) { return bz_rle_write(pre, n, crc_tab, out, BzNoMarks()); }
+
+// ---- the seeded decode of one segment (k_bz_marks_text; the twin runs the same body lane by lane) ----
+// From mark `mk`, `steps` steps of the walk through tt[0, n), every byte fed straight through the run-length layer and the CRC into
+// the block's text at out + mk.off; the bytes in front of the run-length layer are never stored.  `lim`: the text offset the segment
+// must not pass (the next mark's, the block's length behind the last).  *end: where the segment arrived, for the caller's
+// comparison with the next mark.  False: a link leaves the block, or the text would pass lim -- nothing was loaded from tt at an
+// index >= n, nothing stored outside out[mk.off, lim)
+BZ_FN bool bz_segment(const uint32_t *tt, uint32_t n, const BzMark &mk, uint32_t steps, const uint32_t *crc_tab, uint8_t *out, uint32_t lim, BzMark *end) {
+    uint32_t at = mk.at, prev = mk.state & 0xFFFFu, run = mk.state >> 16, off = mk.off, crc = mk.crc;
+    bool good = off <= lim;
+    BzOut o{out + off, 0, 0};
+    for (uint32_t i = 0; good && i < steps; ++i) {
+        if (at >= n) { good = false; break; }
+        const uint32_t e = tt[at], c = e & 255;
+        at = e >> 8;
+        if (run == 4) {
+            if (c > lim - off) { good = false; break; }
+            for (uint32_t j = 0; j < c; ++j) { bz_out_put(o, prev & 255); crc = crc << 8 ^ crc_tab[crc >> 24 ^ (prev & 255)]; }
+            off += c; run = 0; prev = 256;
+            continue;
+        }
+        if (off >= lim) { good = false; break; }
+        if (c == prev) ++run; else { prev = c; run = 1; }
+        bz_out_put(o, c);
+        crc = crc << 8 ^ crc_tab[crc >> 24 ^ c];
+        ++off;
+    }
+    bz_out_flush(o);
+    end->at = at; end->state = prev | run << 16; end->off = off; end->crc = crc;
+    return good;
+}
+// lane j of a block of n bytes (text length len, origPtr orig, stored CRC crc) whose marks are m[0, BZ_MARKS): its segment, and the
+// comparison at its end -- with mark j + 1, or behind the last segment with origPtr, the text length, a closed run and the stored CRC.
+// True: the segment's text stands and continues into the next
+BZ_FN bool bz_segment_lane(const uint32_t *tt, uint32_t n, uint32_t orig, uint32_t crc, uint32_t len, const BzMark *m, uint32_t j, const uint32_t *crc_tab, uint8_t *out) {
+    const uint32_t seg = bz_seg(n), p = j * seg;
+    if (p >= n) return true;                                         // an idle lane
+    const bool last = p + seg >= n;
+    const BzMark mk = m[j];
+    BzMark want, got;
+    if (last) { want.at = orig; want.off = len; want.crc = ~crc; want.state = 0; }
+    else want = m[j + 1];
+    if (mk.off > want.off || want.off > len) return false;
+    if (!bz_segment(tt, n, mk, last ? n - p : seg, crc_tab, out, want.off, &got)) return false;
+    if (last) return got.at == want.at && got.off == want.off && got.crc == want.crc && (got.state >> 16) != 4;
+    return got.at == want.at && got.off == want.off && got.crc == want.crc && got.state == want.state;
 }

@@ -38,6 +38,34 @@ static inline uint32_t bz_host_bits32(const uint8_t *d, uint64_t n, uint64_t pos
     return bz_peek32(b);
 }
 
+// What a recorder sees of a round, after its checks: the accepted links in order (slot: the candidate among pos / res), the stored CRCs
+// their texts gave, the text offset of the round's first byte and the round's text bytes
+struct BzRound { const uint64_t *pos; const BzRes *res; const BzLink *links; uint32_t m; const uint32_t *stored; uint64_t text_base, out_bytes; };
+
+// The recorder of a census that leaves a seek map (fx_seek.h FX_SEEK_BZIP2; Map: FxSeekMap): it keeps the block
+// table, groups the blocks into entries by the spacing and asks the backend once a round for the marks of the accepted blocks, which
+// `finish` left when the backend was told to record (keep_marks): bool marks_out(BzMark *dst, uint32_t m) -- BZ_MARKS marks a link,
+// in the links' order, in one copy down.  One template for device and twin, as GzSeekRec is
+template <class D, class Map> struct BzSeekRec {
+    Map *m;
+    uint64_t spacing;
+    bool round(D &dev, const BzRound &r) {
+        if (!r.m) return true;
+        for (uint32_t a = 0; a < r.m; ++a) {
+            const BzLink &l = r.links[a];
+            const uint64_t off = r.text_base + l.out_off, len = (a + 1 < r.m ? r.links[a + 1].out_off : r.out_bytes) - l.out_off;
+            if (m->bz_ent.empty() || off >= m->bz_ent.back().off + spacing) m->bz_ent.push_back({m->bz.size(), m->bz.size(), off, 0});
+            auto &e = m->bz_ent.back();
+            m->bz.push_back({r.pos[l.slot], r.res[l.slot].end_bit, off, len, l.n, l.orig, r.stored[a], (uint32_t)(m->bz_ent.size() - 1)});
+            ++e.b1; e.len += len;
+        }
+        const size_t at = m->bz_marks.size();
+        m->bz_marks.resize(at + (size_t)r.m * BZ_MARKS);
+        return dev.marks_out(&m->bz_marks[at], r.m);
+    }
+};
+struct BzNoRec { template <class D> bool round(D &, const BzRound &) { return true; } };
+
 // D (the decode backend):
 //   bool load(const uint8_t *d, uint64_t n)                       the whole compressed input
 //   bool find(std::vector<uint64_t> &cand)                        every bit offset with a magic, ascending (BZ_END_FLAG: the end magic)
@@ -48,10 +76,11 @@ static inline uint32_t bz_host_bits32(const uint8_t *d, uint64_t n, uint64_t pos
 //                                                                 fills tt_off / out_off / run_open, the CRC of every block's text, the text
 // sink(bytes, n) -> bool (false: stop with BZ_RUN_DEVICE)
 // cand_in: a candidate list instead of the finder's (tests).
+// rec: a recorder (rec->round(dev, BzRound) after every round's checks; false: stop with BZ_RUN_DEVICE), or null: nothing more is asked of the backend
 // Returns BZ_RUN_OK, BZ_RUN_DEVICE or a BZ_E_* status (*bad_off: the byte offset it belongs to).
-template <class D, class Sink>
+template <class D, class Sink, class Rec = BzNoRec>
 static int bz_run(D &dev, const uint8_t *d, uint64_t n, uint64_t round_blocks, Sink &&sink, BzStats &st, uint64_t *bad_off,
-                  const std::vector<uint64_t> *cand_in = nullptr) {
+                  const std::vector<uint64_t> *cand_in = nullptr, Rec *rec = nullptr) {
     memset(&st, 0, sizeof st);
     uint64_t bad_dummy = 0;
     uint64_t &bad = bad_off ? *bad_off : bad_dummy;
@@ -98,7 +127,7 @@ static int bz_run(D &dev, const uint8_t *d, uint64_t n, uint64_t round_blocks, S
             stored.push_back(r.crc);
             expect = r.end_bit;
         }
-        const uint64_t first = B[i];
+        const uint64_t first = B[i], *round_pos = &B[i];
         i += j;
         const uint32_t m = (uint32_t)links.size();
         crc.assign(m, 0);
@@ -113,6 +142,7 @@ static int bz_run(D &dev, const uint8_t *d, uint64_t n, uint64_t round_blocks, S
             combined = bz_rotl1(combined) ^ crc[a];
         }
         st.blocks += m;
+        if (rec && !rec->round(dev, BzRound{round_pos, res.data(), links.data(), m, stored.data(), st.bytes_out, out_bytes})) return BZ_RUN_DEVICE;
         if (out_bytes && !sink(bytes, out_bytes)) return BZ_RUN_DEVICE;
         st.bytes_out += out_bytes;
     }

@@ -12,6 +12,7 @@
 #include "fastx_core.h"
 #include "win_twin.h"
 #include "gz_twin.h"
+#include "bz_twin.h"
 
 namespace fastx_twin {           // (a name of its own: tools/window_twin_check.cpp holds the three twins in one translation unit)
 namespace {
@@ -169,7 +170,8 @@ struct Scan {
 WinTwinOut gw;
 FxSeekMap gm;                           // the map of the last fastx_twin_census_map
 FxSeekPlan gp;                          // the plan of the last fastx_twin_seek_plan / fastx_twin_mapped
-std::vector<uint8_t> gz_text;           // the text of the last fastx_twin_gz_census_map
+std::vector<uint8_t> gz_text;           // the text of the last fastx_twin_gz_census_map / fastx_twin_bz_census_map
+BzStats bz_st;                          // what bz_run counted in the last fastx_twin_bz_census_map
 }  // namespace
 
 extern "C" {
@@ -364,6 +366,117 @@ int fastx_twin_gz_mapped(const uint8_t *d, uint64_t n, uint64_t tile, uint64_t w
             const uint64_t a = std::max(r.t0, e.off), z = std::min(r.t1, e.off + e.len);
             if (a < z) sub.insert(sub.end(), txt.begin() + (long)(a - e.off), txt.begin() + (long)(z - e.off));
         }
+    if (decoded != gp.blocks || sub.size() != gp.text_bytes) return (int)FX_UNPROVEN;       // (never: the planner counts what is decoded)
+    Scan sc = {tile, false};
+    int rc = win_twin_run(sc, sub.data(), sub.size(), window, piece, true, gw, FX_KEEP_SEL, gp.sel.data(), k);
+    if (rc == WIN_TWIN_INVALID || (!rc && gw.sel.seen != gp.records)) rc = (int)FX_UNPROVEN;
+    if (rc) { gw = WinTwinOut(); return rc; }
+    win_twin_mapped_back(gw, gp, gm);
+    return 0;
+}
+// ---- the seek map of bzip2 (fx_seek.h FX_SEEK_BZIP2) ----
+// The census with a map on bzip2 bytes: bz_run over the twin's backend with the recorder the device uses (round_blocks as
+// bz_twin_inflate; entries every `spacing` text bytes), the text through the windows with the point rule, the entries attached to the
+// points.  A stream bz_run does not accept is FX_UNPROVEN, as on the device.  The text by fastx_twin_gz_text, bz_run's counts by
+// fastx_twin_bz_stats (blocks, candidates, rejected candidates, rounds, bytes out)
+int fastx_twin_bz_census_map(const uint8_t *d, uint64_t n, uint64_t round_blocks, uint64_t spacing, uint64_t tile, uint64_t window, uint64_t piece, uint64_t stride, uint64_t out[4]) {
+    gw = WinTwinOut(); gm = FxSeekMap(); gz_text.clear(); bz_st = BzStats{0, 0, 0, 0, 0};
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (tile < 16 || tile % 16 || !piece || !stride || !spacing) return -1;
+    FxSeekMap m;
+    m.stride = stride; m.bz_spacing = spacing; m.kind = FX_SEEK_BZIP2; m.file_len = n; m.bz_level = n >= 4 ? d[3] : 0;
+    BzTwin t;
+    t.keep_marks = true;
+    BzSeekRec<BzTwin, FxSeekMap> rec = {&m, spacing};
+    if (bz_run(t, d, n, round_blocks, [&](const uint8_t *b, uint64_t k) { gz_text.insert(gz_text.end(), b, b + k); return true; }, bz_st, nullptr, nullptr, &rec))
+        return (int)FX_UNPROVEN;
+    Scan sc = {tile};
+    const int rc = win_twin_run(sc, gz_text.data(), gz_text.size(), window, piece, true, gw, FX_KEEP_NONE, nullptr, 0, &m);
+    if (rc) { m.pts.clear(); m.n_blocks = m.bz_ent.size(); gm = m; return rc; }   // (blocks, marks and text stay readable: they are the bzip2 side's alone)
+    out[0] = gw.sel.seen; out[1] = gw.sel.bases_seen; out[2] = gz_text.size(); out[3] = gw.st.windows;
+    m.records = gw.sel.seen; m.bases = gw.sel.bases_seen; m.text_bytes = gz_text.size(); m.windows = gw.st.windows; m.fmt = gw.fmt;
+    fx_seek_attach_bzip2(m);
+    gm = m;
+    return 0;
+}
+void fastx_twin_bz_stats(uint64_t out[5]) { out[0] = bz_st.blocks; out[1] = bz_st.candidates; out[2] = bz_st.rejected; out[3] = bz_st.rounds; out[4] = bz_st.bytes_out; }
+// would the device enter the last map (fx_bz_enterable)?  The twin's own passes enter every map: they test the decode
+int fastx_twin_bz_enterable(void) { return fx_bz_enterable(gm) ? 1 : 0; }
+
+// the entries of the last map, six words each: first block, the block behind the last, text offset, text length, first file byte, the
+// file byte behind the last; returns how many there are
+uint64_t fastx_twin_bz_entries(uint64_t *out, uint64_t cap) {
+    for (uint64_t i = 0; i < gm.bz_ent.size() && i < cap; ++i) {
+        const FxBzEntry &e = gm.bz_ent[i];
+        uint64_t *o = out + 6 * i;
+        o[0] = e.b0; o[1] = e.b1; o[2] = e.off; o[3] = e.len; o[4] = fx_bz_cover_begin(gm, i); o[5] = fx_bz_cover_end(gm, i);
+    }
+    return gm.bz_ent.size();
+}
+// ... its blocks, eight words each: bit, end bit, text offset, text length, n, origPtr, stored CRC, entry
+uint64_t fastx_twin_bz_blocks(uint64_t *out, uint64_t cap) {
+    for (uint64_t i = 0; i < gm.bz.size() && i < cap; ++i) {
+        const FxBzBlock &b = gm.bz[i];
+        uint64_t *o = out + 8 * i;
+        o[0] = b.bit; o[1] = b.end_bit; o[2] = b.off; o[3] = b.len; o[4] = b.n; o[5] = b.orig; o[6] = b.crc; o[7] = b.ent;
+    }
+    return gm.bz.size();
+}
+// ... the marks of block b, four words each (at, state, text offset, CRC register), FX_BZ_MARKS of them; and one word of one overwritten (a damaged map)
+void fastx_twin_bz_marks(uint64_t b, uint32_t *out) { memcpy(out, &gm.bz_marks[b * FX_BZ_MARKS], FX_BZ_MARKS * sizeof(BzMark)); }
+void fastx_twin_bz_poke_mark(uint64_t b, uint32_t j, uint32_t word, uint32_t v) { ((uint32_t *)&gm.bz_marks[b * FX_BZ_MARKS + j])[word] = v; }
+
+// Block b of the last map entered out of file d[0, n) -- which may be a damaged copy of the census's -- the text at byte `skew` of a 4-byte
+// aligned area: lane j alone from its mark (its segment, out[0, *len) the bytes between mark j's text offset and the next's), or, with
+// j >= FX_BZ_MARKS, the whole block by every lane (out[0, *len) its text).  0, a decode status or BZ_E_ENTRY; -1 when a byte outside
+// the lane's (the block's) text range was written
+int fastx_twin_bz_segment(const uint8_t *d, uint64_t n, uint64_t b, uint32_t j, uint32_t skew, uint8_t *out, uint64_t *len) {
+    *len = 0;
+    if (b >= gm.bz.size() || n < 4) return -1;
+    const FxBzBlock &k = gm.bz[b];
+    const BzMark *m = &gm.bz_marks[b * FX_BZ_MARKS];
+    const uint32_t nm = bz_mark_count(k.n);
+    uint64_t t0 = 0, t1 = k.len;
+    if (j < FX_BZ_MARKS) { if (j >= nm) return 0; t0 = m[j].off; t1 = j + 1 < nm ? m[j + 1].off : k.len; }
+    if (t0 > t1 || t1 > k.len) return (int)BZ_E_ENTRY;
+    std::vector<uint32_t> area((size_t)((skew + k.len + 64) / 4 + 1), 0xA5A5A5A5u);
+    uint8_t *a = (uint8_t *)area.data();
+    const uint32_t rc = bz_twin_seeded(d, n, (uint32_t)(gm.bz_level - '0') * 100000u, k.bit, k.end_bit - k.bit, k.n, k.orig, k.crc, (uint32_t)k.len, m, a + skew, j);
+    for (uint64_t i = 0; i < area.size() * 4; ++i) if ((i < skew + t0 || i >= skew + t1) && a[i] != 0xA5) return -1;
+    if (!rc && t1 > t0) memcpy(out, a + skew + t0, (size_t)(t1 - t0));
+    if (!rc) *len = t1 - t0;
+    return (int)rc;
+}
+
+// The mapped second pass over bzip2 file d, which must have the length of the last map's (WIN_TWIN_INVALID): the plan, every block of the
+// entries the runs touch entered once at its marks, the sub-text built from what the runs take of them, and the selecting run over it,
+// as fastx_twin_mapped.  A block that fails its checks is FX_UNPROVEN (*status: its decode status or BZ_E_ENTRY): the map does not fit the input
+int fastx_twin_bz_mapped(const uint8_t *d, uint64_t n, uint64_t tile, uint64_t window, uint64_t piece, const uint32_t *sel, uint64_t k, uint32_t *status) {
+    gw = WinTwinOut(); gp = FxSeekPlan();
+    if (status) *status = 0;
+    if (tile < 16 || tile % 16 || !piece) return -1;
+    if (n != gm.file_len || gm.kind != FX_SEEK_BZIP2 || win_twin_sel_fits(gm, sel, k)) return WIN_TWIN_INVALID;
+    fx_seek_plan(gm, sel, k, &gp);
+    std::vector<uint8_t> sub;
+    uint64_t prev_b1 = 0, decoded = 0;
+    bool any = false;
+    for (const FxSeekRun &r : gp.runs) {
+        for (uint64_t e = r.b0; e < r.b1; ++e) {
+            if (any && e < prev_b1) continue;                // (decoded for the run before: its text is in `last`)
+            ++decoded;
+        }
+        for (uint64_t e = r.b0; e < r.b1; ++e)
+            for (uint64_t b = gm.bz_ent[e].b0; b < gm.bz_ent[e].b1; ++b) {
+                const FxBzBlock &q = gm.bz[b];
+                const uint64_t a = std::max(r.t0, q.off), z = std::min(r.t1, q.off + q.len);
+                std::vector<uint32_t> al((size_t)(q.len / 4 + 4));
+                uint8_t *txt = (uint8_t *)al.data() + (sub.size() & 3);
+                const uint32_t rc = bz_twin_seeded(d, n, (uint32_t)(gm.bz_level - '0') * 100000u, q.bit, q.end_bit - q.bit, q.n, q.orig, q.crc, (uint32_t)q.len, &gm.bz_marks[b * FX_BZ_MARKS], txt);
+                if (rc) { if (status) *status = rc; return (int)FX_UNPROVEN; }
+                if (a < z) sub.insert(sub.end(), txt + (a - q.off), txt + (z - q.off));
+            }
+        prev_b1 = r.b1; any = true;
+    }
     if (decoded != gp.blocks || sub.size() != gp.text_bytes) return (int)FX_UNPROVEN;       // (never: the planner counts what is decoded)
     Scan sc = {tile, false};
     int rc = win_twin_run(sc, sub.data(), sub.size(), window, piece, true, gw, FX_KEEP_SEL, gp.sel.data(), k);

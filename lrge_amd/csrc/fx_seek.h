@@ -22,12 +22,14 @@
 #include <vector>
 
 #include "bgzf_scan.h"
+#include "bz_core.h"
 #include "fx_window.h"
 
-// OTHER: a container that cannot be entered (bzip2, xz); CRAM: no text at all -- a point is a slice (cram_round.h cram_seek_map:
+// OTHER: a container that cannot be entered (xz), or is not worth entering; CRAM: no text at all -- a point is a slice (cram_round.h cram_seek_map:
 // ord the first record that starts in it, off its base offset, c_off the file offset of its BA block, blk the slice), n_blocks the slices;
-// GZIP: plain or multi-member gzip, entered at the entries below, n_blocks the entries
-enum { FX_SEEK_PLAIN = 0, FX_SEEK_BGZF = 1, FX_SEEK_OTHER = 2, FX_SEEK_CRAM = 3, FX_SEEK_GZIP = 4 };
+// GZIP: plain or multi-member gzip, entered at the entries below, n_blocks the entries;
+// BZIP2: entered at whole blocks, a block at its marks, n_blocks the entries
+enum { FX_SEEK_PLAIN = 0, FX_SEEK_BGZF = 1, FX_SEEK_OTHER = 2, FX_SEEK_CRAM = 3, FX_SEEK_GZIP = 4, FX_SEEK_BZIP2 = 5 };
 #define FX_SEEK_NONE 0xFFFFFFFFu                                     // a cell's slot without a record start
 
 // the record-start rule: a record starts `lead` bytes in front of its identifier
@@ -51,6 +53,17 @@ struct FxSeekPoint { uint64_t ord, off, c_off, o_off; uint32_t c_len; uint32_t b
 #define FX_GZ_SLACK 16u
 struct FxGzEntry { uint64_t bit, off, len; uint32_t crc, valid, in_member, pad; };
 
+// One accepted block of a bzip2 file (bz_round.h BzSeekRec): it starts at absolute bit offset `bit` (its magic) and ends in front of
+// `end_bit`; n bytes in front of the run-length layer, origPtr `orig`, the stored block CRC `crc`; its text is [off, off + len) and it
+// belongs to entry `ent`.  Block b's marks are bz_marks[b * FX_BZ_MARKS ..] (bz_core.h BzMark): 1 KiB a block of host memory outside
+// INGEST_MAX_BYTES, about 0.1 % of a level-9 block.
+// An entry is a group of whole consecutive blocks [b0, b1): a new one opens at the first accepted block whose text offset is at least
+// the spacing behind the previous entry's.  Its file bytes run from bit >> 3 of its first block to (end_bit + 7) >> 3 of its last,
+// without slack: a block decoded from a true start stops by itself
+#define FX_BZ_MARKS BZ_MARKS
+struct FxBzBlock { uint64_t bit, end_bit, off, len; uint32_t n, orig, crc, ent; };
+struct FxBzEntry { uint64_t b0, b1, off, len; };
+
 struct FxSeekMap {
     uint64_t records = 0, bases = 0, text_bytes = 0, file_len = 0, n_blocks = 0, stride = 65536, windows = 0;
     int kind = FX_SEEK_PLAIN, fmt = FX_FMT_EMPTY;
@@ -60,6 +73,11 @@ struct FxSeekMap {
     std::vector<uint8_t> ent_win;                // ... and their windows
     uint64_t gz_spacing = 0;                     // ... and the spacing they were taken at (option INGEST_SEEK_GZIP_BYTES)
     uint64_t gz_links = 0;                       // ... and the accepted chunks of the census they were taken from
+    std::vector<FxBzBlock> bz;                   // FX_SEEK_BZIP2: the accepted blocks in file order; block 0 is bit 32
+    std::vector<BzMark> bz_marks;                // ... their marks
+    std::vector<FxBzEntry> bz_ent;               // ... the entries
+    uint64_t bz_spacing = 0;                     // ... the spacing they were taken at (option INGEST_SEEK_BZIP2_BYTES)
+    uint32_t bz_level = 0;                       // ... and the level byte of the stream header ('1'..'9')
 };
 
 // Is a gzip map worth entering?  Not when the spacing left entry 0 alone although the census walked several chunks: the mapped open
@@ -73,6 +91,12 @@ static inline uint64_t fx_gz_cover_end(const FxSeekMap &m, uint64_t i) {
     const uint64_t e = (m.ent[i + 1].bit >> 3) + FX_GZ_SLACK;
     return e < m.file_len ? e : m.file_len;
 }
+
+// Is a bzip2 map worth entering?  Not when its only entry spans several blocks: nothing could be skipped.  A file of one block is one
+// entry and is entered
+static inline bool fx_bz_enterable(const FxSeekMap &m) { return m.bz_ent.size() > 1 || m.bz.size() <= 1; }
+static inline uint64_t fx_bz_cover_begin(const FxSeekMap &m, uint64_t i) { return m.bz[m.bz_ent[i].b0].bit >> 3; }
+static inline uint64_t fx_bz_cover_end(const FxSeekMap &m, uint64_t i) { return (m.bz[m.bz_ent[i].b1 - 1].end_bit + 7) >> 3; }
 
 // the point rule: record `ord` starts at text offset `off`; records arrive in file order.  A window's first cell may be one an
 // earlier window gave a point to: the earlier point stands
@@ -105,8 +129,21 @@ static inline void fx_seek_attach_gzip(FxSeekMap &m) {
     }
 }
 
+// ... and from the entry table of a bzip2 map, in the same way
+static inline void fx_seek_attach_bzip2(FxSeekMap &m) {
+    const uint64_t n = m.bz_ent.size();
+    m.n_blocks = n;
+    uint64_t b = 0;
+    for (FxSeekPoint &p : m.pts) {
+        while (b < n && m.bz_ent[b].off + m.bz_ent[b].len <= p.off) ++b;
+        if (b == n) return;                      // (never: a point lies inside the text)
+        p.c_off = fx_bz_cover_begin(m, b); p.o_off = m.bz_ent[b].off; p.c_len = (uint32_t)(fx_bz_cover_end(m, b) - p.c_off); p.blk = (uint32_t)b;
+    }
+}
+
 // one run: records [ord0, ord0 + n_rec), text [t0, t1).  BGZF: blocks [b0, b1), which are file bytes [f0, f1), the first of them
-// starting at text offset o0; gzip: entries [b0, b1), file bytes [f0, f1) with the slack of the last; plain: f0 = t0, f1 = t1, no blocks
+// starting at text offset o0; gzip: entries [b0, b1), file bytes [f0, f1) with the slack of the last; bzip2: entries [b0, b1), file bytes
+// [f0, f1) -- two entries may share the byte in which one ends and the next starts; plain: f0 = t0, f1 = t1, no blocks
 struct FxSeekRun { uint64_t ord0, n_rec, t0, t1, f0, f1, b0, b1, o0; };
 
 struct FxSeekPlan {
@@ -136,7 +173,7 @@ static inline void fx_seek_plan(const FxSeekMap &m, const uint32_t *sel, uint64_
         run.ord0 = a.ord; run.t0 = a.off;
         run.n_rec = (to_end ? m.records : m.pts[behind[r]].ord) - a.ord;
         run.t1 = to_end ? m.text_bytes : m.pts[behind[r]].off;
-        if (m.kind == FX_SEEK_BGZF || m.kind == FX_SEEK_GZIP) {
+        if (m.kind == FX_SEEK_BGZF || m.kind == FX_SEEK_GZIP || m.kind == FX_SEEK_BZIP2) {
             run.b0 = a.blk; run.f0 = a.c_off; run.o0 = a.o_off;
             if (to_end) { run.b1 = m.n_blocks; run.f1 = m.file_len; }
             else {
@@ -146,6 +183,7 @@ static inline void fx_seek_plan(const FxSeekMap &m, const uint32_t *sel, uint64_
                 run.f1 = whole ? z.c_off : z.c_off + z.c_len;
             }
             if (m.kind == FX_SEEK_GZIP) run.f1 = fx_gz_cover_end(m, run.b1 - 1);     // (an entry's bytes reach past the next entry's first)
+            if (m.kind == FX_SEEK_BZIP2) run.f1 = fx_bz_cover_end(m, run.b1 - 1);    // (... may share the next entry's first; the last ends in front of the stream's trailer)
             const uint64_t b_from = r && prev_b1 > run.b0 ? prev_b1 : run.b0, f_from = r && prev_f1 > run.f0 ? prev_f1 : run.f0;
             p->blocks += run.b1 > b_from ? run.b1 - b_from : 0;
             p->file_bytes += run.f1 > f_from ? run.f1 - f_from : 0;

@@ -5,6 +5,10 @@
 // candidates decoded per round; its default is what half of the arena's idle bytes plus the device's free bytes hold at
 // bz_candidate_bytes per candidate, at most BZ_ROUND_MAX.  Option BZIP2_TIMING: the stages are separated by synchronisations and
 // their times are printed to stderr when the call ends (tools/bzip2_bench.py).
+//
+// A census that leaves a seek map sets keep_marks: finish launches the recording forms of the walk and the
+// run-length write, and the recorder of bz_round.h fetches the round's marks in one copy (marks_out).  Without it nothing else is
+// launched, copied or reported.  The mapped open enters blocks at their marks through stage_up / seeded (fx_src_seek_bzip2).
 
 #include "dev_keep.h"
 
@@ -25,19 +29,20 @@ static const char *bz_status_name(int s) {
     case BZ_E_TRAILING: return "bytes behind the end of the stream";
     case BZ_E_CHAIN: return "a block ends where no block starts";
     case BZ_E_RUN: return "a block stops behind four equal bytes";
+    case BZ_E_ENTRY: return "a block does not arrive where its marks say";
     default: return "unknown status";
     }
 }
 
 namespace {
 struct BzDev : DevKeep {
-    GzBuf in, list, count, pos, res, L, cnt, links, tt, lens, crc, out, bad;
+    GzBuf in, list, count, pos, res, L, cnt, links, tt, lens, crc, out, bad, marks, tasks;
     u64 n = 0;
     u32 bs = 0;
-    bool timing = false;
-    double ms[5] = {0, 0, 0, 0, 0};                               // find, entropy, scatter, walk, run-length layer and CRC
+    bool timing = false, keep_marks = false;
+    double ms[6] = {0, 0, 0, 0, 0, 0};                            // find, entropy, scatter, walk, run-length layer and CRC, the seeded decode (k_bz_marks_text)
     explicit BzDev(lrge_hip_ctx *c) : DevKeep(c) {
-        for (GzBuf *b : {&in, &list, &count, &pos, &res, &L, &cnt, &links, &tt, &lens, &crc, &out, &bad}) b->ctx = c;
+        for (GzBuf *b : {&in, &list, &count, &pos, &res, &L, &cnt, &links, &tt, &lens, &crc, &out, &bad, &marks, &tasks}) b->ctx = c;
         timing = c->opt("BZIP2_TIMING") != nullptr;
     }
     ~BzDev() { (void)hipStreamSynchronize(ctx->stream); }
@@ -94,6 +99,7 @@ struct BzDev : DevKeep {
             return false;
         if (!ok(hipMemcpyAsync(links.p, l, (size_t)m * sizeof(BzLink), hipMemcpyHostToDevice, st)) || !ok(hipMemsetAsync(bad.p, 0, 4, st))) return false;
         const u32 lane_blocks = (u32)div_up(m, 64);
+        if (keep_marks && (!marks.need((size_t)m * BZ_MARKS * sizeof(BzMark), &e) || !ok(hipMemsetAsync(marks.p, 0, (size_t)m * BZ_MARKS * sizeof(BzMark), st)))) return false;
         {
             Lap lap(*this, ms[2], timing);
             hipLaunchKernelGGL(k_bz_scatter, dim3(m), dim3(64), 0, st, links.as<const BzLink>(), m, bs, L.as<const u8>(), cnt.as<const u32>(), tt.as<u32>());
@@ -101,7 +107,8 @@ struct BzDev : DevKeep {
         }
         {
             Lap lap(*this, ms[3], timing);
-            hipLaunchKernelGGL(k_bz_walk, dim3(lane_blocks), dim3(64), 0, st, links.as<const BzLink>(), m, bs, tt.as<const u32>(), L.as<u8>(), bad.as<u32>());
+            if (keep_marks) hipLaunchKernelGGL(k_bz_walk_rec, dim3(lane_blocks), dim3(64), 0, st, links.as<const BzLink>(), m, bs, tt.as<const u32>(), L.as<u8>(), bad.as<u32>(), marks.as<BzMark>());
+            else hipLaunchKernelGGL(k_bz_walk, dim3(lane_blocks), dim3(64), 0, st, links.as<const BzLink>(), m, bs, tt.as<const u32>(), L.as<u8>(), bad.as<u32>());
             if (!ok(hipGetLastError()) || !lap.end()) return false;
         }
         Lap lap(*this, ms[4], timing);
@@ -119,7 +126,8 @@ struct BzDev : DevKeep {
         if (to_host) { if (!out.need((size_t)total + 4, &e)) return false; dst = out.as<u8>(); }
         else { if (!keep_reserve(total)) return false; dst = keep + keep_len; }
         if (!ok(hipMemcpyAsync(links.p, l, (size_t)m * sizeof(BzLink), hipMemcpyHostToDevice, st))) return false;
-        hipLaunchKernelGGL(k_bz_rle_write, dim3(lane_blocks), dim3(64), 0, st, links.as<const BzLink>(), m, bs, L.as<const u8>(), dst, crc.as<u32>());
+        if (keep_marks) hipLaunchKernelGGL(k_bz_rle_write_rec, dim3(lane_blocks), dim3(64), 0, st, links.as<const BzLink>(), m, bs, L.as<const u8>(), dst, crc.as<u32>(), marks.as<BzMark>());
+        else hipLaunchKernelGGL(k_bz_rle_write, dim3(lane_blocks), dim3(64), 0, st, links.as<const BzLink>(), m, bs, L.as<const u8>(), dst, crc.as<u32>());
         if (!ok(hipGetLastError())) return false;
         if (!ok(hipMemcpyAsync(crc_h, crc.p, (size_t)m * 4, hipMemcpyDeviceToHost, st))) return false;
         if (!lap.end()) return false;
@@ -128,6 +136,43 @@ struct BzDev : DevKeep {
         if (!(*bytes = deliver(dst, total)) || (!to_host && !sync())) return false;
         *out_bytes = total;
         return true;
+    }
+    // the marks finish left for its m links, BZ_MARKS a link, in one copy down (bz_round.h BzSeekRec)
+    bool marks_out(BzMark *dst, uint32_t m) {
+        return ok(hipMemcpyAsync(dst, marks.p, (size_t)m * BZ_MARKS * sizeof(BzMark), hipMemcpyDeviceToHost, ctx->stream)) && sync();
+    }
+
+    // ---- the mapped open (fx_src_seek_bzip2) ----
+    // `total` staged bytes at host pointer h (pinned) in one copy up: comp_len bytes of file ranges back to back, zeros up to marks_at
+    // (a multiple of 16, at least BZ_PAD of them), then the needed blocks' marks.  decode() then takes positions rebased to the ranges
+    u64 marks_at = 0;
+    bool stage_up(const u8 *h, u64 comp_len, u64 at, u64 total) {
+        n = comp_len; marks_at = at;
+        if (!in.need((size_t)total + 16, &e)) return false;
+        return ok(hipMemcpyAsync(in.p, h, (size_t)total, hipMemcpyHostToDevice, ctx->stream));
+    }
+    // m blocks that decode() left in slots 0..m-1 (l: slot, n, orig; tt_off is filled here; t: the same blocks' tasks, tt_off filled
+    // here too) entered at their marks: the scatter, then one wavefront a block writes its text to d_out + t[a].out_off.  status[a]: BZ_OK or BZ_E_ENTRY
+    bool seeded(BzLink *l, BzMarkTask *t, uint32_t m, u8 *d_out, u32 *status) {
+        hipStream_t st = ctx->stream;
+        u64 links_n = 0;
+        for (uint32_t a = 0; a < m; ++a) { l[a].tt_off = t[a].tt_off = links_n; links_n += l[a].n; }
+        if (!links.need((size_t)m * sizeof(BzLink), &e) || !tasks.need((size_t)m * sizeof(BzMarkTask), &e) || !tt.need((size_t)links_n * 4, &e) || !crc.need((size_t)m * 4, &e)) return false;
+        if (!ok(hipMemcpyAsync(links.p, l, (size_t)m * sizeof(BzLink), hipMemcpyHostToDevice, st)) || !ok(hipMemcpyAsync(tasks.p, t, (size_t)m * sizeof(BzMarkTask), hipMemcpyHostToDevice, st)))
+            return false;
+        {
+            Lap lap(*this, ms[2], timing);
+            hipLaunchKernelGGL(k_bz_scatter, dim3(m), dim3(64), 0, st, links.as<const BzLink>(), m, bs, L.as<const u8>(), cnt.as<const u32>(), tt.as<u32>());
+            if (!ok(hipGetLastError()) || !lap.end()) return false;
+        }
+        Lap lap(*this, ms[5], timing);
+        hipLaunchKernelGGL(k_bz_marks_text, dim3(m), dim3(64), 0, st, tasks.as<const BzMarkTask>(), m, tt.as<const u32>(), (const BzMark *)(in.as<const u8>() + marks_at), d_out, crc.as<u32>());
+        if (!ok(hipGetLastError())) return false;
+        if (!ok(hipMemcpyAsync(status, crc.p, (size_t)m * 4, hipMemcpyDeviceToHost, st)) || !sync()) return false;     // (links and tasks are pageable: their copies are done)
+        return lap.end();
+    }
+    void print_timing() const {
+        if (timing) fprintf(stderr, "[lrge_hip] bzip2 stages ms: find %.3f entropy %.3f scatter %.3f walk %.3f rle_crc %.3f marks_text %.3f\n", ms[0], ms[1], ms[2], ms[3], ms[4], ms[5]);
     }
 };
 }  // namespace

@@ -41,7 +41,7 @@ struct lrge_hip_reads {
     CramStats cram;                             // lrge_hip_reads_cram_stats
     uint64_t zs_slide[4] = {0, 0, 0, 0};        // lrge_hip_reads_zstd_stats: the sliding Zstandard rounds of the call (zeros: it did not slide)
     FxSelStats sel = {0, 0, 0, 0};              // lrge_hip_reads_select_stats: the pass of lrge_hip_reads_open_selected* (a window: what it adds)
-    u64 seek[4] = {0, 0, 0, 0};                 // lrge_hip_reads_seek_stats: runs, text bytes brought, file bytes read, BGZF blocks or gzip entries decoded (lrge_hip_reads_open_mapped*)
+    u64 seek[4] = {0, 0, 0, 0};                 // lrge_hip_reads_seek_stats: runs, text bytes brought, file bytes read, BGZF blocks or gzip / bzip2 entries decoded (lrge_hip_reads_open_mapped*)
 };
 
 // the seek map of a census (fx_seek.h), as the caller holds it
@@ -761,11 +761,18 @@ static int fx_src_gzip(FxSink &s, const u8 *d, u64 len, FxSeekMap *map = nullptr
     }, "gzip", "reads_open: gzip data not proven on the device (status %d near file offset %llu)", [](int rc) { return rc; });
 }
 
-static int fx_src_bzip2(FxSink &s, const u8 *d, u64 len) {
+// bzip2.  map: the census leaves the block table, the marks and the entries of a seek map behind (bz_round.h BzSeekRec)
+static int fx_src_bzip2(FxSink &s, const u8 *d, u64 len, FxSeekMap *map = nullptr) {
     BzStats st;
     BzDev dev(s.ctx);
-    return fx_inflate_to_device(s, dev, [&](u64 *bad) { return bz_run(dev, d, len, s.ctx->opt_u64("BZIP2_ROUND_BLOCKS", 0), [](const uint8_t *, uint64_t) { return true; }, st, bad); },
-                                "bzip2", "reads_open: bzip2 data not accepted by the device (%s near file offset %llu)", bz_status_name);
+    dev.keep_marks = map != nullptr;
+    BzSeekRec<BzDev, FxSeekMap> rec = {map, map ? map->bz_spacing : 0};
+    const u64 round = s.ctx->opt_u64("BZIP2_ROUND_BLOCKS", 0);
+    const int rc = fx_inflate_to_device(s, dev, [&](u64 *bad) {
+        return map ? bz_run(dev, d, len, round, [](const uint8_t *, uint64_t) { return true; }, st, bad, nullptr, &rec) : bz_run(dev, d, len, round, [](const uint8_t *, uint64_t) { return true; }, st, bad);
+    }, "bzip2", "reads_open: bzip2 data not accepted by the device (%s near file offset %llu)", bz_status_name);
+    if (map) dev.print_timing();                // (option BZIP2_TIMING: the stages of a census that recorded marks; tools/ingest_bench.py)
+    return rc;
 }
 
 // Zstandard: a match reaches back through the frame's earlier text, so the text is never windowed without
@@ -895,7 +902,10 @@ static int fx_open_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, 
         if (map && !bgzf) { map->kind = FX_SEEK_GZIP; map->gz_spacing = std::max<u64>(1, ctx->opt_u64("INGEST_SEEK_GZIP_BYTES", (u64)1 << 20)); }
         rc = bgzf ? fx_src_bgzf(s, d, t, total) : fx_src_gzip(s, d, len, map);
     }
-    else if (box == FX_BOX_BZIP2 && (flags & LRGE_GPU_INFLATE_BZIP2)) rc = fx_src_bzip2(s, d, len);
+    else if (box == FX_BOX_BZIP2 && (flags & LRGE_GPU_INFLATE_BZIP2)) {
+        if (map) { map->kind = FX_SEEK_BZIP2; map->bz_spacing = std::max<u64>(1, ctx->opt_u64("INGEST_SEEK_BZIP2_BYTES", (u64)512 << 10)); map->bz_level = len >= 4 ? d[3] : 0; }
+        rc = fx_src_bzip2(s, d, len, map);
+    }
     else if (box == FX_BOX_ZSTD && (flags & LRGE_GPU_INFLATE_ZSTD)) rc = fx_src_zstd(s, d, len);
     else if (box == FX_BOX_XZ && xz_whole && (flags & LRGE_GPU_INFLATE_XZ)) rc = fx_src_xz(s, d, len);
     else if (box == FX_BOX_BZIP2 || box == FX_BOX_ZSTD || box == FX_BOX_XZ) {
@@ -912,6 +922,11 @@ static int fx_open_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, 
         // ... and so does a map that is not worth entering (fx_gz_enterable)
         if (map->kind == FX_SEEK_GZIP && (map->fmt == FX_FMT_BAM || map->fmt == FX_FMT_SAM || !fx_gz_enterable(*map))) { map->kind = FX_SEEK_OTHER; map->ent = {}; map->ent_win = {}; map->gz_spacing = 0; }
         if (map->kind == FX_SEEK_GZIP) fx_seek_attach_gzip(*map);
+        // (BAM and SAM inside bzip2 too; and a sole entry over several blocks could skip nothing: fx_bz_enterable)
+        if (map->kind == FX_SEEK_BZIP2 && (map->fmt == FX_FMT_BAM || map->fmt == FX_FMT_SAM || !fx_bz_enterable(*map))) {
+            map->kind = FX_SEEK_OTHER; map->bz = {}; map->bz_marks = {}; map->bz_ent = {}; map->bz_spacing = 0; map->bz_level = 0;
+        }
+        if (map->kind == FX_SEEK_BZIP2) fx_seek_attach_bzip2(*map);
     }
     *out = guard.release();
     return LRGE_OK;
@@ -1011,6 +1026,7 @@ extern "C" int lrge_hip_read_map_points(const lrge_hip_read_map *map, uint64_t *
 extern "C" int lrge_hip_read_map_entries(const lrge_hip_read_map *map, uint64_t out[4]) {
     if (!map || !out) return LRGE_ERR_INVALID;
     out[0] = map->m.ent.size(); out[1] = map->m.ent_win.size(); out[2] = (uint64_t)map->m.kind; out[3] = map->m.gz_spacing;
+    if (map->m.kind == FX_SEEK_BZIP2) { out[0] = map->m.bz_ent.size(); out[1] = map->m.bz_marks.size() * sizeof(BzMark); out[3] = map->m.bz_spacing; }
     return LRGE_OK;
 }
 
@@ -1250,6 +1266,114 @@ static int fx_src_seek_gzip(FxSink &s, const FxInput &in, const FxSeekMap &m, co
     return runs.finish();
 }
 
+// bzip2: only the entries some run touches are decoded, each block of them once.  The file ranges of the plan go back
+// to back through pinned staging to the device in one copy, the needed blocks' marks behind them.  k_bz_decode and k_bz_scatter run
+// unchanged on positions rebased to the staged ranges; a block is accepted only if the decode's n, origPtr, stored CRC and length in
+// bits are the map's.  Then one wavefront a block enters it at its 64 marks (k_bz_marks_text).  A block's text length is the map's, so
+// a batch's blocks lie back to back in the staging block by a prefix, and no length comes back.  Batches are about a window of text
+// inside groups of at most the blocks a round of the decoder holds (BzDev::default_round), which the entropy decode takes at once
+static int fx_src_seek_bzip2(FxSink &s, const FxInput &in, const FxSeekMap &m, const FxSeekPlan &plan) {
+    lrge_hip_ctx *ctx = s.ctx;
+    if (!(s.flags & LRGE_GPU_INFLATE_BZIP2)) { ctx->err = "reads_open: bzip2, zstd and xz input is decompressed on the host"; return LRGE_ERR_UNPROVEN; }
+    // the blocks of the runs' entries, once each, and where their first byte lies in the staging (ranges that touch or overlap are one)
+    struct Need { u64 blk, c_at; };
+    std::vector<Need> need;
+    u64 comp_len = 0, range_f0 = 0, range_f1 = 0, range_at = 0, prev_b1 = 0, n_ent = 0;
+    std::vector<std::pair<u64, u64>> ranges;    // file [first, second)
+    for (const FxSeekRun &r : plan.runs)
+        for (u64 b = n_ent ? std::max<u64>(r.b0, prev_b1) : r.b0; b < r.b1; prev_b1 = ++b, ++n_ent) {
+            if (b >= m.bz_ent.size() || m.bz_ent[b].b0 >= m.bz_ent[b].b1 || m.bz_ent[b].b1 > m.bz.size()) return fx_map_range(ctx);
+            const u64 f0 = fx_bz_cover_begin(m, b), f1 = fx_bz_cover_end(m, b);
+            if (f1 < f0 || f1 > in.len) return fx_map_range(ctx);
+            if (ranges.empty() || f0 > range_f1) { range_at = comp_len; range_f0 = f0; range_f1 = f1; ranges.push_back({f0, f1}); comp_len += f1 - f0; }
+            else if (f1 > range_f1) { comp_len += f1 - range_f1; range_f1 = f1; ranges.back().second = f1; }
+            for (u64 q = m.bz_ent[b].b0; q < m.bz_ent[b].b1; ++q) {
+                const FxBzBlock &k = m.bz[q];
+                if (k.bit >> 3 < f0 || k.end_bit <= k.bit || (k.end_bit + 7) >> 3 > f1 || k.len >> 32) return fx_map_range(ctx);
+                need.push_back(Need{q, range_at + ((k.bit >> 3) - range_f0)});
+            }
+        }
+    if (n_ent != plan.blocks || comp_len != plan.file_bytes) return fx_map_range(ctx);        // (never: the planner counts the same entries and bytes)
+    const u32 bs = (u32)(m.bz_level - '0') * 100000u;
+    BzDev dev(ctx);
+    // The entropy decode is one serial chain a block, so its latency is one block's however many blocks a launch holds: it runs once
+    // for a group of as many blocks as a round of the decoder holds.  The text of a group is then made in batches of about a window
+    const size_t most = dev.default_round(bs);
+    const auto blk_len = [&](size_t a) { return (u64)m.bz[need[a].blk].len; };
+    struct Batch { size_t i, end; u64 bytes; };
+    std::vector<Batch> batches;
+    u64 stage_cap = 0;
+    for (size_t g = 0; g < need.size(); g = std::min(need.size(), g + most))
+        for (size_t i = g, g_end = std::min(need.size(), g + most), end; i < g_end; i = end) {
+            u64 bytes;
+            end = fx_batch_end(i, g_end, s.window, blk_len, &bytes);
+            batches.push_back(Batch{i, end, bytes});
+            stage_cap = std::max(stage_cap, bytes);
+        }
+    if (stage_cap > s.cap || stage_cap >> 32) return s.over_cap();     // (the text of one batch above the budget)
+    const auto dev_rc = [&]() -> int {
+        LRGE_SET_ERR(ctx, "reads_open: bzip2 inflate: %s", hipGetErrorString(dev.e != hipSuccess ? dev.e : hipErrorUnknown));
+        (void)hipGetLastError();
+        return LRGE_ERR_DEVICE;
+    };
+    FxPinned pin;
+    const u64 marks_at = ((comp_len + 15) & ~(u64)15) + BZ_PAD, total = marks_at + (u64)need.size() * FX_BZ_MARKS * sizeof(BzMark);
+    HIPCHK(ctx, hipHostMalloc((void **)&pin.p, (size_t)total, hipHostMallocDefault));
+    {
+        u64 at = 0;
+        for (const auto &r : ranges) { if (!in.read(r.first, r.second - r.first, pin.p + at)) return fx_read_failed(ctx); at += r.second - r.first; }
+        memset(pin.p + comp_len, 0, (size_t)(marks_at - comp_len));
+        for (size_t i = 0; i < need.size(); ++i) memcpy(pin.p + marks_at + i * (size_t)FX_BZ_MARKS * sizeof(BzMark), &m.bz_marks[need[i].blk * (size_t)FX_BZ_MARKS], FX_BZ_MARKS * sizeof(BzMark));
+    }
+    if (!dev.stage_up(pin.p, comp_len, marks_at, total)) return dev_rc();
+    Scratch sc(ctx);
+    ALLOC_OR_FAIL(d_stage, sc, u8, stage_cap + FX_PAD);
+    int rc;
+    FxRunsTaker runs(s, plan);
+    size_t g = 0, g_end = 0;                    // the group whose blocks the decode left in slots 0 .. g_end - g - 1
+    for (const Batch &bt : batches) {
+        if (bt.i >= g_end) {
+            g = bt.i; g_end = std::min(need.size(), g + most);
+            const u32 k = (u32)(g_end - g);
+            std::vector<u64> pos(k);
+            std::vector<BzRes> res(k);
+            for (u32 j = 0; j < k; ++j) pos[j] = 8 * need[g + j].c_at + (m.bz[need[g + j].blk].bit & 7);
+            if (!dev.decode(pos.data(), k, bs, res.data())) return dev_rc();
+            for (u32 j = 0; j < k; ++j) {
+                const FxBzBlock &b = m.bz[need[g + j].blk];
+                const BzRes &r = res[j];
+                if (r.status == BZ_OK && r.n == b.n && r.orig == b.orig && r.crc == b.crc && r.end_bit - pos[j] == b.end_bit - b.bit) continue;
+                char why[128];
+                snprintf(why, sizeof why, "bzip2 block %llu: %s", (unsigned long long)need[g + j].blk, r.status != BZ_OK ? bz_status_name((int)r.status) : "another block than the map's");
+                return fx_map_misfit(ctx, why);
+            }
+        }
+        const u32 k = (u32)(bt.end - bt.i);
+        std::vector<BzLink> links(k);
+        std::vector<BzMarkTask> task(k);
+        std::vector<u32> status(k);
+        std::vector<FxPiece> pc;
+        u64 at = 0;                             // where the block's text lies in the staging block
+        for (u32 j = 0; j < k; ++j) {
+            const FxBzBlock &b = m.bz[need[bt.i + j].blk];
+            links[j] = BzLink{0, 0, (u32)(bt.i + j - g), b.n, b.orig, 0};
+            task[j] = BzMarkTask{0, at, b.n, b.orig, b.crc, (u32)b.len, (u32)(bt.i + j), 0};
+            pc.push_back(FxPiece{b.off, b.len, at});
+            at += b.len;
+        }
+        if (!dev.seeded(links.data(), task.data(), k, d_stage, status.data())) return dev_rc();
+        for (u32 j = 0; j < k; ++j)
+            if (status[j]) {
+                char why[128];
+                snprintf(why, sizeof why, "bzip2 block %llu: %s", (unsigned long long)need[bt.i + j].blk, bz_status_name((int)status[j]));
+                return fx_map_misfit(ctx, why);
+            }
+        if ((rc = runs.take(pc, d_stage, bt.bytes))) return rc;
+    }
+    dev.print_timing();
+    return runs.finish();
+}
+
 // One mapped open.  Everything that can be refused is refused before any device work: a selection that is not ascending, a map of
 // another input, an ordinal at or above the map's records
 static int fx_open_mapped(lrge_hip_ctx *ctx, FxInput &in, int flags, const lrge_hip_read_map *map, const u32 *sel, u64 k, lrge_hip_reads **out) {
@@ -1279,7 +1403,12 @@ static int fx_open_mapped(lrge_hip_ctx *ctx, FxInput &in, int flags, const lrge_
     const bool gz = box == FX_BOX_GZIP, packed = gz || box == FX_BOX_BZIP2 || box == FX_BOX_ZSTD || box == FX_BOX_XZ;
     std::vector<BgzfBlock> t;
     u64 total = 0;
-    bool fits = m.file_len == in.len && (m.kind == FX_SEEK_PLAIN ? !packed && m.text_bytes == in.len : m.kind == FX_SEEK_BGZF || m.kind == FX_SEEK_GZIP ? gz : packed);
+    bool fits = m.file_len == in.len && (m.kind == FX_SEEK_PLAIN ? !packed && m.text_bytes == in.len : m.kind == FX_SEEK_BGZF || m.kind == FX_SEEK_GZIP ? gz :
+                                         m.kind == FX_SEEK_BZIP2 ? box == FX_BOX_BZIP2 : packed);
+    if (fits && m.kind == FX_SEEK_BZIP2) {      // the level byte is the census's; the tables are whole: as many entries as the points name, all blocks in them, a set of marks a block, all of the text
+        fits = nh >= 4 && h[3] == m.bz_level && m.bz_level >= '1' && m.bz_level <= '9' && !m.bz_ent.empty() && m.bz_ent.size() == m.n_blocks && m.bz_ent.back().b1 == m.bz.size() &&
+               m.bz_marks.size() == m.bz.size() * (size_t)FX_BZ_MARKS && m.bz[0].bit == 32 && m.bz.back().off + m.bz.back().len == m.text_bytes;
+    }
     if (fits && m.kind == FX_SEEK_GZIP) {       // the entry table is whole: as many entries as the points name, a window each but the first, all of the text
         fits = !m.ent.empty() && m.ent.size() == m.n_blocks && m.ent_win.size() == m.ent.size() * (size_t)FX_GZ_WIN && m.ent[0].bit == 0 &&
                m.ent.back().off + m.ent.back().len == m.text_bytes;
@@ -1309,7 +1438,8 @@ static int fx_open_mapped(lrge_hip_ctx *ctx, FxInput &in, int flags, const lrge_
     if (m.fmt == FX_FMT_BAM || m.fmt == FX_FMT_SAM) s.run->dev.kind = m.fmt;      // (the sub-text is never sniffed: it is a record stream, or whole SAM lines, without a header)
     if ((rc = s.run->dev.select(FX_KEEP_SEL, plan.sel.data(), k))) return rc;
     s.run->attach(&s.blk);
-    rc = m.kind == FX_SEEK_PLAIN ? fx_src_seek_raw(s, in, plan) : m.kind == FX_SEEK_GZIP ? fx_src_seek_gzip(s, in, m, plan) : fx_src_seek_bgzf(s, in, plan);
+    rc = m.kind == FX_SEEK_PLAIN ? fx_src_seek_raw(s, in, plan) : m.kind == FX_SEEK_GZIP ? fx_src_seek_gzip(s, in, m, plan) : m.kind == FX_SEEK_BZIP2 ? fx_src_seek_bzip2(s, in, m, plan) :
+                                                                                                                                     fx_src_seek_bgzf(s, in, plan);
     if (!rc) rc = fx_finish_windowed(s, t0);
     // the sub-text is proven again, and holds exactly the planner's records: else the input is not the one the map was made of
     if (rc == LRGE_ERR_INVALID && s.run->dev.at < s.run->dev.k) return fx_map_misfit(ctx, "fewer records than the plan");

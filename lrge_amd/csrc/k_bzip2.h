@@ -6,6 +6,10 @@
 //   k_bz_walk        one lane per block: n dependent loads through tt (latency-bound: the blocks of a round are its parallelism)
 //   k_bz_rle_count   one lane per block: the length of the block's text behind the run-length layer
 //   k_bz_rle_write   one lane per block: the text at its place in the round's output, with the block's CRC
+// A census that leaves a seek map runs k_bz_walk_rec and k_bz_rle_write_rec in their place: the same bodies with the
+// recording mark sink (bz_core.h BzMarkRec), BZ_MARKS marks a block.  The mapped open enters a block at those marks:
+//   k_bz_marks_text  one wavefront per block, lane j from mark j: its segment of the walk fed straight through the run-length layer
+//                    and the CRC into the text (bz_segment_lane); the bytes in front of the run-length layer are never stored
 #pragma once
 #include "bz_core.h"
 #include "bz_round.h"
@@ -120,4 +124,45 @@ __global__ __launch_bounds__(64) void k_bz_rle_write(const BzLink *__restrict__ 
     if (a >= m) return;
     const BzLink K = links[a];
     crc[a] = bz_rle_write(pre + (u64)K.slot * bs, K.n, tab, out + K.out_off);
+}
+
+// ---- the recording forms: marks + a * BZ_MARKS are link a's (zeroed by the host: a block has bz_mark_count(n) of them) ----
+__global__ __launch_bounds__(64) void k_bz_walk_rec(const BzLink *__restrict__ links, u32 m, u32 bs, const u32 *__restrict__ tt, u8 *__restrict__ L, u32 *__restrict__ bad,
+                                                    BzMark *__restrict__ marks) {
+    const u32 a = blockIdx.x * 64 + threadIdx.x;
+    if (a >= m) return;
+    const BzLink K = links[a];
+    if (!bz_walk(tt + K.tt_off, K.n, K.orig, L + (u64)K.slot * bs, BzMarkRec(marks + (u64)a * BZ_MARKS, K.n))) atomicOr(bad, 1u);
+}
+
+__global__ __launch_bounds__(64) void k_bz_rle_write_rec(const BzLink *__restrict__ links, u32 m, u32 bs, const u8 *__restrict__ pre, u8 *__restrict__ out,
+                                                         u32 *__restrict__ crc, BzMark *__restrict__ marks) {
+    __shared__ u32 tab[256];
+    bz_crc_table(tab, threadIdx.x, 64);
+    __syncthreads();
+    const u32 a = blockIdx.x * 64 + threadIdx.x;
+    if (a >= m) return;
+    const BzLink K = links[a];
+    crc[a] = bz_rle_write(pre + (u64)K.slot * bs, K.n, tab, out + K.out_off, BzMarkRec(marks + (u64)a * BZ_MARKS, K.n));
+}
+
+// ---- the seeded decode ----
+// Block a of a mapped open's batch: its links tt + tt_off (k_bz_scatter's, n of them), its text out + out_off of `len` bytes, its marks
+// marks + mark0 * BZ_MARKS; orig and crc are the map's (the host has compared the entropy decode's with them).  Lane j runs segment j
+// (an idle lane where j * seg >= n) and compares where it arrives with mark j + 1; a lane that fails gives the block BZ_E_ENTRY.
+// No lane loads tt at an index >= n or stores outside its own text range [mark j's offset, mark j + 1's), whatever the marks hold
+struct BzMarkTask { u64 tt_off, out_off; u32 n, orig, crc, len, mark0, pad; };
+__global__ __launch_bounds__(64) void k_bz_marks_text(const BzMarkTask *__restrict__ tasks, u32 m, const u32 *__restrict__ tt, const BzMark *__restrict__ marks,
+                                                      u8 *__restrict__ out, u32 *__restrict__ status) {
+    __shared__ u32 tab[256];
+    __shared__ BzMark mk[BZ_MARKS];
+    const u32 a = blockIdx.x, lane = threadIdx.x;
+    if (a >= m) return;
+    bz_crc_table(tab, lane, 64);
+    const BzMarkTask K = tasks[a];
+    mk[lane] = marks[(u64)K.mark0 * BZ_MARKS + lane];
+    __syncthreads();
+    const bool good = bz_segment_lane(tt + K.tt_off, K.n, K.orig, K.crc, K.len, mk, lane, tab, out + K.out_off);
+    const bool all = __all(good);
+    if (lane == 0) status[a] = all ? (u32)BZ_OK : (u32)BZ_E_ENTRY;
 }

@@ -383,7 +383,8 @@ class ReadMap:
         return list(zip(*(x[:k].tolist() for x in a)))
 
     def entries(self):
-        """(entries, window bytes held, kind, spacing in force) of a gzip map; (0, 0, kind, 0) of any other"""
+        """(entries, window bytes held, kind, spacing in force) of a gzip map; (entries, mark bytes held, 5, spacing) of a
+        bzip2 map (section 29); (0, 0, kind, 0) of any other"""
         a = (C.c_uint64 * 4)()
         rc = self._lib.lrge_hip_read_map_entries(self.h, C.byref(a))
         if rc:

@@ -20,6 +20,9 @@ beside it is the route the parent commit took for the mapped open, "blocks_decod
 (--kinds sam,sam.gz,cram --sampled K1,K2 --seek: the same on unaligned SAM text, plain and bgzipped, under LRGE_GPU_INGEST_SELECT_SAM, and on an
 unaligned CRAM of --cram-slices slices under LRGE_GPU_INGEST_SELECT_CRAM; the single open beside them is the parent
 commit's route for the same command -- the full windowed SAM open, the full CRAM open.  The kinds sam.gz and cram are written only when named)
+(--kinds fq.bz2 --sampled K1,K2 --seek: the same on the FASTQ as one bzip2 stream of level 9, entered at whole blocks and a block at its 64 marks; the
+selected open beside it is the route the parent commit took for the mapped open, "blocks_decoded" counts entries, and one run more under BZIP2_TIMING gives the stage times
+of the census that records marks and of the mapped open under "bzip2_stages")
 (lrge_hip_reads_census, lrge_hip_reads_census_map), the selected open and the mapped open of the same K seeded ordinals
 (lrge_hip_reads_open_selected, lrge_hip_reads_open_mapped) and the existing windowed open, all alternating in one run; with the
 bytes the mapped open brought and read, under the key "sampled_seek" / "<K>" of --out.
@@ -241,10 +244,10 @@ def _bgzf(data, block=65280, level=1):
 
 
 KINDS = ("fq", "bgzf.fq.gz", "fq.gz", "bam", "sam")
-EXTRA_KINDS = ("sam.gz", "cram")      # written only when --kinds names them: bgzipped SAM, and an unaligned CRAM (cram_file)
+EXTRA_KINDS = ("sam.gz", "cram", "fq.bz2")      # written only when --kinds names them: bgzipped SAM, an unaligned CRAM (cram_file), the FASTQ as one bzip2 stream of level 9
 # the flags of the single open and of the sampled calls, by kind (fq, bgzf.fq.gz, bam: as before)
-OPEN_FLAGS = {"cram": 3 | 512}
-SEEK_FLAGS = {"bam": 15 | 1024, "sam": 15 | 4096, "sam.gz": 15 | 4096, "cram": 3 | 512 | 8192}
+OPEN_FLAGS = {"cram": 3 | 512, "fq.bz2": 15 | 16 | 32 | 64}
+SEEK_FLAGS = {"bam": 15 | 1024, "sam": 15 | 4096, "sam.gz": 15 | 4096, "cram": 3 | 512 | 8192, "fq.bz2": 15 | 16}
 
 
 def cram_file(path, slices, slice_kb):
@@ -298,8 +301,18 @@ def write_files(d, parts, kinds):
     paths = {k: os.path.join(d, "ingest." + k) for k in kinds}
     size = {k: 0 for k in paths}
     files = {k: open(p, "wb") for k, p in paths.items()}
+    bz = None
+    if "fq.bz2" in kinds:                       # (one stream: the parts go through one compressor, in order, in this process)
+        import bz2
+        import gzip_bench as GB
+        bz = bz2.BZ2Compressor(9)
+        for i in range(parts):
+            d = GB._fastq(i)
+            files["fq.bz2"].write(bz.compress(d))
+            size["fq.bz2"] += len(d)
+        files["fq.bz2"].write(bz.flush())
     with mp.get_context("spawn").Pool(16) as pool:
-        for part in pool.imap(_part, [(i, tuple(kinds)) for i in range(parts)]):
+        for part in pool.imap(_part, [(i, tuple(k for k in kinds if k != "fq.bz2")) for i in range(parts)] if len(kinds) > (bz is not None) else []):
             for k, (n, data) in part.items():
                 files[k].write(data)
                 size[k] += n
@@ -472,6 +485,31 @@ def zstd_runs(a, ctx, H, HS, paths, n_text):
     json.dump(result, open(a.out, "w"), indent=1)
 
 
+def bzip2_stages(ctx, HK, p, flags, sel):
+    """one route_seek under BZIP2_TIMING: the stage lines the library prints to stderr -- the census with a map (its walk and
+    run-length write record marks), then the mapped open (entropy, scatter and k_bz_marks_text of the touched blocks only)"""
+    import re
+    ctx.set_option("BZIP2_TIMING", "1")
+    sys.stderr.flush()
+    saved = os.dup(2)
+    with tempfile.TemporaryFile() as tmp:
+        os.dup2(tmp.fileno(), 2)
+        try:
+            ms5, cen, mst, sst, sk = (C.c_double * 5)(), (C.c_uint64 * 4)(), (C.c_uint64 * 4)(), (C.c_uint64 * 4)(), (C.c_uint64 * 4)()
+            rc = HK.route_seek(ctx.h, p.encode(), flags, sel.ctypes.data, sel.size, C.byref(ms5), C.byref(cen), C.byref(mst), C.byref(sst), C.byref(sk))
+        finally:
+            os.dup2(saved, 2)
+            os.close(saved)
+            ctx.set_option("BZIP2_TIMING", None)
+        tmp.seek(0)
+        text = tmp.read().decode(errors="replace")
+    keys = ("find_ms", "entropy_ms", "scatter_ms", "walk_ms", "rle_crc_ms", "marks_text_ms")
+    lines = [dict(zip(keys, (float(g) for g in m))) for m in re.findall(r"bzip2 stages ms: find ([\d.]+) entropy ([\d.]+) scatter ([\d.]+) walk ([\d.]+) rle_crc ([\d.]+) marks_text ([\d.]+)", text)]
+    if rc != 0 or len(lines) != 2:
+        return {"error": "rc %d, %d stage lines" % (rc, len(lines))}
+    return {"census_map": lines[0], "mapped_open": lines[1], "timed_census_map_ms": ms5[1], "timed_mapped_open_ms": ms5[3]}
+
+
 def seek_runs(a, ctx, H, HK, kinds, paths, text_bytes, ks):
     """for every K: the windowed open, the census without and with a map, the selected and the mapped open on every file, all
     alternating in every repeat; into the key "sampled_seek" / "<K>" of a.out"""
@@ -509,6 +547,8 @@ def seek_runs(a, ctx, H, HK, kinds, paths, text_bytes, ks):
                     runs.append(dict(open_ms=ms2[0], census_ms=ms5[0], census_map_ms=ms5[1], selected_open_ms=ms5[2], mapped_open_ms=ms5[3], seqset_k_ms=ms5[4],
                                      map_cost_ms=ms5[1] - ms5[0], two_pass_ms=ms5[1] + ms5[3], two_pass_parent_ms=ms5[0] + ms5[2]))
             f = dict(file_bytes=os.path.getsize(p), text_bytes=text_bytes[kind], every_run=runs, **seen)
+            if kind == "fq.bz2":                                      # (the stages of the census that records marks and of the mapped open, one run more)
+                f["bzip2_stages"] = bzip2_stages(ctx, HK, p, SEEK_FLAGS[kind], sel)
             for key in runs[0]:
                 f["%s_median" % key] = statistics.median(x[key] for x in runs)
                 f["%s_range" % key] = (min(x[key] for x in runs), max(x[key] for x in runs))
@@ -598,7 +638,7 @@ def main():
         HK.full_bytes.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_uint64 * 2)]
         HK.kept_bytes.argtypes = [C.POINTER(C.c_uint64 * 2)]
         a.window_mb = int(a.window_mb.split(",")[0])
-        seek_runs(a, ctx, H, HK, [k for k in kinds if k in ("fq", "bgzf.fq.gz", "fq.gz", "bam", "sam", "sam.gz", "cram")], paths, text_bytes, seek_ks)
+        seek_runs(a, ctx, H, HK, [k for k in kinds if k in ("fq", "bgzf.fq.gz", "fq.gz", "bam", "sam", "sam.gz", "cram", "fq.bz2")], paths, text_bytes, seek_ks)
         ctx.close()
         for p in list(paths.values()) + [src, so] + extra:
             os.remove(p)

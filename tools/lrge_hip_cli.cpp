@@ -93,7 +93,7 @@ int main(int argc, char **argv) {
         else if (a == "--gpu-bzip2") gpu_bzip2 = true;           // bzip2 input decompressed on --device (with --gpu-ingest: kept in HBM)
         else if (a == "--gpu-ingest") { gpu_ingest = true; gpu_gzip = true; }   // FASTA / FASTQ / unaligned BAM / unaligned SAM parsed on --device too: the bases never reach host memory (implies --gpu-gzip)
         else if (a == "--gpu-sample") gpu_sample = true;         // beside --gpu-ingest: a count pass, then only the drawn reads are kept (lrge_hip_reads_census, lrge_hip_reads_open_selected); not implied by --gpu-ingest
-        else if (a == "--gpu-seek") gpu_seek = true;             // beside --gpu-sample: the count pass keeps a seek map, the second pass reads and decodes only the runs of plain / BGZF input that hold drawn reads (lrge_hip_reads_census_map, lrge_hip_reads_open_mapped)
+        else if (a == "--gpu-seek") gpu_seek = true;             // beside --gpu-sample: the count pass keeps a seek map, the second pass reads and decodes only the runs of plain / BGZF input, the entries of gzip and (with --gpu-bzip2) the blocks of bzip2 that hold drawn reads (lrge_hip_reads_census_map, lrge_hip_reads_open_mapped)
         else if (a == "--gpu-names") gpu_names = true;           // identifier ranks computed on --device (lrge_hip_name_ranks); not implied by --gpu-ingest
         else if (a == "--dump-records") dump_records = true;   // host-only: print "id<TAB>sequence" per record and exit (tests)
         else if (a == "-q" || a == "--quiet") ++quiet; else if (a == "-qq") quiet += 2; else if (a == "-qqq") quiet += 3;

@@ -12,7 +12,10 @@
 // sam_twin_census_map at strides 1, 64, 3000 and above the text, sam_twin_seek_plan, sam_twin_mapped).  Prints the
 // Every *.gz file (plain or multi-member gzip of FASTA / FASTQ) goes through the seek map of gzip: fastx_twin_gz_census_map
 // at chunks 64 and 1024 and spacings 1, 4096 and above the text, every entry decoded alone from its seed at the four staging skews against its
-// slice of the text, the plan, and fastx_twin_gz_mapped against fastx_twin_selected on the text.  Prints the
+// slice of the text, the plan, and fastx_twin_gz_mapped against fastx_twin_selected on the text.
+// Every *.bz2 file goes through the seek map of bzip2: fastx_twin_bz_census_map at rounds of 1 block and of all and
+// spacings 1, 4096 and above the text, every block entered at every mark alone and by all lanes at the four staging skews against its
+// slice of the text, the plan, and fastx_twin_bz_mapped against fastx_twin_selected on the text.  Prints the
 // verdict counts; the exit status is 1 when the verdicts of one file disagree.
 // TEST INFRASTRUCTURE, not part of the product library.
 #include <stdio.h>
@@ -298,6 +301,64 @@ static uint64_t gzip_seek(const char *path, const std::vector<uint8_t> &d) {
     return bad;
 }
 
+// The seek map of a bzip2 file: returns the disagreements
+static uint64_t bzip2_seek(const char *path, const std::vector<uint8_t> &d) {
+    uint64_t bad = 0;
+    const auto fail = [&](const char *what, uint64_t round, uint64_t spacing) { ++bad; fprintf(stderr, "%s: bzip2 seek, round %llu spacing %llu: %s\n", path, (unsigned long long)round, (unsigned long long)spacing, what); };
+    for (uint64_t round : {(uint64_t)1, (uint64_t)0})
+        for (uint64_t sp = 0; sp < 3; ++sp) {
+            uint64_t cs[4];
+            uint64_t spacing = sp == 0 ? 1 : 4096;
+            int rc = fastx_twin::fastx_twin_bz_census_map(d.data(), d.size(), round, spacing, 64, 3001, 4096, 512, cs);
+            if (sp == 2) { spacing = fastx_twin::fastx_twin_gz_text(nullptr) + 1; rc = fastx_twin::fastx_twin_bz_census_map(d.data(), d.size(), round, spacing, 64, 3001, 4096, 512, cs); }
+            std::vector<uint8_t> text((size_t)fastx_twin::fastx_twin_gz_text(nullptr) + 1);
+            const uint64_t n = fastx_twin::fastx_twin_gz_text(text.data());
+            const uint64_t nb = fastx_twin::fastx_twin_bz_blocks(nullptr, 0), ne = fastx_twin::fastx_twin_bz_entries(nullptr, 0);
+            std::vector<uint64_t> blk(8 * nb + 8), ent(6 * ne + 6);
+            fastx_twin::fastx_twin_bz_blocks(blk.data(), nb);
+            fastx_twin::fastx_twin_bz_entries(ent.data(), ne);
+            if (!nb || !ne || blk[0] != 32 || blk[2] || ent[0] || ent[6 * (ne - 1) + 1] != nb) { fail("block 0 is not the start of the file, or the entries do not hold the blocks", round, spacing); continue; }
+            for (uint64_t i = 0; i < nb; ++i) {
+                const uint64_t off = blk[8 * i + 2], len = blk[8 * i + 3];
+                if (off + len > n || (i + 1 < nb && (blk[8 * i + 10] != off + len || blk[8 * i + 8] != blk[8 * i + 1])) || (i + 1 == nb && off + len != n)) { fail("the blocks do not tile the text", round, spacing); break; }
+                std::vector<uint8_t> out((size_t)len + 1);
+                uint64_t got = 0, sum = 0;
+                bool good = true;
+                for (uint32_t j = 0; j < FX_BZ_MARKS && good; ++j) {       // every lane alone: the segments tile the block's text
+                    good = !fastx_twin::fastx_twin_bz_segment(d.data(), d.size(), i, j, j & 3, out.data(), &got) && !memcmp(out.data(), text.data() + off + sum, (size_t)got);
+                    sum += got;
+                }
+                for (uint32_t skew = 0; skew < 4 && good; ++skew)
+                    good = !fastx_twin::fastx_twin_bz_segment(d.data(), d.size(), i, FX_BZ_MARKS, skew, out.data(), &got) && got == len && !memcmp(out.data(), text.data() + off, (size_t)len);
+                if (!good || sum != len) { fail("a block entered at its marks is not its text", round, spacing); break; }
+            }
+            if (rc) continue;                      // (a text that is no FASTA / FASTQ: blocks and marks are the bzip2 side's alone)
+            std::vector<uint32_t> sel;
+            for (uint64_t i = 0; i < cs[0]; i += 3) sel.push_back((uint32_t)i);
+            if (cs[0] && sel.back() != cs[0] - 1) sel.push_back((uint32_t)(cs[0] - 1));
+            uint64_t ps[4], ms[4];
+            uint32_t status = 0;
+            if (fastx_twin::fastx_twin_seek_plan(nullptr, nullptr, 0, 0, sel.data(), sel.size(), ps) || ps[1] > n || ps[2] > d.size() || ps[3] > ne) fail("the plan", round, spacing);
+            if (fastx_twin::fastx_twin_bz_mapped(d.data(), d.size(), 64, 3001, 4096, sel.data(), sel.size(), &status)) { fail("the mapped pass is not proven", round, spacing); continue; }
+            fastx_twin::fastx_twin_plan_stats(ms);
+            if (memcmp(ps, ms, sizeof ps)) fail("the mapped pass brought something else than the plan", round, spacing);
+            const uint64_t k = fastx_twin::fastx_twin_windowed_count();
+            std::vector<FxRec> tab(k);
+            fastx_twin::fastx_twin_windowed_table(tab.data());
+            std::vector<std::vector<uint8_t>> seqs(k);
+            for (uint64_t j = 0; j < k; ++j) { seqs[j].resize(tab[j].seq_len + 1); fastx_twin::fastx_twin_windowed_seq(j, seqs[j].data()); }
+            if (fastx_twin::fastx_twin_selected(text.data(), n, 64, 3001, 4096, sel.data(), sel.size()) || fastx_twin::fastx_twin_windowed_count() != k) { fail("the selected pass differs", round, spacing); continue; }
+            std::vector<FxRec> want(k);
+            fastx_twin::fastx_twin_windowed_table(want.data());
+            for (uint64_t j = 0; j < k; ++j) {
+                std::vector<uint8_t> out(want[j].seq_len + 1);
+                fastx_twin::fastx_twin_windowed_seq(j, out.data());
+                if (want[j].name_off != tab[j].name_off || want[j].seq_len != tab[j].seq_len || memcmp(out.data(), seqs[j].data(), want[j].seq_len)) { fail("a record of the mapped pass differs", round, spacing); break; }
+            }
+        }
+    return bad;
+}
+
 int main(int argc, char **argv) {
     const uint64_t windows[] = {64, 257, 3001, 20000}, segs[] = {64, 257, 4096}, tiles[] = {64, 4096};
     uint64_t runs = 0, proven = 0, bad = 0;
@@ -307,6 +368,7 @@ int main(int argc, char **argv) {
         const bool is_bam = ends(".bam"), is_sam = ends(".sam");
         const std::vector<uint8_t> t = slurp(argv[a]);
         if (path.size() > 3 && path.compare(path.size() - 3, 3, ".gz") == 0) { bad += gzip_seek(argv[a], t); ++runs; continue; }
+        if (ends(".bz2")) { bad += bzip2_seek(argv[a], t); ++runs; continue; }
         const uint64_t n = t.size();
         int first = -100;
         uint64_t first_count = 0;
