@@ -761,6 +761,38 @@ int      lrge_hip_reads_seek_stats(const lrge_hip_reads *reads, uint64_t out[4])
 #define LRGE_GPU_INGEST_WINDOWED_ZSTD 2048
 int      lrge_hip_reads_zstd_stats(const lrge_hip_reads *reads, uint64_t out[4]);
 
+/* The streamed first pass (no kernel of its own): without this flag lrge_hip_reads_open, _census, _open_selected and
+   _census_map read the whole file into host memory before the first kernel runs, so the host holds as many bytes as the file has.
+   | LRGE_GPU_INGEST_STREAM (opt-in; without it every call does what it did, the message texts included): those four calls read the
+   file by range, in pieces of option INGEST_STREAM_BYTES (P; default 64 MiB, at least 1), into two pinned buffers.  The _mem forms
+   accept and ignore the flag.  lrge_hip_reads_open needs LRGE_GPU_INGEST_WINDOWED beside it (LRGE_ERR_INVALID, the message names both
+   flags): the size of the text is not known before the last piece, so every text passes through the windows whatever its size, as
+   in the sampled calls, and there is no resident route.  BAM or SAM text, found by the first window's sniff, needs
+   LRGE_GPU_INGEST_WINDOWED_ALN as always; without it the call is LRGE_ERR_UNPROVEN and says so.
+   Plain text: pieces of min(P, window) bytes through two buffers, one filled while the other's copy is in flight (the first buffer is
+   made before the container is known and has a BGZF buffer's size, min(P, file length) + 64 KiB; the second holds a piece); every file
+   byte is read once.
+   BGZF (unaligned BAM included): a buffer holds up to P compressed bytes behind the partial member the buffer before it ended in (it
+   grows to hold one whole member where P is smaller); the block walk runs piece by piece under the rules of lrge_hip_bgzf_scan, the
+   whole members are decoded from where they lie, and every file byte is read once.  Whether a file is BGZF is decided by its first
+   member: a later member that is no BGZF block, a truncated member or trailing bytes end the call with LRGE_ERR_UNPROVEN and a
+   message that gives the file offset and says to open without the flag (the whole-file route gives such a file to the gzip decoder;
+   windows have been delivered by then, so the streamed call cannot start again).  That is the one difference in outcome, and it is
+   a refusal, never other records.  With a seek map the whole block table is kept, about 40 bytes a block of ordinary host memory
+   outside out[2] below; without one only the current buffer's blocks are.
+   Plain and multi-member gzip: the rounds, loads and prefetches are the ranges of the whole-file route, read from the file as they
+   are staged; text, statuses and the entries of a seek map are the same by construction.  The bytes read exceed the file length by
+   the overhang every round reads again, and the pinned staging is a round's (option GZIP_ROUND_BYTES), not P: out[2] is then the
+   capacity of the staging buffer the context keeps across calls -- at least this call's largest round, and an earlier, larger file's
+   where there was one.
+   bzip2, Zstandard, xz and CRAM take the flag and are read whole as without it.  lrge_hip_reads_open_mapped with a map that is not
+   entered (kind 2) streams its full selected pass under the flag.  A path that cannot be opened or read by range, a short read and a
+   file that shrank are LRGE_ERR_IO; no partial result is handed out.
+   lrge_hip_last_stream_stats: the reading of the last of those path calls on `ctx` -- out[0] read calls issued, out[1] file bytes
+   read, out[2] pinned host bytes held for file bytes at the peak, out[3] 1 if the pass streamed, 0 if it read the file whole. */
+#define LRGE_GPU_INGEST_STREAM 16384
+int      lrge_hip_last_stream_stats(const lrge_hip_ctx *ctx, uint64_t out[4]);
+
 /* Read sets built on the device from unaligned CRAM 3.0 / 3.1 (k_rans_decode): | LRGE_GPU_INGEST_CRAM (opt-in:
    no other flag implies it, and without it every call does what it did) sends input that starts with "CRAM" to a host walk of the
    containers -- the record loop of lrge_hip_read_records under a policy that reads no base, so identifiers, lengths and flags are

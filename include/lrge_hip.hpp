@@ -83,6 +83,7 @@ struct Ctx {
 // | LRGE_GPU_INGEST_SELECT_ALN (opt-in) beside LRGE_GPU_INGEST_BAM: census / open_selected / census_map / open_mapped take unaligned BAM too;
 // | LRGE_GPU_INGEST_SELECT_SAM (opt-in) beside LRGE_GPU_INGEST_SAM: ... and unaligned SAM;
 // | LRGE_GPU_INGEST_SELECT_CRAM (opt-in) beside LRGE_GPU_INGEST_CRAM: ... and unaligned CRAM;
+// | LRGE_GPU_INGEST_STREAM (opt-in): open / census / open_selected / census_map read plain, BGZF and gzip files in pinned pieces of option INGEST_STREAM_BYTES instead of whole (open needs LRGE_GPU_INGEST_WINDOWED beside it);
 // | LRGE_GPU_INGEST_CRAM (opt-in, implied by nothing): unaligned CRAM, walked on the host, its base blocks decoded on the device (the flags pass through as given)
 // (lrge_hip_reads_open, io.rs:154-184): identifiers and lengths on
 // the host, the bases resident in HBM as text.  Owns its context; the strategies built on it run in that context and take

@@ -67,6 +67,7 @@ pub const LRGE_GPU_INGEST_SELECT_ALN: c_int = 1024; // beside LRGE_GPU_INGEST_BA
 pub const LRGE_GPU_INGEST_CRAM: c_int = 512; // lrge_hip_reads_open*: unaligned CRAM, its base blocks decoded on the device (io.rs:93, 154-184); opt-in
 pub const LRGE_GPU_INFLATE_XZ: c_int = 256; // lrge_hip_reads_open* / lrge_hip_read_records_gpu_ex: xz decompressed on the device (io.rs:36-63)
 pub const LRGE_GPU_INFLATE_ZSTD: c_int = 128; // lrge_hip_reads_open* / lrge_hip_read_records_gpu_ex: Zstandard decompressed on the device (io.rs:36-63)
+pub const LRGE_GPU_INGEST_STREAM: c_int = 16384; // the path forms of lrge_hip_reads_open / _census / _open_selected / _census_map read the file in pinned pieces, not whole (io.rs:36-63 streams its input too); opt-in
 pub const LRGE_GPU_INGEST_WINDOWED_ZSTD: c_int = 2048; // beside LRGE_GPU_INFLATE_ZSTD: Zstandard text through the windows, and in lrge_hip_reads_census* / _open_selected* / _census_map* / _open_mapped* (io.rs:36-63, 140-145); opt-in
 pub const LRGE_GPU_INFLATE_BZIP2: c_int = 16; // lrge_hip_reads_open* / lrge_hip_read_records_gpu_ex: bzip2 decompressed on the device (io.rs:36-63)
 

@@ -24,6 +24,7 @@ GPU_INGEST_SELECT_ALN = 1024
 GPU_INGEST_WINDOWED_ZSTD = 2048
 GPU_INGEST_SELECT_SAM = 4096
 GPU_INGEST_SELECT_CRAM = 8192
+GPU_INGEST_STREAM = 16384
 PRESET_AVA_ONT, PRESET_AVA_PB = 0, 1
 
 T_NAMES = ["pack", "sketch", "index_sort", "index_table", "qfilter", "lookup", "expand", "anchor_sort", "group",
@@ -57,7 +58,7 @@ EXPORTS = [
     "lrge_hip_name_ranks", "lrge_hip_reads_name_ranks",
     "lrge_hip_reads_census", "lrge_hip_reads_census_mem", "lrge_hip_reads_open_selected", "lrge_hip_reads_open_selected_mem", "lrge_hip_reads_select_stats",
     "lrge_hip_reads_census_map", "lrge_hip_reads_census_map_mem", "lrge_hip_read_map_free", "lrge_hip_read_map_stats", "lrge_hip_read_map_points", "lrge_hip_read_map_entries",
-    "lrge_hip_reads_open_mapped", "lrge_hip_reads_open_mapped_mem", "lrge_hip_reads_seek_stats", "lrge_hip_reads_zstd_stats",
+    "lrge_hip_reads_open_mapped", "lrge_hip_reads_open_mapped_mem", "lrge_hip_reads_seek_stats", "lrge_hip_reads_zstd_stats", "lrge_hip_last_stream_stats",
     "lrge_hip_index_build", "lrge_hip_index_build_for", "lrge_hip_index_build_sharded", "lrge_hip_index_build_tsharded", "lrge_hip_last_shard_stats", "lrge_hip_index_free",
     "lrge_hip_comm_alltoallv", "lrge_hip_comm_rccl_ranks", "lrge_hip_comm_rccl_ops", "lrge_hip_comm_local_group_serialize", "lrge_hip_comm_local_turn",
     "lrge_hip_comm_busy_ms", "lrge_hip_comm_standin_ms",
@@ -166,6 +167,8 @@ def lib():
         L.lrge_hip_reads_seek_stats.argtypes = [vp, C.POINTER(C.c_uint64 * 4)]
     if hasattr(L, "lrge_hip_reads_zstd_stats"):              # (LRGE_HIP_LIB_AB may name a build from before the sliding Zstandard ingest)
         L.lrge_hip_reads_zstd_stats.argtypes = [vp, C.POINTER(C.c_uint64 * 4)]
+    if hasattr(L, "lrge_hip_last_stream_stats"):             # (LRGE_HIP_LIB_AB may name a build from before the streamed first pass)
+        L.lrge_hip_last_stream_stats.argtypes = [vp, C.POINTER(C.c_uint64 * 4)]
     L.lrge_hip_reads_free.argtypes = [vp]
     L.lrge_hip_reads_free.restype = None
     L.lrge_hip_pack_choice.argtypes = [C.c_int, C.POINTER(C.c_double)]

@@ -12,6 +12,8 @@
 // leaves a seek map behind, with which lrge_hip_reads_open_mapped* brings only the runs of plain or BGZF input that hold chosen records
 // (fx_seek.h, fx_src_seek_raw, fx_src_seek_bgzf); with the formats' own opt-in flags the four sampled calls take unaligned
 // BAM, Zstandard (section 26), unaligned SAM through its windows and unaligned CRAM through fx_cram_sampled (section 27).
+// With LRGE_GPU_INGEST_STREAM the four first-pass calls that take a path read plain, BGZF and gzip files in pinned pieces instead of whole
+// (fx_input.h, fx_open_stream, fx_src_raw_stream, fx_src_bgzf_stream).
 // Included into lrge_hip.hip.
 // A call (lrge_hip_reads_open_mem) is one source (fx_src_raw, _bgzf, _gzip, _bzip2), which brings the text to the sink (FxSink) resident
 // or through the windows of the sink's FxWinRun, and one record scan (fx_parse_kind), chosen by the sniff (fx_kind).
@@ -21,6 +23,7 @@
 #include <unistd.h>
 
 #include "dev_keep.h"
+#include "fx_input.h"
 #include "fx_window.h"
 #include "fx_seek.h"
 #include "cram_round.h"
@@ -67,6 +70,15 @@ static int fx_sel_checked(lrge_hip_ctx *ctx, const u32 *sel, u64 k) {
 }
 static int fx_ordinal_rc(lrge_hip_ctx *ctx, u32 ordinal, u64 records) { LRGE_SET_ERR(ctx, "reads_open_selected: ordinal %u of %llu records", ordinal, (unsigned long long)records); return LRGE_ERR_INVALID; }
 static int fx_read_failed(lrge_hip_ctx *ctx) { ctx->err = "reads_open_mapped: the file could not be read"; return LRGE_ERR_IO; }
+// the streamed first pass
+static int fx_open_failed(lrge_hip_ctx *ctx, const char *path) { LRGE_SET_ERR(ctx, "IO error: %s: cannot be opened for reading by range", path); return LRGE_ERR_IO; }
+static int fx_stream_read_failed(lrge_hip_ctx *ctx) { ctx->err = "reads_open: the file could not be read"; return LRGE_ERR_IO; }
+static int fx_stream_needs_windowed(lrge_hip_ctx *ctx) { ctx->err = "reads_open: LRGE_GPU_INGEST_STREAM without LRGE_GPU_INGEST_WINDOWED"; return LRGE_ERR_INVALID; }
+static int fx_stream_needs_aln(lrge_hip_ctx *ctx) { ctx->err = "reads_open: BAM or SAM text under LRGE_GPU_INGEST_STREAM without LRGE_GPU_INGEST_WINDOWED_ALN"; return LRGE_ERR_UNPROVEN; }
+static int fx_stream_not_bgzf(lrge_hip_ctx *ctx, u64 off) {
+    LRGE_SET_ERR(ctx, "reads_open: no BGZF block at file offset %llu behind BGZF blocks: open without LRGE_GPU_INGEST_STREAM", (unsigned long long)off);
+    return LRGE_ERR_UNPROVEN;
+}
 static int fx_map_other(lrge_hip_ctx *ctx) { ctx->err = "reads_open_mapped: the map is of another input"; return LRGE_ERR_INVALID; }
 static int fx_map_misfit(lrge_hip_ctx *ctx, const char *what) { LRGE_SET_ERR(ctx, "reads_open_mapped: the map does not fit the input (%s)", what); return LRGE_ERR_UNPROVEN; }
 static int fx_map_range(lrge_hip_ctx *ctx) { ctx->err = "reads_open_mapped: a file range does not hold the blocks of the map"; return LRGE_ERR_INVALID; }
@@ -600,8 +612,9 @@ struct FxSink {
     DevKeep blk;
     const u8 *host_text = nullptr;              // the file's bytes, when they are the text
     FxKeepMode mode;                            // the census and the selected open: every text goes through the windows, whatever its size
+    static u64 window_bytes(lrge_hip_ctx *c, u64 cap) { return std::max<u64>(1, c->opt_u64("INGEST_WINDOW_BYTES", std::min<u64>((u64)1 << 30, cap / 4))); }
     FxSink(lrge_hip_ctx *c, lrge_hip_reads *r, int f, FxKeepMode m = FX_KEEP_ALL) : ctx(c), R(r), flags(f), cap(ingest_cap(c)),
-        window(std::max<u64>(1, c->opt_u64("INGEST_WINDOW_BYTES", std::min<u64>((u64)1 << 30, cap / 4)))), blk(c), mode(m) {
+        window(window_bytes(c, cap)), blk(c), mode(m) {
         if ((flags & LRGE_GPU_INGEST_WINDOWED) || mode != FX_KEEP_ALL) run.reset(new FxWinRun(ctx, R, flags, cap, window));
         blk.keep_max = cap; blk.keep_slack = FX_PAD;
     }
@@ -659,9 +672,9 @@ static int fx_src_raw(FxSink &s, const u8 *d, u64 len) {
 }
 
 // blocks `t` of BGZF file d decoded to dst + their o_off by the chunk pipeline of host_inflate.inl, every block checked
-static int fx_bgzf_decode(lrge_hip_ctx *ctx, const u8 *d, const std::vector<BgzfBlock> &t, u8 *dst) {
+static int fx_bgzf_decode(lrge_hip_ctx *ctx, const u8 *d, const std::vector<BgzfBlock> &t, u8 *dst, bool d_pinned = false) {
     BgzfBad bad;
-    const int rc = bgzf_inflate_chunks(ctx, d, t, nullptr, dst, "reads_open: bgzf inflate", &bad);
+    const int rc = bgzf_inflate_chunks(ctx, d, t, nullptr, dst, "reads_open: bgzf inflate", &bad, d_pinned);
     if (rc) return rc;
     if (bad.status != INF_OK) { ctx->err = "reads_open: a BGZF block failed its checks"; return LRGE_ERR_UNPROVEN; }
     return LRGE_OK;
@@ -747,18 +760,23 @@ static int fx_inflate_to_device(FxSink &s, Dev &dev, Run run, const char *codec,
 }
 
 // any other gzip input.  map: the census leaves the entry table of a seek map behind (gzip_round.h GzSeekRec)
-static int fx_src_gzip(FxSink &s, const u8 *d, u64 len, FxSeekMap *map = nullptr) {
+// src: the streamed first pass -- d is null, and the rounds' ranges [off, off + n) of the file are read from src as they are staged (GzDev::stage)
+static int fx_src_gzip(FxSink &s, const u8 *d, u64 len, FxSeekMap *map = nullptr, const FxInput *src = nullptr) {
     lrge_hip_ctx *ctx = s.ctx;
     if (!(s.flags & LRGE_GPU_INFLATE_GZIP)) { ctx->err = "reads_open: gzip input without LRGE_GPU_INFLATE_GZIP"; return LRGE_ERR_UNPROVEN; }
     const GzCfg cfg = gz_cfg(ctx);
     GzStats st;
     GzDev dev(ctx, cfg);
+    dev.src = src;
     // a first size: the last member's ISIZE (the whole text of a single-member file below 4 GiB); later rounds grow the block
-    if (len >= 18) dev.keep_hint = std::min<u64>(s.cap, bgzf_u32(d + len - 4));
+    u32 isize = 0;
+    if (src && !src->gzip_isize(&isize)) return fx_stream_read_failed(ctx);
+    if (len >= 18) dev.keep_hint = std::min<u64>(s.cap, src ? isize : bgzf_u32(d + len - 4));
     GzSeekRec<GzDev> rec = {map, map ? map->gz_spacing : 0};
-    return fx_inflate_to_device(s, dev, [&](u64 *bad) {
+    const int rc = fx_inflate_to_device(s, dev, [&](u64 *bad) {
         return map ? gz_run(dev, d, len, cfg, [](const uint8_t *, uint64_t) { return true; }, st, bad, &rec) : gz_run(dev, d, len, cfg, [](const uint8_t *, uint64_t) { return true; }, st, bad);
     }, "gzip", "reads_open: gzip data not proven on the device (status %d near file offset %llu)", [](int rc) { return rc; });
+    return dev.io_failed ? fx_stream_read_failed(ctx) : rc;
 }
 
 // bzip2.  map: the census leaves the block table, the marks and the entries of a seek map behind (bz_round.h BzSeekRec)
@@ -864,6 +882,38 @@ static FxReadsGuard fx_new_reads(lrge_hip_ctx *ctx) {
     return guard;
 }
 
+// a census that leaves a seek map: the map as every source finds it
+static void fx_map_begin(FxSink &s, FxSeekMap *map, u64 file_len) {
+    *map = FxSeekMap();
+    map->stride = std::max<u64>(1, s.ctx->opt_u64("INGEST_SEEK_STRIDE_BYTES", 65536));
+    map->kind = FX_SEEK_OTHER; map->file_len = file_len;
+    s.run->dev.map = map;
+}
+static void fx_map_gzip(lrge_hip_ctx *ctx, FxSeekMap *map) { map->kind = FX_SEEK_GZIP; map->gz_spacing = std::max<u64>(1, ctx->opt_u64("INGEST_SEEK_GZIP_BYTES", (u64)1 << 20)); }
+
+// behind the source of a call: the end that fits how the text arrived (windowed: windows were flushed, or the run does not keep all), the
+// tables of the seek map (t: the block table of a BGZF file), and the handle is the caller's
+static int fx_open_finish(FxSink &s, FxReadsGuard &guard, bool windowed, FxSeekMap *map, const std::vector<BgzfBlock> &t, double t0, lrge_hip_reads **out) {
+    int rc;
+    if ((rc = windowed ? fx_finish_windowed(s, t0) : fx_finish_resident(s, t0))) return rc;
+    if (map) {
+        map->records = guard->sel.seen; map->bases = guard->sel.bases_seen; map->text_bytes = guard->text_bytes; map->windows = guard->win.windows;
+        map->fmt = guard->fmt;
+        if (map->kind == FX_SEEK_BGZF) fx_seek_attach(*map, t.data(), t.size());
+        // (BAM and SAM inside plain gzip keep the full selected pass: DESIGN section 28 -- the entry table is dropped)
+        // ... and so does a map that is not worth entering (fx_gz_enterable)
+        if (map->kind == FX_SEEK_GZIP && (map->fmt == FX_FMT_BAM || map->fmt == FX_FMT_SAM || !fx_gz_enterable(*map))) { map->kind = FX_SEEK_OTHER; map->ent = {}; map->ent_win = {}; map->gz_spacing = 0; }
+        if (map->kind == FX_SEEK_GZIP) fx_seek_attach_gzip(*map);
+        // (BAM and SAM inside bzip2 too; and a sole entry over several blocks could skip nothing: fx_bz_enterable)
+        if (map->kind == FX_SEEK_BZIP2 && (map->fmt == FX_FMT_BAM || map->fmt == FX_FMT_SAM || !fx_bz_enterable(*map))) {
+            map->kind = FX_SEEK_OTHER; map->bz = {}; map->bz_marks = {}; map->bz_ent = {}; map->bz_spacing = 0; map->bz_level = 0;
+        }
+        if (map->kind == FX_SEEK_BZIP2) fx_seek_attach_bzip2(*map);
+    }
+    *out = guard.release();
+    return LRGE_OK;
+}
+
 // one call: lrge_hip_reads_open_mem (FX_KEEP_ALL), the census (FX_KEEP_NONE) or the selected open (FX_KEEP_SEL with sel[0, k))
 // map: a census (FX_KEEP_NONE) that leaves the seek map of the text behind (fx_seek.h)
 static int fx_open_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, int flags, FxKeepMode mode, const u32 *sel, u64 k, lrge_hip_reads **out, FxSeekMap *map = nullptr) {
@@ -890,16 +940,11 @@ static int fx_open_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, 
     std::vector<BgzfBlock> t;
     uint64_t total = 0;
     if (mode != FX_KEEP_ALL && (rc = s.run->dev.select(mode, sel, k))) return rc;
-    if (map) {
-        *map = FxSeekMap();
-        map->stride = std::max<u64>(1, ctx->opt_u64("INGEST_SEEK_STRIDE_BYTES", 65536));
-        map->kind = FX_SEEK_OTHER; map->file_len = len;
-        s.run->dev.map = map;
-    }
+    if (map) fx_map_begin(s, map, len);
     if (box == FX_BOX_GZIP) {
         const bool bgzf = bgzf_scan_blocks(d, len, &t, &total);
         if (map && bgzf) { map->kind = FX_SEEK_BGZF; map->n_blocks = t.size(); }
-        if (map && !bgzf) { map->kind = FX_SEEK_GZIP; map->gz_spacing = std::max<u64>(1, ctx->opt_u64("INGEST_SEEK_GZIP_BYTES", (u64)1 << 20)); }
+        if (map && !bgzf) fx_map_gzip(ctx, map);
         rc = bgzf ? fx_src_bgzf(s, d, t, total) : fx_src_gzip(s, d, len, map);
     }
     else if (box == FX_BOX_BZIP2 && (flags & LRGE_GPU_INFLATE_BZIP2)) {
@@ -913,23 +958,7 @@ static int fx_open_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, 
         rc = LRGE_ERR_UNPROVEN;
     } else { if (map) map->kind = FX_SEEK_PLAIN; rc = fx_src_raw(s, d, len); }
     if (rc) return rc;
-    if ((rc = s.run && (s.run->win.st.windows || mode != FX_KEEP_ALL) ? fx_finish_windowed(s, t0) : fx_finish_resident(s, t0))) return rc;
-    if (map) {
-        map->records = guard->sel.seen; map->bases = guard->sel.bases_seen; map->text_bytes = guard->text_bytes; map->windows = guard->win.windows;
-        map->fmt = guard->fmt;
-        if (map->kind == FX_SEEK_BGZF) fx_seek_attach(*map, t.data(), t.size());
-        // (BAM and SAM inside plain gzip keep the full selected pass: DESIGN section 28 -- the entry table is dropped)
-        // ... and so does a map that is not worth entering (fx_gz_enterable)
-        if (map->kind == FX_SEEK_GZIP && (map->fmt == FX_FMT_BAM || map->fmt == FX_FMT_SAM || !fx_gz_enterable(*map))) { map->kind = FX_SEEK_OTHER; map->ent = {}; map->ent_win = {}; map->gz_spacing = 0; }
-        if (map->kind == FX_SEEK_GZIP) fx_seek_attach_gzip(*map);
-        // (BAM and SAM inside bzip2 too; and a sole entry over several blocks could skip nothing: fx_bz_enterable)
-        if (map->kind == FX_SEEK_BZIP2 && (map->fmt == FX_FMT_BAM || map->fmt == FX_FMT_SAM || !fx_bz_enterable(*map))) {
-            map->kind = FX_SEEK_OTHER; map->bz = {}; map->bz_marks = {}; map->bz_ent = {}; map->bz_spacing = 0; map->bz_level = 0;
-        }
-        if (map->kind == FX_SEEK_BZIP2) fx_seek_attach_bzip2(*map);
-    }
-    *out = guard.release();
-    return LRGE_OK;
+    return fx_open_finish(s, guard, s.run && (s.run->win.st.windows || mode != FX_KEEP_ALL), map, t, t0, out);
 }
 
 extern "C" int lrge_hip_reads_open_mem(lrge_hip_ctx *ctx, const void *file_bytes, uint64_t len, int flags, lrge_hip_reads **out) {
@@ -969,15 +998,218 @@ template <class F> static int fx_with_file(lrge_hip_ctx *ctx, const char *path, 
     return rc ? rc : mem(raw.data(), (uint64_t)raw.size());
 }
 
+// ---- the streamed first pass (LRGE_GPU_INGEST_STREAM): the file is read in pieces into two pinned slots ----
+// Two pinned host buffers that grow on demand, an event each that says when the copy out of it is done.  peak: the most bytes both held
+struct FxSlots {
+    lrge_hip_ctx *ctx;
+    u8 *p[2] = {nullptr, nullptr};
+    u64 cap[2] = {0, 0}, peak = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool busy[2] = {false, false};
+    explicit FxSlots(lrge_hip_ctx *c) : ctx(c) {}
+    ~FxSlots() { release(); }
+    void release() {
+        for (int i = 0; i < 2; ++i) {
+            if (busy[i]) (void)hipEventSynchronize(ev[i]);
+            if (ev[i]) (void)hipEventDestroy(ev[i]);
+            if (p[i]) (void)hipHostFree(p[i]);
+            p[i] = nullptr; cap[i] = 0; ev[i] = nullptr; busy[i] = false;
+        }
+    }
+    // slot i holds `bytes` bytes at least; its contents are not kept
+    int need(int i, u64 bytes) {
+        if (p[i] && cap[i] >= bytes) return LRGE_OK;
+        int rc;
+        if ((rc = wait(i))) return rc;
+        if (p[i]) (void)hipHostFree(p[i]);
+        p[i] = nullptr; cap[i] = 0;
+        HIPCHK(ctx, hipHostMalloc((void **)&p[i], (size_t)std::max<u64>(bytes, 64), hipHostMallocDefault));
+        cap[i] = std::max<u64>(bytes, 64);
+        peak = std::max(peak, cap[0] + cap[1]);
+        return LRGE_OK;
+    }
+    // a copy out of slot i was queued on `st`: the slot is written again only behind it
+    int sent(int i, hipStream_t st) {
+        if (!ev[i]) HIPCHK(ctx, hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
+        HIPCHK(ctx, hipEventRecord(ev[i], st));
+        busy[i] = true;
+        return LRGE_OK;
+    }
+    int wait(int i) {
+        if (busy[i]) { busy[i] = false; HIPCHK(ctx, hipEventSynchronize(ev[i])); }
+        return LRGE_OK;
+    }
+};
+
+// plain input: slot 0 holds the file's first n0 bytes; pread fills one slot while the copy of the other is in flight, a piece at a time
+static int fx_src_raw_stream(FxSink &s, const FxInput &in, FxSlots &sl, u64 n0, u64 piece) {
+    lrge_hip_ctx *ctx = s.ctx;
+    s.run->attach(&s.blk);
+    int rc, cur = 0;
+    for (u64 fill = n0, fpos = n0;;) {
+        if ((rc = s.room(fill))) return rc;
+        HIPCHK(ctx, hipMemcpyAsync(s.blk.keep + s.blk.keep_len, sl.p[cur], (size_t)fill, hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = sl.sent(cur, ctx->stream))) return rc;
+        s.blk.keep_len += fill;
+        const u64 next = std::min<u64>(piece, in.len - fpos);
+        if (next) {
+            if ((rc = sl.need(cur ^ 1, next)) || (rc = sl.wait(cur ^ 1))) return rc;
+            if (!in.read(fpos, next, sl.p[cur ^ 1])) return fx_stream_read_failed(ctx);
+        }
+        if ((rc = s.appended())) return rc;
+        if (s.run->win.off) return fx_stream_needs_aln(ctx);
+        if (!next) break;
+        cur ^= 1; fill = next; fpos += next;
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    s.hand_over(s.blk);
+    return LRGE_OK;
+}
+
+// BGZF: slot 0 holds the file's first n0 bytes.  A slot holds the partial member the slot before it ended in and up to P bytes read
+// behind it (more where one member needs more); its whole members are found by the walk of bgzf_scan.h and decoded from where they
+// lie, in batches of a window of text as fx_src_bgzf makes them; the partial member at its end moves to the front of the other
+// slot.  Whether the file is BGZF is its first member's word (*is_bgzf false: nothing was delivered, the gzip source takes the
+// file); a later member that is no BGZF block, a truncated one and trailing bytes end the call.  all (may be null): the whole
+// file's block table, for a seek map
+static int fx_src_bgzf_stream(FxSink &s, const FxInput &in, FxSlots &sl, u64 n0, u64 P, std::vector<BgzfBlock> *all, bool *is_bgzf) {
+    lrge_hip_ctx *ctx = s.ctx;
+    *is_bgzf = false;
+    int rc, cur = 0;
+    u64 fill = n0, base = 0, fpos = n0, o = 0, need = 18;      // the slot holds file [base, base + fill); fpos: the next byte to read; o: text bytes so far
+    for (;;) {
+        std::vector<BgzfBlock> part;                           // the slot's whole members, c_off counted from the slot's front
+        u64 used = 0, bad = 0;
+        const int w = bgzf_walk_members(sl.p[cur], fill, base, 0, &o, &part, &used, &need, &bad);
+        const bool over = fpos == in.len;
+        if (w == BGZF_MEMBER_BAD || (w == BGZF_MEMBER_MORE && over)) {
+            if (!*is_bgzf && part.empty()) return LRGE_OK;
+            return fx_stream_not_bgzf(ctx, w == BGZF_MEMBER_BAD ? bad : base + used);
+        }
+        if (w == BGZF_MEMBER_OK) need = 18;
+        if (!part.empty()) {
+            if (!*is_bgzf) {
+                *is_bgzf = true;
+                if (!(s.flags & LRGE_GPU_INFLATE_BGZF)) { ctx->err = "reads_open: BGZF input without LRGE_GPU_INFLATE_BGZF"; return LRGE_ERR_UNPROVEN; }
+                s.run->attach(&s.blk);
+            }
+            if (all) for (BgzfBlock b : part) { b.c_off += base; all->push_back(b); }
+            const auto isize = [&](size_t b) { return (u64)part[b].isize; };
+            for (size_t i = 0, j; i < part.size(); i = j) {
+                u64 bytes;
+                j = fx_batch_end(i, part.size(), s.window, isize, &bytes);
+                if ((rc = s.room(bytes)) || (rc = fx_bgzf_decode(ctx, sl.p[cur], fx_bgzf_part(part, i, j, s.blk.keep_len), s.blk.keep, true))) return rc;
+                s.blk.keep_len += bytes;
+                if ((rc = s.appended())) return rc;
+                if (s.run->win.off) return fx_stream_needs_aln(ctx);
+            }
+        }
+        const u64 rest = fill - used;
+        if (over && !rest) break;
+        const u64 more = std::min<u64>(in.len - fpos, std::max<u64>(P, need > rest ? need - rest : 0));
+        if ((rc = sl.need(cur ^ 1, std::max<u64>(sl.cap[0], rest + more)))) return rc;     // (slot 0 was made for P bytes and one member: the two are the same size whatever the file's length)
+        if (rest) memcpy(sl.p[cur ^ 1], sl.p[cur] + used, (size_t)rest);
+        if (!in.read(fpos, more, sl.p[cur ^ 1] + rest)) return fx_stream_read_failed(ctx);
+        cur ^= 1; base += used; fill = rest + more; fpos += more;
+    }
+    s.hand_over(s.blk);
+    return LRGE_OK;
+}
+
+// One call that takes a path under LRGE_GPU_INGEST_STREAM: plain text, BGZF and gzip are read in pieces of option INGEST_STREAM_BYTES
+// and every text passes through the windows whatever its size; every other container, and an empty file, is read whole as without
+// the flag.  The call's reading is left in ctx->stream_stats
+static int fx_open_stream(lrge_hip_ctx *ctx, FxInput &in, int flags, FxKeepMode mode, const u32 *sel, u64 k, lrge_hip_reads **out, FxSeekMap *map = nullptr) {
+    *out = nullptr;
+    int rc;
+    if (mode == FX_KEEP_SEL && (rc = fx_sel_checked(ctx, sel, k))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const double t0 = fx_now_ms();
+    const u64 P = std::max<u64>(1, ctx->opt_u64("INGEST_STREAM_BYTES", (u64)64 << 20));
+    const u64 piece = std::min<u64>(P, FxSink::window_bytes(ctx, ingest_cap(ctx)));
+    const u64 n0 = std::min<u64>(in.len, std::max<u64>(piece, 6));      // (the sniff of the container wants six bytes)
+    FxSlots sl(ctx);
+    u64 pinned = 0;
+    const auto stats = [&](bool streamed) { ctx->stream_stats[0] = in.n_reads; ctx->stream_stats[1] = in.n_bytes; ctx->stream_stats[2] = std::max(pinned, sl.peak); ctx->stream_stats[3] = streamed; };
+    stats(false);
+    // (P bytes and the partial member in front of them: the size a BGZF slot needs, so that the pinned bytes do not depend on where the members lie)
+    if (n0 && ((rc = sl.need(0, std::max<u64>(n0, std::min<u64>(P, in.len)) + 65536)) || (rc = in.read(0, n0, sl.p[0]) ? (int)LRGE_OK : fx_stream_read_failed(ctx)))) return rc;
+    const FxBox box = fx_container(sl.p[0], n0);
+    if (!n0 || (box != FX_BOX_OTHER && box != FX_BOX_GZIP)) {  // read whole: the route without the flag
+        sl.release();
+        std::string raw;
+        if (!(rc = fx_slurp(ctx, in.path, &raw))) { ++in.n_reads; in.n_bytes += raw.size(); rc = fx_open_mem(ctx, raw.data(), raw.size(), flags, mode, sel, k, out, map); }
+        stats(false);
+        return rc;
+    }
+    FxReadsGuard guard = fx_new_reads(ctx);
+    FxSink s(ctx, guard.get(), flags, mode);
+    std::vector<BgzfBlock> t;
+    if (mode != FX_KEEP_ALL && (rc = s.run->dev.select(mode, sel, k))) return rc;
+    if (map) fx_map_begin(s, map, in.len);
+    if (box == FX_BOX_GZIP) {
+        bool bgzf = false;
+        rc = fx_src_bgzf_stream(s, in, sl, n0, P, map ? &t : nullptr, &bgzf);
+        if (map && bgzf) { map->kind = FX_SEEK_BGZF; map->n_blocks = t.size(); }
+        if (!rc && !bgzf) {
+            sl.release();
+            if (map) fx_map_gzip(ctx, map);
+            rc = fx_src_gzip(s, nullptr, in.len, map, &in);
+            pinned = ctx->gz_pin_cap[0];
+        }
+    } else { if (map) map->kind = FX_SEEK_PLAIN; rc = fx_src_raw_stream(s, in, sl, n0, piece); }
+    stats(true);
+    if (rc) return rc;
+    if (s.run->win.off) return fx_stream_needs_aln(ctx);
+    sl.release();
+    rc = fx_open_finish(s, guard, true, map, t, t0, out);
+    if (!rc && s.run->win.off) { lrge_hip_reads_free(*out); *out = nullptr; return fx_stream_needs_aln(ctx); }      // (a text that ended before its first flush was sniffed by the last window)
+    return rc;
+}
+// the census of a streamed call, as fx_census
+static int fx_census_stream(lrge_hip_ctx *ctx, FxInput &in, int flags, uint64_t out[4], FxSeekMap *map) {
+    lrge_hip_reads *r = nullptr;
+    const int rc = fx_open_stream(ctx, in, flags, FX_KEEP_NONE, nullptr, 0, &r, map);
+    if (rc) return rc;
+    out[0] = r->sel.seen; out[1] = r->sel.bases_seen; out[2] = r->text_bytes; out[3] = r->win.windows;
+    lrge_hip_reads_free(r);
+    return LRGE_OK;
+}
+// ... for the four calls that take a path: with the flag `streamed(in)`, else mem(bytes, len) over the whole file
+template <class S, class F> static int fx_with_path(lrge_hip_ctx *ctx, const char *path, int flags, S streamed, F mem) {
+    if (flags & LRGE_GPU_INGEST_STREAM) {
+        FxInput in;
+        memset(ctx->stream_stats, 0, sizeof ctx->stream_stats);
+        if (!in.open_path(path)) return fx_open_failed(ctx, path);
+        return streamed(in);
+    }
+    const int rc = fx_with_file(ctx, path, [&](const void *d, uint64_t n) {
+        ctx->stream_stats[0] = 1; ctx->stream_stats[1] = n; ctx->stream_stats[2] = ctx->stream_stats[3] = 0;
+        return mem(d, n);
+    });
+    if (rc == LRGE_ERR_IO) memset(ctx->stream_stats, 0, sizeof ctx->stream_stats);
+    return rc;
+}
+
+extern "C" int lrge_hip_last_stream_stats(const lrge_hip_ctx *ctx, uint64_t out[4]) {
+    if (!ctx || !out) return LRGE_ERR_INVALID;
+    memcpy(out, ctx->stream_stats, sizeof ctx->stream_stats);
+    return LRGE_OK;
+}
+
 extern "C" int lrge_hip_reads_census(lrge_hip_ctx *ctx, const char *path, int flags, uint64_t out[4]) {
     if (!ctx || !path || !out) return LRGE_ERR_INVALID;
-    return fx_with_file(ctx, path, [&](const void *d, uint64_t n) { return lrge_hip_reads_census_mem(ctx, d, n, flags, out); });
+    return fx_with_path(ctx, path, flags, [&](FxInput &in) {
+        out[0] = out[1] = out[2] = out[3] = 0;
+        return fx_census_stream(ctx, in, flags, out, nullptr);
+    }, [&](const void *d, uint64_t n) { return lrge_hip_reads_census_mem(ctx, d, n, flags, out); });
 }
 
 extern "C" int lrge_hip_reads_open_selected(lrge_hip_ctx *ctx, const char *path, int flags, const uint32_t *sel, uint32_t k, lrge_hip_reads **out) {
     if (!ctx || !path || !out) return LRGE_ERR_INVALID;
     *out = nullptr;
-    return fx_with_file(ctx, path, [&](const void *d, uint64_t n) { return lrge_hip_reads_open_selected_mem(ctx, d, n, flags, sel, k, out); });
+    return fx_with_path(ctx, path, flags, [&](FxInput &in) { return fx_open_stream(ctx, in, flags, FX_KEEP_SEL, sel, k, out); },
+                        [&](const void *d, uint64_t n) { return lrge_hip_reads_open_selected_mem(ctx, d, n, flags, sel, k, out); });
 }
 
 extern "C" int lrge_hip_reads_select_stats(const lrge_hip_reads *r, uint64_t out[4]) {
@@ -1000,7 +1232,13 @@ extern "C" int lrge_hip_reads_census_map_mem(lrge_hip_ctx *ctx, const void *file
 extern "C" int lrge_hip_reads_census_map(lrge_hip_ctx *ctx, const char *path, int flags, uint64_t out[4], lrge_hip_read_map **map) {
     if (!ctx || !path || !out || !map) return LRGE_ERR_INVALID;
     *map = nullptr;
-    return fx_with_file(ctx, path, [&](const void *d, uint64_t n) { return lrge_hip_reads_census_map_mem(ctx, d, n, flags, out, map); });
+    return fx_with_path(ctx, path, flags, [&](FxInput &in) {
+        out[0] = out[1] = out[2] = out[3] = 0;
+        std::unique_ptr<lrge_hip_read_map> m(new lrge_hip_read_map());
+        const int rc = fx_census_stream(ctx, in, flags, out, &m->m);
+        if (!rc) *map = m.release();
+        return rc;
+    }, [&](const void *d, uint64_t n) { return lrge_hip_reads_census_map_mem(ctx, d, n, flags, out, map); });
 }
 
 extern "C" void lrge_hip_read_map_free(lrge_hip_read_map *map) { delete map; }
@@ -1036,24 +1274,7 @@ extern "C" int lrge_hip_reads_seek_stats(const lrge_hip_reads *r, uint64_t out[4
     return LRGE_OK;
 }
 
-// the file of a mapped open: the whole buffer, or a descriptor that is read by range
-struct FxInput {
-    const u8 *d = nullptr;
-    u64 len = 0;
-    int fd = -1;
-    const char *path = nullptr;
-    ~FxInput() { if (fd >= 0) close(fd); }
-    bool read(u64 off, u64 n, u8 *dst) const {
-        if (off > len || n > len - off) return false;
-        if (d) { if (n) memcpy(dst, d + off, (size_t)n); return true; }
-        for (u64 got = 0; got < n;) {
-            const ssize_t k = pread(fd, dst + got, (size_t)(n - got), (off_t)(off + got));
-            if (k <= 0) return false;
-            got += (u64)k;
-        }
-        return true;
-    }
-};
+// (the file of a mapped open -- the whole buffer, or a descriptor that is read by range: FxInput, fx_input.h)
 // the whole file in memory, for what takes a buffer: the input is read by its path into raw, unless it is a buffer already
 static int fx_input_whole(lrge_hip_ctx *ctx, FxInput &in, std::string *raw) {
     if (in.d) return LRGE_OK;
@@ -1422,7 +1643,9 @@ static int fx_open_mapped(lrge_hip_ctx *ctx, FxInput &in, int flags, const lrge_
         if (sel[j] >= m.records) return fx_ordinal_rc(ctx, sel[j], m.records);
     if (m.kind == FX_SEEK_OTHER) {              // a container that cannot be entered: the full selected pass, the same handle
         lrge_hip_reads *r = nullptr;
-        if ((rc = fx_input_whole(ctx, in, &raw)) || (rc = fx_open_mem(ctx, in.d, in.len, flags, FX_KEEP_SEL, sel, k, &r))) return rc;
+        // (the path form under LRGE_GPU_INGEST_STREAM: that pass streams where the container allows)
+        if (!in.d && (flags & LRGE_GPU_INGEST_STREAM)) { if ((rc = fx_open_stream(ctx, in, flags, FX_KEEP_SEL, sel, k, &r))) return rc; }
+        else if ((rc = fx_input_whole(ctx, in, &raw)) || (rc = fx_open_mem(ctx, in.d, in.len, flags, FX_KEEP_SEL, sel, k, &r))) return rc;
         if (r->sel.seen != m.records || r->text_bytes != m.text_bytes) { lrge_hip_reads_free(r); return fx_map_misfit(ctx, "another record count"); }
         *out = r;
         return LRGE_OK;
@@ -1466,16 +1689,16 @@ extern "C" int lrge_hip_reads_open_mapped(lrge_hip_ctx *ctx, const char *path, i
     if (!ctx || !path || !out || !map) return LRGE_ERR_INVALID;
     *out = nullptr;
     FxInput in;
-    struct stat st;
-    if ((in.fd = open(path, O_RDONLY | O_CLOEXEC)) < 0 || fstat(in.fd, &st) != 0 || !S_ISREG(st.st_mode)) { LRGE_SET_ERR(ctx, "IO error: %s: cannot be opened for reading by range", path); return LRGE_ERR_IO; }
-    in.len = (u64)st.st_size; in.path = path;
+    if (!in.open_path(path)) return fx_open_failed(ctx, path);
     return fx_open_mapped(ctx, in, flags, map, sel, k, out);
 }
 
 extern "C" int lrge_hip_reads_open(lrge_hip_ctx *ctx, const char *path, int flags, lrge_hip_reads **out) {
     if (!ctx || !path || !out) return LRGE_ERR_INVALID;
     *out = nullptr;
-    return fx_with_file(ctx, path, [&](const void *d, uint64_t n) { return lrge_hip_reads_open_mem(ctx, d, n, flags, out); });
+    if ((flags & LRGE_GPU_INGEST_STREAM) && !(flags & LRGE_GPU_INGEST_WINDOWED)) return fx_stream_needs_windowed(ctx);
+    return fx_with_path(ctx, path, flags, [&](FxInput &in) { return fx_open_stream(ctx, in, flags, FX_KEEP_ALL, nullptr, 0, out); },
+                        [&](const void *d, uint64_t n) { return lrge_hip_reads_open_mem(ctx, d, n, flags, out); });
 }
 
 extern "C" uint64_t lrge_hip_reads_count(const lrge_hip_reads *r) { return r ? r->n : 0; }

@@ -8,6 +8,7 @@
 // a round decodes; the pinned buffers are kept in the context across calls.
 
 #include "dev_keep.h"
+#include "fx_input.h"
 
 static const char *gz_status_name(u32 s) {
     switch (s) {
@@ -67,10 +68,15 @@ struct GzDev : DevKeep {
     int cur = 0;
     u64 pf_off = 0; u32 pf_len = 0; bool pf = false;
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
+    // src: the streamed first pass -- the round's bytes are read from the file into the pinned buffer, `d` is a
+    // null base; a read that fails stops the run (io_failed: the caller reports an IO error, not a device failure)
+    const FxInput *src = nullptr;
+    bool io_failed = false;
     bool stage(const uint8_t *d, u64 off, u32 len, int slot, hipStream_t st) {
         u8 *h = ctx_pin(0, len);
         if (!h || !in2[slot].need(len, &e)) return false;
-        memcpy(h, d + off, len);
+        if (!src) memcpy(h, d + off, len);
+        else if (!src->read(off, len, h)) { io_failed = true; return false; }
         return ok(hipMemcpyAsync(in2[slot].p, h, len, hipMemcpyHostToDevice, st));
     }
     void prefetch(const uint8_t *d, uint64_t off, uint32_t len) {

@@ -39,7 +39,10 @@ struct BgzfBad { u32 status; u64 c_off; };      // the first block that failed i
 // Every block of `t` (a table of `comp`) decoded into [0, sum of ISIZE) of d_out, a block resident in HBM, or, when d_out is
 // null, of h_out, a host buffer (null only where no block has output).  LRGE_OK with *bad the first block that failed (the
 // destination is not to be used then), or LRGE_ERR_DEVICE with "<what>: <the runtime's text>".
-static int bgzf_inflate_chunks(lrge_hip_ctx *ctx, const uint8_t *comp, const std::vector<BgzfBlock> &t, uint8_t *h_out, u8 *d_out, const char *what, BgzfBad *bad) {
+// comp_pinned: `comp` is pinned host memory already (the slots of the streamed source, host_fastx.inl): a chunk's bytes go up from
+// where they lie, and the pipeline's own pinned slots hold the block tables alone.
+static int bgzf_inflate_chunks(lrge_hip_ctx *ctx, const uint8_t *comp, const std::vector<BgzfBlock> &t, uint8_t *h_out, u8 *d_out, const char *what, BgzfBad *bad,
+                               bool comp_pinned = false) {
     struct Chunk { size_t b0, b1; u64 c0, cn, o0, on; };
     const u64 limit = std::max<u64>(1, ctx->opt_u64("INFLATE_CHUNK_BYTES", (u64)256 << 20));
     std::vector<Chunk> ch;
@@ -67,7 +70,7 @@ static int bgzf_inflate_chunks(lrge_hip_ctx *ctx, const uint8_t *comp, const std
     hipError_t e = hipSuccess;
     for (int s = 0; s < 2 && e == hipSuccess; ++s) {
         if (!(d_up[s] = (u8 *)ctx->pool.alloc(up_bytes, &e)) || !(d_dn[s] = (u8 *)ctx->pool.alloc(dn_bytes, &e))) break;
-        if ((e = hipHostMalloc((void **)&h_up[s], up_bytes, hipHostMallocDefault)) != hipSuccess) break;
+        if ((e = hipHostMalloc((void **)&h_up[s], comp_pinned ? up_bytes - tab_off : up_bytes, hipHostMallocDefault)) != hipSuccess) break;
         if ((e = hipHostMalloc((void **)&h_dn[s], dn_bytes, hipHostMallocDefault)) != hipSuccess) break;
         if ((e = hipEventCreateWithFlags(&ev_up[s], hipEventDisableTiming)) != hipSuccess) break;
         if ((e = hipEventCreateWithFlags(&ev_k[s], hipEventDisableTiming)) != hipSuccess) break;
@@ -94,13 +97,16 @@ static int bgzf_inflate_chunks(lrge_hip_ctx *ctx, const uint8_t *comp, const std
             // at any offset, the pointer is the chunk's start rounded down (a slot's buffer holds its chunk from byte 0)
             const u32 lead = d_out ? (u32)(c.o0 & 3) : 0;
             u8 *dst = d_out ? d_out + (c.o0 - lead) : d_dn[s];
-            memcpy(h_up[s], comp + c.c0, (size_t)c.cn);
-            InfBlk *tb = (InfBlk *)(h_up[s] + tab_off);
+            if (!comp_pinned) memcpy(h_up[s], comp + c.c0, (size_t)c.cn);
+            InfBlk *tb = (InfBlk *)(h_up[s] + (comp_pinned ? 0 : tab_off));
             for (u32 i = 0; i < n; ++i) {
                 const BgzfBlock &b = t[c.b0 + i];
                 tb[i] = InfBlk{(u32)(b.c_off - c.c0) + b.d_off, b.d_len, (u32)(b.o_off - c.o0) + lead, b.isize, b.crc};
             }
-            if ((e = hipMemcpyAsync(d_up[s], h_up[s], tab_off + (size_t)n * sizeof(InfBlk), hipMemcpyHostToDevice, ctx->copy_stream)) != hipSuccess) break;
+            if (comp_pinned) {
+                if (c.cn && (e = hipMemcpyAsync(d_up[s], comp + c.c0, (size_t)c.cn, hipMemcpyHostToDevice, ctx->copy_stream)) != hipSuccess) break;
+                if ((e = hipMemcpyAsync(d_up[s] + tab_off, tb, (size_t)n * sizeof(InfBlk), hipMemcpyHostToDevice, ctx->copy_stream)) != hipSuccess) break;
+            } else if ((e = hipMemcpyAsync(d_up[s], h_up[s], tab_off + (size_t)n * sizeof(InfBlk), hipMemcpyHostToDevice, ctx->copy_stream)) != hipSuccess) break;
             if ((e = hipEventRecord(ev_up[s], ctx->copy_stream)) != hipSuccess) break;
             if ((e = hipStreamWaitEvent(ctx->stream, ev_up[s], 0)) != hipSuccess) break;
             hipLaunchKernelGGL(k_inflate, dim3(n), dim3(64), 0, ctx->stream, d_up[s], (const InfBlk *)(d_up[s] + tab_off), n, dst, (u32 *)(d_dn[s] + st_off));

@@ -48,6 +48,36 @@ int inflate_twin_scan(const uint8_t *d, uint64_t n, uint64_t *n_blocks, uint64_t
     return 0;
 }
 
+// the block table of the whole buffer, for comparison: 0 and the first min(cap, *n_blocks) records copied to tab (7 words a block:
+// c_off, o_off, d_off, d_len, c_len, isize, crc); -2: not BGZF
+static void twin_table_out(const std::vector<BgzfBlock> &t, uint64_t *tab, uint64_t cap) {
+    for (size_t i = 0; i < t.size() && i < cap; ++i) {
+        const BgzfBlock &b = t[i];
+        const uint64_t w[7] = {b.c_off, b.o_off, b.d_off, b.d_len, b.c_len, b.isize, b.crc};
+        memcpy(tab + 7 * i, w, sizeof w);
+    }
+}
+int inflate_twin_scan_table(const uint8_t *d, uint64_t n, uint64_t *tab, uint64_t cap, uint64_t *n_blocks, uint64_t *out_len) {
+    std::vector<BgzfBlock> t;
+    if (!bgzf_scan_blocks(d, n, &t, out_len)) return -2;
+    *n_blocks = t.size();
+    twin_table_out(t, tab, cap);
+    return 0;
+}
+
+// the incremental walk (BgzfWalk) over the same buffer cut into pieces of `piece` bytes: 0 and the table as above; -2: refused,
+// *bad_off the file offset the walk names
+int inflate_twin_walk_pieces(const uint8_t *d, uint64_t n, uint64_t piece, uint64_t *tab, uint64_t cap, uint64_t *n_blocks, uint64_t *out_len, uint64_t *bad_off) {
+    std::vector<BgzfBlock> t;
+    BgzfWalk w;
+    bool ok = piece != 0;
+    for (uint64_t at = 0; ok && at < n; at += piece) ok = w.feed(d + at, piece < n - at ? piece : n - at, &t);
+    if (!ok || !w.end()) { *bad_off = w.bad_off; return -2; }
+    *n_blocks = t.size(); *out_len = w.o;
+    twin_table_out(t, tab, cap);
+    return 0;
+}
+
 // the whole file: 0 and out_len bytes in `out` (out_cap >= the scan's out_len); -2: not BGZF; > 0: the INF_* status of
 // the first bad block, whose file offset goes to *bad_off
 int inflate_twin_bgzf(const uint8_t *d, uint64_t n, uint8_t *out, uint64_t out_cap, uint64_t *bad_off) {

@@ -180,6 +180,14 @@ class Context:
         self._check(rc)
         return tuple(int(x) for x in out), ReadMap(self, h)
 
+    def last_stream_stats(self):
+        """How the last open_reads / census_reads / open_reads_selected / census_map_reads of a path read its file
+        (lrge_hip_last_stream_stats): (read calls issued, file bytes read, pinned host bytes held for file bytes at the peak, 1 if
+        the pass streamed under _ffi.GPU_INGEST_STREAM -- pieces of option INGEST_STREAM_BYTES -- or 0 if it read the file whole)."""
+        a = (C.c_uint64 * 4)()
+        self._check(self._lib.lrge_hip_last_stream_stats(self.h, C.byref(a)))
+        return tuple(int(x) for x in a)
+
     def open_reads_mapped(self, src, map, sel, flags=_ffi.GPU_INFLATE_BGZF | _ffi.GPU_INFLATE_GZIP):
         """open_reads_selected of the input `map` was made of (lrge_hip_reads_open_mapped*): for plain and BGZF input only the runs
         that hold records `sel` are read, decoded and scanned; the DeviceReads is the one open_reads_selected gives, and

@@ -14,6 +14,13 @@ LRGE_GPU_INGEST_WINDOWED_ZSTD), the census, the selected open
 one thread, then the open of the plain text) run one after the other, so all five alternate in one process; under the key
 "zstd_windowed" of --out.  With LRGE_HIP_LIB_AB naming a build from before the flag only the resident open is timed, under the
 key "zstd_windowed_parent".
+--stream [--sampled K --seek] (kinds fq, bgzf.fq.gz, fq.gz, bam; DESIGN section 30, BASELINE section 20): in every repeat the single windowed
+open, the census and the selected open of K seeded ordinals from a path, each without and with LRGE_GPU_INGEST_STREAM, and with --seek
+the two-pass totals (census with a map, then the mapped open), all alternating in one process; the calls without the flag are
+unchanged code and stand for the parent commit.  lrge_hip_last_stream_stats of every streamed call is kept, and the peak resident
+set of one open per route is taken in a fresh child process each (VmHWM of /proc/self/status before and behind the open: ru_maxrss is
+inherited from the parent across exec).  One warm-up and --reps timed repeats, every repeat
+written; the default --out becomes profiles/ingest_stream_bench.json.
 --sampled K1,K2,.. --seek: on the plain and the BGZF FASTQ file and on the uBAM (kind bam: LRGE_GPU_INGEST_SELECT_ALN), for every K, the census without and with a seek map
 (--kinds fq.gz --sampled K1,K2 --seek [--gzip-chunk-kb N]: the same on the plain gzip FASTQ, entered at the entries of its map; the selected open
 beside it is the route the parent commit took for the mapped open, "blocks_decoded" counts entries, and with --gzip-chunk-kb the result goes under "<K>@chunk<N>k")
@@ -565,6 +572,102 @@ def seek_runs(a, ctx, H, HK, kinds, paths, text_bytes, ks):
     json.dump(result, open(a.out, "w"), indent=1)
 
 
+STREAM = 16384
+STREAM_KINDS = ("fq", "bgzf.fq.gz", "fq.gz", "bam")
+
+
+def _vm_kib(field):
+    """a field of /proc/self/status in KiB (VmHWM: the peak resident set of this process image -- it starts anew at exec, where the
+    ru_maxrss of getrusage is inherited from the parent's high-water mark and says nothing about a child of a large parent)"""
+    for line in open("/proc/self/status"):
+        if line.startswith(field + ":"):
+            return int(line.split()[1])
+    return -1
+
+
+def _rss_child(path, flags):
+    """one open of `path` in this (fresh) process: its code, the stream statistics, and the process's own peak resident set (VmHWM)
+    with the context made, before the open, and behind the open -- the difference is what the open added"""
+    from lrge_amd import engine
+    ctx = engine.Context(0)
+    h, st = C.c_void_p(), (C.c_uint64 * 4)()
+    before = _vm_kib("VmHWM")
+    rc = ctx._lib.lrge_hip_reads_open(ctx.h, path.encode(), flags, C.byref(h))
+    after = _vm_kib("VmHWM")
+    ctx._lib.lrge_hip_last_stream_stats(ctx.h, C.byref(st))
+    ctx._lib.lrge_hip_reads_free(h)
+    print(json.dumps(dict(rc=rc, stream_stats=[int(x) for x in st], vm_hwm_before_open_kib=before, vm_hwm_after_open_kib=after, open_added_kib=after - before)), flush=True)
+    ctx.close()
+
+
+def stream_runs(a, ctx, kinds, paths, text_bytes, k_sel, seek):
+    """every path call without and with LRGE_GPU_INGEST_STREAM on every file, alternating; into a.out"""
+    import numpy as np
+    L = ctx._lib
+    ctx.set_option("INGEST_WINDOW_BYTES", str(a.window_mb << 20))
+    out = {"window_bytes": a.window_mb << 20, "stream_bytes": int(os.environ.get("LRGE_HIP_INGEST_STREAM_BYTES") or (64 << 20)), "reps": a.reps, "k": k_sel, "seek": bool(seek), "files": {}}
+    for kind in kinds:
+        p = paths[kind].encode()
+        with open(paths[kind], "rb") as fh:
+            while fh.read(64 << 20):
+                pass                                                  # page cache
+        open_fl, sel_fl = 15 | 32 | 64, 15 | (1024 if kind == "bam" else 0)
+        runs = {"whole": [], "stream": []}
+        stats, sel, seen = {}, None, {}
+
+        def last():
+            st = (C.c_uint64 * 4)()
+            L.lrge_hip_last_stream_stats(ctx.h, C.byref(st))
+            return [int(x) for x in st]
+
+        def timed(call):
+            t0 = time.perf_counter()
+            rc = call()
+            assert rc == 0, (kind, rc, L.lrge_hip_last_error(ctx.h))
+            return (time.perf_counter() - t0) * 1e3
+
+        for rep_i in range(a.reps + 1):
+            for route, fl in (("whole", 0), ("stream", STREAM)):
+                r, h, cen, m = {}, C.c_void_p(), (C.c_uint64 * 4)(), C.c_void_p()
+                r["open_ms"] = timed(lambda: L.lrge_hip_reads_open(ctx.h, p, open_fl | fl, C.byref(h)))
+                stats[route + "_open"] = last()
+                assert L.lrge_hip_reads_text_bytes(h) == text_bytes[kind] and seen.setdefault("reads", int(L.lrge_hip_reads_count(h))) == L.lrge_hip_reads_count(h)
+                L.lrge_hip_reads_free(h)
+                r["census_ms"] = timed(lambda: L.lrge_hip_reads_census(ctx.h, p, sel_fl | fl, C.byref(cen)))
+                stats[route + "_census"] = last()
+                assert (cen[0], cen[2]) == (seen["reads"], text_bytes[kind]) and seen.setdefault("bases", int(cen[1])) == cen[1], list(cen)
+                if sel is None:
+                    sel = np.sort(np.random.default_rng(1).choice(seen["reads"], min(k_sel, seen["reads"]), replace=False)).astype(np.uint32)
+                r["selected_open_ms"] = timed(lambda: L.lrge_hip_reads_open_selected(ctx.h, p, sel_fl | fl, sel.ctypes.data, sel.size, C.byref(h)))
+                stats[route + "_selected"] = last()
+                assert L.lrge_hip_reads_count(h) == sel.size
+                L.lrge_hip_reads_free(h)
+                r["two_pass_ms"] = r["census_ms"] + r["selected_open_ms"]
+                if seek:
+                    r["census_map_ms"] = timed(lambda: L.lrge_hip_reads_census_map(ctx.h, p, sel_fl | fl, C.byref(cen), C.byref(m)))
+                    r["mapped_open_ms"] = timed(lambda: L.lrge_hip_reads_open_mapped(ctx.h, p, sel_fl | fl, m, sel.ctypes.data, sel.size, C.byref(h)))
+                    assert L.lrge_hip_reads_count(h) == sel.size
+                    L.lrge_hip_reads_free(h)
+                    L.lrge_hip_read_map_free(m)
+                    r["two_pass_seek_ms"] = r["census_map_ms"] + r["mapped_open_ms"]
+                if rep_i:                                              # (run 0 is the warm-up)
+                    runs[route].append(r)
+        f = dict(file_bytes=os.path.getsize(paths[kind]), text_bytes=text_bytes[kind], stream_stats=stats, whole_route=runs["whole"], stream_route=runs["stream"], **seen)
+        for route in ("whole", "stream"):
+            for key in runs[route][0]:
+                f["%s_%s_median" % (route, key)] = statistics.median(x[key] for x in runs[route])
+                f["%s_%s_range" % (route, key)] = (min(x[key] for x in runs[route]), max(x[key] for x in runs[route]))
+        for route, fl in (("whole", 0), ("stream", STREAM)):        # the peak resident set of one open, a fresh child process a route
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--rss-child", paths[kind], str(open_fl | fl), "--window-mb", str(a.window_mb)], capture_output=True, text=True)
+            assert r.returncode == 0, r.stderr[-2000:]
+            f[route + "_open_child"] = json.loads(r.stdout.strip().splitlines()[-1])
+        out["files"][kind] = f
+        print(kind, json.dumps({k: v for k, v in f.items() if not k.endswith("_route")}), flush=True)
+    ctx.set_option("INGEST_WINDOW_BYTES", None)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    json.dump(out, open(a.out, "w"), indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gbases", type=float, default=1.08)
@@ -581,7 +684,12 @@ def main():
     ap.add_argument("--zstd-windowed", type=int, default=0)
     ap.add_argument("--cram-slices", type=int, default=512)
     ap.add_argument("--cram-slice-kb", type=int, default=256)
+    ap.add_argument("--stream", action="store_true")
+    ap.add_argument("--rss-child", nargs=2, metavar=("PATH", "FLAGS"))
     a = ap.parse_args()
+    if a.rss_child:
+        os.environ["LRGE_HIP_INGEST_WINDOW_BYTES"] = str(int(a.window_mb.split(",")[0]) << 20)
+        return _rss_child(a.rss_child[0], int(a.rss_child[1]))
     seek_ks = [int(k) for k in a.sampled.split(",") if int(k)] if a.seek else []
     a.sampled = 0 if a.seek else int(a.sampled)
     if a.seek and not seek_ks:
@@ -618,13 +726,23 @@ def main():
             os.remove(p)
         os.rmdir(work)
         return
-    kinds = [k for k in KINDS + EXTRA_KINDS if k in a.kinds.split(",")]
+    kinds = [k for k in KINDS + EXTRA_KINDS if k in a.kinds.split(",") and (not a.stream or k in STREAM_KINDS)]
     paths, text_bytes = write_files(work, parts, [k for k in kinds if k != "cram"])
     if "cram" in kinds:
         paths["cram"] = os.path.join(work, "ingest.cram")
         text_bytes["cram"] = cram_file(paths["cram"], a.cram_slices, a.cram_slice_kb)      # (what lrge_hip_reads_text_bytes reports: the bases)
     print("files written in %.0f s: %s text bytes" % (time.perf_counter() - t0, text_bytes), flush=True)
     ctx = engine.Context(0)
+    if a.stream:
+        if a.out == os.path.join(ROOT, "profiles", "ingest_bench.json"):
+            a.out = os.path.join(ROOT, "profiles", "ingest_stream_bench.json")
+        a.window_mb = int(a.window_mb.split(",")[0])
+        stream_runs(a, ctx, [k for k in kinds if k in STREAM_KINDS], paths, text_bytes, seek_ks[0] if seek_ks else (a.sampled or 1000), bool(seek_ks))
+        ctx.close()
+        for p in list(paths.values()) + [src, so]:
+            os.remove(p)
+        os.rmdir(work)
+        return
     H = C.CDLL(so)
     H.route_host.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_double * 3), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     H.route_device.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_double * 2), C.POINTER(C.c_float * 4), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),

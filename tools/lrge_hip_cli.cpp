@@ -63,7 +63,7 @@ int main(int argc, char **argv) {
     bool T_set = false, Q_set = false, filter = false, with_inf = false, precise = false, use_min_ref = false, honour_platform = false;
     float q1 = lrge::LOWER_QUANTILE, q3 = lrge::UPPER_QUANTILE, ratio = 0.2f;
     size_t threads = 1; std::optional<uint64_t> seed; int quiet = 0, verbose = 0, device = 0;
-    bool keep_temp = false, dump_records = false, gpu_inflate = false, gpu_gzip = false, gpu_bzip2 = false, gpu_zstd = false, gpu_xz = false, gpu_cram = false, gpu_ingest = false, gpu_sample = false, gpu_seek = false, gpu_names = false; std::string temp_dir;
+    bool keep_temp = false, dump_records = false, gpu_inflate = false, gpu_gzip = false, gpu_bzip2 = false, gpu_zstd = false, gpu_xz = false, gpu_cram = false, gpu_ingest = false, gpu_sample = false, gpu_seek = false, gpu_stream = false, gpu_names = false; std::string temp_dir;
     auto need = [&](int &i) -> const char * { if (i + 1 >= argc) { fprintf(stderr, "error: missing value for %s\n", argv[i]); exit(2); } return argv[++i]; };
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -94,6 +94,7 @@ int main(int argc, char **argv) {
         else if (a == "--gpu-ingest") { gpu_ingest = true; gpu_gzip = true; }   // FASTA / FASTQ / unaligned BAM / unaligned SAM parsed on --device too: the bases never reach host memory (implies --gpu-gzip)
         else if (a == "--gpu-sample") gpu_sample = true;         // beside --gpu-ingest: a count pass, then only the drawn reads are kept (lrge_hip_reads_census, lrge_hip_reads_open_selected); not implied by --gpu-ingest
         else if (a == "--gpu-seek") gpu_seek = true;             // beside --gpu-sample: the count pass keeps a seek map, the second pass reads and decodes only the runs of plain / BGZF input, the entries of gzip and (with --gpu-bzip2) the blocks of bzip2 that hold drawn reads (lrge_hip_reads_census_map, lrge_hip_reads_open_mapped)
+        else if (a == "--gpu-stream") gpu_stream = true;         // beside --gpu-ingest: the first pass reads plain, BGZF and gzip input in pinned pieces instead of whole (LRGE_GPU_INGEST_STREAM, option INGEST_STREAM_BYTES); not implied by --gpu-ingest
         else if (a == "--gpu-names") gpu_names = true;           // identifier ranks computed on --device (lrge_hip_name_ranks); not implied by --gpu-ingest
         else if (a == "--dump-records") dump_records = true;   // host-only: print "id<TAB>sequence" per record and exit (tests)
         else if (a == "-q" || a == "--quiet") ++quiet; else if (a == "-qq") quiet += 2; else if (a == "-qqq") quiet += 3;
@@ -106,6 +107,7 @@ int main(int argc, char **argv) {
     if (!(q1 >= 0.f && q1 <= 0.5f) || !(q3 >= 0.5f && q3 <= 1.f) || !(ratio >= 0.f && ratio <= 1.f)) { fprintf(stderr, "error: quantile/ratio out of range\n"); return 2; }
     if (gpu_sample && !gpu_ingest) { fprintf(stderr, "error: the argument '--gpu-sample' requires '--gpu-ingest'\n"); return 2; }
     if (gpu_seek && !gpu_sample) { fprintf(stderr, "error: the argument '--gpu-seek' requires '--gpu-sample'\n"); return 2; }
+    if (gpu_stream && !gpu_ingest) { fprintf(stderr, "error: the argument '--gpu-stream' requires '--gpu-ingest'\n"); return 2; }
     if (quiet && verbose) { fprintf(stderr, "error: --quiet cannot be used with --verbose\n"); return 2; }
     const bool info = quiet == 0;
     try {
@@ -121,7 +123,7 @@ int main(int argc, char **argv) {
         // do not prove takes the route of --gpu-ingest alone
         std::unique_ptr<lrge::SampledSource> sampled;
         if (gpu_ingest) {
-            const int fl = LRGE_GPU_INFLATE_BGZF | LRGE_GPU_INFLATE_GZIP | LRGE_GPU_INGEST_BAM | LRGE_GPU_INGEST_SAM | LRGE_GPU_INGEST_WINDOWED | LRGE_GPU_INGEST_WINDOWED_ALN | (gpu_bzip2 ? LRGE_GPU_INFLATE_BZIP2 : 0) | (gpu_zstd ? LRGE_GPU_INFLATE_ZSTD | LRGE_GPU_INGEST_WINDOWED_ZSTD : 0) | (gpu_xz ? LRGE_GPU_INFLATE_XZ : 0) | (gpu_cram ? LRGE_GPU_INGEST_CRAM : 0);
+            const int fl = LRGE_GPU_INFLATE_BGZF | LRGE_GPU_INFLATE_GZIP | LRGE_GPU_INGEST_BAM | LRGE_GPU_INGEST_SAM | LRGE_GPU_INGEST_WINDOWED | LRGE_GPU_INGEST_WINDOWED_ALN | (gpu_bzip2 ? LRGE_GPU_INFLATE_BZIP2 : 0) | (gpu_zstd ? LRGE_GPU_INFLATE_ZSTD | LRGE_GPU_INGEST_WINDOWED_ZSTD : 0) | (gpu_xz ? LRGE_GPU_INFLATE_XZ : 0) | (gpu_cram ? LRGE_GPU_INGEST_CRAM : 0) | (gpu_stream ? LRGE_GPU_INGEST_STREAM : 0);
             if (gpu_sample) {
                 sampled.reset(new lrge::SampledSource{input, fl | LRGE_GPU_INGEST_SELECT_ALN | LRGE_GPU_INGEST_SELECT_SAM | (gpu_cram ? LRGE_GPU_INGEST_SELECT_CRAM : 0), device});       // (unaligned BAM, SAM and -- with --gpu-cram -- CRAM take the sampled route too: DESIGN sections 25 and 27)
                 sampled->seek = gpu_seek;
