@@ -277,6 +277,37 @@ int  lrge_hip_chains(lrge_hip_ctx *ctx, const lrge_hip_index *ix, const lrge_hip
 int  lrge_hip_paf_stats(lrge_hip_ctx *ctx, const lrge_hip_index *ix, const lrge_hip_seqset *queries,
                         int32_t *rep_len, uint64_t *sum_span, uint32_t *n_kept);
 
+/* overlaps.paf written on the device: the lines lrge::paf_lines (include/lrge_hip.hpp) formats on the host from
+   lrge_hip_chains + lrge_hip_paf_stats, each with its line feed, byte for byte -- or nothing.  The statistics run once, the chains job
+   runs with its records kept in HBM (chain_hint: room for that many records; 0: option PAF_CHAINS_FIRST, default 64, times the number
+   of queries; a second run with the exact count when that was too few), every line is measured (dv code, its proof, the length), and
+   the text is written in slices of at most option PAF_PIECE_BYTES (default 64 MiB) that reach `sink` one call per slice, whole lines
+   each, in the run's record order (undefined, as in the reference).  q_names / q_name_off: the identifiers of `queries` back to back,
+   uint64_t[n + 1] offsets; t_names / t_name_off: those of the indexed set.
+   LRGE_ERR_UNPROVEN, nothing delivered: an identifier above option PAF_NAME_MAX_BYTES (default 1024; before any device work), or "dv of
+   N lines not proven on the device" -- the host takes glibc's pow, the device its own, and a chain whose dv lies so close to a rounding
+   boundary of "%.4f" that the two libraries' error bounds straddle it is not decided here: the caller writes lrge::paf_lines.
+   LRGE_ERR_INVALID, before any device work: offsets that do not ascend, no sink.  LRGE_ERR_PAF_WRITE: the sink returned nonzero (what
+   it took before is the caller's to discard).  No chains, or an empty set: LRGE_OK and the sink is never called.  A partitioned index
+   and its refusals: as lrge_hip_chains; the records of ALL parts are held in one device buffer (48 bytes per chain of the whole call, not
+   of one part) and the text is measured and written once, behind the last part -- not after every part -- because only so does an
+   unproven chain of a later part still end the call with nothing delivered.
+   Which model: dv follows lrge_amd/paf.py: chain_dv, whose n_tot and end differences are wide integers (64-bit here); lrge::paf_lines
+   computes them in int.  The two agree on every record the chain kernels can produce (n_seeds + 2 and read lengths below 2^31); on
+   others (tests feed INT32_MAX) the device gives the Python model's bytes.
+   lrge_hip_last_paf_stats: {lines, text bytes, chain runs, slices, pieces handed to the sink, records held on the device, unproven
+   chains, microseconds of measuring + writing + delivering}.
+   BENCH ONLY, no part of what a caller needs (tools/paf_bench.py is their one user; they may change with it):
+   lrge_hip_last_paf_phases, the host clock of the call in microseconds, {statistics, chains, measure, write (scan + kernel), waiting
+   for copies, inside the sink, total, setup (device text blocks and pinned pieces taken)}; and option PAF_SERIAL, with which every
+   slice is written, copied and delivered before the next is begun, so that the phases add up instead of overlapping (same bytes,
+   same order, slower). */
+int  lrge_hip_paf_text(lrge_hip_ctx *ctx, const lrge_hip_index *ix, const lrge_hip_seqset *queries, int dual,
+                       const char *q_names, const uint64_t *q_name_off, const char *t_names, const uint64_t *t_name_off,
+                       uint64_t chain_hint, int (*sink)(void *user, const void *bytes, uint64_t n), void *user);
+int  lrge_hip_last_paf_stats(const lrge_hip_ctx *ctx, uint64_t out[8]);
+int  lrge_hip_last_paf_phases(const lrge_hip_ctx *ctx, uint64_t out[8]);
+
 /*
  * Multi-GPU: one context per GPU, every rank owns a range of the streamed reads end to end.  A
  * communicator carries the two exchanges of the path -- a SUM all-reduce of small integer vectors (the global

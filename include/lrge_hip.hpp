@@ -368,6 +368,48 @@ inline std::vector<std::string> paf_lines(lrge_hip_ctx *ctx, const lrge_hip_inde
                                           const std::vector<const std::string *> &qn, const std::vector<uint32_t> &qlen,
                                           const std::vector<const std::string *> &tn, const std::vector<uint32_t> &tlen);
 
+// overlaps.paf through a sink of text (lrge_hip_paf_text): the device formats the lines and hands them over in
+// pieces of whole lines; when it cannot prove them (LRGE_ERR_UNPROVEN: a dv at a rounding boundary, an identifier above
+// PAF_NAME_MAX_BYTES) the host lines of paf_lines go through the same sink instead, and nothing of the device's had been delivered.
+// `hint`: room for that many chain records (0: the library's default).  `note` (may be empty) hears which path ran.  A sink that
+// returns false ends the call with the reference's PafWriteError.
+using PafTextSink = std::function<bool(const char *, size_t)>;
+inline void paf_text(lrge_hip_ctx *ctx, const lrge_hip_index *ix, const lrge_hip_seqset *qs, int dual, const std::vector<const std::string *> &qn,
+                     const std::vector<uint32_t> &qlen, const std::vector<const std::string *> &tn, const std::vector<uint32_t> &tlen, uint64_t hint,
+                     const PafTextSink &sink, const std::function<void(bool)> &note) {
+    auto table = [](const std::vector<const std::string *> &names, std::string &blob, std::vector<uint64_t> &off) {
+        off.assign(names.size() + 1, 0);
+        for (size_t i = 0; i < names.size(); ++i) off[i + 1] = off[i] + names[i]->size();
+        blob.reserve(off.back());
+        for (const std::string *n : names) blob += *n;
+    };
+    std::string qb, tb; std::vector<uint64_t> qo, to;
+    table(qn, qb, qo);
+    const bool same = &tn == &qn;
+    if (!same) table(tn, tb, to);
+    struct Fwd { const PafTextSink *sink; } fwd{&sink};
+    auto cb = [](void *user, const void *bytes, uint64_t n) -> int { return (*static_cast<Fwd *>(user)->sink)(static_cast<const char *>(bytes), (size_t)n) ? 0 : 1; };
+    const int rc = lrge_hip_paf_text(ctx, ix, qs, dual, qb.data(), qo.data(), same ? qb.data() : tb.data(), same ? qo.data() : to.data(), hint, cb, &fwd);
+    if (rc == LRGE_ERR_UNPROVEN) {
+        if (note) note(false);
+        std::string piece;
+        for (const std::string &l : paf_lines(ctx, ix, qs, dual, qn, qlen, tn, tlen)) {
+            piece += l; piece += '\n';
+            if (piece.size() >= (1u << 20)) { if (!sink(piece.data(), piece.size())) throw LrgeError(LRGE_ERR_PAF_WRITE, "Error writing PAF file: the sink refused the lines"); piece.clear(); }
+        }
+        if (!piece.empty() && !sink(piece.data(), piece.size())) throw LrgeError(LRGE_ERR_PAF_WRITE, "Error writing PAF file: the sink refused the lines");
+        return;
+    }
+    if (rc) throw LrgeError(rc, lrge_hip_last_error(ctx));
+    if (note) note(true);
+}
+// what the strategies pass as `hint`: the counts they already have, and a margin (a chain per counted overlap, some pairs chain twice)
+inline uint64_t paf_chain_hint(const std::vector<uint32_t> &counts) {
+    uint64_t s = 0;
+    for (uint32_t c : counts) s += c;
+    return s + s / 4 + 1024;
+}
+
 // ------------------------------------------------------------------------------------------
 // two-set strategy
 // ------------------------------------------------------------------------------------------
@@ -388,6 +430,8 @@ public:
     int device = 0;
     std::vector<std::string> warnings;
     std::vector<std::string> *paf_sink = nullptr;   // when set, receives the lines of overlaps.paf (the reference always writes it)
+    PafTextSink paf_text_sink;                      // when set, overlaps.paf arrives as text formatted on the device (paf_text above); paf_sink is not filled
+    std::function<void(bool)> paf_text_note;        // hears whether the device (true) or the host formatted it
     bool device_name_ranks = false;                 // name ranks by lrge_hip_name_ranks (opt-in; the host sort when the device hands them back)
     std::function<void(bool)> name_ranks_note;      // hears whether the device (true) or the host computed them, when device_name_ranks is set
 
@@ -455,13 +499,15 @@ public:
             ctx.check(lrge_hip_seqset_presketch(ctx.h, T.h, preset));   // streamed set: sketched beside the index build
             detail::Index ix(ctx, Q, preset);
             ctx.check(lrge_hip_overlap_inverse(ctx.h, ix.h, T.h, &p, counts.data()));
-            if (paf_sink) *paf_sink = paf_lines(ctx.h, ix.h, T.h, 1, tn, T.lens, qn, Q.lens);
+            if (paf_text_sink) paf_text(ctx.h, ix.h, T.h, 1, tn, T.lens, qn, Q.lens, paf_chain_hint(counts), paf_text_sink, paf_text_note);
+            else if (paf_sink) *paf_sink = paf_lines(ctx.h, ix.h, T.h, 1, tn, T.lens, qn, Q.lens);
             for (uint32_t c : counts) no_mapping += c == 0;                       // twoset.rs:545-569
         } else {
             ctx.check(lrge_hip_seqset_presketch(ctx.h, Q.h, preset));
             detail::Index ix(ctx, T, preset);
             ctx.check(lrge_hip_overlap_twoset(ctx.h, ix.h, Q.h, &p, counts.data(), has.data()));
-            if (paf_sink) *paf_sink = paf_lines(ctx.h, ix.h, Q.h, 1, qn, Q.lens, tn, T.lens);
+            if (paf_text_sink) paf_text(ctx.h, ix.h, Q.h, 1, qn, Q.lens, tn, T.lens, paf_chain_hint(counts), paf_text_sink, paf_text_note);
+            else if (paf_sink) *paf_sink = paf_lines(ctx.h, ix.h, Q.h, 1, qn, Q.lens, tn, T.lens);
             for (uint32_t h : has) no_mapping += h == 0;                          // twoset.rs:303-309
         }
         std::vector<float> est(counts.size());
@@ -479,8 +525,10 @@ class Builder {   // twoset/builder.rs:22-185
     Platform platform_ = Platform::Nanopore;
     int device_ = 0;
     bool device_name_ranks_ = false;
+    PafTextSink paf_text_sink_;
 public:
     Builder &device_name_ranks(bool f) { device_name_ranks_ = f; return *this; }
+    Builder &paf_text_sink(PafTextSink f) { paf_text_sink_ = std::move(f); return *this; }
     Builder &target_num_reads(size_t n) { t_ = n; return *this; }
     Builder &query_num_reads(size_t n) { q_ = n; return *this; }
     Builder &remove_internal(bool f, float ratio) { remove_internal_ = f; if (f) ratio_ = ratio; return *this; }
@@ -496,6 +544,7 @@ public:
         s.target_num_reads = t_; s.query_num_reads = q_; s.remove_internal = remove_internal_; s.max_overhang_ratio = ratio_;
         s.use_min_ref = use_min_ref_; s.threads = threads_; s.seed = seed_; s.platform = platform_; s.device = device_;
         s.device_name_ranks = device_name_ranks_;
+        s.paf_text_sink = paf_text_sink_;
         return s;
     }
 };
@@ -519,6 +568,8 @@ public:
     int device = 0;
     std::vector<std::string> warnings;
     std::vector<std::string> *paf_sink = nullptr;
+    PafTextSink paf_text_sink;                      // as TwoSetStrategy::paf_text_sink
+    std::function<void(bool)> paf_text_note;
     bool device_name_ranks = false;                 // as TwoSetStrategy::device_name_ranks
     std::function<void(bool)> name_ranks_note;
 
@@ -566,7 +617,8 @@ public:
         lrge_hip_params p{remove_internal ? 1 : 0, max_overhang_ratio};
         std::vector<uint32_t> counts(R.lens.size());
         ctx.check(lrge_hip_overlap_ava(ctx.h, ix.h, R.h, &p, counts.data()));
-        if (paf_sink) *paf_sink = paf_lines(ctx.h, ix.h, R.h, 0, rn, R.lens, rn, R.lens);
+        if (paf_text_sink) paf_text(ctx.h, ix.h, R.h, 0, rn, R.lens, rn, R.lens, paf_chain_hint(counts), paf_text_sink, paf_text_note);
+        else if (paf_sink) *paf_sink = paf_lines(ctx.h, ix.h, R.h, 0, rn, R.lens, rn, R.lens);
         const size_t n_target = num_reads - 1;                                   // ava.rs:339-346
         const float avg = (float)num_bases / (float)n_target;
         std::vector<float> est(counts.size());
@@ -585,8 +637,10 @@ class Builder {   // ava/builder.rs:19-153
     Platform platform_ = Platform::Nanopore;
     int device_ = 0;
     bool device_name_ranks_ = false;
+    PafTextSink paf_text_sink_;
 public:
     Builder &device_name_ranks(bool f) { device_name_ranks_ = f; return *this; }
+    Builder &paf_text_sink(PafTextSink f) { paf_text_sink_ = std::move(f); return *this; }
     Builder &num_reads(size_t n) { n_ = n; return *this; }
     Builder &remove_internal(bool f, float ratio) { remove_internal_ = f; if (f) ratio_ = ratio; return *this; }
     Builder &threads(size_t n) { threads_ = n; return *this; }
@@ -600,24 +654,16 @@ public:
         s.num_reads = n_; s.remove_internal = remove_internal_; s.max_overhang_ratio = ratio_; s.threads = threads_;
         s.seed = seed_; s.platform = platform_; s.device = device_;
         s.device_name_ranks = device_name_ranks_;
+        s.paf_text_sink = paf_text_sink_;
         return s;
     }
 };
 }  // namespace ava
 
-// overlaps.paf (twoset.rs:246-250,289-293; mapping.rs:81-177): one line per chain, unordered like the reference
-inline std::vector<std::string> paf_lines(lrge_hip_ctx *ctx, const lrge_hip_index *ix, const lrge_hip_seqset *qs, int dual,
-                                          const std::vector<const std::string *> &qn, const std::vector<uint32_t> &qlen,
-                                          const std::vector<const std::string *> &tn, const std::vector<uint32_t> &tlen) {
-    uint64_t n = 0;
-    int rc = lrge_hip_chains(ctx, ix, qs, dual, nullptr, 0, &n);
-    if (rc) throw LrgeError(rc, lrge_hip_last_error(ctx));
-    std::vector<lrge_hip_chain> ch(n ? n : 1);
-    rc = lrge_hip_chains(ctx, ix, qs, dual, ch.data(), n, &n);
-    if (rc) throw LrgeError(rc, lrge_hip_last_error(ctx));
-    std::vector<int32_t> rl(qn.size() + 1); std::vector<uint64_t> ss(qn.size() + 1); std::vector<uint32_t> nk(qn.size() + 1);
-    rc = lrge_hip_paf_stats(ctx, ix, qs, rl.data(), ss.data(), nk.data());
-    if (rc) throw LrgeError(rc, lrge_hip_last_error(ctx));
+// the lines of overlaps.paf from n chain records and the per-query statistics (mapping.rs:81-177), no line feed
+inline std::vector<std::string> paf_format_lines(const lrge_hip_chain *ch, uint64_t n, const int32_t *rl, const uint64_t *ss, const uint32_t *nk,
+                                                 const std::vector<const std::string *> &qn, const std::vector<uint32_t> &qlen,
+                                                 const std::vector<const std::string *> &tn, const std::vector<uint32_t> &tlen) {
     std::vector<std::string> out;
     char buf[512];
     for (uint64_t i = 0; i < n; ++i) {
@@ -640,6 +686,22 @@ inline std::vector<std::string> paf_lines(lrge_hip_ctx *ctx, const lrge_hip_inde
         out.push_back(line + buf);
     }
     return out;
+}
+
+// overlaps.paf (twoset.rs:246-250,289-293; mapping.rs:81-177): one line per chain, unordered like the reference
+inline std::vector<std::string> paf_lines(lrge_hip_ctx *ctx, const lrge_hip_index *ix, const lrge_hip_seqset *qs, int dual,
+                                          const std::vector<const std::string *> &qn, const std::vector<uint32_t> &qlen,
+                                          const std::vector<const std::string *> &tn, const std::vector<uint32_t> &tlen) {
+    uint64_t n = 0;
+    int rc = lrge_hip_chains(ctx, ix, qs, dual, nullptr, 0, &n);
+    if (rc) throw LrgeError(rc, lrge_hip_last_error(ctx));
+    std::vector<lrge_hip_chain> ch(n ? n : 1);
+    rc = lrge_hip_chains(ctx, ix, qs, dual, ch.data(), n, &n);
+    if (rc) throw LrgeError(rc, lrge_hip_last_error(ctx));
+    std::vector<int32_t> rl(qn.size() + 1); std::vector<uint64_t> ss(qn.size() + 1); std::vector<uint32_t> nk(qn.size() + 1);
+    rc = lrge_hip_paf_stats(ctx, ix, qs, rl.data(), ss.data(), nk.data());
+    if (rc) throw LrgeError(rc, lrge_hip_last_error(ctx));
+    return paf_format_lines(ch.data(), n, rl.data(), ss.data(), nk.data(), qn, qlen, tn, tlen);
 }
 
 // lrge/src/utils.rs:19-49

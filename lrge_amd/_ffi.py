@@ -44,7 +44,10 @@ CRAM_STAT_NAMES = ["containers", "slices", "records", "ba_raw", "ba_rans4x8", "b
                    "rounds", "walk_us", "decode_us"]   # lrge_hip_cram_stats
 BAM_STAT_NAMES = ["segments", "empty_segments", "speculative_starts", "rejected_starts", "repair_rounds", "rewalked_segments"]   # lrge_hip_bam_stats
 
-# int (*sink)(void *user, const void *bytes, uint64_t n) of lrge_hip_gzip_inflate, lrge_hip_bzip2_inflate, lrge_hip_zstd_inflate and lrge_hip_xz_inflate
+PAF_STAT_NAMES = ["lines", "bytes", "chain_runs", "slices", "pieces", "records", "unproven", "format_us"]   # lrge_hip_last_paf_stats
+PAF_PHASE_NAMES = ["stats_us", "chains_us", "measure_us", "write_us", "copy_wait_us", "sink_us", "total_us", "setup_us"]   # lrge_hip_last_paf_phases
+
+# int (*sink)(void *user, const void *bytes, uint64_t n) of lrge_hip_paf_text, lrge_hip_gzip_inflate, lrge_hip_bzip2_inflate, lrge_hip_zstd_inflate and lrge_hip_xz_inflate
 GZIP_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)
 
 EXPORTS = [
@@ -66,7 +69,7 @@ EXPORTS = [
     "lrge_hip_comm_create_local", "lrge_hip_comm_create_host", "lrge_hip_comm_destroy", "lrge_hip_comm_abort", "lrge_hip_comm_rank", "lrge_hip_comm_world",
     "lrge_hip_comm_allreduce_u32", "lrge_hip_comm_allgather", "lrge_hip_index_stats",
     "lrge_hip_overlap_twoset", "lrge_hip_overlap_twoset_tsharded", "lrge_hip_overlap_inverse", "lrge_hip_overlap_ava", "lrge_hip_chains",
-    "lrge_hip_estimates", "lrge_hip_median", "lrge_hip_paf_stats",
+    "lrge_hip_estimates", "lrge_hip_median", "lrge_hip_paf_stats", "lrge_hip_paf_text", "lrge_hip_last_paf_stats", "lrge_hip_last_paf_phases",
     "lrge_hip_unique_random_set", "lrge_hip_chacha_block",
     "lrge_hip_sketch_dump", "lrge_hip_index_dump", "lrge_hip_anchors_dump",
     "lrge_hip_set_timer_level", "lrge_hip_last_timings", "lrge_hip_last_counters", "lrge_hip_version",
@@ -209,6 +212,9 @@ def lib():
     L.lrge_hip_overlap_ava.argtypes = [vp, vp, vp, C.POINTER(Params), vp]
     L.lrge_hip_chains.argtypes = [vp, vp, vp, C.c_int, vp, C.c_uint64, C.POINTER(C.c_uint64)]
     L.lrge_hip_paf_stats.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.lrge_hip_paf_text.argtypes = [vp, vp, vp, C.c_int, C.c_char_p, vp, C.c_char_p, vp, C.c_uint64, GZIP_SINK, vp]
+    L.lrge_hip_last_paf_stats.argtypes = [vp, C.POINTER(C.c_uint64 * 8)]
+    L.lrge_hip_last_paf_phases.argtypes = [vp, C.POINTER(C.c_uint64 * 8)]
     L.lrge_hip_estimates.argtypes = [vp, vp, vp, C.c_uint32, C.c_float, C.c_uint64, C.c_uint32, vp]
     L.lrge_hip_median.argtypes = [vp, C.c_uint64, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float,
                                   C.POINTER(C.c_float * 3), C.POINTER(C.c_int * 3)]

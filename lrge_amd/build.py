@@ -50,6 +50,7 @@ NAMES_LSD_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_names_lsd_twin.so")
 ZSTD_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_zstd_twin.so")
 XZ_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_xz_twin.so")
 CRAM_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_cram_twin.so")
+PAF_TWIN_PATH = os.path.join(LIB_DIR, "liblrge_paf_twin.so")
 
 
 def _build_twin(out, main, force, libs=()):
@@ -63,11 +64,12 @@ def _build_twin(out, main, force, libs=()):
 
 
 def build_twin(force=False):
-    """The host twins, all eleven: of k_inflate (csrc/inflate_twin.cpp, the same bit-level core), and of the speculative gzip
+    """The host twins, all twelve: of k_inflate (csrc/inflate_twin.cpp, the same bit-level core), and of the speculative gzip
     decode (build_gzip_twin), of the FASTA / FASTQ record scan (build_fastx_twin), of the BAM record scan (build_bam_twin), of
     the SAM record scan (build_sam_twin), of the identifier ranking by refinement (build_names_twin) and by fixed LSD passes (build_names_lsd_twin)
-    and of the bzip2 decode (build_bzip2_twin), the Zstandard decode (build_zstd_twin) and the xz decode (build_xz_twin), and of the CRAM base-block ingest (build_cram_twin)."""
+    and of the bzip2 decode (build_bzip2_twin), the Zstandard decode (build_zstd_twin) and the xz decode (build_xz_twin), and of the CRAM base-block ingest (build_cram_twin), and of the PAF writer (build_paf_twin)."""
     build_cram_twin(force)
+    build_paf_twin(force)
     build_gzip_twin(force)
     build_fastx_twin(force)
     build_bam_twin(force)
@@ -132,6 +134,12 @@ def build_cram_twin(force=False):
     return _build_twin(CRAM_TWIN_PATH, "cram_twin.cpp", force, libs=("-lz", "-ldl"))
 
 
+def build_paf_twin(force=False):
+    """The host twin of the device PAF writer (csrc/paf_twin.cpp over csrc/paf_core.h): the measure, scan and
+    write steps as loops, the dv code of a float and the proof of a p."""
+    return _build_twin(PAF_TWIN_PATH, "paf_twin.cpp", force)
+
+
 PRIMS_CHECK_PATH = os.path.join(LIB_DIR, "libprims_check.so")
 
 
@@ -177,6 +185,22 @@ def build_cli(force=False):
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-o", CLI_PATH, src, "-L" + LIB_DIR, "-llrge_hip", "-lz", "-ldl",
                            "-Wl,-rpath,$ORIGIN"])
     return CLI_PATH
+
+
+PAF_HOST_BENCH_PATH = os.path.join(LIB_DIR, "libpaf_host_bench.so")
+
+
+def build_paf_host_bench(force=False):
+    """The host path of overlaps.paf with a clock around each step (tools/paf_host_bench.cpp over include/lrge_hip.hpp), for
+    tools/paf_bench.py; g++, links liblrge_hip.so."""
+    src = os.path.join(os.path.dirname(_HERE), "tools", "paf_host_bench.cpp")
+    inc = os.path.join(os.path.dirname(_HERE), "include")
+    deps = [src, LIB_PATH] + [os.path.join(inc, h) for h in ("lrge_hip.hpp", "lrge_hip.h", "lrge_rand.hpp")]
+    if not force and os.path.exists(PAF_HOST_BENCH_PATH) and os.path.getmtime(PAF_HOST_BENCH_PATH) >= _newest(deps):
+        return PAF_HOST_BENCH_PATH
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-fPIC", "-shared", "-o", PAF_HOST_BENCH_PATH, src, "-L" + LIB_DIR, "-llrge_hip",
+                           "-Wl,-rpath,$ORIGIN"])
+    return PAF_HOST_BENCH_PATH
 
 
 if __name__ == "__main__":

@@ -49,6 +49,9 @@ struct OverlapJob {
     u32 *counts = nullptr;          // size: nq (twoset) or n_indexed (inverse / ava)
     u32 *has_map = nullptr;
     lrge_hip_chain *chains = nullptr; u64 chain_cap = 0; u64 *n_chains = nullptr;
+    // chain records kept on the device (lrge_hip_paf_text): the caller's buffer of chain_cap records and its counter, used in place of
+    // the run's scratch.  The counter is the caller's to reset: runs over the parts of an index append.  finish reads back the count only.
+    lrge_hip_chain *d_chain_buf = nullptr; unsigned long long *d_chain_cnt = nullptr;
     // anchors of one query instead of chaining
     bool dump_anchors = false; u32 dump_query = 0; u64 *ax = nullptr, *ay = nullptr; u64 acap = 0; u64 *an = nullptr;
     // per-query PAF statistics instead of chaining
@@ -163,7 +166,9 @@ int OverlapRun::prepare() {
     if (!d_counts || !d_hasmap) return LRGE_ERR_DEVICE;
     HIPCHK(ctx, hipMemsetAsync(d_counts, 0, ((size_t)n_out + 1) * 4, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(d_hasmap, 0, ((size_t)nq + 1) * 4, ctx->stream));
-    if (job.n_chains) {
+    if (job.n_chains && job.d_chain_buf && job.d_chain_cnt) {
+        d_nchains = job.d_chain_cnt; d_chains = job.d_chain_buf;
+    } else if (job.n_chains) {
         d_nchains = (unsigned long long *)sc.get<u64>(1);
         d_chains = sc.get<lrge_hip_chain>(job.chain_cap ? job.chain_cap : 1);
         if (!d_nchains || !d_chains) return LRGE_ERR_DEVICE;

@@ -203,6 +203,8 @@ struct lrge_hip_ctx {
     int timer_level = 1;                     // see StageTimer
     u64 shard_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // last sharded index build (lrge_hip_last_shard_stats)
     u64 stream_stats[4] = {0, 0, 0, 0};      // the last ingest call that took a path (lrge_hip_last_stream_stats): read calls, file bytes read, peak pinned bytes held for file bytes, 1: it streamed
+    u64 paf_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // last lrge_hip_paf_text (lrge_hip_last_paf_stats)
+    u64 paf_phase_us[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // its host clock by phase (lrge_hip_last_paf_phases)
     bool qshard_fresh = false;               // lrge_hip_seqset_presketch_sharded has just left its exchange volumes in shard_stats: the target-sharded build that follows keeps them
     u64 part_hint_total = 0, part_hint_bases = 0; int part_hint_preset = -1;   // the part size a build of this job had to fall back to (lrge_hip_index_build)
     double kept_ratio = 0.5; bool kept_seen = false;   // survivors per seed hit of the dead-pair filter in this context's recent batches (the batch planner's memory estimate)

@@ -35,6 +35,7 @@
 #include "k_fastx.h"
 #include "k_bam.h"
 #include "k_sam.h"
+#include "k_paf.h"
 #include "../../include/lrge_rand.hpp"
 #include "../../include/lrge_io.hpp"
 
@@ -237,3 +238,4 @@ extern "C" int lrge_hip_last_counters(const lrge_hip_ctx *ctx, uint64_t c[LRGE_C
 #include "host_xz.inl"
 #include "host_fastx.inl"
 #include "host_names.inl"
+#include "host_paf.inl"

@@ -247,6 +247,16 @@ class Context:
         self._lib.lrge_hip_last_counters(self.h, C.byref(a))
         return dict(zip(_ffi.C_NAMES, [int(x) for x in a]))
 
+    def last_paf_stats(self):
+        """The last Index.paf_text / paf_text_to of this context (lrge_hip_last_paf_stats): lines, bytes, chain_runs, slices, pieces,
+        records (held on the device), unproven, format_us; and the host clock of its phases (lrge_hip_last_paf_phases)."""
+        a, b = (C.c_uint64 * 8)(), (C.c_uint64 * 8)()
+        self._check(self._lib.lrge_hip_last_paf_stats(self.h, C.byref(a)))
+        self._check(self._lib.lrge_hip_last_paf_phases(self.h, C.byref(b)))
+        d = dict(zip(_ffi.PAF_STAT_NAMES, [int(x) for x in a]))
+        d.update(zip(_ffi.PAF_PHASE_NAMES, [int(x) for x in b]))
+        return d
+
     def upload(self, bases, offsets, ranks=None, wait=True):
         """Read set -> 2-bit packed in HBM.  `bases`: numpy uint8 (pageable or pinned host memory, see host_alloc) or an
         int device pointer to ASCII already resident in HBM.  wait=False queues the transfer + pack on the copy stream
@@ -676,6 +686,45 @@ class Index:
         self.ctx._check(self.ctx._lib.lrge_hip_paf_stats(self.ctx.h, self.h, queries.h, rl.ctypes.data, ss.ctypes.data,
                                                          nk.ctypes.data))
         return rl[:queries.n], ss[:queries.n], nk[:queries.n]
+
+    def paf_text_to(self, write, queries, q_names, t_names, dual=True, chain_hint=0):
+        """overlaps.paf formatted on the device (lrge_hip_paf_text): `write(bytes)` is called once per slice with
+        whole lines -- those of paf.paf_lines over chains + paf_stats, each with its line feed, in the run's record order.  A falsy
+        return of `write` other than None, or an exception in it, stops the call (ERR_PAF_WRITE; the exception is raised again).
+        UnprovenInput, nothing written: an identifier above option PAF_NAME_MAX_BYTES, or a dv the device cannot prove -- take
+        paf.paf_lines.  q_names / t_names: the identifiers of `queries` and of the indexed set (bytes or str)."""
+        def blob(names):
+            names = [n if isinstance(n, bytes) else n.encode() for n in names]
+            off = np.zeros(len(names) + 1, dtype=np.uint64)
+            if names:
+                np.cumsum(np.fromiter(map(len, names), dtype=np.uint64, count=len(names)), out=off[1:])
+            return b"".join(names), off
+        if len(q_names) != queries.n or len(t_names) != self.targets.n:
+            raise ValueError("paf_text: %d / %d names for %d queries and %d indexed reads" % (len(q_names), len(t_names), queries.n, self.targets.n))
+        qb, qo = blob(q_names)
+        tb, to = (qb, qo) if t_names is q_names else blob(t_names)
+        failed = []
+
+        def sink(_user, p, n):
+            try:
+                r = write(C.string_at(p, n))
+            except BaseException as e:      # (an exception must not unwind through the C frames)
+                failed.append(e)
+                return 1
+            return 0 if r is None or r else 1
+        cb = _ffi.GZIP_SINK(sink)
+        rc = self.ctx._lib.lrge_hip_paf_text(self.ctx.h, self.h, queries.h, int(bool(dual)), qb, qo.ctypes.data, tb, to.ctypes.data, int(chain_hint), cb, None)
+        if failed:
+            raise failed[0]
+        if rc == _ffi.ERR_UNPROVEN:
+            raise UnprovenInput(rc, self.ctx._lib.lrge_hip_last_error(self.ctx.h).decode())
+        self.ctx._check(rc)
+
+    def paf_text(self, queries, q_names, t_names, dual=True, chain_hint=0):
+        """paf_text_to collected: the whole of overlaps.paf as bytes."""
+        parts = []
+        self.paf_text_to(parts.append, queries, q_names, t_names, dual, chain_hint)
+        return b"".join(parts)
 
     def anchors(self, queries, q, dual=True):
         n = C.c_uint64()

@@ -63,7 +63,7 @@ int main(int argc, char **argv) {
     bool T_set = false, Q_set = false, filter = false, with_inf = false, precise = false, use_min_ref = false, honour_platform = false;
     float q1 = lrge::LOWER_QUANTILE, q3 = lrge::UPPER_QUANTILE, ratio = 0.2f;
     size_t threads = 1; std::optional<uint64_t> seed; int quiet = 0, verbose = 0, device = 0;
-    bool keep_temp = false, dump_records = false, gpu_inflate = false, gpu_gzip = false, gpu_bzip2 = false, gpu_zstd = false, gpu_xz = false, gpu_cram = false, gpu_ingest = false, gpu_sample = false, gpu_seek = false, gpu_stream = false, gpu_names = false; std::string temp_dir;
+    bool keep_temp = false, dump_records = false, gpu_inflate = false, gpu_gzip = false, gpu_bzip2 = false, gpu_zstd = false, gpu_xz = false, gpu_cram = false, gpu_ingest = false, gpu_sample = false, gpu_seek = false, gpu_stream = false, gpu_names = false, gpu_paf = false; std::string temp_dir;
     auto need = [&](int &i) -> const char * { if (i + 1 >= argc) { fprintf(stderr, "error: missing value for %s\n", argv[i]); exit(2); } return argv[++i]; };
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -96,6 +96,7 @@ int main(int argc, char **argv) {
         else if (a == "--gpu-seek") gpu_seek = true;             // beside --gpu-sample: the count pass keeps a seek map, the second pass reads and decodes only the runs of plain / BGZF input, the entries of gzip and (with --gpu-bzip2) the blocks of bzip2 that hold drawn reads (lrge_hip_reads_census_map, lrge_hip_reads_open_mapped)
         else if (a == "--gpu-stream") gpu_stream = true;         // beside --gpu-ingest: the first pass reads plain, BGZF and gzip input in pinned pieces instead of whole (LRGE_GPU_INGEST_STREAM, option INGEST_STREAM_BYTES); not implied by --gpu-ingest
         else if (a == "--gpu-names") gpu_names = true;           // identifier ranks computed on --device (lrge_hip_name_ranks); not implied by --gpu-ingest
+        else if (a == "--gpu-paf") gpu_paf = true;               // beside -C: overlaps.paf is formatted on --device and written piece by piece (lrge_hip_paf_text); without -C it has no effect; not implied by --gpu-ingest
         else if (a == "--dump-records") dump_records = true;   // host-only: print "id<TAB>sequence" per record and exit (tests)
         else if (a == "-q" || a == "--quiet") ++quiet; else if (a == "-qq") quiet += 2; else if (a == "-qqq") quiet += 3;
         else if (a == "-v" || a == "--verbose") ++verbose; else if (a == "-vv") verbose += 2;
@@ -156,10 +157,21 @@ int main(int argc, char **argv) {
             st = &ts;
         }
         std::vector<std::string> paf;
-        if (keep_temp) { ts.paf_sink = &paf; as.paf_sink = &paf; }   // -C keeps overlaps.paf (main.rs:37-48, twoset.rs:246-250)
+        const std::string dir = temp_dir.empty() ? "." : temp_dir;
+        std::ofstream paf_out;
+        if (keep_temp && gpu_paf) {      // the pieces go straight to the file as the device hands them over
+            paf_out.open(dir + "/overlaps.paf", std::ios::binary);
+            if (!paf_out) { fprintf(stderr, "Error: Failed to write PAF record\n"); return 1; }
+            const lrge::PafTextSink to_file = [&](const char *p, size_t n) { paf_out.write(p, (std::streamsize)n); return (bool)paf_out; };
+            const std::function<void(bool)> paf_note = [&](bool on_device) { if (info) fprintf(stderr, "[INFO] gpu-paf: %s\n", on_device ? "device" : "host"); };
+            ts.paf_text_sink = to_file; as.paf_text_sink = to_file; ts.paf_text_note = paf_note; as.paf_text_note = paf_note;
+        } else if (keep_temp) { ts.paf_sink = &paf; as.paf_sink = &paf; }   // -C keeps overlaps.paf (main.rs:37-48, twoset.rs:246-250)
         lrge::EstimateResult r = st->estimate(!with_inf, q1, q3);
-        if (keep_temp) {
-            const std::string dir = temp_dir.empty() ? "." : temp_dir;
+        if (keep_temp && gpu_paf) {
+            paf_out.close();
+            if (!paf_out) { fprintf(stderr, "Error: Failed to generate estimate\n\nCaused by:\n    Error writing PAF file: closing %s/overlaps.paf failed\n", dir.c_str()); return 1; }
+            if (info) fprintf(stderr, "[INFO] Created temporary directory at %s\n", dir.c_str());
+        } else if (keep_temp) {
             std::ofstream pf(dir + "/overlaps.paf");
             if (!pf) { fprintf(stderr, "Error: Failed to write PAF record\n"); return 1; }
             for (auto &l : paf) pf << l << "\n";
